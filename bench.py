@@ -2,17 +2,23 @@
 """bench.py -- env-steps/sec of the population-rollout fitness evaluation (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload serl50|serl10|mixed] [--pop MEMBERS_PER_GPU | --total-pop MEMBERS]
+                  [--dump-outputs DIR] [--full]
   (N > 1: one rank per GPU over RCCL -- launched by torch.distributed.run, or, when started as a plain
-   `python bench.py --gpus N`, bench.py re-executes itself under torch.distributed.run; fewer than N visible GPUs ->
-   one JSON line {"skipped": ...} and exit code 0)
+   `python bench.py --gpus N`, bench.py starts itself under torch.distributed.run in a child process; fewer than N visible
+   GPUs -> one JSON line {"skipped": ...} and exit code 0)
 
 A "step" is one population evaluation: pop members x num_evals episodes x 8 001 env steps of the
 PH-LAB attitude-tracking task (t_max = 80 s), weights and reference tables already resident in HBM.
+A plain run sets up, runs W warm-up and K timed steps, writes the last timed step's results if --dump-outputs is given
+(DIR/<name>.npy, f64: fitness, return, smoothness, length_t, length_steps, cost_steps [num_evals, members], pop_fitness
+[members], champion [1]; the inputs are seeded, so two builds can be compared output for output) and prints the line.
+--full adds everything else the line can carry: the CPU baseline and the parity check against the CPU restatement
+(N = 1), the evaluation with host-resident inputs, the N-GPU partition check and the strong-scaling legs (N > 1).
 Default (weak scaling): every GPU evaluates its own block of `pop` members (shipped actors, tiled with seeded noise
 beyond the shipped ones) and the per-member result rows are all-gathered (RCCL).  Prints ONE JSON line on rank 0.
 --total-pop M (strong scaling, BASELINE configs 4 / 5): ONE population of M members sharded over the N ranks in contiguous
 member blocks (serl_amd.distributed.member_block, the partition of base/core/agent.py:234-256's loop), "scaling": "strong";
-with --gpus 1 all M x num_evals episodes run on one GPU and are checked against the CPU restatement.
+with --gpus 1 all M x num_evals episodes run on one GPU (and, with --full, are checked against the CPU restatement).
 
 Workloads (BASELINE.json configs): serl50 = config 3 (the metric's configuration, default: pop=50, actor 7-32x4-3;
 --pop 64 is one GPU's share of config 4, pop=512 over 8), serl10 = config 2 (pop=10, actor 7-72x4-3), mixed = one
@@ -49,6 +55,26 @@ def make_population(pop, rank, seed=7, tag='serl50'):
     for (off, n), z in zip(spec.genome_segments(), noise):
         w[:, off:off + n] += z * fresh[:, None]
     return w
+
+
+ROW_NAMES = ('fitness', 'return', 'smoothness', 'length_t', 'length_steps', 'cost_steps')     # serl_amd.distributed.ROW, in order
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, rows, champion):
+    """--dump-outputs: the gathered result rows of one population evaluation (f64 [num_evals, members, ROW]) as one f64 array per
+    column, the population fitness and the champion.  Beyond DUMP_BYTES, a fixed seeded sample of the members (member_index.npy)."""
+    rows = rows.detach().cpu().numpy().astype(np.float64)
+    members = rows.shape[1]
+    out = {'pop_fitness': rows[..., 0].mean(0), 'champion': np.array([champion], np.float64)}
+    per_member = (rows.shape[0] * rows.shape[2] + 2) * 8            # its rows, its pop_fitness and (sampled) its index
+    if members * per_member > DUMP_BYTES - 4096:                    # (4 KiB for the .npy headers)
+        keep = np.sort(np.random.default_rng(0).choice(members, (DUMP_BYTES - 4096) // per_member, replace=False))
+        rows, out['pop_fitness'], out['member_index'] = rows[:, keep], out['pop_fitness'][keep], keep.astype(np.float64)
+    out.update({n: rows[..., i] for i, n in enumerate(ROW_NAMES)})
+    os.makedirs(out_dir, exist_ok=True)
+    for n, v in out.items():
+        np.save(os.path.join(out_dir, n + '.npy'), np.ascontiguousarray(v))
 
 
 def fp64_measured(ach_f64):
@@ -127,8 +153,9 @@ def cpu_baseline(w, hidden, ref, moe, faults_of=None, build_of=None):
 
 
 def self_launch(a):
-    """`python bench.py --gpus N` without a launcher: become N ranks under torch.distributed.run (RCCL rendezvous on
-    127.0.0.1), or report why not and exit 0."""
+    """`python bench.py --gpus N` without a launcher: run N ranks under torch.distributed.run (RCCL rendezvous on
+    127.0.0.1) in a child process and exit with its status, or report why not and exit 0.  (A child, not exec: this
+    process has already asked the runtime for its devices.)"""
     import torch
     have = torch.cuda.device_count() if torch.cuda.is_available() else 0
     if have < a.gpus:
@@ -139,8 +166,8 @@ def self_launch(a):
         s.bind(('127.0.0.1', 0))
         port = s.getsockname()[1]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get('HSA_ENABLE_IPC_MODE_LEGACY', '0'))
-    os.execvpe(sys.executable, [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(a.gpus),
-                                '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:], env)
+    sys.exit(subprocess.call([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(a.gpus),
+                              '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:], env=env))
 
 
 def main():
@@ -153,11 +180,14 @@ def main():
     ap.add_argument('--total-pop', type=int, default=0, help='strong scaling: ONE population of this many members sharded over the ranks')
     ap.add_argument('--num-evals', type=int, default=3)
     ap.add_argument('--lanes', type=int, default=0, help='episodes per wavefront (0 = auto)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-partition-check', action='store_true')
+    ap.add_argument('--full', action='store_true', help='also the CPU baseline and parity check, the host-buffer variant, the partition check and '
+                                                        'the strong-scaling legs (a plain run measures the line\'s `value` only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the results of the last timed step as DIR/<name>.npy (f64)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: leave the CPU baseline leg out')
+    ap.add_argument('--no-partition-check', action='store_true', help='--full: leave the N-GPU partition check out')
     ap.add_argument('--fused', action='store_true', help='mixed workload: ONE launch of one code object (the default whenever the library takes the combination; kept for A/B scripts)')
     ap.add_argument('--no-fused', action='store_true', help='mixed workload: a launch per dynamics build side by side instead of ONE launch of one code object (A/B)')
-    ap.add_argument('--strong-legs', choices=['auto', 'on', 'off'], default='auto', help='append the strong-scaling legs (pop=512, mixed pop=2048) to the line: auto = when N > 1 and no --total-pop / --pop')
+    ap.add_argument('--strong-legs', choices=['auto', 'on', 'off'], default='auto', help='append the strong-scaling legs (pop=512, mixed pop=2048) to the line: auto = with --full when N > 1 and no --total-pop / --pop')
     ap.add_argument('--timeout-s', type=float, default=900.0, help='--dry-partition: the time-out the plan is checked against (the driver\'s is not known to this script; "within minutes" is the contract)')
     ap.add_argument('--dry-partition', action='store_true', help='print the member / episode blocks of every rank for --gpus N [--total-pop M | --pop P] and exit: no GPU, no launcher')
     a = ap.parse_args()
@@ -197,13 +227,13 @@ def main():
     res = measure(a, ctx)
     # The driver's N-GPU command carries no --total-pop: on its own it is the WEAK-scaling line of the metric's configuration (pop = 50
     # per GPU).  BASELINE config 4 -- the one numeric target of north_star: ONE population of 512 sharded over the node, base/core/agent.py:234-256 --
-    # and config 5 (mixed-fault sweep, pop = 2 048) are strong-scaling questions, so the same run appends them as short legs (a few evaluations each,
+    # and config 5 (mixed-fault sweep, pop = 2 048) are strong-scaling questions, so a --full run appends them as short legs (a few evaluations each,
     # every rank in the same process group, the partition checked against one GPU), without touching the timed region above.
     legs = strong_legs(a, world)
     if legs:
         out = []
         for leg in legs:
-            a2 = argparse.Namespace(**dict(vars(a), **leg, no_cpu_baseline=True))
+            a2 = argparse.Namespace(**dict(vars(a), **leg, no_cpu_baseline=True, dump_outputs=None))
             r2 = measure(a2, ctx)
             if rank == 0:
                 out.append({k: r2[k] for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'scaling', 'kernel_ms', 't_step_us', 'config',
@@ -258,8 +288,9 @@ def _eval_seconds(workload, episodes, cus=256):
 
 
 def expected_wall(a, world):
-    """--dry-partition: what the command is expected to take on an N-GPU node, piece by piece (seconds), from PLAN_TIMES: the line itself, the
-    strong-scaling legs it appends, and rank 0's partition checks (one GPU re-evaluating all members) -- the only pieces that GROW with N."""
+    """--dry-partition: what the command is expected to take on an N-GPU node, piece by piece (seconds), from PLAN_TIMES: the line itself and,
+    with --full, the strong-scaling legs it appends and rank 0's partition checks (one GPU re-evaluating all members) -- the only pieces that
+    GROW with N."""
     from serl_amd import distributed as sd_
     P = PLAN_TIMES
     pieces = []
@@ -270,13 +301,13 @@ def expected_wall(a, world):
         t = dict(name=name, episodes_per_gpu=e_rank,
                  inputs_s=round(e_rank * P['ref_table_s_per_episode'] + per_rank_members * P['member_s'], 2),
                  timed_and_warmup_s=round((steps + warmup) * _eval_seconds(workload, e_rank), 2),
-                 host_buffer_variant_s=round(2 * _eval_seconds(workload, e_rank), 2),
+                 host_buffer_variant_s=round(2 * _eval_seconds(workload, e_rank), 2) if a.full else 0.0,
                  partition_check_s=round((e_all * P['ref_table_s_per_episode'] + total_members * P['member_s'] + _eval_seconds(workload, e_all)) if check else 0.0, 2))
         t['total_s'] = round(t['inputs_s'] + t['timed_and_warmup_s'] + t['host_buffer_variant_s'] + t['partition_check_s'], 2)
         pieces.append(t)
 
     wl = WORKLOADS[a.workload]
-    check = world > 1 and not a.no_partition_check
+    check = world > 1 and a.full and not a.no_partition_check
     if a.total_pop > 0:
         per = max(sd_.member_block(a.total_pop, world, r)[1] - sd_.member_block(a.total_pop, world, r)[0] for r in range(world))
         piece('line (strong: pop = %d over %d GPUs)' % (a.total_pop, world), a.workload, a.total_pop, per, a.steps, a.warmup, check)
@@ -297,10 +328,10 @@ def expected_wall(a, world):
 
 
 def strong_legs(a, world):
-    """the strong-scaling legs `bench.py --gpus N` (N > 1, no --total-pop) appends to its line; --strong-legs on / off forces or drops them"""
+    """the strong-scaling legs `bench.py --gpus N --full` (N > 1, no --total-pop) appends to its line; --strong-legs on / off forces or drops them"""
     if a.strong_legs == 'off' or a.total_pop > 0 or a.workload != 'serl50' or a.pop:
         return []
-    if a.strong_legs != 'on' and world <= 1:
+    if a.strong_legs != 'on' and (world <= 1 or not a.full):
         return []
     return [dict(workload='serl50', total_pop=512, steps=3, warmup=1), dict(workload='mixed', total_pop=2048, steps=2, warmup=1)]
 
@@ -396,6 +427,8 @@ def measure(a, ctx):
         kernel_ms.append(eng.kernel_ms() if not mixed else eng.last_kernel_ms)   # HIP events around the kernel, on its stream
     barrier()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, g, champion)
     steps_local = int(ls.abs().sum())
     # what the collective layer saw, gathered THROUGH it: every rank's id, its device, its mean kernel time and env steps -- a line from
     # an N-GPU run proves by itself that N distinct ranks on N distinct devices took part
@@ -421,7 +454,7 @@ def measure(a, ctx):
         return None
     value = steps_total * a.steps / dt
     res_extra = {}
-    if world > 1 and not a.no_partition_check:
+    if a.full and world > 1 and not a.no_partition_check:
         # the gathered result of the N-way sharded evaluation must be bit-identical to ONE GPU
         # evaluating the same pop x world members (rank 0 rebuilds every rank's block: the inputs are deterministic)
         if strong:
@@ -435,16 +468,19 @@ def measure(a, ctx):
         rows1, _, _ = evaluate(ws, rs, np.repeat(np.arange(gather_pop, dtype=np.int32), ne), gather_pop, ms if mixed else None)
         res_extra['partition_invariance'] = {'members': gather_pop, 'bit_identical_to_one_gpu': bool(torch.equal(rows1, g)),
                                              'champion': champion}
-    # informational (never `value`): the same evaluation when the boundary hands over HOST buffers -- weights and
-    # reference tables cross PCIe inside the timed region (pinned memory, one H2D copy each per evaluation)
-    w_pin, ref_pin = w_host.pin_memory(), torch.from_numpy(ref_host).pin_memory()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(2):
-        w.copy_(w_pin, non_blocking=True); ref.copy_(ref_pin, non_blocking=True)
-        one_step()
-    torch.cuda.synchronize()
-    value_host = steps_local * 2 / (time.perf_counter() - t1)
+    if a.full:
+        # informational (never `value`): the same evaluation when the boundary hands over HOST buffers -- weights and
+        # reference tables cross PCIe inside the timed region (pinned memory, one H2D copy each per evaluation)
+        w_pin, ref_pin = w_host.pin_memory(), torch.from_numpy(ref_host).pin_memory()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(2):
+            w.copy_(w_pin, non_blocking=True); ref.copy_(ref_pin, non_blocking=True)
+            one_step()
+        torch.cuda.synchronize()
+        # SURVEY 8(d) words the metric "incl. H2D of weights / refs"; the bench contract of this build forbids a PCIe-inclusive rate as
+        # `value`, so it rides along: this rank's evaluation with weights and reference tables crossing PCIe inside the timed region
+        res_extra['value_incl_h2d_of_inputs'] = steps_local * 2 / (time.perf_counter() - t1)
     k_ms = float(np.mean(kernel_ms))
     ach_hbm = steps_local * B_ALG / (k_ms * 1e-3)
     ach_f64 = steps_local * F_ALG / (k_ms * 1e-3)
@@ -508,15 +544,12 @@ def measure(a, ctx):
                                'frac': ach_f64 / FP64_PEAK}, **fp64_measured(ach_f64)),
         'roofline_issue': issue,
         't_step_us': t_step_us,
-        # SURVEY 8(d) words the metric "incl. H2D of weights / refs"; the bench contract of this build forbids a PCIe-inclusive rate as
-        # `value`, so it rides along: this rank's evaluation with weights and reference tables crossing PCIe inside the timed region
-        'value_incl_h2d_of_inputs': value_host,
         'rccl': rccl,
     }
     if mixed and placements:
         res['mixed_placement'] = placements[-1]      # (decision 1 = census of the CU pairs; 2 = tickets: shared GPU or another pair mapping, ~10 % slower; None = a launch per build)
     res.update(res_extra)
-    if not a.no_cpu_baseline and world == 1:          # (the contract: the CPU baseline leg runs on rank 0 at N = 1 only)
+    if a.full and not a.no_cpu_baseline and world == 1:          # (the contract: the CPU baseline leg runs on rank 0 at N = 1 only)
         build_of = faults_of = None
         if mixed:
             rs_ = [builds.resolve_mode(m) for m in modes]

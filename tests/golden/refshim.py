@@ -7,8 +7,8 @@ base/core/genetic_agent.py Actor) run under this container's Python 3.10 / torch
   * `envs.<build>._citation` -- ctypes-backed module around the reference's own shared object
                   (the cp38 SWIG extension cannot be imported by 3.10; its raw C entry points can)
 
-Used only by tests/golden/make_golden.py (golden-vector generation in the build container) and by
-the tests marked `needs_reference`.  Nothing here is imported by the product.
+Used only by the golden-vector generators of this directory (run in the build container) and by
+tests/tools/time_reference.py.  Nothing here is imported by the product.
 """
 import sys, types, os
 import numpy as np

@@ -179,7 +179,7 @@ def test_bench_n_gpu_command_plans_the_strong_scaling_legs():
     import subprocess, json
 
     def dry(*args):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--dry-partition'] + list(args), capture_output=True, text=True, timeout=120)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--dry-partition', '--full'] + list(args), capture_output=True, text=True, timeout=120)
         assert r.returncode == 0, r.stderr[-2000:]
         return json.loads(r.stdout.strip().splitlines()[-1])
     d = dry('--gpus', '2')
@@ -190,6 +190,11 @@ def test_bench_n_gpu_command_plans_the_strong_scaling_legs():
     assert [l['blocks'][-1] for l in dry('--gpus', '8')['strong_scaling_legs']] == [[448, 512], [1792, 2048]]
     for args in (('--gpus', '1'), ('--gpus', '8', '--total-pop', '512'), ('--gpus', '8', '--pop', '64'), ('--gpus', '8', '--strong-legs', 'off')):
         assert dry(*args)['strong_scaling_legs'] == []
+    # a plain run (no --full) measures the line only: no legs, no partition check
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--dry-partition', '--gpus', '8'], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    plain = json.loads(r.stdout.strip().splitlines()[-1])
+    assert plain['strong_scaling_legs'] == [] and [p['partition_check_s'] for p in plain['expected']['pieces']] == [0.0]
 
 
 def test_bench_n_gpu_plan_fits_the_time_out_and_says_what_to_drop():
@@ -199,7 +204,7 @@ def test_bench_n_gpu_plan_fits_the_time_out_and_says_what_to_drop():
     import subprocess, json
 
     def dry(*args):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--dry-partition'] + list(args), capture_output=True, text=True, timeout=120)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--dry-partition', '--full'] + list(args), capture_output=True, text=True, timeout=120)
         assert r.returncode == 0, r.stderr[-2000:]
         return json.loads(r.stdout.strip().splitlines()[-1])['expected']
     e8 = dry('--gpus', '8')
@@ -269,7 +274,7 @@ def test_sharded_evaluation_over_a_one_rank_rccl_group():
 
 @pytest.mark.gpu
 @pytest.mark.timeout(600)
-def test_bench_starts_itself_for_n_gpus_or_says_why_not():
+def test_bench_starts_itself_for_n_gpus_or_says_why_not(tmp_path):
     """`python bench.py --gpus N` without a launcher: with fewer than N GPUs one JSON line {"skipped": ...}, exit code 0;
     under torch.distributed.run with one rank the RCCL bench path runs end to end."""
     import subprocess, json
@@ -278,17 +283,24 @@ def test_bench_starts_itself_for_n_gpus_or_says_why_not():
     assert r.returncode == 0, r.stderr[-2000:]
     assert 'skipped' in json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get('HSA_ENABLE_IPC_MODE_LEGACY', '0'))
+    dump = tmp_path / 'outputs'
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
                         '--master-port', str(29700 + os.getpid() % 2000), os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '1',
-                        '--warmup', '0', '--pop', '4', '--no-cpu-baseline'], capture_output=True, text=True, timeout=500, env=env)
+                        '--warmup', '0', '--pop', '4', '--no-cpu-baseline', '--dump-outputs', str(dump)], capture_output=True, text=True, timeout=500, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith('{')][-1])
-    assert line['n_gpus'] == 1 and line['value'] > 0
+    assert line['n_gpus'] == 1 and line['value'] > 0 and line['ms_per_step'] > 0
     assert 'strong_scaling_legs' not in line          # (--pop given: no legs)
+    assert 'value_incl_h2d_of_inputs' not in line and 'cpu_baseline' not in line          # (no --full: the line's value only)
+    # --dump-outputs: the last timed step's gathered rows, one f64 array per column
+    out = {f.stem: np.load(f) for f in dump.glob('*.npy')}
+    assert sorted(out) == sorted(['fitness', 'return', 'smoothness', 'length_t', 'length_steps', 'cost_steps', 'pop_fitness', 'champion'])
+    assert all(v.dtype == np.float64 for v in out.values()) and out['fitness'].shape == (3, 4) and out['pop_fitness'].shape == (4,)
+    assert out['champion'][0] == np.argmax(out['pop_fitness']) and line['value'] == pytest.approx(np.abs(out['length_steps']).sum() / line['ms_per_step'] * 1e3)
     # ... and the strong-scaling legs an N-GPU run appends (forced here on the one rank): BASELINE configs 4 and 5 through the same process group
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
                         '--master-port', str(29750 + os.getpid() % 2000), os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '1',
-                        '--warmup', '0', '--no-cpu-baseline', '--strong-legs', 'on'], capture_output=True, text=True, timeout=550, env=env)
+                        '--warmup', '0', '--no-cpu-baseline', '--strong-legs', 'on', '--full'], capture_output=True, text=True, timeout=550, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith('{')][-1])
     legs = line['strong_scaling_legs']

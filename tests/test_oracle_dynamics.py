@@ -2,9 +2,9 @@
 
   * golden: tests/golden/dyn_open_loop.npz holds what the REFERENCE'S OWN shared object returned for a seeded
     3 000-step command sequence, for all 9 distinct builds (5 code variants) -- bit-exact.
-  * live (build container only, marker needs_reference): every one of the 14 build directories, step by
-    step against the loaded reference library -- outputs, the 19 continuous states and all block signals
-    rtB bit-exact, including re-initialisation.
+  * live: tests/golden/ref_live.npz holds digests of what the reference library returned for every one of the 14
+    build directories, step by step -- outputs, the 19 continuous states and all block signals rtB bit-exact,
+    including re-initialisation.
 """
 import numpy as np
 import pytest
@@ -57,24 +57,24 @@ def test_instances_are_independent():
         np.testing.assert_array_equal(ref.step(ca), xa[k])
 
 
-@pytest.mark.needs_reference
 @pytest.mark.parametrize('build', BUILDS14)
-def test_live_reference_library_step_by_step(build):
+def test_live_reference_library_step_by_step(golden, build):
+    """tests/golden/ref_live.npz: digests of what the reference library returned step by step for the seeded command sequence
+    of make_live_golden.live_commands (tests/golden/make_live_golden.py)"""
+    import hashlib, os, sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden'))
+    from make_live_golden import live_commands, digest64
     from oracle.dynamics import CitationDynamics
-    from oracle.refso import RefCitation
-    ref, sim = RefCitation(build), CitationDynamics(build)
-    rng = np.random.default_rng(hash(build) % 1000)
-    nB = len(sim.B)
-    for k in range(400):
-        cmd = np.zeros(10)
-        cmd[:3] = np.deg2rad(rng.uniform(-6, 6, 3)) * (k % 37 != 0)
-        if k > 200:
-            cmd[8:10] = rng.uniform(0, 0.2)
-        xr, xs = ref.step(cmd), sim.step(cmd)
-        np.testing.assert_array_equal(xs, xr, err_msg='%s step %d' % (build, k))
-        np.testing.assert_array_equal(np.asarray(sim.X), np.asarray(ref.X), err_msg='%s X step %d' % (build, k))
+    g = golden('ref_live')
+    cmds = live_commands(build)
+    assert hashlib.sha256(cmds.tobytes()).digest() == bytes(g[build + '_cmd_sha256']), 'not the command sequence the reference was driven with'
+    sim = CitationDynamics(build)
+    assert len(sim.B) == int(g[build + '_nB'])
+    for k, cmd in enumerate(cmds):
+        xs = sim.step(cmd)
+        assert digest64(xs) == g[build + '_y'][k], '%s step %d' % (build, k)
+        assert digest64(sim.X) == g[build + '_X'][k], '%s X step %d' % (build, k)
         if k % 50 == 0:
-            np.testing.assert_array_equal(np.asarray(sim.B)[:nB].view(np.uint64), np.asarray(ref.B)[:nB].view(np.uint64),
-                                          err_msg='%s rtB step %d' % (build, k))
-    ref.initialize(); sim.initialize()
-    np.testing.assert_array_equal(sim.step(np.zeros(10)), ref.step(np.zeros(10)))
+            assert digest64(sim.B) == g[build + '_B'][k // 50], '%s rtB step %d' % (build, k)
+    sim.initialize()
+    np.testing.assert_array_equal(sim.step(np.zeros(10)), g[build + '_y_reinit'])

@@ -5,7 +5,7 @@
 #   tests            the whole GPU suite (pytest -m gpu)
 #   ab:<lib,...>     tools/ab.py on each library (product = "default"; others by the tag of serl_amd/csrc/libserl_amd_<tag>.so), twice each,
 #                    150 episodes of the SERL50 shape; AB_E / AB_ACTORS override
-#   bench            the driver's command (bench.py, defaults)
+#   bench            bench.py --full: the line with every leg (CPU baseline, parity, host-buffer variant)
 #   bench:<args>     bench.py with the given arguments (commas for spaces), e.g. bench:--workload,serl10,--no-cpu-baseline
 #   pmc              the SQ issue counters + FETCH / WRITE sizes of one evaluation (separate passes, MI355X_MICROARCH.md)
 #   icache:<args>    instruction-cache counters (SQC_ICACHE_REQ / HITS / MISSES / MISSES_DUPLICATE, SQ_IFETCH) of one evaluation of bench.py <args>
@@ -36,7 +36,7 @@ for STEP in "$@"; do
       done
       cut -c1-200 $O/ab.txt ;;
     bench)
-      timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; tail -c 1500 $O/bench.json ;;
+      timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 1500 $O/bench.json ;;
     bench:*)
       A=$(echo ${STEP#bench:} | tr ',' ' '); N=$(echo ${STEP#bench:} | tr -c 'a-zA-Z0-9' '_')
       timeout 900 python bench.py $A > $O/bench$N.json 2> $O/bench$N.err; tail -c 600 $O/bench$N.json ;;

@@ -11,8 +11,8 @@ mkdir -p $O
 (cd $R && python serl_amd/build.py --source-hash) > $O/csrc_sha256.txt      # what these measurements belong to (bench.py quotes them only while it matches)
 cd /tmp && export TMPDIR=/tmp
 B="python $R/bench.py"
-timeout 900 $B --steps 10 --warmup 3 > $O/bench_serl50.json 2> $O/bench_serl50.err
-timeout 900 $B --total-pop 512 --steps 3 --warmup 1 > $O/bench_total512.json 2> $O/bench_total512.err                     # BASELINE config 4 on one GPU, parity vs the CPU restatement on all 1 536 episodes
+timeout 900 $B --full --steps 10 --warmup 3 > $O/bench_serl50.json 2> $O/bench_serl50.err
+timeout 900 $B --full --total-pop 512 --steps 3 --warmup 1 > $O/bench_total512.json 2> $O/bench_total512.err                     # BASELINE config 4 on one GPU, parity vs the CPU restatement on all 1 536 episodes
 timeout 600 $B --workload serl10 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_serl10.json 2> $O/bench_serl10.err
 SERL_REMOTE_ACTOR=0 timeout 600 $B --workload serl10 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_serl10_samecu.json 2> $O/bench_serl10_samecu.err      # A/B: the streamed actor on the team's CU (round 5's kernel)
 timeout 600 $B --workload serl10 --pop 128 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_serl10_pop128.json 2> $O/bench_serl10_pop128.err   # 384 episodes, H = 72: two per team, two actor wavefronts
