@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SERL_ABI_VERSION 8
+#define SERL_ABI_VERSION 9
 
 enum serl_error {
   SERL_OK = 0,
@@ -192,7 +192,8 @@ int serl_env_action_dim(int env_config);
 int serl_abi_version(void);
 /* Layout self-check for bindings that mirror the structs by hand (ctypes, cgo ...): fills out[0 .. n) with
  *   sizeof(serl_rollout_desc), then offsetof of each of its members in declaration order,
- *   then sizeof(serl_build_desc), sizeof(serl_fault_row), sizeof(serl_ref_spec), sizeof(serl_replay_job)
+ *   then sizeof(serl_build_desc), sizeof(serl_fault_row), sizeof(serl_ref_spec), sizeof(serl_replay_job),
+ *   then (ABI v9) sizeof(serl_venv_desc) and offsetof of each of its members in declaration order
  * as this library was compiled, and returns the number of values (written or not: call with capacity 0 to size). */
 int serl_abi_layout(int32_t *out, int32_t capacity);
 /* number of f32 parameters of an actor: H*S+H + L*(H*H+3H) + A*H+A */
@@ -230,6 +231,58 @@ int serl_rollout_multi(serl_ctx *ctx, int32_t n, const serl_rollout_desc *descs,
  * reference's step(cmd) -- cmds f64 [n_episodes][T][10] -> states f64 [n_episodes][T][12] (device). */
 int serl_dyn_open_loop(serl_ctx *ctx, int slot, int32_t n_episodes, int32_t T, const double *cmds,
                        double *states, int32_t lanes_per_wave, int32_t kernel_hint /* AUTO, TEAM or WAVE */, void *stream);
+
+/* ---- ABI v9: the env step-wise -- a batched vector env (CitationEnv.reset / .step, envs/phlabenv.py:401-482) ------------------
+ * For callers that drive the dynamics with a policy of their own (any torch module, a PID / MPC baseline, an RL library) instead of
+ * the fused actor of serl_rollout.  One lane = one env; one launch per call covers all envs; nothing is allocated and nothing is
+ * synchronised.  Env state lives in a caller-owned opaque DEVICE buffer of serl_venv_state_bytes(n_envs) bytes that must be
+ * zero-filled before its first use: a zero state is a fresh env (carried error 0, model clock 0) that is not running -- stepping
+ * it returns zeros and done = 1 until it is reset.  The glue is the fused kernels' (rollout_variant.inc / rollout_wave.inc):
+ *   reset  initialize() -- the model clock keeps counting (see tick0) --, one step with a zero command (fault row applied), sensor
+ *          noise entry 0, V0 = x[3], t = 0, k = 0, last_u = 0;  obs0 = [carried error (A), x[obs_idx], last_u (A, incremental)].
+ *          The error is NOT cleared (envs/phlabenv.py:401-428 never clears self.error): a re-used env's obs0 carries its last error.
+ *   step   action scaled as scale_action (envs/phlabenv.py:62-73) with the fused kernels' precision: f32 actions compute
+ *          s = 0.5f * (a + 1.0f) in f32, then low + s * (high - low) in f64; f64 actions are f64 throughout.  The env does NOT
+ *          clip (the reference's agent does, base/core/agent.py:93).  Incremental control: u = last_u + scaled * dt.  Fault row,
+ *          step(), sensor noise entry k + 1, reference row k (or generated at the pre-increment t), reward / cost / bounds /
+ *          penalty as envs/phlabenv.py:347-399, then t += dt, k += 1.
+ *   done   done = bounds hit (envs/phlabenv.py:391-399) OR k == max_steps (the reference tables are exhausted).  A done env is
+ *          FROZEN: stepping it returns its last obs, x, ref, t and cost with reward 0 and done = 1 and changes nothing until it
+ *          is reset, so no step ever reads ref / sensor_noise past max_steps.  The reference env would keep integrating: a
+ *          deliberate difference.  No auto-reset. */
+typedef struct serl_venv_desc {
+  int32_t n_envs;                   /* envs of the batch, >= 1 */
+  int32_t build_slot;               /* slot given to serl_ctx_load_build: one dynamics build per env object */
+  int32_t env_config;               /* enum serl_env_config, as serl_rollout_desc.env_config */
+  int32_t incremental;              /* 1 = the action is an actuator rate (serl_rollout_desc.incremental) */
+  int32_t state_dim, action_dim;    /* must equal serl_env_state_dim(env_config, incremental) / serl_env_action_dim(env_config) */
+  int32_t max_steps;                /* rows of every env's ref table; sensor_noise rows hold max_steps + 1 entries */
+  int32_t pad0;
+  double t_max;                     /* episode length, seconds (bounds and termination penalty) */
+  const serl_fault_row *faults;     /* [n_envs] or NULL (nominal) */
+  const double *ref;                /* [.., max_steps, 3] radians, as serl_rollout_desc.ref; NULL when ref_spec is given */
+  int64_t ref_stride;               /* doubles between consecutive envs' tables (0 = one shared table) */
+  const serl_ref_spec *ref_spec;    /* [n_envs] (stride 1) or one shared spec (stride 0): references generated in the kernel, or NULL */
+  int64_t ref_spec_stride;
+  const double *sensor_noise;       /* [rows][max_steps + 1][7] additive sensor noise, as serl_rollout_desc.sensor_noise, or NULL */
+  const int32_t *sensor_row;        /* [n_envs] row of sensor_noise, -1 = none; NULL = row e for env e */
+  const double *err0;               /* serl_venv_reset only: [n_envs][3] error put into obs0 instead of the carried one, or NULL */
+  const int32_t *tick0;             /* serl_venv_reset only: [n_envs] model clock to start from instead of the carried one, or NULL.
+                                       The carried clock counts one tick per reset and one per step (initialize() does not reset
+                                       clockTick0, see serl_rollout_desc.tick0); a fresh env starts at 0 */
+  void *state;                      /* DEVICE, serl_venv_state_bytes(n_envs) bytes, zero-filled before first use; opaque */
+} serl_venv_desc;
+/* bytes of the state buffer of n_envs envs (SoA: [field][n_envs rounded up to 64]); 0 for n_envs < 1 */
+int64_t serl_venv_state_bytes(int32_t n_envs);
+/* reset the envs with mask[e] != 0 (mask: DEVICE u8 [n_envs], NULL = all).  obs: DEVICE f64 [n_envs][state_dim], written for
+ * EVERY env: obs0 of the reset ones, the current observation of the others. */
+int serl_venv_reset(serl_ctx *ctx, const serl_venv_desc *desc, const uint8_t *mask, double *obs, void *stream);
+/* one env step of every env.  actions: DEVICE [n_envs][action_dim], f32 (actions_f64 = 0) or f64 (actions_f64 = 1).
+ * Outputs (DEVICE): obs f64 [n_envs][state_dim], reward f64 [n_envs], done u8 [n_envs]; optional (NULL = not written):
+ * x f64 [n_envs][12] (what step() returned, sensor noise included), ref f64 [n_envs][3] (theta, phi, beta reference of the step),
+ * t f64 [n_envs] (info['t'], after the increment), cost i32 [n_envs] (get_cost of the step). */
+int serl_venv_step(serl_ctx *ctx, const serl_venv_desc *desc, const void *actions, int32_t actions_f64, double *obs,
+                   double *reward, uint8_t *done, double *x, double *ref, double *t, int32_t *cost, void *stream);
 
 /* Development aid: with SERL_PROFILE=1 in the environment serl_rollout records shader-clock cycles of wave 0 of
  * workgroup 0: out[0..3] = {actor forward, dynamics step, env bookkeeping, env steps}; out[4..31] = phase

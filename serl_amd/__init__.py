@@ -14,6 +14,7 @@ and the host-side mirror of the reference interface for this path:
   SSNE operators and epoch     base/core/mod_neuro_evo.py           (ga.py, ssne.py, distill.py)
   DeviceReplay rings           base/core/replay_memory.py:12-103, agent.py:101-112   (replay.py)
   member sharding + RCCL all-gather of fitness                      (distributed.py)
+  CitationVecEnv               CitationEnv.reset / .step, envs/phlabenv.py:401-482: N envs stepped by any torch policy (venv.py)
 
 The HIP extension is mandatory: importing the evaluator on a machine without the built
 library, or calling it without a GPU, raises -- there is no CPU fallback in the product.
@@ -24,8 +25,9 @@ from .evaluator import RolloutEngine, evaluate_pop, validate_pop, make_evaluate,
 from .generation import evaluate_generation, validate_actor, GenerationResult
 from .replay import DeviceReplay
 from .ssne import SSNE
+from .venv import CitationVecEnv
 from . import refsignals, metrics, ga, distributed, builds, replay, ssne
 
 __all__ = ['Actor', 'GeneticAgent', 'pack_actor', 'pack_population', 'NetSpec', 'Episode', 'RolloutEngine',
            'evaluate_pop', 'validate_pop', 'make_evaluate', 'PopResult', 'evaluate_generation', 'validate_actor',
-           'GenerationResult', 'DeviceReplay', 'SSNE', 'replay', 'ssne', 'refsignals', 'metrics', 'ga', 'distributed', 'builds']
+           'GenerationResult', 'DeviceReplay', 'SSNE', 'CitationVecEnv', 'replay', 'ssne', 'refsignals', 'metrics', 'ga', 'distributed', 'builds']

@@ -12,7 +12,8 @@ EXPORTS = ['serl_abi_version', 'serl_last_error', 'serl_param_count', 'serl_ctx_
            'serl_ctx_load_build', 'serl_rollout', 'serl_rollout_multi', 'serl_dyn_open_loop', 'serl_debug_profile', 'serl_debug_mixed_placement', 'serl_last_rollout_ms', 'serl_last_rollout_info', 'serl_ga_clone', 'serl_ga_crossover',
            'serl_ga_mutate', 'serl_ga_scaled_perturb', 'serl_abi_layout', 'serl_ga_sensitivity', 'serl_ga_novelty',
            'serl_replay_scatter', 'serl_env_state_dim', 'serl_env_action_dim',
-           'serl_smoothness', 'serl_smoothness_work_size', 'serl_ga_distill', 'serl_host_sample_slots']
+           'serl_smoothness', 'serl_smoothness_work_size', 'serl_ga_distill', 'serl_host_sample_slots',
+           'serl_venv_state_bytes', 'serl_venv_reset', 'serl_venv_step']
 
 
 class BuildDesc(ctypes.Structure):
@@ -50,9 +51,17 @@ class ReplayJob(ctypes.Structure):
                 ('length', ctypes.c_int32), ('cost_only', ctypes.c_int32), ('skip', ctypes.c_int32)]
 
 
+class VenvDesc(ctypes.Structure):
+    """serl_venv_desc (ABI v9): the step-wise vector env"""
+    _fields_ = [('n_envs', ctypes.c_int32), ('build_slot', ctypes.c_int32), ('env_config', ctypes.c_int32), ('incremental', ctypes.c_int32),
+                ('state_dim', ctypes.c_int32), ('action_dim', ctypes.c_int32), ('max_steps', ctypes.c_int32), ('pad0', ctypes.c_int32),
+                ('t_max', ctypes.c_double), ('faults', VP), ('ref', VP), ('ref_stride', ctypes.c_int64), ('ref_spec', VP),
+                ('ref_spec_stride', ctypes.c_int64), ('sensor_noise', VP), ('sensor_row', VP), ('err0', VP), ('tick0', VP), ('state', VP)]
+
+
 # serl_rollout_desc.kernel_hint (enum serl_kernel_hint)
 KERNEL_HINTS = {None: 0, 'auto': 0, 'team': 1, 'wave': 2, 'half': 3, 'team2': 4, 'team4': 5}
-ABI_VERSION = 8
+ABI_VERSION = 9
 # serl_last_rollout_info out[0] (enum serl_kernel_family)
 FAMILIES = {0: None, 1: 'team', 2: 'teams', 3: 'teams2', 4: 'teamx', 5: 'team2', 6: 'team2s', 7: 'team4', 8: 'team4_mixed', 9: 'half', 10: 'wave', 11: 'wavex', 12: 'lane', 13: 'teamr'}
 
@@ -60,7 +69,8 @@ FAMILIES = {0: None, 1: 'team', 2: 'teams', 3: 'teams2', 4: 'teamx', 5: 'team2',
 def expected_layout():
     """What serl_abi_layout() must return for these hand-written mirrors to be right."""
     return ([ctypes.sizeof(RolloutDesc)] + [getattr(RolloutDesc, n).offset for n, _ in RolloutDesc._fields_] +
-            [ctypes.sizeof(BuildDesc), ctypes.sizeof(FaultRow), ctypes.sizeof(RefSpec), ctypes.sizeof(ReplayJob)])
+            [ctypes.sizeof(BuildDesc), ctypes.sizeof(FaultRow), ctypes.sizeof(RefSpec), ctypes.sizeof(ReplayJob)] +
+            [ctypes.sizeof(VenvDesc)] + [getattr(VenvDesc, n).offset for n, _ in VenvDesc._fields_])
 
 
 _lib = None
@@ -105,9 +115,12 @@ def lib():
     L.serl_smoothness_work_size.argtypes = [i32, i32]
     L.serl_ga_distill.argtypes = [VP, VP, ctypes.c_int64, i32, i32, i32, i32, i32, i32, VP, VP, VP, i32, VP, i32, VP, VP, ctypes.c_float, VP]
     L.serl_host_sample_slots.argtypes = [VP, ctypes.c_longlong, i32, i32, i32, VP, i32]
+    L.serl_venv_state_bytes.argtypes = [i32]
+    L.serl_venv_reset.argtypes = [VP, ctypes.POINTER(VenvDesc), VP, VP, VP]
+    L.serl_venv_step.argtypes = [VP, ctypes.POINTER(VenvDesc), VP, i32, VP, VP, VP, VP, VP, VP, VP, VP]
     for f in EXPORTS:
         if f not in ('serl_last_error',):
-            getattr(L, f).restype = ctypes.c_longlong if f == 'serl_host_sample_slots' else ctypes.c_int
+            getattr(L, f).restype = ctypes.c_longlong if f in ('serl_host_sample_slots', 'serl_venv_state_bytes') else ctypes.c_int
     if L.serl_abi_version() != ABI_VERSION:
         raise RuntimeError('serl_amd: ABI version mismatch (library %d, binding %d): rebuild with `python serl_amd/build.py`'
                            % (L.serl_abi_version(), ABI_VERSION))

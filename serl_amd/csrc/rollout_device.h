@@ -33,6 +33,45 @@ struct RolloutArgs {
   int32_t wt_members;                 // ... (serl_capi.hip serl_regroup_weights_kernel, once per launch); nullptr: every lane walks its member's row of d.weights
 };
 
+// The step-wise vector env (serl_venv_reset / serl_venv_step, venv_variant.inc): one lane = one env.  Its state is the caller's
+// opaque buffer, structure of arrays -- field f of env e at [f][npad] + e, npad = n_envs rounded up to 64, so that the 64 lanes of a
+// wavefront load and store whole lines: the f64 fields first, the i32 fields behind them.
+enum SerlVenvF64 {
+  SERL_VF_X = 0,                          // CitCtx.X[19]
+  SERL_VF_DW = SERL_VF_X + 19,            // CitCtx.DW[29] (the Derivative-block banks)
+  SERL_VF_CT = SERL_VF_DW + 29,           // CitCtx.t
+  SERL_VF_CSTOP,                          // CitCtx.stop_time
+  SERL_VF_ERR,                            // env error[3] (carried into obs0 by reset)
+  SERL_VF_LASTU = SERL_VF_ERR + 3,        // env last_u[3]
+  SERL_VF_V0 = SERL_VF_LASTU + 3,         // env V0
+  SERL_VF_T,                              // env t (accumulated)
+  SERL_VF_XO,                             // x[12] the last call of step() returned (sensor noise included): a done env's outputs
+  SERL_VF_REF = SERL_VF_XO + 12,          // reference[3] of the last env step
+  SERL_VENV_F64 = SERL_VF_REF + 3
+};
+enum SerlVenvI32 {
+  SERL_VI_IW = 0,                         // CitCtx.IW[4]
+  SERL_VI_TICK = SERL_VI_IW + 4,          // CitCtx.tick (clockTick0: keeps counting across resets)
+  SERL_VI_CERR,                           // CitCtx.err
+  SERL_VI_HINT,                           // CitCtx.hint[8]
+  SERL_VI_K = SERL_VI_HINT + 8,           // env steps taken since the reset
+  SERL_VI_LIVE,                           // 1 = running (reset and not done); 0 = done or never reset: the env is frozen
+  SERL_VI_COST,                           // get_cost of the last env step
+  SERL_VENV_I32
+};
+static inline int64_t serl_venv_npad(int32_t n_envs) { return ((int64_t)n_envs + 63) / 64 * 64; }
+
+struct VenvArgs {
+  serl_venv_desc d;
+  int64_t npad;                           // serl_venv_npad(d.n_envs)
+  const uint8_t *mask;                    // reset: [n_envs] envs to reset, nullptr = all
+  const void *actions;                    // step: [n_envs][A] f32 or (actions_f64) f64
+  int32_t actions_f64;
+  double *obs, *reward, *x, *ref, *t;     // outputs [n_envs][S], [n_envs], [n_envs][12], [n_envs][3], [n_envs] (x, ref, t optional)
+  uint8_t *done;
+  int32_t *cost;                          // optional
+};
+
 // The mailbox of ONE episode between its team workgroup and its actor workgroup on another CU (serl_rollout_teamr_kernel_<v>): the state x_k travels
 // one way behind xseq = k + 2, the command of env step k + 1 the other way behind aseq = k + 2 (device-scope release / acquire; a cache line each)
 struct SerlMail {

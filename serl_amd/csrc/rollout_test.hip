@@ -38,6 +38,7 @@ static_assert(8 * (CIT_RO_LDS_WORDS + cit_test_NSLOPE) <= 160 * 1024, "tables + 
 #define CIT_Y_IS_STATE 1      // (gen/citation_test_lane.inc: `if (major) c->Y[i] = X[i]`, i < 12 -- the outputs of step() are the states in front of the integration)
 #include "citation_step_dev.h"
 #include "rollout_variant.inc"
+#include "venv_variant.inc"
 #undef CIT_NO_AXES
 #undef CIT_B_AT
 #undef SERL_FLAVOUR_LDS
@@ -49,3 +50,6 @@ void serl_launch_dyn_test(const RolloutArgs &a, const double *cmds, double *stat
 {
   bdag::serl_launch_dyn_test(a, cmds, states, T, grid, stream);
 }
+
+void serl_launch_venv_reset_test(const RolloutArgs &a, const VenvArgs &v, int grid, hipStream_t stream) { bdag::serl_launch_venv_reset_test(a, v, grid, stream); }
+void serl_launch_venv_step_test(const RolloutArgs &a, const VenvArgs &v, int grid, hipStream_t stream) { bdag::serl_launch_venv_step_test(a, v, grid, stream); }

@@ -40,6 +40,22 @@ static void serl_launch_dyn_lane(int code, const RolloutArgs &a, const double *c
     default: serl_launch_dyn_nominal(a, cmds, states, T, grid, stream); break;
   }
 }
+// the step-wise vector env (venv_variant.inc, behind the lane kernels of rollout_<variant>.hip): one lane = one env
+#define SERL_VENV_DECL(v) \
+  void serl_launch_venv_reset_##v(const RolloutArgs &a, const VenvArgs &v_, int grid, hipStream_t stream); \
+  void serl_launch_venv_step_##v(const RolloutArgs &a, const VenvArgs &v_, int grid, hipStream_t stream);
+SERL_VENV_DECL(nominal) SERL_VENV_DECL(ice) SERL_VENV_DECL(cg_timed) SERL_VENV_DECL(gust) SERL_VENV_DECL(test)
+#undef SERL_VENV_DECL
+static void serl_launch_venv(int code, bool step, const RolloutArgs &a, const VenvArgs &v, int grid, hipStream_t stream)
+{
+  switch (code) {
+    case SERL_DYN_ICE: (step ? serl_launch_venv_step_ice : serl_launch_venv_reset_ice)(a, v, grid, stream); break;
+    case SERL_DYN_CG_TIMED: (step ? serl_launch_venv_step_cg_timed : serl_launch_venv_reset_cg_timed)(a, v, grid, stream); break;
+    case SERL_DYN_GUST: (step ? serl_launch_venv_step_gust : serl_launch_venv_reset_gust)(a, v, grid, stream); break;
+    case SERL_DYN_TEST: (step ? serl_launch_venv_step_test : serl_launch_venv_reset_test)(a, v, grid, stream); break;
+    default: (step ? serl_launch_venv_step_nominal : serl_launch_venv_reset_nominal)(a, v, grid, stream); break;
+  }
+}
 #define SERL_DECL_WAVE(v)                                                                                     \
   void serl_launch_rollout_wave_##v(const RolloutArgs &a, int grid, hipStream_t stream);                          \
   void serl_launch_rollout_wavex_##v(const RolloutArgs &a, int grid, hipStream_t stream);                         \
@@ -364,7 +380,13 @@ int serl_abi_layout(int32_t *out, int32_t capacity)
     SERL_OFF(concurrent_episodes), SERL_OFF(kernel_hint), SERL_OFF(fitness), SERL_OFF(length_steps), SERL_OFF(length_t),
     SERL_OFF(cost_steps), SERL_OFF(actions), SERL_OFF(states), SERL_OFF(rewards), SERL_OFF(transitions), SERL_OFF(ref_spec),
     SERL_OFF(ref_spec_stride), SERL_OFF(env_config), SERL_OFF(incremental),
-    (int32_t)sizeof(serl_build_desc), (int32_t)sizeof(serl_fault_row), (int32_t)sizeof(serl_ref_spec), (int32_t)sizeof(serl_replay_job)};
+    (int32_t)sizeof(serl_build_desc), (int32_t)sizeof(serl_fault_row), (int32_t)sizeof(serl_ref_spec), (int32_t)sizeof(serl_replay_job),
+#undef SERL_OFF
+#define SERL_OFF(m) (int32_t)offsetof(serl_venv_desc, m)
+    (int32_t)sizeof(serl_venv_desc),
+    SERL_OFF(n_envs), SERL_OFF(build_slot), SERL_OFF(env_config), SERL_OFF(incremental), SERL_OFF(state_dim), SERL_OFF(action_dim),
+    SERL_OFF(max_steps), SERL_OFF(pad0), SERL_OFF(t_max), SERL_OFF(faults), SERL_OFF(ref), SERL_OFF(ref_stride), SERL_OFF(ref_spec),
+    SERL_OFF(ref_spec_stride), SERL_OFF(sensor_noise), SERL_OFF(sensor_row), SERL_OFF(err0), SERL_OFF(tick0), SERL_OFF(state)};
 #undef SERL_OFF
   const int32_t n = (int32_t)(sizeof(v) / sizeof(v[0]));
   for (int32_t i = 0; out && i < n && i < capacity; ++i) out[i] = v[i];
@@ -878,6 +900,85 @@ int serl_dyn_open_loop(serl_ctx *c, int slot, int32_t n_episodes, int32_t T, con
   HIP_TRY(hipEventRecord(c->ev1, stream));
   c->timed = true;
   return SERL_OK;
+}
+
+// ---- the step-wise vector env (include/serl_amd.h, ABI v9) ----------------------------------------------------------------------
+int64_t serl_venv_state_bytes(int32_t n_envs)
+{
+  if (n_envs < 1) return 0;
+  return serl_venv_npad(n_envs) * (int64_t)(SERL_VENV_F64 * sizeof(double) + SERL_VENV_I32 * sizeof(int32_t));
+}
+
+static int serl_venv_check(serl_ctx *c, const serl_venv_desc *d, const char *what)
+{
+  const std::string w(what);
+  if (!c || !d) return fail(SERL_E_INVALID, w + ": NULL argument");
+  if (d->n_envs <= 0) return fail(SERL_E_INVALID, w + ": n_envs <= 0");
+  if (d->build_slot < 0 || d->build_slot >= SERL_MAX_SLOTS || !c->slots[d->build_slot].loaded)
+    return fail(SERL_E_INVALID, w + ": build slot not loaded");
+  if (!serl_has_lane_kernel(c->slots[d->build_slot].code)) return fail(SERL_E_UNSUPPORTED, w + ": unknown code variant");
+  if (serl_env_state_dim(d->env_config, d->incremental) == 0)
+    return fail(SERL_E_INVALID, w + ": env_config must be SERL_ENV_ATTITUDE, SERL_ENV_SYMMETRIC or SERL_ENV_FULL");
+  if (d->state_dim != serl_env_state_dim(d->env_config, d->incremental) || d->action_dim != serl_env_action_dim(d->env_config))
+    return fail(SERL_E_INVALID, w + ": state_dim / action_dim do not match the env configuration (attitude 7 / 3, symmetric 2 / 1, full 13 / 3; incremental adds action_dim observations)");
+  if (d->max_steps <= 0) return fail(SERL_E_INVALID, w + ": max_steps <= 0");
+  if (!(d->t_max > 0.0)) return fail(SERL_E_INVALID, w + ": t_max <= 0");
+  if (!d->ref && !d->ref_spec) return fail(SERL_E_INVALID, w + ": neither ref nor ref_spec");
+  if (d->ref && !d->ref_spec && d->ref_stride != 0 && d->ref_stride < (int64_t)d->max_steps * 3)
+    return fail(SERL_E_INVALID, w + ": ref_stride smaller than max_steps x 3");
+  if (d->ref_spec && d->ref_spec_stride != 0 && d->ref_spec_stride != 1) return fail(SERL_E_INVALID, w + ": ref_spec_stride must be 0 or 1");
+  if (!d->state) return fail(SERL_E_INVALID, w + ": state is NULL");
+  if (((uintptr_t)d->state & 7) != 0) return fail(SERL_E_INVALID, w + ": state must be 8-byte aligned");
+  return SERL_OK;
+}
+
+// the launch shape of serl_dyn_open_loop's lane kernels: lanes per wavefront from the batch, so that small batches still spread over the CUs
+static int serl_venv_launch(serl_ctx *c, const serl_venv_desc *d, bool step, VenvArgs &v, hipStream_t stream)
+{
+  const BuildSlot &s = c->slots[d->build_slot];
+  RolloutArgs a;
+  memset(&a, 0, sizeof(a));
+  a.d.n_episodes = d->n_envs;
+  a.ro = s.blob; a.t3 = s.blob + s.n_ro; a.x0 = a.t3 + 46; a.dw0 = a.x0 + 19;
+  a.dyn_dt = s.dt;
+  int lanes = (d->n_envs + 255) / 256;
+  if (lanes > 64) lanes = 64;
+  a.lanes = lanes;
+  const int nwaves = (d->n_envs + lanes - 1) / lanes;
+  const int wpb = serl_waves_per_block(c, nwaves);
+  a.block = 64 * wpb;
+  const int grid = (nwaves + wpb - 1) / wpb;
+  v.d = *d;
+  v.npad = serl_venv_npad(d->n_envs);
+  serl_launch_venv(s.code, step, a, v, grid, stream);
+  HIP_TRY(hipGetLastError());
+  return SERL_OK;
+}
+
+int serl_venv_reset(serl_ctx *c, const serl_venv_desc *d, const uint8_t *mask, double *obs, void *stream_)
+{
+  { const int rc_ = serl_venv_check(c, d, "serl_venv_reset"); if (rc_ != SERL_OK) return rc_; }
+  if (!obs) return fail(SERL_E_INVALID, "serl_venv_reset: obs is NULL");
+  HIP_TRY(hipSetDevice(c->device));
+  VenvArgs v;
+  memset(&v, 0, sizeof(v));
+  v.mask = mask;
+  v.obs = obs;
+  return serl_venv_launch(c, d, false, v, (hipStream_t)stream_);
+}
+
+int serl_venv_step(serl_ctx *c, const serl_venv_desc *d, const void *actions, int32_t actions_f64, double *obs,
+                   double *reward, uint8_t *done, double *x, double *ref, double *t, int32_t *cost, void *stream_)
+{
+  { const int rc_ = serl_venv_check(c, d, "serl_venv_step"); if (rc_ != SERL_OK) return rc_; }
+  if (!actions || !obs || !reward || !done) return fail(SERL_E_INVALID, "serl_venv_step: actions / obs / reward / done is NULL");
+  if (actions_f64 != 0 && actions_f64 != 1) return fail(SERL_E_INVALID, "serl_venv_step: actions_f64 must be 0 (f32) or 1 (f64)");
+  HIP_TRY(hipSetDevice(c->device));
+  VenvArgs v;
+  memset(&v, 0, sizeof(v));
+  v.actions = actions; v.actions_f64 = actions_f64;
+  v.obs = obs; v.reward = reward; v.done = done; v.x = x; v.ref = ref; v.t = t; v.cost = cost;
+  return serl_venv_launch(c, d, true, v, (hipStream_t)stream_);
 }
 
 /* development aid (SERL_PROFILE=1): shader-clock cycles wave 0 of workgroup 0 spent in the actor forward, the

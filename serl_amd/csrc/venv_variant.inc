@@ -1,0 +1,229 @@
+// venv_variant.inc -- the step-wise vector env (CitationEnv.reset / .step, envs/phlabenv.py:401-482; serl_venv_reset /
+// serl_venv_step in include/serl_amd.h), instantiated once per dynamics code variant (VARIANT) behind rollout_variant.inc, whose
+// LDS staging (serl_stage_and_index_<v>) and dynamics step (cit_step_<v>) it reuses.  Inside namespace bdag.
+//
+// One lane = one env, per call: load the env's state from the caller's SoA buffer (rollout_device.h SerlVenvF64 / SerlVenvI32) into
+// a CitCtx in the kernel's stack frame -- so that CitCtx.dwm points at this lane's private copy of the banks, as in the lane
+// rollout kernels --, run one reset() or step(), store the state back.  The glue is the lane / wave rollout kernels' own
+// (rollout_variant.inc, rollout_wave.inc X = true): all three env configurations and incremental control, widths from the descriptor.
+#define VV_PASTE2(a, b) a##b
+#define VV_PASTE(a, b) VV_PASTE2(a, b)
+#define VV_NAME(x) VV_PASTE(x, VARIANT)
+
+#ifndef SERL_VENV_COMMON
+#define SERL_VENV_COMMON
+// observation = [error (A), observed states, last_u (A, incremental only)] (envs/phlabenv.py:84-97,415-428,462-466)
+static __device__ __forceinline__ void serl_venv_write_obs(int cfg, bool incr, const double (&err)[3], const double (&x)[12],
+                                                           const double (&u)[3], double *o)
+{
+  if (cfg == SERL_ENV_SYMMETRIC) {
+    o[0] = err[0]; o[1] = x[1];
+    if (incr) o[2] = u[0];
+  } else if (cfg == SERL_ENV_FULL) {
+    o[0] = err[0]; o[1] = err[1]; o[2] = err[2];
+    for (int i = 0; i < 10; ++i) o[3 + i] = x[i];
+    if (incr) { o[13] = u[0]; o[14] = u[1]; o[15] = u[2]; }
+  } else {
+    o[0] = err[0]; o[1] = err[1]; o[2] = err[2];
+    o[3] = x[0]; o[4] = x[1]; o[5] = x[2]; o[6] = x[4];
+    if (incr) { o[7] = u[0]; o[8] = u[1]; o[9] = u[2]; }
+  }
+}
+
+// the outputs of an env that does not move in this call (not in the reset mask; stepped while done / never reset): its current
+// observation from the stored state, and (step) the stored x / ref / t / cost with reward 0 and done = 1
+static __device__ __forceinline__ void serl_venv_write_frozen(const VenvArgs &v, int e, bool step)
+{
+  const serl_venv_desc &d = v.d;
+  const double *S = (const double *)d.state;
+  const int32_t *I = (const int32_t *)(S + SERL_VENV_F64 * v.npad);
+  const int64_t np = v.npad;
+  double err[3], u[3], x[12];
+  for (int i = 0; i < 3; ++i) { err[i] = S[(SERL_VF_ERR + i) * np + e]; u[i] = S[(SERL_VF_LASTU + i) * np + e]; }
+  for (int i = 0; i < 12; ++i) x[i] = S[(SERL_VF_XO + i) * np + e];
+  serl_venv_write_obs(d.env_config, d.incremental != 0, err, x, u, v.obs + (size_t)e * d.state_dim);
+  if (!step) return;
+  v.reward[e] = 0.0;
+  v.done[e] = 1;
+  if (v.x) for (int i = 0; i < 12; ++i) v.x[(size_t)e * 12 + i] = x[i];
+  if (v.ref) for (int i = 0; i < 3; ++i) v.ref[(size_t)e * 3 + i] = S[(SERL_VF_REF + i) * np + e];
+  if (v.t) v.t[e] = S[SERL_VF_T * np + e];
+  if (v.cost) v.cost[e] = I[SERL_VI_COST * np + e];
+}
+
+// the row of pre-drawn sensor noise env e adds to what step() returns at entry j (0: the step of reset(), k + 1: env step k), or nullptr
+static __device__ __forceinline__ const double *serl_venv_sensor(const serl_venv_desc &d, int e, int j)
+{
+  if (!d.sensor_noise) return nullptr;
+  const int sr = d.sensor_row ? d.sensor_row[e] : e;
+  return sr < 0 ? nullptr : d.sensor_noise + ((size_t)sr * ((size_t)d.max_steps + 1) + (size_t)j) * 7;
+}
+#endif  // SERL_VENV_COMMON
+
+// the dynamics state of env e: state buffer <-> a CitCtx in the caller's stack frame
+static __device__ __forceinline__ void VV_NAME(serl_venv_load_ctx_)(const RolloutArgs &a, const VenvArgs &v, int e, CitCtx &ctx)
+{
+  const double *S = (const double *)v.d.state;
+  const int32_t *I = (const int32_t *)(S + SERL_VENV_F64 * v.npad);
+  const int64_t np = v.npad;
+  for (int i = 0; i < 19; ++i) ctx.X[i] = S[(SERL_VF_X + i) * np + e];
+  for (int i = 0; i < 29; ++i) ctx.DW[i] = S[(SERL_VF_DW + i) * np + e];
+  for (int i = 0; i < 4; ++i) ctx.IW[i] = I[(SERL_VI_IW + i) * np + e];
+  for (int i = 0; i < 8; ++i) ctx.hint[i] = (uint32_t)I[(SERL_VI_HINT + i) * np + e];
+  ctx.t = S[SERL_VF_CT * np + e]; ctx.stop_time = S[SERL_VF_CSTOP * np + e];
+  ctx.tick = (uint32_t)I[SERL_VI_TICK * np + e]; ctx.err = I[SERL_VI_CERR * np + e];
+  ctx.ro = a.ro; ctx.t3 = a.t3; ctx.dt = a.dyn_dt; ctx.major = 1;
+  ctx.bslot = 0;      // (SERL_FLAVOUR_LDS == 0 in the lane units: the block signals live in registers)
+}
+
+static __device__ __forceinline__ void VV_NAME(serl_venv_store_ctx_)(const VenvArgs &v, int e, const CitCtx &ctx)
+{
+  double *S = (double *)v.d.state;
+  int32_t *I = (int32_t *)(S + SERL_VENV_F64 * v.npad);
+  const int64_t np = v.npad;
+  for (int i = 0; i < 19; ++i) S[(SERL_VF_X + i) * np + e] = ctx.X[i];
+  for (int i = 0; i < 29; ++i) S[(SERL_VF_DW + i) * np + e] = ctx.DW[i];
+  for (int i = 0; i < 4; ++i) I[(SERL_VI_IW + i) * np + e] = ctx.IW[i];
+  for (int i = 0; i < 8; ++i) I[(SERL_VI_HINT + i) * np + e] = (int32_t)ctx.hint[i];
+  S[SERL_VF_CT * np + e] = ctx.t; S[SERL_VF_CSTOP * np + e] = ctx.stop_time;
+  I[SERL_VI_TICK * np + e] = (int32_t)ctx.tick; I[SERL_VI_CERR * np + e] = ctx.err;
+}
+
+// reset() of the envs in the mask (envs/phlabenv.py:401-428)
+__global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_reset_kernel_)(RolloutArgs a, VenvArgs v)
+{
+  const int e = VV_NAME(serl_stage_and_index_)(a);
+  if (e < 0) return;
+  if (v.mask && !v.mask[e]) { serl_venv_write_frozen(v, e, false); return; }
+  const serl_venv_desc &d = v.d;
+  double *S = (double *)d.state;
+  int32_t *I = (int32_t *)(S + SERL_VENV_F64 * v.npad);
+  const int64_t np = v.npad;
+  const int A = d.action_dim;
+  double err[3], u[3] = {0.0, 0.0, 0.0}, x[12], cmd[10];
+  for (int i = 0; i < 3; ++i) err[i] = S[(SERL_VF_ERR + i) * np + e];      // self.error is never cleared
+  if (d.err0) for (int i = 0; i < 3; ++i) err[i] = i < A ? d.err0[(size_t)e * 3 + i] : 0.0;
+  const uint32_t tick = d.tick0 ? (uint32_t)d.tick0[e] : (uint32_t)I[SERL_VI_TICK * np + e];   // initialize() leaves the clock running
+  serl_fault_row f = {1.0, __longlong_as_double(0x7ff0000000000000LL), __longlong_as_double(0x7ff0000000000000LL),
+                      0.0, 0.0, 0, 0, 0};
+  if (d.faults) f = d.faults[e];
+  CitCtx ctx;
+  cit_reset(&ctx, a.ro, a.t3, a.x0, a.dw0, a.dyn_dt);
+  if (tick) { ctx.tick = tick; ctx.t = (double)ctx.tick * ctx.dt; }
+  ctx.bslot = 0;
+  for (int i = 0; i < 10; ++i) cmd[i] = 0.0;
+  cmd[0] = serl_clip(cmd[0] * f.elev_gain, -f.elev_clip, f.elev_clip);
+  cmd[1] = serl_clip(cmd[1], -f.ail_clip, f.ail_clip);
+  if (f.rudder_jam_on != 0.0) cmd[2] = f.rudder_jam;
+  VV_NAME(cit_step_)(&ctx, cmd, x);
+  if (const double *sn = serl_venv_sensor(d, e, 0)) {
+    x[0] += sn[0]; x[1] += sn[1]; x[2] += sn[2]; x[4] += sn[3]; x[5] += sn[4]; x[6] += sn[5]; x[7] += sn[6];
+  }
+  VV_NAME(serl_venv_store_ctx_)(v, e, ctx);
+  for (int i = 0; i < 3; ++i) {
+    S[(SERL_VF_ERR + i) * np + e] = err[i]; S[(SERL_VF_LASTU + i) * np + e] = 0.0; S[(SERL_VF_REF + i) * np + e] = 0.0;
+  }
+  for (int i = 0; i < 12; ++i) S[(SERL_VF_XO + i) * np + e] = x[i];
+  S[SERL_VF_V0 * np + e] = x[3];
+  S[SERL_VF_T * np + e] = 0.0;
+  I[SERL_VI_K * np + e] = 0;
+  I[SERL_VI_LIVE * np + e] = 1;
+  I[SERL_VI_COST * np + e] = 0;
+  serl_venv_write_obs(d.env_config, d.incremental != 0, err, x, u, v.obs + (size_t)e * d.state_dim);
+}
+
+// step(action) of every env (envs/phlabenv.py:430-482)
+__global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_step_kernel_)(RolloutArgs a, VenvArgs v)
+{
+  const int e = VV_NAME(serl_stage_and_index_)(a);
+  if (e < 0) return;
+  const serl_venv_desc &d = v.d;
+  double *S = (double *)d.state;
+  int32_t *I = (int32_t *)(S + SERL_VENV_F64 * v.npad);
+  const int64_t np = v.npad;
+  if (!I[SERL_VI_LIVE * np + e]) { serl_venv_write_frozen(v, e, true); return; }
+  const double PI = 3.14159265358979323846;
+  const double deg2rad = PI / 180.0, rad2deg = 180.0 / PI;
+  const int cfg = d.env_config, A = d.action_dim;
+  const bool incr = d.incremental != 0;
+  const double bound = (incr ? 25.0 : 10.0) * deg2rad, low = -bound, high = bound;   // rate bound [rad/s] / deflection bound [rad]
+  const double max_theta = 60.0 * deg2rad, max_phi = 75.0 * deg2rad;
+  const double scaler[3] = {6.0 / PI * 1.0, 6.0 / PI * 1.0, 6.0 / PI * 4.0};
+  const double dt = 0.01;
+  double err[3], u[3], x[12], cmd[10];
+  for (int i = 0; i < 3; ++i) { err[i] = S[(SERL_VF_ERR + i) * np + e]; u[i] = S[(SERL_VF_LASTU + i) * np + e]; }
+  const double V0 = S[SERL_VF_V0 * np + e];
+  double t = S[SERL_VF_T * np + e];
+  const int k = I[SERL_VI_K * np + e];
+  // scale_action (envs/phlabenv.py:62-73) without clipping; incremental control integrates the rate (:377-380,446-450)
+  double scl[3] = {0.0, 0.0, 0.0};
+  for (int i = 0; i < 3; ++i) {
+    if (i >= A) continue;
+    if (v.actions_f64) {
+      const double ai = ((const double *)v.actions)[(size_t)e * A + i];
+      scl[i] = low + 0.5 * (ai + 1.0) * (high - low);
+    } else {
+      const float s = 0.5f * (((const float *)v.actions)[(size_t)e * A + i] + 1.0f);
+      scl[i] = low + (double)s * (high - low);
+    }
+  }
+  for (int i = 0; i < 3; ++i) u[i] = incr ? u[i] + scl[i] * dt : scl[i];
+  serl_fault_row f = {1.0, __longlong_as_double(0x7ff0000000000000LL), __longlong_as_double(0x7ff0000000000000LL),
+                      0.0, 0.0, 0, 0, 0};
+  if (d.faults) f = d.faults[e];
+  for (int i = 0; i < 10; ++i) cmd[i] = 0.0;
+  cmd[0] = serl_clip(u[0] * f.elev_gain, -f.elev_clip, f.elev_clip);
+  cmd[1] = serl_clip(u[1], -f.ail_clip, f.ail_clip);
+  cmd[2] = (f.rudder_jam_on != 0.0) ? f.rudder_jam : u[2];
+  CitCtx ctx;
+  VV_NAME(serl_venv_load_ctx_)(a, v, e, ctx);
+  VV_NAME(cit_step_)(&ctx, cmd, x);
+  if (const double *sn = serl_venv_sensor(d, e, k + 1)) {      // k < max_steps: entry k + 1 <= max_steps exists
+    x[0] += sn[0]; x[1] += sn[1]; x[2] += sn[2]; x[4] += sn[3]; x[5] += sn[4]; x[6] += sn[5]; x[7] += sn[6];
+  }
+  double rk[3];
+  if (d.ref_spec) serl_ref_generate(d.ref_spec + (size_t)e * d.ref_spec_stride, t, d.t_max, rk[0], rk[1], rk[2]);   // at the pre-increment t
+  else {
+    const double *r = d.ref + (size_t)e * d.ref_stride + (size_t)k * 3;
+    rk[0] = r[0]; rk[1] = r[1]; rk[2] = r[2];
+  }
+  err[0] = rk[0] - x[7];
+  if (A > 1) { err[1] = rk[1] - x[6]; err[2] = rk[2] - x[5]; }
+  double rsum = 0.0;
+  for (int i = 0; i < 3; ++i) if (i < A) rsum = rsum + fabs(serl_clip(scaler[i] * err[i], -1.0, 1.0));
+  double reward = -rsum / (double)A;
+  const int cost = (rad2deg * fabs(x[4]) > 11.0) || (rad2deg * fabs(x[6]) > 0.75 * max_phi) || (x[3] < V0 / 3.0);
+  const bool fin = (t >= d.t_max) || (fabs(x[7]) > max_theta) || (fabs(x[6]) > max_phi) || (x[9] < 50.0);
+  if (fin) reward += -1.0 / dt * (d.t_max - t) * 2.0;
+  t += dt;
+  const bool done = fin || k + 1 >= d.max_steps;     // (the tables end: the env freezes instead of reading past them)
+  VV_NAME(serl_venv_store_ctx_)(v, e, ctx);
+  for (int i = 0; i < 3; ++i) {
+    S[(SERL_VF_ERR + i) * np + e] = err[i]; S[(SERL_VF_LASTU + i) * np + e] = u[i]; S[(SERL_VF_REF + i) * np + e] = rk[i];
+  }
+  for (int i = 0; i < 12; ++i) S[(SERL_VF_XO + i) * np + e] = x[i];
+  S[SERL_VF_T * np + e] = t;
+  I[SERL_VI_K * np + e] = k + 1;
+  I[SERL_VI_LIVE * np + e] = done ? 0 : 1;
+  I[SERL_VI_COST * np + e] = cost;
+  serl_venv_write_obs(cfg, incr, err, x, u, v.obs + (size_t)e * d.state_dim);
+  v.reward[e] = reward;
+  v.done[e] = done ? 1 : 0;
+  if (v.x) for (int i = 0; i < 12; ++i) v.x[(size_t)e * 12 + i] = x[i];
+  if (v.ref) for (int i = 0; i < 3; ++i) v.ref[(size_t)e * 3 + i] = rk[i];
+  if (v.t) v.t[e] = t;
+  if (v.cost) v.cost[e] = cost;
+}
+
+void VV_NAME(serl_launch_venv_reset_)(const RolloutArgs &a, const VenvArgs &v, int grid, hipStream_t stream)
+{
+  hipLaunchKernelGGL(VV_NAME(serl_venv_reset_kernel_), dim3(grid), dim3(a.block), 0, stream, a, v);
+}
+
+void VV_NAME(serl_launch_venv_step_)(const RolloutArgs &a, const VenvArgs &v, int grid, hipStream_t stream)
+{
+  hipLaunchKernelGGL(VV_NAME(serl_venv_step_kernel_), dim3(grid), dim3(a.block), 0, stream, a, v);
+}
+#undef VV_NAME
+#undef VV_PASTE
+#undef VV_PASTE2
