@@ -132,9 +132,16 @@ def genome_size(spec: NetSpec):
     return sum(n for _, n in spec.genome_segments())
 
 
-def sensitivity(engine, weights, members, spec: NetSpec, states):
+# the network shapes serl_ga_sensitivity / serl_ga_novelty take (serl_ga.hip check_net); within them the only other refusal is LDS
+def _kernel_shape_ok(spec: NetSpec):
+    return 1 <= spec.state_dim <= 64 and 1 <= spec.action_dim <= 16 and 2 <= spec.hidden <= 256 and 0 <= spec.num_layers <= 16
+
+
+def sensitivity(engine, weights, members, spec: NetSpec, states, fallback=True):
     """The clamped output sensitivity of proximal_mutate / safe_mutate (mod_neuro_evo.py:188-217) for several members at
-    once: states f32 [n, B, state_dim] (device) -> scaling f32 [n, G] (device)."""
+    once: states f32 [n, B, state_dim] (device) -> scaling f32 [n, G] (device).  The kernel keeps one output's gradient of the
+    whole genome in LDS; an actor whose genome does not fit there (H = 128 with three hidden layers: ~208 KB) is refused with
+    SERL_E_UNSUPPORTED and, with `fallback`, computed by sensitivity_torch instead (the policy of serl_ga_distill)."""
     dev = weights.device
     members = np.atleast_1d(np.asarray(members, dtype=np.int32))
     states = torch.as_tensor(states, dtype=torch.float32).to(dev).contiguous()
@@ -145,9 +152,53 @@ def sensitivity(engine, weights, members, spec: NetSpec, states):
         return torch.ones(n, G, dtype=torch.float32, device=dev)
     out = torch.empty(n, G, dtype=torch.float32, device=dev)
     m = _i32(dev, members)
-    _capi.check(engine.lib.serl_ga_sensitivity(engine.ctx, weights.data_ptr(), weights.stride(0), *_net_args(spec), m.data_ptr(), n,
-                                               states.data_ptr(), B, out.data_ptr(), _stream(dev)), 'serl_ga_sensitivity')
+    rc = engine.lib.serl_ga_sensitivity(engine.ctx, weights.data_ptr(), weights.stride(0), *_net_args(spec), m.data_ptr(), n,
+                                        states.data_ptr(), B, out.data_ptr(), _stream(dev))
+    if rc == _capi.E_UNSUPPORTED and fallback and _kernel_shape_ok(spec):
+        return sensitivity_torch(weights, members, spec, states)
+    _capi.check(rc, 'serl_ga_sensitivity')
     return out
+
+
+def _actor_forward_torch(spec: NetSpec, row, genome, x):
+    """Actor.forward (genetic_agent.py:104; LayerNorm mod_utils.py:47-50: unbiased std, eps on the std) over a packed row whose 2-D
+    weights are the tensors `genome` (W0, W1 .. WL, Wo)"""
+    S, H, L, A = spec.state_dim, spec.hidden, spec.num_layers, spec.action_dim
+    act = {'tanh': torch.tanh, 'elu': torch.nn.functional.elu,
+           'relu': lambda v: torch.nn.functional.leaky_relu(v, 0.01)}[spec.activation.lower()]
+    off = H * S
+    h = act(x @ genome[0].t() + row[off:off + H])
+    off += H
+    for l in range(L):
+        off += H * H
+        b, g, be = row[off:off + H], row[off + H:off + 2 * H], row[off + 2 * H:off + 3 * H]
+        z = h @ genome[1 + l].t() + b
+        h = act(g * (z - z.mean(-1, keepdim=True)) / (z.std(-1, keepdim=True) + 1e-6) + be)
+        off += 3 * H
+    off += A * H
+    return torch.tanh(h @ genome[-1].t() + row[off:off + A])
+
+
+def sensitivity_torch(weights, members, spec: NetSpec, states):
+    """sensitivity() in PyTorch autograd (f32, on the weights' device), for the shapes the kernel has no room for: per member and action
+    the gradient of sum_b out[b, i] with respect to the 2-D weights, scaling = sqrt(sum_i grad_i^2) with the clamps of
+    mod_neuro_evo.py:213-217.  torch's std backward masks the term of a LayerNorm whose inputs are all equal, as the reference's does."""
+    states = torch.as_tensor(states, dtype=torch.float32).to(weights.device)
+    out = []
+    for k, member in enumerate(np.atleast_1d(members)):
+        row = weights[int(member)].detach()
+        shapes = [(spec.hidden, spec.state_dim)] + [(spec.hidden, spec.hidden)] * spec.num_layers + [(spec.action_dim, spec.hidden)]
+        genome = [row[o:o + n].clone().view(shp).requires_grad_() for (o, n), shp in zip(spec.genome_segments(), shapes)]
+        y = _actor_forward_torch(spec, row, genome, states[k])
+        sq = torch.zeros(sum(n for _, n in spec.genome_segments()), dtype=torch.float32, device=weights.device)
+        for i in range(spec.action_dim):
+            g = torch.autograd.grad(y[:, i].sum(), genome, retain_graph=i + 1 < spec.action_dim)
+            sq += torch.cat([t.reshape(-1) for t in g]) ** 2
+        sc = torch.sqrt(sq)
+        sc[sc == 0] = 1.0
+        sc[sc < 0.01] = 0.01
+        out.append(sc)
+    return torch.stack(out)
 
 
 def draw_delta(spec: NetSpec, mag):

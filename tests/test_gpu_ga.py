@@ -264,3 +264,223 @@ def test_fused_distillation_of_several_pairs(engine, golden):
         a, b = row.cpu().numpy()[:spec.param_count], row2.cpu().numpy()[:spec.param_count]
         assert np.abs(a - w[s].cpu().numpy()[:spec.param_count]).max() > 5e-3
         np.testing.assert_allclose(a, b, rtol=0, atol=3e-4)
+
+
+# ---- serl_ga_sensitivity / serl_ga_novelty against float64 autograd, across the shapes the kernels accept ----------------------------
+def _net(S, A, H, L, act):
+    return dict(state_dim=S, action_dim=A, hidden=H, num_layers=L, activation=act, env_config=0, incremental=False)
+
+
+def _raw_sensitivity64(s, row, states):
+    """the reference's own computation (mod_neuro_evo.py:198-214) in float64 on the reference's Actor: for every action i the gradient of
+    sum_b out[b, i] w.r.t. the 2-D weights in genome order (extract_grad), then sqrt(sum_i g_i^2) -- before the clamps"""
+    import actor_shapes as X
+    from serl_amd.actor import unpack_into
+    m = X.actor_module(s, torch.float64)
+    unpack_into(m, torch.from_numpy(np.asarray(row, dtype=np.float64)))
+    out = m(torch.from_numpy(np.asarray(states, dtype=np.float64)))
+    sq = 0.0
+    for i in range(s['action_dim']):
+        m.zero_grad()
+        go = torch.zeros_like(out)
+        go[:, i] = 1.0
+        out.backward(go, retain_graph=True)
+        sq = sq + m.extract_grad() ** 2
+    return torch.sqrt(sq).numpy()
+
+
+def _clamped(raw):
+    """mod_neuro_evo.py:215-217"""
+    sc = raw.copy()
+    sc[sc == 0] = 1.0
+    sc[sc < 0.01] = 0.01
+    return sc
+
+
+def _novelty64(s, row, states, actions):
+    import actor_shapes as X
+    from serl_amd.actor import unpack_into
+    m = X.actor_module(s, torch.float64)
+    unpack_into(m, torch.from_numpy(np.asarray(row, dtype=np.float64)))
+    with torch.no_grad():
+        out = m(torch.from_numpy(np.asarray(states, dtype=np.float64))).numpy()
+    return float(np.mean(np.sum((np.asarray(actions, np.float64) - out) ** 2, -1)))
+
+
+# Tolerance of the sensitivity: every entry is an f32 sum over the batch of products of an f32 forward and backward pass, accumulated
+# in another order than autograd's; entries whose terms cancel carry an absolute error of the order of the larger entries' rounding.
+# |got - want| <= SENS_RTOL want + SENS_ATOL max(want of the same weight matrix): the f32 autograd path of serl_amd.ga (the same
+# sums in torch's order) stays below 2e-5 relative / 3e-7 of the maximum on these shapes.  Entries whose unclamped value lies within
+# 5 % of the 0.01 clamp are only checked to be clamped to no less than 0.01.  A wrong term in the LayerNorm backward moves entries by tens of percent.
+SENS_RTOL, SENS_ATOL = 2e-4, 1e-5
+NOV_RTOL = 1e-5          # novelty: a mean of B f32 sums of A squares, each difference to f32 rounding of the forward pass
+
+
+def _check_sensitivity(got, raw, what, spec):
+    want = _clamped(raw)
+    near = np.abs(raw - 0.01) < 5e-4
+    err = np.abs(got - want)
+    scale = np.concatenate([np.full(n, want[o:o + n].max()) for o, n in _genome_offsets(spec)])      # per weight matrix
+    bad = (err > SENS_RTOL * want + SENS_ATOL * scale) & ~near
+    assert not bad.any(), '%s: %d entries off, worst at %d: got %r want %r (raw %r)' % (
+        what, bad.sum(), np.argmax(np.where(bad, err, 0)), got[bad][:4], want[bad][:4], raw[bad][:4])
+    np.testing.assert_array_equal(got[raw == 0], 1.0, err_msg=what + ': scaling == 0 -> 1')
+    np.testing.assert_array_equal(got[(raw > 0) & (raw < 0.0095)], np.float32(0.01), err_msg=what + ': scaling < 0.01 -> 0.01')
+    assert (got[near] >= np.float32(0.01)).all(), what
+
+
+def _genome_offsets(spec):
+    """(offset, length) of every 2-D weight inside the genome vector"""
+    out, o = [], 0
+    for _, n in spec.genome_segments():
+        out.append((o, n)); o += n
+    return out
+
+
+# (S, A) of the attitude task, the symmetric / full configurations and full + incremental; hidden sizes below a wavefront, odd, one and
+# more than one wavefront's worth of rows, the 256 the kernels' range ends at; batch sizes 1, 2, SSNE's 86 and 256.  (H = 2 only without
+# hidden layers: a LayerNorm over two values is a sign function whose gradient is eps / sd^2, the difference of two ~1 / sd terms --
+# pure f32 rounding in any implementation.)
+SENS_CASES = [(7, 3, 2, 0, 'tanh', 86), (7, 3, 3, 3, 'elu', 2), (2, 1, 33, 3, 'relu', 86), (13, 3, 64, 1, 'tanh', 256),
+              (16, 3, 65, 3, 'elu', 86), (7, 3, 100, 1, 'relu', 1), (7, 3, 128, 1, 'tanh', 86), (16, 3, 256, 0, 'relu', 86),
+              (2, 1, 256, 0, 'elu', 256), (7, 3, 33, 0, 'tanh', 2), (13, 3, 100, 3, 'tanh', 86), (2, 1, 2, 0, 'relu', 1),
+              (7, 3, 64, 3, 'elu', 256), (16, 3, 3, 1, 'tanh', 86)]
+
+
+@pytest.mark.parametrize('S,A,H,L,act,B', SENS_CASES)
+def test_sensitivity_and_novelty_vs_float64_autograd(engine, S, A, H, L, act, B):
+    """serl_ga_sensitivity (the analytic backward pass through LayerNorm with the unbiased std) and serl_ga_novelty (Actor.get_novelty)
+    for several members in one launch, repeats among them, against float64 autograd on the reference's Actor"""
+    import actor_shapes as X
+    from serl_amd import ga
+    import serl_amd
+    s = _net(S, A, H, L, act)
+    spec = serl_amd.NetSpec(S, A, H, L, act)
+    w = torch.from_numpy(X.make_weights(s, 3, 7 * H + L)).to(engine.device)
+    members = [2, 0, 2, 1]
+    rng = np.random.default_rng(H + 100 * L + B)
+    st = (rng.standard_normal((len(members), B, S)) * rng.uniform(0.2, 2.0, S)).astype(np.float32)
+    acts = rng.uniform(-1, 1, (len(members), B, A)).astype(np.float32)
+    sc = ga.sensitivity(engine, w, members, spec, torch.from_numpy(st), fallback=False).cpu().numpy()
+    nov = ga.novelty(engine, w, members, spec, torch.from_numpy(st), torch.from_numpy(acts)).cpu().numpy()
+    wc = w.cpu().numpy()
+    for k, m in enumerate(members):
+        what = 'S%d A%d H%d L%d %s B%d member %d' % (S, A, H, L, act, B, m)
+        _check_sensitivity(sc[k], _raw_sensitivity64(s, wc[m], st[k]), what, spec)
+        np.testing.assert_allclose(nov[k], _novelty64(s, wc[m], st[k], acts[k]), rtol=NOV_RTOL, err_msg=what)
+
+
+def test_sensitivity_edge_cases_vs_float64_autograd(engine):
+    """a hidden layer whose pre-LayerNorm values are all equal (sd = 0: torch's std backward masks the term, the kernel's `sd > 0`
+    branch), a state column that is zero in every batch row (its W0 entries have no gradient: exactly 1.0 by the `scaling == 0`
+    rule), a column scaled so small that its W0 entries fall under the 0.01 clamp"""
+    import actor_shapes as X
+    from serl_amd import ga
+    import serl_amd
+    for H, L, layer, act in ((32, 3, 1, 'tanh'), (65, 1, 0, 'elu'), (100, 3, 2, 'relu'), (7, 3, 0, 'tanh')):
+        S, A, B = 7, 3, 86
+        s = _net(S, A, H, L, act)
+        spec = serl_amd.NetSpec(S, A, H, L, act)
+        w = X.make_weights(s, 2, 3 + H)
+        off = H * S + H + layer * (H * H + 3 * H)         # hidden layer `layer`: W = 0, one bias for every row -> z constant, sd = 0
+        w[1, off:off + H * H] = 0.0
+        w[1, off + H * H:off + H * H + H] = 0.375
+        rng = np.random.default_rng(H)
+        st = rng.standard_normal((2, B, S)).astype(np.float32)
+        st[:, :, 2] = 0.0                                 # a state column that is zero in every row
+        st[:, :, 5] *= 1e-4                               # a column whose W0 entries fall under the clamp
+        wt = torch.from_numpy(w).to(engine.device)
+        sc = ga.sensitivity(engine, wt, [0, 1], spec, torch.from_numpy(st), fallback=False).cpu().numpy()
+        assert np.isfinite(sc).all()
+        for k in (0, 1):
+            what = 'H%d L%d %s member %d' % (H, L, act, k)
+            raw = _raw_sensitivity64(s, w[k], st[k])
+            assert np.isfinite(raw).all()
+            _check_sensitivity(sc[k], raw, what, spec)
+            w0 = sc[k][:H * S].reshape(H, S)
+            np.testing.assert_array_equal(w0[:, 2], 1.0, err_msg=what)
+            if k == 0:
+                assert (w0[:, 5] == np.float32(0.01)).mean() > 0.5, what
+            else:                                         # nothing flows below a layer whose weights are zero
+                np.testing.assert_array_equal(sc[k][:H * S + layer * H * H], 1.0, err_msg=what)
+        g_off = H * S + layer * H * H                      # the degenerate layer's W in genome order: gradient through the masked std term
+        assert (np.abs(_raw_sensitivity64(s, w[1], st[1])[g_off:g_off + H * H]) > 0.02).any()
+
+
+def _prox_epoch_args(n):
+    return types.SimpleNamespace(pop_size=n, elite_fraction=0.25, mutation_prob=0.9, mutation_mag=MAG, mut_type='proximal',
+                                 distil_crossover=True, distil_type='distance', crossover_prob=0.0, mutation_batch_size=MBS,
+                                 individual_bs=2_000)
+
+
+def test_sensitivity_beyond_the_kernels_lds_vs_float64_autograd(engine, golden):
+    """H = 128 with three hidden layers: the rollout accepts the actor, but one output's gradient of its genome (50 432 floats) and
+    the forward buffers need ~208 KB of LDS -- serl_ga_sensitivity refuses the shape (SERL_E_UNSUPPORTED) and ga.sensitivity
+    computes it in PyTorch.  Both paths against float64 autograd: the PyTorch path on that shape (mixed batch sizes through
+    ProximalBatch, as an SSNE epoch applies them), the kernel's refusal itself."""
+    import actor_shapes as X
+    from serl_amd import ga, _capi
+    import serl_amd
+    for H, L, act in ((128, 3, 'tanh'), (124, 4, 'relu')):
+        s = _net(7, 3, H, L, act)
+        spec = serl_amd.NetSpec(7, 3, H, L, act)
+        w = torch.from_numpy(X.make_weights(s, 3, 11)).to(engine.device)
+        st = torch.from_numpy(np.random.default_rng(1).standard_normal((2, 86, 7)).astype(np.float32))
+        with pytest.raises(RuntimeError, match=r'serl_ga_sensitivity failed \(%d\)' % _capi.E_UNSUPPORTED):
+            ga.sensitivity(engine, w, [0, 2], spec, st, fallback=False)
+        sc = ga.sensitivity(engine, w, [0, 2], spec, st).cpu().numpy()
+        for k, m in enumerate((0, 2)):
+            _check_sensitivity(sc[k], _raw_sensitivity64(s, w[m].cpu().numpy(), st[k].numpy()), 'H%d L%d member %d' % (H, L, m), spec)
+    # ProximalBatch with buffers of different fill (one sensitivity call per batch size): every row moved by delta / scaling
+    from serl_amd.replay import DeviceReplay
+    g = golden('proximal')
+    spec = serl_amd.NetSpec(7, 3, 128, 3, 'tanh')
+    w = torch.from_numpy(X.make_weights(_net(7, 3, 128, 3, 'tanh'), 3, 12)).to(engine.device)
+    w0 = w.cpu().numpy().copy()
+    rings = []
+    for n_rows in (40, 200, 30):
+        r = DeviceReplay(10_000, engine.device, engine)
+        r.append_rows(torch.from_numpy(g['buf_serl50_18'][:n_rows]))
+        rings.append(r)
+    random.seed(4); torch.manual_seed(4)
+    batch = ga.ProximalBatch(engine, w, spec, MAG, MBS)
+    for m in (0, 1, 2):
+        batch.add(m, rings[m])
+    items = [(m, st.clone(), d.clone()) for m, st, d in batch.items]
+    batch.apply()
+    torch.cuda.synchronize()
+    s = _net(7, 3, 128, 3, 'tanh')
+    for m, st, delta in items:
+        assert st.shape[0] == min(MBS, len(rings[m]))
+        want = _clamped(_raw_sensitivity64(s, w0[m], st.cpu().numpy()))
+        got = _genome(w[m].cpu().numpy(), spec) - _genome(w0[m], spec)
+        np.testing.assert_allclose(got, delta.numpy() / want, rtol=1e-3, atol=2e-6, err_msg='member %d' % m)
+
+
+def test_proximal_epoch_at_hidden_128_three_layers(engine, golden):
+    """the default SSNE configuration (proximal mutation) on a population of H = 128, L = 3 actors -- a shape the rollout accepts and
+    whose sensitivity does not fit the kernel's LDS: one epoch completes, mutates members, and leaves every weight finite"""
+    import actor_shapes as X
+    from serl_amd import ssne
+    import serl_amd
+    spec = serl_amd.NetSpec(7, 3, 128, 3, 'tanh')
+    g = golden('proximal')
+    n = 6
+    w0 = X.make_weights(_net(7, 3, 128, 3, 'tanh'), n, 21)
+    w = torch.from_numpy(w0.copy()).to(engine.device)
+    keys = ['serl50_18', 'serl50_0', 'serl50_7']
+    rings = [_rings(engine, g, keys[i % 3]) for i in range(n)]
+    torch.manual_seed(0)
+    critic = _Critic().to(engine.device)
+    fit = np.random.default_rng(5).normal(-150, 50, n)
+    rec = []
+    random.seed(3); np.random.seed(3); torch.manual_seed(3)
+    s = ssne.SSNE(_prox_epoch_args(n), engine, spec, critic=critic, record=rec)
+    s.epoch(w, fit, buffers=[r[0] for r in rings], critical=[r[1] for r in rings])
+    torch.cuda.synchronize()
+    out = w.cpu().numpy()
+    assert np.isfinite(out).all()
+    mutated = sorted({r[1] for r in rec if r[0] == 2})
+    assert mutated, 'the epoch should mutate some member'
+    for m in mutated:
+        assert np.abs(out[m] - w0[m]).max() > 0, m
