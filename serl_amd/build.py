@@ -10,15 +10,15 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(CSRC, 'libserl_amd.so')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-UNITS = ['serl_capi.hip', 'serl_ga.hip', 'serl_metrics.hip', 'serl_distill.hip', 'rollout_nominal.hip', 'rollout_ice.hip', 'rollout_cg_timed.hip', 'rollout_gust.hip', 'rollout_test.hip', 'rollout_wave_nominal.hip', 'rollout_wave_ice.hip',
-         'rollout_wave_cg_timed.hip', 'rollout_wave_gust.hip', 'rollout_wave_test.hip', 'rollout_team_nominal.hip',
-         'rollout_team_ice.hip', 'rollout_team_cg_timed.hip', 'rollout_team_gust.hip', 'rollout_team_test.hip',
-         'rollout_team2_nominal.hip', 'rollout_team2_ice.hip', 'rollout_team2_cg_timed.hip', 'rollout_team2_gust.hip', 'rollout_team2_test.hip',
-         'rollout_team4_mixed.hip', 'rollout_team4_nominal.hip', 'rollout_team4_ice.hip', 'rollout_team4_cg_timed.hip', 'rollout_team4_gust.hip', 'rollout_team4_test.hip',
-         'rollout_teams2_nominal.hip', 'rollout_teams2_ice.hip', 'rollout_teams2_cg_timed.hip', 'rollout_teams2_gust.hip', 'rollout_teams2_test.hip',
-         'rollout_teamr_nominal.hip', 'rollout_teamr_ice.hip', 'rollout_teamr_cg_timed.hip', 'rollout_teamr_gust.hip', 'rollout_teamr_test.hip',
-         'rollout_team2s_nominal.hip', 'rollout_team2s_ice.hip', 'rollout_team2s_cg_timed.hip', 'rollout_team2s_gust.hip', 'rollout_team2s_test.hip',
-         'rollout_half_nominal.hip', 'rollout_half_ice.hip', 'rollout_half_cg_timed.hip', 'rollout_half_gust.hip', 'rollout_half_test.hip']
+# index = serl_dyn_code (include/serl_amd.h): csrc/serl_variant.h turns -DSERL_DYN=<code> into the variant's names and generated files
+VARIANTS = ['nominal', 'ice', 'cg_timed', 'gust', 'test']
+# kernel families: csrc/family_<f>.hip, compiled once per code variant into build/rollout_<f>_<variant>.o (the lane family: rollout_<variant>.o)
+FAMILIES = ['lane', 'wave', 'half', 'team', 'teamr', 'teams2', 'team2', 'team2s', 'team4']
+# object stem -> (source, defines)
+UNITS = {s: (s + '.hip', []) for s in ('serl_capi', 'serl_ga', 'serl_metrics', 'serl_distill')}
+UNITS.update({('rollout_' if f == 'lane' else 'rollout_%s_' % f) + v: ('family_%s.hip' % f, ['-DSERL_DYN=%d' % code])
+              for f in FAMILIES for code, v in enumerate(VARIANTS)})
+UNITS['rollout_team4_mixed'] = ('rollout_team4_mixed.hip', [])      # (two code variants in one code object)
 # -ffp-contract=off: the IEEE-754 operation order of the reference binary is part of the contract (no FMA fusion).
 # -disable-machine-licm: the model evaluation is inlined into the ODE5 stage loop; hoisting its ~110 f64 literals
 # out of the loop (2 SGPRs each) makes them spill -- rematerialising them at use is cheaper.
@@ -50,32 +50,57 @@ def source_hash():
     return h.hexdigest()
 
 
-def build(force=False, verbose=False, extra_flags=(), lib=None, tag=''):
-    """extra_flags / lib / tag build a variant next to the product library (e.g. the phase-profiling build:
-    extra_flags=['-DCITW_PROFILE'], lib='libserl_amd_prof.so', tag='_prof')."""
-    LIB = os.path.join(CSRC, lib) if lib else globals()['LIB']
-    if not force and os.path.exists(LIB) and all(os.path.getmtime(LIB) >= os.path.getmtime(d) for d in _deps()):
-        return LIB
-    objdir = os.path.join(CSRC, 'build')
-    os.makedirs(objdir, exist_ok=True)
+def unit_stem(unit):
+    """The object stem of a unit named by its stem or, as before the family sources, by '<stem>.hip' (e.g. 'rollout_team4_nominal.hip': build/rollout_team4_nominal.o, family_team4.hip with -DSERL_DYN=0)."""
+    stem = unit[:-4] if unit.endswith('.hip') else unit
+    if stem not in UNITS:
+        raise KeyError('unknown unit %r (one of: %s)' % (unit, ', '.join(UNITS)))
+    return stem
+
+
+def compile_argv(unit, out, extra_flags=(), flags=None):
+    """The hipcc command line that compiles `unit` (unit_stem) into `out`: the product's FLAGS (or `flags`), the unit's defines, `extra_flags`."""
+    src, defines = UNITS[unit_stem(unit)]
+    return [HIPCC] + list(FLAGS if flags is None else flags) + defines + list(extra_flags) + ['-c', os.path.join(CSRC, src), '-o', out]
+
+
+def obj_path(unit, tag=''):
+    return os.path.join(CSRC, 'build', unit_stem(unit) + tag + '.o')
+
+
+def _compile(units, tag, extra_flags, verbose=False):
+    os.makedirs(os.path.join(CSRC, 'build'), exist_ok=True)
 
     def cc(unit):
-        obj = os.path.join(objdir, unit.replace('.hip', tag + '.o'))
-        cmd = [HIPCC] + FLAGS + list(extra_flags) + ['-c', os.path.join(CSRC, unit), '-o', obj]
-        r = subprocess.run(cmd, capture_output=True, text=True)
+        obj = obj_path(unit, tag)
+        r = subprocess.run(compile_argv(unit, obj, extra_flags), capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError('hipcc failed for %s:\n%s' % (unit, r.stderr[-4000:]))
         if verbose and r.stderr:
             print(r.stderr, file=sys.stderr)
         return obj
+    with ThreadPoolExecutor(max_workers=min(len(units), max(4, 4 * (os.cpu_count() or 8)))) as ex:      # (hipcc spends most of its time waiting on its own sub-processes)
+        return list(ex.map(cc, units))
 
-    with ThreadPoolExecutor(max_workers=min(len(UNITS), max(4, 4 * (os.cpu_count() or 8)))) as ex:      # (hipcc spends most of its time waiting on its own sub-processes)
-        objs = list(ex.map(cc, UNITS))
-    r = subprocess.run([HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', LIB] + objs,
-                       capture_output=True, text=True)
+
+def link(path, objs):
+    r = subprocess.run([HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', path] + list(objs), capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError('link failed:\n' + r.stderr[-4000:])
-    return LIB
+    return path
+
+
+def _fresh(path, deps):
+    return os.path.exists(path) and all(os.path.getmtime(path) >= os.path.getmtime(d) for d in deps)
+
+
+def build(force=False, verbose=False, extra_flags=(), lib=None, tag=''):
+    """extra_flags / lib / tag build a variant next to the product library (e.g. the phase-profiling build:
+    extra_flags=['-DCITW_PROFILE'], lib='libserl_amd_prof.so', tag='_prof')."""
+    path = os.path.join(CSRC, lib) if lib else LIB
+    if not force and _fresh(path, _deps()):
+        return path
+    return link(path, _compile(list(UNITS), tag, extra_flags, verbose))
 
 
 JITTER_LIB = 'libserl_amd_jitter.so'
@@ -87,23 +112,10 @@ def build_variant(lib, tag, extra_flags, units, force=False):
     product's own."""
     build()
     path = os.path.join(CSRC, lib)
-    if not force and os.path.exists(path) and all(os.path.getmtime(path) >= os.path.getmtime(d) for d in _deps() + [LIB]):
+    if not force and _fresh(path, _deps() + [LIB]):
         return path
-    objdir = os.path.join(CSRC, 'build')
-
-    def cc(unit):
-        obj = os.path.join(objdir, unit.replace('.hip', tag + '.o'))
-        r = subprocess.run([HIPCC] + FLAGS + list(extra_flags) + ['-c', os.path.join(CSRC, unit), '-o', obj], capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError('hipcc failed for %s:\n%s' % (unit, r.stderr[-4000:]))
-        return obj
-    with ThreadPoolExecutor(max_workers=min(len(units), max(4, 4 * (os.cpu_count() or 8)))) as ex:
-        mine = list(ex.map(cc, units))
-    objs = mine + [os.path.join(objdir, u.replace('.hip', '.o')) for u in UNITS if u not in units]
-    r = subprocess.run([HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', path] + objs, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError('link failed:\n' + r.stderr[-4000:])
-    return path
+    units = [unit_stem(u) for u in units]
+    return link(path, _compile(units, tag, extra_flags) + [obj_path(u) for u in UNITS if u not in units])
 
 
 def build_jitter(force=False):

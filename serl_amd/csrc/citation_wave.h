@@ -265,7 +265,7 @@ __shared__ alignas(64) double g_y[32 * CITW_GROUPS];   // team kernels: values t
 // Phase profile of the model evaluation (profiling builds only, -DCITW_PROFILE): shader-clock cycles of wave 0 of
 // workgroup 0 between the CITW_T marks of the generated code, accumulated in LDS and copied out by the kernel.
 #ifdef CITW_PROFILE
-// (the marks of role r fire on the hardware wavefront that RUNS role r -- rollout_team_<v>.hip maps roles to wavefronts; units without a map: role = wavefront)
+// (the marks of role r fire on the hardware wavefront that RUNS role r -- family_team.hip maps roles to wavefronts; units without a map: role = wavefront)
 #ifdef CITW_PROF_TEAM_ROLES      // (one-episode team units: rollout_team.inc defines the map; wavefront 7 is the actor)
 static __device__ __forceinline__ int serl_team_role(const bool stream);
 #define CITW_PROF_ROLE() ((threadIdx.x >> 6) < 7 ? serl_team_role(false) : 8)

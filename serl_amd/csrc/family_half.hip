@@ -1,4 +1,4 @@
-// rollout_half_test.hip -- two episodes per wavefront (rollout_half.inc) for the 'test' dynamics code variant: the
+// family_half.hip -- two episodes per wavefront (rollout_half.inc) for one dynamics code variant (serl_variant.h): the
 // regime beyond one wavefront per SIMD (more than 4 x CUs episodes per launch), SERL50 actor shape (H = 32).
 #define CITW_GROUP_LANES 32
 #define CITW_MAX_WAVES 8          // LDS rows: 4 wavefronts x 2 episodes
@@ -6,7 +6,6 @@
 #define CITW_INV_SLOTS 8
 #include "citation_wave.h"
 #include "rollout_device.h"
-#include "gen/citation_test_wave.inc"
-#define VARIANT test
+#include "serl_variant.h"
+#include SERL_GEN_WAVE
 #include "rollout_half.inc"
-#undef VARIANT

@@ -1,8 +1,6 @@
-// rollout_teamr_gust.hip -- REMOTE-ACTOR team kernel (round 6: the seven team wavefronts + a courier on one CU, the episode's two actor wavefronts in a workgroup of their own on another; rollout_team.inc SERL_TEAM_REMOTE) for the 'gust' dynamics code variant
-// (rollout_team.inc, gen/citation_gust_team.inc): the latency-bound regime, fewer episodes than CUs.
+// family_team.hip -- team (seven wavefronts + the actor wavefront per episode) rollout kernels for one dynamics code variant (serl_variant.h)
+// (rollout_team.inc, gen/citation_<variant>_team.inc): the latency-bound regime, fewer episodes than CUs.
 #define CITW_SEARCH_BATCH 1
-#define SERL_ACTOR_WAVES 2          // (the LDS rows and flags of a forward pass shared by several wavefronts: rollout_team.inc)
-#define SERL_TEAM_REMOTE 1
 #define CITW_MAX_WAVES 1          // one episode per workgroup: the team shares row 0 of every blackboard ...
 #ifndef CITW_M_ROWS
 #define CITW_M_ROWS 8             // ... except the libm results: one row per wavefront of the team
@@ -28,18 +26,17 @@
 #endif
 // Round 5: the LDS-actor kernel keeps every role's f64 literals -- the glue's, the coefficients of the short sincos / pow bodies, the actor's
 // activation polynomial -- in registers for the episode (citation_wave.h CITW_K, citation_libm.h CITW_LK, rollout_device.h DET_K): 143 -> 235 of
-// the 256 VGPRs two wavefronts per SIMD allow, 9 481 -> 8 747 static instructions (nominal).
+// the 256 VGPRs two wavefronts per SIMD allow, 9 481 -> 8 747 static instructions (SERL_DYN=0).
 #define CITW_PROF_TEAM_ROLES 1      // profiling builds: the marks of role r fire on the hardware wavefront that runs it (citation_wave.h CITW_PROF_IS)
 #ifndef SERL_TEAM_KREGS
 #define SERL_TEAM_KREGS 1
 #endif
 #include "citation_wave.h"
 #include "rollout_device.h"
-#include "gen/citation_gust_wave.inc"   // look-up descriptor tables (shared with the one-wave kernels)
+#include "serl_variant.h"
+#include SERL_GEN_WAVE   // look-up descriptor tables (shared with the one-wave kernels)
 #ifndef CITW_TEAM_INC
-#define CITW_TEAM_INC "gen/citation_gust_team.inc"
+#define CITW_TEAM_INC SERL_GEN_TEAM
 #endif
 #include CITW_TEAM_INC
-#define VARIANT gust
 #include "rollout_team.inc"
-#undef VARIANT

@@ -1,5 +1,5 @@
-// rollout_team2_nominal.hip -- two episodes per team (rollout_team.inc + rollout_team_half.inc, lane groups of 32) for the 'nominal'
-// dynamics code variant: between CUs and 4 x CUs episodes per launch, SERL50 actor shape (H = 32).
+// family_team2.hip -- two episodes per team (rollout_team.inc + rollout_team_half.inc, lane groups of 32) for one dynamics code
+// variant (serl_variant.h): between CUs and 4 x CUs episodes per launch, SERL50 actor shape (H = 32).
 #define CITW_SEARCH_BATCH 1
 #define CITW_GROUP_LANES 32
 #define CITW_MAX_WAVES 2          // blackboard rows: one per episode of the team
@@ -9,11 +9,10 @@
 #define SERL_NO_CHUNKED_ACTOR 1      // (these kernels carry H = 32 actors only: serl_capi.hip)
 #include "citation_wave.h"
 #include "rollout_device.h"
-#include "gen/citation_nominal_wave.inc"   // look-up descriptor tables (shared with the one-wave kernels)
+#include "serl_variant.h"
+#include SERL_GEN_WAVE   // look-up descriptor tables (shared with the one-wave kernels)
 #ifndef CITW_TEAM_INC
-#define CITW_TEAM_INC "gen/citation_nominal_teamg.inc"      // (tools/exp_build.py: A/B builds around another generated file)
+#define CITW_TEAM_INC SERL_GEN_TEAMG      // (tools/exp_build.py: A/B builds around another generated file)
 #endif
 #include CITW_TEAM_INC
-#define VARIANT nominal
 #include "rollout_team.inc"
-#undef VARIANT

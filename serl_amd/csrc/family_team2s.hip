@@ -1,5 +1,5 @@
-// rollout_team2s_ice.hip -- two episodes per team for actors that STREAM their weights (hidden != 32: SERL10's 72, the TD3 actor's
-// 96), 'ice' dynamics code variant: a team of SIX wavefronts (gen/citation_ice_team6.inc) carries the two episodes in lane
+// family_team2s.hip -- two episodes per team for actors that STREAM their weights (hidden != 32: SERL10's 72, the TD3 actor's
+// 96), one dynamics code variant (serl_variant.h): a team of SIX wavefronts (gen/citation_<variant>_team6.inc) carries the two episodes in lane
 // groups of 32, TWO actor wavefronts run one episode's forward pass each (rollout_team.inc + rollout_team_half.inc).
 #define CITW_SEARCH_BATCH 1
 #define CITW_GROUP_LANES 32
@@ -11,8 +11,7 @@
 #define SERL_TEAMG_TAG team2s_
 #include "citation_wave.h"
 #include "rollout_device.h"
-#include "gen/citation_ice_wave.inc"   // look-up descriptor tables (shared with the one-wave kernels)
-#include "gen/citation_ice_team6.inc"
-#define VARIANT ice
+#include "serl_variant.h"
+#include SERL_GEN_WAVE   // look-up descriptor tables (shared with the one-wave kernels)
+#include SERL_GEN_TEAM6
 #include "rollout_team.inc"
-#undef VARIANT

@@ -1,5 +1,5 @@
-// rollout_teams2_gust.hip -- one episode per team for actors that STREAM their weights (hidden > 64: SERL10's 72, the TD3 actor's 96), 'gust'
-// dynamics code variant: a team of SIX wavefronts (gen/citation_gust_team6.inc) integrates the model, TWO actor wavefronts share ONE forward
+// family_teams2.hip -- one episode per team for actors that STREAM their weights (hidden > 64: SERL10's 72, the TD3 actor's 96), one dynamics
+// code variant (serl_variant.h): a team of SIX wavefronts (gen/citation_<variant>_team6.inc) integrates the model, TWO actor wavefronts share ONE forward
 // pass beside it -- each owns half of every layer's rows (rollout_device.h: serl_actor_forward_split; rollout_team.inc).
 #define CITW_SEARCH_BATCH 1
 #define CITW_MAX_WAVES 1          // one episode per workgroup: the team shares row 0 of every blackboard ...
@@ -9,8 +9,7 @@
 #define SERL_ACTOR_WAVES 2
 #include "citation_wave.h"
 #include "rollout_device.h"
-#include "gen/citation_gust_wave.inc"   // look-up descriptor tables (shared with the one-wave kernels)
-#include "gen/citation_gust_team6.inc"
-#define VARIANT gust
+#include "serl_variant.h"
+#include SERL_GEN_WAVE   // look-up descriptor tables (shared with the one-wave kernels)
+#include SERL_GEN_TEAM6
 #include "rollout_team.inc"
-#undef VARIANT

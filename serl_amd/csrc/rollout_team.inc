@@ -87,7 +87,7 @@ __shared__ alignas(64) unsigned g_aflagw[4];                  // ... one per act
 #define SERL_TEAM_ROLES {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}
 #endif
 #ifndef SERL_TEAMS_ROLES
-#define SERL_TEAMS_ROLES SERL_TEAM_ROLES      // the map of the kernels whose actor wavefront streams its weights (a busy neighbour: rollout_team_<v>.hip)
+#define SERL_TEAMS_ROLES SERL_TEAM_ROLES      // the map of the kernels whose actor wavefront streams its weights (a busy neighbour: family_team.hip)
 #endif
 // (the map is a nibble per hardware wavefront in one 32-bit literal: readfirstlane + four scalar instructions where a chain of selects
 // over the array took sixteen -- and a team wavefront asks eight times per env step)
@@ -114,7 +114,7 @@ static __device__ __forceinline__ double serl_readlane_f64(double v, int srclane
 }
 #endif      // SERL_TEAM_INC_ONCE
 #if CITW_GROUP_LANES != 64
-#ifdef SERL_TEAMG_TAG      // (rollout_team2s_<variant>.hip: six team wavefronts + two actor wavefronts)
+#ifdef SERL_TEAMG_TAG      // (family_team2s.hip: six team wavefronts + two actor wavefronts)
 #define W_TEAMG(x) W_PASTE(W_PASTE(x, SERL_TEAMG_TAG), VARIANT)
 #elif CITW_GROUP_LANES == 32
 #define W_TEAMG(x) W_PASTE(W_PASTE(x, team2_), VARIANT)
@@ -170,7 +170,7 @@ static __device__ __forceinline__ void W_NAME(citw_team_integrate_)(const int wv
   CITW_WAVE_FENCE();      // lane 0 stored, every lane of this wavefront loads (citation_wave.h)
   // what does not change over the six evaluations; every wavefront of the team computes it into its own LDS rows
   W_PASTE(W_PASTE(citw_, VARIANT), _step_invariants)(W_ROLE(), 0);
-#ifdef CITW_ROLE_PRIO_MASK      // a static issue priority for roles that make no libm calls for the team (rollout_team_<v>.hip)
+#ifdef CITW_ROLE_PRIO_MASK      // a static issue priority for roles that make no libm calls for the team (family_team.hip)
   if ((CITW_ROLE_PRIO_MASK >> W_ROLE()) & 1) __builtin_amdgcn_s_setprio(1);
 #endif
 #pragma nounroll

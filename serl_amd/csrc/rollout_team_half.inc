@@ -26,7 +26,7 @@
 // ACTORS THAT DO NOT HAVE ONE HIDDEN ROW PER LANE (hidden != 32: SERL10's 72, the TD3 actor's 96): the actor wavefront runs the
 // episodes' forward passes one after the other with the streaming forward of the one-episode kernels
 // (serl_actor_forward), paying the step's barriers in proportion -- two passes of H = 72 take longer than the team's step (measured:
-// 40.6 us per env step for the pair).  The kernels for these shapes (rollout_team2s_<variant>.hip, SERL_ACTOR_WAVES = 2) therefore
+// 40.6 us per env step for the pair).  The kernels for these shapes (family_team2s.hip, SERL_ACTOR_WAVES = 2) therefore
 // run a team of SIX wavefronts (gen/citation_<v>_team6.inc) and TWO actor wavefronts, one per episode: eight wavefronts as before,
 // the two forward passes side by side.
 
@@ -42,7 +42,7 @@ static __device__ __forceinline__ void W_NAME(serl_teamg_actor_wave_)(const Roll
   const serl_rollout_desc &d = a.d;
   const int lane = threadIdx.x & 63, grp = lane / CITW_GROUP_LANES, gl = lane % CITW_GROUP_LANES;
   // one hidden row (two at 16 lanes) per lane: hidden == 32, the only shape serl_capi.hip launches the one-actor-wavefront units with (serl_use_teamg; the streamed
-  // shapes run rollout_team2s_<v>.hip, SERL_ACTOR_WAVES = 2, and only those).  A compile-time fact: the other forward pass -- 15.8 KB of the four-per-team kernel's
+  // shapes run family_team2s.hip, SERL_ACTOR_WAVES = 2, and only those).  A compile-time fact: the other forward pass -- 15.8 KB of the four-per-team kernel's
   // 82.5 KB, in the middle of the actor wavefront's loop -- is not compiled into a kernel that never runs it (the 64 KB instruction cache is shared by two CUs)
 #ifdef SERL_TEAMG_ROWS32_RUNTIME      // (A/B builds: the round-5 code, both forward passes in every kernel)
   const bool rows32 = __builtin_amdgcn_readfirstlane(d.hidden) == 32;

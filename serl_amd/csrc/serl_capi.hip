@@ -14,101 +14,59 @@ static thread_local std::string g_err;
 int serl_fail(int code, const std::string &msg) { g_err = msg; return code; }
 static int fail(int code, const std::string &msg) { return serl_fail(code, msg); }
 
-#define SERL_LANE_DECL(v) \
-  void serl_launch_rollout_##v(const RolloutArgs &a, int grid, hipStream_t stream); \
-  void serl_launch_dyn_##v(const RolloutArgs &a, const double *cmds, double *states, int T, int grid, hipStream_t stream);
-SERL_LANE_DECL(nominal) SERL_LANE_DECL(ice) SERL_LANE_DECL(cg_timed) SERL_LANE_DECL(gust) SERL_LANE_DECL(test)
-#undef SERL_LANE_DECL
-// the lane-per-episode kernels (rollout_<variant>.hip: one episode per lane around the branch-free DAG evaluation), one unit per code variant
-static void serl_launch_rollout_lane(int code, const RolloutArgs &a, int grid, hipStream_t stream)
+// The kernel families, each compiled once per dynamics code variant (serl_amd/build.py: csrc/family_<f>.hip with -DSERL_DYN=<code>), and the launcher
+// every unit exports for its variant v.  X(type, member of SerlLaunchers, function of variant v):
+typedef void SerlLaunch(const RolloutArgs &a, int grid, hipStream_t stream);
+typedef void SerlLaunchDyn(const RolloutArgs &a, const double *cmds, double *states, int T, int grid, hipStream_t stream);
+typedef void SerlLaunchVenv(const RolloutArgs &a, const VenvArgs &v, int grid, hipStream_t stream);
+#define SERL_LAUNCHERS(X, v)                                                                                                                     \
+  X(SerlLaunch, lane, serl_launch_rollout_##v)              /* one episode per lane (family_lane.hip, rollout_variant.inc) */                   \
+  X(SerlLaunchDyn, dyn_lane, serl_launch_dyn_##v)                                                                                                \
+  X(SerlLaunchVenv, venv_reset, serl_launch_venv_reset_##v) /* the step-wise vector env, one lane per env (venv_variant.inc) */                  \
+  X(SerlLaunchVenv, venv_step, serl_launch_venv_step_##v)                                                                                        \
+  X(SerlLaunch, wave, serl_launch_rollout_wave_##v)         /* one wavefront per episode (rollout_wave.inc) ... */                               \
+  X(SerlLaunch, wavex, serl_launch_rollout_wavex_##v)       /* ... env configurations other than the attitude task */                           \
+  X(SerlLaunchDyn, dyn_wave, serl_launch_dyn_wave_##v)                                                                                           \
+  X(SerlLaunch, team, serl_launch_rollout_team_##v)         /* a team of wavefronts per episode (rollout_team.inc: 7 + the actor wavefront) */  \
+  X(SerlLaunch, teamx, serl_launch_rollout_teamx_##v)       /* ... other env configurations */                                                  \
+  X(SerlLaunch, teams, serl_launch_rollout_teams_##v)       /* ... the actor wavefront streams its weights */                                   \
+  X(SerlLaunchDyn, dyn_team, serl_launch_dyn_team_##v)                                                                                           \
+  X(SerlLaunch, teams2, serl_launch_rollout_teams2_##v)     /* ... one forward pass over two actor wavefronts (family_teams2.hip) */            \
+  X(SerlLaunch, teamr, serl_launch_rollout_teamr_##v)       /* ... the actor in a workgroup of its own (family_teamr.hip) */                    \
+  X(SerlLaunch, half, serl_launch_rollout_half_##v)         /* two episodes per wavefront (rollout_half.inc) */                                 \
+  X(SerlLaunch, team2, serl_launch_rollout_team2_##v)       /* two / four episodes per team (rollout_team_half.inc) */                          \
+  X(SerlLaunch, team2s, serl_launch_rollout_team2s_##v)                                                                                          \
+  X(SerlLaunch, team4, serl_launch_rollout_team4_##v)
+#define SERL_MEMBER(T, m, fn) T *m;
+#define SERL_DECL(T, m, fn) T fn;
+#define SERL_INIT(T, m, fn) fn,
+struct SerlLaunchers { SERL_LAUNCHERS(SERL_MEMBER, v) };
+// one record per code variant, row = serl_dyn_code (include/serl_amd.h)
+#define SERL_VARIANTS(X) X(nominal, SERL_DYN_NOMINAL) X(ice, SERL_DYN_ICE) X(cg_timed, SERL_DYN_CG_TIMED) X(gust, SERL_DYN_GUST) X(test, SERL_DYN_TEST)
+#define SERL_VARIANT_DECL(v, code) SERL_LAUNCHERS(SERL_DECL, v)
+#define SERL_VARIANT_ROW(v, code) {SERL_LAUNCHERS(SERL_INIT, v)},
+#define SERL_VARIANT_CODE(v, code) code,
+SERL_VARIANTS(SERL_VARIANT_DECL)
+static const SerlLaunchers k_launchers[] = {SERL_VARIANTS(SERL_VARIANT_ROW)};
+static constexpr int k_launcher_code[] = {SERL_VARIANTS(SERL_VARIANT_CODE)};
+static constexpr int SERL_N_VARIANTS = (int)(sizeof k_launcher_code / sizeof k_launcher_code[0]);
+static constexpr bool serl_rows_in_code_order()
 {
-  switch (code) {
-    case SERL_DYN_ICE: serl_launch_rollout_ice(a, grid, stream); break;
-    case SERL_DYN_CG_TIMED: serl_launch_rollout_cg_timed(a, grid, stream); break;
-    case SERL_DYN_GUST: serl_launch_rollout_gust(a, grid, stream); break;
-    case SERL_DYN_TEST: serl_launch_rollout_test(a, grid, stream); break;
-    default: serl_launch_rollout_nominal(a, grid, stream); break;
-  }
+  for (int i = 0; i < SERL_N_VARIANTS; ++i)
+    if (k_launcher_code[i] != i) return false;
+  return true;
 }
-static void serl_launch_dyn_lane(int code, const RolloutArgs &a, const double *cmds, double *states, int T, int grid, hipStream_t stream)
-{
-  switch (code) {
-    case SERL_DYN_ICE: serl_launch_dyn_ice(a, cmds, states, T, grid, stream); break;
-    case SERL_DYN_CG_TIMED: serl_launch_dyn_cg_timed(a, cmds, states, T, grid, stream); break;
-    case SERL_DYN_GUST: serl_launch_dyn_gust(a, cmds, states, T, grid, stream); break;
-    case SERL_DYN_TEST: serl_launch_dyn_test(a, cmds, states, T, grid, stream); break;
-    default: serl_launch_dyn_nominal(a, cmds, states, T, grid, stream); break;
-  }
-}
-// the step-wise vector env (venv_variant.inc, behind the lane kernels of rollout_<variant>.hip): one lane = one env
-#define SERL_VENV_DECL(v) \
-  void serl_launch_venv_reset_##v(const RolloutArgs &a, const VenvArgs &v_, int grid, hipStream_t stream); \
-  void serl_launch_venv_step_##v(const RolloutArgs &a, const VenvArgs &v_, int grid, hipStream_t stream);
-SERL_VENV_DECL(nominal) SERL_VENV_DECL(ice) SERL_VENV_DECL(cg_timed) SERL_VENV_DECL(gust) SERL_VENV_DECL(test)
-#undef SERL_VENV_DECL
-static void serl_launch_venv(int code, bool step, const RolloutArgs &a, const VenvArgs &v, int grid, hipStream_t stream)
-{
-  switch (code) {
-    case SERL_DYN_ICE: (step ? serl_launch_venv_step_ice : serl_launch_venv_reset_ice)(a, v, grid, stream); break;
-    case SERL_DYN_CG_TIMED: (step ? serl_launch_venv_step_cg_timed : serl_launch_venv_reset_cg_timed)(a, v, grid, stream); break;
-    case SERL_DYN_GUST: (step ? serl_launch_venv_step_gust : serl_launch_venv_reset_gust)(a, v, grid, stream); break;
-    case SERL_DYN_TEST: (step ? serl_launch_venv_step_test : serl_launch_venv_reset_test)(a, v, grid, stream); break;
-    default: (step ? serl_launch_venv_step_nominal : serl_launch_venv_reset_nominal)(a, v, grid, stream); break;
-  }
-}
-#define SERL_DECL_WAVE(v)                                                                                     \
-  void serl_launch_rollout_wave_##v(const RolloutArgs &a, int grid, hipStream_t stream);                          \
-  void serl_launch_rollout_wavex_##v(const RolloutArgs &a, int grid, hipStream_t stream);                         \
-  void serl_launch_dyn_wave_##v(const RolloutArgs &a, const double *cmds, double *states, int T, int grid, hipStream_t stream);
-SERL_DECL_WAVE(nominal) SERL_DECL_WAVE(ice) SERL_DECL_WAVE(cg_timed) SERL_DECL_WAVE(gust) SERL_DECL_WAVE(test)
+static_assert(serl_rows_in_code_order(), "k_launchers: row i must be serl_dyn_code i");
 
-// a team of wavefronts per episode (rollout_team.inc: 7 + the actor wavefront, two per SIMD): the latency-bound regime
-#define SERL_DECL_TEAM(v)                                                                                     \
-  void serl_launch_rollout_team_##v(const RolloutArgs &a, int grid, hipStream_t stream);                          \
-  void serl_launch_rollout_teamx_##v(const RolloutArgs &a, int grid, hipStream_t stream);                         \
-  void serl_launch_rollout_teams_##v(const RolloutArgs &a, int grid, hipStream_t stream);                         \
-  void serl_launch_dyn_team_##v(const RolloutArgs &a, const double *cmds, double *states, int T, int grid, hipStream_t stream);
-SERL_DECL_TEAM(nominal) SERL_DECL_TEAM(ice) SERL_DECL_TEAM(cg_timed) SERL_DECL_TEAM(gust) SERL_DECL_TEAM(test)
-// ... with one forward pass over two actor wavefronts (rollout_teams2_<v>.hip: hidden > 64)
+// the record of a loaded build's code variant (serl_ctx_load_build admits only codes with a row)
+static const SerlLaunchers &serl_launchers(int code) { return k_launchers[code]; }
+
 #include "serl_mixed.h"
-#define SERL_DECL_TEAMS2(v) void serl_launch_rollout_teams2_##v(const RolloutArgs &a, int grid, hipStream_t stream); \
-                            void serl_launch_rollout_teamr_##v(const RolloutArgs &a, int grid, hipStream_t stream);
-SERL_DECL_TEAMS2(nominal) SERL_DECL_TEAMS2(ice) SERL_DECL_TEAMS2(cg_timed) SERL_DECL_TEAMS2(gust) SERL_DECL_TEAMS2(test)
 
-// two episodes per wavefront (rollout_half.inc): beyond one wavefront per SIMD
-#define SERL_DECL_HALF(v) void serl_launch_rollout_half_##v(const RolloutArgs &a, int grid, hipStream_t stream);
-SERL_DECL_HALF(nominal) SERL_DECL_HALF(ice) SERL_DECL_HALF(cg_timed) SERL_DECL_HALF(gust) SERL_DECL_HALF(test)
-
-static void serl_launch_rollout_half(int code, const RolloutArgs &a, int grid, hipStream_t stream)
-{
-  switch (code) {
-    case SERL_DYN_NOMINAL: serl_launch_rollout_half_nominal(a, grid, stream); break;
-    case SERL_DYN_ICE: serl_launch_rollout_half_ice(a, grid, stream); break;
-    case SERL_DYN_CG_TIMED: serl_launch_rollout_half_cg_timed(a, grid, stream); break;
-    case SERL_DYN_GUST: serl_launch_rollout_half_gust(a, grid, stream); break;
-    default: serl_launch_rollout_half_test(a, grid, stream); break;
-  }
-}
-
-// two / four episodes per team (rollout_team_half.inc): between CUs and 4 x CUs episodes
-#define SERL_DECL_TEAMG(v) void serl_launch_rollout_team2_##v(const RolloutArgs &a, int grid, hipStream_t stream); \
-                           void serl_launch_rollout_team2s_##v(const RolloutArgs &a, int grid, hipStream_t stream); \
-                           void serl_launch_rollout_team4_##v(const RolloutArgs &a, int grid, hipStream_t stream);
-SERL_DECL_TEAMG(nominal) SERL_DECL_TEAMG(ice) SERL_DECL_TEAMG(cg_timed) SERL_DECL_TEAMG(gust) SERL_DECL_TEAMG(test)
-
-static void serl_launch_rollout_teamg(int code, int groups, const RolloutArgs &a, int grid, hipStream_t stream)
+static void serl_launch_rollout_teamg(const SerlLaunchers &L, int groups, const RolloutArgs &a, int grid, hipStream_t stream)
 {
   // (two per team with a streamed actor -- hidden != 32 -- is a kernel of its own: six team wavefronts + two actor wavefronts)
-#define SERL_TEAMG_CASE(v) (groups == 4 ? serl_launch_rollout_team4_##v(a, grid, stream) : \
-                            (a.d.hidden != 32 ? serl_launch_rollout_team2s_##v(a, grid, stream) : serl_launch_rollout_team2_##v(a, grid, stream)))
-  switch (code) {
-    case SERL_DYN_NOMINAL: SERL_TEAMG_CASE(nominal); break;
-    case SERL_DYN_ICE: SERL_TEAMG_CASE(ice); break;
-    case SERL_DYN_CG_TIMED: SERL_TEAMG_CASE(cg_timed); break;
-    case SERL_DYN_GUST: SERL_TEAMG_CASE(gust); break;
-    default: SERL_TEAMG_CASE(test); break;
-  }
-#undef SERL_TEAMG_CASE
+  (groups == 4 ? L.team4 : a.d.hidden != 32 ? L.team2s : L.team2)(a, grid, stream);
 }
 
 // Episodes per team, 0 = use another kernel.  Measured per env step: 21.6 us with one episode per team, 22.2 with two,
@@ -177,7 +135,7 @@ static bool serl_use_team(const serl_ctx *c, int hint, int episodes)
 static bool serl_lds_actor_shape(const serl_rollout_desc &d) { return d.hidden == 32 && d.num_layers <= 3 && d.state_dim == 7 && d.action_dim == 3; }
 
 // Round 6: streamed actors (hidden 65 .. 128: SERL10's 72, the TD3 actor's 96) of the attitude task with the actor in a workgroup of its own on another CU
-// (rollout_teamr_<v>.hip): two workgroups per episode, pairs (b, b + 8) of a group of sixteen.  Only while every workgroup of the launch -- and of the launches it
+// (family_teamr.hip): two workgroups per episode, pairs (b, b + 8) of a group of sixteen.  Only while every workgroup of the launch -- and of the launches it
 // was told about -- can be resident at once: a team spins on its partner's mailbox.  0 = not eligible, else the grid.
 static int serl_remote_actor_grid(const serl_ctx *c, const serl_rollout_desc *d, int together)
 {
@@ -186,68 +144,21 @@ static int serl_remote_actor_grid(const serl_ctx *c, const serl_rollout_desc *d,
   return all <= c->num_cus ? grid : 0;
 }
 
-static void serl_launch_rollout_teamr(int code, const RolloutArgs &a, int grid, hipStream_t stream)
-{
-  switch (code) {
-    case SERL_DYN_NOMINAL: serl_launch_rollout_teamr_nominal(a, grid, stream); break;
-    case SERL_DYN_ICE: serl_launch_rollout_teamr_ice(a, grid, stream); break;
-    case SERL_DYN_CG_TIMED: serl_launch_rollout_teamr_cg_timed(a, grid, stream); break;
-    case SERL_DYN_GUST: serl_launch_rollout_teamr_gust(a, grid, stream); break;
-    default: serl_launch_rollout_teamr_test(a, grid, stream); break;
-  }
-}
-
-static void serl_launch_rollout_team(int code, const RolloutArgs &a, int grid, hipStream_t stream, bool split_actor = false)
+static void serl_launch_rollout_team(const SerlLaunchers &L, const RolloutArgs &a, int grid, hipStream_t stream, bool split_actor = false)
 {
   // (rollout_device.h: serl_lds_actor_ok) shapes whose weights the actor wavefront streams have a kernel of their own
   const bool lds_actor = serl_lds_actor_shape(a.d);
-  if (!lds_actor && split_actor && a.d.hidden > 64 && a.d.hidden <= 128) {
-    // (development override SERL_SPLIT_ACTOR=1) two actor wavefronts share ONE forward pass beside a six-wavefront team: round 4
-    // built it for the shapes whose lone actor wavefront needed a whole step (H = 72: 43 k cycles) -- and then found that a
-    // shape-specialised forward (serl_actor_forward_big: 25 k) on ONE wavefront beside the seven-wavefront team is faster
-    switch (code) {
-      case SERL_DYN_NOMINAL: serl_launch_rollout_teams2_nominal(a, grid, stream); break;
-      case SERL_DYN_ICE: serl_launch_rollout_teams2_ice(a, grid, stream); break;
-      case SERL_DYN_CG_TIMED: serl_launch_rollout_teams2_cg_timed(a, grid, stream); break;
-      case SERL_DYN_GUST: serl_launch_rollout_teams2_gust(a, grid, stream); break;
-      default: serl_launch_rollout_teams2_test(a, grid, stream); break;
-    }
-    return;
-  }
-  if (!lds_actor) {
-    switch (code) {
-      case SERL_DYN_NOMINAL: serl_launch_rollout_teams_nominal(a, grid, stream); break;
-      case SERL_DYN_ICE: serl_launch_rollout_teams_ice(a, grid, stream); break;
-      case SERL_DYN_CG_TIMED: serl_launch_rollout_teams_cg_timed(a, grid, stream); break;
-      case SERL_DYN_GUST: serl_launch_rollout_teams_gust(a, grid, stream); break;
-      default: serl_launch_rollout_teams_test(a, grid, stream); break;
-    }
-    return;
-  }
-  switch (code) {
-    case SERL_DYN_NOMINAL: serl_launch_rollout_team_nominal(a, grid, stream); break;
-    case SERL_DYN_ICE: serl_launch_rollout_team_ice(a, grid, stream); break;
-    case SERL_DYN_CG_TIMED: serl_launch_rollout_team_cg_timed(a, grid, stream); break;
-    case SERL_DYN_GUST: serl_launch_rollout_team_gust(a, grid, stream); break;
-    default: serl_launch_rollout_team_test(a, grid, stream); break;
-  }
-}
-
-static void serl_launch_dyn_team(int code, const RolloutArgs &a, const double *cmds, double *states, int T, int grid, hipStream_t stream)
-{
-  switch (code) {
-    case SERL_DYN_NOMINAL: serl_launch_dyn_team_nominal(a, cmds, states, T, grid, stream); break;
-    case SERL_DYN_ICE: serl_launch_dyn_team_ice(a, cmds, states, T, grid, stream); break;
-    case SERL_DYN_CG_TIMED: serl_launch_dyn_team_cg_timed(a, cmds, states, T, grid, stream); break;
-    case SERL_DYN_GUST: serl_launch_dyn_team_gust(a, cmds, states, T, grid, stream); break;
-    default: serl_launch_dyn_team_test(a, cmds, states, T, grid, stream); break;
-  }
+  // (development override SERL_SPLIT_ACTOR=1) two actor wavefronts share ONE forward pass beside a six-wavefront team: round 4
+  // built it for the shapes whose lone actor wavefront needed a whole step (H = 72: 43 k cycles) -- and then found that a
+  // shape-specialised forward (serl_actor_forward_big: 25 k) on ONE wavefront beside the seven-wavefront team is faster
+  const bool split = !lds_actor && split_actor && a.d.hidden > 64 && a.d.hidden <= 128;
+  (lds_actor ? L.team : split ? L.teams2 : L.teams)(a, grid, stream);
 }
 
 // The wave-cooperative kernels (one wavefront per episode, rollout_wave.inc) exist for every code variant; the
 // lane-per-episode kernels (rollout_variant.inc, lanes_per_wave > 0) for every code variant since round 6.
-static bool serl_has_wave_kernel(int code) { return code >= SERL_DYN_NOMINAL && code <= SERL_DYN_TEST; }
-static bool serl_has_lane_kernel(int code) { return code >= SERL_DYN_NOMINAL && code <= SERL_DYN_TEST; }
+static bool serl_has_wave_kernel(int code) { return code >= 0 && code < SERL_N_VARIANTS; }
+static bool serl_has_lane_kernel(int code) { return code >= 0 && code < SERL_N_VARIANTS; }
 
 // Lane-per-episode kernels (rollout_device.h serl_actor_forward_lane32_t): the population [members][stride] regrouped to [ceil(P / 4)][mpad][4], so that parameter
 // group g of 64 consecutive members is ONE run of 1 KB.  Reads run along a member's row, writes are 16 B pieces (30 MB for 2 048 SERL50 actors: microseconds in front of a
@@ -288,51 +199,6 @@ static int serl_regroup_weights(serl_ctx *c, const serl_rollout_desc *d, Rollout
   a.wt = (const float *)c->wt[slot];
   a.wt_members = mpad;
   return SERL_OK;
-}
-
-static void serl_launch_rollout_wave(int code, const RolloutArgs &a, int grid, hipStream_t stream)
-{
-  switch (code) {
-    case SERL_DYN_NOMINAL: serl_launch_rollout_wave_nominal(a, grid, stream); break;
-    case SERL_DYN_ICE: serl_launch_rollout_wave_ice(a, grid, stream); break;
-    case SERL_DYN_CG_TIMED: serl_launch_rollout_wave_cg_timed(a, grid, stream); break;
-    case SERL_DYN_GUST: serl_launch_rollout_wave_gust(a, grid, stream); break;
-    default: serl_launch_rollout_wave_test(a, grid, stream); break;
-  }
-}
-
-// env configurations other than the attitude task (serl_rollout_desc.env_config / incremental)
-static void serl_launch_rollout_teamx(int code, const RolloutArgs &a, int grid, hipStream_t stream)
-{
-  switch (code) {
-    case SERL_DYN_NOMINAL: serl_launch_rollout_teamx_nominal(a, grid, stream); break;
-    case SERL_DYN_ICE: serl_launch_rollout_teamx_ice(a, grid, stream); break;
-    case SERL_DYN_CG_TIMED: serl_launch_rollout_teamx_cg_timed(a, grid, stream); break;
-    case SERL_DYN_GUST: serl_launch_rollout_teamx_gust(a, grid, stream); break;
-    default: serl_launch_rollout_teamx_test(a, grid, stream); break;
-  }
-}
-
-static void serl_launch_rollout_wavex(int code, const RolloutArgs &a, int grid, hipStream_t stream)
-{
-  switch (code) {
-    case SERL_DYN_NOMINAL: serl_launch_rollout_wavex_nominal(a, grid, stream); break;
-    case SERL_DYN_ICE: serl_launch_rollout_wavex_ice(a, grid, stream); break;
-    case SERL_DYN_CG_TIMED: serl_launch_rollout_wavex_cg_timed(a, grid, stream); break;
-    case SERL_DYN_GUST: serl_launch_rollout_wavex_gust(a, grid, stream); break;
-    default: serl_launch_rollout_wavex_test(a, grid, stream); break;
-  }
-}
-
-static void serl_launch_dyn_wave(int code, const RolloutArgs &a, const double *cmds, double *states, int T, int grid, hipStream_t stream)
-{
-  switch (code) {
-    case SERL_DYN_NOMINAL: serl_launch_dyn_wave_nominal(a, cmds, states, T, grid, stream); break;
-    case SERL_DYN_ICE: serl_launch_dyn_wave_ice(a, cmds, states, T, grid, stream); break;
-    case SERL_DYN_CG_TIMED: serl_launch_dyn_wave_cg_timed(a, cmds, states, T, grid, stream); break;
-    case SERL_DYN_GUST: serl_launch_dyn_wave_gust(a, cmds, states, T, grid, stream); break;
-    default: serl_launch_dyn_wave_test(a, cmds, states, T, grid, stream); break;
-  }
 }
 
 // Wavefronts per workgroup of the wave-cooperative kernels: one per CU while there are no more episodes than CUs,
@@ -536,6 +402,7 @@ int serl_rollout(serl_ctx *c, const serl_rollout_desc *d, void *stream_)
   const bool general_env = d->env_config != SERL_ENV_ATTITUDE || d->incremental != 0;
   HIP_TRY(hipSetDevice(c->device));
   const BuildSlot &s = c->slots[d->build_slot];
+  const SerlLaunchers &L = serl_launchers(s.code);
   hipStream_t stream = (hipStream_t)stream_;
   RolloutArgs a;
   memset(&a, 0, sizeof(a));
@@ -570,7 +437,7 @@ int serl_rollout(serl_ctx *c, const serl_rollout_desc *d, void *stream_)
       for (int e0 = 0; e0 < d->n_episodes; e0 += c->num_cus) {
         const int n = d->n_episodes - e0 < c->num_cus ? d->n_episodes - e0 : c->num_cus;
         a.e0 = e0; a.e_end = e0 + n;
-        serl_launch_rollout_teamx(s.code, a, n, stream);
+        L.teamx(a, n, stream);
         HIP_TRY(hipGetLastError());
         ++launches; last = n;
       }
@@ -579,7 +446,7 @@ int serl_rollout(serl_ctx *c, const serl_rollout_desc *d, void *stream_)
       const int wpb = serl_wave_kernel_waves_per_block(c, together + (timed ? 0 : 16));
       a.lanes = 1;
       a.block = 64 * wpb;
-      serl_launch_rollout_wavex(s.code, a, (d->n_episodes + wpb - 1) / wpb, stream);
+      L.wavex(a, (d->n_episodes + wpb - 1) / wpb, stream);
       HIP_TRY(hipGetLastError());
       serl_note_launch(c, SERL_FAMILY_WAVEX, (d->n_episodes + wpb - 1) / wpb, 1, false, 0, true, 1, s.code);
     }
@@ -601,14 +468,14 @@ int serl_rollout(serl_ctx *c, const serl_rollout_desc *d, void *stream_)
       HIP_TRY(hipMemsetAsync(a.mail, 0, (size_t)d->n_episodes * sizeof(SerlMail), stream));
       a.block = 512;
       if (timed) HIP_TRY(hipEventRecord(c->ev0, stream));      // (re-recorded behind the memset: the kernel alone is timed)
-      serl_launch_rollout_teamr(s.code, a, rgrid, stream);
+      L.teamr(a, rgrid, stream);
       HIP_TRY(hipGetLastError());
       serl_note_launch(c, SERL_FAMILY_TEAMR, rgrid, 1, false, 4, true, 1, s.code);
       if (timed) HIP_TRY(hipEventRecord(c->ev1, stream));
       c->timed = timed;
       return SERL_OK;
     }
-    serl_launch_rollout_team(s.code, a, d->n_episodes, stream, c->env_split_actor != 0);
+    serl_launch_rollout_team(L, a, d->n_episodes, stream, c->env_split_actor != 0);
     HIP_TRY(hipGetLastError());
     {
       const bool lds_actor = serl_lds_actor_shape(*d), split = !lds_actor && c->env_split_actor != 0 && d->hidden > 64 && d->hidden <= 128;
@@ -633,7 +500,7 @@ int serl_rollout(serl_ctx *c, const serl_rollout_desc *d, void *stream_)
     } else {
       a.queue = nullptr; a.q0 = d->n_episodes;
     }
-    serl_launch_rollout_teamg(s.code, teamg, a, grid, stream);
+    serl_launch_rollout_teamg(L, teamg, a, grid, stream);
     HIP_TRY(hipGetLastError());
     serl_note_launch(c, teamg == 4 ? SERL_FAMILY_TEAM4 : d->hidden != 32 ? SERL_FAMILY_TEAM2S : SERL_FAMILY_TEAM2, grid, teamg, a.queue != nullptr,
                      (teamg == 2 && d->hidden != 32) ? 2 : 1, true /* the lane-group kernels' actor wavefronts stream the weights */, 1, s.code);
@@ -677,7 +544,7 @@ int serl_rollout(serl_ctx *c, const serl_rollout_desc *d, void *stream_)
       a.q0 = 4 * grid;
       HIP_TRY(hipMemsetAsync(a.queue, 0, sizeof(int32_t), stream));
     }
-    serl_launch_rollout_teamg(s.code, 4, a, grid, stream);
+    L.team4(a, grid, stream);
     HIP_TRY(hipGetLastError());
     serl_note_launch(c, SERL_FAMILY_TEAM4, grid, 4, a.queue != nullptr, 1, true, 1, s.code);
     if (timed) HIP_TRY(hipEventRecord(c->ev1, stream));
@@ -692,7 +559,7 @@ int serl_rollout(serl_ctx *c, const serl_rollout_desc *d, void *stream_)
     a.block = 64 * wpb;
     const int grid = (waves + wpb - 1) / wpb;
     if (timed) HIP_TRY(hipEventRecord(c->ev0, stream));
-    serl_launch_rollout_half(s.code, a, grid, stream);
+    L.half(a, grid, stream);
     HIP_TRY(hipGetLastError());
     serl_note_launch(c, SERL_FAMILY_HALF, grid, 2, false, 0, true, 1, s.code);
     if (timed) HIP_TRY(hipEventRecord(c->ev1, stream));
@@ -707,7 +574,7 @@ int serl_rollout(serl_ctx *c, const serl_rollout_desc *d, void *stream_)
     a.block = 64 * wpb;
     const int grid = (d->n_episodes + wpb - 1) / wpb;
     if (timed) HIP_TRY(hipEventRecord(c->ev0, stream));
-    serl_launch_rollout_wave(s.code, a, grid, stream);
+    L.wave(a, grid, stream);
     HIP_TRY(hipGetLastError());
     serl_note_launch(c, SERL_FAMILY_WAVE, grid, 1, false, 0, true, 1, s.code);
     if (timed) HIP_TRY(hipEventRecord(c->ev1, stream));
@@ -734,7 +601,7 @@ int serl_rollout(serl_ctx *c, const serl_rollout_desc *d, void *stream_)
     if (rc != SERL_OK) return rc;
   }
   if (timed) HIP_TRY(hipEventRecord(c->ev0, stream));
-  serl_launch_rollout_lane(s.code, a, grid, stream);
+  L.lane(a, grid, stream);
   HIP_TRY(hipGetLastError());
   if (a.wt) HIP_TRY(hipEventRecord(c->wt_done[c->wt_slot_of_launch], stream));
   serl_note_launch(c, SERL_FAMILY_LANE, grid, lanes, false, 0, true, 1, s.code);
@@ -854,6 +721,7 @@ int serl_dyn_open_loop(serl_ctx *c, int slot, int32_t n_episodes, int32_t T, con
   if (slot < 0 || slot >= SERL_MAX_SLOTS || !c->slots[slot].loaded) return fail(SERL_E_INVALID, "serl_dyn_open_loop: build slot not loaded");
   HIP_TRY(hipSetDevice(c->device));
   const BuildSlot &s = c->slots[slot];
+  const SerlLaunchers &L = serl_launchers(s.code);
   RolloutArgs a;
   memset(&a, 0, sizeof(a));
   a.d.n_episodes = n_episodes;
@@ -865,7 +733,7 @@ int serl_dyn_open_loop(serl_ctx *c, int slot, int32_t n_episodes, int32_t T, con
     a.lanes = 1;
     a.block = 128;
     HIP_TRY(hipEventRecord(c->ev0, stream));
-    serl_launch_dyn_team(s.code, a, cmds, states, T, n_episodes, stream);
+    L.dyn_team(a, cmds, states, T, n_episodes, stream);
     HIP_TRY(hipGetLastError());
     serl_note_launch(c, SERL_FAMILY_TEAM, n_episodes, 1, false, 0, false, 1, s.code);      // (dynamics only: the team without an actor wavefront)
     HIP_TRY(hipEventRecord(c->ev1, stream));
@@ -877,7 +745,7 @@ int serl_dyn_open_loop(serl_ctx *c, int slot, int32_t n_episodes, int32_t T, con
     a.lanes = 1;
     a.block = 64 * wpb;
     HIP_TRY(hipEventRecord(c->ev0, stream));
-    serl_launch_dyn_wave(s.code, a, cmds, states, T, (n_episodes + wpb - 1) / wpb, stream);
+    L.dyn_wave(a, cmds, states, T, (n_episodes + wpb - 1) / wpb, stream);
     HIP_TRY(hipGetLastError());
     serl_note_launch(c, SERL_FAMILY_WAVE, (n_episodes + wpb - 1) / wpb, 1, false, 0, false, 1, s.code);
     HIP_TRY(hipEventRecord(c->ev1, stream));
@@ -894,7 +762,7 @@ int serl_dyn_open_loop(serl_ctx *c, int slot, int32_t n_episodes, int32_t T, con
   a.block = 64 * wpb;
   const int grid = (nwaves + wpb - 1) / wpb;
   HIP_TRY(hipEventRecord(c->ev0, stream));
-  serl_launch_dyn_lane(s.code, a, cmds, states, T, grid, stream);
+  L.dyn_lane(a, cmds, states, T, grid, stream);
   HIP_TRY(hipGetLastError());
   serl_note_launch(c, SERL_FAMILY_LANE, grid, lanes, false, 0, false, 1, s.code);
   HIP_TRY(hipEventRecord(c->ev1, stream));
@@ -936,6 +804,7 @@ static int serl_venv_check(serl_ctx *c, const serl_venv_desc *d, const char *wha
 static int serl_venv_launch(serl_ctx *c, const serl_venv_desc *d, bool step, VenvArgs &v, hipStream_t stream)
 {
   const BuildSlot &s = c->slots[d->build_slot];
+  const SerlLaunchers &L = serl_launchers(s.code);
   RolloutArgs a;
   memset(&a, 0, sizeof(a));
   a.d.n_episodes = d->n_envs;
@@ -950,7 +819,7 @@ static int serl_venv_launch(serl_ctx *c, const serl_venv_desc *d, bool step, Ven
   const int grid = (nwaves + wpb - 1) / wpb;
   v.d = *d;
   v.npad = serl_venv_npad(d->n_envs);
-  serl_launch_venv(s.code, step, a, v, grid, stream);
+  (step ? L.venv_step : L.venv_reset)(a, v, grid, stream);
   HIP_TRY(hipGetLastError());
   return SERL_OK;
 }

@@ -36,7 +36,7 @@ struct serl_ctx {
   // environment overrides, read once when the context is made (-1 = not set)
   int env_kernel = 0 /* serl_kernel_hint from SERL_KERNEL */, env_waves_per_block = -1, env_profile = 0;
   int env_split_actor = 0;              // SERL_SPLIT_ACTOR=1: streamed actors of one-episode teams (hidden > 64) on TWO actor wavefronts that share the forward pass
-                                        // (rollout_teams2_<v>.hip; measured slower than one wavefront with the specialised forward: profiles/r04_experiments.md)
+                                        // (family_teams2.hip; measured slower than one wavefront with the specialised forward: profiles/r04_experiments.md)
   unsigned env_jitter_sites = ~0u;      // SERL_JITTER_SITES: classes of sites that pause (citation_wave.h; all by default)
   int env_mixed_place = SERL_MIXED_PLACE_DEFAULT;      // SERL_MIXED_PLACE: how serl_rollout_multi places the parts' workgroups (serl_mixed.h)
   int32_t *mixed_state = nullptr;       // device [SERL_MIXED_STATES][SERL_MIXED_STATE]
@@ -49,8 +49,8 @@ struct serl_ctx {
   unsigned long long *prof = nullptr;   // device [32], allocated when SERL_PROFILE=1
   int32_t *queue = nullptr;             // device [SERL_QUEUE_COUNTERS]: work-queue counters of the multi-episode team kernels, one per LAUNCH (a ring)
   int queue_next = 0;
-  int env_remote_actor = 1;             // SERL_REMOTE_ACTOR=0: streamed actors of one-episode teams stay on the team's CU (rollout_team_<v>.hip serl_rollout_teams_kernel_; A/B)
-  void *mail = nullptr;                 // device [SERL_MAIL_REGIONS][num_cus] SerlMail: team <-> remote actor workgroup (rollout_teamr_<v>.hip)
+  int env_remote_actor = 1;             // SERL_REMOTE_ACTOR=0: streamed actors of one-episode teams stay on the team's CU (family_team.hip serl_rollout_teams_kernel_; A/B)
+  void *mail = nullptr;                 // device [SERL_MAIL_REGIONS][num_cus] SerlMail: team <-> remote actor workgroup (family_teamr.hip)
   int mail_next = 0;
   int env_lane_regroup = 1;             // SERL_LANE_WEIGHTS=rows: the lane-per-episode kernels walk [members][P] rows instead of the regrouped copy (A/B)
   void *wt[SERL_WT_SLOTS] = {};         // lane-per-episode kernels: regrouped weights [ceil(P / 4)][members up to 64][4] of the launches in flight (a ring; grown on demand)

@@ -130,15 +130,14 @@ def test_smoothness_full_pass_and_speculation():
 def test_role_maps_and_pairing_sweep():
     """The role <-> wavefront maps of the team kernels are permutations of the seven roles with the actor on wavefront 7, and
     tools/sweep_roles.py enumerates every pairing of the roles on the four SIMDs exactly once (105), the shipped map first."""
-    import re, subprocess, sys, glob
-    for f in glob.glob(os.path.join(ROOT, 'serl_amd', 'csrc', 'rollout_team_*.hip')):
-        t = open(f).read()
-        for name in ('SERL_TEAM_ROLES', 'SERL_TEAMS_ROLES'):
-            m = re.search(r'#define %s \{([0-9, ]+)\}' % name, t)
-            if m is None:
-                continue
-            r = [int(v) for v in m.group(1).split(',')]
-            assert len(r) == 16 and sorted(r[:7]) == list(range(7)) and r[7] == 7, (f, name, r)
+    import re, subprocess, sys
+    f = os.path.join(ROOT, 'serl_amd', 'csrc', 'family_team.hip')      # (family_teamr.hip includes it)
+    t = open(f).read()
+    for name in ('SERL_TEAM_ROLES', 'SERL_TEAMS_ROLES'):
+        m = re.search(r'#define %s \{([0-9, ]+)\}' % name, t)
+        assert m is not None, (f, name)
+        r = [int(v) for v in m.group(1).split(',')]
+        assert len(r) == 16 and sorted(r[:7]) == list(range(7)) and r[7] == 7, (f, name, r)
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'sweep_roles.py')], capture_output=True, text=True, check=True).stdout.split()
     assert len(out) == 105 and len(set(out)) == 105
     pair_sets = set()

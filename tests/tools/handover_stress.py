@@ -35,9 +35,9 @@ def cases(cus):
     """name -> (actor tag, kernel hint, episodes): every kernel family of rollout_team.inc / rollout_team_half.inc"""
     return {
         'team': ('serl50', 'team', 12),                # seven team wavefronts + the actor wavefront, weights in LDS
-        'teamr': ('serl10', 'team', 6),                # ... the streamed actor in a workgroup of its own on another CU: mailboxes in global memory, a courier wavefront (rollout_teamr_<v>.hip)
+        'teamr': ('serl10', 'team', 6),                # ... the streamed actor in a workgroup of its own on another CU: mailboxes in global memory, a courier wavefront (family_teamr.hip)
         'teams': ('serl10', 'team', 6),                # ... the actor streams its weights on the team's CU (SERL_REMOTE_ACTOR=0)
-        'teams_split': ('serl10', 'team', 6),          # ... on TWO actor wavefronts that share the forward pass (SERL_SPLIT_ACTOR=1, rollout_teams2_<v>.hip)
+        'teams_split': ('serl10', 'team', 6),          # ... on TWO actor wavefronts that share the forward pass (SERL_SPLIT_ACTOR=1, family_teams2.hip)
         'team2': ('serl50', 'team2', 21),              # two episodes per team (an odd count: one lane group stays empty)
         'team2s': ('serl10', 'team2', 11),             # six team wavefronts + two streaming actor wavefronts
         'team4': ('serl50', 'team4', 35),              # four episodes per team

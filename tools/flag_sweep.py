@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compiler-flag variants of the one-episode team kernel (bit-identical by construction: no flag here touches floating-point semantics):
     python tools/flag_sweep.py tools/sweeps/<name>.json        {"tag": [extra hipcc flags ...], ...}
-builds serl_amd/csrc/libserl_amd_<tag>.so for every tag (tools/exp_build.py: only rollout_team_nominal.hip is recompiled), reports the kernel's
+builds serl_amd/csrc/libserl_amd_<tag>.so for every tag (tools/exp_build.py: only the unit rollout_team_nominal is recompiled), reports the kernel's
 static instruction count / registers / spills, and writes tools/sweep_libs.txt for tools/sweep_run.sh (A/B through tools/ab.py on the GPU box)."""
 import json, os, re, subprocess, sys
 from concurrent.futures import ThreadPoolExecutor

@@ -25,7 +25,7 @@ def main():
     flags = [a for a in args if a.startswith('-D') or a.startswith('-m')]
     with tempfile.TemporaryDirectory() as td:
         co, elf = os.path.join(td, 'u.co'), os.path.join(td, 'u.elf')
-        r = subprocess.run([B.HIPCC] + B.FLAGS + flags + ['--cuda-device-only', '-gline-tables-only', '-c', os.path.join(B.CSRC, unit), '-o', co], capture_output=True, text=True)
+        r = subprocess.run(B.compile_argv(unit, co, flags + ['--cuda-device-only', '-gline-tables-only']), capture_output=True, text=True)
         if r.returncode:
             sys.exit(r.stderr[-3000:])
         subprocess.run([LLVM + '/clang-offload-bundler', '--unbundle', '--type=o', '--input=' + co, '--targets=hipv4-amdgcn-amd-amdhsa--gfx950', '--output=' + elf], check=True)

@@ -2,7 +2,7 @@
 """Static instruction mix of ONE kernel of a unit as the product build compiles it, attributed to source files:
 
   python tools/isa/kernel_isa.py [unit.hip] [kernel-name substring] [extra hipcc flags ...] [--json]
-  (defaults: rollout_team_nominal.hip serl_rollout_team_kernel)
+  (defaults: rollout_team_nominal.hip serl_rollout_team_kernel; a unit is named by its object stem + .hip: serl_amd/build.py UNITS)
 
 Compiles the unit for gfx950 with the product's flags + line tables (device only), disassembles it and reports for the kernel:
 registers / spills / LDS from the code-object notes; instructions; the moves that only materialise a constant -- split into f64 literal
@@ -25,8 +25,7 @@ def main():
     flags = [a for a in rest if a.startswith('-')]
     with tempfile.TemporaryDirectory() as td:
         co, elf = os.path.join(td, 'u.co'), os.path.join(td, 'u.elf')
-        r = subprocess.run([B.HIPCC] + B.FLAGS + flags + ['--cuda-device-only', '-gline-tables-only', '-c', os.path.join(B.CSRC, unit), '-o', co],
-                           capture_output=True, text=True)
+        r = subprocess.run(B.compile_argv(unit, co, flags + ['--cuda-device-only', '-gline-tables-only']), capture_output=True, text=True)
         if r.returncode:
             sys.exit(r.stderr[-3000:])
         subprocess.run([LLVM + '/clang-offload-bundler', '--unbundle', '--type=o', '--input=' + co, '--targets=hipv4-amdgcn-amd-amdhsa--gfx950',

@@ -68,14 +68,14 @@ LIBM_GUARDED = re.compile(r'^(exp|log10|log)$')
 def main():
     args = sys.argv[1:]
     variant = args[args.index('--variant') + 1] if '--variant' in args else 'nominal'
-    unit = 'rollout_team_%s.hip' % variant
+    unit = 'rollout_team_%s' % variant
     kname = 'serl_rollout_team_kernel_%s' % variant
     flags = [a for a in args if a.startswith('-D')]
     gen = os.path.join(B.CSRC, 'gen', 'citation_%s_team.inc' % variant)
     wline = gen_line_weights(gen, variant)
     with tempfile.TemporaryDirectory() as td:
         co, elf = os.path.join(td, 'u.co'), os.path.join(td, 'u.elf')
-        r = subprocess.run([B.HIPCC] + B.FLAGS + flags + ['--cuda-device-only', '-gline-tables-only', '-c', os.path.join(B.CSRC, unit), '-o', co], capture_output=True, text=True)
+        r = subprocess.run(B.compile_argv(unit, co, flags + ['--cuda-device-only', '-gline-tables-only']), capture_output=True, text=True)
         if r.returncode:
             sys.exit(r.stderr[-3000:])
         subprocess.run([LLVM + '/clang-offload-bundler', '--unbundle', '--type=o', '--input=' + co, '--targets=hipv4-amdgcn-amd-amdhsa--gfx950', '--output=' + elf], check=True)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Every pairing of the seven team roles on the four SIMDs of a CU (hardware wavefronts w and w + 4 share one; wavefront 7 is the actor):
 105 role maps for libserl_amd_devroles.so (-DSERL_DEV_ROLE_MAP=1: the map comes in through SERL_JITTER_SITES, a nibble per hardware wavefront).
-    python tools/sweep_roles.py            -> one hex map per line (the compiled map of rollout_team_<v>.hip first)"""
+    python tools/sweep_roles.py            -> one hex map per line (the compiled map of family_team.hip first)"""
 import itertools
 
 
@@ -24,7 +24,7 @@ def to_map(roles_of_wave):
 
 
 if __name__ == '__main__':
-    shipped = [1, 3, 5, 0, 2, 4, 6, 7]      # SERL_TEAM_ROLES of rollout_team_<v>.hip (the LDS-resident actor; SERL_TEAMS_ROLES, beside a streaming actor, is 0 6 2 3 4 5 1 7)
+    shipped = [1, 3, 5, 0, 2, 4, 6, 7]      # SERL_TEAM_ROLES of family_team.hip (the LDS-resident actor; SERL_TEAMS_ROLES, beside a streaming actor, is 0 6 2 3 4 5 1 7)
     seen = set()
     out = ['%08x' % to_map(shipped)]
     seen.add(frozenset([frozenset((shipped[w], shipped[w + 4])) for w in range(4)]))
