@@ -181,9 +181,11 @@ __global__ void __launch_bounds__(DB) distill_kernel(DistillArgs a)
       }
     }
     // ---------------- loss: sum (out - target)^2 + mean(out^2) over the kept states (genetic_agent.py:49-52)
+    // A minibatch the Q-filter drops entirely still takes its Adam step, with a zero gradient, as the reference's does: its loss is
+    // NaN (the mean over no state), but no term of it reaches a weight, every .grad is 0, and Adam's step advances the bias
+    // corrections and applies the decayed first moment.  Here every dpre is 0 (keep = 0), so are all the gradients below.
     const int kept = __syncthreads_count(keep != 0.0f);
-    if (kept == 0) continue;             // (the reference's mean over an empty batch is NaN; no step is taken here)
-    const float inv_n = 1.0f / (float)(kept * A);
+    const float inv_n = kept > 0 ? 1.0f / (float)(kept * A) : 0.0f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const float tgt = (live && k < A) ? tg_p[(size_t)slot * A + k] : 0.0f;

@@ -23,12 +23,11 @@ are accepted.  Two reference defects on this path, and what happens here:
     `sort_groups_by_novelty(..., bcs_evals)`, which raises TypeError when `bcs_evals` is None (what Agent.train passes).
     Here: bcs_evals None -> the distance-sorted groups (the evident intent); bcs_evals given -> the novelty-sorted groups,
     like the reference (the distance draws are still consumed first).
-Two more deliberate deviations from the reference's behaviour in corner cases:
-  * `clone(master, replacee)` with master == replacee (an elite that is its own replacement slot) is a no-op here; the
-    reference's clone (:371-382) wipes the replacee's buffer and refills it from the master's -- which is the same, emptied,
-    object -- so there the elite loses its buffer.
-  * an Adam step of the fused distillation kernel whose Q-filter keeps no state of the minibatch is skipped; the reference
-    takes the mean over an empty selection (genetic_agent.py:44-59) and its child's weights become NaN.
+One more deliberate deviation from the reference's behaviour in a corner case: `clone(master, replacee)` with
+master == replacee (an elite that is its own replacement slot) is a no-op here; the reference's clone (:371-382) wipes the
+replacee's buffer and refills it from the master's -- which is the same, emptied, object -- so there the elite loses its
+buffer.  (A distillation minibatch whose Q-filter keeps no state is no deviation: the reference's loss is NaN there, but its
+gradients are all zero and Adam still steps -- the fused kernel takes the same step, tests/test_distill_host.py.)
 """
 import random
 import numpy as np
