@@ -320,7 +320,11 @@ int serl_last_rollout_ms(serl_ctx *ctx, float *ms);
 /* ---- SSNE weight-tensor edits (base/core/mod_neuro_evo.py) as elementwise kernels.  `weights` is
  * the same [n_members][stride] f32 tensor; index lists are DEVICE int32/float arrays generated by
  * the host from the reference's RNG streams so that selection stays bit-compatible. ------------ */
-/* clone (mod_neuro_evo.py:371-382): weights[dst[i]] = weights[src[i]], i < n */
+/* clone (mod_neuro_evo.py:371-382): weights[dst[i]][0 .. param_count) = weights[src[i]][0 .. param_count), i < n; the columns from
+ * param_count to stride are left alone.  The pairs of one call are copied IN PARALLEL and must be independent: a destination
+ * that is another pair's source (or two pairs with one destination) has no defined result; src[i] == dst[i] is fine.  The pairs
+ * are a dimension of the launch grid: n = 65 536 and 65 537 are served on the MI355X (tests/test_gpu_support_kernels.py), no
+ * smaller limit than int32 was found; a launch the runtime refuses returns SERL_E_HIP and has written nothing.  n = 0: no-op. */
 int serl_ga_clone(serl_ctx *ctx, float *weights, int64_t stride, int32_t param_count,
                   const int32_t *src, const int32_t *dst, int32_t n, void *stream);
 /* crossover_inplace (mod_neuro_evo.py:61-93): n row/element swaps between two members:
@@ -331,7 +335,9 @@ int serl_ga_crossover(serl_ctx *ctx, float *weights, int64_t stride, int32_t mem
 /* mutate_inplace (mod_neuro_evo.py:329-369): n sparse edits of one member applied IN ORDER:
  *   kind 0:  w[idx] += z * (strength * w[idx])   (normal / super mutation: random.gauss(0, strength*w) = z*sigma)
  *   kind 1:  w[idx]  = z                          (reset: random.gauss(0, 1))
- * each followed by the reference's hard clamp to +-1e6 (regularize_weight, :57-59,366). */
+ * each followed by the reference's hard clamp to +-1e6 (regularize_weight, :57-59,366) with torch.clamp's semantics: a value that
+ * is NaN (a NaN weight, a NaN draw, inf - inf, 0 * inf) STAYS NaN -- a diverged actor does not come back as a finite one --
+ * and +-inf becomes +-1e6.  idx / kind / z / strength may be NULL only when n == 0 (SERL_E_INVALID otherwise). */
 int serl_ga_mutate(serl_ctx *ctx, float *weights, int64_t stride, int32_t member,
                    const int32_t *idx, const int32_t *kind, const float *z, const float *strength,
                    int32_t n, void *stream);
@@ -376,7 +382,12 @@ int serl_replay_scatter(serl_ctx *ctx, const float *staged, int64_t rows_per_epi
  *   f = linspace(dt, 1 / (2 dt), N/2 - 1);  out[e] = -sqrt(S) * 100 * (80 / (N dt))   (0 for N < 4)
  * evaluated as a direct DFT (one thread per frequency, the N twiddles in LDS), so there is no per-length FFT plan.
  * actions: f64 [n_episodes][episode_stride / 3][3] (env.last_u per step: serl_rollout_desc.actions), rows past N ignored;
- * work: f64 [serl_smoothness_work_size(n_episodes, max_len)] scratch; max_len >= every |length|, <= 8192. */
+ * work: f64 [serl_smoothness_work_size(n_episodes, max_len)] scratch; max_len >= every |length|, <= 8192 (SERL_E_UNSUPPORTED above).
+ * The summation order is fixed: out[e] depends on the episode's own samples, |length| and dt only -- not on max_len,
+ * episode_stride, n_episodes or the episode's place in the batch.  The episodes are a dimension of the launch grid:
+ * n_episodes = 65 536 (the saturating configuration) and 65 537 are served on the MI355X (tests/test_gpu_support_kernels.py); the
+ * limit that remains is the int result of serl_smoothness_work_size, n_episodes * ceil((max_len / 2 - 1) / 256) < 2^31.  A launch
+ * the runtime refuses returns SERL_E_HIP with `out` untouched. */
 int serl_smoothness_work_size(int32_t n_episodes, int32_t max_len);
 int serl_smoothness(serl_ctx *ctx, const double *actions, int64_t episode_stride, const int32_t *lengths, int32_t n_episodes,
                     int32_t max_len, double dt, double *work, double *out, void *stream);

@@ -920,7 +920,8 @@ __global__ void ga_crossover_kernel(float *w, int64_t stride, int32_t ma, int32_
 
 // Sequential sparse edits of one member (edits may hit the same weight twice; order matters).
 // kind 0: w += z * (strength * w)   [random.gauss(0, strength*w) = z*sigma]   kind 1: w = z
-// followed by the reference's hard clamp to +-1e6 (mod_neuro_evo.py:57-59,366).
+// followed by the reference's hard clamp to +-1e6 (mod_neuro_evo.py:57-59,366): torch.clamp keeps a NaN, so the clamp is two
+// comparisons (fminf(fmaxf(v, lo), hi) returns lo for a NaN: a diverged actor would come back finite).
 __global__ void ga_mutate_kernel(float *w, int64_t stride, int32_t member, const int32_t *idx, const int32_t *kind,
                                  const float *z, const float *strength, int32_t n)
 {
@@ -929,7 +930,7 @@ __global__ void ga_mutate_kernel(float *w, int64_t stride, int32_t member, const
   for (int i = 0; i < n; ++i) {
     float v = p[idx[i]];
     if (kind[i] == 0) v = v + z[i] * (strength[i] * v); else v = z[i];
-    v = fminf(fmaxf(v, -1000000.0f), 1000000.0f);
+    v = v > 1000000.0f ? 1000000.0f : (v < -1000000.0f ? -1000000.0f : v);
     p[idx[i]] = v;
   }
 }
@@ -974,7 +975,7 @@ int serl_ga_crossover(serl_ctx *c, float *weights, int64_t stride, int32_t ma, i
 int serl_ga_mutate(serl_ctx *c, float *weights, int64_t stride, int32_t member, const int32_t *idx, const int32_t *kind,
                    const float *z, const float *strength, int32_t n, void *stream)
 {
-  if (!c || !weights || n < 0) return fail(SERL_E_INVALID, "serl_ga_mutate: bad argument");
+  if (!c || !weights || n < 0 || (n > 0 && (!idx || !kind || !z || !strength))) return fail(SERL_E_INVALID, "serl_ga_mutate: bad argument");
   if (n == 0) return SERL_OK;
   HIP_TRY(hipSetDevice(c->device));
   hipLaunchKernelGGL(ga_mutate_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, weights, stride, member, idx, kind, z, strength, n);
