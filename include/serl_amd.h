@@ -365,17 +365,28 @@ int serl_ga_novelty(serl_ctx *ctx, const float *weights, int64_t stride, int32_t
                     const float *states, const float *actions, int32_t batch, float *novelty, void *stream);
 
 /* ---- device replay rings (base/core/replay_memory.py:21-31 `add`, base/core/agent.py:101-112) ---------------------------
- * A ring is f32 [capacity][20] rows (obs7, a3, next_obs7, r, done, cost) in HBM.  One job appends the rows of one stored
- * episode -- staged[episode][0 .. length), what serl_rollout wrote to `transitions` -- to ring slots
- * (position + k) % capacity in step order, k = rank of the row among the rows taken: all of them, or (cost_only) the
- * cost-flagged ones, compacted (agent.critical_buffer).  The first `skip` ranks are not written (an episode longer than
- * the ring leaves only its tail, as sequential add() calls would).  The host keeps position / fill of every ring. */
+ * A ring is f32 [capacity][W] rows (obs S, action A, next_obs S, r, done, cost), W = 2 S + A + 3, in HBM -- the dense
+ * layout serl_rollout writes to `transitions`, so a ring row equals a staged row bit for bit.  One job appends the rows of
+ * one stored episode -- staged[episode][0 .. length) -- to ring slots (position + k) % capacity in step order, k = rank of
+ * the row among the rows taken: all of them, or (cost_only) the cost-flagged ones (row[W - 1] != 0), compacted
+ * (agent.critical_buffer).  The first `skip` ranks are not written (an episode longer than the ring leaves only its tail,
+ * as sequential add() calls would).  The host keeps position / fill of every ring.
+ *   serl_replay_scatter        rows of the attitude task: S = 7, A = 3, W = 20.
+ *   serl_replay_scatter_rows   rows of any env configuration: 1 <= state_dim <= 64, 1 <= action_dim <= 16 (the range of
+ *                              the networks; SERL_E_UNSUPPORTED outside it, nothing launched).  staged is
+ *                              [episodes][rows_per_episode][W].  Same jobs, same meaning; any W, odd ones included: rows
+ *                              move with 16 B accesses when W % 4 == 0 and the ring and the episode are 16 B aligned, with
+ *                              8 B accesses likewise for even W, with 4 B accesses otherwise.  A job without a ring, with
+ *                              capacity < 1, position outside [0, capacity), length > rows_per_episode or a negative
+ *                              field is skipped; length == 0 and skip == rows taken are no-ops, as in serl_replay_scatter. */
 typedef struct serl_replay_job {
   float *ring;
   int32_t capacity, position, episode, length, cost_only, skip;
 } serl_replay_job;
 int serl_replay_scatter(serl_ctx *ctx, const float *staged, int64_t rows_per_episode, const serl_replay_job *jobs /* device */,
                         int32_t n_jobs, void *stream);
+int serl_replay_scatter_rows(serl_ctx *ctx, const float *staged, int64_t rows_per_episode, int32_t state_dim, int32_t action_dim,
+                             const serl_replay_job *jobs /* device */, int32_t n_jobs, void *stream);
 
 /* calc_smoothness (base/core/utils.py:82-120) of n_episodes action traces of DIFFERENT lengths in one launch:
  *   Y = fft(y, N) per channel, N = |lengths[e]|;  S = sum_c sum_{1 <= i < N/2} |Y_i,c|^2 * dt * f_i * 2 / N  with

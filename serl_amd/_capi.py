@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get('SERL_LIB') or os.path.join(os.path.dirname(os.path.ab
 EXPORTS = ['serl_abi_version', 'serl_last_error', 'serl_param_count', 'serl_ctx_create', 'serl_ctx_destroy',
            'serl_ctx_load_build', 'serl_rollout', 'serl_rollout_multi', 'serl_dyn_open_loop', 'serl_debug_profile', 'serl_debug_mixed_placement', 'serl_last_rollout_ms', 'serl_last_rollout_info', 'serl_ga_clone', 'serl_ga_crossover',
            'serl_ga_mutate', 'serl_ga_scaled_perturb', 'serl_abi_layout', 'serl_ga_sensitivity', 'serl_ga_novelty',
-           'serl_replay_scatter', 'serl_env_state_dim', 'serl_env_action_dim',
+           'serl_replay_scatter', 'serl_replay_scatter_rows', 'serl_env_state_dim', 'serl_env_action_dim',
            'serl_smoothness', 'serl_smoothness_work_size', 'serl_ga_distill', 'serl_host_sample_slots',
            'serl_venv_state_bytes', 'serl_venv_reset', 'serl_venv_step']
 
@@ -111,6 +111,7 @@ def lib():
     L.serl_ga_sensitivity.argtypes = [VP, VP, ctypes.c_int64, i32, i32, i32, i32, i32, VP, i32, VP, i32, VP, VP]
     L.serl_ga_novelty.argtypes = [VP, VP, ctypes.c_int64, i32, i32, i32, i32, i32, VP, i32, VP, VP, i32, VP, VP]
     L.serl_replay_scatter.argtypes = [VP, VP, ctypes.c_int64, VP, i32, VP]
+    L.serl_replay_scatter_rows.argtypes = [VP, VP, ctypes.c_int64, i32, i32, VP, i32, VP]
     L.serl_smoothness.argtypes = [VP, VP, ctypes.c_int64, VP, i32, i32, ctypes.c_double, VP, VP, VP]
     L.serl_smoothness_work_size.argtypes = [i32, i32]
     L.serl_ga_distill.argtypes = [VP, VP, ctypes.c_int64, i32, i32, i32, i32, i32, i32, VP, VP, VP, i32, VP, i32, VP, VP, ctypes.c_float, VP]

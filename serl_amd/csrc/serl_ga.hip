@@ -10,11 +10,14 @@
 //                         sum_a (action - actor(state))^2 -- the distance of SSNE.get_distance / sort_groups_by_distance
 //                         (:411-445), all (actor, batch) pairs of an epoch in one launch.
 //   serl_replay_scatter   append whole stored episodes (rows the rollout kernel wrote) to device replay rings; cost-flagged
-//                         rows compacted for the critical rings (base/core/agent.py:101-112).
+//                         rows compacted for the critical rings (base/core/agent.py:101-112).  20-float rows (attitude).
+//   serl_replay_scatter_rows   the same append for rows of any width 2 S + A + 3 (every env configuration), the rows of a
+//                         job moved as one flat stream so that consecutive lanes touch consecutive addresses.
 //
 // f32 throughout like the reference's torch CPU kernels (the summation order differs: agreement is to f32 rounding).
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stdint.h>
 #include "serl_ctx.h"
 
 namespace {
@@ -241,6 +244,94 @@ __global__ void __launch_bounds__(256) replay_scatter_kernel(const float *staged
   }
 }
 
+// ---- rows of any width (serl_replay_scatter_rows) ---------------------------------------------------------------------
+// A row is W = 2 S + A + 3 floats and rings / staged episodes are dense, so the rows a job takes are moved as a flat
+// stream of V-float vectors (V | W): consecutive lanes move consecutive vectors, whatever W is.
+template <int V> struct RowVec;
+template <> struct RowVec<4> { typedef float4 type; };
+template <> struct RowVec<2> { typedef float2 type; };
+template <> struct RowVec<1> { typedef float type; };
+
+constexpr int kRowsParts = 16;    // workgroups that may share the span of one job (grid.y)
+
+// every row of the job: staged rows [skip, length) are ONE contiguous span of floats, and it lands on the ring as at most
+// two (before and after the wrap).  Workgroup `part` of `parts` takes every parts-th tile of 256 vectors.
+template <int V>
+__device__ void scatter_span(const float *src, const ReplayJob &j, int W, int part, int parts)
+{
+  typedef typename RowVec<V>::type vec;
+  const vec *s = reinterpret_cast<const vec *>(src);
+  vec *d = reinterpret_cast<vec *>(j.ring);
+  const int64_t nv = W / V;
+  const int64_t ring = (int64_t)j.capacity * nv, hi = (int64_t)j.length * nv, stride = (int64_t)parts * 256;
+  int64_t i = (int64_t)j.skip * nv + (int64_t)part * 256 + threadIdx.x;
+  if (i >= hi) return;
+  int64_t o = ((int64_t)j.position * nv + i) % ring;
+  for (; i < hi; i += stride, o += stride) {
+    if (o >= ring) o %= ring;          // (the wrap: once per job unless the ring is shorter than a tile)
+    d[o] = s[i];
+  }
+}
+
+// the cost-flagged rows of the job, compacted: 256 rows at a time are ranked (ballot + prefix count, as in
+// replay_scatter_kernel), the taken ones listed in LDS in rank order, and the listed rows are then moved like a span --
+// consecutive lanes write consecutive vectors of the ring.
+template <int V>
+__device__ void scatter_flagged(const float *src, const ReplayJob &j, int W, int *wsum, int *taken)
+{
+  typedef typename RowVec<V>::type vec;
+  const vec *s = reinterpret_cast<const vec *>(src);
+  vec *d = reinterpret_cast<vec *>(j.ring);
+  const int nv = W / V;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  int64_t base = 0;                    // rows taken before this tile (the same in every thread)
+  for (int r0 = 0; r0 < j.length; r0 += 256) {
+    const int r = r0 + t;
+    const bool take = r < j.length && src[(size_t)r * W + (W - 1)] != 0.0f;
+    const unsigned long long bal = __ballot(take);
+    if (lane == 0) wsum[w] = __popcll(bal);
+    __syncthreads();
+    int before = 0;
+    for (int i = 0; i < w; ++i) before += wsum[i];
+    if (take) taken[before + __popcll(bal & ((1ull << lane) - 1ull))] = r;
+    const int n = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    __syncthreads();
+    const int64_t first = j.skip > base ? (int64_t)j.skip - base : 0;       // ranks below `skip` are not written
+    for (int64_t e = first * nv + t; e < (int64_t)n * nv; e += 256) {
+      const int k = (int)(e / nv), col = (int)(e - (int64_t)k * nv);
+      const int64_t slot = ((int64_t)j.position + base + k) % j.capacity;
+      d[slot * nv + col] = s[(int64_t)taken[k] * nv + col];
+    }
+    base += n;
+    __syncthreads();                   // wsum / taken are rewritten by the next tile
+  }
+}
+
+// grid = (jobs, parts).  The access width is what the addresses allow: 16 B when W % 4 == 0 and both bases are 16 B
+// aligned (then every row, and the wrap, falls on a 16 B boundary), 8 B likewise for even W, 4 B otherwise.  A job the
+// host filled in wrongly (no ring, capacity < 1, position outside the ring, length > rows_per_episode) is left alone.
+__global__ void __launch_bounds__(256) replay_scatter_rows_kernel(const float *staged, int64_t T, int W, const ReplayJob *jobs)
+{
+  __shared__ int wsum[4], taken[256];
+  const ReplayJob j = jobs[blockIdx.x];
+  if (!j.ring || j.capacity < 1 || j.position < 0 || j.position >= j.capacity || j.episode < 0 || j.length < 1 || j.length > T ||
+      j.skip < 0 || j.skip >= j.length)
+    return;
+  if (j.cost_only && blockIdx.y != 0) return;
+  const float *src = staged + (size_t)j.episode * T * W;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(j.ring);
+  const int V = (W % 4 == 0 && bits % 16 == 0) ? 4 : (W % 2 == 0 && bits % 8 == 0) ? 2 : 1;
+  if (j.cost_only) {
+    if (V == 4) scatter_flagged<4>(src, j, W, wsum, taken);
+    else if (V == 2) scatter_flagged<2>(src, j, W, wsum, taken);
+    else scatter_flagged<1>(src, j, W, wsum, taken);
+  } else {
+    if (V == 4) scatter_span<4>(src, j, W, blockIdx.y, gridDim.y);
+    else if (V == 2) scatter_span<2>(src, j, W, blockIdx.y, gridDim.y);
+    else scatter_span<1>(src, j, W, blockIdx.y, gridDim.y);
+  }
+}
+
 int check_net(const serl_ctx *c, int S, int H, int L, int A, int act, size_t lds_bytes, const char *who)
 {
   if (S < 1 || S > 64 || A < 1 || A > 16 || H < 2 || H > 256 || L < 0 || L > 16 || act < 0 || act > 2)
@@ -300,6 +391,25 @@ int serl_replay_scatter(serl_ctx *c, const float *staged, int64_t rows_per_episo
   if (n_jobs == 0) return SERL_OK;
   HIP_TRY(hipSetDevice(c->device));
   hipLaunchKernelGGL(replay_scatter_kernel, dim3(n_jobs), dim3(256), 0, (hipStream_t)stream, staged, rows_per_episode,
+                     reinterpret_cast<const ReplayJob *>(jobs));
+  HIP_TRY(hipGetLastError());
+  return SERL_OK;
+}
+
+int serl_replay_scatter_rows(serl_ctx *c, const float *staged, int64_t rows_per_episode, int32_t state_dim, int32_t action_dim,
+                             const serl_replay_job *jobs, int32_t n_jobs, void *stream)
+{
+  if (!c || !staged || !jobs || n_jobs < 0 || rows_per_episode <= 0)
+    return serl_fail(SERL_E_INVALID, "serl_replay_scatter_rows: bad argument");
+  if (state_dim < 1 || state_dim > 64 || action_dim < 1 || action_dim > 16)
+    return serl_fail(SERL_E_UNSUPPORTED, "serl_replay_scatter_rows: state_dim / action_dim out of range (1..64 / 1..16)");
+  if (n_jobs == 0) return SERL_OK;
+  const int W = 2 * state_dim + action_dim + 3;
+  // one workgroup moves 256 x 16 B per pass: enough of them per job that a 2 001-step episode is not one workgroup's work
+  const int64_t tiles = (rows_per_episode * W + 1023) / 1024;
+  const int parts = (int)(tiles < kRowsParts ? tiles : kRowsParts);
+  HIP_TRY(hipSetDevice(c->device));
+  hipLaunchKernelGGL(replay_scatter_rows_kernel, dim3(n_jobs, parts), dim3(256), 0, (hipStream_t)stream, staged, rows_per_episode, W,
                      reinterpret_cast<const ReplayJob *>(jobs));
   HIP_TRY(hipGetLastError());
   return SERL_OK;

@@ -26,6 +26,15 @@ def _actor_from_row(args, spec, row, device):
     return actor.to(device)
 
 
+def _child_ring(cap, dev, engine, spec, parent):
+    """the empty buffer of a distillation child: rows of the parents' dims, which must be the actors' (spec)"""
+    S, A = getattr(parent, 'state_dim', spec.state_dim), getattr(parent, 'action_dim', spec.action_dim)
+    if (S, A) != (spec.state_dim, spec.action_dim):
+        raise ValueError('distillation: the parents\' rings hold rows of state_dim %d, action_dim %d, the actors take state_dim %d, '
+                         'action_dim %d' % (S, A, spec.state_dim, spec.action_dim))
+    return replay.DeviceReplay(cap, dev, engine, S, A)
+
+
 def update_parameters(child, optim, batch, p1, p2, critic):
     """GeneticAgent.update_parameters (genetic_agent.py:22-59)"""
     state = batch[0]
@@ -53,7 +62,7 @@ def distilation_crossover(args, engine, spec, weights, first, second, buffers, c
     dev = weights.device
     P = spec.param_count
     cap = int(args.individual_bs)
-    buf = replay.DeviceReplay(cap, dev, engine)
+    buf = _child_ring(cap, dev, engine, spec, buffers[first])
     buf.add_latest_from(buffers[first], cap // 2)
     buf.add_latest_from(buffers[second], cap // 2)
     buf.shuffle(rng)
@@ -71,7 +80,7 @@ def distilation_crossover(args, engine, spec, weights, first, second, buffers, c
         for _ in range(iters):
             losses.append(update_parameters(child, optim, buf.sample(batch_size, rng), p1, p2, critic))
     row = pack_actor(child).to(dev)
-    return row, buf, replay.DeviceReplay(cap, dev, engine)
+    return row, buf, buf.like()
 
 
 # ---- all distillations of an epoch in one launch ----------------------------------------------------------------------
@@ -140,7 +149,7 @@ def distil_batch(args, engine, spec, weights, pairs, buffers, critic, rng=random
     cap = int(args.individual_bs)
     bufs, slots, nsteps, batch = [], [], [], []
     for first, second in pairs:
-        buf = replay.DeviceReplay(cap, dev, engine)
+        buf = _child_ring(cap, dev, engine, spec, buffers[first])
         buf.add_latest_from(buffers[first], cap // 2)
         buf.add_latest_from(buffers[second], cap // 2)
         buf.shuffle(rng)
@@ -178,4 +187,4 @@ def distil_batch(args, engine, spec, weights, pairs, buffers, critic, rng=random
                                             spec.activation_id, states.data_ptr(), targets.data_ptr(), keep.data_ptr(), states.shape[1],
                                             sl_t.data_ptr(), sl.shape[1], ns_t.data_ptr(), bt_t.data_ptr(), ctypes.c_float(1e-3),
                                             ctypes.c_void_p(stream)), 'serl_ga_distill')
-    return [(child[k, :P], bufs[k], replay.DeviceReplay(cap, dev, engine)) for k in range(K)]
+    return [(child[k, :P], bufs[k], bufs[k].like()) for k in range(K)]

@@ -38,20 +38,30 @@ class GenerationResult:
     rl_episode: Optional[Episode]     # the RL actor's exploration episode (agent.py:269), None without an RL actor
     kernel_ms: float
     stored: Optional[list] = None     # (_defer_store) [(agent, episode index, steps, cost steps)] of the episodes to store
-    staged: Optional[torch.Tensor] = None   # (_defer_store) the staged transition rows [episodes, T, 20]
+    staged: Optional[torch.Tensor] = None   # (_defer_store) the staged transition rows [episodes, T, 2 S + A + 3]
 
 
-def store_transitions(rows, agent, replay_buffer=None, counters=None, engine=None):
-    """rows: f32 [n, 20] = (obs7, a3, next_obs7, r, done, cost) of ONE stored episode (device tensor or array) -> the
-    buffers of agent.py:101-112 and the counters of agent.py:111-125 (see replay.store_episodes)."""
+def store_transitions(rows, agent, replay_buffer=None, counters=None, engine=None, state_dim=None, action_dim=None):
+    """rows: f32 [n, 2 S + A + 3] = (obs S, action A, next_obs S, r, done, cost) of ONE stored episode (device tensor or
+    array) -> the buffers of agent.py:101-112 and the counters of agent.py:111-125 (see replay.store_episodes).
+    state_dim / action_dim: the env configuration's (builds.env_dims); None = those of the first DeviceReplay ring among
+    the buffers, the attitude task's 7 / 3 without one."""
     from . import replay
     rows = torch.as_tensor(rows)
     n = rows.shape[0]
-    nc = int((rows[:, 19] != 0).sum())
+    if state_dim is None or action_dim is None:
+        rings = [b for b in (replay_buffer, getattr(agent, 'buffer', None), getattr(agent, 'critical_buffer', None))
+                 if isinstance(b, replay.DeviceReplay)]
+        state_dim, action_dim = (rings[0].state_dim, rings[0].action_dim) if rings else (7, 3)
+    if rows.dim() != 2 or rows.shape[1] != replay.row_width(state_dim, action_dim):
+        raise ValueError('store_transitions: rows of shape %s are not transitions of state_dim %d, action_dim %d'
+                         % (tuple(rows.shape), state_dim, action_dim))
+    nc = int((rows[:, rows.shape[1] - 1] != 0).sum())
     if rows.is_cuda:
-        replay.store_episodes(engine or default_engine(), rows[None].contiguous(), [(agent, 0, n, nc)], replay_buffer, counters)
+        replay.store_episodes(engine or default_engine(), rows[None].contiguous(), [(agent, 0, n, nc)], replay_buffer, counters,
+                              state_dim=state_dim, action_dim=action_dim)
     else:                          # host rows can only feed host-side buffers (objects with add(*transition))
-        replay.store_episodes(None, rows[None], [(agent, 0, n, nc)], replay_buffer, counters)
+        replay.store_episodes(None, rows[None], [(agent, 0, n, nc)], replay_buffer, counters, state_dim=state_dim, action_dim=action_dim)
 
 
 def _actor_of(agent):
@@ -80,8 +90,8 @@ def evaluate_generation(pop: Sequence, rl_agent=None, *, args, mode='nominal', t
                [pop*num_evals (+1)] / [1] (generated in the kernel); None = base reference
     rl_noise : f64 [T, 3] clipped exploration noise; None = drawn here as agent.py:90-93 would
     store    : append the transitions of every member's last evaluation and of the RL episode to the buffers
-    env_config / incremental : builds.env_config(name) for the other env configurations (the attitude task by default; the
-               device replay rings hold the attitude task's rows only: use list-backed buffers with the others)
+    env_config / incremental : builds.env_config(name) for the other env configurations (the attitude task by default);
+               DeviceReplay rings among the buffers must have been made with that configuration's dims (builds.env_dims)
     _defer_store : (evaluate_generation_sharded) stage the transitions but leave the buffers alone; the list of stored
                episodes and the staged rows come back as result.stored / result.staged"""
     engine = engine or default_engine()
@@ -242,7 +252,8 @@ def evaluate_generation_sharded(pop: Sequence, rl_agent=None, *, args, mode='nom
             a_, e_, n_, c_ = g.stored[-1]
             allb = torch.cat([allb, torch.as_tensor(g.staged[e_:e_ + 1]).to(allb.device)])
             items.append((rl_agent, n_pop, n_, c_))
-        replay.store_episodes(engine, allb, items, replay_buffer, counters)
+        S_, A_ = builds.env_dims(env_config, incremental)
+        replay.store_episodes(engine, allb, items, replay_buffer, counters, state_dim=S_, action_dim=A_)
     return GenerationResult(pop=res, rl_episode=g.rl_episode, kernel_ms=g.kernel_ms)
 
 

@@ -2,9 +2,11 @@
 
 The reference keeps a Python list of `Transition` tuples per buffer (shared buffer of the RL learner, `buffer` and
 `critical_buffer` of every GeneticAgent) and appends to it one tuple per env step (base/core/agent.py:101-112).  Here a
-buffer is one f32 tensor `rows[capacity, 20]` in HBM -- the row layout the rollout kernel writes,
-(obs[7], action[3], next_obs[7], reward, done, cost) -- and whole episodes are appended by ONE scatter kernel
-(`serl_replay_scatter`, include/serl_amd.h): every stored episode of a generation to the shared ring, to its agent's
+buffer is one f32 tensor `rows[capacity, 2 S + A + 3]` in HBM -- the row layout the rollout kernel writes,
+(obs[S], action[A], next_obs[S], reward, done, cost); 20 floats for the attitude task (S = 7, A = 3), 8 to 38 for the
+other env configurations (builds.env_dims) -- and whole episodes are appended by ONE scatter kernel
+(`serl_replay_scatter` for 20-float rows, `serl_replay_scatter_rows` for every other width, include/serl_amd.h): every
+stored episode of a generation to the shared ring, to its agent's
 ring, and its cost-flagged rows compacted into the agent's critical ring.  Nothing crosses to the host per step.
 
 Index semantics are the reference's, slot for slot, and every random draw is made on the host from the same python
@@ -16,7 +18,30 @@ import ctypes, random
 import numpy as np
 import torch
 
-ROW = 20          # obs7 | action3 | next_obs7 | reward | done | cost
+ROW = 20          # obs7 | action3 | next_obs7 | reward | done | cost   (the attitude task, the default of DeviceReplay)
+
+
+def row_width(state_dim, action_dim):
+    """floats per transition row: obs S | action A | next_obs S | reward | done | cost"""
+    return 2 * int(state_dim) + int(action_dim) + 3
+
+
+def split_rows(rows, state_dim=7, action_dim=3):
+    """rows [B, 2 S + A + 3] -> (state [B,S], action [B,A], next_state [B,S], reward [B,1], done [B,1]) like ReplayMemory.sample"""
+    S, A = int(state_dim), int(action_dim)
+    if rows.shape[-1] != row_width(S, A):
+        raise ValueError('rows of %d floats are not transitions of state_dim %d, action_dim %d (%d floats)'
+                         % (rows.shape[-1], S, A, row_width(S, A)))
+    return rows[:, 0:S], rows[:, S:S + A], rows[:, S + A:2 * S + A], rows[:, 2 * S + A:2 * S + A + 1], rows[:, 2 * S + A + 1:2 * S + A + 2]
+
+
+class _Split:
+    """`DeviceReplay.split(rows)` on the class cuts 20-float rows (the attitude task); `ring.split(rows)` cuts rows of the
+    ring's own dims."""
+
+    def __get__(self, ring, owner=None):
+        S, A = (7, 3) if ring is None else (ring.state_dim, ring.action_dim)
+        return lambda rows: split_rows(rows, S, A)
 
 
 def sample_many(n, k, calls, rng=random):
@@ -53,11 +78,15 @@ def sample_many(n, k, calls, rng=random):
 class DeviceReplay:
     """Uniform replay ring on the GPU with the interface of replay_memory.ReplayMemory."""
 
-    def __init__(self, capacity, device, engine=None):
+    def __init__(self, capacity, device, engine=None, state_dim=7, action_dim=3):
         self.capacity = int(capacity)
         self.device = torch.device(device)
         self.engine = engine
-        self.rows = torch.zeros(self.capacity, ROW, dtype=torch.float32, device=self.device)
+        self.state_dim, self.action_dim = int(state_dim), int(action_dim)
+        if self.state_dim < 1 or self.action_dim < 1:
+            raise ValueError('DeviceReplay: state_dim and action_dim must be positive (got %d, %d)' % (self.state_dim, self.action_dim))
+        self.row = row_width(self.state_dim, self.action_dim)
+        self.rows = torch.zeros(self.capacity, self.row, dtype=torch.float32, device=self.device)
         self.position = 0
         self.size = 0
 
@@ -66,6 +95,15 @@ class DeviceReplay:
 
     def reset(self):
         self.position, self.size = 0, 0
+
+    def like(self, capacity=None):
+        """an empty ring of this ring's dims, device and engine"""
+        return DeviceReplay(self.capacity if capacity is None else capacity, self.device, self.engine, self.state_dim, self.action_dim)
+
+    def _same_dims(self, other, what):
+        if (other.state_dim, other.action_dim) != (self.state_dim, self.action_dim):
+            raise ValueError('%s: the source ring holds rows of state_dim %d, action_dim %d, this ring of state_dim %d, action_dim %d'
+                             % (what, other.state_dim, other.action_dim, self.state_dim, self.action_dim))
 
     # ---- appends ----------------------------------------------------------------------------------------------
     def _advance(self, n):
@@ -82,8 +120,11 @@ class DeviceReplay:
         self.append_rows(torch.from_numpy(r.astype(np.float32))[None])
 
     def append_rows(self, rows):
-        """rows f32 [n, 20] (device or host), appended in order like n calls of add()"""
+        """rows f32 [n, self.row] (device or host), appended in order like n calls of add()"""
         rows = torch.as_tensor(rows, dtype=torch.float32).to(self.device)
+        if rows.dim() != 2 or rows.shape[1] != self.row:
+            raise ValueError('append_rows: rows of shape %s do not fit a ring of %d-float rows (state_dim %d, action_dim %d)'
+                             % (tuple(rows.shape), self.row, self.state_dim, self.action_dim))
         n = rows.shape[0]
         if n == 0:
             return
@@ -111,9 +152,11 @@ class DeviceReplay:
         return self.rows[torch.from_numpy(self.latest_slots(latest)).to(self.device)]
 
     def add_content_of(self, other):
+        self._same_dims(other, 'add_content_of')
         self.append_rows(other.get_latest(self.capacity))
 
     def add_latest_from(self, other, latest):
+        self._same_dims(other, 'add_latest_from')
         self.append_rows(other.get_latest(latest))
 
     def shuffle(self, rng=random):
@@ -124,10 +167,7 @@ class DeviceReplay:
             self.rows[:self.size] = self.rows[torch.as_tensor(perm, dtype=torch.int64, device=self.device)]
 
     # ---- sampling ----------------------------------------------------------------------------------------------
-    @staticmethod
-    def split(rows):
-        """rows [B, 20] -> (state [B,7], action [B,3], next_state [B,7], reward [B,1], done [B,1]) like ReplayMemory.sample"""
-        return rows[:, 0:7], rows[:, 7:10], rows[:, 10:17], rows[:, 17:18], rows[:, 18:19]
+    split = _Split()          # split(rows) -> (state, action, next_state, reward, done): see _Split, split_rows
 
     def sample_slots(self, batch_size, rng=random):
         return rng.sample(range(self.size), batch_size)
@@ -150,7 +190,9 @@ class _Job(ctypes.Structure):
 def scatter_episodes(engine, staged, jobs):
     """Append stored episodes to rings with one kernel launch.
 
-    staged : f32 [E, T, 20] device tensor the rollout kernel wrote (`transitions`)
+    staged : f32 [E, T, W] device tensor the rollout kernel wrote (`transitions`), W = 2 S + A + 3; every ring of the call
+             holds rows of that width (ValueError otherwise).  20-float rows go through serl_replay_scatter, every other
+             width through serl_replay_scatter_rows.
     jobs   : list of (ring: DeviceReplay, episode index, n_steps, cost_only, n_rows) in the order the reference would
              have add()-ed them (agent.py:101-112: shared buffer, agent.buffer, agent.critical_buffer per step; rings
              are independent, so per-ring order is what matters); n_rows = n_steps, or the episode's cost-step count
@@ -158,6 +200,16 @@ def scatter_episodes(engine, staged, jobs):
     from . import _capi
     if not jobs:
         return
+    if staged.dim() != 3:
+        raise ValueError('scatter_episodes: staged must be [episodes, rows per episode, row width], got %s' % (tuple(staged.shape),))
+    S, A = jobs[0][0].state_dim, jobs[0][0].action_dim
+    for ring, _, n, _, _ in jobs:
+        if (ring.state_dim, ring.action_dim) != (S, A) or ring.row != staged.shape[2]:
+            raise ValueError('scatter_episodes: staged rows have %d floats, a ring holds rows of state_dim %d, action_dim %d (%d floats), '
+                             'the first ring of state_dim %d, action_dim %d' % (staged.shape[2], ring.state_dim, ring.action_dim, ring.row, S, A))
+        if int(n) > staged.shape[1]:
+            raise ValueError('scatter_episodes: an episode of %d steps in staged rows of %d per episode' % (int(n), staged.shape[1]))
+    staged = staged.contiguous()
     arr = (_Job * len(jobs))()
     # rows a later job of this launch (or the tail of the same job) overwrites are never written: a row survives iff fewer
     # than `capacity` rows follow it on its ring -- the state n sequential add() calls would leave, without write races
@@ -174,8 +226,12 @@ def scatter_episodes(engine, staged, jobs):
     dev = staged.device
     buf = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _capi.check(engine.lib.serl_replay_scatter(engine.ctx, staged.data_ptr(), int(staged.shape[1]), buf.data_ptr(), len(jobs), stream),
-                'serl_replay_scatter')
+    if (S, A) == (7, 3):
+        _capi.check(engine.lib.serl_replay_scatter(engine.ctx, staged.data_ptr(), int(staged.shape[1]), buf.data_ptr(), len(jobs), stream),
+                    'serl_replay_scatter')
+    else:
+        _capi.check(engine.lib.serl_replay_scatter_rows(engine.ctx, staged.data_ptr(), int(staged.shape[1]), S, A, buf.data_ptr(), len(jobs),
+                                                        stream), 'serl_replay_scatter_rows')
 
 
 def store_episodes(engine, staged, items, replay_buffer=None, counters=None, state_dim=7, action_dim=3):
@@ -184,10 +240,10 @@ def store_episodes(engine, staged, items, replay_buffer=None, counters=None, sta
     items : [(agent, episode index in `staged`, n_steps, n_cost_steps)] in the reference's order (member by member, then
             the RL actor).  Every episode goes to `replay_buffer` (the learner's shared buffer) and to agent.buffer, its
             cost-flagged rows to agent.critical_buffer; num_frames / gen_frames advance by the steps, num_episodes by one
-            per episode.  Buffers that are DeviceReplay rings are filled by ONE serl_replay_scatter launch; any other
+            per episode.  Buffers that are DeviceReplay rings are filled by ONE scatter launch (scatter_episodes); any other
             object with the reference's `add(*transition)` is fed tuple by tuple from a host copy (compatibility with
-            the reference's list-backed ReplayMemory).  Rows are (obs S, action A, next_obs S, reward, done, cost); the
-            device rings hold the attitude task's 20-float rows (S = 7, A = 3) only."""
+            the reference's list-backed ReplayMemory).  Rows are (obs S, action A, next_obs S, reward, done, cost); a
+            DeviceReplay ring must have been made with the same state_dim / action_dim (ValueError otherwise)."""
     S, A = int(state_dim), int(action_dim)
     jobs, host = [], []
     for agent, e, n, nc in items:
@@ -197,9 +253,10 @@ def store_episodes(engine, staged, items, replay_buffer=None, counters=None, sta
             if ring is None:
                 continue
             if isinstance(ring, DeviceReplay):
-                if (S, A) != (7, 3):
-                    raise NotImplementedError('DeviceReplay rings hold the 20-float rows of the attitude task; use list-backed '
-                                              'buffers (ReplayMemory) for the other env configurations')
+                if (ring.state_dim, ring.action_dim) != (S, A):
+                    raise ValueError('store_episodes: a DeviceReplay ring of state_dim %d, action_dim %d cannot take transitions of '
+                                     'state_dim %d, action_dim %d: construct the rings with the env configuration\'s dims '
+                                     '(builds.env_dims)' % (ring.state_dim, ring.action_dim, S, A))
                 jobs.append((ring, e, n, cost_only, rows))
             else:
                 host.append((ring, e, n, cost_only))
