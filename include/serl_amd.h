@@ -422,6 +422,74 @@ int serl_ga_distill(serl_ctx *ctx, float *child, int64_t stride, int32_t n_pairs
 long long serl_host_sample_slots(const uint32_t *words, long long n_words, int32_t n, int32_t k, int32_t calls, int32_t *out,
                                  int32_t out_stride);
 
+/* ---- the TD3 learner: K consecutive gradient updates as one launch (SERL_ABI_VERSION stays 9: serl_abi_layout and every struct
+ * above are unchanged; this descriptor has a layout self-check of its own, serl_td3_layout) ---------------------------------------
+ * Agent.train_rl (base/core/agent.py:155-186) calls TD3.update_parameters (base/core/td3.py:123-198) once per frame of the
+ * generation.  serl_td3_train runs n_updates of them back to back for n_learners independent learners, one workgroup each, reading
+ * the minibatches straight from a device replay ring.  Every array is a DEVICE pointer owned by the caller; the call is asynchronous
+ * on the stream; nothing is allocated or synchronised.
+ *   networks   actor / actor_target: the packed actor row of serl_rollout_desc (state_dict order).  critic / critic_target: the
+ *              TRAINED parameters of the reference's Critic (td3.py:17-85; 64-64 hidden units, activation_actor, the project's
+ *              LayerNorm: unbiased std, eps 1e-6 on the std) as one row, critic 1 then critic 2, each
+ *                W1[64][S+A] b1[64] g1[64] be1[64]  W2[64][64] b2[64] g2[64] be2[64]  Wo[64] bo[1]
+ *              = serl_td3_param_count(S, A) floats in all (10 370 at S + A = 10).  The reference's bnorm_* parameters take no part
+ *              in forward, get no gradient (their .grad stays None: Adam and the norm clip skip them) and are not in the row.
+ *   state      per learner, updated in place: the four rows, Adam's first and second moments of actor and critic (actor_m / _v,
+ *              critic_m / _v, laid out like the rows) and adam_steps i32 [n_learners][2] = {critic steps, actor steps} taken so
+ *              far, so that a second call continues the first.
+ *   inputs     ring f32 [capacity][2 S + A + 3] (the rows serl_rollout writes: obs, action, next_obs, reward, done, cost);
+ *              slots i32 [n_updates][slot_cols], the first `batch` columns of a row are the minibatch of that update, drawn by the
+ *              host (a slot outside [0, capacity) is clamped into it); target_noise f32 [n_updates][batch][A] standard-normal draws
+ *              (the kernel applies * noise_sd and the clamp to +-noise_clip); caps_noise f32 [actor updates][batch][S] uniform
+ *              [0, 1) draws, one block per ACTOR update of the call in order, or NULL = CAPS off (lambda_s, lambda_t, eps_sd unused).
+ *   update u   iteration = iteration0 + u + 1, exactly td3.py:123-198:
+ *                next_a = clamp(noise + actor_target(s'), -1, 1);  target_q = r + gamma * (1 - done) * min(Q1', Q2')
+ *                td = mse(Q1, target_q) + mse(Q2, target_q); one gradient-norm clip over BOTH critics (coef = max_grad_norm /
+ *                (norm + 1e-6), applied when below 1); Adam (torch defaults, torch.optim.Adam's bias correction) with lr
+ *                if iteration % policy_update_freq == 0:  pg = -mean(Q1(s, actor(s))) [+ lambda_t * mse(a, actor(s)) + lambda_s *
+ *                mse(a, actor(s + eps_sd * u)) with a the BATCH action in both terms, as the reference writes them]; clip; Adam;
+ *                critic_target <- (1 - tau) critic_target + tau critic; the same for actor_target unless update_actor_target == 0
+ *                (the reference's use_champion_target).
+ *   outputs    td_loss f32 [n_updates]; pg_loss f32 [n_updates], written at actor updates only (other entries left as given).
+ *              n_updates == 0 leaves every buffer bit for bit unchanged.
+ *   learners   every per-learner array has a stride (in elements) between learners; ring_stride / slots_stride / noise_stride /
+ *              caps_stride may be 0 (shared).  A learner's result does not depend on the others or on its place in the grid.
+ *   work       serl_td3_work_bytes(n_learners, S, A, hidden, num_layers, batch) bytes of scratch (0 = shape not compiled).
+ * Arithmetic is f32 with this library's summation order: agreement with a float64 run is to rounding, not bit for bit.
+ * Compiled for hidden a multiple of 4 in 4 .. 128, 0 .. 4 hidden layers, S 1 .. 16, A 1 .. 4, batch 1 .. 128: any other positive
+ * shape returns SERL_E_UNSUPPORTED with nothing launched (the caller trains in PyTorch); NULL or out-of-range arguments return
+ * SERL_E_INVALID before any device work. */
+typedef struct serl_td3_desc {
+  int32_t state_dim, action_dim, hidden, num_layers, activation;   /* the actor (enum serl_activation also drives the critic) */
+  int32_t n_learners, batch, n_updates;
+  int32_t capacity, slot_cols;
+  int32_t policy_update_freq, iteration0, update_actor_target, pad0;
+  float lr, gamma, tau, noise_sd, noise_clip, lambda_s, lambda_t, eps_sd, max_grad_norm, pad1;
+  float *actor, *actor_target, *actor_m, *actor_v;
+  int64_t actor_stride;             /* floats between learners, >= serl_param_count */
+  float *critic, *critic_target, *critic_m, *critic_v;
+  int64_t critic_stride;            /* >= serl_td3_param_count */
+  int32_t *adam_steps;              /* [n_learners][2] */
+  const float *ring;
+  int64_t ring_stride;
+  const int32_t *slots;
+  int64_t slots_stride;
+  const float *target_noise;
+  int64_t noise_stride;
+  const float *caps_noise;
+  int64_t caps_stride;
+  float *td_loss, *pg_loss;
+  int64_t loss_stride;              /* >= n_updates */
+  void *work;
+  int64_t work_bytes;
+} serl_td3_desc;
+/* floats of the critic row: 2 * (64 (S + A) + 64 * 64 + 6 * 64 + 64 + 1); 0 for dims < 1 */
+int serl_td3_param_count(int state_dim, int action_dim);
+int64_t serl_td3_work_bytes(int32_t n_learners, int32_t state_dim, int32_t action_dim, int32_t hidden, int32_t num_layers, int32_t batch);
+/* layout self-check like serl_abi_layout: sizeof(serl_td3_desc), then offsetof of each member in declaration order */
+int serl_td3_layout(int32_t *out, int32_t capacity);
+int serl_td3_train(serl_ctx *ctx, const serl_td3_desc *desc, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

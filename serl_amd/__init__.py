@@ -14,6 +14,7 @@ and the host-side mirror of the reference interface for this path:
   SSNE operators and epoch     base/core/mod_neuro_evo.py           (ga.py, ssne.py, distill.py)
   DeviceReplay rings           base/core/replay_memory.py:12-103, agent.py:101-112   (replay.py)
   member sharding + RCCL all-gather of fitness                      (distributed.py)
+  TD3, Critic                  base/core/td3.py:17-198; a generation's updates (Agent.train_rl, agent.py:155-186) as one launch (td3.py)
   CitationVecEnv               CitationEnv.reset / .step, envs/phlabenv.py:401-482: N envs stepped by any torch policy (venv.py)
 
 The HIP extension is mandatory: importing the evaluator on a machine without the built
@@ -26,8 +27,10 @@ from .generation import evaluate_generation, validate_actor, GenerationResult
 from .replay import DeviceReplay
 from .ssne import SSNE
 from .venv import CitationVecEnv
-from . import refsignals, metrics, ga, distributed, builds, replay, ssne
+from .td3 import TD3, Critic
+from .actor import pack_critic, unpack_critic
+from . import refsignals, metrics, ga, distributed, builds, replay, ssne, td3
 
 __all__ = ['Actor', 'GeneticAgent', 'pack_actor', 'pack_population', 'NetSpec', 'Episode', 'RolloutEngine',
            'evaluate_pop', 'validate_pop', 'make_evaluate', 'PopResult', 'evaluate_generation', 'validate_actor',
-           'GenerationResult', 'DeviceReplay', 'SSNE', 'CitationVecEnv', 'replay', 'ssne', 'refsignals', 'metrics', 'ga', 'distributed', 'builds']
+           'GenerationResult', 'DeviceReplay', 'SSNE', 'CitationVecEnv', 'TD3', 'Critic', 'pack_critic', 'unpack_critic', 'td3', 'replay', 'ssne', 'refsignals', 'metrics', 'ga', 'distributed', 'builds']

@@ -13,7 +13,8 @@ EXPORTS = ['serl_abi_version', 'serl_last_error', 'serl_param_count', 'serl_ctx_
            'serl_ga_mutate', 'serl_ga_scaled_perturb', 'serl_abi_layout', 'serl_ga_sensitivity', 'serl_ga_novelty',
            'serl_replay_scatter', 'serl_replay_scatter_rows', 'serl_env_state_dim', 'serl_env_action_dim',
            'serl_smoothness', 'serl_smoothness_work_size', 'serl_ga_distill', 'serl_host_sample_slots',
-           'serl_venv_state_bytes', 'serl_venv_reset', 'serl_venv_step']
+           'serl_venv_state_bytes', 'serl_venv_reset', 'serl_venv_step',
+           'serl_td3_train', 'serl_td3_work_bytes', 'serl_td3_param_count', 'serl_td3_layout']
 
 
 class BuildDesc(ctypes.Structure):
@@ -57,6 +58,25 @@ class VenvDesc(ctypes.Structure):
                 ('state_dim', ctypes.c_int32), ('action_dim', ctypes.c_int32), ('max_steps', ctypes.c_int32), ('pad0', ctypes.c_int32),
                 ('t_max', ctypes.c_double), ('faults', VP), ('ref', VP), ('ref_stride', ctypes.c_int64), ('ref_spec', VP),
                 ('ref_spec_stride', ctypes.c_int64), ('sensor_noise', VP), ('sensor_row', VP), ('err0', VP), ('tick0', VP), ('state', VP)]
+
+
+class Td3Desc(ctypes.Structure):
+    """serl_td3_desc: the fused TD3 learner (checked against the library by serl_td3_layout, not part of serl_abi_layout)"""
+    _fields_ = ([(n, ctypes.c_int32) for n in ('state_dim', 'action_dim', 'hidden', 'num_layers', 'activation', 'n_learners', 'batch',
+                                               'n_updates', 'capacity', 'slot_cols', 'policy_update_freq', 'iteration0',
+                                               'update_actor_target', 'pad0')] +
+                [(n, ctypes.c_float) for n in ('lr', 'gamma', 'tau', 'noise_sd', 'noise_clip', 'lambda_s', 'lambda_t', 'eps_sd',
+                                               'max_grad_norm', 'pad1')] +
+                [('actor', VP), ('actor_target', VP), ('actor_m', VP), ('actor_v', VP), ('actor_stride', ctypes.c_int64),
+                 ('critic', VP), ('critic_target', VP), ('critic_m', VP), ('critic_v', VP), ('critic_stride', ctypes.c_int64),
+                 ('adam_steps', VP), ('ring', VP), ('ring_stride', ctypes.c_int64), ('slots', VP), ('slots_stride', ctypes.c_int64),
+                 ('target_noise', VP), ('noise_stride', ctypes.c_int64), ('caps_noise', VP), ('caps_stride', ctypes.c_int64),
+                 ('td_loss', VP), ('pg_loss', VP), ('loss_stride', ctypes.c_int64), ('work', VP), ('work_bytes', ctypes.c_int64)])
+
+
+def expected_td3_layout():
+    """What serl_td3_layout() must return for Td3Desc to be right."""
+    return [ctypes.sizeof(Td3Desc)] + [getattr(Td3Desc, n).offset for n, _ in Td3Desc._fields_]
 
 
 # serl_rollout_desc.kernel_hint (enum serl_kernel_hint)
@@ -119,9 +139,13 @@ def lib():
     L.serl_venv_state_bytes.argtypes = [i32]
     L.serl_venv_reset.argtypes = [VP, ctypes.POINTER(VenvDesc), VP, VP, VP]
     L.serl_venv_step.argtypes = [VP, ctypes.POINTER(VenvDesc), VP, i32, VP, VP, VP, VP, VP, VP, VP, VP]
+    L.serl_td3_train.argtypes = [VP, ctypes.POINTER(Td3Desc), VP]
+    L.serl_td3_work_bytes.argtypes = [i32] * 6
+    L.serl_td3_param_count.argtypes = [ctypes.c_int, ctypes.c_int]
+    L.serl_td3_layout.argtypes = [VP, ctypes.c_int32]
     for f in EXPORTS:
         if f not in ('serl_last_error',):
-            getattr(L, f).restype = ctypes.c_longlong if f in ('serl_host_sample_slots', 'serl_venv_state_bytes') else ctypes.c_int
+            getattr(L, f).restype = ctypes.c_longlong if f in ('serl_host_sample_slots', 'serl_venv_state_bytes', 'serl_td3_work_bytes') else ctypes.c_int
     if L.serl_abi_version() != ABI_VERSION:
         raise RuntimeError('serl_amd: ABI version mismatch (library %d, binding %d): rebuild with `python serl_amd/build.py`'
                            % (L.serl_abi_version(), ABI_VERSION))
@@ -131,11 +155,18 @@ def lib():
     if n != len(want) or list(got) != want:
         raise RuntimeError('serl_amd: struct layout of the ctypes mirrors differs from the library (serl_abi_layout): '
                            'library %s, binding %s' % (list(got)[:n], want))
+    want = expected_td3_layout()
+    got = (ctypes.c_int32 * len(want))()
+    n = L.serl_td3_layout(got, len(want))
+    if n != len(want) or list(got) != want:
+        raise RuntimeError('serl_amd: layout of the Td3Desc mirror differs from the library (serl_td3_layout): library %s, binding %s'
+                           % (list(got)[:n], want))
     _lib = L
     return L
 
 
 E_UNSUPPORTED = -3      # enum serl_status SERL_E_UNSUPPORTED
+E_INVALID = -1          # SERL_E_INVALID
 
 
 def check(rc, what):

@@ -206,3 +206,21 @@ def unpack_into(actor, row):
         n = v.numel()
         v.copy_(row[off:off + n].view(v.shape))
         off += n
+
+
+def pack_critic(critic):
+    """Flat f32 row of a td3.Critic's trained parameters as serl_td3_train reads it: critic 1, then critic 2, each
+    W1[64][S+A] b1 gamma1 beta1  W2[64][64] b2 gamma2 beta2  Wo[64] bo (include/serl_amd.h)."""
+    return torch.cat([p.detach().reshape(-1) for p in critic.parameters()]).to(torch.float32).cpu()
+
+
+def unpack_critic(critic, row):
+    """Write a packed critic row back into a td3.Critic's parameters."""
+    off = 0
+    row = row.detach().cpu()
+    with torch.no_grad():
+        for p in critic.parameters():
+            n = p.numel()
+            p.copy_(row[off:off + n].view(p.shape))
+            off += n
+    return off

@@ -1,0 +1,578 @@
+// serl_td3.hip -- a generation's TD3 gradient updates as ONE launch.
+//
+// Reference: Agent.train_rl (base/core/agent.py:155-186) calls TD3.update_parameters (base/core/td3.py:123-198) once per frame the
+// generation produced -- up to ~100 000 strictly sequential updates of a minibatch of 86 rows through a 7-72x4-3 actor and a twin
+// 10-64-64-1 critic, as eager PyTorch a few hundred tiny launches each.  Here one workgroup per learner runs the whole chain of
+// updates: minibatches are read straight from the device replay ring through slots the host drew, the Gaussian / uniform draws come
+// pre-drawn, parameters and Adam moments live in global memory (four rows plus gradients of a 17 k-parameter actor and a 10 k-parameter
+// critic do not fit an LDS; they stay L2-resident), activations move through two LDS tiles in [feature][sample] layout, and what the
+// backward passes need again is kept on a tape in the caller's workspace in the same layout.  Phases are separated by __syncthreads
+// only; no workgroup ever waits on another.  f32 like torch; summation orders are this file's (agreement with float64 to rounding,
+// tests/test_gpu_td3.py).
+//
+// Thread map of the dense phases (512 threads): sample b = t & 127, output group g = t >> 7 (uniform per wavefront, so a weight is
+// a scalar operand and an activation one LDS read per four multiply-adds).  Weight gradients are batch-reduction products over the
+// two tiles: one 4 x 4 block of dW per thread, rows and columns interleaved so that a wavefront's 16 B reads fall into different banks
+// (row stride 132 floats).
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include "serl_ctx.h"
+
+namespace {
+
+constexpr int NT = 512;                 // threads per workgroup
+constexpr int NW = NT / 64;             // wavefronts
+constexpr int BP = 128;                 // samples per row of a global activation array = the largest minibatch
+constexpr int NG = NT / BP;             // output groups
+constexpr int LP = 132;                 // floats per row of an LDS tile (128 samples + 4: consecutive rows start 4 banks apart)
+constexpr int TILE_ROWS = 128;          // the widest layer
+constexpr int HC = 64;                  // hidden units of the critic (td3.py:24)
+constexpr int MAX_IN = 20;              // S + A at most
+
+struct Td3Args {
+  serl_td3_desc d;
+  int64_t work_floats;                  // per learner
+};
+
+__device__ __forceinline__ float t_act(float v, int act)
+{
+  if (act == SERL_ACT_TANH) return tanhf(v);
+  if (act == SERL_ACT_ELU) return v > 0.0f ? v : expm1f(v);
+  return v > 0.0f ? v : 0.01f * v;
+}
+
+// derivative of the activation, from its VALUE a
+__device__ __forceinline__ float t_dact(float a, int act)
+{
+  if (act == SERL_ACT_TANH) return 1.0f - a * a;
+  if (act == SERL_ACT_ELU) return a > 0.0f ? 1.0f : a + 1.0f;
+  return a > 0.0f ? 1.0f : 0.01f;
+}
+
+// one Linear of a packed row: offsets of W[N][K], b[N] and, with ln, gamma[N], beta[N]; fin: 0 = activation, 1 = tanh, 2 = identity
+struct Layer { int oW, ob, og, obe, N, K, ln, fin; };
+struct Net { int critic, S, H, L, A; };          // critic: one twin of the Critic (K0 = S + A); else the actor
+
+__device__ __forceinline__ int net_layers(const Net &n) { return n.critic ? 3 : n.L + 2; }
+__device__ __forceinline__ int net_width(const Net &n) { return n.critic ? HC : n.H; }
+__device__ __forceinline__ int net_in(const Net &n) { return n.critic ? n.S + n.A : n.S; }
+
+__device__ __forceinline__ Layer net_layer(const Net &n, int l)
+{
+  Layer y;
+  y.og = y.obe = 0; y.ln = 0; y.fin = 0;
+  if (n.critic) {
+    const int K0 = n.S + n.A, l1 = HC * K0 + 3 * HC, l2 = l1 + HC * HC + 3 * HC;
+    if (l == 0) { y.oW = 0; y.N = HC; y.K = K0; y.ln = 1; }
+    else if (l == 1) { y.oW = l1; y.N = HC; y.K = HC; y.ln = 1; }
+    else { y.oW = l2; y.N = 1; y.K = HC; y.fin = 2; }
+  } else {
+    const int H = n.H, l1 = H * n.S + H, ls = H * H + 3 * H;
+    if (l == 0) { y.oW = 0; y.N = H; y.K = n.S; }
+    else if (l <= n.L) { y.oW = l1 + (l - 1) * ls; y.N = H; y.K = H; y.ln = 1; }
+    else { y.oW = l1 + n.L * ls; y.N = n.A; y.K = H; y.fin = 1; }
+  }
+  y.ob = y.oW + y.N * y.K;
+  if (y.ln) { y.og = y.ob + y.N; y.obe = y.og + y.N; }
+  return y;
+}
+
+// floats of a tape: per layer the normalised values n [W][BP] and the outputs h [W][BP], then the standard deviations [layers][BP]
+__host__ __device__ inline int64_t tape_floats(int layers, int width) { return ((int64_t)2 * layers * width + layers) * BP; }
+
+struct Ctx {
+  float *T0, *T1;               // LDS tiles [TILE_ROWS][LP]
+  float *red, *red4;            // LDS [NW], [NG][BP]
+  int t, b, g, wave, lane;
+  int B, B4, act;
+  bool live;                    // this wavefront holds samples of the minibatch
+};
+
+__device__ __forceinline__ float block_sum(const Ctx &c, float v)
+{
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  __syncthreads();
+  if (c.lane == 0) c.red[c.wave] = v;
+  __syncthreads();
+  float s = 0.0f;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) s += c.red[w];
+  return s;
+}
+
+// the sum over the four output groups of a sample
+__device__ __forceinline__ float sample_sum(const Ctx &c, float v)
+{
+  __syncthreads();
+  c.red4[c.g * BP + c.b] = v;
+  __syncthreads();
+  return (c.red4[c.b] + c.red4[BP + c.b]) + (c.red4[2 * BP + c.b] + c.red4[3 * BP + c.b]);
+}
+
+// rows [K][BP] of a global array -> an LDS tile
+__device__ __forceinline__ void stage(const Ctx &c, const float *src, int K, float *T)
+{
+  for (int e = c.t; e < K * BP; e += NT) T[(e >> 7) * LP + (e & 127)] = src[e];
+}
+
+typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));      // four consecutive weights of a row that is only 4 B aligned
+
+// Y[i][b] = bias[i] + sum_j W[i][j] X[j][b]
+__device__ __forceinline__ void dense_fwd(const Ctx &c, const float *W, const float *bias, int N, int K, const float *X, float *Y)
+{
+  if (!c.live) return;
+  for (int i0 = 4 * c.g; i0 < N; i0 += 4 * NG) {
+    const int i1 = min(i0 + 1, N - 1), i2 = min(i0 + 2, N - 1), i3 = min(i0 + 3, N - 1);
+    const float *w0 = W + (size_t)i0 * K, *w1 = W + (size_t)i1 * K, *w2 = W + (size_t)i2 * K, *w3 = W + (size_t)i3 * K;
+    float a0 = bias[i0], a1 = bias[i1], a2 = bias[i2], a3 = bias[i3];
+    int j = 0;
+    for (; j + 3 < K; j += 4) {
+      const f4u u0 = *reinterpret_cast<const f4u *>(w0 + j), u1 = *reinterpret_cast<const f4u *>(w1 + j);
+      const f4u u2 = *reinterpret_cast<const f4u *>(w2 + j), u3 = *reinterpret_cast<const f4u *>(w3 + j);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float x = X[(j + q) * LP + c.b];
+        a0 = fmaf(u0[q], x, a0); a1 = fmaf(u1[q], x, a1); a2 = fmaf(u2[q], x, a2); a3 = fmaf(u3[q], x, a3);
+      }
+    }
+    for (; j < K; ++j) {
+      const float x = X[j * LP + c.b];
+      a0 = fmaf(w0[j], x, a0); a1 = fmaf(w1[j], x, a1); a2 = fmaf(w2[j], x, a2); a3 = fmaf(w3[j], x, a3);
+    }
+    Y[i0 * LP + c.b] = a0;
+    if (i0 + 1 < N) Y[(i0 + 1) * LP + c.b] = a1;
+    if (i0 + 2 < N) Y[(i0 + 2) * LP + c.b] = a2;
+    if (i0 + 3 < N) Y[(i0 + 3) * LP + c.b] = a3;
+  }
+}
+
+// Xo[j][b] = sum_i W[i][j] D[i][b]
+__device__ __forceinline__ void dense_bwd_x(const Ctx &c, const float *W, int N, int K, const float *D, float *Xo)
+{
+  if (!c.live) return;
+  for (int j0 = 4 * c.g; j0 < K; j0 += 4 * NG) {
+    const int j1 = min(j0 + 1, K - 1), j2 = min(j0 + 2, K - 1), j3 = min(j0 + 3, K - 1);
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+    if (j0 + 3 < K) {
+#pragma unroll 4
+      for (int i = 0; i < N; ++i) {
+        const float dv = D[i * LP + c.b];
+        const f4u u = *reinterpret_cast<const f4u *>(W + (size_t)i * K + j0);
+        a0 = fmaf(u[0], dv, a0); a1 = fmaf(u[1], dv, a1); a2 = fmaf(u[2], dv, a2); a3 = fmaf(u[3], dv, a3);
+      }
+    } else {
+      for (int i = 0; i < N; ++i) {
+        const float dv = D[i * LP + c.b];
+        const float *w = W + (size_t)i * K;
+        a0 = fmaf(w[j0], dv, a0); a1 = fmaf(w[j1], dv, a1); a2 = fmaf(w[j2], dv, a2); a3 = fmaf(w[j3], dv, a3);
+      }
+    }
+    Xo[j0 * LP + c.b] = a0;
+    if (j0 + 1 < K) Xo[(j0 + 1) * LP + c.b] = a1;
+    if (j0 + 2 < K) Xo[(j0 + 2) * LP + c.b] = a2;
+    if (j0 + 3 < K) Xo[(j0 + 3) * LP + c.b] = a3;
+  }
+}
+
+// gW[i][j] (+)= sum_b D[i][b] X[j][b] over the samples below B4; a thread's block: rows a + ti r, columns q + tj s (r, s < 4)
+__device__ __forceinline__ void dense_bwd_w(const Ctx &c, const float *D, const float *X, int N, int K, float *gW, bool accum)
+{
+  const int ti = (N + 3) >> 2, tj = (K + 3) >> 2;
+  for (int tile = c.t; tile < ti * tj; tile += NT) {
+    const int a = tile / tj, q = tile - a * tj;
+    const float *dr[4], *xr[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { dr[r] = D + min(a + ti * r, N - 1) * LP; xr[r] = X + min(q + tj * r, K - 1) * LP; }
+    float acc[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) acc[r][s] = 0.0f;
+    for (int b = 0; b < c.B4; b += 4) {
+      float4 dv[4], xv[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { dv[r] = *reinterpret_cast<const float4 *>(dr[r] + b); xv[r] = *reinterpret_cast<const float4 *>(xr[r] + b); }
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+          acc[r][s] = fmaf(dv[r].x, xv[s].x, fmaf(dv[r].y, xv[s].y, fmaf(dv[r].z, xv[s].z, fmaf(dv[r].w, xv[s].w, acc[r][s]))));
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int i = a + ti * r, j = q + tj * s;
+        if (i < N && j < K) gW[(size_t)i * K + j] = accum ? gW[(size_t)i * K + j] + acc[r][s] : acc[r][s];
+      }
+  }
+}
+
+// g1[i] (+)= sum_b D[i][b], and with tn: g2[i] (+)= sum_b D[i][b] tn[i][b]; one wavefront per row
+__device__ __forceinline__ void row_grads(const Ctx &c, const float *D, const float *tn, int N, float *g1, float *g2, bool accum)
+{
+  for (int i = c.wave; i < N; i += NW) {
+    float s = 0.0f, p = 0.0f;
+    for (int b = c.lane; b < c.B4; b += 64) {
+      const float dv = D[i * LP + b];
+      s += dv;
+      if (tn) p = fmaf(dv, tn[i * BP + b], p);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); p += __shfl_xor(p, o); }
+    if (c.lane == 0) {
+      g1[i] = accum ? g1[i] + s : s;
+      if (tn) g2[i] = accum ? g2[i] + p : p;
+    }
+  }
+}
+
+// the project's LayerNorm (unbiased std, eps on the std) and the activation, in place on Y; n, h and the std go to the tape
+__device__ __forceinline__ void ln_act(const Ctx &c, float *Y, const float *gam, const float *bet, int N, float *tn, float *th, float *tsd)
+{
+  float s = 0.0f;
+  for (int i = c.g; i < N; i += NG) s += Y[i * LP + c.b];
+  const float mean = sample_sum(c, s) / (float)N;
+  float v = 0.0f;
+  for (int i = c.g; i < N; i += NG) { const float dv = Y[i * LP + c.b] - mean; v = fmaf(dv, dv, v); }
+  const float sd = sqrtf(sample_sum(c, v) / (float)(N - 1));
+  const float Dn = sd + 1e-6f;
+  for (int i = c.g; i < N; i += NG) {
+    const float n = (Y[i * LP + c.b] - mean) / Dn;
+    const float h = t_act(gam[i] * n + bet[i], c.act);
+    Y[i * LP + c.b] = h;
+    if (tn) { tn[i * BP + c.b] = n; th[i * BP + c.b] = h; }
+  }
+  if (tn && c.g == 0) tsd[c.b] = sd;
+}
+
+// D = dL/dh of a LayerNorm layer -> dL/dy in place; dgamma / dbeta to gg / gbe when given
+__device__ __forceinline__ void ln_act_bwd(const Ctx &c, float *D, const float *gam, int N, const float *tn, const float *th, const float *tsd,
+                                           float *gg, float *gbe, bool accum)
+{
+  float s1 = 0.0f, s2 = 0.0f;
+  for (int i = c.g; i < N; i += NG) {
+    const float dz = D[i * LP + c.b] * t_dact(th[i * BP + c.b], c.act);
+    D[i * LP + c.b] = dz;
+    const float dn = dz * gam[i];
+    s1 += dn;
+    s2 = fmaf(dn, tn[i * BP + c.b], s2);
+  }
+  s1 = sample_sum(c, s1);
+  s2 = sample_sum(c, s2);
+  if (gg) row_grads(c, D, tn, N, gbe, gg, accum);
+  __syncthreads();
+  const float sd = tsd[c.b];
+  const float Dn = sd + 1e-6f, m = s1 / (float)N;
+  const float k2 = sd > 0.0f ? s2 / ((float)(N - 1) * sd) : 0.0f;
+  for (int i = c.g; i < N; i += NG) D[i * LP + c.b] = (D[i * LP + c.b] * gam[i] - m) / Dn - tn[i * BP + c.b] * k2;
+}
+
+// forward pass of `net` (parameters w) on the global input x [K0][BP]; -> the LDS tile that holds the output rows.  With a tape the
+// outputs of every layer (and n, std of the LayerNorm ones) are kept for mlp_bwd.
+__device__ __forceinline__ float *mlp_fwd(const Ctx &c, const Net &net, const float *w, const float *x, float *tape)
+{
+  const int nl = net_layers(net), Wd = net_width(net);
+  float *Tin = c.T0, *Tout = c.T1;
+  __syncthreads();
+  stage(c, x, net_in(net), Tin);
+  __syncthreads();
+  for (int l = 0; l < nl; ++l) {
+    const Layer y = net_layer(net, l);
+    dense_fwd(c, w + y.oW, w + y.ob, y.N, y.K, Tin, Tout);
+    __syncthreads();
+    float *tn = tape ? tape + (size_t)(2 * l) * Wd * BP : nullptr, *th = tape ? tn + (size_t)Wd * BP : nullptr;
+    float *tsd = tape ? tape + (size_t)2 * nl * Wd * BP + (size_t)l * BP : nullptr;
+    if (y.ln) ln_act(c, Tout, w + y.og, w + y.obe, y.N, tn, th, tsd);
+    else if (y.fin != 2) {
+      for (int i = c.g; i < y.N; i += NG) {
+        const float v = Tout[i * LP + c.b];
+        const float h = y.fin == 1 ? tanhf(v) : t_act(v, c.act);
+        Tout[i * LP + c.b] = h;
+        if (th) th[i * BP + c.b] = h;
+      }
+    }
+    __syncthreads();
+    float *s = Tin; Tin = Tout; Tout = s;
+  }
+  return Tin;
+}
+
+// backward pass from D = dL/d(the last Linear's output) (an LDS tile, rows of the last layer): parameter gradients to g (laid out
+// like the row; added to when accum), unless g is NULL; with want_dx the gradient of the input is returned (an LDS tile, K0 rows).
+__device__ __forceinline__ float *mlp_bwd(const Ctx &c, const Net &net, const float *w, const float *x, const float *tape, float *D, float *g, bool accum,
+                          bool want_dx)
+{
+  const int nl = net_layers(net), Wd = net_width(net);
+  float *X = D == c.T0 ? c.T1 : c.T0;
+  for (int l = nl - 1; l >= 0; --l) {
+    const Layer y = net_layer(net, l);
+    __syncthreads();
+    if (g) {
+      stage(c, l == 0 ? x : tape + (size_t)(2 * (l - 1) + 1) * Wd * BP, y.K, X);
+      __syncthreads();
+      dense_bwd_w(c, D, X, y.N, y.K, g + y.oW, accum);
+      row_grads(c, D, nullptr, y.N, g + y.ob, nullptr, accum);
+      __syncthreads();
+    }
+    if (l == 0 && !want_dx) break;
+    dense_bwd_x(c, w + y.oW, y.N, y.K, D, X);
+    __syncthreads();
+    float *s = D; D = X; X = s;
+    if (l == 0) break;
+    const Layer p = net_layer(net, l - 1);
+    const float *tn = tape + (size_t)(2 * (l - 1)) * Wd * BP, *th = tn + (size_t)Wd * BP;
+    if (p.ln) ln_act_bwd(c, D, w + p.og, p.N, tn, th, tape + (size_t)2 * nl * Wd * BP + (size_t)(l - 1) * BP, g ? g + p.og : nullptr,
+                         g ? g + p.obe : nullptr, accum);
+    else
+      for (int i = c.g; i < p.N; i += NG) D[i * LP + c.b] *= t_dact(th[i * BP + c.b], c.act);
+  }
+  __syncthreads();
+  return D;
+}
+
+// nn.utils.clip_grad_norm_ (coef = max_norm / (norm + 1e-6), applied when below 1) and torch.optim.Adam's step `step` (defaults)
+__device__ __forceinline__ void clip_adam(const Ctx &c, float *w, float *m, float *v, const float *g, int P, int step, float lr, float max_norm)
+{
+  float s = 0.0f;
+  for (int e = c.t; e < P; e += NT) s = fmaf(g[e], g[e], s);
+  const float norm = sqrtf(block_sum(c, s));
+  float coef = max_norm / (norm + 1e-6f);
+  if (!(coef < 1.0f)) coef = 1.0f;
+  const double b1t = pow(0.9, (double)step), b2t = pow(0.999, (double)step);
+  const float step_size = (float)((double)lr / (1.0 - b1t));
+  const float bc2_sqrt = (float)sqrt(1.0 - b2t);
+  // (1 - beta as torch forms them: in double, rounded once -- 1.0f - 0.999f is off by 1.3e-5 of its value)
+  const float beta2 = 0.999f, omb1 = (float)(1.0 - 0.9), omb2 = (float)(1.0 - 0.999), eps = 1e-8f;
+  for (int e = c.t; e < P; e += NT) {
+    const float ge = g[e] * coef;
+    const float m1 = m[e] + (ge - m[e]) * omb1;
+    const float v1 = v[e] * beta2 + ge * ge * omb2;
+    m[e] = m1; v[e] = v1;
+    w[e] -= step_size * m1 / (sqrtf(v1) / bc2_sqrt + eps);
+  }
+  __syncthreads();
+}
+
+__global__ void __launch_bounds__(NT) td3_kernel(Td3Args a)
+{
+  extern __shared__ float lds[];
+  const serl_td3_desc &d = a.d;
+  const int p = blockIdx.x;
+  Ctx c;
+  c.T0 = lds; c.T1 = c.T0 + TILE_ROWS * LP; c.red4 = c.T1 + TILE_ROWS * LP; c.red = c.red4 + NG * BP;
+  float *tq = c.red + 64;               // [BP] target Q
+  c.t = threadIdx.x; c.b = c.t & (BP - 1); c.g = __builtin_amdgcn_readfirstlane(c.t >> 7);
+  c.wave = __builtin_amdgcn_readfirstlane(c.t >> 6); c.lane = c.t & 63;
+  c.B = d.batch; c.B4 = (d.batch + 3) & ~3; c.act = d.activation;
+  c.live = (c.b & 64) < c.B;
+  const int S = d.state_dim, A = d.action_dim, SA = S + A, RW = 2 * S + A + 3, B = d.batch, b = c.b;
+  const Net actor = {0, S, d.hidden, d.num_layers, A}, critic = {1, S, d.hidden, d.num_layers, A};
+  const int Pa = d.hidden * S + d.hidden + d.num_layers * (d.hidden * d.hidden + 3 * d.hidden) + A * d.hidden + A;
+  const int Pc1 = HC * SA + 3 * HC + HC * HC + 3 * HC + HC + 1, Pc = 2 * Pc1;
+  float *wa = d.actor + (size_t)p * d.actor_stride, *wat = d.actor_target + (size_t)p * d.actor_stride;
+  float *ma = d.actor_m + (size_t)p * d.actor_stride, *va = d.actor_v + (size_t)p * d.actor_stride;
+  float *wc = d.critic + (size_t)p * d.critic_stride, *wct = d.critic_target + (size_t)p * d.critic_stride;
+  float *mc = d.critic_m + (size_t)p * d.critic_stride, *vc = d.critic_v + (size_t)p * d.critic_stride;
+  const float *ring = d.ring + (size_t)p * d.ring_stride;
+  const int32_t *slots = d.slots + (size_t)p * d.slots_stride;
+  const float *tnoise = d.target_noise + (size_t)p * d.noise_stride;
+  const float *cnoise = d.caps_noise ? d.caps_noise + (size_t)p * d.caps_stride : nullptr;
+  float *td_loss = d.td_loss + (size_t)p * d.loss_stride, *pg_loss = d.pg_loss + (size_t)p * d.loss_stride;
+  // workspace of this learner: gradients | inputs s, s2, (s, a), (s2, a2) | the actor's tape | the critic's tape
+  float *wk = (float *)d.work + (size_t)p * a.work_floats;
+  float *g = wk;
+  float *in_s = g + ((max(Pa, Pc) + 3) & ~3), *in_s2 = in_s + MAX_IN * BP, *in_sa = in_s2 + MAX_IN * BP, *in_sa2 = in_sa + MAX_IN * BP;
+  float *tape_a = in_sa2 + MAX_IN * BP, *tape_c = tape_a + tape_floats(d.num_layers + 2, d.hidden);
+  int step_c = d.adam_steps[2 * p], step_a = d.adam_steps[2 * p + 1];
+  int n_actor = 0;
+  const float invB = 1.0f / (float)B, invBA = 1.0f / (float)(B * A);
+
+  for (int u = 0; u < d.n_updates; ++u) {
+    const int iteration = d.iteration0 + u + 1;
+    // ---- the minibatch: rows slots[u][0 .. B) of the ring; samples from B on are zeros
+    const bool on = b < B;
+    int slot = on ? slots[(size_t)u * d.slot_cols + b] : 0;
+    slot = min(max(slot, 0), d.capacity - 1);
+    const float *row = ring + (size_t)slot * RW;
+    __syncthreads();
+    if (c.g == 0) {
+      for (int j = 0; j < S; ++j) {
+        const float s = on ? row[j] : 0.0f, s2 = on ? row[SA + j] : 0.0f;
+        in_s[j * BP + b] = s; in_sa[j * BP + b] = s; in_s2[j * BP + b] = s2; in_sa2[j * BP + b] = s2;
+      }
+      for (int k = 0; k < A; ++k) in_sa[(S + k) * BP + b] = on ? row[S + k] : 0.0f;
+    }
+    const float rew = on ? row[2 * S + A] : 0.0f, done = on ? row[2 * S + A + 1] : 0.0f;
+    // ---- target action and target Q (td3.py:137-146)
+    {
+      const float *out = mlp_fwd(c, actor, wat, in_s2, nullptr);
+      if (c.g == 0)
+        for (int k = 0; k < A; ++k) {
+          float nz = on ? tnoise[((size_t)u * B + b) * A + k] * d.noise_sd : 0.0f;
+          nz = fminf(fmaxf(nz, -d.noise_clip), d.noise_clip);
+          in_sa2[(S + k) * BP + b] = fminf(fmaxf(nz + out[k * LP + b], -1.0f), 1.0f);
+        }
+      const float q1 = mlp_fwd(c, critic, wct, in_sa2, nullptr)[b];
+      const float q2 = mlp_fwd(c, critic, wct + Pc1, in_sa2, nullptr)[b];
+      if (c.g == 0) tq[b] = rew + d.gamma * (fminf(q1, q2) * (1.0f - done));
+    }
+    // ---- critic loss and gradients of both twins (td3.py:149-158)
+    float td = 0.0f;
+    for (int k = 0; k < 2; ++k) {
+      float *out = mlp_fwd(c, critic, wc + k * Pc1, in_sa, tape_c);
+      const float e = (on && c.g == 0) ? out[b] - tq[b] : 0.0f;
+      td += block_sum(c, e * e) * invB;
+      if (c.g == 0) out[b] = 2.0f * e * invB;
+      mlp_bwd(c, critic, wc + k * Pc1, in_sa, tape_c, out, g + k * Pc1, false, false);
+    }
+    ++step_c;
+    clip_adam(c, wc, mc, vc, g, Pc, step_c, d.lr, d.max_grad_norm);
+    if (c.t == 0) td_loss[u] = td;
+    if (iteration % d.policy_update_freq != 0) continue;
+    // ---- actor update (td3.py:177-198) with the critic just stepped
+    float pg;
+    {
+      float *out = mlp_fwd(c, actor, wa, in_s, tape_a);
+      float acur[4] = {0.0f, 0.0f, 0.0f, 0.0f}, abat[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      for (int k = 0; k < A; ++k) { acur[k] = out[k * LP + b]; abat[k] = in_sa[(S + k) * BP + b]; }
+      __syncthreads();
+      if (c.g == 0)
+        for (int j = 0; j < SA; ++j) in_sa2[j * BP + b] = j < S ? in_s[j * BP + b] : acur[j - S];
+      float *q = mlp_fwd(c, critic, wc, in_sa2, tape_c);
+      float loss = (on && c.g == 0) ? -q[b] * invB : 0.0f;
+      if (c.g == 0) q[b] = on ? -invB : 0.0f;
+      float *dx = mlp_bwd(c, critic, wc, in_sa2, tape_c, q, nullptr, false, true);
+      float da[4];
+      for (int k = 0; k < A; ++k) da[k] = dx[(S + k) * LP + b];
+      __syncthreads();
+      if (cnoise && on && c.g == 0)
+        for (int k = 0; k < A; ++k) {
+          const float df = abat[k] - acur[k];
+          loss += d.lambda_t * df * df * invBA;
+          da[k] -= d.lambda_t * 2.0f * df * invBA;
+        }
+      if (c.g == 0)
+        for (int k = 0; k < A; ++k) dx[k * LP + b] = da[k] * (1.0f - acur[k] * acur[k]);
+      mlp_bwd(c, actor, wa, in_s, tape_a, dx, g, false, false);
+      if (cnoise) {
+        // state_bar = state + rand * eps_sd; lambda_s * mse(action_batch, actor(state_bar))
+        if (c.g == 0)
+          for (int j = 0; j < S; ++j)
+            in_s2[j * BP + b] = on ? in_s[j * BP + b] + cnoise[((size_t)n_actor * B + b) * S + j] * d.eps_sd : 0.0f;
+        float *ob = mlp_fwd(c, actor, wa, in_s2, tape_a);
+        float abar[4];
+        for (int k = 0; k < A; ++k) abar[k] = ob[k * LP + b];
+        __syncthreads();
+        if (c.g == 0)
+          for (int k = 0; k < A; ++k) {
+            const float df = on ? abat[k] - abar[k] : 0.0f;
+            loss += d.lambda_s * df * df * invBA;
+            ob[k * LP + b] = -d.lambda_s * 2.0f * df * invBA * (1.0f - abar[k] * abar[k]);
+          }
+        mlp_bwd(c, actor, wa, in_s2, tape_a, ob, g, true, false);
+      }
+      pg = block_sum(c, loss);
+    }
+    ++step_a; ++n_actor;
+    clip_adam(c, wa, ma, va, g, Pa, step_a, d.lr, d.max_grad_norm);
+    if (c.t == 0) pg_loss[u] = pg;
+    // ---- soft updates (mod_utils.py:25-28): target = target * (1 - tau) + param * tau
+    const float tau = d.tau;
+    for (int e = c.t; e < Pc; e += NT) wct[e] = wct[e] * (1.0f - tau) + wc[e] * tau;
+    if (d.update_actor_target)
+      for (int e = c.t; e < Pa; e += NT) wat[e] = wat[e] * (1.0f - tau) + wa[e] * tau;
+    __syncthreads();
+  }
+  if (c.t == 0 && d.n_updates > 0) { d.adam_steps[2 * p] = step_c; d.adam_steps[2 * p + 1] = step_a; }
+}
+
+size_t td3_lds_bytes() { return ((size_t)2 * TILE_ROWS * LP + NG * BP + 64 + BP) * sizeof(float); }
+
+int64_t td3_work_floats(int S, int A, int H, int L)
+{
+  const int64_t Pa = (int64_t)H * S + H + (int64_t)L * (H * H + 3 * H) + A * H + A;
+  const int64_t Pc = 2 * ((int64_t)HC * (S + A) + 3 * HC + HC * HC + 3 * HC + HC + 1);
+  const int64_t gmax = ((Pa > Pc ? Pa : Pc) + 3) & ~(int64_t)3;
+  return gmax + 4 * MAX_IN * BP + tape_floats(L + 2, H) + tape_floats(3, HC);
+}
+
+bool td3_shape_ok(int S, int A, int H, int L, int B)
+{
+  return H >= 4 && H <= TILE_ROWS && H % 4 == 0 && L >= 0 && L <= 4 && S >= 1 && S <= 16 && A >= 1 && A <= 4 && B >= 1 && B <= BP;
+}
+
+}  // namespace
+
+extern "C" {
+
+int serl_td3_param_count(int state_dim, int action_dim)
+{
+  if (state_dim < 1 || action_dim < 1) return 0;
+  return 2 * (HC * (state_dim + action_dim) + 3 * HC + HC * HC + 3 * HC + HC + 1);
+}
+
+int64_t serl_td3_work_bytes(int32_t n_learners, int32_t state_dim, int32_t action_dim, int32_t hidden, int32_t num_layers, int32_t batch)
+{
+  if (n_learners < 1 || !td3_shape_ok(state_dim, action_dim, hidden, num_layers, batch)) return 0;
+  return (int64_t)n_learners * td3_work_floats(state_dim, action_dim, hidden, num_layers) * (int64_t)sizeof(float);
+}
+
+int serl_td3_layout(int32_t *out, int32_t capacity)
+{
+#define TD3_OFF(m) (int32_t)offsetof(serl_td3_desc, m)
+  const int32_t v[] = {
+    (int32_t)sizeof(serl_td3_desc),
+    TD3_OFF(state_dim), TD3_OFF(action_dim), TD3_OFF(hidden), TD3_OFF(num_layers), TD3_OFF(activation), TD3_OFF(n_learners), TD3_OFF(batch),
+    TD3_OFF(n_updates), TD3_OFF(capacity), TD3_OFF(slot_cols), TD3_OFF(policy_update_freq), TD3_OFF(iteration0), TD3_OFF(update_actor_target),
+    TD3_OFF(pad0), TD3_OFF(lr), TD3_OFF(gamma), TD3_OFF(tau), TD3_OFF(noise_sd), TD3_OFF(noise_clip), TD3_OFF(lambda_s), TD3_OFF(lambda_t),
+    TD3_OFF(eps_sd), TD3_OFF(max_grad_norm), TD3_OFF(pad1), TD3_OFF(actor), TD3_OFF(actor_target), TD3_OFF(actor_m), TD3_OFF(actor_v),
+    TD3_OFF(actor_stride), TD3_OFF(critic), TD3_OFF(critic_target), TD3_OFF(critic_m), TD3_OFF(critic_v), TD3_OFF(critic_stride),
+    TD3_OFF(adam_steps), TD3_OFF(ring), TD3_OFF(ring_stride), TD3_OFF(slots), TD3_OFF(slots_stride), TD3_OFF(target_noise),
+    TD3_OFF(noise_stride), TD3_OFF(caps_noise), TD3_OFF(caps_stride), TD3_OFF(td_loss), TD3_OFF(pg_loss), TD3_OFF(loss_stride),
+    TD3_OFF(work), TD3_OFF(work_bytes)};
+#undef TD3_OFF
+  const int n = (int)(sizeof(v) / sizeof(v[0]));
+  for (int i = 0; i < n && i < capacity; ++i)
+    if (out) out[i] = v[i];
+  return n;
+}
+
+int serl_td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream)
+{
+  if (!c || !d) return serl_fail(SERL_E_INVALID, "serl_td3_train: NULL context or descriptor");
+  if (!d->actor || !d->actor_target || !d->actor_m || !d->actor_v || !d->critic || !d->critic_target || !d->critic_m || !d->critic_v ||
+      !d->adam_steps || !d->ring || !d->slots || !d->target_noise || !d->td_loss || !d->pg_loss || !d->work)
+    return serl_fail(SERL_E_INVALID, "serl_td3_train: NULL array (only caps_noise may be NULL: CAPS off)");
+  if (d->state_dim < 1 || d->action_dim < 1 || d->hidden < 1 || d->num_layers < 0 || d->batch < 1 || d->activation < 0 || d->activation > 2)
+    return serl_fail(SERL_E_INVALID, "serl_td3_train: network shape / minibatch / activation");
+  if (d->n_learners < 1 || d->n_updates < 0 || d->capacity < 1 || d->slot_cols < d->batch || d->policy_update_freq < 1 || d->iteration0 < 0)
+    return serl_fail(SERL_E_INVALID, "serl_td3_train: n_learners >= 1, n_updates >= 0, capacity >= 1, slot_cols >= batch, policy_update_freq >= 1, iteration0 >= 0");
+  if ((long long)d->iteration0 + d->n_updates > 2147483646LL) return serl_fail(SERL_E_INVALID, "serl_td3_train: iteration0 + n_updates overflows");
+  if (!(d->lr > 0.0f) || !(d->gamma >= 0.0f) || !(d->tau >= 0.0f && d->tau <= 1.0f) || !(d->noise_sd >= 0.0f) || !(d->noise_clip >= 0.0f) ||
+      !(d->max_grad_norm > 0.0f) || !(d->eps_sd >= 0.0f) || d->lambda_s != d->lambda_s || d->lambda_t != d->lambda_t)
+    return serl_fail(SERL_E_INVALID, "serl_td3_train: lr > 0, gamma >= 0, 0 <= tau <= 1, noise_sd >= 0, noise_clip >= 0, max_grad_norm > 0, eps_sd >= 0");
+  if (!td3_shape_ok(d->state_dim, d->action_dim, d->hidden, d->num_layers, d->batch))
+    return serl_fail(SERL_E_UNSUPPORTED, "serl_td3_train: compiled for hidden a multiple of 4 in 4 .. 128, 0 .. 4 hidden layers, state_dim 1 .. 16, "
+                                         "action_dim 1 .. 4, minibatches of 1 .. 128 rows; other shapes train in PyTorch");
+  const int Pa = serl_param_count(d->state_dim, d->hidden, d->num_layers, d->action_dim), Pc = serl_td3_param_count(d->state_dim, d->action_dim);
+  if (d->actor_stride < Pa || d->critic_stride < Pc) return serl_fail(SERL_E_INVALID, "serl_td3_train: a row stride is smaller than its parameter count");
+  if (d->ring_stride < 0 || d->slots_stride < 0 || d->noise_stride < 0 || d->caps_stride < 0 || d->loss_stride < d->n_updates)
+    return serl_fail(SERL_E_INVALID, "serl_td3_train: negative learner stride, or loss_stride < n_updates");
+  if (d->work_bytes < serl_td3_work_bytes(d->n_learners, d->state_dim, d->action_dim, d->hidden, d->num_layers, d->batch))
+    return serl_fail(SERL_E_INVALID, "serl_td3_train: workspace smaller than serl_td3_work_bytes");
+  const size_t lds = td3_lds_bytes();
+  if (lds > (size_t)c->lds_per_block) return serl_fail(SERL_E_UNSUPPORTED, "serl_td3_train: the activation tiles do not fit this device's LDS per workgroup");
+  if (d->n_updates == 0) return SERL_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  Td3Args a;
+  a.d = *d;
+  a.work_floats = td3_work_floats(d->state_dim, d->action_dim, d->hidden, d->num_layers);
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(td3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(td3_kernel, dim3(d->n_learners), dim3(NT), lds, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return SERL_OK;
+}
+
+}  // extern "C"

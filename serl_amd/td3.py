@@ -1,0 +1,286 @@
+"""The TD3 learner behind the reference's class API (base/core/td3.py:17-198): `Critic`, and `TD3` with `.actor`, `.actor_target`,
+`.critic`, `.critic_target`, `.buffer`, `.critical_buffer`, `update_parameters(batch, iteration, champion_policy)`.
+
+`update_parameters` is one eager update, as the reference runs it.  `train` is what Agent.train_rl (base/core/agent.py:155-186) does
+with it -- one update per frame of the generation, minibatches sampled from the shared replay buffer -- as ONE kernel launch
+(serl_td3_train, include/serl_amd.h): the host draws the minibatch slots from python's `random` stream and the noise from a torch CPU
+generator in the order a CPU run of the reference consumes them, the device does the rest.  Without a GPU, or for a shape the kernel
+is not compiled for, `train` loops `update_parameters` over the same draws.
+"""
+import ctypes
+import random
+import numpy as np
+import torch
+import torch.nn as nn
+from torch.nn import functional as F
+from torch.optim import Adam
+from . import replay as _replay
+from .actor import Actor, LayerNorm, _activation, pack_actor, unpack_into, pack_critic, unpack_critic, ACTIVATION_IDS
+
+MAX_GRAD_NORM = 10.0            # td3.py:13
+CRITIC_HIDDEN = 64              # td3.py:24
+CAPS = {'lambda_s': 0.5, 'lambda_t': 0.1, 'eps_sd': 0.05}          # td3.py:115-120
+# `train` takes the fused path by default because it was measured faster than the eager float32 loop on the same MI355X at the default
+# shape (hidden 72, 3 layers, minibatch 86, CAPS on): tools/bench_td3.py, profiles/td3_fused_timing.json.
+FUSED_DEFAULT = True
+
+
+class _QNet(nn.Module):
+    """one of the twins: Linear(S + A, 64) LayerNorm act, Linear(64, 64) LayerNorm act, Linear(64, 1)"""
+
+    def __init__(self, n_in, activation):
+        super().__init__()
+        self.l1 = nn.Linear(n_in, CRITIC_HIDDEN)
+        self.ln1 = LayerNorm(CRITIC_HIDDEN)
+        self.l2 = nn.Linear(CRITIC_HIDDEN, CRITIC_HIDDEN)
+        self.ln2 = LayerNorm(CRITIC_HIDDEN)
+        self.out = nn.Linear(CRITIC_HIDDEN, 1)
+        self.act = _activation(activation)
+        with torch.no_grad():                   # the output layer starts small (td3.py:46-47)
+            self.out.weight.mul_(0.1)
+            self.out.bias.mul_(0.1)
+
+    def forward(self, x):
+        h = self.act(self.ln1(self.l1(x)))
+        h = self.act(self.ln2(self.l2(h)))
+        return self.out(h)
+
+
+class Critic(nn.Module):
+    """Twin Q-networks on (state, action) -> (q1, q2), the callable `ssne.SSNE(critic=...)` expects.  Only what the reference's Critic
+    trains: its two BatchNorm layers are never called and never get a gradient, so they are left out; parameters() walks critic 1, then
+    critic 2, in the order of the packed row (actor.pack_critic)."""
+
+    def __init__(self, args):
+        super().__init__()
+        self.args = args
+        n_in = args.state_dim + args.action_dim
+        self.q1 = _QNet(n_in, args.activation_actor)
+        self.q2 = _QNet(n_in, args.activation_actor)
+        self.to(getattr(args, 'device', 'cpu'))
+
+    def forward(self, state, action):
+        x = torch.cat((state, action), 1)
+        return self.q1(x), self.q2(x)
+
+
+def critic_param_count(state_dim, action_dim):
+    H = CRITIC_HIDDEN
+    return 2 * (H * (state_dim + action_dim) + 3 * H + H * H + 3 * H + H + 1)
+
+
+def _hard_update(target, source):
+    with torch.no_grad():
+        for t, s in zip(target.parameters(), source.parameters()):
+            t.copy_(s)
+
+
+def _soft_update(target, source, tau):
+    with torch.no_grad():
+        for t, s in zip(target.parameters(), source.parameters()):
+            t.copy_(t * (1.0 - tau) + s * tau)
+
+
+def _pack_adam(optim, params):
+    """(first moments, second moments, steps taken) of a torch Adam over `params`, as packed f32 rows"""
+    m, v, step = [], [], 0
+    for p in params:
+        st = optim.state.get(p, {})
+        m.append(st['exp_avg'].detach().reshape(-1) if 'exp_avg' in st else torch.zeros(p.numel()))
+        v.append(st['exp_avg_sq'].detach().reshape(-1) if 'exp_avg_sq' in st else torch.zeros(p.numel()))
+        if 'step' in st:
+            step = int(st['step'])
+    return torch.cat(m).to(torch.float32).cpu(), torch.cat(v).to(torch.float32).cpu(), step
+
+
+def _unpack_adam(optim, params, m, v, step):
+    off = 0
+    m, v = m.detach().cpu(), v.detach().cpu()
+    for p in params:
+        n = p.numel()
+        optim.state[p] = {'step': torch.tensor(float(step)),
+                          'exp_avg': m[off:off + n].view(p.shape).to(device=p.device, dtype=p.dtype).clone(),
+                          'exp_avg_sq': v[off:off + n].view(p.shape).to(device=p.device, dtype=p.dtype).clone()}
+        off += n
+
+
+def draw_noise(n_updates, batch, state_dim, action_dim, iteration0, policy_update_freq, caps, generator=None):
+    """The draws of n_updates consecutive update_parameters calls from a torch CPU generator, in the order a CPU run of the reference
+    consumes them: per update randn [B, A] (the target-policy noise, td3.py:138), and at actor updates with CAPS rand [B, S]
+    (td3.py:186).  -> (target_noise f32 [n_updates, B, A], caps_noise f32 [actor updates, B, S] or None)"""
+    tn, cn = [], []
+    for u in range(n_updates):
+        tn.append(torch.randn(batch, action_dim, generator=generator))
+        if caps and (iteration0 + u + 1) % policy_update_freq == 0:
+            cn.append(torch.rand(batch, state_dim, generator=generator))
+    tn = torch.stack(tn) if tn else torch.zeros(0, batch, action_dim)
+    if not caps:
+        return tn, None
+    return tn, (torch.stack(cn) if cn else torch.zeros(0, batch, state_dim))
+
+
+class TD3:
+    def __init__(self, args, engine=None):
+        self.args = args
+        self.engine = engine
+        dev = getattr(args, 'device', 'cpu')
+        S, A = args.state_dim, args.action_dim
+        self.buffer = _replay.DeviceReplay(args.individual_bs, dev, engine, S, A)
+        self.critical_buffer = _replay.DeviceReplay(args.individual_bs, dev, engine, S, A)
+        self.actor = Actor(args, init=True)
+        self.actor_target = Actor(args, init=True)
+        self.actor_optim = Adam(self.actor.parameters(), lr=args.lr)
+        self.critic = Critic(args)
+        self.critic_target = Critic(args)
+        self.critic_optim = Adam(self.critic.parameters(), lr=args.lr)
+        self.gamma, self.tau = args.gamma, args.tau
+        _hard_update(self.actor_target, self.actor)
+        _hard_update(self.critic_target, self.critic)
+        self.caps_dict = dict(CAPS) if getattr(args, 'use_caps', False) else None
+        self.last_path = None                   # 'fused' / 'eager': what the most recent train() ran
+
+    # ---- one eager update (td3.py:123-198); also the fallback of train() -------------------------------------------------------------
+    def update_parameters(self, batch, iteration, champion_policy=False, *, noise=None, caps_noise=None):
+        """`noise` (standard-normal [B, A]) and `caps_noise` (uniform [B, S]) replace the draws from torch's global generator."""
+        a = self.args
+        state, action, next_state, reward, done = batch
+        dev = next(self.critic.parameters()).device
+        state, action, next_state, reward, done = (x.to(dev) for x in (state, action, next_state, reward, done))
+        with torch.no_grad():
+            z = torch.randn_like(action) if noise is None else noise.to(action)
+            z = (z * a.noise_sd).clamp(-a.noise_clip, a.noise_clip)
+            next_action = torch.clamp(z + self.actor_target(next_state), -1, 1)
+            q1t, q2t = self.critic_target(next_state, next_action)
+            target_q = reward + (self.gamma * (torch.min(q1t, q2t) * (1 - done))).detach()
+        q1, q2 = self.critic(state, action)
+        td = F.mse_loss(q1, target_q) + F.mse_loss(q2, target_q)
+        self.critic_optim.zero_grad()
+        td.backward()
+        nn.utils.clip_grad_norm_(self.critic.parameters(), MAX_GRAD_NORM)
+        self.critic_optim.step()
+        td_data = td.data.cpu().numpy()
+        pgl = None
+        if iteration % a.policy_update_freq == 0:
+            self.actor_optim.zero_grad()
+            q, _ = self.critic(state, self.actor(state))
+            loss = -torch.mean(q)
+            if self.caps_dict is not None:
+                c = self.caps_dict
+                a_now = self.actor(state)
+                u = torch.rand_like(state) if caps_noise is None else caps_noise.to(state)
+                a_bar = self.actor(state + u * c['eps_sd'])
+                # as the reference writes them: both terms compare with the BATCH action
+                loss = loss + c['lambda_t'] * F.mse_loss(action, a_now) + c['lambda_s'] * F.mse_loss(action, a_bar)
+            loss.backward()
+            nn.utils.clip_grad_norm_(self.actor.parameters(), MAX_GRAD_NORM)
+            self.actor_optim.step()
+            if not champion_policy:
+                _soft_update(self.actor_target, self.actor, self.tau)
+            _soft_update(self.critic_target, self.critic, self.tau)
+            pgl = loss.data.cpu().numpy()
+        return pgl, td_data
+
+    # ---- a generation's updates ---------------------------------------------------------------------------------------------------------
+    def fused_supported(self, device):
+        """would serl_td3_train run this learner's shape on `device`?"""
+        from . import _capi
+        a = self.args
+        if torch.device(device).type != 'cuda' or self.engine is None or not torch.cuda.is_available():
+            return False
+        if a.activation_actor.lower() not in ACTIVATION_IDS:
+            return False
+        return _capi.lib().serl_td3_work_bytes(1, a.state_dim, a.action_dim, a.hidden_size, a.num_layers, int(a.batch_size)) > 0
+
+    def train(self, replay, n_updates, *, iteration0, champion_target=False, rng=random, generator=None, fused=None):
+        """n_updates consecutive updates on minibatches of args.batch_size rows of `replay` (a DeviceReplay), update u with iteration
+        iteration0 + u + 1 -- the loop of Agent.train_rl.  -> {'PG_obj': mean(-pg), 'TD_loss': median(td)} like train_rl.
+        fused: None = the fused kernel where it runs (FUSED_DEFAULT), False = the eager loop, True = the kernel or an error."""
+        a = self.args
+        n_updates, B = int(n_updates), int(a.batch_size)
+        S, A = a.state_dim, a.action_dim
+        if (replay.state_dim, replay.action_dim) != (S, A):
+            raise ValueError('TD3.train: the ring holds rows of state_dim %d, action_dim %d, the learner takes %d, %d'
+                             % (replay.state_dim, replay.action_dim, S, A))
+        if n_updates <= 0:
+            return {'PG_obj': float('nan'), 'TD_loss': float('nan')}
+        if len(replay) < B:
+            raise ValueError('TD3.train: %d rows in the ring, minibatches of %d' % (len(replay), B))
+        slots = _replay.sample_many(len(replay), B, n_updates, rng)
+        freq = int(a.policy_update_freq)
+        tn, cn = draw_noise(n_updates, B, S, A, int(iteration0), freq, self.caps_dict is not None, generator)
+        can = self.fused_supported(replay.device)
+        if fused and not can:
+            raise RuntimeError('TD3.train(fused=True): serl_td3_train does not run this shape / device')
+        use = can and (FUSED_DEFAULT if fused is None else bool(fused))
+        if use:
+            td, pg = self._train_fused(replay, slots, tn, cn, int(iteration0), not champion_target)
+            self.last_path = 'fused'
+        else:
+            td, pg = self._train_eager(replay, slots, tn, cn, int(iteration0), champion_target)
+            self.last_path = 'eager'
+        return {'PG_obj': float(np.mean([-x for x in pg])) if len(pg) else float('nan'), 'TD_loss': float(np.median(td))}
+
+    def _train_eager(self, replay, slots, tn, cn, iteration0, champion_target):
+        td, pg, k = [], [], 0
+        freq = int(self.args.policy_update_freq)
+        for u in range(len(slots)):
+            it = iteration0 + u + 1
+            rows = replay.rows[torch.as_tensor(slots[u], dtype=torch.int64, device=replay.device)]
+            cz = None
+            if cn is not None and it % freq == 0:
+                cz, k = cn[k], k + 1
+            pgl, t = self.update_parameters(replay.split(rows), it, champion_target, noise=tn[u], caps_noise=cz)
+            td.append(float(t))
+            if pgl is not None:
+                pg.append(float(pgl))
+        return td, pg
+
+    def _train_fused(self, replay, slots, tn, cn, iteration0, update_actor_target):
+        from . import _capi
+        a, dev = self.args, replay.device
+        L = _capi.lib()
+        n, B = slots.shape
+        S, A = a.state_dim, a.action_dim
+        ap, cp = list(self.actor.parameters()), list(self.critic.parameters())
+        am, av, astep = _pack_adam(self.actor_optim, ap)
+        cm, cv, cstep = _pack_adam(self.critic_optim, cp)
+        t = lambda x: x.contiguous().to(dev)
+        rows = {k: t(v) for k, v in dict(actor=pack_actor(self.actor), actor_target=pack_actor(self.actor_target), actor_m=am, actor_v=av,
+                                         critic=pack_critic(self.critic), critic_target=pack_critic(self.critic_target), critic_m=cm,
+                                         critic_v=cv).items()}
+        steps = torch.tensor([cstep, astep], dtype=torch.int32, device=dev)
+        sl = t(torch.from_numpy(np.ascontiguousarray(slots, dtype=np.int32)))
+        tn_d = t(tn.to(torch.float32))
+        cn_d = t(cn.to(torch.float32)) if cn is not None else None
+        td = torch.zeros(n, dtype=torch.float32, device=dev)
+        pg = torch.full((n,), float('nan'), dtype=torch.float32, device=dev)
+        wb = int(L.serl_td3_work_bytes(1, S, A, a.hidden_size, a.num_layers, B))
+        work = torch.empty(wb // 4, dtype=torch.float32, device=dev)
+        c = self.caps_dict or {'lambda_s': 0.0, 'lambda_t': 0.0, 'eps_sd': 0.0}
+        d = _capi.Td3Desc(state_dim=S, action_dim=A, hidden=a.hidden_size, num_layers=a.num_layers,
+                          activation=ACTIVATION_IDS[a.activation_actor.lower()], n_learners=1, batch=B, n_updates=n,
+                          capacity=replay.capacity, slot_cols=B, policy_update_freq=int(a.policy_update_freq), iteration0=iteration0,
+                          update_actor_target=int(bool(update_actor_target)), lr=a.lr, gamma=a.gamma, tau=a.tau, noise_sd=a.noise_sd,
+                          noise_clip=a.noise_clip, lambda_s=c['lambda_s'], lambda_t=c['lambda_t'], eps_sd=c['eps_sd'],
+                          max_grad_norm=MAX_GRAD_NORM,
+                          actor=rows['actor'].data_ptr(), actor_target=rows['actor_target'].data_ptr(), actor_m=rows['actor_m'].data_ptr(),
+                          actor_v=rows['actor_v'].data_ptr(), actor_stride=rows['actor'].numel(),
+                          critic=rows['critic'].data_ptr(), critic_target=rows['critic_target'].data_ptr(),
+                          critic_m=rows['critic_m'].data_ptr(), critic_v=rows['critic_v'].data_ptr(), critic_stride=rows['critic'].numel(),
+                          adam_steps=steps.data_ptr(), ring=replay.rows.data_ptr(), ring_stride=0, slots=sl.data_ptr(), slots_stride=0,
+                          target_noise=tn_d.data_ptr(), noise_stride=0, caps_noise=cn_d.data_ptr() if cn_d is not None and cn_d.numel() else
+                          (work.data_ptr() if cn_d is not None else None), caps_stride=0, td_loss=td.data_ptr(), pg_loss=pg.data_ptr(),
+                          loss_stride=n, work=work.data_ptr(), work_bytes=wb)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _capi.check(L.serl_td3_train(self.engine.ctx, ctypes.byref(d), stream), 'serl_td3_train')
+        torch.cuda.synchronize(dev)
+        unpack_into(self.actor, rows['actor'])
+        unpack_into(self.actor_target, rows['actor_target'])
+        unpack_critic(self.critic, rows['critic'])
+        unpack_critic(self.critic_target, rows['critic_target'])
+        cstep, astep = (int(x) for x in steps.cpu())
+        _unpack_adam(self.critic_optim, cp, rows['critic_m'], rows['critic_v'], cstep)
+        if astep:
+            _unpack_adam(self.actor_optim, ap, rows['actor_m'], rows['actor_v'], astep)
+        td, pg = td.cpu().numpy(), pg.cpu().numpy()
+        return list(td), [x for x in pg if not np.isnan(x)]

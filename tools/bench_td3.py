@@ -1,0 +1,113 @@
+#!/usr/bin/env python
+"""ms per TD3 update: the fused launch (serl_td3_train) against the eager float32 PyTorch loop on the same GPU.
+
+The eager loop is the tests' literal restatement of the reference's update (tests/td3_64.py: td3_literal with dtype=float32,
+device='cuda') -- what a SERL user runs today.  Both get the same rows, ring, slots and draws.  Per shape: one warm-up run of each, then
+`--reps` timed repetitions (host wall clock around a synchronised run; the fused launch also by device events), reported as median and
+range.  Results go to profiles/td3_fused_timing.json.
+
+  python tools/bench_td3.py                      # hidden 72 / 32 / 96, 3 layers, minibatch 86, CAPS on, 2 000 updates
+  python tools/bench_td3.py --hidden 72 --updates 200 --eager-updates 50 --reps 3
+"""
+import argparse, ctypes, json, os, statistics, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import numpy as np
+import torch
+
+
+def fused_run(engine, d, n):
+    """-> (device ms, wall ms) of one serl_td3_train launch of n updates on fresh copies of the case's rows"""
+    import td3_64 as T
+    from serl_amd import _capi
+    L = _capi.lib()
+    dev = engine.device
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    rows = {k: t(d[k]) for k in T.ROWS}
+    for k in T.MOMENTS:
+        rows[k] = torch.zeros_like(rows[k.split('_')[0]])
+    steps = torch.zeros(2, dtype=torch.int32, device=dev)
+    ring, slots, tn = t(d['ring']), t(d['slots'][:n]), t(d['tn'][:n])
+    cn = t(d['cn']) if d['caps'] else None
+    td, pg = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+    wb = int(L.serl_td3_work_bytes(1, d['S'], d['A'], d['H'], d['L'], d['B']))
+    work = torch.empty(wb // 4, dtype=torch.float32, device=dev)
+    desc = _capi.Td3Desc(state_dim=d['S'], action_dim=d['A'], hidden=d['H'], num_layers=d['L'], activation={'tanh': 0, 'elu': 1, 'relu': 2}[d['act']],
+                         n_learners=1, batch=d['B'], n_updates=n, capacity=ring.shape[0], slot_cols=slots.shape[1], policy_update_freq=d['freq'],
+                         iteration0=d['it0'], update_actor_target=int(d['uat']), lr=T.LR, gamma=T.GAMMA, tau=T.TAU, noise_sd=T.NOISE_SD,
+                         noise_clip=T.NOISE_CLIP, lambda_s=T.CAPS['lambda_s'], lambda_t=T.CAPS['lambda_t'], eps_sd=T.CAPS['eps_sd'],
+                         max_grad_norm=T.MAX_NORM, actor=rows['actor'].data_ptr(), actor_target=rows['actor_target'].data_ptr(),
+                         actor_m=rows['actor_m'].data_ptr(), actor_v=rows['actor_v'].data_ptr(), actor_stride=rows['actor'].numel(),
+                         critic=rows['critic'].data_ptr(), critic_target=rows['critic_target'].data_ptr(), critic_m=rows['critic_m'].data_ptr(),
+                         critic_v=rows['critic_v'].data_ptr(), critic_stride=rows['critic'].numel(), adam_steps=steps.data_ptr(),
+                         ring=ring.data_ptr(), slots=slots.data_ptr(), target_noise=tn.data_ptr(),
+                         caps_noise=cn.data_ptr() if cn is not None else None, td_loss=td.data_ptr(), pg_loss=pg.data_ptr(), loss_stride=n,
+                         work=work.data_ptr(), work_bytes=wb)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    w0 = time.perf_counter()
+    e0.record()
+    _capi.check(L.serl_td3_train(engine.ctx, ctypes.byref(desc), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'serl_td3_train')
+    e1.record()
+    torch.cuda.synchronize()
+    wall = (time.perf_counter() - w0) * 1e3
+    assert torch.isfinite(td).all()
+    return e0.elapsed_time(e1), wall
+
+
+def eager_run(d, n):
+    import td3_64 as T
+    torch.cuda.synchronize()
+    w0 = time.perf_counter()
+    r = T.td3_literal(d, torch.float32, 'cuda', n)
+    torch.cuda.synchronize()
+    wall = (time.perf_counter() - w0) * 1e3
+    assert np.isfinite(r['td']).all()
+    return wall
+
+
+def spread(v):
+    return {'median': statistics.median(v), 'min': min(v), 'max': max(v), 'n': len(v)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--hidden', type=int, nargs='*', default=[72, 32, 96])
+    ap.add_argument('--layers', type=int, default=3)
+    ap.add_argument('--batch', type=int, default=86)
+    ap.add_argument('--updates', type=int, default=2000)
+    ap.add_argument('--eager-updates', type=int, default=300, help='updates of one eager repetition (the loop is slow; ms per update is what is compared)')
+    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--only-fused', action='store_true', help='one fused launch per shape and nothing else (for a kernel trace)')
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'td3_fused_timing.json'))
+    a = ap.parse_args()
+    import serl_amd
+    import td3_64 as T
+    engine = serl_amd.RolloutEngine(0)
+    res = {'device': torch.cuda.get_device_name(0), 'batch': a.batch, 'layers': a.layers, 'updates': a.updates, 'eager_updates': a.eager_updates,
+           'caps': True, 'policy_update_freq': 2, 'shapes': {}}
+    for H in a.hidden:
+        d = T.make_case((7, 3, H, a.layers, 'tanh', a.batch, 2, 0, a.updates, 1, 1, 'small'), seed=H)
+        fused_run(engine, d, min(a.updates, 50))                        # warm-up
+        if a.only_fused:
+            print('H %d fused %.3f ms per update' % (H, fused_run(engine, d, a.updates)[0] / a.updates))
+            continue
+        eager_run(d, 20)
+        f = [fused_run(engine, d, a.updates) for _ in range(a.reps)]
+        e = [eager_run(d, a.eager_updates) / a.eager_updates for _ in range(a.reps)]
+        r = {'fused_ms_per_update_device': spread([x[0] / a.updates for x in f]), 'fused_ms_per_update_wall': spread([x[1] / a.updates for x in f]),
+             'eager_f32_ms_per_update_wall': spread(e)}
+        r['speedup_median'] = r['eager_f32_ms_per_update_wall']['median'] / r['fused_ms_per_update_wall']['median']
+        res['shapes']['H%d_L%d_B%d' % (H, a.layers, a.batch)] = r
+        print('H %d  fused %.4f ms/update (device; wall %.4f)  eager f32 %.3f ms/update  x%.1f' % (
+            H, r['fused_ms_per_update_device']['median'], r['fused_ms_per_update_wall']['median'], r['eager_f32_ms_per_update_wall']['median'],
+            r['speedup_median']), flush=True)
+    if not a.only_fused:
+        with open(a.out, 'w') as fh:
+            json.dump(res, fh, indent=1)
+        print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()
