@@ -249,7 +249,7 @@ int serl_dyn_open_loop(serl_ctx *ctx, int slot, int32_t n_episodes, int32_t T, c
  *   done   done = bounds hit (envs/phlabenv.py:391-399) OR k == max_steps (the reference tables are exhausted).  A done env is
  *          FROZEN: stepping it returns its last obs, x, ref, t and cost with reward 0 and done = 1 and changes nothing until it
  *          is reset, so no step ever reads ref / sensor_noise past max_steps.  The reference env would keep integrating: a
- *          deliberate difference.  No auto-reset. */
+ *          deliberate difference.  serl_venv_reset / serl_venv_step do not auto-reset; serl_venv_step_auto (below) does. */
 typedef struct serl_venv_desc {
   int32_t n_envs;                   /* envs of the batch, >= 1 */
   int32_t build_slot;               /* slot given to serl_ctx_load_build: one dynamics build per env object */
@@ -283,6 +283,44 @@ int serl_venv_reset(serl_ctx *ctx, const serl_venv_desc *desc, const uint8_t *ma
  * t f64 [n_envs] (info['t'], after the increment), cost i32 [n_envs] (get_cost of the step). */
 int serl_venv_step(serl_ctx *ctx, const serl_venv_desc *desc, const void *actions, int32_t actions_f64, double *obs,
                    double *reward, uint8_t *done, double *x, double *ref, double *t, int32_t *cost, void *stream);
+
+/* ---- auto-reset inside the step (SERL_ABI_VERSION stays 9: serl_abi_layout, serl_venv_desc, the state buffer and the two entry
+ * points above are unchanged; this descriptor has a layout self-check of its own, serl_venv_auto_layout) -------------------------
+ * serl_venv_step_auto is serl_venv_step for envs that restart themselves: a running env takes the step exactly as above, and if that
+ * step ends its episode (bounds hit, or k == max_steps) the same launch then does what serl_venv_reset does for that env -- carried
+ * error kept, the carried model clock takes the reset's tick, the same fault row, initialize() and one step with the zero command,
+ * sensor-noise entry 0 of the env's table, V0 = x[3], t = 0, k = 0, last_u = 0 -- so the env is running again when the call returns.
+ * The "same-step" convention of vector envs: obs is obs0 of the NEW episode; reward, done = 1, x, ref, t and cost are the terminal
+ * step's; final_obs holds the terminal observation and ep_return / ep_length the finished episode's sum of rewards (f64,
+ * ret = ret + reward in step order) and number of steps.  An env that did not finish gets final_obs = obs and leaves ep_return /
+ * ep_length as they were.  An env that is not running (never reset) stays frozen exactly as in serl_venv_step, with final_obs =
+ * obs: auto-reset restarts episodes, it does not start the first one.  desc->err0 / tick0 are not read.  Sensor-noise tables are
+ * reused by the restarted episodes.  A wavefront in which some env finishes pays two dynamics steps in that call.
+ *   references  desc->ref / desc->ref_spec as given: the restarted episode flies them again.  Or ref_pool: `pool_rows` specs per env,
+ *               [n_envs][pool_rows]; the step reads row cursor[e] of env e and a restart advances the cursor to (cursor + 1) %
+ *               pool_rows, so the pool recycles after pool_rows episodes.  With a pool desc->ref must be NULL and desc->ref_spec
+ *               is not read (it may be NULL).
+ *   run state   run_return / run_length / cursor are the caller's: zero them for the envs serl_venv_reset starts (the episode an
+ *               explicit reset starts uses pool row 0).  They are not part of desc->state.  Without a pool the cursor counts restarts (wrapping
+ *               to 0 after 2^31 - 1). */
+typedef struct serl_venv_auto_desc {
+  double *final_obs;                /* out [n_envs][state_dim]: the observation of this step in front of a restart */
+  double *ep_return;                /* out [n_envs]: written where done */
+  int32_t *ep_length;               /* out [n_envs]: written where done */
+  double *run_return;               /* in / out [n_envs]: sum of rewards of the running episode */
+  int32_t *run_length;              /* in / out [n_envs]: steps of the running episode */
+  int32_t *cursor;                  /* in / out [n_envs]: pool row of the running episode */
+  const serl_ref_spec *ref_pool;    /* [n_envs][pool_rows], or NULL: references from desc->ref / desc->ref_spec */
+  int32_t pool_rows;                /* >= 1 with a pool */
+  int32_t pad0;
+} serl_venv_auto_desc;
+/* layout self-check like serl_abi_layout: sizeof(serl_venv_auto_desc), then offsetof of each member in declaration order */
+int serl_venv_auto_layout(int32_t *out, int32_t capacity);
+/* arguments as serl_venv_step, all outputs of `au` required.  SERL_E_INVALID before any launch for a NULL argument, pool_rows < 1
+ * with a pool, a pool together with desc->ref, actions_f64 other than 0 / 1. */
+int serl_venv_step_auto(serl_ctx *ctx, const serl_venv_desc *desc, const void *actions, int32_t actions_f64, double *obs,
+                        double *reward, uint8_t *done, double *x, double *ref, double *t, int32_t *cost,
+                        const serl_venv_auto_desc *au, void *stream);
 
 /* Development aid: with SERL_PROFILE=1 in the environment serl_rollout records shader-clock cycles of wave 0 of
  * workgroup 0: out[0..3] = {actor forward, dynamics step, env bookkeeping, env steps}; out[4..31] = phase

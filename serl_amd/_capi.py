@@ -13,7 +13,7 @@ EXPORTS = ['serl_abi_version', 'serl_last_error', 'serl_param_count', 'serl_ctx_
            'serl_ga_mutate', 'serl_ga_scaled_perturb', 'serl_abi_layout', 'serl_ga_sensitivity', 'serl_ga_novelty',
            'serl_replay_scatter', 'serl_replay_scatter_rows', 'serl_env_state_dim', 'serl_env_action_dim',
            'serl_smoothness', 'serl_smoothness_work_size', 'serl_ga_distill', 'serl_host_sample_slots',
-           'serl_venv_state_bytes', 'serl_venv_reset', 'serl_venv_step',
+           'serl_venv_state_bytes', 'serl_venv_reset', 'serl_venv_step', 'serl_venv_step_auto', 'serl_venv_auto_layout',
            'serl_td3_train', 'serl_td3_work_bytes', 'serl_td3_param_count', 'serl_td3_layout']
 
 
@@ -58,6 +58,17 @@ class VenvDesc(ctypes.Structure):
                 ('state_dim', ctypes.c_int32), ('action_dim', ctypes.c_int32), ('max_steps', ctypes.c_int32), ('pad0', ctypes.c_int32),
                 ('t_max', ctypes.c_double), ('faults', VP), ('ref', VP), ('ref_stride', ctypes.c_int64), ('ref_spec', VP),
                 ('ref_spec_stride', ctypes.c_int64), ('sensor_noise', VP), ('sensor_row', VP), ('err0', VP), ('tick0', VP), ('state', VP)]
+
+
+class VenvAutoDesc(ctypes.Structure):
+    """serl_venv_auto_desc: auto-reset inside the step (checked against the library by serl_venv_auto_layout, not part of serl_abi_layout)"""
+    _fields_ = [('final_obs', VP), ('ep_return', VP), ('ep_length', VP), ('run_return', VP), ('run_length', VP), ('cursor', VP),
+                ('ref_pool', VP), ('pool_rows', ctypes.c_int32), ('pad0', ctypes.c_int32)]
+
+
+def expected_venv_auto_layout():
+    """What serl_venv_auto_layout() must return for VenvAutoDesc to be right."""
+    return [ctypes.sizeof(VenvAutoDesc)] + [getattr(VenvAutoDesc, n).offset for n, _ in VenvAutoDesc._fields_]
 
 
 class Td3Desc(ctypes.Structure):
@@ -139,6 +150,8 @@ def lib():
     L.serl_venv_state_bytes.argtypes = [i32]
     L.serl_venv_reset.argtypes = [VP, ctypes.POINTER(VenvDesc), VP, VP, VP]
     L.serl_venv_step.argtypes = [VP, ctypes.POINTER(VenvDesc), VP, i32, VP, VP, VP, VP, VP, VP, VP, VP]
+    L.serl_venv_step_auto.argtypes = [VP, ctypes.POINTER(VenvDesc), VP, i32, VP, VP, VP, VP, VP, VP, VP, ctypes.POINTER(VenvAutoDesc), VP]
+    L.serl_venv_auto_layout.argtypes = [VP, ctypes.c_int32]
     L.serl_td3_train.argtypes = [VP, ctypes.POINTER(Td3Desc), VP]
     L.serl_td3_work_bytes.argtypes = [i32] * 6
     L.serl_td3_param_count.argtypes = [ctypes.c_int, ctypes.c_int]
@@ -160,6 +173,12 @@ def lib():
     n = L.serl_td3_layout(got, len(want))
     if n != len(want) or list(got) != want:
         raise RuntimeError('serl_amd: layout of the Td3Desc mirror differs from the library (serl_td3_layout): library %s, binding %s'
+                           % (list(got)[:n], want))
+    want = expected_venv_auto_layout()
+    got = (ctypes.c_int32 * len(want))()
+    n = L.serl_venv_auto_layout(got, len(want))
+    if n != len(want) or list(got) != want:
+        raise RuntimeError('serl_amd: layout of the VenvAutoDesc mirror differs from the library (serl_venv_auto_layout): library %s, binding %s'
                            % (list(got)[:n], want))
     _lib = L
     return L

@@ -19,11 +19,13 @@ static int fail(int code, const std::string &msg) { return serl_fail(code, msg);
 typedef void SerlLaunch(const RolloutArgs &a, int grid, hipStream_t stream);
 typedef void SerlLaunchDyn(const RolloutArgs &a, const double *cmds, double *states, int T, int grid, hipStream_t stream);
 typedef void SerlLaunchVenv(const RolloutArgs &a, const VenvArgs &v, int grid, hipStream_t stream);
+typedef void SerlLaunchVenvAuto(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, int grid, hipStream_t stream);
 #define SERL_LAUNCHERS(X, v)                                                                                                                     \
   X(SerlLaunch, lane, serl_launch_rollout_##v)              /* one episode per lane (family_lane.hip, rollout_variant.inc) */                   \
   X(SerlLaunchDyn, dyn_lane, serl_launch_dyn_##v)                                                                                                \
   X(SerlLaunchVenv, venv_reset, serl_launch_venv_reset_##v) /* the step-wise vector env, one lane per env (venv_variant.inc) */                  \
   X(SerlLaunchVenv, venv_step, serl_launch_venv_step_##v)                                                                                        \
+  X(SerlLaunchVenvAuto, venv_step_auto, serl_launch_venv_step_auto_##v) /* ... step with auto-reset */                                           \
   X(SerlLaunch, wave, serl_launch_rollout_wave_##v)         /* one wavefront per episode (rollout_wave.inc) ... */                               \
   X(SerlLaunch, wavex, serl_launch_rollout_wavex_##v)       /* ... env configurations other than the attitude task */                           \
   X(SerlLaunchDyn, dyn_wave, serl_launch_dyn_wave_##v)                                                                                           \
@@ -801,7 +803,8 @@ static int serl_venv_check(serl_ctx *c, const serl_venv_desc *d, const char *wha
 }
 
 // the launch shape of serl_dyn_open_loop's lane kernels: lanes per wavefront from the batch, so that small batches still spread over the CUs
-static int serl_venv_launch(serl_ctx *c, const serl_venv_desc *d, bool step, VenvArgs &v, hipStream_t stream)
+static int serl_venv_launch(serl_ctx *c, const serl_venv_desc *d, bool step, VenvArgs &v, hipStream_t stream,
+                            const serl_venv_auto_desc *au = nullptr)
 {
   const BuildSlot &s = c->slots[d->build_slot];
   const SerlLaunchers &L = serl_launchers(s.code);
@@ -819,7 +822,8 @@ static int serl_venv_launch(serl_ctx *c, const serl_venv_desc *d, bool step, Ven
   const int grid = (nwaves + wpb - 1) / wpb;
   v.d = *d;
   v.npad = serl_venv_npad(d->n_envs);
-  (step ? L.venv_step : L.venv_reset)(a, v, grid, stream);
+  if (au) L.venv_step_auto(a, v, *au, grid, stream);
+  else (step ? L.venv_step : L.venv_reset)(a, v, grid, stream);
   HIP_TRY(hipGetLastError());
   return SERL_OK;
 }
@@ -848,6 +852,40 @@ int serl_venv_step(serl_ctx *c, const serl_venv_desc *d, const void *actions, in
   v.actions = actions; v.actions_f64 = actions_f64;
   v.obs = obs; v.reward = reward; v.done = done; v.x = x; v.ref = ref; v.t = t; v.cost = cost;
   return serl_venv_launch(c, d, true, v, (hipStream_t)stream_);
+}
+
+int serl_venv_auto_layout(int32_t *out, int32_t capacity)
+{
+#define SERL_OFF(m) (int32_t)offsetof(serl_venv_auto_desc, m)
+  const int32_t v[] = {(int32_t)sizeof(serl_venv_auto_desc), SERL_OFF(final_obs), SERL_OFF(ep_return), SERL_OFF(ep_length),
+                       SERL_OFF(run_return), SERL_OFF(run_length), SERL_OFF(cursor), SERL_OFF(ref_pool), SERL_OFF(pool_rows), SERL_OFF(pad0)};
+#undef SERL_OFF
+  const int32_t n = (int32_t)(sizeof(v) / sizeof(v[0]));
+  for (int32_t i = 0; out && i < n && i < capacity; ++i) out[i] = v[i];
+  return n;
+}
+
+int serl_venv_step_auto(serl_ctx *c, const serl_venv_desc *d, const void *actions, int32_t actions_f64, double *obs,
+                        double *reward, uint8_t *done, double *x, double *ref, double *t, int32_t *cost,
+                        const serl_venv_auto_desc *au, void *stream_)
+{
+  const char *w = "serl_venv_step_auto";
+  if (!c || !d || !au) return fail(SERL_E_INVALID, std::string(w) + ": NULL argument");
+  if (au->ref_pool && d->ref) return fail(SERL_E_INVALID, std::string(w) + ": ref_pool together with desc->ref");
+  if (au->ref_pool && au->pool_rows < 1) return fail(SERL_E_INVALID, std::string(w) + ": pool_rows < 1");
+  serl_venv_desc dd = *d;
+  if (au->ref_pool) { dd.ref_spec = au->ref_pool; dd.ref_spec_stride = 1; }      // (the kernel reads the pool: desc->ref_spec may be NULL)
+  { const int rc_ = serl_venv_check(c, &dd, w); if (rc_ != SERL_OK) return rc_; }
+  if (!actions || !obs || !reward || !done) return fail(SERL_E_INVALID, std::string(w) + ": actions / obs / reward / done is NULL");
+  if (!au->final_obs || !au->ep_return || !au->ep_length || !au->run_return || !au->run_length || !au->cursor)
+    return fail(SERL_E_INVALID, std::string(w) + ": final_obs / ep_return / ep_length / run_return / run_length / cursor is NULL");
+  if (actions_f64 != 0 && actions_f64 != 1) return fail(SERL_E_INVALID, std::string(w) + ": actions_f64 must be 0 (f32) or 1 (f64)");
+  HIP_TRY(hipSetDevice(c->device));
+  VenvArgs v;
+  memset(&v, 0, sizeof(v));
+  v.actions = actions; v.actions_f64 = actions_f64;
+  v.obs = obs; v.reward = reward; v.done = done; v.x = x; v.ref = ref; v.t = t; v.cost = cost;
+  return serl_venv_launch(c, &dd, true, v, (hipStream_t)stream_, au);
 }
 
 /* development aid (SERL_PROFILE=1): shader-clock cycles wave 0 of workgroup 0 spent in the actor forward, the

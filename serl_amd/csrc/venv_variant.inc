@@ -215,6 +215,133 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_step_kernel_)(Ro
   if (v.cost) v.cost[e] = cost;
 }
 
+// step(action) of every env, and reset() of those whose episode that step ends, in the same launch (serl_venv_step_auto in
+// include/serl_amd.h).  cit_step_<v> is the whole cost and tens of KB inlined, so there is ONE call site in a two-trip loop: the first
+// trip is serl_venv_step_kernel_'s step, the second -- entered only by lanes whose episode ended -- is serl_venv_reset_kernel_'s
+// initialize() + step with the zero command.  The glue around it is those two kernels', statement for statement.
+__global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_step_auto_kernel_)(RolloutArgs a, VenvArgs v, serl_venv_auto_desc au)
+{
+  const int e = VV_NAME(serl_stage_and_index_)(a);
+  if (e < 0) return;
+  const serl_venv_desc &d = v.d;
+  double *S = (double *)d.state;
+  int32_t *I = (int32_t *)(S + SERL_VENV_F64 * v.npad);
+  const int64_t np = v.npad;
+  double *fobs = au.final_obs + (size_t)e * d.state_dim;
+  if (!I[SERL_VI_LIVE * np + e]) {      // never reset: frozen, as in serl_venv_step
+    serl_venv_write_frozen(v, e, true);
+    for (int i = 0; i < d.state_dim; ++i) fobs[i] = v.obs[(size_t)e * d.state_dim + i];
+    return;
+  }
+  const double PI = 3.14159265358979323846;
+  const double deg2rad = PI / 180.0, rad2deg = 180.0 / PI;
+  const int cfg = d.env_config, A = d.action_dim;
+  const bool incr = d.incremental != 0;
+  const double bound = (incr ? 25.0 : 10.0) * deg2rad, low = -bound, high = bound;
+  const double max_theta = 60.0 * deg2rad, max_phi = 75.0 * deg2rad;
+  const double scaler[3] = {6.0 / PI * 1.0, 6.0 / PI * 1.0, 6.0 / PI * 4.0};
+  const double dt = 0.01;
+  double err[3], u[3], x[12], cmd[10], rk[3];
+  for (int i = 0; i < 3; ++i) { err[i] = S[(SERL_VF_ERR + i) * np + e]; u[i] = S[(SERL_VF_LASTU + i) * np + e]; }
+  const double V0 = S[SERL_VF_V0 * np + e];
+  double t = S[SERL_VF_T * np + e];
+  int k = I[SERL_VI_K * np + e];
+  double scl[3] = {0.0, 0.0, 0.0};
+  for (int i = 0; i < 3; ++i) {
+    if (i >= A) continue;
+    if (v.actions_f64) {
+      const double ai = ((const double *)v.actions)[(size_t)e * A + i];
+      scl[i] = low + 0.5 * (ai + 1.0) * (high - low);
+    } else {
+      const float s = 0.5f * (((const float *)v.actions)[(size_t)e * A + i] + 1.0f);
+      scl[i] = low + (double)s * (high - low);
+    }
+  }
+  for (int i = 0; i < 3; ++i) u[i] = incr ? u[i] + scl[i] * dt : scl[i];
+  serl_fault_row f = {1.0, __longlong_as_double(0x7ff0000000000000LL), __longlong_as_double(0x7ff0000000000000LL),
+                      0.0, 0.0, 0, 0, 0};
+  if (d.faults) f = d.faults[e];
+  for (int i = 0; i < 10; ++i) cmd[i] = 0.0;
+  cmd[0] = serl_clip(u[0] * f.elev_gain, -f.elev_clip, f.elev_clip);
+  cmd[1] = serl_clip(u[1], -f.ail_clip, f.ail_clip);
+  cmd[2] = (f.rudder_jam_on != 0.0) ? f.rudder_jam : u[2];
+  // the running episode's reference: its row of the pool (the cursor is the caller's memory: kept inside the pool whatever it holds)
+  const int32_t cur = au.cursor[e];
+  const int row = au.ref_pool ? (int)((uint32_t)cur % (uint32_t)au.pool_rows) : 0;
+  const serl_ref_spec *spec = au.ref_pool ? au.ref_pool + (size_t)e * au.pool_rows + row
+                            : d.ref_spec ? d.ref_spec + (size_t)e * d.ref_spec_stride : nullptr;
+  int cost = 0;
+  double V0n = V0;
+  bool restart = false;
+  CitCtx ctx;
+  VV_NAME(serl_venv_load_ctx_)(a, v, e, ctx);
+#pragma nounroll
+  for (int trip = 0; trip < 2; ++trip) {
+    VV_NAME(cit_step_)(&ctx, cmd, x);
+    if (const double *sn = serl_venv_sensor(d, e, restart ? 0 : k + 1)) {
+      x[0] += sn[0]; x[1] += sn[1]; x[2] += sn[2]; x[4] += sn[3]; x[5] += sn[4]; x[6] += sn[5]; x[7] += sn[6];
+    }
+    if (restart) { V0n = x[3]; break; }
+    if (spec) serl_ref_generate(spec, t, d.t_max, rk[0], rk[1], rk[2]);
+    else {
+      const double *r = d.ref + (size_t)e * d.ref_stride + (size_t)k * 3;
+      rk[0] = r[0]; rk[1] = r[1]; rk[2] = r[2];
+    }
+    err[0] = rk[0] - x[7];
+    if (A > 1) { err[1] = rk[1] - x[6]; err[2] = rk[2] - x[5]; }
+    double rsum = 0.0;
+    for (int i = 0; i < 3; ++i) if (i < A) rsum = rsum + fabs(serl_clip(scaler[i] * err[i], -1.0, 1.0));
+    double reward = -rsum / (double)A;
+    cost = (rad2deg * fabs(x[4]) > 11.0) || (rad2deg * fabs(x[6]) > 0.75 * max_phi) || (x[3] < V0 / 3.0);
+    const bool fin = (t >= d.t_max) || (fabs(x[7]) > max_theta) || (fabs(x[6]) > max_phi) || (x[9] < 50.0);
+    if (fin) reward += -1.0 / dt * (d.t_max - t) * 2.0;
+    t += dt;
+    k += 1;
+    const bool done = fin || k >= d.max_steps;
+    serl_venv_write_obs(cfg, incr, err, x, u, fobs);
+    v.reward[e] = reward;
+    v.done[e] = done ? 1 : 0;
+    if (v.x) for (int i = 0; i < 12; ++i) v.x[(size_t)e * 12 + i] = x[i];
+    if (v.ref) for (int i = 0; i < 3; ++i) v.ref[(size_t)e * 3 + i] = rk[i];
+    if (v.t) v.t[e] = t;
+    if (v.cost) v.cost[e] = cost;
+    const double ret = au.run_return[e] + reward;
+    const int32_t len = au.run_length[e] + 1;
+    if (!done) { au.run_return[e] = ret; au.run_length[e] = len; break; }
+    au.ep_return[e] = ret; au.ep_length[e] = len;
+    au.run_return[e] = 0.0; au.run_length[e] = 0;
+    au.cursor[e] = au.ref_pool ? (row + 1) % au.pool_rows : (int32_t)(((uint32_t)cur + 1u) & 0x7fffffffu);      // (no pool: restarts counted, wrapping to 0)
+    // reset() of this env (serl_venv_reset_kernel_ without err0 / tick0): the error stays, the clock keeps counting
+    restart = true;
+    const uint32_t tick = ctx.tick;
+    cit_reset(&ctx, a.ro, a.t3, a.x0, a.dw0, a.dyn_dt);
+    if (tick) { ctx.tick = tick; ctx.t = (double)ctx.tick * ctx.dt; }
+    ctx.bslot = 0;
+    for (int i = 0; i < 3; ++i) { u[i] = 0.0; rk[i] = 0.0; }
+    t = 0.0; k = 0; cost = 0;
+    for (int i = 0; i < 10; ++i) cmd[i] = 0.0;
+    cmd[0] = serl_clip(cmd[0] * f.elev_gain, -f.elev_clip, f.elev_clip);
+    cmd[1] = serl_clip(cmd[1], -f.ail_clip, f.ail_clip);
+    if (f.rudder_jam_on != 0.0) cmd[2] = f.rudder_jam;
+  }
+  VV_NAME(serl_venv_store_ctx_)(v, e, ctx);
+  for (int i = 0; i < 3; ++i) {
+    S[(SERL_VF_ERR + i) * np + e] = err[i]; S[(SERL_VF_LASTU + i) * np + e] = u[i]; S[(SERL_VF_REF + i) * np + e] = rk[i];
+  }
+  for (int i = 0; i < 12; ++i) S[(SERL_VF_XO + i) * np + e] = x[i];
+  S[SERL_VF_V0 * np + e] = V0n;
+  S[SERL_VF_T * np + e] = t;
+  I[SERL_VI_K * np + e] = k;
+  I[SERL_VI_LIVE * np + e] = 1;
+  I[SERL_VI_COST * np + e] = cost;
+  serl_venv_write_obs(cfg, incr, err, x, u, v.obs + (size_t)e * d.state_dim);
+}
+
+void VV_NAME(serl_launch_venv_step_auto_)(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, int grid, hipStream_t stream)
+{
+  hipLaunchKernelGGL(VV_NAME(serl_venv_step_auto_kernel_), dim3(grid), dim3(a.block), 0, stream, a, v, au);
+}
+
 void VV_NAME(serl_launch_venv_reset_)(const RolloutArgs &a, const VenvArgs &v, int grid, hipStream_t stream)
 {
   hipLaunchKernelGGL(VV_NAME(serl_venv_reset_kernel_), dim3(grid), dim3(a.block), 0, stream, a, v);

@@ -7,7 +7,17 @@ One JSON line: env-steps/s and microseconds per `step` call at each N, in three 
                closed loop, no host synchronisation inside the loop
     fused      for reference: the fused lane rollout (lanes_per_wave = 64: actor + env + dynamics in one kernel) at the same N
 -- timed with device events after a warm-up, every env flying the base reference (one shared table) from a fresh reset; only live env
-steps count (a done env is frozen and costs little).  Also the resource usage of the new kernels (tools/kernel_regs.sh on the build's objects)."""
+steps count (a done env is frozen and costs little).  Also the resource usage of the new kernels (tools/kernel_regs.sh on the build's objects).
+
+    python tools/bench_venv.py --auto-reset [--sizes 1024,65536] [--auto-steps 1000] [--reps 5] [--out profiles/venv_auto_timing.json]
+runs the auto-reset leg instead: CitationVecEnv(auto_reset=True) (serl_venv_step_auto) against the loop it replaces, medians and
+[min .. max] of `reps` repetitions after a warm-up, the versions of a comparison alternating within each repetition --
+    staggered  episodes of 32 steps on a shared table, the envs' phases spread evenly (3 % of the envs finish per step):
+               `step` with auto_reset=True against `step` followed by `reset(done)` every step (two launches, no host draw)
+    drawn      the same with refs=None at t_max = 5 (502 steps, 0.2 % finish per step): the manual loop's `reset(done)` then finds the
+               finished envs on the host and draws their references there (one synchronisation per step); auto flies its pool
+               (N <= --drawn-max-n only: the host draws dominate beyond)
+    idle       no env finishing (t_max = 20, fewer steps than an episode): the auto step against the plain step -- the cost of the larger kernel"""
 import argparse, json, os, subprocess, sys
 import numpy as np
 import torch
@@ -15,7 +25,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import serl_amd
-from serl_amd import refsignals as rs
+from serl_amd import build as hip_build, refsignals as rs
 
 
 def serl50_policy(device):
@@ -67,6 +77,81 @@ def bench_fused(eng, N, ref, warmup):
     return dict(N=N, config='fused', calls=1, ms=round(ms, 3), us_per_call=None, live_env_steps=n, env_steps_per_s=round(n / (ms * 1e-3), 1))
 
 
+def _stagger(env, L, fixed):
+    """phases spread evenly over an episode of L steps: afterwards env e has taken (L - 1 - e % L) steps of its episode"""
+    e = torch.arange(env.n_envs, device=env.device)
+    for j in range(L):
+        env.reset(e % L == j)
+        if j + 1 < L:
+            obs, rew, done, info = env.step(fixed)
+            if not env.auto_reset:
+                env.reset(done)
+
+
+def _timed(env, steps, fixed, manual_reset):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    nfin = torch.zeros((), dtype=torch.int64, device=env.device)
+    e0.record()
+    for _ in range(steps):
+        obs, rew, done, info = env.step(fixed)
+        if manual_reset:
+            env.reset(done)
+    e1.record()
+    e1.synchronize()
+    nfin += done.sum()
+    return e0.elapsed_time(e1), int(nfin)
+
+
+def _summary(N, steps, ms):
+    rate = sorted(N * steps / (m * 1e-3) for m in ms)
+    us = sorted(1e3 * m / steps for m in ms)
+    med = lambda v: v[len(v) // 2]
+    return dict(env_steps_per_s=dict(median=round(med(rate), 1), min=round(rate[0], 1), max=round(rate[-1], 1)),
+                us_per_step=dict(median=round(med(us), 2), min=round(us[0], 2), max=round(us[-1], 2)), reps_ms=[round(m, 3) for m in ms])
+
+
+def bench_auto(eng, N, steps, warmup, reps, drawn_steps, drawn_max_n):
+    """One size: the three comparisons of the module docstring.  Every env is live in every timed step of every version."""
+    dev = eng.device
+    fixed = torch.zeros(N, 3, dtype=torch.float32, device=dev)
+    L = 32
+    table = np.ascontiguousarray(rs.tabulate(*rs.base_reference(20), 20)[:L])
+    out = dict(N=N, steps=steps, reps=reps, warmup=warmup)
+
+    def compare(name, make, steps, stagger_L, manual_reset):
+        envs = {v: make(v == 'auto') for v in ('auto', 'manual')}
+        ms = {v: [] for v in envs}
+        fin = {}
+        with torch.no_grad():
+            for v, env in envs.items():
+                if stagger_L:
+                    _stagger(env, stagger_L, fixed)
+                else:
+                    env.reset()
+                _timed(env, warmup, fixed, manual_reset and v == 'manual')
+            for r in range(reps):
+                for v, env in (list(envs.items()) if r % 2 == 0 else list(envs.items())[::-1]):      # alternate the order
+                    if not stagger_L:
+                        env.reset()      # idle: every repetition from a fresh episode, so that no env finishes
+                    m, fin[v] = _timed(env, steps, fixed, manual_reset and v == 'manual')
+                    ms[v].append(m)
+        out[name] = dict(steps=steps, auto=_summary(N, steps, ms['auto']), manual=_summary(N, steps, ms['manual']),
+                         finished_on_last_step=fin)
+        a, m = out[name]['auto']['env_steps_per_s'], out[name]['manual']['env_steps_per_s']
+        out[name]['speedup_of_medians'] = round(a['median'] / m['median'], 3)
+
+    compare('staggered', lambda auto: serl_amd.CitationVecEnv(N, mode='nominal', t_max=20, refs=table, engine=eng, auto_reset=auto),
+            steps, L, True)
+    np.random.seed(0)
+    if N <= drawn_max_n:      # (beyond, the manual loop's time is the host's reference draws, not the GPU's)
+        compare('drawn', lambda auto: serl_amd.CitationVecEnv(N, mode='nominal', t_max=5, engine=eng, auto_reset=auto), drawn_steps,
+                rs.n_steps_for(5), True)
+    full = rs.tabulate(*rs.base_reference(20), 20)
+    assert steps + warmup < len(full)
+    compare('idle', lambda auto: serl_amd.CitationVecEnv(N, mode='nominal', t_max=20, refs=full, engine=eng, auto_reset=auto), steps, 0, False)
+    return out
+
+
 def kernel_report():
     rep = {}
     for v in ('nominal', 'ice', 'cg_timed', 'gust', 'test'):
@@ -80,7 +165,7 @@ def kernel_report():
                 continue
             f = dict(p.strip().split(': ', 1) for p in line.split('\t') if ': ' in p)
             name = f['.name'].strip()
-            kind = 'step' if 'step' in name else 'reset'
+            kind = 'step_auto' if 'step_auto' in name else 'step' if 'step' in name else 'reset'
             rep['%s_%s' % (kind, v)] = dict(vgpr=int(f['.vgpr_count']), vgpr_spill=int(f['.vgpr_spill_count']), sgpr_spill=int(f['.sgpr_spill_count']),
                                             lds_bytes=int(f['.group_segment_fixed_size']), scratch_bytes=int(f['.private_segment_fixed_size']))
     return rep
@@ -92,8 +177,26 @@ def main():
     ap.add_argument('--steps', type=int, default=2001)
     ap.add_argument('--warmup', type=int, default=50)
     ap.add_argument('--no-fused', action='store_true')
+    ap.add_argument('--auto-reset', action='store_true', help='the auto-reset leg instead of the others')
+    ap.add_argument('--auto-steps', type=int, default=1000)
+    ap.add_argument('--drawn-steps', type=int, default=300)
+    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--drawn-max-n', type=int, default=8192, help='largest N of the drawn comparison')
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'venv_auto_timing.json'))
     args = ap.parse_args()
     eng = serl_amd.RolloutEngine(0)
+    if args.auto_reset:
+        sizes = [int(s) for s in (args.sizes if args.sizes != ap.get_default('sizes') else '1024,65536').split(',')]
+        res = dict(tool='bench_venv --auto-reset', device=torch.cuda.get_device_name(0), source_hash=hip_build.source_hash(),
+                   results=[bench_auto(eng, N, args.auto_steps, args.warmup, args.reps, args.drawn_steps, args.drawn_max_n) for N in sizes])
+        kernels = kernel_report()      # (needs the build's objects: empty where only the library was shipped)
+        if kernels:
+            res['kernels'] = kernels
+        with open(args.out, 'w') as f:
+            json.dump(res, f, indent=1)
+            f.write('\n')
+        print(json.dumps(res))
+        return
     ref = rs.tabulate(*rs.base_reference(20), 20)
     policy = serl50_policy(eng.device)
     res = []
