@@ -322,6 +322,57 @@ int serl_venv_step_auto(serl_ctx *ctx, const serl_venv_desc *desc, const void *a
                         double *reward, uint8_t *done, double *x, double *ref, double *t, int32_t *cost,
                         const serl_venv_auto_desc *au, void *stream);
 
+/* ---- K policy-driven steps of persistent envs in one launch (SERL_ABI_VERSION stays 9: nothing above has moved; this descriptor has
+ * a layout self-check of its own, serl_venv_rollout_layout) -----------------------------------------------------------------------------
+ * serl_venv_rollout collects n_steps steps of experience from the envs of `desc` under a given policy: per env and step the actor
+ * forward on the current observation (obsf[i] = (float)obs[i]; the arithmetic of serl_rollout_desc, bit for bit; every lane runs its
+ * own actor on its member's plain row of `weights`), the action path of serl_rollout -- without noise the f32 action scaled as an f32
+ * action of serl_venv_step; with action_noise an = clip((double)act + noise, -1, 1) scaled as an f64 action -- and then exactly the step
+ * of serl_venv_step_auto, restart included.  The env state, `au`'s run state (run_return / run_length / cursor: read once, written once
+ * per call) and the reference pool are those of serl_venv_step_auto: serl_venv_step / _step_auto may follow a rollout and vice versa.
+ * Attitude task without rate control only (state_dim 7, action_dim 3), and the actor shape of the lane kernels only: hidden 32, any
+ * num_layers >= 0 and activation.  Outputs are step-major, [n_steps][n_envs] rows; all but obs are optional (NULL = not written):
+ *   obs          f64 [n_steps + 1][n_envs][7]  row 0: the observation the segment starts from; row k + 1: what serl_venv_step_auto returns
+ *                                              after step k (obs0 of the new episode where done)
+ *   actions      f64 [n_steps][n_envs][3]      the executed action in actor units: (double)act without noise, the clipped an with noise
+ *   reward f64, done u8, final_obs f64 [..][7], x f64 [..][12], ref f64 [..][3], t f64, cost i32: as serl_venv_step_auto per step
+ *   ep_return f64, ep_length i32 [n_steps][n_envs]: written where done only
+ *   transitions  f32 [n_steps][n_envs][20]     (obs 7, executed action 3 as f32, final_obs 7, reward, fin, cost): the row of
+ *                                              serl_rollout_desc.transitions; fin = bounds hit or t >= t_max, NOT the end of the tables
+ * An env that was never reset stays frozen in every row as serl_venv_step_auto leaves it (reward 0, done 1, its obs, final_obs = obs);
+ * its actions are 0 and its transition rows (obs, 0, obs, 0, 1, cost).  member_of_env indices are taken modulo n_members. */
+typedef struct serl_venv_rollout_desc {
+  int32_t state_dim, action_dim, hidden, num_layers, activation;   /* the actor, as serl_rollout_desc */
+  int32_t n_members;                /* rows of weights, >= 1 */
+  const float *weights;             /* DEVICE f32 [n_members][weight_stride], packed as serl_rollout_desc.weights, 16-byte aligned rows */
+  int64_t weight_stride;            /* in floats, >= param_count, a multiple of 4 */
+  const int32_t *member_of_env;     /* DEVICE [n_envs], or NULL: every env runs member 0 (one shared policy) */
+  int32_t n_steps;                  /* K >= 1 */
+  int32_t pad0;
+  const double *action_noise;       /* DEVICE [n_steps][n_envs][3] added to the actor's output, or NULL */
+  double *obs;
+  double *actions;
+  double *reward;
+  uint8_t *done;
+  double *final_obs;
+  double *ep_return;
+  int32_t *ep_length;
+  double *x;
+  double *ref;
+  double *t;
+  int32_t *cost;
+  float *transitions;
+} serl_venv_rollout_desc;
+/* layout self-check: sizeof(serl_venv_rollout_desc), then offsetof of each member in declaration order */
+int serl_venv_rollout_layout(int32_t *out, int32_t capacity);
+/* Asynchronous on `stream`, one launch, no host synchronisation.  SERL_E_INVALID before any launch for a NULL argument, NULL obs or
+ * weights, n_steps < 1, n_members < 1, an env other than the attitude task without rate control, an actor other than 7 -> 32 .. -> 3
+ * (or num_layers < 0, an unknown activation, a weight_stride below the parameter count or not a multiple of 4), and for what
+ * serl_venv_step_auto refuses in `desc` / `au` (run_return / run_length / cursor are required; au->final_obs is not used; au->ep_return /
+ * ep_length, where given, receive the last finished episode's values as the same steps of serl_venv_step_auto would leave them). */
+int serl_venv_rollout(serl_ctx *ctx, const serl_venv_desc *desc, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *ro,
+                      void *stream);
+
 /* Development aid: with SERL_PROFILE=1 in the environment serl_rollout records shader-clock cycles of wave 0 of
  * workgroup 0: out[0..3] = {actor forward, dynamics step, env bookkeeping, env steps}; out[4..31] = phase
  * counters of the model evaluation (non-zero only in builds compiled with -DCITW_PROFILE). */

@@ -14,6 +14,7 @@ EXPORTS = ['serl_abi_version', 'serl_last_error', 'serl_param_count', 'serl_ctx_
            'serl_replay_scatter', 'serl_replay_scatter_rows', 'serl_env_state_dim', 'serl_env_action_dim',
            'serl_smoothness', 'serl_smoothness_work_size', 'serl_ga_distill', 'serl_host_sample_slots',
            'serl_venv_state_bytes', 'serl_venv_reset', 'serl_venv_step', 'serl_venv_step_auto', 'serl_venv_auto_layout',
+           'serl_venv_rollout', 'serl_venv_rollout_layout',
            'serl_td3_train', 'serl_td3_work_bytes', 'serl_td3_param_count', 'serl_td3_layout']
 
 
@@ -69,6 +70,20 @@ class VenvAutoDesc(ctypes.Structure):
 def expected_venv_auto_layout():
     """What serl_venv_auto_layout() must return for VenvAutoDesc to be right."""
     return [ctypes.sizeof(VenvAutoDesc)] + [getattr(VenvAutoDesc, n).offset for n, _ in VenvAutoDesc._fields_]
+
+
+class VenvRolloutDesc(ctypes.Structure):
+    """serl_venv_rollout_desc: K policy-driven steps in one launch (checked against the library by serl_venv_rollout_layout)"""
+    _fields_ = ([(n, ctypes.c_int32) for n in ('state_dim', 'action_dim', 'hidden', 'num_layers', 'activation', 'n_members')] +
+                [('weights', VP), ('weight_stride', ctypes.c_int64), ('member_of_env', VP), ('n_steps', ctypes.c_int32),
+                 ('pad0', ctypes.c_int32), ('action_noise', VP)] +
+                [(n, VP) for n in ('obs', 'actions', 'reward', 'done', 'final_obs', 'ep_return', 'ep_length', 'x', 'ref', 't', 'cost',
+                                   'transitions')])
+
+
+def expected_venv_rollout_layout():
+    """What serl_venv_rollout_layout() must return for VenvRolloutDesc to be right."""
+    return [ctypes.sizeof(VenvRolloutDesc)] + [getattr(VenvRolloutDesc, n).offset for n, _ in VenvRolloutDesc._fields_]
 
 
 class Td3Desc(ctypes.Structure):
@@ -152,6 +167,8 @@ def lib():
     L.serl_venv_step.argtypes = [VP, ctypes.POINTER(VenvDesc), VP, i32, VP, VP, VP, VP, VP, VP, VP, VP]
     L.serl_venv_step_auto.argtypes = [VP, ctypes.POINTER(VenvDesc), VP, i32, VP, VP, VP, VP, VP, VP, VP, ctypes.POINTER(VenvAutoDesc), VP]
     L.serl_venv_auto_layout.argtypes = [VP, ctypes.c_int32]
+    L.serl_venv_rollout.argtypes = [VP, ctypes.POINTER(VenvDesc), ctypes.POINTER(VenvAutoDesc), ctypes.POINTER(VenvRolloutDesc), VP]
+    L.serl_venv_rollout_layout.argtypes = [VP, ctypes.c_int32]
     L.serl_td3_train.argtypes = [VP, ctypes.POINTER(Td3Desc), VP]
     L.serl_td3_work_bytes.argtypes = [i32] * 6
     L.serl_td3_param_count.argtypes = [ctypes.c_int, ctypes.c_int]
@@ -179,6 +196,12 @@ def lib():
     n = L.serl_venv_auto_layout(got, len(want))
     if n != len(want) or list(got) != want:
         raise RuntimeError('serl_amd: layout of the VenvAutoDesc mirror differs from the library (serl_venv_auto_layout): library %s, binding %s'
+                           % (list(got)[:n], want))
+    want = expected_venv_rollout_layout()
+    got = (ctypes.c_int32 * len(want))()
+    n = L.serl_venv_rollout_layout(got, len(want))
+    if n != len(want) or list(got) != want:
+        raise RuntimeError('serl_amd: layout of the VenvRolloutDesc mirror differs from the library (serl_venv_rollout_layout): library %s, binding %s'
                            % (list(got)[:n], want))
     _lib = L
     return L

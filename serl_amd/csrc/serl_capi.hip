@@ -20,12 +20,15 @@ typedef void SerlLaunch(const RolloutArgs &a, int grid, hipStream_t stream);
 typedef void SerlLaunchDyn(const RolloutArgs &a, const double *cmds, double *states, int T, int grid, hipStream_t stream);
 typedef void SerlLaunchVenv(const RolloutArgs &a, const VenvArgs &v, int grid, hipStream_t stream);
 typedef void SerlLaunchVenvAuto(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, int grid, hipStream_t stream);
+typedef void SerlLaunchVenvRollout(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, const serl_venv_rollout_desc &rd, int grid,
+                                   hipStream_t stream);
 #define SERL_LAUNCHERS(X, v)                                                                                                                     \
   X(SerlLaunch, lane, serl_launch_rollout_##v)              /* one episode per lane (family_lane.hip, rollout_variant.inc) */                   \
   X(SerlLaunchDyn, dyn_lane, serl_launch_dyn_##v)                                                                                                \
   X(SerlLaunchVenv, venv_reset, serl_launch_venv_reset_##v) /* the step-wise vector env, one lane per env (venv_variant.inc) */                  \
   X(SerlLaunchVenv, venv_step, serl_launch_venv_step_##v)                                                                                        \
   X(SerlLaunchVenvAuto, venv_step_auto, serl_launch_venv_step_auto_##v) /* ... step with auto-reset */                                           \
+  X(SerlLaunchVenvRollout, venv_rollout, serl_launch_venv_rollout_##v)  /* ... K steps under the lane actor */                                   \
   X(SerlLaunch, wave, serl_launch_rollout_wave_##v)         /* one wavefront per episode (rollout_wave.inc) ... */                               \
   X(SerlLaunch, wavex, serl_launch_rollout_wavex_##v)       /* ... env configurations other than the attitude task */                           \
   X(SerlLaunchDyn, dyn_wave, serl_launch_dyn_wave_##v)                                                                                           \
@@ -804,7 +807,7 @@ static int serl_venv_check(serl_ctx *c, const serl_venv_desc *d, const char *wha
 
 // the launch shape of serl_dyn_open_loop's lane kernels: lanes per wavefront from the batch, so that small batches still spread over the CUs
 static int serl_venv_launch(serl_ctx *c, const serl_venv_desc *d, bool step, VenvArgs &v, hipStream_t stream,
-                            const serl_venv_auto_desc *au = nullptr)
+                            const serl_venv_auto_desc *au = nullptr, const serl_venv_rollout_desc *rd = nullptr)
 {
   const BuildSlot &s = c->slots[d->build_slot];
   const SerlLaunchers &L = serl_launchers(s.code);
@@ -822,7 +825,11 @@ static int serl_venv_launch(serl_ctx *c, const serl_venv_desc *d, bool step, Ven
   const int grid = (nwaves + wpb - 1) / wpb;
   v.d = *d;
   v.npad = serl_venv_npad(d->n_envs);
-  if (au) L.venv_step_auto(a, v, *au, grid, stream);
+  if (rd) {      // the actor shape the lane forward reads (rollout_device.h serl_actor_forward_lane32)
+    a.d.state_dim = rd->state_dim; a.d.action_dim = rd->action_dim; a.d.hidden = rd->hidden;
+    a.d.num_layers = rd->num_layers; a.d.activation = rd->activation;
+    L.venv_rollout(a, v, *au, *rd, grid, stream);
+  } else if (au) L.venv_step_auto(a, v, *au, grid, stream);
   else (step ? L.venv_step : L.venv_reset)(a, v, grid, stream);
   HIP_TRY(hipGetLastError());
   return SERL_OK;
@@ -886,6 +893,50 @@ int serl_venv_step_auto(serl_ctx *c, const serl_venv_desc *d, const void *action
   v.actions = actions; v.actions_f64 = actions_f64;
   v.obs = obs; v.reward = reward; v.done = done; v.x = x; v.ref = ref; v.t = t; v.cost = cost;
   return serl_venv_launch(c, &dd, true, v, (hipStream_t)stream_, au);
+}
+
+int serl_venv_rollout_layout(int32_t *out, int32_t capacity)
+{
+#define SERL_OFF(m) (int32_t)offsetof(serl_venv_rollout_desc, m)
+  const int32_t v[] = {(int32_t)sizeof(serl_venv_rollout_desc), SERL_OFF(state_dim), SERL_OFF(action_dim), SERL_OFF(hidden), SERL_OFF(num_layers),
+                       SERL_OFF(activation), SERL_OFF(n_members), SERL_OFF(weights), SERL_OFF(weight_stride), SERL_OFF(member_of_env),
+                       SERL_OFF(n_steps), SERL_OFF(pad0), SERL_OFF(action_noise), SERL_OFF(obs), SERL_OFF(actions), SERL_OFF(reward), SERL_OFF(done),
+                       SERL_OFF(final_obs), SERL_OFF(ep_return), SERL_OFF(ep_length), SERL_OFF(x), SERL_OFF(ref), SERL_OFF(t), SERL_OFF(cost),
+                       SERL_OFF(transitions)};
+#undef SERL_OFF
+  const int32_t n = (int32_t)(sizeof(v) / sizeof(v[0]));
+  for (int32_t i = 0; out && i < n && i < capacity; ++i) out[i] = v[i];
+  return n;
+}
+
+int serl_venv_rollout(serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd, void *stream_)
+{
+  const std::string w("serl_venv_rollout");
+  // (the descriptors first: none of these checks reads the context)
+  if (!c || !d || !au || !rd) return fail(SERL_E_INVALID, w + ": NULL argument");
+  if (!rd->obs || !rd->weights) return fail(SERL_E_INVALID, w + ": obs / weights is NULL");
+  if (rd->n_steps < 1) return fail(SERL_E_INVALID, w + ": n_steps < 1");
+  if (rd->n_members < 1) return fail(SERL_E_INVALID, w + ": n_members < 1");
+  if (d->env_config != SERL_ENV_ATTITUDE || d->incremental != 0)
+    return fail(SERL_E_INVALID, w + ": the attitude task without rate control only (env_config SERL_ENV_ATTITUDE, incremental 0)");
+  if (rd->hidden != 32 || rd->state_dim != 7 || rd->action_dim != 3)      // (rollout_device.h serl_lane_actor_ok)
+    return fail(SERL_E_INVALID, w + ": the in-kernel actor is 7 -> 32 .. -> 3 only (hidden 32, state_dim 7, action_dim 3)");
+  if (rd->num_layers < 0) return fail(SERL_E_INVALID, w + ": num_layers < 0");
+  if (rd->activation != SERL_ACT_TANH && rd->activation != SERL_ACT_ELU && rd->activation != SERL_ACT_LEAKY_RELU)
+    return fail(SERL_E_INVALID, w + ": unknown activation");
+  if (rd->weight_stride < (int64_t)serl_param_count(rd->state_dim, rd->hidden, rd->num_layers, rd->action_dim) || (rd->weight_stride & 3) != 0 ||
+      ((uintptr_t)rd->weights & 15) != 0)
+    return fail(SERL_E_INVALID, w + ": weight_stride below the parameter count or not a multiple of 4 floats, or weights not 16-byte aligned");
+  if (au->ref_pool && d->ref) return fail(SERL_E_INVALID, w + ": ref_pool together with desc->ref");
+  if (au->ref_pool && au->pool_rows < 1) return fail(SERL_E_INVALID, w + ": pool_rows < 1");
+  if (!au->run_return || !au->run_length || !au->cursor) return fail(SERL_E_INVALID, w + ": run_return / run_length / cursor is NULL");
+  serl_venv_desc dd = *d;
+  if (au->ref_pool) { dd.ref_spec = au->ref_pool; dd.ref_spec_stride = 1; }
+  { const int rc_ = serl_venv_check(c, &dd, w.c_str()); if (rc_ != SERL_OK) return rc_; }
+  HIP_TRY(hipSetDevice(c->device));
+  VenvArgs v;
+  memset(&v, 0, sizeof(v));
+  return serl_venv_launch(c, &dd, true, v, (hipStream_t)stream_, au, rd);
 }
 
 /* development aid (SERL_PROFILE=1): shader-clock cycles wave 0 of workgroup 0 spent in the actor forward, the

@@ -27,12 +27,18 @@ no second launch, no host synchronisation -- with the "same-step" convention of 
 The restart is what `reset(mask)` does (carried error kept, one clock tick, sensor-noise entry 0); the restarted episode flies the
 given references again, reuses the env's sensor-noise table, and with `refs=None` takes the next of `ref_pool` references drawn per
 env by the last explicit `reset` (the pool recycles after `ref_pool` episodes; an explicit `reset` draws a new one).
+
+`env.rollout(policy, K)` (serl_venv_rollout) collects K such steps in ONE launch, the actor running inside the kernel:
+
+    out = env.rollout(actor, 64, transitions=True)      # dict of step-major device tensors: obs [K + 1, N, S], actions, reward, done, ...
+    replay.append_rows(out['transitions'].reshape(-1, 20))
 """
 import ctypes
 import numpy as np
 import torch
 
 from . import _capi, builds, refsignals
+from .actor import Actor, pad_rows, spec_of, unpack_into
 
 
 class CitationVecEnv:
@@ -233,3 +239,168 @@ class CitationVecEnv:
                                             self._refk.data_ptr(), self._t.data_ptr(), self._cost.data_ptr(), self._stream()),
                     'serl_venv_step')
         return self._obs, self._reward, self._done, {'x': self._x, 'ref': self._refk, 't': self._t, 'cost': self._cost}
+
+    # ---- K policy-driven steps in one launch (serl_venv_rollout) ------------------------------------------------------------------
+    last_rollout_path = None      # 'fused' (serl_venv_rollout) or 'loop' (step by step with a torch forward) of the last rollout()
+
+    def fused_rollout_ok(self, spec):
+        """True when rollout() runs `spec` actors inside the kernel: the attitude task without rate control and the lane actor's
+        shape (7 observations, hidden 32, 3 actions; any number of hidden layers and activation)."""
+        return (self.env_config == 0 and not self.incremental and
+                (spec.state_dim, spec.hidden, spec.action_dim) == (7, 32, 3) and spec.num_layers >= 0)
+
+    def _check_rollout_args(self, policy, n_steps, spec, member_of_env, action_noise):
+        """The argument checks of rollout() that need no device work -> (K, list of actor modules or None, NetSpec)."""
+        if not self.auto_reset:
+            raise ValueError('rollout needs an env made with auto_reset=True')
+        if isinstance(n_steps, bool) or int(n_steps) != n_steps or int(n_steps) < 1:
+            raise ValueError('n_steps: an integer >= 1, not %r' % (n_steps,))
+        K, N = int(n_steps), self.n_envs
+        mods = None
+        if isinstance(policy, torch.Tensor):
+            if spec is None:
+                raise ValueError('policy: packed weights need spec=NetSpec(...)')
+            if policy.device != self.device:
+                raise ValueError('policy: packed weights on %s, the env is on %s' % (policy.device, self.device))
+            if policy.dtype != torch.float32 or policy.dim() != 2 or policy.shape[0] < 1 or policy.shape[1] < spec.param_count:
+                raise ValueError('policy: packed f32 [members, >= %d]' % spec.param_count)
+        else:
+            mods = [getattr(p, 'actor', p) for p in (policy if isinstance(policy, (list, tuple)) else [policy])]
+            if not mods:
+                raise ValueError('policy: an empty list')
+            spec = spec_of(mods[0])
+            if any(spec_of(m) != spec for m in mods):
+                raise ValueError('policy: the actors of a list must have one shape')
+        if (spec.state_dim, spec.action_dim) != (self.state_dim, self.action_dim):
+            raise ValueError('actor %d -> %d does not fit the env (%d observations, %d actions)'
+                             % (spec.state_dim, spec.action_dim, self.state_dim, self.action_dim))
+        if member_of_env is not None and tuple(np.shape(member_of_env)) != (N,):
+            raise ValueError('member_of_env: i32 [%d], not %s' % (N, tuple(np.shape(member_of_env))))
+        if action_noise is not None and tuple(np.shape(action_noise)) != (K, N, 3):
+            raise ValueError('action_noise: f64 %s, not %s' % ((K, N, 3), tuple(np.shape(action_noise))))
+        return K, mods, spec
+
+    def rollout(self, policy, n_steps, *, member_of_env=None, action_noise=None, transitions=False, info=True, spec=None):
+        """n_steps steps of every env under `policy`, restarts included, in ONE launch without host synchronisation
+        (serl_venv_rollout: the actor runs inside the kernel, bit-identical to the fused rollout kernels' forward).  Needs auto_reset=True.
+
+        policy         an Actor / GeneticAgent, a list of them, or packed f32 weights [members, >= P] on the env's device with
+                       spec=NetSpec(...) (the zero-overhead form: modules are packed on the device at every call)
+        member_of_env  i32 [N], each in [0, members): the env's member of the population; None: every env runs member 0
+        action_noise   f64 [n_steps, N, 3] added to the actor's output, the sum clipped to [-1, 1] (base/core/agent.py:90-93)
+        -> dict of fresh device tensors, step-major: 'obs' f64 [K + 1, N, S] (row 0: where the segment started; row k + 1: what
+        step() returns after step k), 'actions' f64 [K, N, A] (the executed action, actor units), 'reward' f64, 'done' bool,
+        'final_obs' f64 [K, N, S], 'ep_return' f64 / 'ep_length' i32 (valid where done, 0 elsewhere); info: 'x' [K, N, 12], 'ref'
+        [K, N, 3], 't', 'cost' i32; transitions: 'transitions' f32 [K, N, 2 S + A + 3] = (obs, action, final_obs, reward, fin, cost),
+        what DeviceReplay.append_rows takes after reshape(-1, 20) -- fin is the bounds / t_max flag, not the end of a reference table.
+        Never-reset envs stay frozen (reward 0, done, action 0; their transition rows carry fin = 1: mask them out).
+        step() and rollout() share the env state and may be mixed.  Shapes the kernel does not take (fused_rollout_ok) are stepped one by
+        one with a batched torch forward to the same dictionary; `last_rollout_path` says 'fused' or 'loop'."""
+        K, mods, spec = self._check_rollout_args(policy, n_steps, spec, member_of_env, action_noise)
+        N, S, A, dev = self.n_envs, self.state_dim, self.action_dim, self.device
+        moe = None
+        if member_of_env is not None:
+            moe = torch.as_tensor(member_of_env).to(device=dev, dtype=torch.int32).contiguous()
+        noise = None
+        if action_noise is not None:
+            noise = torch.as_tensor(action_noise, dtype=torch.float64).to(dev).contiguous()
+        if not self.fused_rollout_ok(spec):
+            self.last_rollout_path = 'loop'
+            return self._rollout_loop(policy, mods, spec, K, moe, noise, transitions, info)
+        if mods is None:
+            w = policy
+        else:      # packed on the device: no .cpu() round trip, no synchronisation
+            w = torch.stack([torch.cat([p.detach().reshape(-1) for p in m.parameters()]).to(device=dev, dtype=torch.float32) for m in mods])
+        if w.shape[1] % 4 or w.stride(0) % 4 or not w.is_contiguous():
+            w = pad_rows(w)
+        if w.data_ptr() % 16:      # (a view into a larger tensor: the kernel reads rows with 16-byte loads)
+            w = w.clone()
+        out = self._rollout_buffers(K, transitions, info)
+        rd = _capi.VenvRolloutDesc(state_dim=spec.state_dim, action_dim=spec.action_dim, hidden=spec.hidden, num_layers=spec.num_layers,
+                                   activation=spec.activation_id, n_members=w.shape[0], weights=w.data_ptr(),
+                                   weight_stride=w.stride(0) if w.shape[0] > 1 else w.shape[1], n_steps=K,
+                                   member_of_env=None if moe is None else moe.data_ptr(),
+                                   action_noise=None if noise is None else noise.data_ptr(),
+                                   obs=out['obs'].data_ptr(), actions=out['actions'].data_ptr(), reward=out['reward'].data_ptr(),
+                                   done=out['done'].data_ptr(), final_obs=out['final_obs'].data_ptr(),
+                                   ep_return=out['ep_return'].data_ptr(), ep_length=out['ep_length'].data_ptr())
+        if info:
+            rd.x, rd.ref, rd.t, rd.cost = (out[k].data_ptr() for k in ('x', 'ref', 't', 'cost'))
+        if transitions:
+            rd.transitions = out['transitions'].data_ptr()
+        _capi.check(self.lib.serl_venv_rollout(self.engine.ctx, ctypes.byref(self.desc), ctypes.byref(self.auto_desc), ctypes.byref(rd),
+                                               self._stream()), 'serl_venv_rollout')
+        del w, moe, noise      # (freed memory is handed out again only to work ordered behind this launch on the same stream)
+        self.last_rollout_path = 'fused'
+        return out
+
+    def _rollout_buffers(self, K, transitions, info):
+        N, S, A, dev = self.n_envs, self.state_dim, self.action_dim, self.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        out = {'obs': torch.empty(K + 1, N, S, **f64), 'actions': torch.empty(K, N, A, **f64), 'reward': torch.empty(K, N, **f64),
+               'done': torch.empty(K, N, dtype=torch.bool, device=dev), 'final_obs': torch.empty(K, N, S, **f64),
+               'ep_return': torch.zeros(K, N, **f64), 'ep_length': torch.zeros(K, N, dtype=torch.int32, device=dev)}
+        if info:
+            out.update(x=torch.empty(K, N, 12, **f64), ref=torch.empty(K, N, 3, **f64), t=torch.empty(K, N, **f64),
+                       cost=torch.empty(K, N, dtype=torch.int32, device=dev))
+        if transitions:
+            out['transitions'] = torch.empty(K, N, 2 * S + A + 3, dtype=torch.float32, device=dev)
+        return out
+
+    def _rollout_loop(self, policy, mods, spec, K, moe, noise, transitions, info):
+        """rollout() for the shapes serl_venv_rollout does not take: K x step() with a batched torch forward, to the same dictionary."""
+        N, S, A, dev = self.n_envs, self.state_dim, self.action_dim, self.device
+        if mods is None:      # packed rows -> modules (a host round trip per member: this is the slow path)
+            import types
+            args = types.SimpleNamespace(state_dim=spec.state_dim, action_dim=spec.action_dim, hidden_size=spec.hidden,
+                                         num_layers=spec.num_layers, activation_actor=spec.activation, device=dev)
+            mods = []
+            for row in policy:
+                mods.append(Actor(args))
+                unpack_into(mods[-1], row)
+        else:
+            import copy
+            mods = [m if next(m.parameters()).device == dev else copy.deepcopy(m).to(dev) for m in mods]
+
+        def forward(o):
+            with torch.no_grad():
+                if moe is None:
+                    return mods[0](o)
+                a = torch.zeros(N, A, dtype=torch.float32, device=dev)
+                for j, m in enumerate(mods):
+                    a = torch.where((moe == j)[:, None], m(o), a)
+                return a
+        # the state buffer (csrc/rollout_device.h SerlVenvF64 / SerlVenvI32): 73 f64 fields, then 17 i32 fields, [field][N rounded up to 64]
+        npad = (N + 63) // 64 * 64
+        t_env = self._state[:73 * npad * 8].view(torch.float64).view(73, npad)[57, :N]      # SERL_VF_T: the env's accumulated time
+        live = self._state[73 * npad * 8:].view(torch.int32).view(17, npad)[15, :N].ne(0).clone()      # SERL_VI_LIVE: never changes under auto-reset
+        deg = 3.14159265358979323846 / 180.0
+        out = self._rollout_buffers(K, transitions, info)
+        # the current observation of every env: a reset of no env writes it
+        none = torch.zeros(N, dtype=torch.bool, device=dev)
+        _capi.check(self.lib.serl_venv_reset(self.engine.ctx, ctypes.byref(self.desc), none.data_ptr(), self._obs.data_ptr(),
+                                             self._stream()), 'serl_venv_reset')
+        out['obs'][0].copy_(self._obs)
+        for k in range(K):
+            o = out['obs'][k]
+            a = forward(o.float())
+            if noise is not None:
+                a = torch.clamp(a.double() + noise[k, :, :A], -1.0, 1.0)
+            out['actions'][k].copy_(torch.where(live[:, None], a.double(), torch.zeros_like(a, dtype=torch.float64)))
+            timed_out = t_env >= self.t_max      # (at the pre-increment t, as the env decides it)
+            obs, rew, done, inf = self.step(a)
+            out['obs'][k + 1].copy_(obs); out['reward'][k].copy_(rew); out['done'][k].copy_(done)
+            out['final_obs'][k].copy_(inf['final_obs'])
+            ended = done & live
+            out['ep_return'][k].copy_(torch.where(ended, inf['episode_return'], torch.zeros_like(rew)))
+            out['ep_length'][k].copy_(torch.where(ended, inf['episode_length'], torch.zeros_like(inf['episode_length'])))
+            if info:
+                for key in ('x', 'ref', 't', 'cost'):
+                    out[key][k].copy_(inf[key])
+            if transitions:
+                x = inf['x']
+                fin = timed_out | (x[:, 7].abs() > 60.0 * deg) | (x[:, 6].abs() > 75.0 * deg) | (x[:, 9] < 50.0)
+                fin = torch.where(live, fin, torch.ones_like(fin))
+                out['transitions'][k].copy_(torch.cat([o.float(), out['actions'][k].float(), inf['final_obs'].float(), rew.float()[:, None],
+                                                       fin.float()[:, None], inf['cost'].ne(0).float()[:, None]], dim=1))
+        return out

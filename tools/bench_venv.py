@@ -17,7 +17,13 @@ runs the auto-reset leg instead: CitationVecEnv(auto_reset=True) (serl_venv_step
     drawn      the same with refs=None at t_max = 5 (502 steps, 0.2 % finish per step): the manual loop's `reset(done)` then finds the
                finished envs on the host and draws their references there (one synchronisation per step); auto flies its pool
                (N <= --drawn-max-n only: the host draws dominate beyond)
-    idle       no env finishing (t_max = 20, fewer steps than an episode): the auto step against the plain step -- the cost of the larger kernel"""
+    idle       no env finishing (t_max = 20, fewer steps than an episode): the auto step against the plain step -- the cost of the larger kernel
+
+    python tools/bench_venv.py --rollout [--sizes 1024,65536] [--auto-steps 1000] [--rollout-k 50] [--reps 5] [--out profiles/venv_rollout_timing.json]
+runs the rollout leg: `env.rollout(actor, K)` (serl_venv_rollout: the SERL50 actor inside the kernel, K steps per launch, fresh output
+tensors per call) against the loop it replaces, `obs, ... = env.step(actor(obs.float()))` on an auto_reset env with the same actor as a
+torch module on the same stream -- the same `staggered` and `idle` settings, medians and [min .. max] of `reps` repetitions of
+--auto-steps env steps after a warm-up, the versions alternating."""
 import argparse, json, os, subprocess, sys
 import numpy as np
 import torch
@@ -152,6 +158,55 @@ def bench_auto(eng, N, steps, warmup, reps, drawn_steps, drawn_max_n):
     return out
 
 
+def bench_rollout(eng, N, steps, K, warmup, reps):
+    """One size: rollout(actor, K) against the step loop with the torch actor, episodes of 32 steps at spread phases and no env finishing."""
+    dev = eng.device
+    fixed = torch.zeros(N, 3, dtype=torch.float32, device=dev)
+    actor = serl50_policy(dev)
+    L = 32
+    table = np.ascontiguousarray(rs.tabulate(*rs.base_reference(20), 20)[:L])
+    full = rs.tabulate(*rs.base_reference(20), 20)
+    assert steps % K == 0 and warmup % K == 0 and steps + warmup < len(full)
+    out = dict(N=N, steps=steps, K=K, reps=reps, warmup=warmup)
+
+    def run(env, v, n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        if v == 'rollout':
+            for _ in range(n // K):
+                o = env.rollout(actor, K)
+            assert env.last_rollout_path == 'fused'
+            done = o['done'][-1]
+        else:
+            obs = env.reset(torch.zeros(N, dtype=torch.bool, device=dev)) if n else None      # (the current observation; one launch per run)
+            for _ in range(n):
+                obs, rew, done, info = env.step(actor(obs.float()))
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1), int(done.sum())
+
+    for name, refs, stagger_L in (('staggered', table, L), ('idle', full, 0)):
+        envs = {v: serl_amd.CitationVecEnv(N, mode='nominal', t_max=20, refs=refs, engine=eng, auto_reset=True) for v in ('rollout', 'loop')}
+        ms, fin = {v: [] for v in envs}, {}
+        with torch.no_grad():
+            for v, env in envs.items():
+                if stagger_L:
+                    _stagger(env, stagger_L, fixed)
+                else:
+                    env.reset()
+                run(env, v, warmup)
+            for r in range(reps):
+                for v, env in (list(envs.items()) if r % 2 == 0 else list(envs.items())[::-1]):      # alternate the order
+                    if not stagger_L:
+                        env.reset()      # idle: every repetition from a fresh episode, so that no env finishes
+                    m, fin[v] = run(env, v, steps)
+                    ms[v].append(m)
+        out[name] = dict(rollout=_summary(N, steps, ms['rollout']), loop=_summary(N, steps, ms['loop']), finished_on_last_step=fin)
+        a, m = out[name]['rollout']['env_steps_per_s'], out[name]['loop']['env_steps_per_s']
+        out[name]['speedup_of_medians'] = round(a['median'] / m['median'], 3)
+    return out
+
+
 def kernel_report():
     rep = {}
     for v in ('nominal', 'ice', 'cg_timed', 'gust', 'test'):
@@ -165,7 +220,7 @@ def kernel_report():
                 continue
             f = dict(p.strip().split(': ', 1) for p in line.split('\t') if ': ' in p)
             name = f['.name'].strip()
-            kind = 'step_auto' if 'step_auto' in name else 'step' if 'step' in name else 'reset'
+            kind = 'rollout' if 'venv_rollout' in name else 'step_auto' if 'step_auto' in name else 'step' if 'step' in name else 'reset'
             rep['%s_%s' % (kind, v)] = dict(vgpr=int(f['.vgpr_count']), vgpr_spill=int(f['.vgpr_spill_count']), sgpr_spill=int(f['.sgpr_spill_count']),
                                             lds_bytes=int(f['.group_segment_fixed_size']), scratch_bytes=int(f['.private_segment_fixed_size']))
     return rep
@@ -182,9 +237,25 @@ def main():
     ap.add_argument('--drawn-steps', type=int, default=300)
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--drawn-max-n', type=int, default=8192, help='largest N of the drawn comparison')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'venv_auto_timing.json'))
+    ap.add_argument('--rollout', action='store_true', help='the rollout leg instead of the others')
+    ap.add_argument('--rollout-k', type=int, default=50, help='steps per rollout() call')
+    ap.add_argument('--out', default=None, help='default: profiles/venv_auto_timing.json (--auto-reset), profiles/venv_rollout_timing.json (--rollout)')
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, 'profiles', 'venv_rollout_timing.json' if args.rollout else 'venv_auto_timing.json')
     eng = serl_amd.RolloutEngine(0)
+    if args.rollout:
+        sizes = [int(s) for s in (args.sizes if args.sizes != ap.get_default('sizes') else '1024,65536').split(',')]
+        res = dict(tool='bench_venv --rollout', device=torch.cuda.get_device_name(0), source_hash=hip_build.source_hash(),
+                   results=[bench_rollout(eng, N, args.auto_steps, args.rollout_k, args.warmup, args.reps) for N in sizes])
+        kernels = kernel_report()      # (needs the build's objects: empty where only the library was shipped)
+        if kernels:
+            res['kernels'] = kernels
+        with open(args.out, 'w') as f:
+            json.dump(res, f, indent=1)
+            f.write('\n')
+        print(json.dumps(res))
+        return
     if args.auto_reset:
         sizes = [int(s) for s in (args.sizes if args.sizes != ap.get_default('sizes') else '1024,65536').split(',')]
         res = dict(tool='bench_venv --auto-reset', device=torch.cuda.get_device_name(0), source_hash=hip_build.source_hash(),
