@@ -373,6 +373,20 @@ int serl_venv_rollout_layout(int32_t *out, int32_t capacity);
 int serl_venv_rollout(serl_ctx *ctx, const serl_venv_desc *desc, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *ro,
                       void *stream);
 
+/* serl_venv_rollout for every env configuration and actor shape: the same three descriptors (no member added, the layout functions and
+ * SERL_ABI_VERSION unchanged), the same semantics, one launch of a second kernel whose actor keeps its activations in private memory.
+ * state_dim / action_dim of `ro` must be those of the env configuration of `desc` (attitude 7 / 3, symmetric 2 / 1, full 13 / 3;
+ * incremental adds action_dim observations, and the action is then a rate, integrated as serl_venv_step does); hidden a multiple of 4
+ * in 4 .. 128, num_layers 0 .. 16, every activation.  Rows are [n_steps][n_envs][state_dim], [..][action_dim] and, for transitions,
+ * [..][2 state_dim + action_dim + 3] = (obs, executed action, final_obs, reward, fin, cost), the row of serl_rollout_desc.transitions
+ * in that configuration.  action_noise keeps its [n_steps][n_envs][3] layout; its first action_dim columns are read.
+ * SERL_E_INVALID / SERL_E_UNSUPPORTED (hidden, num_layers out of range) before any launch: a NULL argument, NULL obs or weights, n_steps
+ * < 1, n_members < 1, an actor that does not fit the env configuration, an unknown activation, a weight_stride below the parameter count
+ * or not a multiple of 4, weights not 16-byte aligned, and what serl_venv_step_auto refuses in `desc` / `au`.  serl_venv_rollout itself
+ * keeps its one shape: where both take a call they return the same bits. */
+int serl_venv_rollout_general(serl_ctx *ctx, const serl_venv_desc *desc, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *ro,
+                              void *stream);
+
 /* Development aid: with SERL_PROFILE=1 in the environment serl_rollout records shader-clock cycles of wave 0 of
  * workgroup 0: out[0..3] = {actor forward, dynamics step, env bookkeeping, env steps}; out[4..31] = phase
  * counters of the model evaluation (non-zero only in builds compiled with -DCITW_PROFILE). */

@@ -14,7 +14,7 @@ EXPORTS = ['serl_abi_version', 'serl_last_error', 'serl_param_count', 'serl_ctx_
            'serl_replay_scatter', 'serl_replay_scatter_rows', 'serl_env_state_dim', 'serl_env_action_dim',
            'serl_smoothness', 'serl_smoothness_work_size', 'serl_ga_distill', 'serl_host_sample_slots',
            'serl_venv_state_bytes', 'serl_venv_reset', 'serl_venv_step', 'serl_venv_step_auto', 'serl_venv_auto_layout',
-           'serl_venv_rollout', 'serl_venv_rollout_layout',
+           'serl_venv_rollout', 'serl_venv_rollout_layout', 'serl_venv_rollout_general',
            'serl_td3_train', 'serl_td3_work_bytes', 'serl_td3_param_count', 'serl_td3_layout']
 
 
@@ -169,6 +169,7 @@ def lib():
     L.serl_venv_auto_layout.argtypes = [VP, ctypes.c_int32]
     L.serl_venv_rollout.argtypes = [VP, ctypes.POINTER(VenvDesc), ctypes.POINTER(VenvAutoDesc), ctypes.POINTER(VenvRolloutDesc), VP]
     L.serl_venv_rollout_layout.argtypes = [VP, ctypes.c_int32]
+    L.serl_venv_rollout_general.argtypes = L.serl_venv_rollout.argtypes
     L.serl_td3_train.argtypes = [VP, ctypes.POINTER(Td3Desc), VP]
     L.serl_td3_work_bytes.argtypes = [i32] * 6
     L.serl_td3_param_count.argtypes = [ctypes.c_int, ctypes.c_int]

@@ -57,3 +57,4 @@ void SERL_V(serl_launch_venv_reset_)(const RolloutArgs &a, const VenvArgs &v, in
 void SERL_V(serl_launch_venv_step_)(const RolloutArgs &a, const VenvArgs &v, int grid, hipStream_t stream) { bdag::SERL_V(serl_launch_venv_step_)(a, v, grid, stream); }
 void SERL_V(serl_launch_venv_step_auto_)(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, int grid, hipStream_t stream) { bdag::SERL_V(serl_launch_venv_step_auto_)(a, v, au, grid, stream); }
 void SERL_V(serl_launch_venv_rollout_)(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, const serl_venv_rollout_desc &rd, int grid, hipStream_t stream) { bdag::SERL_V(serl_launch_venv_rollout_)(a, v, au, rd, grid, stream); }
+void SERL_V(serl_launch_venv_rollout_general_)(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, const serl_venv_rollout_desc &rd, int grid, hipStream_t stream) { bdag::SERL_V(serl_launch_venv_rollout_general_)(a, v, au, rd, grid, stream); }

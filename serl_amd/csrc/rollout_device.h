@@ -1258,6 +1258,162 @@ static __device__ void serl_actor_forward_lane32(const serl_rollout_desc &dd, co
   }
 }
 
+// ---- one env per LANE, every actor shape the ABI takes (venv_variant.inc serl_venv_rollout_general_kernel_<v>) -----------------------------------------
+// hidden a multiple of 4 in 4 .. 128, 0 .. 16 hidden layers, every activation, up to 16 observations, 1 or 3 actions.  The lane kernels have no LDS left
+// (the tables take 163 800 of 163 840 B) and 2 x 128 activations are no register set, so the two activation vectors live in PRIVATE memory, indexed at
+// run time: scratch is lane-interleaved, the index is wave-uniform, so every access is one coalesced line per wavefront.  Four output rows per pass over the
+// previous layer -- one 16-byte load of h[j .. j + 3] feeds 16 multiply-adds -- and hidden / output rows read with 16-byte loads: every tensor offset of
+// the packed layout is a multiple of four floats when H % 4 == 0.  The layer-0 rows of S floats are not aligned and are read float by float.  The arithmetic
+// is the scalar statement of the ABI (oracle/rollout_ref.c actor_forward: dot4, tree_sum), as in serl_actor_forward_lane32: four interleaved fma partial sums
+// p[j & 3] over ascending j, bias + ((p0 + p1) + (p2 + p3)); LayerNorm sums as a balanced pairwise tree per block of 16 rows, zero padded, the blocks added in
+// order.  H, L, S, A and the activation are wave-uniform (the descriptor), the weights are the lane's own member's.
+static __device__ __forceinline__ float serl_tree16_v4(const serl_v4f &a, const serl_v4f &b, const serl_v4f &c, const serl_v4f &d)
+{
+  const float a0 = a.x + a.y, a1 = a.z + a.w, a2 = b.x + b.y, a3 = b.z + b.w;
+  const float a4 = c.x + c.y, a5 = c.z + c.w, a6 = d.x + d.y, a7 = d.z + d.w;
+  const float b0 = a0 + a1, b1 = a2 + a3, b2 = a4 + a5, b3 = a6 + a7;
+  const float c0 = b0 + b1, c1 = b2 + b3;
+  return c0 + c1;
+}
+// R rows of H columns from `rows` (row stride H floats, 16-byte aligned) against h[0 .. H): out[r] = (p0 + p1) + (p2 + p3), the bias is the caller's.
+// Sixteen columns per trip: the 4 R + 4 loads of a trip are issued together (a lone wavefront pays one memory round trip per trip, not one per group of
+// four columns); the groups beyond H -- H % 16 != 0 -- load the last group again (an address inside the row) and are left out of the sums.
+template <int R>
+static __device__ __forceinline__ void serl_lane_rows(serl_gptr rows, const int H, const float *h, float (&out)[R])
+{
+  float p[R][4];
+#pragma unroll
+  for (int r = 0; r < R; ++r) { p[r][0] = 0.0f; p[r][1] = 0.0f; p[r][2] = 0.0f; p[r][3] = 0.0f; }
+#pragma nounroll
+  for (int j = 0; j < H; j += 16) {
+    serl_v4f hv[4], wv[R][4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int jq = j + 4 * q < H ? j + 4 * q : H - 4;
+      hv[q] = *(const serl_v4f *)(h + jq);
+#pragma unroll
+      for (int r = 0; r < R; ++r) wv[r][q] = *(serl_gptr4)(rows + (size_t)r * H + jq);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if (j + 4 * q < H) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          p[r][0] = __builtin_fmaf(wv[r][q].x, hv[q].x, p[r][0]); p[r][1] = __builtin_fmaf(wv[r][q].y, hv[q].y, p[r][1]);
+          p[r][2] = __builtin_fmaf(wv[r][q].z, hv[q].z, p[r][2]); p[r][3] = __builtin_fmaf(wv[r][q].w, hv[q].w, p[r][3]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r) out[r] = (p[r][0] + p[r][1]) + (p[r][2] + p[r][3]);
+}
+static __device__ void serl_actor_forward_lane_general(const serl_rollout_desc &dd, const float *w_lane, const float (&obs)[16], float (&act_out)[3])
+{
+  const int H = __builtin_amdgcn_readfirstlane(dd.hidden), L = __builtin_amdgcn_readfirstlane(dd.num_layers);
+  const int S = __builtin_amdgcn_readfirstlane(dd.state_dim), A = __builtin_amdgcn_readfirstlane(dd.action_dim);
+  const int act = __builtin_amdgcn_readfirstlane(dd.activation);
+  serl_gptr W = (serl_gptr)w_lane;                      // this lane's member
+  __attribute__((aligned(16))) float hbuf[2][SERL_MAX_HIDDEN];
+  float *h0 = hbuf[0], *h1 = hbuf[1];
+  // ---- Linear(S, H) act
+  {
+    serl_gptr b0 = W + (size_t)H * S;
+#pragma nounroll
+    for (int i = 0; i < H; i += 4) {
+      float p[4][4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { p[r][0] = 0.0f; p[r][1] = 0.0f; p[r][2] = 0.0f; p[r][3] = 0.0f; }
+      serl_gptr row = W + (size_t)i * S;
+      float wv[4][16];      // (all loads of the four rows first; the columns beyond S read column S - 1 again and are left out of the sums)
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const int jc = j < S ? j : S - 1;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) wv[r][j] = row[r * S + jc];
+      }
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        if (j < S) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) p[r][j & 3] = __builtin_fmaf(wv[r][j], obs[j], p[r][j & 3]);
+        }
+      }
+      const serl_v4f bv = *(serl_gptr4)(b0 + i);
+      serl_v4f t;
+      t.x = serl_act(bv.x + ((p[0][0] + p[0][1]) + (p[0][2] + p[0][3])), act);
+      t.y = serl_act(bv.y + ((p[1][0] + p[1][1]) + (p[1][2] + p[1][3])), act);
+      t.z = serl_act(bv.z + ((p[2][0] + p[2][1]) + (p[2][2] + p[2][3])), act);
+      t.w = serl_act(bv.w + ((p[3][0] + p[3][1]) + (p[3][2] + p[3][3])), act);
+      *(serl_v4f *)(h0 + i) = t;
+    }
+  }
+  const size_t lstride = (size_t)H * H + 3 * (size_t)H;
+  serl_gptr hid = W + (size_t)H * S + H;
+  const serl_v4f zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma nounroll
+  for (int l = 0; l < L; ++l) {
+    serl_gptr Wl = hid + (size_t)l * lstride, bl = Wl + (size_t)H * H;
+#pragma nounroll
+    for (int i = 0; i < H; i += 4) {
+      float t[4];
+      serl_lane_rows<4>(Wl + (size_t)i * H, H, h0, t);
+      const serl_v4f bv = *(serl_gptr4)(bl + i);
+      serl_v4f o;
+      o.x = bv.x + t[0]; o.y = bv.y + t[1]; o.z = bv.z + t[2]; o.w = bv.w + t[3];
+      *(serl_v4f *)(h1 + i) = o;
+    }
+    // LayerNorm: the two sums block by block of 16 rows (the last block zero padded: H % 4 == 0, so whole groups of four)
+    float sum = 0.0f;
+#pragma nounroll
+    for (int b = 0; b < H; b += 16) {
+      serl_v4f v[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[q] = b + 4 * q < H ? *(const serl_v4f *)(h1 + b + 4 * q) : zero4;
+      const float t = serl_tree16_v4(v[0], v[1], v[2], v[3]);
+      sum = b == 0 ? t : sum + t;
+    }
+    const float mean = sum / (float)H;
+    float var = 0.0f;
+#pragma nounroll
+    for (int b = 0; b < H; b += 16) {
+      serl_v4f v[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        v[q] = zero4;
+        if (b + 4 * q < H) {
+          const serl_v4f hv = *(const serl_v4f *)(h1 + b + 4 * q);
+          const float d0 = hv.x - mean, d1 = hv.y - mean, d2 = hv.z - mean, d3 = hv.w - mean;
+          v[q].x = d0 * d0; v[q].y = d1 * d1; v[q].z = d2 * d2; v[q].w = d3 * d3;
+        }
+      }
+      const float t = serl_tree16_v4(v[0], v[1], v[2], v[3]);
+      var = b == 0 ? t : var + t;
+    }
+    const float den = sqrtf(var / (float)(H - 1)) + 1e-6f;
+#pragma nounroll
+    for (int i = 0; i < H; i += 4) {
+      const serl_v4f hv = *(const serl_v4f *)(h1 + i);
+      const serl_v4f gm = *(serl_gptr4)(bl + H + i), bt = *(serl_gptr4)(bl + 2 * H + i);
+      serl_v4f t;
+      t.x = serl_act(gm.x * (hv.x - mean) / den + bt.x, act);
+      t.y = serl_act(gm.y * (hv.y - mean) / den + bt.y, act);
+      t.z = serl_act(gm.z * (hv.z - mean) / den + bt.z, act);
+      t.w = serl_act(gm.w * (hv.w - mean) / den + bt.w, act);
+      *(serl_v4f *)(h0 + i) = t;
+    }
+  }
+  // ---- Linear(H, A) tanh
+  serl_gptr outl = hid + (size_t)L * lstride;
+#pragma nounroll
+  for (int i = 0; i < A; ++i) {
+    float t[1];
+    serl_lane_rows<1>(outl + (size_t)i * H, H, h0, t);
+    const float r = det_tanhf((outl + (size_t)A * H)[i] + t[0]);
+    if (i == 0) act_out[0] = r; else if (i == 1) act_out[1] = r; else act_out[2] = r;
+  }
+}
+
 // The same forward pass over the REGROUPED weights (RolloutArgs.wt: [ceil(P / 4)][members][4], serl_capi.hip serl_regroup_weights_kernel).  A lane that walks
 // its member's row of [members][P] asks the texture path for 64 different cache lines per load instruction (a row of 32 weights is one line: four rows in
 // flight x 64 lanes are the whole 32 KB L1), and the forward pass -- 3.7 k fma per lane -- cost 0.23 M cycles per wavefront and env step.  Here parameter

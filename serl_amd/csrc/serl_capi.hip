@@ -29,6 +29,7 @@ typedef void SerlLaunchVenvRollout(const RolloutArgs &a, const VenvArgs &v, cons
   X(SerlLaunchVenv, venv_step, serl_launch_venv_step_##v)                                                                                        \
   X(SerlLaunchVenvAuto, venv_step_auto, serl_launch_venv_step_auto_##v) /* ... step with auto-reset */                                           \
   X(SerlLaunchVenvRollout, venv_rollout, serl_launch_venv_rollout_##v)  /* ... K steps under the lane actor */                                   \
+  X(SerlLaunchVenvRollout, venv_rollout_general, serl_launch_venv_rollout_general_##v) /* ... any env configuration and actor shape */          \
   X(SerlLaunch, wave, serl_launch_rollout_wave_##v)         /* one wavefront per episode (rollout_wave.inc) ... */                               \
   X(SerlLaunch, wavex, serl_launch_rollout_wavex_##v)       /* ... env configurations other than the attitude task */                           \
   X(SerlLaunchDyn, dyn_wave, serl_launch_dyn_wave_##v)                                                                                           \
@@ -807,7 +808,7 @@ static int serl_venv_check(serl_ctx *c, const serl_venv_desc *d, const char *wha
 
 // the launch shape of serl_dyn_open_loop's lane kernels: lanes per wavefront from the batch, so that small batches still spread over the CUs
 static int serl_venv_launch(serl_ctx *c, const serl_venv_desc *d, bool step, VenvArgs &v, hipStream_t stream,
-                            const serl_venv_auto_desc *au = nullptr, const serl_venv_rollout_desc *rd = nullptr)
+                            const serl_venv_auto_desc *au = nullptr, const serl_venv_rollout_desc *rd = nullptr, bool general = false)
 {
   const BuildSlot &s = c->slots[d->build_slot];
   const SerlLaunchers &L = serl_launchers(s.code);
@@ -825,10 +826,10 @@ static int serl_venv_launch(serl_ctx *c, const serl_venv_desc *d, bool step, Ven
   const int grid = (nwaves + wpb - 1) / wpb;
   v.d = *d;
   v.npad = serl_venv_npad(d->n_envs);
-  if (rd) {      // the actor shape the lane forward reads (rollout_device.h serl_actor_forward_lane32)
+  if (rd) {      // the actor shape the lane forward reads (rollout_device.h serl_actor_forward_lane32 / _lane_general)
     a.d.state_dim = rd->state_dim; a.d.action_dim = rd->action_dim; a.d.hidden = rd->hidden;
     a.d.num_layers = rd->num_layers; a.d.activation = rd->activation;
-    L.venv_rollout(a, v, *au, *rd, grid, stream);
+    (general ? L.venv_rollout_general : L.venv_rollout)(a, v, *au, *rd, grid, stream);
   } else if (au) L.venv_step_auto(a, v, *au, grid, stream);
   else (step ? L.venv_step : L.venv_reset)(a, v, grid, stream);
   HIP_TRY(hipGetLastError());
@@ -937,6 +938,38 @@ int serl_venv_rollout(serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto
   VenvArgs v;
   memset(&v, 0, sizeof(v));
   return serl_venv_launch(c, &dd, true, v, (hipStream_t)stream_, au, rd);
+}
+
+int serl_venv_rollout_general(serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd, void *stream_)
+{
+  const std::string w("serl_venv_rollout_general");
+  // (the descriptors first: none of these checks reads the context)
+  if (!c || !d || !au || !rd) return fail(SERL_E_INVALID, w + ": NULL argument");
+  if (!rd->obs || !rd->weights) return fail(SERL_E_INVALID, w + ": obs / weights is NULL");
+  if (rd->n_steps < 1) return fail(SERL_E_INVALID, w + ": n_steps < 1");
+  if (rd->n_members < 1) return fail(SERL_E_INVALID, w + ": n_members < 1");
+  if (serl_env_state_dim(d->env_config, d->incremental) == 0)
+    return fail(SERL_E_INVALID, w + ": env_config must be SERL_ENV_ATTITUDE, SERL_ENV_SYMMETRIC or SERL_ENV_FULL");
+  if (rd->state_dim != serl_env_state_dim(d->env_config, d->incremental) || rd->action_dim != serl_env_action_dim(d->env_config))
+    return fail(SERL_E_INVALID, w + ": the actor's state_dim / action_dim do not match the env configuration (attitude 7 / 3, symmetric 2 / 1, full 13 / 3; incremental adds action_dim observations)");
+  if (rd->hidden < 4 || rd->hidden > SERL_MAX_HIDDEN || rd->hidden % 4 != 0)
+    return fail(SERL_E_UNSUPPORTED, w + ": hidden must be a multiple of 4 in 4 .. 128");
+  if (rd->num_layers < 0 || rd->num_layers > 16) return fail(SERL_E_UNSUPPORTED, w + ": num_layers must be 0 .. 16");
+  if (rd->activation != SERL_ACT_TANH && rd->activation != SERL_ACT_ELU && rd->activation != SERL_ACT_LEAKY_RELU)
+    return fail(SERL_E_INVALID, w + ": unknown activation");
+  if (rd->weight_stride < (int64_t)serl_param_count(rd->state_dim, rd->hidden, rd->num_layers, rd->action_dim) || (rd->weight_stride & 3) != 0 ||
+      ((uintptr_t)rd->weights & 15) != 0)
+    return fail(SERL_E_INVALID, w + ": weight_stride below the parameter count or not a multiple of 4 floats, or weights not 16-byte aligned");
+  if (au->ref_pool && d->ref) return fail(SERL_E_INVALID, w + ": ref_pool together with desc->ref");
+  if (au->ref_pool && au->pool_rows < 1) return fail(SERL_E_INVALID, w + ": pool_rows < 1");
+  if (!au->run_return || !au->run_length || !au->cursor) return fail(SERL_E_INVALID, w + ": run_return / run_length / cursor is NULL");
+  serl_venv_desc dd = *d;
+  if (au->ref_pool) { dd.ref_spec = au->ref_pool; dd.ref_spec_stride = 1; }
+  { const int rc_ = serl_venv_check(c, &dd, w.c_str()); if (rc_ != SERL_OK) return rc_; }
+  HIP_TRY(hipSetDevice(c->device));
+  VenvArgs v;
+  memset(&v, 0, sizeof(v));
+  return serl_venv_launch(c, &dd, true, v, (hipStream_t)stream_, au, rd, true);
 }
 
 /* development aid (SERL_PROFILE=1): shader-clock cycles wave 0 of workgroup 0 spent in the actor forward, the

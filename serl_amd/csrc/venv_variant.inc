@@ -517,6 +517,210 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_rollout_kernel_)
   au.run_return[e] = run_return; au.run_length[e] = run_length; au.cursor[e] = cur;
 }
 
+// The same K policy-driven steps for EVERY env configuration and actor shape (serl_venv_rollout_general in include/serl_amd.h): cfg, incr, S and A
+// come from the env descriptor at run time, as in serl_venv_step_auto_kernel_ -- whose action path, err / reward / write_obs handling for A == 1 and
+// incremental command are taken statement for statement, the noise and f32 forms from the general-env branch of the wave kernels (rollout_wave.inc) --
+// and the actor is rollout_device.h serl_actor_forward_lane_general (its two activation vectors in private memory).  Rows are [k][N][S], [k][N][A] and
+// [k][N][2 S + A + 3]; action_noise stays [K][N][3], of which the first A columns are read.  ONE call site of the actor and ONE of cit_step_<v>, both loops
+// rolled, exactly as above.
+__global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_rollout_general_kernel_)(RolloutArgs a, VenvArgs v, serl_venv_auto_desc au, serl_venv_rollout_desc rd)
+{
+  const int e = VV_NAME(serl_stage_and_index_)(a);
+  if (e < 0) return;
+  const serl_venv_desc &d = v.d;
+  double *S_ = (double *)d.state;
+  int32_t *I = (int32_t *)(S_ + SERL_VENV_F64 * v.npad);
+  const int64_t np = v.npad;
+  const size_t N = (size_t)d.n_envs;
+  const int K = rd.n_steps;
+  const int cfg = d.env_config, A = d.action_dim, S = d.state_dim;
+  const bool incr = d.incremental != 0;
+  const int TW = 2 * S + A + 3;
+  double err[3], u[3], x[12], obs[16];
+  for (int i = 0; i < 3; ++i) { err[i] = S_[(SERL_VF_ERR + i) * np + e]; u[i] = S_[(SERL_VF_LASTU + i) * np + e]; }
+  for (int i = 0; i < 12; ++i) x[i] = S_[(SERL_VF_XO + i) * np + e];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) obs[i] = 0.0;
+  serl_venv_write_obs(cfg, incr, err, x, u, obs);      // the current observation, as serl_venv_write_frozen rebuilds it
+#pragma unroll
+  for (int i = 0; i < 16; ++i) if (i < S) rd.obs[(size_t)e * S + i] = obs[i];
+  if (!I[SERL_VI_LIVE * np + e]) {      // never reset: frozen in every row, as in serl_venv_step_auto (no action: zeros; the transition marks itself terminal)
+    const double rf[3] = {S_[(SERL_VF_REF + 0) * np + e], S_[(SERL_VF_REF + 1) * np + e], S_[(SERL_VF_REF + 2) * np + e]};
+    const double tf = S_[SERL_VF_T * np + e];
+    const int32_t cf = I[SERL_VI_COST * np + e];
+#pragma nounroll
+    for (int kk = 0; kk < K; ++kk) {
+      const size_t kn = (size_t)kk * N + (size_t)e;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) if (i < S) rd.obs[(kn + N) * S + i] = obs[i];
+      if (rd.actions) for (int i = 0; i < 3; ++i) if (i < A) rd.actions[kn * A + i] = 0.0;
+      if (rd.reward) rd.reward[kn] = 0.0;
+      if (rd.done) rd.done[kn] = 1;
+      if (rd.final_obs) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) if (i < S) rd.final_obs[kn * S + i] = obs[i];
+      }
+      if (rd.x) for (int i = 0; i < 12; ++i) rd.x[kn * 12 + i] = x[i];
+      if (rd.ref) for (int i = 0; i < 3; ++i) rd.ref[kn * 3 + i] = rf[i];
+      if (rd.t) rd.t[kn] = tf;
+      if (rd.cost) rd.cost[kn] = cf;
+      if (rd.transitions) {
+        float *tr = rd.transitions + kn * TW;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) if (i < S) { tr[i] = (float)obs[i]; tr[S + A + i] = (float)obs[i]; }
+        for (int i = 0; i < 3; ++i) if (i < A) tr[S + i] = 0.0f;
+        tr[2 * S + A] = 0.0f; tr[2 * S + A + 1] = 1.0f; tr[2 * S + A + 2] = cf ? 1.0f : 0.0f;
+      }
+    }
+    return;
+  }
+  const double PI = 3.14159265358979323846;
+  const double deg2rad = PI / 180.0, rad2deg = 180.0 / PI;
+  const double bound = (incr ? 25.0 : 10.0) * deg2rad, low = -bound, high = bound;
+  const double max_theta = 60.0 * deg2rad, max_phi = 75.0 * deg2rad;
+  const double scaler[3] = {6.0 / PI * 1.0, 6.0 / PI * 1.0, 6.0 / PI * 4.0};
+  const double dt = 0.01;
+  double cmd[10], rk[3] = {0.0, 0.0, 0.0};
+  double V0 = S_[SERL_VF_V0 * np + e];
+  double t = S_[SERL_VF_T * np + e];
+  int k = I[SERL_VI_K * np + e];
+  int cost = 0;
+  serl_fault_row f = {1.0, __longlong_as_double(0x7ff0000000000000LL), __longlong_as_double(0x7ff0000000000000LL),
+                      0.0, 0.0, 0, 0, 0};
+  if (d.faults) f = d.faults[e];
+  // the env's member of the packed population (the index is the caller's memory: kept inside the population whatever it holds)
+  const unsigned member = rd.member_of_env ? (unsigned)rd.member_of_env[e] % (unsigned)rd.n_members : 0u;
+  const float *w = rd.weights + (size_t)member * rd.weight_stride;
+  int32_t cur = au.cursor[e];
+  double run_return = au.run_return[e];
+  int32_t run_length = au.run_length[e];
+  CitCtx ctx;
+  VV_NAME(serl_venv_load_ctx_)(a, v, e, ctx);
+#pragma nounroll
+  for (int kk = 0; kk < K; ++kk) {
+    const size_t kn = (size_t)kk * N + (size_t)e;
+    float obsf[16], act[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int i = 0; i < 16; ++i) obsf[i] = (float)obs[i];
+    serl_actor_forward_lane_general(a.d, w, obsf, act);
+    // ---- the action path of serl_venv_step_auto_kernel_ (noise / f32: the general-env branch of the wave kernels)
+    double scl[3] = {0.0, 0.0, 0.0};
+    if (rd.action_noise) {
+      const double *noise = rd.action_noise + kn * 3;
+      for (int i = 0; i < 3; ++i) {
+        if (i >= A) continue;
+        double an = serl_clip((double)act[i] + noise[i], -1.0, 1.0);
+        scl[i] = low + 0.5 * (an + 1.0) * (high - low);
+        act[i] = (float)an;     // the transition holds the action that was executed (agent.py:93,103)
+        if (rd.actions) rd.actions[kn * A + i] = an;
+      }
+    } else {
+      for (int i = 0; i < 3; ++i) {
+        if (i >= A) continue;
+        const float s = 0.5f * (act[i] + 1.0f);
+        scl[i] = low + (double)s * (high - low);
+        if (rd.actions) rd.actions[kn * A + i] = (double)act[i];
+      }
+    }
+    for (int i = 0; i < 3; ++i) u[i] = incr ? u[i] + scl[i] * dt : scl[i];
+    // ---- the step of serl_venv_step_auto_kernel_
+    for (int i = 0; i < 10; ++i) cmd[i] = 0.0;
+    cmd[0] = serl_clip(u[0] * f.elev_gain, -f.elev_clip, f.elev_clip);
+    cmd[1] = serl_clip(u[1], -f.ail_clip, f.ail_clip);
+    cmd[2] = (f.rudder_jam_on != 0.0) ? f.rudder_jam : u[2];
+    const int row = au.ref_pool ? (int)((uint32_t)cur % (uint32_t)au.pool_rows) : 0;
+    const serl_ref_spec *spec = au.ref_pool ? au.ref_pool + (size_t)e * au.pool_rows + row
+                              : d.ref_spec ? d.ref_spec + (size_t)e * d.ref_spec_stride : nullptr;
+    double V0n = V0;
+    bool restart = false;
+#pragma nounroll
+    for (int trip = 0; trip < 2; ++trip) {
+      VV_NAME(cit_step_)(&ctx, cmd, x);
+      if (const double *sn = serl_venv_sensor(d, e, restart ? 0 : k + 1)) {
+        x[0] += sn[0]; x[1] += sn[1]; x[2] += sn[2]; x[4] += sn[3]; x[5] += sn[4]; x[6] += sn[5]; x[7] += sn[6];
+      }
+      if (restart) { V0n = x[3]; break; }
+      if (spec) serl_ref_generate(spec, t, d.t_max, rk[0], rk[1], rk[2]);
+      else {
+        const double *r = d.ref + (size_t)e * d.ref_stride + (size_t)k * 3;
+        rk[0] = r[0]; rk[1] = r[1]; rk[2] = r[2];
+      }
+      err[0] = rk[0] - x[7];
+      if (A > 1) { err[1] = rk[1] - x[6]; err[2] = rk[2] - x[5]; }
+      double rsum = 0.0;
+      for (int i = 0; i < 3; ++i) if (i < A) rsum = rsum + fabs(serl_clip(scaler[i] * err[i], -1.0, 1.0));
+      double reward = -rsum / (double)A;
+      cost = (rad2deg * fabs(x[4]) > 11.0) || (rad2deg * fabs(x[6]) > 0.75 * max_phi) || (x[3] < V0 / 3.0);
+      const bool fin = (t >= d.t_max) || (fabs(x[7]) > max_theta) || (fabs(x[6]) > max_phi) || (x[9] < 50.0);
+      if (fin) reward += -1.0 / dt * (d.t_max - t) * 2.0;
+      t += dt;
+      k += 1;
+      const bool done = fin || k >= d.max_steps;
+      double nobs[16];
+      serl_venv_write_obs(cfg, incr, err, x, u, nobs);      // the terminal-aware next observation: final_obs and the transition row
+      if (rd.final_obs) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) if (i < S) rd.final_obs[kn * S + i] = nobs[i];
+      }
+      if (rd.reward) rd.reward[kn] = reward;
+      if (rd.done) rd.done[kn] = done ? 1 : 0;
+      if (rd.x) for (int i = 0; i < 12; ++i) rd.x[kn * 12 + i] = x[i];
+      if (rd.ref) for (int i = 0; i < 3; ++i) rd.ref[kn * 3 + i] = rk[i];
+      if (rd.t) rd.t[kn] = t;
+      if (rd.cost) rd.cost[kn] = cost;
+      if (rd.transitions) {      // (obs S, executed action A, next obs S, reward, fin, cost): the row of the general-env rollout kernels
+        float *tr = rd.transitions + kn * TW;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) if (i < S) { tr[i] = (float)obs[i]; tr[S + A + i] = (float)nobs[i]; }
+        for (int i = 0; i < 3; ++i) if (i < A) tr[S + i] = act[i];
+        tr[2 * S + A] = (float)reward; tr[2 * S + A + 1] = fin ? 1.0f : 0.0f; tr[2 * S + A + 2] = cost ? 1.0f : 0.0f;
+      }
+      const double ret = run_return + reward;
+      const int32_t len = run_length + 1;
+      if (!done) { run_return = ret; run_length = len; break; }
+      if (rd.ep_return) rd.ep_return[kn] = ret;
+      if (rd.ep_length) rd.ep_length[kn] = len;
+      if (au.ep_return) au.ep_return[e] = ret;      // (the env's own "last finished episode", as a step() at this point would leave it)
+      if (au.ep_length) au.ep_length[e] = len;
+      run_return = 0.0; run_length = 0;
+      cur = au.ref_pool ? (row + 1) % au.pool_rows : (int32_t)(((uint32_t)cur + 1u) & 0x7fffffffu);
+      // reset() of this env, as in serl_venv_step_auto_kernel_: the error stays, the clock keeps counting
+      restart = true;
+      const uint32_t tick = ctx.tick;
+      cit_reset(&ctx, a.ro, a.t3, a.x0, a.dw0, a.dyn_dt);
+      if (tick) { ctx.tick = tick; ctx.t = (double)ctx.tick * ctx.dt; }
+      ctx.bslot = 0;
+      for (int i = 0; i < 3; ++i) { u[i] = 0.0; rk[i] = 0.0; }
+      t = 0.0; k = 0; cost = 0;
+      for (int i = 0; i < 10; ++i) cmd[i] = 0.0;
+      cmd[0] = serl_clip(cmd[0] * f.elev_gain, -f.elev_clip, f.elev_clip);
+      cmd[1] = serl_clip(cmd[1], -f.ail_clip, f.ail_clip);
+      if (f.rudder_jam_on != 0.0) cmd[2] = f.rudder_jam;
+    }
+    V0 = V0n;
+    serl_venv_write_obs(cfg, incr, err, x, u, obs);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) if (i < S) rd.obs[(kn + N) * S + i] = obs[i];
+  }
+  VV_NAME(serl_venv_store_ctx_)(v, e, ctx);
+  for (int i = 0; i < 3; ++i) {
+    S_[(SERL_VF_ERR + i) * np + e] = err[i]; S_[(SERL_VF_LASTU + i) * np + e] = u[i]; S_[(SERL_VF_REF + i) * np + e] = rk[i];
+  }
+  for (int i = 0; i < 12; ++i) S_[(SERL_VF_XO + i) * np + e] = x[i];
+  S_[SERL_VF_V0 * np + e] = V0;
+  S_[SERL_VF_T * np + e] = t;
+  I[SERL_VI_K * np + e] = k;
+  I[SERL_VI_LIVE * np + e] = 1;
+  I[SERL_VI_COST * np + e] = cost;
+  au.run_return[e] = run_return; au.run_length[e] = run_length; au.cursor[e] = cur;
+}
+
+void VV_NAME(serl_launch_venv_rollout_general_)(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, const serl_venv_rollout_desc &rd,
+                                                int grid, hipStream_t stream)
+{
+  hipLaunchKernelGGL(VV_NAME(serl_venv_rollout_general_kernel_), dim3(grid), dim3(a.block), 0, stream, a, v, au, rd);
+}
+
 void VV_NAME(serl_launch_venv_rollout_)(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, const serl_venv_rollout_desc &rd, int grid,
                                         hipStream_t stream)
 {

@@ -32,6 +32,11 @@ env by the last explicit `reset` (the pool recycles after `ref_pool` episodes; a
 
     out = env.rollout(actor, 64, transitions=True)      # dict of step-major device tensors: obs [K + 1, N, S], actions, reward, done, ...
     replay.append_rows(out['transitions'].reshape(-1, 20))
+
+By default (`path='auto'`) that kernel takes the SERL50 actor on the attitude task (7 -> 32 .. -> 3) and every other shape is stepped
+one by one with a batched torch forward.  `path='fused'` also runs every other actor the C ABI packs -- hidden a multiple of 4 up to 128,
+up to 16 hidden layers, any activation -- on every env configuration in one launch (serl_venv_rollout_general, transition rows of
+2 S + A + 3 floats), or raises; `path='loop'` forces the step loop.
 """
 import ctypes
 import numpy as np
@@ -241,7 +246,9 @@ class CitationVecEnv:
         return self._obs, self._reward, self._done, {'x': self._x, 'ref': self._refk, 't': self._t, 'cost': self._cost}
 
     # ---- K policy-driven steps in one launch (serl_venv_rollout) ------------------------------------------------------------------
-    last_rollout_path = None      # 'fused' (serl_venv_rollout) or 'loop' (step by step with a torch forward) of the last rollout()
+    # 'fused' (serl_venv_rollout), 'fused-general' (serl_venv_rollout_general) or 'loop' (step by step with a torch forward) of the last rollout()
+    last_rollout_path = None
+    ROLLOUT_PATHS = ('auto', 'fused', 'loop')
 
     def fused_rollout_ok(self, spec):
         """True when rollout() runs `spec` actors inside the kernel: the attitude task without rate control and the lane actor's
@@ -249,8 +256,16 @@ class CitationVecEnv:
         return (self.env_config == 0 and not self.incremental and
                 (spec.state_dim, spec.hidden, spec.action_dim) == (7, 32, 3) and spec.num_layers >= 0)
 
-    def _check_rollout_args(self, policy, n_steps, spec, member_of_env, action_noise):
+    def fused_general_ok(self, spec):
+        """True when rollout(path='fused') can run `spec` actors inside the general kernel (serl_venv_rollout_general): every env
+        configuration; an actor that fits this env, hidden a multiple of 4 in 4 .. 128, 0 .. 16 hidden layers, any activation."""
+        return ((spec.state_dim, spec.action_dim) == (self.state_dim, self.action_dim) and
+                spec.hidden % 4 == 0 and 4 <= spec.hidden <= 128 and 0 <= spec.num_layers <= 16)
+
+    def _check_rollout_args(self, policy, n_steps, spec, member_of_env, action_noise, path='auto'):
         """The argument checks of rollout() that need no device work -> (K, list of actor modules or None, NetSpec)."""
+        if path not in self.ROLLOUT_PATHS:
+            raise ValueError("path: one of 'auto', 'fused', 'loop', not %r" % (path,))
         if not self.auto_reset:
             raise ValueError('rollout needs an env made with auto_reset=True')
         if isinstance(n_steps, bool) or int(n_steps) != n_steps or int(n_steps) < 1:
@@ -278,9 +293,12 @@ class CitationVecEnv:
             raise ValueError('member_of_env: i32 [%d], not %s' % (N, tuple(np.shape(member_of_env))))
         if action_noise is not None and tuple(np.shape(action_noise)) != (K, N, 3):
             raise ValueError('action_noise: f64 %s, not %s' % ((K, N, 3), tuple(np.shape(action_noise))))
+        if path == 'fused' and not (self.fused_rollout_ok(spec) or self.fused_general_ok(spec)):
+            raise ValueError("path='fused': no kernel runs a %d -> %d x %d -> %d actor (hidden: a multiple of 4 in 4 .. 128; 0 .. 16 "
+                             "hidden layers)" % (spec.state_dim, spec.hidden, spec.num_layers, spec.action_dim))
         return K, mods, spec
 
-    def rollout(self, policy, n_steps, *, member_of_env=None, action_noise=None, transitions=False, info=True, spec=None):
+    def rollout(self, policy, n_steps, *, member_of_env=None, action_noise=None, transitions=False, info=True, spec=None, path='auto'):
         """n_steps steps of every env under `policy`, restarts included, in ONE launch without host synchronisation
         (serl_venv_rollout: the actor runs inside the kernel, bit-identical to the fused rollout kernels' forward).  Needs auto_reset=True.
 
@@ -294,9 +312,13 @@ class CitationVecEnv:
         [K, N, 3], 't', 'cost' i32; transitions: 'transitions' f32 [K, N, 2 S + A + 3] = (obs, action, final_obs, reward, fin, cost),
         what DeviceReplay.append_rows takes after reshape(-1, 20) -- fin is the bounds / t_max flag, not the end of a reference table.
         Never-reset envs stay frozen (reward 0, done, action 0; their transition rows carry fin = 1: mask them out).
-        step() and rollout() share the env state and may be mixed.  Shapes the kernel does not take (fused_rollout_ok) are stepped one by
-        one with a batched torch forward to the same dictionary; `last_rollout_path` says 'fused' or 'loop'."""
-        K, mods, spec = self._check_rollout_args(policy, n_steps, spec, member_of_env, action_noise)
+        step() and rollout() share the env state and may be mixed.
+        path           'auto': the lane kernel where fused_rollout_ok(spec) (attitude task, 7 -> 32 .. -> 3), else one step() per step with
+                       a batched torch forward, to the same dictionary; 'fused': in a kernel or ValueError -- the lane kernel where
+                       fused_rollout_ok, else the general kernel (serl_venv_rollout_general: every env configuration, hidden a multiple
+                       of 4 up to 128, up to 16 hidden layers) where fused_general_ok; 'loop': always the step loop (A/B runs, tests).
+                       `last_rollout_path` says 'fused', 'fused-general' or 'loop'."""
+        K, mods, spec = self._check_rollout_args(policy, n_steps, spec, member_of_env, action_noise, path)
         N, S, A, dev = self.n_envs, self.state_dim, self.action_dim, self.device
         moe = None
         if member_of_env is not None:
@@ -304,7 +326,8 @@ class CitationVecEnv:
         noise = None
         if action_noise is not None:
             noise = torch.as_tensor(action_noise, dtype=torch.float64).to(dev).contiguous()
-        if not self.fused_rollout_ok(spec):
+        lane32 = self.fused_rollout_ok(spec)
+        if path == 'loop' or (path == 'auto' and not lane32):
             self.last_rollout_path = 'loop'
             return self._rollout_loop(policy, mods, spec, K, moe, noise, transitions, info)
         if mods is None:
@@ -328,10 +351,11 @@ class CitationVecEnv:
             rd.x, rd.ref, rd.t, rd.cost = (out[k].data_ptr() for k in ('x', 'ref', 't', 'cost'))
         if transitions:
             rd.transitions = out['transitions'].data_ptr()
-        _capi.check(self.lib.serl_venv_rollout(self.engine.ctx, ctypes.byref(self.desc), ctypes.byref(self.auto_desc), ctypes.byref(rd),
-                                               self._stream()), 'serl_venv_rollout')
+        entry = 'serl_venv_rollout' if lane32 else 'serl_venv_rollout_general'
+        _capi.check(getattr(self.lib, entry)(self.engine.ctx, ctypes.byref(self.desc), ctypes.byref(self.auto_desc), ctypes.byref(rd),
+                                             self._stream()), entry)
         del w, moe, noise      # (freed memory is handed out again only to work ordered behind this launch on the same stream)
-        self.last_rollout_path = 'fused'
+        self.last_rollout_path = 'fused' if lane32 else 'fused-general'
         return out
 
     def _rollout_buffers(self, K, transitions, info):

@@ -23,7 +23,12 @@ runs the auto-reset leg instead: CitationVecEnv(auto_reset=True) (serl_venv_step
 runs the rollout leg: `env.rollout(actor, K)` (serl_venv_rollout: the SERL50 actor inside the kernel, K steps per launch, fresh output
 tensors per call) against the loop it replaces, `obs, ... = env.step(actor(obs.float()))` on an auto_reset env with the same actor as a
 torch module on the same stream -- the same `staggered` and `idle` settings, medians and [min .. max] of `reps` repetitions of
---auto-steps env steps after a warm-up, the versions alternating."""
+--auto-steps env steps after a warm-up, the versions alternating.
+
+    python tools/bench_venv.py --rollout --hidden 72 [--layers 3] [--path fused] [--out profiles/venv_rollout_general_timing.json]
+runs the same leg for an actor of another shape (7 -> hidden x layers -> 3, tanh, seeded default initialisation) on the attitude task:
+`env.rollout(actor, K, path=<--path>)` (serl_venv_rollout_general for 'fused') against `env.rollout(actor, K, path='loop')`, the only
+path these shapes had before.  --hidden takes a comma-separated list; the results of all shapes go into one file."""
 import argparse, json, os, subprocess, sys
 import numpy as np
 import torch
@@ -158,21 +163,41 @@ def bench_auto(eng, N, steps, warmup, reps, drawn_steps, drawn_max_n):
     return out
 
 
-def bench_rollout(eng, N, steps, K, warmup, reps):
-    """One size: rollout(actor, K) against the step loop with the torch actor, episodes of 32 steps at spread phases and no env finishing."""
+def seeded_policy(device, hidden, layers):
+    """a 7 -> hidden x layers -> 3 tanh actor with torch's default initialisation under a fixed seed"""
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(1234)
+        a = serl_amd.Actor(argparse.Namespace(hidden_size=hidden, num_layers=layers, activation_actor='tanh', state_dim=7, action_dim=3,
+                                              device=torch.device('cpu')))
+    return a.to(device).eval()
+
+
+def bench_rollout(eng, N, steps, K, warmup, reps, hidden=None, layers=3, path='fused'):
+    """One size: rollout(actor, K) against the step loop with the torch actor, episodes of 32 steps at spread phases and no env finishing.
+    hidden: another actor shape -- rollout(path=path) against rollout(path='loop')."""
     dev = eng.device
     fixed = torch.zeros(N, 3, dtype=torch.float32, device=dev)
-    actor = serl50_policy(dev)
+    actor = serl50_policy(dev) if hidden is None else seeded_policy(dev, hidden, layers)
     L = 32
     table = np.ascontiguousarray(rs.tabulate(*rs.base_reference(20), 20)[:L])
     full = rs.tabulate(*rs.base_reference(20), 20)
     assert steps % K == 0 and warmup % K == 0 and steps + warmup < len(full)
     out = dict(N=N, steps=steps, K=K, reps=reps, warmup=warmup)
+    if hidden is not None:
+        out.update(hidden=hidden, layers=layers, path=path)
 
     def run(env, v, n):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        if v == 'rollout':
+        if hidden is not None:      # both versions through rollout(): the kernel (or whatever `path` picks) against the step loop
+            for _ in range(n // K):
+                o = env.rollout(actor, K, path=path if v == 'rollout' else 'loop')
+            if n:
+                out.setdefault('paths', {})[v] = env.last_rollout_path
+                done = o['done'][-1]
+            else:
+                done = torch.zeros(N, dtype=torch.bool, device=dev)
+        elif v == 'rollout':
             for _ in range(n // K):
                 o = env.rollout(actor, K)
             assert env.last_rollout_path == 'fused'
@@ -220,7 +245,8 @@ def kernel_report():
                 continue
             f = dict(p.strip().split(': ', 1) for p in line.split('\t') if ': ' in p)
             name = f['.name'].strip()
-            kind = 'rollout' if 'venv_rollout' in name else 'step_auto' if 'step_auto' in name else 'step' if 'step' in name else 'reset'
+            kind = ('rollout_general' if 'venv_rollout_general' in name else 'rollout' if 'venv_rollout' in name else 'step_auto' if 'step_auto' in name
+                    else 'step' if 'step' in name else 'reset')
             rep['%s_%s' % (kind, v)] = dict(vgpr=int(f['.vgpr_count']), vgpr_spill=int(f['.vgpr_spill_count']), sgpr_spill=int(f['.sgpr_spill_count']),
                                             lds_bytes=int(f['.group_segment_fixed_size']), scratch_bytes=int(f['.private_segment_fixed_size']))
     return rep
@@ -239,15 +265,23 @@ def main():
     ap.add_argument('--drawn-max-n', type=int, default=8192, help='largest N of the drawn comparison')
     ap.add_argument('--rollout', action='store_true', help='the rollout leg instead of the others')
     ap.add_argument('--rollout-k', type=int, default=50, help='steps per rollout() call')
-    ap.add_argument('--out', default=None, help='default: profiles/venv_auto_timing.json (--auto-reset), profiles/venv_rollout_timing.json (--rollout)')
+    ap.add_argument('--hidden', default=None, help='--rollout: hidden size(s) of another actor shape, e.g. 72,96 (default: the SERL50 actor, hidden 32)')
+    ap.add_argument('--layers', type=int, default=3, help='--rollout --hidden: hidden layers')
+    ap.add_argument('--path', default='fused', choices=['auto', 'fused', 'loop'], help="--rollout --hidden: rollout(path=...) of the version compared with 'loop'")
+    ap.add_argument('--out', default=None, help='default: profiles/venv_auto_timing.json (--auto-reset), profiles/venv_rollout_timing.json (--rollout), '
+                                                'profiles/venv_rollout_general_timing.json (--rollout --hidden)')
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, 'profiles', 'venv_rollout_timing.json' if args.rollout else 'venv_auto_timing.json')
+        args.out = os.path.join(ROOT, 'profiles', ('venv_rollout_general_timing.json' if args.hidden else 'venv_rollout_timing.json') if args.rollout
+                                else 'venv_auto_timing.json')
     eng = serl_amd.RolloutEngine(0)
     if args.rollout:
         sizes = [int(s) for s in (args.sizes if args.sizes != ap.get_default('sizes') else '1024,65536').split(',')]
         res = dict(tool='bench_venv --rollout', device=torch.cuda.get_device_name(0), source_hash=hip_build.source_hash(),
-                   results=[bench_rollout(eng, N, args.auto_steps, args.rollout_k, args.warmup, args.reps) for N in sizes])
+                   results=[bench_rollout(eng, N, args.auto_steps, args.rollout_k, args.warmup, args.reps, H, args.layers, args.path)
+                            for H in ([int(h) for h in args.hidden.split(',')] if args.hidden else [None]) for N in sizes])
+        if args.hidden:
+            res['tool'] += ' --hidden %s --layers %d --path %s' % (args.hidden, args.layers, args.path)
         kernels = kernel_report()      # (needs the build's objects: empty where only the library was shipped)
         if kernels:
             res['kernels'] = kernels
