@@ -74,7 +74,13 @@ typedef struct serl_fault_row {
  *   ref = (pi/180) * [v_theta + (0 <= t <= t_max ? trim_deg : 0),  v_phi,  0]
  * cos(pi s) is evaluated with + - * only (det_cospi: reflection to [0, 1/4], Taylor polynomials of cos / sin through
  * x^20 / x^21 in Horner form) so that the kernels and the CPU oracle agree bit for bit; against a libm cosine the
- * reference value differs by <= 2 ulp.  Per env step this replaces the 24 B read of ref[k] by arithmetic. */
+ * reference value differs by <= 2 ulp.  Per env step this replaces the 24 B read of ref[k] by arithmetic.
+ * Contract of a row (the library does not read rows on the host; serl_amd.refsignals.check_specs enforces it for the Python callers):
+ *   0 <= n_theta, n_phi <= SERL_REF_MAX_STEPS;  w_theta, w_phi finite and > 0 (at w = 0 the formula above is 0 / 0 on the step, where
+ *   the kernels' `s < 1 ? s : 1` gives the level);  t_*[0 .. n) finite and NON-DECREASING (ties are legal: the last of tied steps is
+ *   `i`, and prev is the amplitude of the step hit before it -- for non-decreasing times that is amps[i-1], as written above; for
+ *   decreasing times it is not, and `signals` would blend from another level);  a_*[0 .. n) and trim_deg finite.
+ *   Entries [n .. SERL_REF_MAX_STEPS) of the four arrays are NOT USED: they may hold anything, NaN included. */
 #define SERL_REF_MAX_STEPS 8
 typedef struct serl_ref_spec {
   int32_t n_theta, n_phi;            /* number of steps of each channel, <= SERL_REF_MAX_STEPS */

@@ -118,6 +118,7 @@ class RolloutEngine:
         spec_t = None
         if isinstance(ref, np.ndarray) and ref.dtype.names:     # refsignals.ref_specs rows: generated in the kernel
             assert ref.dtype == refsignals.REF_SPEC_DTYPE and len(ref) in (1, E)
+            refsignals.check_specs(ref)      # (widths > 0, non-decreasing times: before any device work)
             spec_t = torch.from_numpy(np.ascontiguousarray(ref).view(np.uint8).reshape(len(ref), -1)).to(dev)
             ref_t, shared, T = None, True, refsignals.n_steps_for(t_max)
         else:

@@ -25,7 +25,12 @@ def n_steps_for(t_max, dt=0.01):
 
 class SmoothedStepSequence:
     """Levels `amplitudes[i]` starting at `times[i]`, blended from the previous level (0 before the
-    first) along 0.5*(1-cos(pi*(t-t_i)/w)) over [t_i, t_i+w]."""
+    first) along 0.5*(1-cos(pi*(t-t_i)/w)) over [t_i, t_i+w].
+    This literal form and the kernels' generator (serl_ref_spec) agree for widths > 0 and non-decreasing times, which is
+    all `training_references`, `gen_refs` and `base_reference` produce.  Outside that they differ: with width 0 this form
+    gives NaN (0 / 0) at a sample that coincides with a step where the kernel gives the level, and with decreasing times
+    `prev` here is the amplitude of the step listed before, hit or not, where the kernel takes the one it hit last.
+    `ref_specs` / `check_specs` refuse both, so no such sequence reaches a kernel."""
 
     def __init__(self, times, amplitudes, smooth_width):
         self.times = np.asarray(times, dtype=np.float64)
@@ -141,9 +146,46 @@ REF_SPEC_DTYPE = np.dtype([('n_theta', np.int32), ('n_phi', np.int32), ('w_theta
 assert REF_SPEC_DTYPE.itemsize == 8 + 3 * 8 + 4 * 8 * REF_MAX_STEPS
 
 
+def check_specs(rows):
+    """The contract of serl_ref_spec rows (include/serl_amd.h), checked on the host before a row reaches a kernel: 0 .. 8 steps
+    per channel; widths finite and > 0 (the literal formula divides 0 by 0 at width 0); within the first n entries finite times
+    that do not decrease (ties are legal: the last of them wins) and finite amplitudes; a finite trim.  Entries past n are not read
+    by the generator and not checked.  Raises ValueError naming the field; -> rows."""
+    rows = np.asarray(rows)
+    if rows.dtype != REF_SPEC_DTYPE:
+        raise ValueError('serl_ref_spec rows: a structured array of refsignals.REF_SPEC_DTYPE, not %s' % (rows.dtype,))
+    r = rows.reshape(-1)
+
+    def first(bad):
+        return int(np.argmax(bad.reshape(len(r), -1).any(axis=1)))
+    bad = ~np.isfinite(r['trim_deg'])
+    if bad.any():
+        raise ValueError('trim_deg: row %d is not finite (%r)' % (first(bad), r['trim_deg'][first(bad)]))
+    col = np.arange(REF_MAX_STEPS)[None, :]
+    for nk, wk, tk, ak in (('n_theta', 'w_theta', 't_theta', 'a_theta'), ('n_phi', 'w_phi', 't_phi', 'a_phi')):
+        n, w, t, a = r[nk], r[wk], r[tk], r[ak]
+        bad = (n < 0) | (n > REF_MAX_STEPS)
+        if bad.any():
+            raise ValueError('%s: row %d has %d steps, outside 0 .. %d' % (nk, first(bad), n[first(bad)], REF_MAX_STEPS))
+        bad = ~(np.isfinite(w) & (w > 0.0))
+        if bad.any():
+            raise ValueError('%s: row %d has width %r; a smooth width must be finite and > 0' % (wk, first(bad), w[first(bad)]))
+        used = col < n[:, None]
+        for k, v in ((tk, t), (ak, a)):
+            bad = used & ~np.isfinite(v)
+            if bad.any():
+                raise ValueError('%s: row %d has a non-finite entry within its first %d' % (k, first(bad), n[first(bad)]))
+        bad = used[:, 1:] & (t[:, 1:] < t[:, :-1])
+        if bad.any():
+            raise ValueError('%s: row %d has decreasing step times %s; times must not decrease (ties are legal)'
+                             % (tk, first(bad), t[first(bad)][:n[first(bad)]]))
+    return rows
+
+
 def ref_specs(theta, phi, theta_trim_deg=0.22):
     """Sequences of SmoothedStepSequence objects (one pair per episode) -> structured array [E] of serl_ref_spec rows.
-    The kernel evaluates them at the env's accumulated step times instead of reading a [T, 3] table per episode."""
+    The kernel evaluates them at the env's accumulated step times instead of reading a [T, 3] table per episode.
+    Refuses what the rows' contract excludes (check_specs): more than 8 steps, a width <= 0 or not finite, decreasing times."""
     theta, phi = list(theta), list(phi)
     assert len(theta) == len(phi)
     out = np.zeros(len(theta), dtype=REF_SPEC_DTYPE)
@@ -156,7 +198,7 @@ def ref_specs(theta, phi, theta_trim_deg=0.22):
             out[e][nk], out[e][wk] = n, sig.w
             out[e][tk][:n], out[e][ak][:n] = sig.times, sig.amps
         out[e]['trim_deg'] = trims[e]
-    return out
+    return check_specs(out)
 
 
 def det_cospi(s):
@@ -180,8 +222,8 @@ def det_cospi(s):
 
 
 def tabulate_specs(specs, t_max, dt=0.01):
-    """The table the kernel's generator produces for `specs` (same operations, vectorised on the host): f64 [E, T, 3].
-    Differs from `tabulate` (libm cosine, the reference's own arithmetic) by at most a few ulp."""
+    """The table the kernel's generator produces for `specs` (same operations, vectorised on the host, the clamp `s < 1 ? s : 1`
+    included): f64 [E, T, 3].  Differs from `tabulate` (libm cosine, the reference's own arithmetic) by at most a few ulp."""
     n = n_steps_for(t_max, dt)
     t = env_times(n, dt)
     out = np.zeros((len(specs), n, 3))
@@ -193,7 +235,8 @@ def tabulate_specs(specs, t_max, dt=0.01):
                 hit = t >= r[tk][i]
                 prev = np.where(hit, np.where(on, a, 0.0), prev)
                 ti = np.where(hit, r[tk][i], ti); a = np.where(hit, r[ak][i], a); on = on | hit
-            s = np.minimum((t - ti) / r[wk], 1.0)
+            s = (t - ti) / r[wk]
+            s = np.where(s < 1.0, s, 1.0)
             v = np.where(on, prev + (a - prev) * (1.0 - det_cospi(np.where(on, s, 0.0))) / 2.0, 0.0)
             if c == 0:
                 v = v + np.where((0.0 <= t) & (t <= t_max), r['trim_deg'], 0.0)

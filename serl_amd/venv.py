@@ -54,7 +54,7 @@ class CitationVecEnv:
     refs          None: every reset draws a fresh training reference per env, as CitationEnv.reset() does without user_refs
                   (refsignals.training_references, the draws make_evaluate makes), generated in the kernel (serl_ref_spec rows);
                   or a f64 table [N, T, 3] / [T, 3] (radians, rows at the env's accumulated step times: T bounds the episode), or
-                  refsignals.ref_specs rows [N] / [1].  Given references stay until `reset(refs=...)` replaces those of the reset envs.
+                  refsignals.ref_specs rows [N] / [1] (hand-made rows must satisfy refsignals.check_specs).  Given references stay until `reset(refs=...)` replaces those of the reset envs.
     sensor_noise  None: the modes with a sensor model ('noise', 'gust') draw builds.sensor_noise_table per env at every reset;
                   False: none; or f64 [N, T + 1, 7] (entry 0 belongs to the step of reset(), entry k + 1 to env step k).
     engine        the RolloutEngine whose HIP context holds the build tables (default: the process's engine).
@@ -66,6 +66,8 @@ class CitationVecEnv:
 
     def __init__(self, n_envs, mode='PHlab_attitude_nominal', t_max=20, refs=None, sensor_noise=None, engine=None, auto_reset=False,
                  ref_pool=4):
+        if isinstance(refs, np.ndarray) and refs.dtype.names:
+            refsignals.check_specs(refs)      # (widths > 0, non-decreasing times: before any device work)
         if not torch.cuda.is_available():
             raise RuntimeError('serl_amd.CitationVecEnv needs a ROCm GPU (torch.cuda.is_available() is False); '
                                'the product has no CPU path')
@@ -169,6 +171,8 @@ class CitationVecEnv:
         draws their ref_pool references (env-major), or `refs` rows become their pool row 0 -- rows 1 .. ref_pool - 1 keep what they
         held (the previous draw; zero references, i.e. trim only, if no drawing reset came before), and the restarts fly them."""
         N, dev = self.n_envs, self.device
+        if isinstance(refs, np.ndarray) and refs.dtype.names:
+            refsignals.check_specs(refs)      # (before any device work)
         m = None
         if mask is not None:
             m = torch.as_tensor(mask, device=dev)
