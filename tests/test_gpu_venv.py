@@ -144,10 +144,10 @@ def test_replay_of_oracle_episodes_configurations(engine, golden, case, name, re
     _replay(env, o, S, A)
 
 
-# ---- 3. f64 actions (outside [-1, 1] too) against the open-loop dynamics and the env glue restated here -------------------------------
+# ---- 3. f64 actions (outside [-1, 1] too) against the open-loop dynamics and the env glue restated in tests/env_glue.py ----------------
 @pytest.mark.parametrize('mode', ['PHlab_attitude_nominal', 'PHlab_attitude_incremental'])
 def test_f64_actions_against_the_dynamics(engine, mode):
-    from oracle.dynamics import CitationDynamics
+    import env_glue as G
     from serl_amd import refsignals as rs
     N, t_max = 6, 3.0
     T = rs.n_steps_for(t_max)
@@ -163,47 +163,20 @@ def test_f64_actions_against_the_dynamics(engine, mode):
         obs, rew, done, info = env.step(torch.from_numpy(acts[k]).to(env.device))
         out.append([obs.cpu().numpy(), rew.cpu().numpy(), done.cpu().numpy(), info['x'].cpu().numpy(), info['t'].cpu().numpy(),
                     info['cost'].cpu().numpy()])
-    PI = 3.14159265358979323846
-    d2r, r2d = PI / 180.0, 180.0 / PI
-    bound = (25.0 if incr else 10.0) * d2r
-    lo, hi = -bound, bound
-    scaler = [6.0 / PI * 1.0, 6.0 / PI * 1.0, 6.0 / PI * 4.0]
-    max_theta, max_phi, dt = 60.0 * d2r, 75.0 * d2r, 0.01
     for e in range(N):
-        dyn = CitationDynamics('h2000_v90', short_libm=True)
-        x = dyn.step(np.zeros(10))
-        V0, err, u, t = x[3], np.zeros(3), np.zeros(3), 0.0
-
-        def ob(x):
-            o = [err[0], err[1], err[2], x[0], x[1], x[2], x[4]]
-            return np.array(o + (list(u) if incr else []))
-        np.testing.assert_array_equal(obs0[e], ob(x))
+        py = G.GlueEnv('h2000_v90', G.ATTITUDE, incr, None, refs[e], None, t_max)      # the literal Python env (tests/env_glue.py)
+        np.testing.assert_array_equal(obs0[e], np.array(py.reset()))
         n = None
         for k in range(T + 3):
             o_, r_, d_, x_, t_, c_ = (v[e] for v in out[k])
             if n is not None:       # frozen
-                assert d_ and r_ == 0.0 and t_ == t
+                assert d_ and r_ == 0.0 and t_ == py.t
                 continue
-            a = acts[k, e]
-            scl = lo + 0.5 * (a + 1.0) * (hi - lo)
-            u = u + scl * dt if incr else scl
-            cmd = np.zeros(10); cmd[:3] = u
-            x = dyn.step(cmd)
-            rk = refs[e, k]
-            err = np.array([rk[0] - x[7], rk[1] - x[6], rk[2] - x[5]])
-            rsum = 0.0
-            for i in range(3):
-                rsum = rsum + abs(min(max(scaler[i] * err[i], -1.0), 1.0))
-            reward = -rsum / 3.0
-            cost = int(r2d * abs(x[4]) > 11.0 or r2d * abs(x[6]) > 0.75 * max_phi or x[3] < V0 / 3.0)
-            fin = t >= t_max or abs(x[7]) > max_theta or abs(x[6]) > max_phi or x[9] < 50.0
-            if fin:
-                reward += -1.0 / dt * (t_max - t) * 2.0
-            t += dt
-            np.testing.assert_array_equal(x_, x, err_msg='env %d step %d' % (e, k))
-            np.testing.assert_array_equal(o_, ob(x), err_msg='env %d step %d' % (e, k))
-            assert r_ == reward and c_ == cost and t_ == t, (e, k, r_, reward)
-            assert bool(d_) == (fin or k + 1 >= T), (e, k)
+            r = py.step(np.asarray(acts[k, e], dtype=np.float64))
+            np.testing.assert_array_equal(x_, np.array(r['x']), err_msg='env %d step %d' % (e, k))
+            np.testing.assert_array_equal(o_, np.array(r['obs']), err_msg='env %d step %d' % (e, k))
+            assert r_ == r['reward'] and c_ == r['cost'] and t_ == r['t'], (e, k, r_, r['reward'])
+            assert bool(d_) == (r['fin'] or k + 1 >= T), (e, k)
             if d_:
                 n = k + 1
         assert n is not None
