@@ -393,6 +393,66 @@ int serl_venv_rollout(serl_ctx *ctx, const serl_venv_desc *desc, const serl_venv
 int serl_venv_rollout_general(serl_ctx *ctx, const serl_venv_desc *desc, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *ro,
                               void *stream);
 
+/* ---- sensor and exploration noise drawn inside the env kernels (SERL_ABI_VERSION stays 9: nothing above has moved; this descriptor has
+ * a layout self-check of its own, serl_venv_noise_layout) --------------------------------------------------------------------------------
+ * A counter-based generator (csrc/serl_rng.h) replaces the pre-drawn tables: no table, no host draw, a fresh and reproducible realisation
+ * per (seed, env, episode, step), and any single episode's noise can be written out again on demand (serl_venv_noise_fill).
+ *   bits     Philox4x32-10, key = seed (low word, high word), counter = (env index, episode ordinal of that env, entry within the episode,
+ *            stream << 16 | block); stream 0 = sensor, 1 = action
+ *   uniform  from two words: k = (uint64)w0 << 20 | w1 >> 12, u = (2 k + 1) 2^-53 -- exact in f64, strictly inside (0, 1)
+ *   normal   one Philox call = two uniforms = one Box-Muller pair: r = sqrt(-2 log u0), (s, c) = sincospi(2 u1), normals r c and r s
+ *   sensor   blocks 0 .. 3 = 8 normals, the first 7 in channel order p q r | alpha | beta | phi theta; the addend of channel i is
+ *            sensor_bias[i] + sensor_scale[i] z (multiply, then add).  Entry 0 belongs to the step of the reset, entry k + 1 to env step k:
+ *            where the table path reads its row
+ *   action   blocks 0 .. 1 = 4 normals, the first action_dim are used; the addend is clip(action_sd z, -action_clip, action_clip)
+ *            (base/core/agent.py:90-93).  The entry is the env's in-episode step index, so two rollouts of K1 and K2 steps draw what one of
+ *            K1 + K2 steps draws
+ *   episode  episode_count[e] counts the episode starts of env e, explicit resets and in-kernel restarts alike; the running episode's
+ *            ordinal is episode_count[e] - 1.  The caller owns the array (zeroed for fresh envs) and may save / restore it with the seed. */
+typedef struct serl_venv_noise_desc {
+  uint64_t seed;
+  int32_t *episode_count;           /* DEVICE in / out [n_envs] */
+  int32_t sensor;                   /* 1 = sensor noise from the generator (desc->sensor_noise must then be NULL); 0 = as desc says */
+  int32_t pad0;
+  double sensor_bias[7];
+  double sensor_scale[7];
+  int32_t action;                   /* 1 = exploration noise from the generator (ro->action_noise must then be NULL); 0 = as ro says */
+  int32_t pad1;
+  double action_sd;                 /* >= 0 */
+  double action_clip;               /* >= 0 */
+} serl_venv_noise_desc;
+/* layout self-check: sizeof(serl_venv_noise_desc), then offsetof of each member in declaration order */
+int serl_venv_noise_layout(int32_t *out, int32_t capacity);
+/* serl_venv_reset / _step_auto / _rollout / _rollout_general with `nz` (required): one launch each of a second instantiation of the same
+ * kernels.  Besides what their namesakes refuse, SERL_E_INVALID before any launch for a NULL nz or episode_count, desc->sensor_noise
+ * together with nz->sensor, ro->action_noise together with nz->action, action_sd < 0 or action_clip < 0 (or NaN).  With nz->sensor = 0
+ * and nz->action = 0 they compute what their namesakes compute (and still count episodes).  There is no serl_venv_step with `nz`. */
+int serl_venv_reset_noise(serl_ctx *ctx, const serl_venv_desc *desc, const uint8_t *mask, double *obs, const serl_venv_noise_desc *nz,
+                          void *stream);
+int serl_venv_step_auto_noise(serl_ctx *ctx, const serl_venv_desc *desc, const void *actions, int32_t actions_f64, double *obs,
+                              double *reward, uint8_t *done, double *x, double *ref, double *t, int32_t *cost,
+                              const serl_venv_auto_desc *au, const serl_venv_noise_desc *nz, void *stream);
+int serl_venv_rollout_noise(serl_ctx *ctx, const serl_venv_desc *desc, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *ro,
+                            const serl_venv_noise_desc *nz, void *stream);
+int serl_venv_rollout_general_noise(serl_ctx *ctx, const serl_venv_desc *desc, const serl_venv_auto_desc *au,
+                                    const serl_venv_rollout_desc *ro, const serl_venv_noise_desc *nz, void *stream);
+/* What the env kernels draw, written out by the same device functions: row i of `out` holds `entries` consecutive entries, entry0[i]
+ * onwards, of (nz->seed; env[i], episode[i]).  env / episode / entry0: DEVICE i32 [rows]; out: DEVICE [rows][entries][W];
+ * nz->episode_count is not read.  mode 0: the raw Philox words of the sensor stream's four blocks followed by the action stream's two,
+ * u32, W = 24;  1: the sensor stream's standard normals, f64, W = 7;  2: the sensor addends, f64, W = 7;  3: the action addends,
+ * f64, W = 3.  SERL_E_INVALID for a NULL argument, rows or entries < 1, an unknown mode, action_sd / action_clip < 0 in mode 3. */
+int serl_venv_noise_fill(serl_ctx *ctx, const serl_venv_noise_desc *nz, int32_t mode, int32_t rows, const int32_t *env,
+                         const int32_t *episode, const int32_t *entry0, int32_t entries, void *out, void *stream);
+/* The in-kernel actor of serl_venv_rollout / _rollout_general alone, one lane per env: actions f32 [n_envs][action_dim] = the forward pass of
+ * the env's member (member_of_env modulo n_members, NULL = member 0) on obsf[i] = (float)obs[i], obs f64 [n_envs][state_dim] -- the bits those
+ * kernels compute (hidden 32, state_dim 7, action_dim 3 runs serl_venv_rollout's forward, every other shape the general one).  Of `ro` only the actor
+ * members are read (state_dim .. member_of_env); refusals as serl_venv_rollout_general's for them, and n_envs < 1.  The step loop of a device-noise
+ * env uses it, so that it stays interchangeable with the kernels bit for bit. */
+int serl_venv_actor_forward(serl_ctx *ctx, const serl_venv_rollout_desc *ro, int32_t n_envs, const double *obs, float *actions, void *stream);
+/* the generator's bit-level parts on the host, compiled from the kernels' text (csrc/serl_rng.h) */
+void serl_host_philox(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t out4[4]);
+double serl_host_uniform(uint32_t w0, uint32_t w1);
+
 /* Development aid: with SERL_PROFILE=1 in the environment serl_rollout records shader-clock cycles of wave 0 of
  * workgroup 0: out[0..3] = {actor forward, dynamics step, env bookkeeping, env steps}; out[4..31] = phase
  * counters of the model evaluation (non-zero only in builds compiled with -DCITW_PROFILE). */

@@ -26,11 +26,11 @@ from .evaluator import RolloutEngine, evaluate_pop, validate_pop, make_evaluate,
 from .generation import evaluate_generation, validate_actor, GenerationResult
 from .replay import DeviceReplay
 from .ssne import SSNE
-from .venv import CitationVecEnv
+from .venv import CitationVecEnv, venv_noise
 from .td3 import TD3, Critic
 from .actor import pack_critic, unpack_critic
 from . import refsignals, metrics, ga, distributed, builds, replay, ssne, td3
 
 __all__ = ['Actor', 'GeneticAgent', 'pack_actor', 'pack_population', 'NetSpec', 'Episode', 'RolloutEngine',
            'evaluate_pop', 'validate_pop', 'make_evaluate', 'PopResult', 'evaluate_generation', 'validate_actor',
-           'GenerationResult', 'DeviceReplay', 'SSNE', 'CitationVecEnv', 'TD3', 'Critic', 'pack_critic', 'unpack_critic', 'td3', 'replay', 'ssne', 'refsignals', 'metrics', 'ga', 'distributed', 'builds']
+           'GenerationResult', 'DeviceReplay', 'SSNE', 'CitationVecEnv', 'venv_noise', 'TD3', 'Critic', 'pack_critic', 'unpack_critic', 'td3', 'replay', 'ssne', 'refsignals', 'metrics', 'ga', 'distributed', 'builds']

@@ -15,7 +15,9 @@ EXPORTS = ['serl_abi_version', 'serl_last_error', 'serl_param_count', 'serl_ctx_
            'serl_smoothness', 'serl_smoothness_work_size', 'serl_ga_distill', 'serl_host_sample_slots',
            'serl_venv_state_bytes', 'serl_venv_reset', 'serl_venv_step', 'serl_venv_step_auto', 'serl_venv_auto_layout',
            'serl_venv_rollout', 'serl_venv_rollout_layout', 'serl_venv_rollout_general',
-           'serl_td3_train', 'serl_td3_work_bytes', 'serl_td3_param_count', 'serl_td3_layout']
+           'serl_td3_train', 'serl_td3_work_bytes', 'serl_td3_param_count', 'serl_td3_layout',
+           'serl_venv_noise_layout', 'serl_venv_reset_noise', 'serl_venv_step_auto_noise', 'serl_venv_rollout_noise',
+           'serl_venv_rollout_general_noise', 'serl_venv_noise_fill', 'serl_venv_actor_forward', 'serl_host_philox', 'serl_host_uniform']
 
 
 class BuildDesc(ctypes.Structure):
@@ -84,6 +86,18 @@ class VenvRolloutDesc(ctypes.Structure):
 def expected_venv_rollout_layout():
     """What serl_venv_rollout_layout() must return for VenvRolloutDesc to be right."""
     return [ctypes.sizeof(VenvRolloutDesc)] + [getattr(VenvRolloutDesc, n).offset for n, _ in VenvRolloutDesc._fields_]
+
+
+class VenvNoiseDesc(ctypes.Structure):
+    """serl_venv_noise_desc: sensor / exploration noise drawn inside the env kernels (checked against the library by serl_venv_noise_layout)"""
+    _fields_ = [('seed', ctypes.c_uint64), ('episode_count', VP), ('sensor', ctypes.c_int32), ('pad0', ctypes.c_int32),
+                ('sensor_bias', ctypes.c_double * 7), ('sensor_scale', ctypes.c_double * 7), ('action', ctypes.c_int32), ('pad1', ctypes.c_int32),
+                ('action_sd', ctypes.c_double), ('action_clip', ctypes.c_double)]
+
+
+def expected_venv_noise_layout():
+    """What serl_venv_noise_layout() must return for VenvNoiseDesc to be right."""
+    return [ctypes.sizeof(VenvNoiseDesc)] + [getattr(VenvNoiseDesc, n).offset for n, _ in VenvNoiseDesc._fields_]
 
 
 class Td3Desc(ctypes.Structure):
@@ -171,11 +185,25 @@ def lib():
     L.serl_venv_rollout_layout.argtypes = [VP, ctypes.c_int32]
     L.serl_venv_rollout_general.argtypes = L.serl_venv_rollout.argtypes
     L.serl_td3_train.argtypes = [VP, ctypes.POINTER(Td3Desc), VP]
+    NZ = ctypes.POINTER(VenvNoiseDesc)
+    L.serl_venv_noise_layout.argtypes = [VP, ctypes.c_int32]
+    L.serl_venv_reset_noise.argtypes = [VP, ctypes.POINTER(VenvDesc), VP, VP, NZ, VP]
+    L.serl_venv_step_auto_noise.argtypes = [VP, ctypes.POINTER(VenvDesc), VP, i32, VP, VP, VP, VP, VP, VP, VP, ctypes.POINTER(VenvAutoDesc), NZ, VP]
+    L.serl_venv_rollout_noise.argtypes = [VP, ctypes.POINTER(VenvDesc), ctypes.POINTER(VenvAutoDesc), ctypes.POINTER(VenvRolloutDesc), NZ, VP]
+    L.serl_venv_rollout_general_noise.argtypes = L.serl_venv_rollout_noise.argtypes
+    L.serl_venv_noise_fill.argtypes = [VP, NZ, i32, i32, VP, VP, VP, i32, VP, VP]
+    L.serl_venv_actor_forward.argtypes = [VP, ctypes.POINTER(VenvRolloutDesc), i32, VP, VP, VP]
+    L.serl_host_philox.argtypes = [ctypes.c_uint64] + [ctypes.c_uint32] * 4 + [ctypes.POINTER(ctypes.c_uint32)]
+    L.serl_host_uniform.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
     L.serl_td3_work_bytes.argtypes = [i32] * 6
     L.serl_td3_param_count.argtypes = [ctypes.c_int, ctypes.c_int]
     L.serl_td3_layout.argtypes = [VP, ctypes.c_int32]
     for f in EXPORTS:
-        if f not in ('serl_last_error',):
+        if f == 'serl_host_uniform':
+            L.serl_host_uniform.restype = ctypes.c_double
+        elif f == 'serl_host_philox':
+            L.serl_host_philox.restype = None
+        elif f not in ('serl_last_error',):
             getattr(L, f).restype = ctypes.c_longlong if f in ('serl_host_sample_slots', 'serl_venv_state_bytes', 'serl_td3_work_bytes') else ctypes.c_int
     if L.serl_abi_version() != ABI_VERSION:
         raise RuntimeError('serl_amd: ABI version mismatch (library %d, binding %d): rebuild with `python serl_amd/build.py`'
@@ -203,6 +231,12 @@ def lib():
     n = L.serl_venv_rollout_layout(got, len(want))
     if n != len(want) or list(got) != want:
         raise RuntimeError('serl_amd: layout of the VenvRolloutDesc mirror differs from the library (serl_venv_rollout_layout): library %s, binding %s'
+                           % (list(got)[:n], want))
+    want = expected_venv_noise_layout()
+    got = (ctypes.c_int32 * len(want))()
+    n = L.serl_venv_noise_layout(got, len(want))
+    if n != len(want) or list(got) != want:
+        raise RuntimeError('serl_amd: layout of the VenvNoiseDesc mirror differs from the library (serl_venv_noise_layout): library %s, binding %s'
                            % (list(got)[:n], want))
     _lib = L
     return L

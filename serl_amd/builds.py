@@ -111,6 +111,14 @@ def sensor_terms(z):
     return t
 
 
+def sensor_bias_scale():
+    """(bias [7], scale [7]) with sensor_terms(z) == bias + scale * z bit for bit: the literal sub-expressions of sensor_terms, evaluated as it
+    evaluates them (channel alpha has no bias term: 0.0 + s z == s z).  What serl_venv_noise_desc.sensor_bias / sensor_scale take."""
+    bias = np.array([3.0 * 10**(-5)] * 3 + [0.0, 1.8 * 10**(-3)] + [4.0 * 10**(-3)] * 2, np.float64)
+    scale = np.array([6.3 * 10**(-4)] * 3 + [4.0 * 10**(-10), 2.7 * 10**(-4)] + [3.2 * 10**(-5)] * 2, np.float64)
+    return bias, scale
+
+
 def draw_episode_noise(n_steps, action, sensor, rng=np.random, n_actions=3):
     """The np.random draws of ONE sequential reference episode, pre-drawn in the reference's interleaved order:
     reset() -> step(): sensor model 7 draws (if the mode has one); then per env step: exploration noise randn(n_actions)

@@ -5,6 +5,9 @@
 #include "citation_dev.h"
 #include "rollout_device.h"
 #include "serl_variant.h"
+#ifdef SERL_VENV_NOISE
+#include "serl_rng.h"
+#endif
 #define CIT_V(x) SERL_PASTE(SERL_PASTE(cit_, VARIANT), x)      // cit_<variant>x: the names gen/citation_<variant>_lane.inc defines
 #define CIT_RO_LO_W CIT_V(_RO_LO_W)
 #define CIT_RO_HI_W CIT_V(_RO_HI_W)
@@ -46,6 +49,13 @@ static_assert(8 * (CIT_RO_LDS_WORDS + CIT_V(_NSLOPE)) <= 160 * 1024, "tables + i
 }  // namespace bdag
 
 #define SERL_V(x) SERL_PASTE(x, VARIANT)
+#ifdef SERL_VENV_NOISE      // family_lanenz.hip: the env kernels with the in-kernel noise generator, nothing else
+#define SERL_VNZ(x) SERL_PASTE(SERL_PASTE(x, noise_), VARIANT)
+void SERL_VNZ(serl_launch_venv_reset_)(const RolloutArgs &a, const VenvArgs &v, const serl_venv_noise_desc &nz, int grid, hipStream_t stream) { bdag::SERL_VNZ(serl_launch_venv_reset_)(a, v, nz, grid, stream); }
+void SERL_VNZ(serl_launch_venv_step_auto_)(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, const serl_venv_noise_desc &nz, int grid, hipStream_t stream) { bdag::SERL_VNZ(serl_launch_venv_step_auto_)(a, v, au, nz, grid, stream); }
+void SERL_VNZ(serl_launch_venv_rollout_)(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, const serl_venv_rollout_desc &rd, const serl_venv_noise_desc &nz, int grid, hipStream_t stream) { bdag::SERL_VNZ(serl_launch_venv_rollout_)(a, v, au, rd, nz, grid, stream); }
+void SERL_VNZ(serl_launch_venv_rollout_general_)(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, const serl_venv_rollout_desc &rd, const serl_venv_noise_desc &nz, int grid, hipStream_t stream) { bdag::SERL_VNZ(serl_launch_venv_rollout_general_)(a, v, au, rd, nz, grid, stream); }
+#else
 void SERL_V(serl_launch_rollout_)(const RolloutArgs &a, int grid, hipStream_t stream) { bdag::SERL_V(serl_launch_rollout_)(a, grid, stream); }
 
 void SERL_V(serl_launch_dyn_)(const RolloutArgs &a, const double *cmds, double *states, int T, int grid, hipStream_t stream)
@@ -58,3 +68,4 @@ void SERL_V(serl_launch_venv_step_)(const RolloutArgs &a, const VenvArgs &v, int
 void SERL_V(serl_launch_venv_step_auto_)(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, int grid, hipStream_t stream) { bdag::SERL_V(serl_launch_venv_step_auto_)(a, v, au, grid, stream); }
 void SERL_V(serl_launch_venv_rollout_)(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, const serl_venv_rollout_desc &rd, int grid, hipStream_t stream) { bdag::SERL_V(serl_launch_venv_rollout_)(a, v, au, rd, grid, stream); }
 void SERL_V(serl_launch_venv_rollout_general_)(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, const serl_venv_rollout_desc &rd, int grid, hipStream_t stream) { bdag::SERL_V(serl_launch_venv_rollout_general_)(a, v, au, rd, grid, stream); }
+#endif

@@ -5,6 +5,7 @@
 #define V_PASTE(a, b) V_PASTE2(a, b)
 #define V_NAME(x) V_PASTE(x, VARIANT)
 
+#ifndef SERL_VENV_NOISE      // (family_lanenz.hip instantiates venv_variant.inc alone: it needs serl_stage_and_index_<v> only)
 // All 64 lanes of a wavefront enter; lanes with `active` own one episode each.  The actor forward is
 // wave-cooperative (serl_actor_forward_wave), everything else is per lane.
 static __device__ void V_NAME(serl_wave_episodes_)(const RolloutArgs &a, int e, bool active)
@@ -151,6 +152,8 @@ static __device__ void V_NAME(serl_wave_episodes_)(const RolloutArgs &a, int e, 
   if (prof && lane == 0) { a.prof[0] = pc_actor; a.prof[1] = pc_dyn; a.prof[2] = pc_env; a.prof[3] = pc_steps; }
 }
 
+#endif
+
 // stage the build's tables into LDS (all threads of the workgroup), then keep `lanes` lanes per wavefront
 static __device__ __forceinline__ int V_NAME(serl_stage_and_index_)(const RolloutArgs &a)
 {
@@ -177,6 +180,7 @@ static __device__ __forceinline__ int V_NAME(serl_stage_and_index_)(const Rollou
   return (lane >= a.lanes || e >= a.d.n_episodes) ? -1 : e;
 }
 
+#ifndef SERL_VENV_NOISE
 __global__ void __launch_bounds__(SERL_BLOCK) V_NAME(serl_rollout_kernel_)(RolloutArgs a)
 {
   const int e = V_NAME(serl_stage_and_index_)(a);
@@ -208,6 +212,7 @@ void V_NAME(serl_launch_rollout_)(const RolloutArgs &a, int grid, hipStream_t st
 {
   hipLaunchKernelGGL(V_NAME(serl_rollout_kernel_), dim3(grid), dim3(a.block), 0, stream, a);
 }
+#endif
 #undef V_NAME
 #undef V_PASTE
 #undef V_PASTE2

@@ -67,6 +67,23 @@ static_assert(serl_rows_in_code_order(), "k_launchers: row i must be serl_dyn_co
 // the record of a loaded build's code variant (serl_ctx_load_build admits only codes with a row)
 static const SerlLaunchers &serl_launchers(int code) { return k_launchers[code]; }
 
+// the env kernels with the in-kernel noise generator (family_lanenz.hip: venv_variant.inc under SERL_VENV_NOISE), one record per code variant as above
+typedef void SerlLaunchVenvNz(const RolloutArgs &a, const VenvArgs &v, const serl_venv_noise_desc &nz, int grid, hipStream_t stream);
+typedef void SerlLaunchVenvAutoNz(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, const serl_venv_noise_desc &nz, int grid,
+                                  hipStream_t stream);
+typedef void SerlLaunchVenvRolloutNz(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, const serl_venv_rollout_desc &rd,
+                                     const serl_venv_noise_desc &nz, int grid, hipStream_t stream);
+#define SERL_NZ_LAUNCHERS(X, v)                                                       \
+  X(SerlLaunchVenvNz, reset, serl_launch_venv_reset_noise_##v)                        \
+  X(SerlLaunchVenvAutoNz, step_auto, serl_launch_venv_step_auto_noise_##v)            \
+  X(SerlLaunchVenvRolloutNz, rollout, serl_launch_venv_rollout_noise_##v)             \
+  X(SerlLaunchVenvRolloutNz, rollout_general, serl_launch_venv_rollout_general_noise_##v)
+struct SerlNzLaunchers { SERL_NZ_LAUNCHERS(SERL_MEMBER, v) };
+#define SERL_NZ_VARIANT_DECL(v, code) SERL_NZ_LAUNCHERS(SERL_DECL, v)
+#define SERL_NZ_VARIANT_ROW(v, code) {SERL_NZ_LAUNCHERS(SERL_INIT, v)},
+SERL_VARIANTS(SERL_NZ_VARIANT_DECL)
+static const SerlNzLaunchers k_nz_launchers[] = {SERL_VARIANTS(SERL_NZ_VARIANT_ROW)};
+
 #include "serl_mixed.h"
 
 static void serl_launch_rollout_teamg(const SerlLaunchers &L, int groups, const RolloutArgs &a, int grid, hipStream_t stream)
@@ -808,7 +825,8 @@ static int serl_venv_check(serl_ctx *c, const serl_venv_desc *d, const char *wha
 
 // the launch shape of serl_dyn_open_loop's lane kernels: lanes per wavefront from the batch, so that small batches still spread over the CUs
 static int serl_venv_launch(serl_ctx *c, const serl_venv_desc *d, bool step, VenvArgs &v, hipStream_t stream,
-                            const serl_venv_auto_desc *au = nullptr, const serl_venv_rollout_desc *rd = nullptr, bool general = false)
+                            const serl_venv_auto_desc *au = nullptr, const serl_venv_rollout_desc *rd = nullptr, bool general = false,
+                            const serl_venv_noise_desc *nz = nullptr)
 {
   const BuildSlot &s = c->slots[d->build_slot];
   const SerlLaunchers &L = serl_launchers(s.code);
@@ -829,6 +847,13 @@ static int serl_venv_launch(serl_ctx *c, const serl_venv_desc *d, bool step, Ven
   if (rd) {      // the actor shape the lane forward reads (rollout_device.h serl_actor_forward_lane32 / _lane_general)
     a.d.state_dim = rd->state_dim; a.d.action_dim = rd->action_dim; a.d.hidden = rd->hidden;
     a.d.num_layers = rd->num_layers; a.d.activation = rd->activation;
+  }
+  if (nz) {      // (the same launch shapes around the noise instantiations; there is no plain step among them)
+    const SerlNzLaunchers &Z = k_nz_launchers[s.code];
+    if (rd) (general ? Z.rollout_general : Z.rollout)(a, v, *au, *rd, *nz, grid, stream);
+    else if (au) Z.step_auto(a, v, *au, *nz, grid, stream);
+    else Z.reset(a, v, *nz, grid, stream);
+  } else if (rd) {
     (general ? L.venv_rollout_general : L.venv_rollout)(a, v, *au, *rd, grid, stream);
   } else if (au) L.venv_step_auto(a, v, *au, grid, stream);
   else (step ? L.venv_step : L.venv_reset)(a, v, grid, stream);
@@ -846,6 +871,42 @@ int serl_venv_reset(serl_ctx *c, const serl_venv_desc *d, const uint8_t *mask, d
   v.mask = mask;
   v.obs = obs;
   return serl_venv_launch(c, d, false, v, (hipStream_t)stream_);
+}
+
+// what the serl_venv_*_noise entries refuse in `nz` (none of these checks reads the context)
+static int serl_venv_noise_check(const std::string &w, const serl_venv_desc *d, const serl_venv_rollout_desc *rd, const serl_venv_noise_desc *nz)
+{
+  if (!nz) return fail(SERL_E_INVALID, w + ": nz is NULL");
+  if (!nz->episode_count) return fail(SERL_E_INVALID, w + ": nz->episode_count is NULL");
+  if ((nz->sensor != 0 && nz->sensor != 1) || (nz->action != 0 && nz->action != 1)) return fail(SERL_E_INVALID, w + ": nz->sensor / nz->action must be 0 or 1");
+  if (d && d->sensor_noise && nz->sensor) return fail(SERL_E_INVALID, w + ": desc->sensor_noise together with nz->sensor");
+  if (rd && rd->action_noise && nz->action) return fail(SERL_E_INVALID, w + ": ro->action_noise together with nz->action");
+  if (!(nz->action_sd >= 0.0) || !(nz->action_clip >= 0.0)) return fail(SERL_E_INVALID, w + ": nz->action_sd / nz->action_clip < 0");
+  return SERL_OK;
+}
+
+int serl_venv_noise_layout(int32_t *out, int32_t capacity)
+{
+#define SERL_OFF(m) (int32_t)offsetof(serl_venv_noise_desc, m)
+  const int32_t v[] = {(int32_t)sizeof(serl_venv_noise_desc), SERL_OFF(seed), SERL_OFF(episode_count), SERL_OFF(sensor), SERL_OFF(pad0),
+                       SERL_OFF(sensor_bias), SERL_OFF(sensor_scale), SERL_OFF(action), SERL_OFF(pad1), SERL_OFF(action_sd), SERL_OFF(action_clip)};
+#undef SERL_OFF
+  const int32_t n = (int32_t)(sizeof(v) / sizeof(v[0]));
+  for (int32_t i = 0; out && i < n && i < capacity; ++i) out[i] = v[i];
+  return n;
+}
+
+int serl_venv_reset_noise(serl_ctx *c, const serl_venv_desc *d, const uint8_t *mask, double *obs, const serl_venv_noise_desc *nz, void *stream_)
+{
+  { const int rc_ = serl_venv_noise_check("serl_venv_reset_noise", d, nullptr, nz); if (rc_ != SERL_OK) return rc_; }
+  { const int rc_ = serl_venv_check(c, d, "serl_venv_reset_noise"); if (rc_ != SERL_OK) return rc_; }
+  if (!obs) return fail(SERL_E_INVALID, "serl_venv_reset_noise: obs is NULL");
+  HIP_TRY(hipSetDevice(c->device));
+  VenvArgs v;
+  memset(&v, 0, sizeof(v));
+  v.mask = mask;
+  v.obs = obs;
+  return serl_venv_launch(c, d, false, v, (hipStream_t)stream_, nullptr, nullptr, false, nz);
 }
 
 int serl_venv_step(serl_ctx *c, const serl_venv_desc *d, const void *actions, int32_t actions_f64, double *obs,
@@ -873,11 +934,10 @@ int serl_venv_auto_layout(int32_t *out, int32_t capacity)
   return n;
 }
 
-int serl_venv_step_auto(serl_ctx *c, const serl_venv_desc *d, const void *actions, int32_t actions_f64, double *obs,
-                        double *reward, uint8_t *done, double *x, double *ref, double *t, int32_t *cost,
-                        const serl_venv_auto_desc *au, void *stream_)
+static int serl_venv_step_auto_impl(const char *w, serl_ctx *c, const serl_venv_desc *d, const void *actions, int32_t actions_f64, double *obs,
+                                    double *reward, uint8_t *done, double *x, double *ref, double *t, int32_t *cost,
+                                    const serl_venv_auto_desc *au, const serl_venv_noise_desc *nz, void *stream_)
 {
-  const char *w = "serl_venv_step_auto";
   if (!c || !d || !au) return fail(SERL_E_INVALID, std::string(w) + ": NULL argument");
   if (au->ref_pool && d->ref) return fail(SERL_E_INVALID, std::string(w) + ": ref_pool together with desc->ref");
   if (au->ref_pool && au->pool_rows < 1) return fail(SERL_E_INVALID, std::string(w) + ": pool_rows < 1");
@@ -893,7 +953,22 @@ int serl_venv_step_auto(serl_ctx *c, const serl_venv_desc *d, const void *action
   memset(&v, 0, sizeof(v));
   v.actions = actions; v.actions_f64 = actions_f64;
   v.obs = obs; v.reward = reward; v.done = done; v.x = x; v.ref = ref; v.t = t; v.cost = cost;
-  return serl_venv_launch(c, &dd, true, v, (hipStream_t)stream_, au);
+  return serl_venv_launch(c, &dd, true, v, (hipStream_t)stream_, au, nullptr, false, nz);
+}
+
+int serl_venv_step_auto(serl_ctx *c, const serl_venv_desc *d, const void *actions, int32_t actions_f64, double *obs,
+                        double *reward, uint8_t *done, double *x, double *ref, double *t, int32_t *cost,
+                        const serl_venv_auto_desc *au, void *stream_)
+{
+  return serl_venv_step_auto_impl("serl_venv_step_auto", c, d, actions, actions_f64, obs, reward, done, x, ref, t, cost, au, nullptr, stream_);
+}
+
+int serl_venv_step_auto_noise(serl_ctx *c, const serl_venv_desc *d, const void *actions, int32_t actions_f64, double *obs,
+                              double *reward, uint8_t *done, double *x, double *ref, double *t, int32_t *cost,
+                              const serl_venv_auto_desc *au, const serl_venv_noise_desc *nz, void *stream_)
+{
+  { const int rc_ = serl_venv_noise_check("serl_venv_step_auto_noise", d, nullptr, nz); if (rc_ != SERL_OK) return rc_; }
+  return serl_venv_step_auto_impl("serl_venv_step_auto_noise", c, d, actions, actions_f64, obs, reward, done, x, ref, t, cost, au, nz, stream_);
 }
 
 int serl_venv_rollout_layout(int32_t *out, int32_t capacity)
@@ -910,9 +985,10 @@ int serl_venv_rollout_layout(int32_t *out, int32_t capacity)
   return n;
 }
 
-int serl_venv_rollout(serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd, void *stream_)
+static int serl_venv_rollout_impl(const char *what, serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd,
+                                  const serl_venv_noise_desc *nz, void *stream_)
 {
-  const std::string w("serl_venv_rollout");
+  const std::string w(what);
   // (the descriptors first: none of these checks reads the context)
   if (!c || !d || !au || !rd) return fail(SERL_E_INVALID, w + ": NULL argument");
   if (!rd->obs || !rd->weights) return fail(SERL_E_INVALID, w + ": obs / weights is NULL");
@@ -937,12 +1013,25 @@ int serl_venv_rollout(serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto
   HIP_TRY(hipSetDevice(c->device));
   VenvArgs v;
   memset(&v, 0, sizeof(v));
-  return serl_venv_launch(c, &dd, true, v, (hipStream_t)stream_, au, rd);
+  return serl_venv_launch(c, &dd, true, v, (hipStream_t)stream_, au, rd, false, nz);
 }
 
-int serl_venv_rollout_general(serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd, void *stream_)
+int serl_venv_rollout(serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd, void *stream_)
 {
-  const std::string w("serl_venv_rollout_general");
+  return serl_venv_rollout_impl("serl_venv_rollout", c, d, au, rd, nullptr, stream_);
+}
+
+int serl_venv_rollout_noise(serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd,
+                            const serl_venv_noise_desc *nz, void *stream_)
+{
+  { const int rc_ = serl_venv_noise_check("serl_venv_rollout_noise", d, rd, nz); if (rc_ != SERL_OK) return rc_; }
+  return serl_venv_rollout_impl("serl_venv_rollout_noise", c, d, au, rd, nz, stream_);
+}
+
+static int serl_venv_rollout_general_impl(const char *what, serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au,
+                                          const serl_venv_rollout_desc *rd, const serl_venv_noise_desc *nz, void *stream_)
+{
+  const std::string w(what);
   // (the descriptors first: none of these checks reads the context)
   if (!c || !d || !au || !rd) return fail(SERL_E_INVALID, w + ": NULL argument");
   if (!rd->obs || !rd->weights) return fail(SERL_E_INVALID, w + ": obs / weights is NULL");
@@ -969,7 +1058,19 @@ int serl_venv_rollout_general(serl_ctx *c, const serl_venv_desc *d, const serl_v
   HIP_TRY(hipSetDevice(c->device));
   VenvArgs v;
   memset(&v, 0, sizeof(v));
-  return serl_venv_launch(c, &dd, true, v, (hipStream_t)stream_, au, rd, true);
+  return serl_venv_launch(c, &dd, true, v, (hipStream_t)stream_, au, rd, true, nz);
+}
+
+int serl_venv_rollout_general(serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd, void *stream_)
+{
+  return serl_venv_rollout_general_impl("serl_venv_rollout_general", c, d, au, rd, nullptr, stream_);
+}
+
+int serl_venv_rollout_general_noise(serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd,
+                                    const serl_venv_noise_desc *nz, void *stream_)
+{
+  { const int rc_ = serl_venv_noise_check("serl_venv_rollout_general_noise", d, rd, nz); if (rc_ != SERL_OK) return rc_; }
+  return serl_venv_rollout_general_impl("serl_venv_rollout_general_noise", c, d, au, rd, nz, stream_);
 }
 
 /* development aid (SERL_PROFILE=1): shader-clock cycles wave 0 of workgroup 0 spent in the actor forward, the

@@ -9,6 +9,32 @@
 #define VV_PASTE2(a, b) a##b
 #define VV_PASTE(a, b) VV_PASTE2(a, b)
 #define VV_NAME(x) VV_PASTE(x, VARIANT)
+// SERL_VENV_NOISE (family_lanenz.hip): the same text a second time as the kernels of serl_venv_*_noise (include/serl_amd.h serl_venv_noise_desc), in which
+// the sensor-noise row and the action-noise row come out of the counter-based generator (serl_rng.h) where nz.sensor / nz.action say so, and every episode
+// start counts in nz.episode_count.  Without it the VV_NZ_* macros are empty and VV_SENSOR / VV_ACTION_NOISE_* are the table reads they replace.
+#ifdef SERL_VENV_NOISE
+#define VV_KNAME(x) VV_PASTE(VV_PASTE(x, noise_), VARIANT)
+#define VV_NZ_PARAM , serl_venv_noise_desc nz
+#define VV_NZ_LOCALS double nzsn[7], nzan[3]; int32_t nzep = 0; (void)nzan;
+#define VV_NZ_START nzep = nz.episode_count[e]; nz.episode_count[e] = nzep + 1;      /* an explicit reset: the episode it starts has the ordinal the count had */
+#define VV_NZ_LOAD nzep = nz.episode_count[e] - 1;                                   /* the running episode's ordinal */
+#define VV_NZ_RESTART nzep += 1;
+#define VV_NZ_STORE nz.episode_count[e] = nzep + 1;
+#define VV_SENSOR(j) serl_venv_sensor_nz(d, nz, e, nzep, j, nzsn)
+#define VV_ACTION_NOISE_ON (rd.action_noise || nz.action)
+#define VV_ACTION_NOISE_ROW serl_venv_action_nz(rd, nz, kn, e, nzep, k, nzan)
+#else
+#define VV_KNAME(x) VV_NAME(x)
+#define VV_NZ_PARAM
+#define VV_NZ_LOCALS
+#define VV_NZ_START
+#define VV_NZ_LOAD
+#define VV_NZ_RESTART
+#define VV_NZ_STORE
+#define VV_SENSOR(j) serl_venv_sensor(d, e, j)
+#define VV_ACTION_NOISE_ON rd.action_noise
+#define VV_ACTION_NOISE_ROW rd.action_noise + kn * 3
+#endif
 
 #ifndef SERL_VENV_COMMON
 #define SERL_VENV_COMMON
@@ -58,6 +84,25 @@ static __device__ __forceinline__ const double *serl_venv_sensor(const serl_venv
   const int sr = d.sensor_row ? d.sensor_row[e] : e;
   return sr < 0 ? nullptr : d.sensor_noise + ((size_t)sr * ((size_t)d.max_steps + 1) + (size_t)j) * 7;
 }
+#ifdef SERL_VENV_NOISE
+// ... or, where nz.sensor is set, the row the generator draws for (env e, episode ordinal ep, entry j), into the caller's buffer
+static __device__ __forceinline__ const double *serl_venv_sensor_nz(const serl_venv_desc &d, const serl_venv_noise_desc &nz, int e, int32_t ep, int j,
+                                                                    double (&buf)[7])
+{
+  if (!nz.sensor) return serl_venv_sensor(d, e, j);
+  serl_rng_sensor(nz.seed, nz.sensor_bias, nz.sensor_scale, e, ep, j, buf);
+  return buf;
+}
+
+// the action-noise row of step kn: the caller's table, or, where nz.action is set, clip(sd z, +-clip) drawn for (env e, episode ordinal ep, in-episode step k)
+static __device__ __forceinline__ const double *serl_venv_action_nz(const serl_venv_rollout_desc &rd, const serl_venv_noise_desc &nz, size_t kn, int e,
+                                                                    int32_t ep, int k, double (&buf)[3])
+{
+  if (!nz.action) return rd.action_noise + kn * 3;
+  serl_rng_action(nz.seed, nz.action_sd, nz.action_clip, e, ep, k, buf);
+  return buf;
+}
+#endif
 #endif  // SERL_VENV_COMMON
 
 // the dynamics state of env e: state buffer <-> a CitCtx in the caller's stack frame
@@ -90,7 +135,7 @@ static __device__ __forceinline__ void VV_NAME(serl_venv_store_ctx_)(const VenvA
 }
 
 // reset() of the envs in the mask (envs/phlabenv.py:401-428)
-__global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_reset_kernel_)(RolloutArgs a, VenvArgs v)
+__global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_reset_kernel_)(RolloutArgs a, VenvArgs v VV_NZ_PARAM)
 {
   const int e = VV_NAME(serl_stage_and_index_)(a);
   if (e < 0) return;
@@ -100,6 +145,8 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_reset_kernel_)(R
   int32_t *I = (int32_t *)(S + SERL_VENV_F64 * v.npad);
   const int64_t np = v.npad;
   const int A = d.action_dim;
+  VV_NZ_LOCALS
+  VV_NZ_START
   double err[3], u[3] = {0.0, 0.0, 0.0}, x[12], cmd[10];
   for (int i = 0; i < 3; ++i) err[i] = S[(SERL_VF_ERR + i) * np + e];      // self.error is never cleared
   if (d.err0) for (int i = 0; i < 3; ++i) err[i] = i < A ? d.err0[(size_t)e * 3 + i] : 0.0;
@@ -116,7 +163,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_reset_kernel_)(R
   cmd[1] = serl_clip(cmd[1], -f.ail_clip, f.ail_clip);
   if (f.rudder_jam_on != 0.0) cmd[2] = f.rudder_jam;
   VV_NAME(cit_step_)(&ctx, cmd, x);
-  if (const double *sn = serl_venv_sensor(d, e, 0)) {
+  if (const double *sn = VV_SENSOR(0)) {
     x[0] += sn[0]; x[1] += sn[1]; x[2] += sn[2]; x[4] += sn[3]; x[5] += sn[4]; x[6] += sn[5]; x[7] += sn[6];
   }
   VV_NAME(serl_venv_store_ctx_)(v, e, ctx);
@@ -132,6 +179,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_reset_kernel_)(R
   serl_venv_write_obs(d.env_config, d.incremental != 0, err, x, u, v.obs + (size_t)e * d.state_dim);
 }
 
+#ifndef SERL_VENV_NOISE      // (the plain step has no noise instantiation: device noise needs auto-reset)
 // step(action) of every env (envs/phlabenv.py:430-482)
 __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_step_kernel_)(RolloutArgs a, VenvArgs v)
 {
@@ -214,12 +262,13 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_step_kernel_)(Ro
   if (v.t) v.t[e] = t;
   if (v.cost) v.cost[e] = cost;
 }
+#endif
 
 // step(action) of every env, and reset() of those whose episode that step ends, in the same launch (serl_venv_step_auto in
 // include/serl_amd.h).  cit_step_<v> is the whole cost and tens of KB inlined, so there is ONE call site in a two-trip loop: the first
 // trip is serl_venv_step_kernel_'s step, the second -- entered only by lanes whose episode ended -- is serl_venv_reset_kernel_'s
 // initialize() + step with the zero command.  The glue around it is those two kernels', statement for statement.
-__global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_step_auto_kernel_)(RolloutArgs a, VenvArgs v, serl_venv_auto_desc au)
+__global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_step_auto_kernel_)(RolloutArgs a, VenvArgs v, serl_venv_auto_desc au VV_NZ_PARAM)
 {
   const int e = VV_NAME(serl_stage_and_index_)(a);
   if (e < 0) return;
@@ -233,6 +282,8 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_step_auto_kernel
     for (int i = 0; i < d.state_dim; ++i) fobs[i] = v.obs[(size_t)e * d.state_dim + i];
     return;
   }
+  VV_NZ_LOCALS
+  VV_NZ_LOAD
   const double PI = 3.14159265358979323846;
   const double deg2rad = PI / 180.0, rad2deg = 180.0 / PI;
   const int cfg = d.env_config, A = d.action_dim;
@@ -278,7 +329,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_step_auto_kernel
 #pragma nounroll
   for (int trip = 0; trip < 2; ++trip) {
     VV_NAME(cit_step_)(&ctx, cmd, x);
-    if (const double *sn = serl_venv_sensor(d, e, restart ? 0 : k + 1)) {
+    if (const double *sn = VV_SENSOR(restart ? 0 : k + 1)) {
       x[0] += sn[0]; x[1] += sn[1]; x[2] += sn[2]; x[4] += sn[3]; x[5] += sn[4]; x[6] += sn[5]; x[7] += sn[6];
     }
     if (restart) { V0n = x[3]; break; }
@@ -313,6 +364,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_step_auto_kernel
     au.cursor[e] = au.ref_pool ? (row + 1) % au.pool_rows : (int32_t)(((uint32_t)cur + 1u) & 0x7fffffffu);      // (no pool: restarts counted, wrapping to 0)
     // reset() of this env (serl_venv_reset_kernel_ without err0 / tick0): the error stays, the clock keeps counting
     restart = true;
+    VV_NZ_RESTART
     const uint32_t tick = ctx.tick;
     cit_reset(&ctx, a.ro, a.t3, a.x0, a.dw0, a.dyn_dt);
     if (tick) { ctx.tick = tick; ctx.t = (double)ctx.tick * ctx.dt; }
@@ -334,6 +386,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_step_auto_kernel
   I[SERL_VI_K * np + e] = k;
   I[SERL_VI_LIVE * np + e] = 1;
   I[SERL_VI_COST * np + e] = cost;
+  VV_NZ_STORE
   serl_venv_write_obs(cfg, incr, err, x, u, v.obs + (size_t)e * d.state_dim);
 }
 
@@ -343,7 +396,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_step_auto_kernel
 // state are loaded once and stored once; the outputs are step-major rows [k][n_envs].  Attitude task without rate control only
 // (7 observations, 3 actions: the lane actor's shape), so cfg / A / incr are constants here.  ONE call site of the actor and ONE of
 // cit_step_<v>: the two-trip loop sits inside the K loop, both rolled.
-__global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_rollout_kernel_)(RolloutArgs a, VenvArgs v, serl_venv_auto_desc au, serl_venv_rollout_desc rd)
+__global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_rollout_kernel_)(RolloutArgs a, VenvArgs v, serl_venv_auto_desc au, serl_venv_rollout_desc rd VV_NZ_PARAM)
 {
   const int e = VV_NAME(serl_stage_and_index_)(a);
   if (e < 0) return;
@@ -385,6 +438,8 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_rollout_kernel_)
     }
     return;
   }
+  VV_NZ_LOCALS
+  VV_NZ_LOAD
   const double PI = 3.14159265358979323846;
   const double deg2rad = PI / 180.0, rad2deg = 180.0 / PI;
   const double bound = (incr ? 25.0 : 10.0) * deg2rad, low = -bound, high = bound;
@@ -414,8 +469,8 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_rollout_kernel_)
     for (int i = 0; i < 7; ++i) obsf[i] = (float)obs[i];
     serl_actor_forward_lane32(a.d, w, obsf, act);
     // ---- the action path of rollout_variant.inc
-    if (rd.action_noise) {
-      const double *noise = rd.action_noise + kn * 3;
+    if (VV_ACTION_NOISE_ON) {
+      const double *noise = VV_ACTION_NOISE_ROW;
       for (int i = 0; i < 3; ++i) {
         double an = serl_clip((double)act[i] + noise[i], -1.0, 1.0);
         u[i] = low + 0.5 * (an + 1.0) * (high - low);
@@ -442,7 +497,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_rollout_kernel_)
 #pragma nounroll
     for (int trip = 0; trip < 2; ++trip) {
       VV_NAME(cit_step_)(&ctx, cmd, x);
-      if (const double *sn = serl_venv_sensor(d, e, restart ? 0 : k + 1)) {
+      if (const double *sn = VV_SENSOR(restart ? 0 : k + 1)) {
         x[0] += sn[0]; x[1] += sn[1]; x[2] += sn[2]; x[4] += sn[3]; x[5] += sn[4]; x[6] += sn[5]; x[7] += sn[6];
       }
       if (restart) { V0n = x[3]; break; }
@@ -489,6 +544,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_rollout_kernel_)
       cur = au.ref_pool ? (row + 1) % au.pool_rows : (int32_t)(((uint32_t)cur + 1u) & 0x7fffffffu);
       // reset() of this env, as in serl_venv_step_auto_kernel_: the error stays, the clock keeps counting
       restart = true;
+      VV_NZ_RESTART
       const uint32_t tick = ctx.tick;
       cit_reset(&ctx, a.ro, a.t3, a.x0, a.dw0, a.dyn_dt);
       if (tick) { ctx.tick = tick; ctx.t = (double)ctx.tick * ctx.dt; }
@@ -515,6 +571,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_rollout_kernel_)
   I[SERL_VI_LIVE * np + e] = 1;
   I[SERL_VI_COST * np + e] = cost;
   au.run_return[e] = run_return; au.run_length[e] = run_length; au.cursor[e] = cur;
+  VV_NZ_STORE
 }
 
 // The same K policy-driven steps for EVERY env configuration and actor shape (serl_venv_rollout_general in include/serl_amd.h): cfg, incr, S and A
@@ -523,7 +580,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_rollout_kernel_)
 // and the actor is rollout_device.h serl_actor_forward_lane_general (its two activation vectors in private memory).  Rows are [k][N][S], [k][N][A] and
 // [k][N][2 S + A + 3]; action_noise stays [K][N][3], of which the first A columns are read.  ONE call site of the actor and ONE of cit_step_<v>, both loops
 // rolled, exactly as above.
-__global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_rollout_general_kernel_)(RolloutArgs a, VenvArgs v, serl_venv_auto_desc au, serl_venv_rollout_desc rd)
+__global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_rollout_general_kernel_)(RolloutArgs a, VenvArgs v, serl_venv_auto_desc au, serl_venv_rollout_desc rd VV_NZ_PARAM)
 {
   const int e = VV_NAME(serl_stage_and_index_)(a);
   if (e < 0) return;
@@ -574,6 +631,8 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_rollout_general_
     }
     return;
   }
+  VV_NZ_LOCALS
+  VV_NZ_LOAD
   const double PI = 3.14159265358979323846;
   const double deg2rad = PI / 180.0, rad2deg = 180.0 / PI;
   const double bound = (incr ? 25.0 : 10.0) * deg2rad, low = -bound, high = bound;
@@ -605,8 +664,8 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_rollout_general_
     serl_actor_forward_lane_general(a.d, w, obsf, act);
     // ---- the action path of serl_venv_step_auto_kernel_ (noise / f32: the general-env branch of the wave kernels)
     double scl[3] = {0.0, 0.0, 0.0};
-    if (rd.action_noise) {
-      const double *noise = rd.action_noise + kn * 3;
+    if (VV_ACTION_NOISE_ON) {
+      const double *noise = VV_ACTION_NOISE_ROW;
       for (int i = 0; i < 3; ++i) {
         if (i >= A) continue;
         double an = serl_clip((double)act[i] + noise[i], -1.0, 1.0);
@@ -636,7 +695,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_rollout_general_
 #pragma nounroll
     for (int trip = 0; trip < 2; ++trip) {
       VV_NAME(cit_step_)(&ctx, cmd, x);
-      if (const double *sn = serl_venv_sensor(d, e, restart ? 0 : k + 1)) {
+      if (const double *sn = VV_SENSOR(restart ? 0 : k + 1)) {
         x[0] += sn[0]; x[1] += sn[1]; x[2] += sn[2]; x[4] += sn[3]; x[5] += sn[4]; x[6] += sn[5]; x[7] += sn[6];
       }
       if (restart) { V0n = x[3]; break; }
@@ -686,6 +745,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_rollout_general_
       cur = au.ref_pool ? (row + 1) % au.pool_rows : (int32_t)(((uint32_t)cur + 1u) & 0x7fffffffu);
       // reset() of this env, as in serl_venv_step_auto_kernel_: the error stays, the clock keeps counting
       restart = true;
+      VV_NZ_RESTART
       const uint32_t tick = ctx.tick;
       cit_reset(&ctx, a.ro, a.t3, a.x0, a.dw0, a.dyn_dt);
       if (tick) { ctx.tick = tick; ctx.t = (double)ctx.tick * ctx.dt; }
@@ -713,8 +773,33 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_rollout_general_
   I[SERL_VI_LIVE * np + e] = 1;
   I[SERL_VI_COST * np + e] = cost;
   au.run_return[e] = run_return; au.run_length[e] = run_length; au.cursor[e] = cur;
+  VV_NZ_STORE
 }
 
+#ifdef SERL_VENV_NOISE
+void VV_KNAME(serl_launch_venv_rollout_general_)(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, const serl_venv_rollout_desc &rd,
+                                                 const serl_venv_noise_desc &nz, int grid, hipStream_t stream)
+{
+  hipLaunchKernelGGL(VV_KNAME(serl_venv_rollout_general_kernel_), dim3(grid), dim3(a.block), 0, stream, a, v, au, rd, nz);
+}
+
+void VV_KNAME(serl_launch_venv_rollout_)(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, const serl_venv_rollout_desc &rd,
+                                         const serl_venv_noise_desc &nz, int grid, hipStream_t stream)
+{
+  hipLaunchKernelGGL(VV_KNAME(serl_venv_rollout_kernel_), dim3(grid), dim3(a.block), 0, stream, a, v, au, rd, nz);
+}
+
+void VV_KNAME(serl_launch_venv_step_auto_)(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, const serl_venv_noise_desc &nz, int grid,
+                                           hipStream_t stream)
+{
+  hipLaunchKernelGGL(VV_KNAME(serl_venv_step_auto_kernel_), dim3(grid), dim3(a.block), 0, stream, a, v, au, nz);
+}
+
+void VV_KNAME(serl_launch_venv_reset_)(const RolloutArgs &a, const VenvArgs &v, const serl_venv_noise_desc &nz, int grid, hipStream_t stream)
+{
+  hipLaunchKernelGGL(VV_KNAME(serl_venv_reset_kernel_), dim3(grid), dim3(a.block), 0, stream, a, v, nz);
+}
+#else
 void VV_NAME(serl_launch_venv_rollout_general_)(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, const serl_venv_rollout_desc &rd,
                                                 int grid, hipStream_t stream)
 {
@@ -741,6 +826,17 @@ void VV_NAME(serl_launch_venv_step_)(const RolloutArgs &a, const VenvArgs &v, in
 {
   hipLaunchKernelGGL(VV_NAME(serl_venv_step_kernel_), dim3(grid), dim3(a.block), 0, stream, a, v);
 }
+#endif
+#undef VV_SENSOR
+#undef VV_ACTION_NOISE_ON
+#undef VV_ACTION_NOISE_ROW
+#undef VV_NZ_PARAM
+#undef VV_NZ_LOCALS
+#undef VV_NZ_START
+#undef VV_NZ_LOAD
+#undef VV_NZ_RESTART
+#undef VV_NZ_STORE
+#undef VV_KNAME
 #undef VV_NAME
 #undef VV_PASTE
 #undef VV_PASTE2

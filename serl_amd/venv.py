@@ -37,6 +37,11 @@ By default (`path='auto'`) that kernel takes the SERL50 actor on the attitude ta
 one by one with a batched torch forward.  `path='fused'` also runs every other actor the C ABI packs -- hidden a multiple of 4 up to 128,
 up to 16 hidden layers, any activation -- on every env configuration in one launch (serl_venv_rollout_general, transition rows of
 2 S + A + 3 floats), or raises; `path='loop'` forces the step loop.
+
+`sensor_noise='device'` (with auto_reset=True) draws the sensor noise inside the kernels from a counter-based generator (csrc/serl_rng.h,
+serl_venv_*_noise): no table, no host draw, a fresh realisation for every episode of every env, reproducible from `env.noise_seed` and
+`env.noise_episode`; `rollout(..., action_noise='device', noise_sd=, noise_clip=)` draws the exploration noise the same way.  `venv_noise`
+writes any episode's draws out as a table.
 """
 import ctypes
 import numpy as np
@@ -56,7 +61,12 @@ class CitationVecEnv:
                   or a f64 table [N, T, 3] / [T, 3] (radians, rows at the env's accumulated step times: T bounds the episode), or
                   refsignals.ref_specs rows [N] / [1] (hand-made rows must satisfy refsignals.check_specs).  Given references stay until `reset(refs=...)` replaces those of the reset envs.
     sensor_noise  None: the modes with a sensor model ('noise', 'gust') draw builds.sensor_noise_table per env at every reset;
-                  False: none; or f64 [N, T + 1, 7] (entry 0 belongs to the step of reset(), entry k + 1 to env step k).
+                  False: none; or f64 [N, T + 1, 7] (entry 0 belongs to the step of reset(), entry k + 1 to env step k); or 'device'
+                  (needs auto_reset=True): the sensor model's addends (builds.sensor_terms) of normals drawn inside the kernels per
+                  (seed, env, episode ordinal, entry) -- no table, and a restarted episode gets a realisation of its own.
+    seed          the generator's 64-bit seed (None: one from np.random).  `noise_seed` and `noise_episode` (i32 [N]: episode starts
+                  of every env so far; the running episode's ordinal is one less) are the generator's whole state: venv_noise replays
+                  any episode from them.  A seed alone (no 'device' sensor noise) only prepares rollout(action_noise='device').
     engine        the RolloutEngine whose HIP context holds the build tables (default: the process's engine).
     auto_reset    True: `step` restarts the envs whose episode it ends, in the same launch; info gains 'final_obs' f64 [N, S],
                   'episode_return' f64 [N] and 'episode_length' i32 [N] (the last two valid where done).  The sensor-noise tables given
@@ -64,10 +74,26 @@ class CitationVecEnv:
     ref_pool      auto_reset with refs=None: training references drawn per env by every explicit reset; the episode the reset starts
                   flies row 0, the j-th restart after it row j % ref_pool (the pool recycles after ref_pool episodes)."""
 
+    # device noise (serl_venv_noise_desc): the seed, the per-env count of episode starts, whether the sensor noise comes from the generator
+    noise_seed = None
+    noise_episode = None
+    _dev_sensor = False
+
     def __init__(self, n_envs, mode='PHlab_attitude_nominal', t_max=20, refs=None, sensor_noise=None, engine=None, auto_reset=False,
-                 ref_pool=4):
+                 ref_pool=4, seed=None):
         if isinstance(refs, np.ndarray) and refs.dtype.names:
             refsignals.check_specs(refs)      # (widths > 0, non-decreasing times: before any device work)
+        dev_sensor = isinstance(sensor_noise, str)
+        if dev_sensor and sensor_noise != 'device':
+            raise ValueError("sensor_noise: None, False, a table or 'device', not %r" % (sensor_noise,))
+        if dev_sensor and not auto_reset:
+            raise ValueError("sensor_noise='device' needs an env made with auto_reset=True")
+        if seed is not None and not auto_reset:
+            raise ValueError('seed: device noise needs an env made with auto_reset=True')
+        if seed is not None and (isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2**64):
+            raise ValueError('seed: an integer in [0, 2^64), not %r' % (seed,))
+        if dev_sensor:
+            sensor_noise = False      # (no table)
         if not torch.cuda.is_available():
             raise RuntimeError('serl_amd.CitationVecEnv needs a ROCm GPU (torch.cuda.is_available() is False); '
                                'the product has no CPU path')
@@ -117,6 +143,8 @@ class CitationVecEnv:
             self._noise = torch.as_tensor(sensor_noise, dtype=torch.float64).to(dev).contiguous()
             if self._noise.shape != (N, self.max_steps + 1, 7):
                 raise ValueError('sensor_noise: f64 [N, max_steps + 1, 7] = %s' % ((N, self.max_steps + 1, 7),))
+        if dev_sensor or seed is not None:
+            self._enable_device_noise(seed, dev_sensor, started=False)
         self._faults = None
         if row != builds.NOMINAL_ROW:
             self._faults = torch.as_tensor(np.tile(np.asarray(row, np.float64), (N, 1))).to(dev).contiguous()
@@ -155,6 +183,21 @@ class CitationVecEnv:
                                                 run_length=self._run_length.data_ptr(), cursor=self._cursor.data_ptr())
             if self._pool is not None:
                 self.auto_desc.ref_pool, self.auto_desc.pool_rows = self._pool.data_ptr(), self.ref_pool
+
+    def _enable_device_noise(self, seed=None, sensor=False, started=True):
+        """Give the env a generator state; from here on reset / step / rollout run the noise instantiations of their kernels, which count
+        the episode starts.  started: the envs are already flying an episode the count has not seen (ordinal 0)."""
+        if seed is None:
+            seed = int(np.random.randint(0, 2**32)) << 32 | int(np.random.randint(0, 2**32))
+        self.noise_seed = int(seed)
+        self._dev_sensor = bool(sensor)
+        self.noise_episode = torch.full((self.n_envs,), 1 if started else 0, dtype=torch.int32, device=self.device)
+
+    def _nz_desc(self, action=False, sd=0.0, clip=0.0):
+        bias, scale = builds.sensor_bias_scale()
+        return _capi.VenvNoiseDesc(seed=self.noise_seed, episode_count=self.noise_episode.data_ptr(), sensor=int(self._dev_sensor),
+                                   sensor_bias=(ctypes.c_double * 7)(*bias), sensor_scale=(ctypes.c_double * 7)(*scale),
+                                   action=int(action), action_sd=float(sd), action_clip=float(clip))
 
     def _spec_tensor(self, specs):
         return torch.from_numpy(np.ascontiguousarray(specs).view(np.uint8).reshape(len(specs), -1)).to(self.device)
@@ -204,6 +247,8 @@ class CitationVecEnv:
             else:
                 self._spec[idx] = rows
         if sensor_noise is not None:
+            if self._dev_sensor:
+                raise ValueError("sensor_noise: this env draws its sensor noise on the device (sensor_noise='device')")
             if self._noise is None:
                 raise ValueError('sensor_noise: this env was made without a sensor model')
             self._noise[idx] = torch.as_tensor(sensor_noise, dtype=torch.float64).to(dev).reshape(-1, self.max_steps + 1, 7)
@@ -220,8 +265,13 @@ class CitationVecEnv:
         if tick0 is not None:
             t0 = torch.as_tensor(tick0, dtype=torch.int32).to(dev).reshape(N).contiguous()
             d.tick0 = t0.data_ptr(); keep.append(t0)
-        _capi.check(self.lib.serl_venv_reset(self.engine.ctx, ctypes.byref(d), None if m is None else m.data_ptr(),
-                                             self._obs.data_ptr(), self._stream()), 'serl_venv_reset')
+        if self.noise_episode is not None:
+            nz = self._nz_desc()
+            _capi.check(self.lib.serl_venv_reset_noise(self.engine.ctx, ctypes.byref(d), None if m is None else m.data_ptr(),
+                                                       self._obs.data_ptr(), ctypes.byref(nz), self._stream()), 'serl_venv_reset_noise')
+        else:
+            _capi.check(self.lib.serl_venv_reset(self.engine.ctx, ctypes.byref(d), None if m is None else m.data_ptr(),
+                                                 self._obs.data_ptr(), self._stream()), 'serl_venv_reset')
         del keep      # (freed memory is handed out again only to work ordered behind this launch on the same stream)
         return self._obs
 
@@ -236,10 +286,18 @@ class CitationVecEnv:
             raise ValueError('actions: [%d, %d], not %s' % (self.n_envs, self.action_dim, tuple(a.shape)))
         a = a.contiguous()
         if self.auto_reset:
-            _capi.check(self.lib.serl_venv_step_auto(self.engine.ctx, ctypes.byref(self.desc), a.data_ptr(), int(a.dtype == torch.float64),
-                                                     self._obs.data_ptr(), self._reward.data_ptr(), self._done.data_ptr(), self._x.data_ptr(),
-                                                     self._refk.data_ptr(), self._t.data_ptr(), self._cost.data_ptr(),
-                                                     ctypes.byref(self.auto_desc), self._stream()), 'serl_venv_step_auto')
+            if self.noise_episode is not None:
+                nz = self._nz_desc()
+                _capi.check(self.lib.serl_venv_step_auto_noise(self.engine.ctx, ctypes.byref(self.desc), a.data_ptr(), int(a.dtype == torch.float64),
+                                                               self._obs.data_ptr(), self._reward.data_ptr(), self._done.data_ptr(),
+                                                               self._x.data_ptr(), self._refk.data_ptr(), self._t.data_ptr(), self._cost.data_ptr(),
+                                                               ctypes.byref(self.auto_desc), ctypes.byref(nz), self._stream()),
+                            'serl_venv_step_auto_noise')
+            else:
+                _capi.check(self.lib.serl_venv_step_auto(self.engine.ctx, ctypes.byref(self.desc), a.data_ptr(), int(a.dtype == torch.float64),
+                                                         self._obs.data_ptr(), self._reward.data_ptr(), self._done.data_ptr(), self._x.data_ptr(),
+                                                         self._refk.data_ptr(), self._t.data_ptr(), self._cost.data_ptr(),
+                                                         ctypes.byref(self.auto_desc), self._stream()), 'serl_venv_step_auto')
             return self._obs, self._reward, self._done, {'x': self._x, 'ref': self._refk, 't': self._t, 'cost': self._cost,
                                                          'final_obs': self._final_obs, 'episode_return': self._ep_return,
                                                          'episode_length': self._ep_length}
@@ -302,14 +360,18 @@ class CitationVecEnv:
                              "hidden layers)" % (spec.state_dim, spec.hidden, spec.num_layers, spec.action_dim))
         return K, mods, spec
 
-    def rollout(self, policy, n_steps, *, member_of_env=None, action_noise=None, transitions=False, info=True, spec=None, path='auto'):
+    def rollout(self, policy, n_steps, *, member_of_env=None, action_noise=None, transitions=False, info=True, spec=None, path='auto',
+                noise_sd=None, noise_clip=None):
         """n_steps steps of every env under `policy`, restarts included, in ONE launch without host synchronisation
         (serl_venv_rollout: the actor runs inside the kernel, bit-identical to the fused rollout kernels' forward).  Needs auto_reset=True.
 
         policy         an Actor / GeneticAgent, a list of them, or packed f32 weights [members, >= P] on the env's device with
                        spec=NetSpec(...) (the zero-overhead form: modules are packed on the device at every call)
         member_of_env  i32 [N], each in [0, members): the env's member of the population; None: every env runs member 0
-        action_noise   f64 [n_steps, N, 3] added to the actor's output, the sum clipped to [-1, 1] (base/core/agent.py:90-93)
+        action_noise   f64 [n_steps, N, 3] added to the actor's output, the sum clipped to [-1, 1] (base/core/agent.py:90-93); or 'device'
+                       with noise_sd= and noise_clip=: clip(noise_sd z, +-noise_clip) of normals drawn inside the kernel per (noise_seed,
+                       env, episode ordinal, in-episode step) -- rollout(K1) then rollout(K2) draws what rollout(K1 + K2) draws.  On an
+                       env made without seed= / sensor_noise='device' the first such call draws a seed and starts counting episodes.
         -> dict of fresh device tensors, step-major: 'obs' f64 [K + 1, N, S] (row 0: where the segment started; row k + 1: what
         step() returns after step k), 'actions' f64 [K, N, A] (the executed action, actor units), 'reward' f64, 'done' bool,
         'final_obs' f64 [K, N, S], 'ep_return' f64 / 'ep_length' i32 (valid where done, 0 elsewhere); info: 'x' [K, N, 12], 'ref'
@@ -320,10 +382,26 @@ class CitationVecEnv:
         path           'auto': the lane kernel where fused_rollout_ok(spec) (attitude task, 7 -> 32 .. -> 3), else one step() per step with
                        a batched torch forward, to the same dictionary; 'fused': in a kernel or ValueError -- the lane kernel where
                        fused_rollout_ok, else the general kernel (serl_venv_rollout_general: every env configuration, hidden a multiple
-                       of 4 up to 128, up to 16 hidden layers) where fused_general_ok; 'loop': always the step loop (A/B runs, tests).
+                       of 4 up to 128, up to 16 hidden layers) where fused_general_ok; 'loop': always the step loop (A/B runs, tests;
+                       on an env with device noise its forward is the kernels' own, serl_venv_actor_forward, for every shape a kernel takes:
+                       there the paths agree bit for bit).
                        `last_rollout_path` says 'fused', 'fused-general' or 'loop'."""
+        dev_action = isinstance(action_noise, str)
+        if dev_action:
+            if action_noise != 'device':
+                raise ValueError("action_noise: f64 [n_steps, N, 3] or 'device', not %r" % (action_noise,))
+            if noise_sd is None or noise_clip is None or not float(noise_sd) >= 0.0 or not float(noise_clip) >= 0.0:
+                raise ValueError("action_noise='device' needs noise_sd >= 0 and noise_clip >= 0")
+            action_noise = None
+        elif noise_sd is not None or noise_clip is not None:
+            raise ValueError("noise_sd / noise_clip belong to action_noise='device'")
         K, mods, spec = self._check_rollout_args(policy, n_steps, spec, member_of_env, action_noise, path)
         N, S, A, dev = self.n_envs, self.state_dim, self.action_dim, self.device
+        if dev_action and self.noise_episode is None:
+            self._enable_device_noise()
+        nz = None
+        if self.noise_episode is not None:
+            nz = self._nz_desc(dev_action, noise_sd or 0.0, noise_clip or 0.0)
         moe = None
         if member_of_env is not None:
             moe = torch.as_tensor(member_of_env).to(device=dev, dtype=torch.int32).contiguous()
@@ -333,15 +411,8 @@ class CitationVecEnv:
         lane32 = self.fused_rollout_ok(spec)
         if path == 'loop' or (path == 'auto' and not lane32):
             self.last_rollout_path = 'loop'
-            return self._rollout_loop(policy, mods, spec, K, moe, noise, transitions, info)
-        if mods is None:
-            w = policy
-        else:      # packed on the device: no .cpu() round trip, no synchronisation
-            w = torch.stack([torch.cat([p.detach().reshape(-1) for p in m.parameters()]).to(device=dev, dtype=torch.float32) for m in mods])
-        if w.shape[1] % 4 or w.stride(0) % 4 or not w.is_contiguous():
-            w = pad_rows(w)
-        if w.data_ptr() % 16:      # (a view into a larger tensor: the kernel reads rows with 16-byte loads)
-            w = w.clone()
+            return self._rollout_loop(policy, mods, spec, K, moe, noise, transitions, info, nz if dev_action else None)
+        w = self._packed_rows(policy, mods)
         out = self._rollout_buffers(K, transitions, info)
         rd = _capi.VenvRolloutDesc(state_dim=spec.state_dim, action_dim=spec.action_dim, hidden=spec.hidden, num_layers=spec.num_layers,
                                    activation=spec.activation_id, n_members=w.shape[0], weights=w.data_ptr(),
@@ -356,11 +427,28 @@ class CitationVecEnv:
         if transitions:
             rd.transitions = out['transitions'].data_ptr()
         entry = 'serl_venv_rollout' if lane32 else 'serl_venv_rollout_general'
-        _capi.check(getattr(self.lib, entry)(self.engine.ctx, ctypes.byref(self.desc), ctypes.byref(self.auto_desc), ctypes.byref(rd),
-                                             self._stream()), entry)
+        if nz is not None:
+            entry += '_noise'
+            _capi.check(getattr(self.lib, entry)(self.engine.ctx, ctypes.byref(self.desc), ctypes.byref(self.auto_desc), ctypes.byref(rd),
+                                                 ctypes.byref(nz), self._stream()), entry)
+        else:
+            _capi.check(getattr(self.lib, entry)(self.engine.ctx, ctypes.byref(self.desc), ctypes.byref(self.auto_desc), ctypes.byref(rd),
+                                                 self._stream()), entry)
         del w, moe, noise      # (freed memory is handed out again only to work ordered behind this launch on the same stream)
         self.last_rollout_path = 'fused' if lane32 else 'fused-general'
         return out
+
+    def _packed_rows(self, policy, mods):
+        """the packed f32 rows the kernels read: 16-byte aligned, a multiple of 4 floats apart"""
+        if mods is None:
+            w = policy
+        else:      # packed on the device: no .cpu() round trip, no synchronisation
+            w = torch.stack([torch.cat([p.detach().reshape(-1) for p in m.parameters()]).to(device=self.device, dtype=torch.float32) for m in mods])
+        if w.shape[1] % 4 or w.stride(0) % 4 or not w.is_contiguous():
+            w = pad_rows(w)
+        if w.data_ptr() % 16:      # (a view into a larger tensor: the kernel reads rows with 16-byte loads)
+            w = w.clone()
+        return w
 
     def _rollout_buffers(self, K, transitions, info):
         N, S, A, dev = self.n_envs, self.state_dim, self.action_dim, self.device
@@ -375,10 +463,21 @@ class CitationVecEnv:
             out['transitions'] = torch.empty(K, N, 2 * S + A + 3, dtype=torch.float32, device=dev)
         return out
 
-    def _rollout_loop(self, policy, mods, spec, K, moe, noise, transitions, info):
-        """rollout() for the shapes serl_venv_rollout does not take: K x step() with a batched torch forward, to the same dictionary."""
+    def _rollout_loop(self, policy, mods, spec, K, moe, noise, transitions, info, nz=None):
+        """rollout() for the shapes serl_venv_rollout does not take: K x step() with a batched torch forward, to the same dictionary.
+        nz (action_noise='device'): the step's addends are what the kernels would draw, written out by serl_venv_noise_fill.
+        On an env with device noise (noise_episode is set) the forward is the kernels' own where a kernel takes the shape
+        (serl_venv_actor_forward instead of torch, whose f32 kernels differ from the ABI's arithmetic in the last bits): device noise
+        promises bit-exact replay, so there the loop computes what path='fused' computes.  Every other env keeps the torch forward."""
         N, S, A, dev = self.n_envs, self.state_dim, self.action_dim, self.device
-        if mods is None:      # packed rows -> modules (a host round trip per member: this is the slow path)
+        abi_forward = self.noise_episode is not None and (self.fused_rollout_ok(spec) or self.fused_general_ok(spec))
+        if abi_forward:
+            w = self._packed_rows(policy, mods)
+            fd = _capi.VenvRolloutDesc(state_dim=spec.state_dim, action_dim=spec.action_dim, hidden=spec.hidden, num_layers=spec.num_layers,
+                                       activation=spec.activation_id, n_members=w.shape[0], weights=w.data_ptr(),
+                                       weight_stride=w.stride(0) if w.shape[0] > 1 else w.shape[1],
+                                       member_of_env=None if moe is None else moe.data_ptr())
+        elif mods is None:      # packed rows -> modules (a host round trip per member: this is the slow path)
             import types
             args = types.SimpleNamespace(state_dim=spec.state_dim, action_dim=spec.action_dim, hidden_size=spec.hidden,
                                          num_layers=spec.num_layers, activation_actor=spec.activation, device=dev)
@@ -391,6 +490,11 @@ class CitationVecEnv:
             mods = [m if next(m.parameters()).device == dev else copy.deepcopy(m).to(dev) for m in mods]
 
         def forward(o):
+            if abi_forward:      # (o: a row of out['obs'], f64 and contiguous; the kernel converts to f32 as the rollout kernels do)
+                a = torch.empty(N, A, dtype=torch.float32, device=dev)
+                _capi.check(self.lib.serl_venv_actor_forward(self.engine.ctx, ctypes.byref(fd), N, o.data_ptr(), a.data_ptr(), self._stream()),
+                            'serl_venv_actor_forward')
+                return a
             with torch.no_grad():
                 if moe is None:
                     return mods[0](o)
@@ -402,6 +506,8 @@ class CitationVecEnv:
         npad = (N + 63) // 64 * 64
         t_env = self._state[:73 * npad * 8].view(torch.float64).view(73, npad)[57, :N]      # SERL_VF_T: the env's accumulated time
         live = self._state[73 * npad * 8:].view(torch.int32).view(17, npad)[15, :N].ne(0).clone()      # SERL_VI_LIVE: never changes under auto-reset
+        k_env = self._state[73 * npad * 8:].view(torch.int32).view(17, npad)[14, :N]      # SERL_VI_K: steps of the running episode
+        env_index = torch.arange(N, dtype=torch.int32, device=dev)
         deg = 3.14159265358979323846 / 180.0
         out = self._rollout_buffers(K, transitions, info)
         # the current observation of every env: a reset of no env writes it
@@ -411,9 +517,12 @@ class CitationVecEnv:
         out['obs'][0].copy_(self._obs)
         for k in range(K):
             o = out['obs'][k]
-            a = forward(o.float())
+            a = forward(o if abi_forward else o.float())
             if noise is not None:
                 a = torch.clamp(a.double() + noise[k, :, :A], -1.0, 1.0)
+            elif nz is not None:      # (a view of the state buffer is contiguous along the envs; the count is read in stream order)
+                addend = _noise_fill(self.engine, nz, 3, env_index, self.noise_episode - 1, k_env.contiguous(), 1)
+                a = torch.clamp(a.double() + addend[:, 0, :A], -1.0, 1.0)
             out['actions'][k].copy_(torch.where(live[:, None], a.double(), torch.zeros_like(a, dtype=torch.float64)))
             timed_out = t_env >= self.t_max      # (at the pre-increment t, as the env decides it)
             obs, rew, done, inf = self.step(a)
@@ -432,3 +541,51 @@ class CitationVecEnv:
                 out['transitions'][k].copy_(torch.cat([o.float(), out['actions'][k].float(), inf['final_obs'].float(), rew.float()[:, None],
                                                        fin.float()[:, None], inf['cost'].ne(0).float()[:, None]], dim=1))
         return out
+
+
+_FILL_MODES = {'bits': (0, 24, torch.int32), 'normal': (1, 7, torch.float64), 'sensor': (2, 7, torch.float64), 'action': (3, 3, torch.float64)}
+
+
+def _noise_fill(engine, nz, mode, env, episode, entry0, entries):
+    """serl_venv_noise_fill on device i32 [rows] tensors -> a fresh tensor [rows, entries, W]"""
+    code, W, dtype = [v for v in _FILL_MODES.values() if v[0] == mode][0]
+    rows = int(env.shape[0])
+    out = torch.empty(rows, int(entries), W, dtype=dtype, device=engine.device)
+    _capi.check(engine.lib.serl_venv_noise_fill(engine.ctx, ctypes.byref(nz), code, rows, env.data_ptr(), episode.data_ptr(), entry0.data_ptr(),
+                                                int(entries), out.data_ptr(),
+                                                ctypes.c_void_p(torch.cuda.current_stream(engine.device).cuda_stream)), 'serl_venv_noise_fill')
+    return out
+
+
+def venv_noise(seed, env, episode, entries, kind='sensor', *, entry0=0, noise_sd=None, noise_clip=None, engine=None):
+    """What CitationVecEnv's kernels draw for `entries` consecutive entries, entry0 onwards, of the episodes (seed; env[i], episode[i]) ->
+    a device tensor [rows, entries, W], written by the kernels' own device functions (serl_venv_noise_fill).
+
+    env, episode, entry0   integers or integer arrays / tensors [rows] (scalars are broadcast): env index, episode ordinal of that env
+                           (env.noise_episode - 1 is the running one), first entry
+    kind  'sensor'  f64 W = 7: the sensor model's addends (builds.sensor_terms of the normals); entries = max_steps + 1 from entry 0 is the
+                    table CitationVecEnv(sensor_noise=...), reset(sensor_noise=...), evaluate_pop and the oracle take
+          'normal'  f64 W = 7: the standard normals behind them
+          'action'  f64 W = 3: clip(noise_sd z, +-noise_clip), the exploration noise of in-episode step entry0 + j
+          'bits'    the raw Philox words as i32 bit patterns, W = 24: the sensor stream's four blocks, then the action stream's two"""
+    if kind not in _FILL_MODES:
+        raise ValueError("kind: one of 'sensor', 'normal', 'action', 'bits', not %r" % (kind,))
+    if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2**64:
+        raise ValueError('seed: an integer in [0, 2^64), not %r' % (seed,))
+    if isinstance(entries, bool) or int(entries) != entries or int(entries) < 1:
+        raise ValueError('entries: an integer >= 1, not %r' % (entries,))
+    if kind == 'action' and (noise_sd is None or noise_clip is None or not float(noise_sd) >= 0.0 or not float(noise_clip) >= 0.0):
+        raise ValueError("kind='action' needs noise_sd >= 0 and noise_clip >= 0")
+    if not torch.cuda.is_available():
+        raise RuntimeError('serl_amd.venv_noise needs a ROCm GPU (torch.cuda.is_available() is False); the product has no CPU path')
+    from .evaluator import default_engine
+    engine = engine or default_engine()
+    cols = [torch.as_tensor(v).to(device=engine.device, dtype=torch.int32).reshape(-1) for v in (env, episode, entry0)]
+    rows = max(len(c) for c in cols)
+    if any(len(c) not in (1, rows) for c in cols):
+        raise ValueError('env / episode / entry0: scalars or arrays of one length')
+    cols = [c.expand(rows).contiguous() for c in cols]
+    bias, scale = builds.sensor_bias_scale()
+    nz = _capi.VenvNoiseDesc(seed=int(seed), sensor_bias=(ctypes.c_double * 7)(*bias), sensor_scale=(ctypes.c_double * 7)(*scale),
+                             action_sd=float(noise_sd or 0.0), action_clip=float(noise_clip or 0.0))
+    return _noise_fill(engine, nz, _FILL_MODES[kind][0], cols[0], cols[1], cols[2], int(entries))

@@ -28,7 +28,14 @@ torch module on the same stream -- the same `staggered` and `idle` settings, med
     python tools/bench_venv.py --rollout --hidden 72 [--layers 3] [--path fused] [--out profiles/venv_rollout_general_timing.json]
 runs the same leg for an actor of another shape (7 -> hidden x layers -> 3, tanh, seeded default initialisation) on the attitude task:
 `env.rollout(actor, K, path=<--path>)` (serl_venv_rollout_general for 'fused') against `env.rollout(actor, K, path='loop')`, the only
-path these shapes had before.  --hidden takes a comma-separated list; the results of all shapes go into one file."""
+path these shapes had before.  --hidden takes a comma-separated list; the results of all shapes go into one file.
+
+    python tools/bench_venv.py --device-noise [--sizes 1024,65536] [--auto-steps 1000] [--rollout-k 50] [--reps 5] [--out profiles/venv_device_noise_timing.json]
+runs the device-noise leg: mode 'noise', episodes of 64 steps on a shared table at spread phases, CitationVecEnv(sensor_noise='device')
+(serl_venv_*_noise: the sensor noise drawn inside the kernels) against the table path (a pre-drawn f64 [N, 65, 7] table, 238 MB at 65 536 envs) --
+`step` under auto-reset with a fixed action, and `rollout(actor, K)` with the SERL50 actor, there also with action_noise='device' against a
+pre-drawn [K, N, 3] tensor; medians and [min .. max] of `reps` repetitions after a warm-up, the versions alternating.  Then the wall time and
+the bytes of noise tables of one full `reset()` at --reset-n envs with t_max = 20 on both paths (--reset-n 0 skips it)."""
 import argparse, json, os, subprocess, sys
 import numpy as np
 import torch
@@ -232,10 +239,86 @@ def bench_rollout(eng, N, steps, K, warmup, reps, hidden=None, layers=3, path='f
     return out
 
 
-def kernel_report():
+def bench_device_noise(eng, N, steps, K, warmup, reps):
+    """One size: the device generator against the table path, step(auto) and rollout(actor, K), every env live, 1 / 64 of them finishing per step."""
+    dev = eng.device
+    fixed = torch.zeros(N, 3, dtype=torch.float32, device=dev)
+    actor = serl50_policy(dev)
+    spec = serl_amd.NetSpec(7, 3, 32, 3, 'tanh')
+    w = torch.zeros(1, 3716, dtype=torch.float32, device=dev)
+    w[0, :3715] = torch.from_numpy(np.load(os.path.join(ROOT, 'tests', 'golden', 'actors.npz'))['serl50'][18]).to(dev)
+    L = 64
+    table = np.ascontiguousarray(rs.tabulate(*rs.base_reference(20), 20)[:L])
+    assert steps % K == 0 and warmup % K == 0
+    out = dict(N=N, steps=steps, K=K, reps=reps, warmup=warmup, episode_steps=L, table_bytes=N * (L + 1) * 7 * 8)
+
+    def make(v):
+        if v == 'device':
+            return serl_amd.CitationVecEnv(N, mode='noise', t_max=20, refs=table, engine=eng, auto_reset=True, sensor_noise='device', seed=1)
+        g = torch.Generator(device=dev).manual_seed(2)
+        z = torch.randn(N, L + 1, 7, generator=g, dtype=torch.float64, device=dev)
+        bias, scale = (torch.from_numpy(a).to(dev) for a in serl_amd.builds.sensor_bias_scale())
+        return serl_amd.CitationVecEnv(N, mode='noise', t_max=20, refs=table, engine=eng, auto_reset=True, sensor_noise=bias + scale * z)
+
+    def run(env, v, what, n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        if what == 'step_auto':
+            for _ in range(n):
+                env.step(fixed)
+        elif what == 'rollout':
+            for _ in range(n // K):
+                env.rollout(w, K, spec=spec)
+        else:      # rollout with exploration noise: drawn in the kernel, or a torch draw and clamp per call as the caller of the table path writes them
+            for _ in range(n // K):
+                if v == 'device':
+                    env.rollout(w, K, spec=spec, action_noise='device', noise_sd=0.3, noise_clip=0.5)
+                else:
+                    env.rollout(w, K, spec=spec, action_noise=torch.clamp(0.3 * torch.randn(K, N, 3, dtype=torch.float64, device=dev), -0.5, 0.5))
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    for what in ('step_auto', 'rollout', 'rollout_action_noise'):
+        envs = {v: make(v) for v in ('device', 'table')}
+        ms = {v: [] for v in envs}
+        with torch.no_grad():
+            for v, env in envs.items():
+                _stagger(env, L, fixed)
+                run(env, v, what, warmup)
+            for r in range(reps):
+                for v, env in (list(envs.items()) if r % 2 == 0 else list(envs.items())[::-1]):      # alternate the order
+                    ms[v].append(run(env, v, what, steps))
+        out[what] = dict(device=_summary(N, steps, ms['device']), table=_summary(N, steps, ms['table']))
+        a, m = out[what]['device']['us_per_step'], out[what]['table']['us_per_step']
+        out[what]['device_over_table_us_per_step'] = round(a['median'] / m['median'], 4)
+        del envs
+    return out
+
+
+def bench_noise_reset(eng, N):
+    """wall time and noise-table bytes of one full reset() of N envs at t_max = 20 (2 001 steps), mode 'noise', shared table references"""
+    import time
+    table = rs.tabulate(*rs.base_reference(20), 20)
+    out = dict(N=N, t_max=20, max_steps=len(table))
+    for v in ('device', 'table'):
+        kw = dict(sensor_noise='device', seed=1) if v == 'device' else {}
+        env = serl_amd.CitationVecEnv(N, mode='noise', t_max=20, refs=table, engine=eng, auto_reset=True, **kw)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        env.reset()
+        torch.cuda.synchronize()
+        out[v] = dict(reset_wall_s=round(time.perf_counter() - t0, 4), noise_table_bytes=0 if env._noise is None else env._noise.numel() * 8,
+                      host_normals_drawn=0 if env._noise is None else env._noise.numel())
+        del env
+        torch.cuda.empty_cache()
+    return out
+
+
+def kernel_report(stem='rollout_%s.o'):
     rep = {}
     for v in ('nominal', 'ice', 'cg_timed', 'gust', 'test'):
-        obj = os.path.join(ROOT, 'serl_amd', 'csrc', 'build', 'rollout_%s.o' % v)
+        obj = os.path.join(ROOT, 'serl_amd', 'csrc', 'build', stem % v)
         try:
             r = subprocess.run(['bash', os.path.join(ROOT, 'tools', 'kernel_regs.sh'), obj, 'venv'], capture_output=True, text=True, timeout=120)
         except Exception as ex:
@@ -268,6 +351,8 @@ def main():
     ap.add_argument('--hidden', default=None, help='--rollout: hidden size(s) of another actor shape, e.g. 72,96 (default: the SERL50 actor, hidden 32)')
     ap.add_argument('--layers', type=int, default=3, help='--rollout --hidden: hidden layers')
     ap.add_argument('--path', default='fused', choices=['auto', 'fused', 'loop'], help="--rollout --hidden: rollout(path=...) of the version compared with 'loop'")
+    ap.add_argument('--device-noise', action='store_true', help='the device-noise leg instead of the others')
+    ap.add_argument('--reset-n', type=int, default=65536, help='--device-noise: envs of the full-reset measurement at t_max = 20 (0: skip)')
     ap.add_argument('--out', default=None, help='default: profiles/venv_auto_timing.json (--auto-reset), profiles/venv_rollout_timing.json (--rollout), '
                                                 'profiles/venv_rollout_general_timing.json (--rollout --hidden)')
     args = ap.parse_args()
@@ -275,6 +360,26 @@ def main():
         args.out = os.path.join(ROOT, 'profiles', ('venv_rollout_general_timing.json' if args.hidden else 'venv_rollout_timing.json') if args.rollout
                                 else 'venv_auto_timing.json')
     eng = serl_amd.RolloutEngine(0)
+    if args.device_noise:
+        if args.out.endswith('venv_auto_timing.json'):
+            args.out = os.path.join(ROOT, 'profiles', 'venv_device_noise_timing.json')
+        sizes = [int(s) for s in (args.sizes if args.sizes != ap.get_default('sizes') else '1024,65536').split(',')]
+        res = dict(tool='bench_venv --device-noise', device=torch.cuda.get_device_name(0), source_hash=hip_build.source_hash(),
+                   results=[bench_device_noise(eng, N, args.auto_steps, args.rollout_k, args.warmup, args.reps) for N in sizes])
+        kernels = kernel_report('rollout_lanenz_%s.o')      # (needs the build's objects: empty where only the library was shipped)
+        if kernels:
+            res['kernels'] = kernels
+
+        def write():
+            with open(args.out, 'w') as f:
+                json.dump(res, f, indent=1)
+                f.write('\n')
+        write()      # (the timings first: the table path's full reset below draws 0.9 G normals on the host)
+        if args.reset_n > 0:
+            res['full_reset'] = bench_noise_reset(eng, args.reset_n)
+            write()
+        print(json.dumps(res))
+        return
     if args.rollout:
         sizes = [int(s) for s in (args.sizes if args.sizes != ap.get_default('sizes') else '1024,65536').split(',')]
         res = dict(tool='bench_venv --rollout', device=torch.cuda.get_device_name(0), source_hash=hip_build.source_hash(),
