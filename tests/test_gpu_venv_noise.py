@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import noise_replay
 import rng_ref
 from actor_shapes import make_weights, _shape, spec_of
 
@@ -223,14 +224,8 @@ def test_restarted_episodes_get_a_realisation_of_their_own(engine):
 # ---- 7. action noise, exact ----------------------------------------------------------------------------------------------------------------
 def _ordinals(done, first):
     """(episode ordinal, in-episode step) of every [k, e] from the done flags, for envs whose running episode has ordinal `first` at step 0"""
-    K, N = done.shape
-    ordinal, kin = np.zeros((K, N), np.int64), np.zeros((K, N), np.int64)
-    o, j = np.array(first, np.int64).copy(), np.zeros(N, np.int64)
-    for k in range(K):
-        ordinal[k], kin[k] = o, j
-        j = np.where(done[k], 0, j + 1)
-        o = o + done[k]
-    return ordinal, kin
+    first = np.array(first, np.int64)      # (tests/noise_replay.py: envs that fly that episode at row 0, `first + 1` starts counted)
+    return noise_replay.ordinals(done, noise_replay.episodes(done, count0=first + 1, live0=np.ones(len(first), bool), clock0=np.ones(len(first))))
 
 
 @pytest.mark.parametrize('hidden,layers,ask,path', [(32, 3, 'fused', 'fused'), (8, 1, 'fused', 'fused-general'), (32, 3, 'loop', 'loop'),
