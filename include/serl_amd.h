@@ -140,7 +140,8 @@ typedef struct serl_rollout_desc {
                                        four-episode teams with a work queue (a lane group takes the next episode when its
                                        own ends) -- and from 80 x CUs episodes on (hidden 32) the lane-per-episode kernels with 64 episodes per wavefront --
                                        or one wavefront per episode; 1..64 = lane-per-episode kernels with that
-                                       many episodes per wavefront (every code variant, attitude task only) */
+                                       many episodes per wavefront (every code variant, attitude task only).  With
+                                       kernel_hint SERL_KERNEL_LANEQ: the lanes per wavefront of the lane work-queue kernel, 0 = 64 */
   int32_t concurrent_episodes;      /* episodes of OTHER serl_rollout calls expected to run at the same time on other
                                        streams (mixed-build sweeps: one call per dynamics build); the kernel and the
                                        wavefronts per workgroup are chosen for n_episodes + concurrent_episodes so that
@@ -148,8 +149,10 @@ typedef struct serl_rollout_desc {
   int32_t kernel_hint;              /* enum serl_kernel_hint: SERL_KERNEL_AUTO (0) = chosen from the episode count as
                                        described at lanes_per_wave; the others force one of the wave-cooperative kernel
                                        families (tests and A/B measurements compare them: results are bit-identical).
-                                       Ignored when lanes_per_wave > 0.  SERL_E_UNSUPPORTED when the forced kernel does not
-                                       exist for the actor shape (two / four episodes per team, half: hidden 32 only) */
+                                       Ignored when lanes_per_wave > 0, except SERL_KERNEL_LANEQ (the lane-per-episode kernels
+                                       behind a work queue: see the enum).  SERL_E_UNSUPPORTED when the forced kernel does not
+                                       exist for the actor shape (two / four episodes per team, half: hidden 32 only) or the
+                                       env configuration (LANEQ: attitude task only) */
   /* -- results (per episode) */
   double *fitness;                  /* sum of rewards incl. termination penalty */
   int32_t *length_steps;            /* number of env steps taken */
@@ -188,9 +191,15 @@ enum serl_env_config { SERL_ENV_ATTITUDE = 0, SERL_ENV_SYMMETRIC = 1, SERL_ENV_F
  *   TEAM   eight wavefronts = one episode (seven integrate, one runs the actor); rounds of CUs episodes
  *   TEAM2 / TEAM4   the same team carrying two / four episodes in lane groups of 32 / 16 (hidden 32)
  *   WAVE   one wavefront = one episode, up to four per workgroup
- *   HALF   one wavefront = two episodes (hidden 32) */
+ *   HALF   one wavefront = two episodes (hidden 32)
+ *   LANEQ  one LANE = one episode, and a lane whose episode ends takes the next one from a work queue (serl_rollout_laneq_kernel_<variant>): at most
+ *          4 x CUs wavefronts of lanes_per_wave lanes (0 = 64) are launched -- four per workgroup, one workgroup per CU, scaled by the launch's share of
+ *          the episodes when concurrent_episodes > 0 -- and the episodes beyond those lane slots wait behind a device counter.  The only hint that is
+ *          not ignored when lanes_per_wave > 0.  Attitude task, every code variant, every actor shape; serl_rollout only (serl_rollout_multi and
+ *          serl_dyn_open_loop refuse it).  serl_last_rollout_info reports family SERL_FAMILY_LANE and whether the queue was engaged.  Opt-in:
+ *          SERL_KERNEL_AUTO never chooses it. */
 enum serl_kernel_hint { SERL_KERNEL_AUTO = 0, SERL_KERNEL_TEAM = 1, SERL_KERNEL_WAVE = 2, SERL_KERNEL_HALF = 3,
-                        SERL_KERNEL_TEAM2 = 4, SERL_KERNEL_TEAM4 = 5 };
+                        SERL_KERNEL_TEAM2 = 4, SERL_KERNEL_TEAM4 = 5, SERL_KERNEL_LANEQ = 6 };
 /* length of the observation of a configuration (0 = invalid) and its number of actions */
 int serl_env_state_dim(int env_config, int incremental);
 int serl_env_action_dim(int env_config);
@@ -210,8 +219,9 @@ int serl_ctx_create(int device, serl_ctx **out);
 int serl_ctx_destroy(serl_ctx *ctx);
 int serl_ctx_load_build(serl_ctx *ctx, int slot, const serl_build_desc *build);
 /* Development overrides, read from the environment ONCE, by serl_ctx_create (the only getenv of the library):
- *   SERL_KERNEL=team|team2|team4|wave|half   kernel family for descriptors with kernel_hint == SERL_KERNEL_AUTO
+ *   SERL_KERNEL=team|team2|team4|wave|half|laneq   kernel family for descriptors with kernel_hint == SERL_KERNEL_AUTO
  *   SERL_WAVES_PER_BLOCK=n                   wavefronts per workgroup of the one-wavefront kernels
+ *   SERL_LANEQ_WAVES=n                       SERL_KERNEL_LANEQ: at most n wavefronts per launch instead of 4 x CUs (tests engage the work queue with a handful of episodes)
  *   SERL_PROFILE=1                           cycle counters for serl_debug_profile
  *   SERL_SPLIT_ACTOR=1                       one-episode teams with a streamed actor (hidden > 64): two actor wavefronts share the forward pass
  *   SERL_REMOTE_ACTOR=0                      one-episode teams with a streamed actor: the actor stays on the team's CU (default 1: a workgroup of its own on another CU

@@ -39,6 +39,7 @@ static_assert(8 * (CIT_RO_LDS_WORDS + CIT_V(_NSLOPE)) <= 160 * 1024, "tables + i
 #ifdef CIT_WITH_CMD_IN_MEMORY      // (A/B builds around gen files made with CITW_LANE_CMDMEM=1: measured slower)
 #define CIT_CMD_IN_MEMORY 1
 #endif
+#define SERL_LANE_QUEUE 1      // (rollout_variant.inc: the work-queue kernel serl_rollout_laneq_kernel_<v> beside serl_rollout_kernel_<v>)
 #define CIT_Y_IS_STATE 1      // (gen/citation_<variant>_lane.inc: `if (major) c->Y[i] = X[i]`, i < 12 -- the outputs of step() are the states in front of the integration)
 #include "citation_step_dev.h"
 #include "rollout_variant.inc"
@@ -57,6 +58,7 @@ void SERL_VNZ(serl_launch_venv_rollout_)(const RolloutArgs &a, const VenvArgs &v
 void SERL_VNZ(serl_launch_venv_rollout_general_)(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, const serl_venv_rollout_desc &rd, const serl_venv_noise_desc &nz, int grid, hipStream_t stream) { bdag::SERL_VNZ(serl_launch_venv_rollout_general_)(a, v, au, rd, nz, grid, stream); }
 #else
 void SERL_V(serl_launch_rollout_)(const RolloutArgs &a, int grid, hipStream_t stream) { bdag::SERL_V(serl_launch_rollout_)(a, grid, stream); }
+void SERL_V(serl_launch_rollout_laneq_)(const RolloutArgs &a, int grid, hipStream_t stream) { bdag::SERL_V(serl_launch_rollout_laneq_)(a, grid, stream); }
 
 void SERL_V(serl_launch_dyn_)(const RolloutArgs &a, const double *cmds, double *states, int T, int grid, hipStream_t stream)
 {

@@ -24,6 +24,7 @@ typedef void SerlLaunchVenvRollout(const RolloutArgs &a, const VenvArgs &v, cons
                                    hipStream_t stream);
 #define SERL_LAUNCHERS(X, v)                                                                                                                     \
   X(SerlLaunch, lane, serl_launch_rollout_##v)              /* one episode per lane (family_lane.hip, rollout_variant.inc) */                   \
+  X(SerlLaunch, laneq, serl_launch_rollout_laneq_##v)       /* ... finished lanes take the next episode from a work queue */                    \
   X(SerlLaunchDyn, dyn_lane, serl_launch_dyn_##v)                                                                                                \
   X(SerlLaunchVenv, venv_reset, serl_launch_venv_reset_##v) /* the step-wise vector env, one lane per env (venv_variant.inc) */                  \
   X(SerlLaunchVenv, venv_step, serl_launch_venv_step_##v)                                                                                        \
@@ -316,8 +317,9 @@ int serl_ctx_create(int device, serl_ctx **out)
     if ((e = getenv("SERL_KERNEL")) != nullptr) {
       const std::string k(e);
       c->env_kernel = k == "team" ? SERL_KERNEL_TEAM : k == "team2" ? SERL_KERNEL_TEAM2 : k == "team4" ? SERL_KERNEL_TEAM4
-                    : k == "wave" ? SERL_KERNEL_WAVE : k == "half" ? SERL_KERNEL_HALF : SERL_KERNEL_AUTO;
+                    : k == "wave" ? SERL_KERNEL_WAVE : k == "half" ? SERL_KERNEL_HALF : k == "laneq" ? SERL_KERNEL_LANEQ : SERL_KERNEL_AUTO;
     }
+    c->env_laneq_waves = (e = getenv("SERL_LANEQ_WAVES")) ? atoi(e) : -1;
     c->env_waves_per_block = (e = getenv("SERL_WAVES_PER_BLOCK")) ? atoi(e) : -1;
     c->env_profile = getenv("SERL_PROFILE") != nullptr;
     c->env_split_actor = (e = getenv("SERL_SPLIT_ACTOR")) ? atoi(e) : 0;
@@ -388,7 +390,7 @@ static int serl_check_desc(serl_ctx *c, const serl_rollout_desc *d, int *hint_ou
     return fail(SERL_E_INVALID, "serl_rollout: env_config must be SERL_ENV_ATTITUDE, SERL_ENV_SYMMETRIC or SERL_ENV_FULL");
   if (d->state_dim != serl_env_state_dim(d->env_config, d->incremental) || d->action_dim != serl_env_action_dim(d->env_config))
     return fail(SERL_E_INVALID, "serl_rollout: state_dim / action_dim do not match the env configuration (attitude 7 / 3, symmetric 2 / 1, full 13 / 3; incremental adds action_dim observations)");
-  if (general_env && d->lanes_per_wave > 0)
+  if (general_env && (d->lanes_per_wave > 0 || serl_resolve_hint(c, d->kernel_hint) == SERL_KERNEL_LANEQ))
     return fail(SERL_E_UNSUPPORTED, "serl_rollout: the lane-per-episode kernels exist for the attitude task only");
   if (d->hidden < 2 || d->hidden > SERL_MAX_HIDDEN || d->num_layers < 0 || d->num_layers > 16)
     return fail(SERL_E_UNSUPPORTED, "serl_rollout: hidden size / layer count out of range");
@@ -398,8 +400,9 @@ static int serl_check_desc(serl_ctx *c, const serl_rollout_desc *d, int *hint_ou
   if (d->weight_stride < serl_param_count(d->state_dim, d->hidden, d->num_layers, d->action_dim))
     return fail(SERL_E_INVALID, "serl_rollout: weight_stride smaller than the parameter count");
   if (d->max_steps <= 0) return fail(SERL_E_INVALID, "serl_rollout: max_steps");
-  if (d->kernel_hint < SERL_KERNEL_AUTO || d->kernel_hint > SERL_KERNEL_TEAM4) return fail(SERL_E_INVALID, "serl_rollout: kernel_hint");
-  const int hint = d->lanes_per_wave > 0 ? SERL_KERNEL_AUTO : serl_resolve_hint(c, d->kernel_hint);
+  if (d->kernel_hint < SERL_KERNEL_AUTO || d->kernel_hint > SERL_KERNEL_LANEQ) return fail(SERL_E_INVALID, "serl_rollout: kernel_hint");
+  // (LANEQ is the one hint lanes_per_wave > 0 does not switch off: there it is the lanes per wavefront of the work-queue kernel)
+  const int hint = (d->lanes_per_wave > 0 && serl_resolve_hint(c, d->kernel_hint) != SERL_KERNEL_LANEQ) ? SERL_KERNEL_AUTO : serl_resolve_hint(c, d->kernel_hint);
   if (d->hidden != 32 && (hint == SERL_KERNEL_TEAM4 || hint == SERL_KERNEL_HALF))
     return fail(SERL_E_UNSUPPORTED, "serl_rollout: kernel_hint TEAM4 / HALF needs hidden = 32 (other shapes: TEAM2, the actor wavefront runs the two episodes one after the other)");
   *hint_out = hint;
@@ -473,6 +476,44 @@ int serl_rollout(serl_ctx *c, const serl_rollout_desc *d, void *stream_)
       HIP_TRY(hipGetLastError());
       serl_note_launch(c, SERL_FAMILY_WAVEX, (d->n_episodes + wpb - 1) / wpb, 1, false, 0, true, 1, s.code);
     }
+    if (timed) HIP_TRY(hipEventRecord(c->ev1, stream));
+    c->timed = timed;
+    return SERL_OK;
+  }
+  if (hint == SERL_KERNEL_LANEQ) {
+    // One episode per lane behind a work queue (rollout_variant.inc serl_rollout_laneq_kernel_<v>): at most W wavefronts -- four per workgroup, one workgroup per
+    // CU, which is what the LDS copy of the tables allows; beside other launches the launch's share of them -- and the episodes beyond their lane slots in the queue.
+    if (!serl_has_lane_kernel(s.code))
+      return fail(SERL_E_UNSUPPORTED, "serl_rollout: kernel_hint LANEQ (lane-per-episode kernels): unknown code variant");
+    lanes = (lanes <= 0 || lanes > 64) ? 64 : lanes;
+    long long W = 4LL * c->num_cus;
+    if (c->env_laneq_waves >= 1 && c->env_laneq_waves < W) W = c->env_laneq_waves;
+    if (d->concurrent_episodes > 0) W = W * d->n_episodes / together;
+    W = W < 1 ? 1 : W;
+    const int need = (d->n_episodes + lanes - 1) / lanes;
+    const int waves = need < W ? need : (int)W;
+    const int wpb = serl_waves_per_block(c, waves);
+    a.lanes = lanes;
+    a.block = 64 * wpb;
+    const int grid = (waves + wpb - 1) / wpb;
+    if (c->env_lane_regroup && d->hidden == 32 && d->state_dim == 7 && d->action_dim == 3 && d->n_members <= (1 << 22)) {      // (rollout_device.h serl_lane_actor_ok)
+      const int rc = serl_regroup_weights(c, d, a, stream);
+      if (rc != SERL_OK) return rc;
+    }
+    // the lane slots are those of `waves` wavefronts (a last workgroup may hold wavefronts beyond them: their lanes find no episode and leave)
+    const long long slots = (long long)waves * lanes;
+    if (d->n_episodes > slots) {
+      a.queue = serl_next_queue_counter(c);
+      a.q0 = (int32_t)slots;
+      HIP_TRY(hipMemsetAsync(a.queue, 0, sizeof(int32_t), stream));
+    } else {
+      a.queue = nullptr; a.q0 = d->n_episodes;
+    }
+    if (timed) HIP_TRY(hipEventRecord(c->ev0, stream));
+    L.laneq(a, grid, stream);
+    HIP_TRY(hipGetLastError());
+    if (a.wt) HIP_TRY(hipEventRecord(c->wt_done[c->wt_slot_of_launch], stream));
+    serl_note_launch(c, SERL_FAMILY_LANE, grid, lanes, a.queue != nullptr, 0, true, 1, s.code);
     if (timed) HIP_TRY(hipEventRecord(c->ev1, stream));
     c->timed = timed;
     return SERL_OK;

@@ -35,6 +35,7 @@ struct serl_ctx {
   int lds_per_block = 65536;            // sharedMemPerBlockOptin
   // environment overrides, read once when the context is made (-1 = not set)
   int env_kernel = 0 /* serl_kernel_hint from SERL_KERNEL */, env_waves_per_block = -1, env_profile = 0;
+  int env_laneq_waves = -1;             // SERL_LANEQ_WAVES: cap on the wavefronts of a SERL_KERNEL_LANEQ launch (default 4 x CUs)
   int env_split_actor = 0;              // SERL_SPLIT_ACTOR=1: streamed actors of one-episode teams (hidden > 64) on TWO actor wavefronts that share the forward pass
                                         // (family_teams2.hip; measured slower than one wavefront with the specialised forward: profiles/r04_experiments.md)
   unsigned env_jitter_sites = ~0u;      // SERL_JITTER_SITES: classes of sites that pause (citation_wave.h; all by default)

@@ -62,7 +62,7 @@ class RolloutEngine:
         self.num_cus = torch.cuda.get_device_properties(self.device).multi_processor_count
         self.multi_launches = 0          # serl_rollout_multi launches made (a mixed sweep as one launch of one code object)
         # serl_rollout_desc.kernel_hint of rollouts that do not name one (None = chosen from the episode count); tests and
-        # A/B measurements set it to compare the kernel families ('team', 'team2', 'team4', 'wave', 'half')
+        # A/B measurements set it to compare the kernel families ('team', 'team2', 'team4', 'wave', 'half', 'laneq')
         self.kernel_hint = None
 
     def close(self):
@@ -266,7 +266,7 @@ def _as_weights(actors, spec):
 def evaluate_pop(actors, *, mode='nominal', num_evals=3, refs=None, t_max=80, smooth_fitness=False,
                  spec: Optional[NetSpec] = None, engine: Optional[RolloutEngine] = None, traces=False,
                  transitions=False, err0=None, tick0=None, lanes_per_wave=0, need_smoothness=True,
-                 sensor_rng=None, concurrent=True, fused='auto') -> PopResult:
+                 sensor_rng=None, concurrent=True, fused='auto', kernel=None) -> PopResult:
     """Evaluate a whole population: `num_evals` episodes per member (agent.py:229-256).
 
     actors : sequence of Actor / GeneticAgent, or a packed f32 tensor [pop, P] (then pass `spec`)
@@ -281,6 +281,11 @@ def evaluate_pop(actors, *, mode='nominal', num_evals=3, refs=None, t_max=80, sm
     tick0  : i32 [pop*num_evals] model clock each episode starts with (None = 0).  The reference's initialize()
              does not reset the model clock, so in its sequential loop episode j of a process starts at
              tick = sum over earlier episodes of (steps + 1); only the time-switched builds (cg-shift, gust) care.
+    lanes_per_wave : 0 = kernels chosen from the episode count; 1..64 = the lane-per-episode kernels with that many episodes per wavefront
+    kernel     : kernel family of every launch ('team', 'team2', 'team4', 'wave', 'half', 'laneq'; None = the engine's kernel_hint, by default chosen
+                 from the episode count).  Results are bit-identical.  'laneq': one episode per lane, and a lane whose episode ends takes the next one
+                 from a work queue (populations whose episodes differ in length: untrained actors crash within seconds); lanes_per_wave is then the
+                 lanes per wavefront (0 = 64), and several builds fly one launch per build, never serl_rollout_multi
     concurrent : False = the per-build launches run one after the other (A/B switch)
     fused      : several builds as ONE launch of one code object (C ABI v7 serl_rollout_multi), its workgroups placed so that CUs which share an
                  instruction cache run the same code variant.  'auto' (default) and True: whenever the library accepts the combination (more than
@@ -352,13 +357,15 @@ def evaluate_pop(actors, *, mode='nominal', num_evals=3, refs=None, t_max=80, sm
                                   (refs if (whole or refs.dim() == 2) else refs[torch.as_tensor(idx)]), build=b,
                                   faults=faults, err0=None if err0 is None else err0[idx],
                                   tick0=None if tick0 is None else tick0[idx], t_max=t_max, sensor_noise=sn, sensor_row=sr,
-                                  traces=want, transitions=transitions, lanes_per_wave=lanes_per_wave, env_config=env_cfg, incremental=incremental, **kw)
+                                  traces=want, transitions=transitions, lanes_per_wave=lanes_per_wave, env_config=env_cfg, incremental=incremental,
+                                  kernel=kernel, **kw)
 
     # Several builds of the attitude task with the LDS-sized actor shape: ONE launch of ONE code object (C ABI v7 serl_rollout_multi,
     # rollout_team4_mixed.hip), which can place its workgroups: two code variants on CUs that share an instruction cache cost 12 %.  The library says
     # whether the combination is eligible; if not, nothing was launched and the launches below run side by side as before.
     use_multi = False
-    if many and (fused is True or (fused == 'auto' and E > 2 * engine.num_cus)) and 2 <= len(groups) <= 4 and lanes_per_wave == 0 and env_cfg == 0 and not incremental and spec.hidden == 32:
+    laneq = (kernel if kernel is not None else engine.kernel_hint) == 'laneq'      # (the library refuses it in serl_rollout_multi: one launch per build)
+    if not laneq and many and (fused is True or (fused == 'auto' and E > 2 * engine.num_cus)) and 2 <= len(groups) <= 4 and lanes_per_wave == 0 and env_cfg == 0 and not incremental and spec.hidden == 32:
         prepared = [(np.asarray(idx), one_build(b, np.asarray(idx), cur, sync=False, launch=False)) for b, idx in groups.items()]
         if engine.rollout_multi([o for _, o in prepared]):
             use_multi = True

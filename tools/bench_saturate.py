@@ -10,7 +10,15 @@ operations per env step, and -- for the first 64 episodes -- whether the results
 Modes: laneN = the lane-per-episode DAG kernels with N episodes per wavefront (lanes_per_wave = N, rollout_variant.inc); auto = what serl_rollout
 chooses (four episodes per team + work queue beyond 4 x CUs episodes); half = two episodes per wavefront.
 Workload: the shipped SERL50 actors tiled with seeded noise to `members`, member = episode mod members, the base reference of
-/root/reference/base/evaluate.py:173-180 shared by all episodes, nominal build, t_max seconds (2 001 env steps at 20 s)."""
+/root/reference/base/evaluate.py:173-180 shared by all episodes, nominal build, t_max seconds (2 001 env steps at 20 s).
+
+    python tools/bench_saturate.py --mixed-lengths [--slots-x 1,2,4] [--reps 5] [--out profiles/lane_queue_timing.json]
+
+The lane work queue (kernel_hint LANEQ) against today's lane family (lanes_per_wave = 64) and the queue launch of four-episode teams on episodes of UNEQUAL
+length: the population of tools/bench_refill.py (512 members, half shipped SERL50 actors, half untrained ones that leave the envelope within seconds), at
+1 x, 2 x and 4 x the resident lane slots (64 x 4 x CUs episodes), and one equal-length control (shipped actors only) at the largest size.  The three kernels
+alternate within every repetition; median, minimum and maximum of the kernel times (HIP events) are reported, env-steps/s = sum of length_steps over the
+median, and the three results are compared with torch.equal in the same run.  One JSON document, with the source hash, to --out."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -28,9 +36,79 @@ ap.add_argument('--activation', default='tanh', help="tanh (the shipped SERL50 a
 ap.add_argument('--order', choices=['interleaved', 'member-major'], default='interleaved',
                 help='interleaved: member = episode mod members (64 different members per wavefront: the worst case for the per-lane actor); member-major: member = episode // (episodes / members), the order evaluate_pop produces (agent.py:234-256: all episodes of a member one after the other)')
 ap.add_argument('--profile', action='store_true', help='with SERL_PROFILE=1 in the environment: cycles per env step wavefront 0 of workgroup 0 spent in the actor / dynamics / env bookkeeping (lane-per-episode kernels)')
+ap.add_argument('--mixed-lengths', action='store_true', help='the lane work queue against the lane family and the team4 queue launch on episodes of unequal length (see above)')
+ap.add_argument('--slots-x', default='1,2,4', help='--mixed-lengths: episode counts as multiples of the resident lane slots, 64 x 4 x CUs')
+ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'lane_queue_timing.json'), help='--mixed-lengths: where the JSON document goes')
 a = ap.parse_args()
 eng = serl_amd.RolloutEngine(0)
 spec = serl_amd.NetSpec(7, 3, 32, 3, a.activation)
+
+
+def mixed_lengths():
+    from serl_amd import build as hip_build
+    KEYS = ('fitness', 'length_steps', 'length_t', 'cost_steps')
+    MODES = (('laneq', dict(kernel='laneq')), ('lane64', dict(lanes_per_wave=64)), ('team4_queue', dict(kernel='team4')))
+    rng = np.random.default_rng(11)      # (tools/bench_refill.py's population)
+    shipped = np.load(os.path.join(ROOT, 'tests', 'golden', 'actors.npz'))['serl50']
+    pop = 512
+    good = shipped[rng.integers(0, 50, pop)].copy()
+    bad = rng.random(pop) < 0.5
+    r = rng.normal(0, 0.3, good.shape).astype(np.float32)
+    for name, off, shape in spec.param_layout():
+        if name.endswith('gamma'):
+            r[:, off:off + shape[0]] = 1.0
+    mixed = good.copy()
+    mixed[bad] = r[bad]
+    ref = refsignals.tabulate(*refsignals.base_reference(a.t_max), a.t_max)
+    slots = 64 * 4 * eng.num_cus
+    mult = [int(x) for x in a.slots_x.split(',')]
+    cases = [('mixed', m, mixed) for m in mult] + [('equal', max(mult), good)]
+    doc = dict(what='lane work queue (LANEQ) against the lane family (lanes_per_wave=64) and the team4 queue launch; nominal build, base reference, t_max %g s; '
+                    'mixed = 512 members, half shipped SERL50 actors, half untrained; equal = shipped actors only' % a.t_max,
+               source_hash=hip_build.source_hash(), device=torch.cuda.get_device_name(0), cus=eng.num_cus, resident_lane_slots=slots, t_max=a.t_max,
+               steps_per_full_episode=int(ref.shape[0]), reps=a.reps, order='the three kernels alternate within a repetition, rotated from one repetition to the next; one warm-up launch each', cases=[])
+    for label, m, wts in cases:
+        E = m * slots
+        moe = ((np.arange(E) % pop) if a.order == 'interleaved' else (np.arange(E) // (E // pop)) % pop).astype(np.int32)
+        wd = torch.from_numpy(wts).to(eng.device)
+        ms = {name: [] for name, _ in MODES}
+        outs, infos = {}, {}
+        for i in range(-1, a.reps):      # (-1: warm-up, not recorded)
+            for j in range(len(MODES)):
+                name, kw = MODES[(j + max(i, 0)) % len(MODES)]
+                out = eng.rollout(wd, spec, moe, ref, t_max=a.t_max, **kw)
+                if i >= 0:
+                    ms[name].append(eng.last_kernel_ms)
+                if name not in outs:
+                    outs[name] = {k: out[k] for k in KEYS}
+                    infos[name] = eng.last_rollout_info()
+                else:
+                    assert all(torch.equal(out[k], outs[name][k]) for k in KEYS), name + ': a repetition changed the results'
+        ls = outs['laneq']['length_steps']
+        steps = int(ls.abs().sum())
+        equal = bool(all(torch.equal(outs[n][k], outs['laneq'][k]) for n, _ in MODES for k in KEYS))
+        case = dict(case=label, slots_x=m, episodes=E, order=a.order, env_steps=steps, full_flights=int((ls == ref.shape[0]).sum()), median_length=int(ls.median()),
+                    results_equal=equal, kernels={})
+        for name, _ in MODES:
+            v = sorted(ms[name])
+            med = float(np.median(v))
+            case['kernels'][name] = dict(family=infos[name]['family'], workgroups=infos[name]['workgroups'], per_wave_or_team=infos[name]['episodes_per_team'],
+                                         work_queue=infos[name]['work_queue'], kernel_ms=[round(x, 2) for x in ms[name]], median_ms=round(med, 2), min_ms=round(v[0], 2),
+                                         max_ms=round(v[-1], 2), env_steps_per_s=steps / (med * 1e-3))
+        case['laneq_over_lane64'] = case['kernels']['lane64']['median_ms'] / case['kernels']['laneq']['median_ms']
+        case['laneq_over_team4_queue'] = case['kernels']['team4_queue']['median_ms'] / case['kernels']['laneq']['median_ms']
+        doc['cases'].append(case)
+        print(json.dumps(case), flush=True)
+        assert equal, 'the three kernels disagree'
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        json.dump(doc, f, indent=1)
+        f.write('\n')
+
+
+if a.mixed_lengths:
+    mixed_lengths()
+    sys.exit(0)
 w = bench.make_population(a.members, 0, tag='serl50').to(eng.device)
 ref = refsignals.tabulate(*refsignals.base_reference(a.t_max), a.t_max)
 T = ref.shape[0]
