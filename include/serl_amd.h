@@ -459,6 +459,26 @@ int serl_venv_noise_fill(serl_ctx *ctx, const serl_venv_noise_desc *nz, int32_t 
  * members are read (state_dim .. member_of_env); refusals as serl_venv_rollout_general's for them, and n_envs < 1.  The step loop of a device-noise
  * env uses it, so that it stays interchangeable with the kernels bit for bit. */
 int serl_venv_actor_forward(serl_ctx *ctx, const serl_venv_rollout_desc *ro, int32_t n_envs, const double *obs, float *actions, void *stream);
+/* The small-batch path of the step-wise env: the same calls with ONE WAVEFRONT PER ENV (csrc/venv_wave.inc) instead of one lane per env.  A lane flies
+ * the whole model evaluation serially, so a lane call lasts one lane env step however few envs there are; here the evaluation's table look-ups and the 19
+ * ODE5 states are spread over the wavefront's lanes (the wave rollout kernels' evaluation), 1 .. 4 wavefronts to a workgroup.  Timings of both families:
+ * profiles/venv_wave_timing.json.  Arguments, semantics, outputs and refusals are those of the namesakes without `_wave` above, bit for bit in every
+ * output.  The descriptors, serl_venv_state_bytes and the state buffer's layout are the same, and every output of a call of either family behind calls of
+ * the other has been equal to an all-lane run's; of the opaque state, eleven i32 words are not those of an all-lane run: the eight interval hints of the lane
+ * evaluation (which verifies a hint before it uses it) and the three words of the table3 interval cache, which the lane step walks from a work word it
+ * does not initialise (csrc/venv_wave.inc).  A wave step leaves all eleven as it finds them, a wave reset stores initialize()'s image of the cache.
+ * serl_amd.CitationVecEnv.rollout therefore does not run the lane rollout kernels on an env that steps through these entry points.  There is no serl_venv_step_wave with `nz`, as there is no serl_venv_step_noise. */
+int serl_venv_reset_wave(serl_ctx *ctx, const serl_venv_desc *desc, const uint8_t *mask, double *obs, void *stream);
+int serl_venv_step_wave(serl_ctx *ctx, const serl_venv_desc *desc, const void *actions, int32_t actions_f64, double *obs,
+                        double *reward, uint8_t *done, double *x, double *ref, double *t, int32_t *cost, void *stream);
+int serl_venv_step_auto_wave(serl_ctx *ctx, const serl_venv_desc *desc, const void *actions, int32_t actions_f64, double *obs,
+                             double *reward, uint8_t *done, double *x, double *ref, double *t, int32_t *cost,
+                             const serl_venv_auto_desc *au, void *stream);
+int serl_venv_reset_wave_noise(serl_ctx *ctx, const serl_venv_desc *desc, const uint8_t *mask, double *obs, const serl_venv_noise_desc *nz,
+                               void *stream);
+int serl_venv_step_auto_wave_noise(serl_ctx *ctx, const serl_venv_desc *desc, const void *actions, int32_t actions_f64, double *obs,
+                                   double *reward, uint8_t *done, double *x, double *ref, double *t, int32_t *cost,
+                                   const serl_venv_auto_desc *au, const serl_venv_noise_desc *nz, void *stream);
 /* the generator's bit-level parts on the host, compiled from the kernels' text (csrc/serl_rng.h) */
 void serl_host_philox(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t out4[4]);
 double serl_host_uniform(uint32_t w0, uint32_t w1);
@@ -491,6 +511,11 @@ enum serl_kernel_family { SERL_FAMILY_NONE = 0, SERL_FAMILY_TEAM = 1 /* eight wa
                           SERL_FAMILY_WAVEX = 11 /* ... other env configurations */, SERL_FAMILY_LANE = 12 /* one lane = one episode */,
                           SERL_FAMILY_TEAMR = 13 /* eight wavefronts = one episode, its streamed actor (two wavefronts) in a workgroup of its own on another CU */ };
 int serl_last_rollout_info(serl_ctx *ctx, int32_t out[8]);
+/* The same for the step-wise env: WHAT the most recent serl_venv_reset* / _step* / _rollout* call of this context launched (a record of its own:
+ * serl_last_rollout_info keeps describing the last serl_rollout).  out[0] enum serl_kernel_family: SERL_FAMILY_LANE (one lane = one env) or
+ * SERL_FAMILY_WAVE (one wavefront = one env, the `_wave` entry points); out[1] workgroups; out[2] wavefronts per workgroup; out[3] enum serl_dyn_code.
+ * Host-side, does not wait for the device.  SERL_E_INVALID before the first env call of the context. */
+int serl_venv_last_info(serl_ctx *ctx, int32_t out[4]);
 
 /* Duration (ms) of the most recent serl_rollout kernel on its stream, measured with HIP events
  * recorded around the launch; blocks until that kernel has finished. */

@@ -17,7 +17,9 @@ EXPORTS = ['serl_abi_version', 'serl_last_error', 'serl_param_count', 'serl_ctx_
            'serl_venv_rollout', 'serl_venv_rollout_layout', 'serl_venv_rollout_general',
            'serl_td3_train', 'serl_td3_work_bytes', 'serl_td3_param_count', 'serl_td3_layout',
            'serl_venv_noise_layout', 'serl_venv_reset_noise', 'serl_venv_step_auto_noise', 'serl_venv_rollout_noise',
-           'serl_venv_rollout_general_noise', 'serl_venv_noise_fill', 'serl_venv_actor_forward', 'serl_host_philox', 'serl_host_uniform']
+           'serl_venv_rollout_general_noise', 'serl_venv_noise_fill', 'serl_venv_actor_forward', 'serl_host_philox', 'serl_host_uniform',
+           'serl_venv_reset_wave', 'serl_venv_step_wave', 'serl_venv_step_auto_wave', 'serl_venv_reset_wave_noise', 'serl_venv_step_auto_wave_noise',
+           'serl_venv_last_info']
 
 
 class BuildDesc(ctypes.Structure):
@@ -193,6 +195,12 @@ def lib():
     L.serl_venv_rollout_general_noise.argtypes = L.serl_venv_rollout_noise.argtypes
     L.serl_venv_noise_fill.argtypes = [VP, NZ, i32, i32, VP, VP, VP, i32, VP, VP]
     L.serl_venv_actor_forward.argtypes = [VP, ctypes.POINTER(VenvRolloutDesc), i32, VP, VP, VP]
+    L.serl_venv_reset_wave.argtypes = L.serl_venv_reset.argtypes
+    L.serl_venv_step_wave.argtypes = L.serl_venv_step.argtypes
+    L.serl_venv_step_auto_wave.argtypes = L.serl_venv_step_auto.argtypes
+    L.serl_venv_reset_wave_noise.argtypes = L.serl_venv_reset_noise.argtypes
+    L.serl_venv_step_auto_wave_noise.argtypes = L.serl_venv_step_auto_noise.argtypes
+    L.serl_venv_last_info.argtypes = [VP, VP]
     L.serl_host_philox.argtypes = [ctypes.c_uint64] + [ctypes.c_uint32] * 4 + [ctypes.POINTER(ctypes.c_uint32)]
     L.serl_host_uniform.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
     L.serl_td3_work_bytes.argtypes = [i32] * 6

@@ -58,6 +58,7 @@ static __device__ __forceinline__ void W_NAME(citw_reset_)(const int wv, CitwSta
   CITW_WAVE_FENCE();
 }
 
+#ifndef SERL_WAVE_STEP_ONLY      // (family_venvw.hip takes the step, initialize() and the staging from here and brings kernels of its own)
 // X = false: the attitude task (7 observations, 3 actions) every BASELINE configuration uses.  X = true: observation set, number
 // of actions and incremental (rate) control from the descriptor (serl_rollout_desc.env_config / incremental;
 // envs/phlabenv.py:84-97,174-176,205-220,377-380) -- a second instantiation, so that the default path stays as it is.
@@ -246,6 +247,8 @@ static __device__ void W_NAME(serl_wave_episode_)(const RolloutArgs &a, const in
   }
 }
 
+#endif  // SERL_WAVE_STEP_ONLY
+
 // stage the build's tables, the table3 parameters and the look-up descriptors into LDS (whole workgroup)
 static __device__ __forceinline__ void W_NAME(citw_stage_)(const RolloutArgs &a)
 {
@@ -269,6 +272,7 @@ static __device__ __forceinline__ void W_NAME(citw_stage_)(const RolloutArgs &a)
   __syncthreads();
 }
 
+#ifndef SERL_WAVE_STEP_ONLY
 __global__ void __launch_bounds__(64 * CITW_MAX_WAVES) W_NAME(serl_rollout_wave_kernel_)(RolloutArgs a)
 {
 #ifdef CITW_PROFILE
@@ -323,6 +327,7 @@ void W_NAME(serl_launch_rollout_wavex_)(const RolloutArgs &a, int grid, hipStrea
 {
   hipLaunchKernelGGL(W_NAME(serl_rollout_wavex_kernel_), dim3(grid), dim3(a.block), 0, stream, a);
 }
+#endif  // SERL_WAVE_STEP_ONLY
 #undef W_NAME
 #undef W_EVAL
 #undef W_PASTE

@@ -85,6 +85,19 @@ struct SerlNzLaunchers { SERL_NZ_LAUNCHERS(SERL_MEMBER, v) };
 SERL_VARIANTS(SERL_NZ_VARIANT_DECL)
 static const SerlNzLaunchers k_nz_launchers[] = {SERL_VARIANTS(SERL_NZ_VARIANT_ROW)};
 
+// the env kernels with one wavefront per env (family_venvw.hip: venv_wave.inc, plain and under SERL_VENV_NOISE), one record per code variant as above
+#define SERL_VW_LAUNCHERS(X, v)                                                       \
+  X(SerlLaunchVenv, reset, serl_launch_venv_reset_wave_##v)                           \
+  X(SerlLaunchVenv, step, serl_launch_venv_step_wave_##v)                             \
+  X(SerlLaunchVenvAuto, step_auto, serl_launch_venv_step_auto_wave_##v)               \
+  X(SerlLaunchVenvNz, reset_nz, serl_launch_venv_reset_wave_noise_##v)                \
+  X(SerlLaunchVenvAutoNz, step_auto_nz, serl_launch_venv_step_auto_wave_noise_##v)
+struct SerlVwLaunchers { SERL_VW_LAUNCHERS(SERL_MEMBER, v) };
+#define SERL_VW_VARIANT_DECL(v, code) SERL_VW_LAUNCHERS(SERL_DECL, v)
+#define SERL_VW_VARIANT_ROW(v, code) {SERL_VW_LAUNCHERS(SERL_INIT, v)},
+SERL_VARIANTS(SERL_VW_VARIANT_DECL)
+static const SerlVwLaunchers k_vw_launchers[] = {SERL_VARIANTS(SERL_VW_VARIANT_ROW)};
+
 #include "serl_mixed.h"
 
 static void serl_launch_rollout_teamg(const SerlLaunchers &L, int groups, const RolloutArgs &a, int grid, hipStream_t stream)
@@ -864,10 +877,16 @@ static int serl_venv_check(serl_ctx *c, const serl_venv_desc *d, const char *wha
   return SERL_OK;
 }
 
+// serl_venv_last_info's record of an env call (include/serl_amd.h)
+static void serl_note_venv_launch(serl_ctx *c, int family, int grid, int waves_per_block, int code)
+{
+  c->last_venv_info[0] = family; c->last_venv_info[1] = grid; c->last_venv_info[2] = waves_per_block; c->last_venv_info[3] = code;
+}
+
 // the launch shape of serl_dyn_open_loop's lane kernels: lanes per wavefront from the batch, so that small batches still spread over the CUs
 static int serl_venv_launch(serl_ctx *c, const serl_venv_desc *d, bool step, VenvArgs &v, hipStream_t stream,
                             const serl_venv_auto_desc *au = nullptr, const serl_venv_rollout_desc *rd = nullptr, bool general = false,
-                            const serl_venv_noise_desc *nz = nullptr)
+                            const serl_venv_noise_desc *nz = nullptr, bool wave = false)
 {
   const BuildSlot &s = c->slots[d->build_slot];
   const SerlLaunchers &L = serl_launchers(s.code);
@@ -876,6 +895,24 @@ static int serl_venv_launch(serl_ctx *c, const serl_venv_desc *d, bool step, Ven
   a.d.n_episodes = d->n_envs;
   a.ro = s.blob; a.t3 = s.blob + s.n_ro; a.x0 = a.t3 + 46; a.dw0 = a.x0 + 19;
   a.dyn_dt = s.dt;
+  if (wave) {      // one wavefront per env (venv_wave.inc), the launch shape of the wave rollout kernels: the CUs fill before the workgroups do
+    const SerlVwLaunchers &W = k_vw_launchers[s.code];
+    int wpb = serl_wave_kernel_waves_per_block(c, d->n_envs);
+    if (wpb > 4) wpb = 4;
+    a.lanes = 1;
+    a.block = 64 * wpb;
+    const int grid = (d->n_envs + wpb - 1) / wpb;
+    v.d = *d;
+    v.npad = serl_venv_npad(d->n_envs);
+    if (nz) {
+      if (au) W.step_auto_nz(a, v, *au, *nz, grid, stream);
+      else W.reset_nz(a, v, *nz, grid, stream);
+    } else if (au) W.step_auto(a, v, *au, grid, stream);
+    else (step ? W.step : W.reset)(a, v, grid, stream);
+    HIP_TRY(hipGetLastError());
+    serl_note_venv_launch(c, SERL_FAMILY_WAVE, grid, wpb, s.code);
+    return SERL_OK;
+  }
   int lanes = (d->n_envs + 255) / 256;
   if (lanes > 64) lanes = 64;
   a.lanes = lanes;
@@ -899,19 +936,31 @@ static int serl_venv_launch(serl_ctx *c, const serl_venv_desc *d, bool step, Ven
   } else if (au) L.venv_step_auto(a, v, *au, grid, stream);
   else (step ? L.venv_step : L.venv_reset)(a, v, grid, stream);
   HIP_TRY(hipGetLastError());
+  serl_note_venv_launch(c, SERL_FAMILY_LANE, grid, wpb, s.code);
   return SERL_OK;
 }
 
-int serl_venv_reset(serl_ctx *c, const serl_venv_desc *d, const uint8_t *mask, double *obs, void *stream_)
+static int serl_venv_reset_impl(const char *w, serl_ctx *c, const serl_venv_desc *d, const uint8_t *mask, double *obs, const serl_venv_noise_desc *nz,
+                               void *stream_, bool wave)
 {
-  { const int rc_ = serl_venv_check(c, d, "serl_venv_reset"); if (rc_ != SERL_OK) return rc_; }
-  if (!obs) return fail(SERL_E_INVALID, "serl_venv_reset: obs is NULL");
+  { const int rc_ = serl_venv_check(c, d, w); if (rc_ != SERL_OK) return rc_; }
+  if (!obs) return fail(SERL_E_INVALID, std::string(w) + ": obs is NULL");
   HIP_TRY(hipSetDevice(c->device));
   VenvArgs v;
   memset(&v, 0, sizeof(v));
   v.mask = mask;
   v.obs = obs;
-  return serl_venv_launch(c, d, false, v, (hipStream_t)stream_);
+  return serl_venv_launch(c, d, false, v, (hipStream_t)stream_, nullptr, nullptr, false, nz, wave);
+}
+
+int serl_venv_reset(serl_ctx *c, const serl_venv_desc *d, const uint8_t *mask, double *obs, void *stream_)
+{
+  return serl_venv_reset_impl("serl_venv_reset", c, d, mask, obs, nullptr, stream_, false);
+}
+
+int serl_venv_reset_wave(serl_ctx *c, const serl_venv_desc *d, const uint8_t *mask, double *obs, void *stream_)
+{
+  return serl_venv_reset_impl("serl_venv_reset_wave", c, d, mask, obs, nullptr, stream_, true);
 }
 
 // what the serl_venv_*_noise entries refuse in `nz` (none of these checks reads the context)
@@ -940,28 +989,39 @@ int serl_venv_noise_layout(int32_t *out, int32_t capacity)
 int serl_venv_reset_noise(serl_ctx *c, const serl_venv_desc *d, const uint8_t *mask, double *obs, const serl_venv_noise_desc *nz, void *stream_)
 {
   { const int rc_ = serl_venv_noise_check("serl_venv_reset_noise", d, nullptr, nz); if (rc_ != SERL_OK) return rc_; }
-  { const int rc_ = serl_venv_check(c, d, "serl_venv_reset_noise"); if (rc_ != SERL_OK) return rc_; }
-  if (!obs) return fail(SERL_E_INVALID, "serl_venv_reset_noise: obs is NULL");
-  HIP_TRY(hipSetDevice(c->device));
-  VenvArgs v;
-  memset(&v, 0, sizeof(v));
-  v.mask = mask;
-  v.obs = obs;
-  return serl_venv_launch(c, d, false, v, (hipStream_t)stream_, nullptr, nullptr, false, nz);
+  return serl_venv_reset_impl("serl_venv_reset_noise", c, d, mask, obs, nz, stream_, false);
 }
 
-int serl_venv_step(serl_ctx *c, const serl_venv_desc *d, const void *actions, int32_t actions_f64, double *obs,
-                   double *reward, uint8_t *done, double *x, double *ref, double *t, int32_t *cost, void *stream_)
+int serl_venv_reset_wave_noise(serl_ctx *c, const serl_venv_desc *d, const uint8_t *mask, double *obs, const serl_venv_noise_desc *nz, void *stream_)
 {
-  { const int rc_ = serl_venv_check(c, d, "serl_venv_step"); if (rc_ != SERL_OK) return rc_; }
-  if (!actions || !obs || !reward || !done) return fail(SERL_E_INVALID, "serl_venv_step: actions / obs / reward / done is NULL");
-  if (actions_f64 != 0 && actions_f64 != 1) return fail(SERL_E_INVALID, "serl_venv_step: actions_f64 must be 0 (f32) or 1 (f64)");
+  { const int rc_ = serl_venv_noise_check("serl_venv_reset_wave_noise", d, nullptr, nz); if (rc_ != SERL_OK) return rc_; }
+  return serl_venv_reset_impl("serl_venv_reset_wave_noise", c, d, mask, obs, nz, stream_, true);
+}
+
+static int serl_venv_step_impl(const char *w, serl_ctx *c, const serl_venv_desc *d, const void *actions, int32_t actions_f64, double *obs,
+                              double *reward, uint8_t *done, double *x, double *ref, double *t, int32_t *cost, void *stream_, bool wave)
+{
+  { const int rc_ = serl_venv_check(c, d, w); if (rc_ != SERL_OK) return rc_; }
+  if (!actions || !obs || !reward || !done) return fail(SERL_E_INVALID, std::string(w) + ": actions / obs / reward / done is NULL");
+  if (actions_f64 != 0 && actions_f64 != 1) return fail(SERL_E_INVALID, std::string(w) + ": actions_f64 must be 0 (f32) or 1 (f64)");
   HIP_TRY(hipSetDevice(c->device));
   VenvArgs v;
   memset(&v, 0, sizeof(v));
   v.actions = actions; v.actions_f64 = actions_f64;
   v.obs = obs; v.reward = reward; v.done = done; v.x = x; v.ref = ref; v.t = t; v.cost = cost;
-  return serl_venv_launch(c, d, true, v, (hipStream_t)stream_);
+  return serl_venv_launch(c, d, true, v, (hipStream_t)stream_, nullptr, nullptr, false, nullptr, wave);
+}
+
+int serl_venv_step(serl_ctx *c, const serl_venv_desc *d, const void *actions, int32_t actions_f64, double *obs,
+                   double *reward, uint8_t *done, double *x, double *ref, double *t, int32_t *cost, void *stream_)
+{
+  return serl_venv_step_impl("serl_venv_step", c, d, actions, actions_f64, obs, reward, done, x, ref, t, cost, stream_, false);
+}
+
+int serl_venv_step_wave(serl_ctx *c, const serl_venv_desc *d, const void *actions, int32_t actions_f64, double *obs,
+                        double *reward, uint8_t *done, double *x, double *ref, double *t, int32_t *cost, void *stream_)
+{
+  return serl_venv_step_impl("serl_venv_step_wave", c, d, actions, actions_f64, obs, reward, done, x, ref, t, cost, stream_, true);
 }
 
 int serl_venv_auto_layout(int32_t *out, int32_t capacity)
@@ -977,7 +1037,7 @@ int serl_venv_auto_layout(int32_t *out, int32_t capacity)
 
 static int serl_venv_step_auto_impl(const char *w, serl_ctx *c, const serl_venv_desc *d, const void *actions, int32_t actions_f64, double *obs,
                                     double *reward, uint8_t *done, double *x, double *ref, double *t, int32_t *cost,
-                                    const serl_venv_auto_desc *au, const serl_venv_noise_desc *nz, void *stream_)
+                                    const serl_venv_auto_desc *au, const serl_venv_noise_desc *nz, void *stream_, bool wave = false)
 {
   if (!c || !d || !au) return fail(SERL_E_INVALID, std::string(w) + ": NULL argument");
   if (au->ref_pool && d->ref) return fail(SERL_E_INVALID, std::string(w) + ": ref_pool together with desc->ref");
@@ -994,7 +1054,7 @@ static int serl_venv_step_auto_impl(const char *w, serl_ctx *c, const serl_venv_
   memset(&v, 0, sizeof(v));
   v.actions = actions; v.actions_f64 = actions_f64;
   v.obs = obs; v.reward = reward; v.done = done; v.x = x; v.ref = ref; v.t = t; v.cost = cost;
-  return serl_venv_launch(c, &dd, true, v, (hipStream_t)stream_, au, nullptr, false, nz);
+  return serl_venv_launch(c, &dd, true, v, (hipStream_t)stream_, au, nullptr, false, nz, wave);
 }
 
 int serl_venv_step_auto(serl_ctx *c, const serl_venv_desc *d, const void *actions, int32_t actions_f64, double *obs,
@@ -1010,6 +1070,29 @@ int serl_venv_step_auto_noise(serl_ctx *c, const serl_venv_desc *d, const void *
 {
   { const int rc_ = serl_venv_noise_check("serl_venv_step_auto_noise", d, nullptr, nz); if (rc_ != SERL_OK) return rc_; }
   return serl_venv_step_auto_impl("serl_venv_step_auto_noise", c, d, actions, actions_f64, obs, reward, done, x, ref, t, cost, au, nz, stream_);
+}
+
+int serl_venv_step_auto_wave(serl_ctx *c, const serl_venv_desc *d, const void *actions, int32_t actions_f64, double *obs,
+                             double *reward, uint8_t *done, double *x, double *ref, double *t, int32_t *cost,
+                             const serl_venv_auto_desc *au, void *stream_)
+{
+  return serl_venv_step_auto_impl("serl_venv_step_auto_wave", c, d, actions, actions_f64, obs, reward, done, x, ref, t, cost, au, nullptr, stream_, true);
+}
+
+int serl_venv_step_auto_wave_noise(serl_ctx *c, const serl_venv_desc *d, const void *actions, int32_t actions_f64, double *obs,
+                                   double *reward, uint8_t *done, double *x, double *ref, double *t, int32_t *cost,
+                                   const serl_venv_auto_desc *au, const serl_venv_noise_desc *nz, void *stream_)
+{
+  { const int rc_ = serl_venv_noise_check("serl_venv_step_auto_wave_noise", d, nullptr, nz); if (rc_ != SERL_OK) return rc_; }
+  return serl_venv_step_auto_impl("serl_venv_step_auto_wave_noise", c, d, actions, actions_f64, obs, reward, done, x, ref, t, cost, au, nz, stream_, true);
+}
+
+int serl_venv_last_info(serl_ctx *c, int32_t out[4])
+{
+  if (!c || !out) return fail(SERL_E_INVALID, "serl_venv_last_info: NULL argument");
+  if (c->last_venv_info[0] == SERL_FAMILY_NONE) return fail(SERL_E_INVALID, "serl_venv_last_info: no env call recorded");
+  for (int i = 0; i < 4; ++i) out[i] = c->last_venv_info[i];
+  return SERL_OK;
 }
 
 int serl_venv_rollout_layout(int32_t *out, int32_t capacity)

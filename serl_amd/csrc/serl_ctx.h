@@ -59,5 +59,6 @@ struct serl_ctx {
   int wt_next = 0;
   hipEvent_t wt_done[SERL_WT_SLOTS] = {};      // recorded behind the launch that reads a copy: the next launch to take the slot waits for it on ITS stream (no host wait)
   int wt_slot_of_launch = -1;
+  int32_t last_venv_info[4] = {};       // serl_venv_last_info: what the most recent step-wise env call launched (family, workgroups, wavefronts per workgroup, code)
   int32_t last_info[8] = {};            // serl_last_rollout_info: what the most recent rollout call launched (family, workgroups, episodes per team, queue, actor wavefronts, streamed, launches, code)
 };

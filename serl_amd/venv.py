@@ -42,6 +42,10 @@ up to 16 hidden layers, any activation -- on every env configuration in one laun
 serl_venv_*_noise): no table, no host draw, a fresh realisation for every episode of every env, reproducible from `env.noise_seed` and
 `env.noise_episode`; `rollout(..., action_noise='device', noise_sd=, noise_clip=)` draws the exploration noise the same way.  `venv_noise`
 writes any episode's draws out as a table.
+
+`kernel='wave'` (serl_venv_*_wave) runs `reset` / `step` with one wavefront per env instead of one lane per env: the small-batch path, for one
+to a few hundred envs, where a lane call is pure latency.  Same results bit for bit in every output, same state buffer layout; `rollout()` refuses on such an env (the lane
+kernels' table3 interval cache is the one state field the wave kernels cannot reproduce).  `kernel='auto'` takes the wave path up to WAVE_MAX_ENVS envs; `env.last_step_kernel` says what the last call launched.
 """
 import ctypes
 import numpy as np
@@ -49,6 +53,14 @@ import torch
 
 from . import _capi, builds, refsignals
 from .actor import Actor, pad_rows, spec_of, unpack_into
+
+
+# kernel='auto': the wave kernels (one wavefront per env) up to this many envs, the lane kernels beyond.  The largest measured n_envs at which the wave path
+# beats the lane path by more than the lane runs' own spread, both with no env and with 3 % of the envs finishing per step, in
+# profiles/venv_wave_timing.json (tools/bench_venv.py --kernel lane,wave; its `wave_max_envs`): 3x - 4x up to 1 024 envs, 2 - 7 % at 4 096, a loss of 13x at
+# 65 536.  0 would mean never.
+WAVE_MAX_ENVS = 4096
+KERNELS = ('lane', 'wave', 'auto')
 
 
 class CitationVecEnv:
@@ -72,7 +84,9 @@ class CitationVecEnv:
                   'episode_return' f64 [N] and 'episode_length' i32 [N] (the last two valid where done).  The sensor-noise tables given
                   or drawn at the explicit reset are reused by the restarted episodes.
     ref_pool      auto_reset with refs=None: training references drawn per env by every explicit reset; the episode the reset starts
-                  flies row 0, the j-th restart after it row j % ref_pool (the pool recycles after ref_pool episodes)."""
+                  flies row 0, the j-th restart after it row j % ref_pool (the pool recycles after ref_pool episodes).
+    kernel        'lane' (default): one lane per env; 'wave': one wavefront per env for reset / step (small batches); 'auto': 'wave' up to
+                  WAVE_MAX_ENVS envs.  Every output is the same bit for bit; rollout() raises a ValueError on an env that steps on the wave kernels."""
 
     # device noise (serl_venv_noise_desc): the seed, the per-env count of episode starts, whether the sensor noise comes from the generator
     noise_seed = None
@@ -80,7 +94,9 @@ class CitationVecEnv:
     _dev_sensor = False
 
     def __init__(self, n_envs, mode='PHlab_attitude_nominal', t_max=20, refs=None, sensor_noise=None, engine=None, auto_reset=False,
-                 ref_pool=4, seed=None):
+                 ref_pool=4, seed=None, kernel='lane'):
+        if kernel not in KERNELS:
+            raise ValueError("kernel: one of 'lane', 'wave', 'auto', not %r" % (kernel,))
         if isinstance(refs, np.ndarray) and refs.dtype.names:
             refsignals.check_specs(refs)      # (widths > 0, non-decreasing times: before any device work)
         dev_sensor = isinstance(sensor_noise, str)
@@ -101,6 +117,8 @@ class CitationVecEnv:
         self.n_envs = int(n_envs)
         if self.n_envs < 1:
             raise ValueError('n_envs must be >= 1')
+        self.kernel = kernel
+        self._wave = kernel == 'wave' or (kernel == 'auto' and self.n_envs <= WAVE_MAX_ENVS)
         self.mode, self.t_max = mode, float(t_max)
         self.auto_reset, self.ref_pool = bool(auto_reset), int(ref_pool)
         if self.auto_reset and self.ref_pool < 1:
@@ -202,6 +220,18 @@ class CitationVecEnv:
     def _spec_tensor(self, specs):
         return torch.from_numpy(np.ascontiguousarray(specs).view(np.uint8).reshape(len(specs), -1)).to(self.device)
 
+    # 'lane' or 'wave': the kernel family the library said it launched for THIS env's most recent reset / step (serl_venv_last_info, read right
+    # behind the call: the library's record is per context, which other envs share); None before the first one
+    last_step_kernel = None
+
+    def _call(self, name, noise, *args):
+        """the entry point `name` of this env's kernel family (`_wave`) and noise flavour on (ctx, *args); notes what the library launched"""
+        name += ('_wave' if self._wave else '') + ('_noise' if noise else '')
+        _capi.check(getattr(self.lib, name)(self.engine.ctx, *args), name)
+        info = (ctypes.c_int32 * 4)()
+        _capi.check(self.lib.serl_venv_last_info(self.engine.ctx, info), 'serl_venv_last_info')
+        self.last_step_kernel = _capi.FAMILIES[int(info[0])]
+
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
@@ -267,11 +297,10 @@ class CitationVecEnv:
             d.tick0 = t0.data_ptr(); keep.append(t0)
         if self.noise_episode is not None:
             nz = self._nz_desc()
-            _capi.check(self.lib.serl_venv_reset_noise(self.engine.ctx, ctypes.byref(d), None if m is None else m.data_ptr(),
-                                                       self._obs.data_ptr(), ctypes.byref(nz), self._stream()), 'serl_venv_reset_noise')
+            self._call('serl_venv_reset', True, ctypes.byref(d), None if m is None else m.data_ptr(), self._obs.data_ptr(), ctypes.byref(nz),
+                       self._stream())
         else:
-            _capi.check(self.lib.serl_venv_reset(self.engine.ctx, ctypes.byref(d), None if m is None else m.data_ptr(),
-                                                 self._obs.data_ptr(), self._stream()), 'serl_venv_reset')
+            self._call('serl_venv_reset', False, ctypes.byref(d), None if m is None else m.data_ptr(), self._obs.data_ptr(), self._stream())
         del keep      # (freed memory is handed out again only to work ordered behind this launch on the same stream)
         return self._obs
 
@@ -288,23 +317,21 @@ class CitationVecEnv:
         if self.auto_reset:
             if self.noise_episode is not None:
                 nz = self._nz_desc()
-                _capi.check(self.lib.serl_venv_step_auto_noise(self.engine.ctx, ctypes.byref(self.desc), a.data_ptr(), int(a.dtype == torch.float64),
-                                                               self._obs.data_ptr(), self._reward.data_ptr(), self._done.data_ptr(),
-                                                               self._x.data_ptr(), self._refk.data_ptr(), self._t.data_ptr(), self._cost.data_ptr(),
-                                                               ctypes.byref(self.auto_desc), ctypes.byref(nz), self._stream()),
-                            'serl_venv_step_auto_noise')
+                self._call('serl_venv_step_auto', True, ctypes.byref(self.desc), a.data_ptr(), int(a.dtype == torch.float64),
+                           self._obs.data_ptr(), self._reward.data_ptr(), self._done.data_ptr(),
+                           self._x.data_ptr(), self._refk.data_ptr(), self._t.data_ptr(), self._cost.data_ptr(),
+                           ctypes.byref(self.auto_desc), ctypes.byref(nz), self._stream())
             else:
-                _capi.check(self.lib.serl_venv_step_auto(self.engine.ctx, ctypes.byref(self.desc), a.data_ptr(), int(a.dtype == torch.float64),
-                                                         self._obs.data_ptr(), self._reward.data_ptr(), self._done.data_ptr(), self._x.data_ptr(),
-                                                         self._refk.data_ptr(), self._t.data_ptr(), self._cost.data_ptr(),
-                                                         ctypes.byref(self.auto_desc), self._stream()), 'serl_venv_step_auto')
+                self._call('serl_venv_step_auto', False, ctypes.byref(self.desc), a.data_ptr(), int(a.dtype == torch.float64),
+                           self._obs.data_ptr(), self._reward.data_ptr(), self._done.data_ptr(), self._x.data_ptr(),
+                           self._refk.data_ptr(), self._t.data_ptr(), self._cost.data_ptr(),
+                           ctypes.byref(self.auto_desc), self._stream())
             return self._obs, self._reward, self._done, {'x': self._x, 'ref': self._refk, 't': self._t, 'cost': self._cost,
                                                          'final_obs': self._final_obs, 'episode_return': self._ep_return,
                                                          'episode_length': self._ep_length}
-        _capi.check(self.lib.serl_venv_step(self.engine.ctx, ctypes.byref(self.desc), a.data_ptr(), int(a.dtype == torch.float64),
-                                            self._obs.data_ptr(), self._reward.data_ptr(), self._done.data_ptr(), self._x.data_ptr(),
-                                            self._refk.data_ptr(), self._t.data_ptr(), self._cost.data_ptr(), self._stream()),
-                    'serl_venv_step')
+        self._call('serl_venv_step', False, ctypes.byref(self.desc), a.data_ptr(), int(a.dtype == torch.float64),
+                   self._obs.data_ptr(), self._reward.data_ptr(), self._done.data_ptr(), self._x.data_ptr(),
+                   self._refk.data_ptr(), self._t.data_ptr(), self._cost.data_ptr(), self._stream())
         return self._obs, self._reward, self._done, {'x': self._x, 'ref': self._refk, 't': self._t, 'cost': self._cost}
 
     # ---- K policy-driven steps in one launch (serl_venv_rollout) ------------------------------------------------------------------
@@ -412,6 +439,12 @@ class CitationVecEnv:
         if path == 'loop' or (path == 'auto' and not lane32):
             self.last_rollout_path = 'loop'
             return self._rollout_loop(policy, mods, spec, K, moe, noise, transitions, info, nz if dev_action else None)
+        if self._wave:
+            # The lane step walks the table3 S-function's interval cache (IW[0..2] of the state) from a work word it never initialises, so what a
+            # lane call leaves there depends on the compiled kernel and the wave calls cannot reproduce it (they leave the words alone).  No output
+            # has been seen to depend on it, but the lane rollout kernels are not handed a state they did not write.
+            raise ValueError("rollout in a kernel: this env steps on the wave kernels (kernel=%r), whose state the lane rollout kernels do not take over; "
+                             "make the env with kernel='lane', or take path='loop'" % (self.kernel,))
         w = self._packed_rows(policy, mods)
         out = self._rollout_buffers(K, transitions, info)
         rd = _capi.VenvRolloutDesc(state_dim=spec.state_dim, action_dim=spec.action_dim, hidden=spec.hidden, num_layers=spec.num_layers,

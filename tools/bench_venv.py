@@ -35,7 +35,16 @@ runs the device-noise leg: mode 'noise', episodes of 64 steps on a shared table 
 (serl_venv_*_noise: the sensor noise drawn inside the kernels) against the table path (a pre-drawn f64 [N, 65, 7] table, 238 MB at 65 536 envs) --
 `step` under auto-reset with a fixed action, and `rollout(actor, K)` with the SERL50 actor, there also with action_noise='device' against a
 pre-drawn [K, N, 3] tensor; medians and [min .. max] of `reps` repetitions after a warm-up, the versions alternating.  Then the wall time and
-the bytes of noise tables of one full `reset()` at --reset-n envs with t_max = 20 on both paths (--reset-n 0 skips it)."""
+the bytes of noise tables of one full `reset()` at --reset-n envs with t_max = 20 on both paths (--reset-n 0 skips it).
+
+    python tools/bench_venv.py --kernel lane,wave [--sizes 1,16,64,256,1024,4096,65536] [--auto-steps 1000] [--reps 5] [--out profiles/venv_wave_timing.json]
+runs the kernel-family leg: CitationVecEnv(kernel='lane') (one lane per env) against kernel='wave' (one wavefront per env, serl_venv_*_wave) in the loops
+of the auto-reset leg, a fixed action, medians and [min .. max] of `reps` repetitions after a warm-up, the versions alternating --
+    step            the plain `step`, no env finishing (the auto-reset leg's `idle`, manual version)
+    auto_idle       `step` with auto_reset=True, no env finishing (its `idle`, auto version)
+    auto_staggered  `step` with auto_reset=True, episodes of 32 steps at spread phases: 3 % of the envs finish per step (its `staggered`, auto version)
+-- and derives the env count up to which kernel='auto' should take the wave path: the largest measured N at which the wave median is below the lane
+median by more than the lane repetitions' own spread (max - min) in auto_idle and in auto_staggered.  `--kernel lane` or `--kernel wave` measures one."""
 import argparse, json, os, subprocess, sys
 import numpy as np
 import torch
@@ -168,6 +177,49 @@ def bench_auto(eng, N, steps, warmup, reps, drawn_steps, drawn_max_n):
     assert steps + warmup < len(full)
     compare('idle', lambda auto: serl_amd.CitationVecEnv(N, mode='nominal', t_max=20, refs=full, engine=eng, auto_reset=auto), steps, 0, False)
     return out
+
+
+def bench_kernels(eng, N, steps, warmup, reps, kernels):
+    """One size: the kernel families of `kernels` in the three loops of the module docstring.  Every env is live in every timed step."""
+    dev = eng.device
+    fixed = torch.zeros(N, 3, dtype=torch.float32, device=dev)
+    L = 32
+    full = rs.tabulate(*rs.base_reference(20), 20)
+    table = np.ascontiguousarray(full[:L])
+    assert steps + warmup < len(full)
+    out = dict(N=N, steps=steps, reps=reps, warmup=warmup)
+    for name, refs, auto, stagger_L in (('step', full, False, 0), ('auto_idle', full, True, 0), ('auto_staggered', table, True, L)):
+        envs = {k: serl_amd.CitationVecEnv(N, mode='nominal', t_max=20, refs=refs, engine=eng, auto_reset=auto, kernel=k) for k in kernels}
+        ms, fin, ran = {k: [] for k in envs}, {}, {}
+        with torch.no_grad():
+            for k, env in envs.items():
+                if stagger_L:
+                    _stagger(env, stagger_L, fixed)
+                else:
+                    env.reset()
+                _timed(env, warmup, fixed, False)
+                ran[k] = env.last_step_kernel
+            for r in range(reps):
+                for k, env in (list(envs.items()) if r % 2 == 0 else list(envs.items())[::-1]):      # alternate the order
+                    if not stagger_L:
+                        env.reset()      # every repetition from a fresh episode, so that no env finishes
+                    m, fin[k] = _timed(env, steps, fixed, False)
+                    ms[k].append(m)
+        out[name] = {k: _summary(N, steps, ms[k]) for k in envs}
+        out[name].update(launched=ran, finished_on_last_step=fin)
+        if len(envs) == 2:
+            a, b = (out[name][k]['us_per_step'] for k in ('lane', 'wave'))
+            out[name]['wave_over_lane_us_per_step'] = round(b['median'] / a['median'], 4)
+            out[name]['wave_wins_beyond_lane_spread'] = bool(a['median'] - b['median'] > a['max'] - a['min'])
+        del envs
+    return out
+
+
+def wave_max_envs(results):
+    """the largest measured N at which the wave path beats the lane path by more than the lane runs' own spread, both with no env and with 3 % of the envs
+    finishing per step; 0 if there is none"""
+    wins = [r['N'] for r in results if all(r[c].get('wave_wins_beyond_lane_spread') for c in ('auto_idle', 'auto_staggered'))]
+    return max(wins) if wins else 0
 
 
 def seeded_policy(device, hidden, layers):
@@ -353,6 +405,7 @@ def main():
     ap.add_argument('--path', default='fused', choices=['auto', 'fused', 'loop'], help="--rollout --hidden: rollout(path=...) of the version compared with 'loop'")
     ap.add_argument('--device-noise', action='store_true', help='the device-noise leg instead of the others')
     ap.add_argument('--reset-n', type=int, default=65536, help='--device-noise: envs of the full-reset measurement at t_max = 20 (0: skip)')
+    ap.add_argument('--kernel', default=None, help="the kernel-family leg instead of the others: 'lane,wave' (the comparison), 'lane' or 'wave'")
     ap.add_argument('--out', default=None, help='default: profiles/venv_auto_timing.json (--auto-reset), profiles/venv_rollout_timing.json (--rollout), '
                                                 'profiles/venv_rollout_general_timing.json (--rollout --hidden)')
     args = ap.parse_args()
@@ -360,6 +413,25 @@ def main():
         args.out = os.path.join(ROOT, 'profiles', ('venv_rollout_general_timing.json' if args.hidden else 'venv_rollout_timing.json') if args.rollout
                                 else 'venv_auto_timing.json')
     eng = serl_amd.RolloutEngine(0)
+    if args.kernel is not None:
+        kernels = args.kernel.split(',')
+        if not kernels or any(k not in ('lane', 'wave') for k in kernels) or len(set(kernels)) != len(kernels):
+            ap.error("--kernel: 'lane', 'wave' or 'lane,wave'")
+        if args.out.endswith('venv_auto_timing.json'):
+            args.out = os.path.join(ROOT, 'profiles', 'venv_wave_timing.json')
+        sizes = [int(s) for s in (args.sizes if args.sizes != ap.get_default('sizes') else '1,16,64,256,1024,4096,65536').split(',')]
+        res = dict(tool='bench_venv --kernel %s' % args.kernel, device=torch.cuda.get_device_name(0), source_hash=hip_build.source_hash(),
+                   results=[bench_kernels(eng, N, args.auto_steps, args.warmup, args.reps, kernels) for N in sizes])
+        if len(kernels) == 2:
+            res['wave_max_envs'] = wave_max_envs(res['results'])
+        kernels_rep = kernel_report('rollout_venvw_%s.o')      # (needs the build's objects: empty where only the library was shipped)
+        if kernels_rep:
+            res['kernels'] = kernels_rep
+        with open(args.out, 'w') as f:
+            json.dump(res, f, indent=1)
+            f.write('\n')
+        print(json.dumps(res))
+        return
     if args.device_noise:
         if args.out.endswith('venv_auto_timing.json'):
             args.out = os.path.join(ROOT, 'profiles', 'venv_device_noise_timing.json')
