@@ -479,6 +479,17 @@ int serl_venv_reset_wave_noise(serl_ctx *ctx, const serl_venv_desc *desc, const 
 int serl_venv_step_auto_wave_noise(serl_ctx *ctx, const serl_venv_desc *desc, const void *actions, int32_t actions_f64, double *obs,
                                    double *reward, uint8_t *done, double *x, double *ref, double *t, int32_t *cost,
                                    const serl_venv_auto_desc *au, const serl_venv_noise_desc *nz, void *stream);
+/* serl_venv_rollout_general / _general_noise with ONE WAVEFRONT PER ENV (csrc/venv_wave_rollout.inc): K policy-driven steps in one launch on the kernels of
+ * the small-batch path.  The env's state and run state are loaded once and stored once, the tables are staged once, and the actor is the wave-cooperative
+ * forward of the fused wave kernels (one hidden row per lane).  Arguments, descriptors (no member added), semantics, every output row and the refusals
+ * before any launch are those of the namesakes without `_wave`, bit for bit; the state buffer is left as the same steps of serl_venv_step_auto_wave
+ * leave it (the eleven opaque words above included: a restart inside the segment stores initialize()'s image of the table3 cache, nothing else touches
+ * them), so these calls may follow and be followed by any call of either family.  serl_venv_last_info records SERL_FAMILY_WAVE, the grid and the wavefronts
+ * per workgroup.  Timings against the step loop and the lane kernel: profiles/venv_rollout_wave_timing.json. */
+int serl_venv_rollout_wave(serl_ctx *ctx, const serl_venv_desc *desc, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *ro,
+                           void *stream);
+int serl_venv_rollout_wave_noise(serl_ctx *ctx, const serl_venv_desc *desc, const serl_venv_auto_desc *au,
+                                 const serl_venv_rollout_desc *ro, const serl_venv_noise_desc *nz, void *stream);
 /* the generator's bit-level parts on the host, compiled from the kernels' text (csrc/serl_rng.h) */
 void serl_host_philox(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t out4[4]);
 double serl_host_uniform(uint32_t w0, uint32_t w1);

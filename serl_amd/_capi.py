@@ -19,7 +19,7 @@ EXPORTS = ['serl_abi_version', 'serl_last_error', 'serl_param_count', 'serl_ctx_
            'serl_venv_noise_layout', 'serl_venv_reset_noise', 'serl_venv_step_auto_noise', 'serl_venv_rollout_noise',
            'serl_venv_rollout_general_noise', 'serl_venv_noise_fill', 'serl_venv_actor_forward', 'serl_host_philox', 'serl_host_uniform',
            'serl_venv_reset_wave', 'serl_venv_step_wave', 'serl_venv_step_auto_wave', 'serl_venv_reset_wave_noise', 'serl_venv_step_auto_wave_noise',
-           'serl_venv_last_info']
+           'serl_venv_last_info', 'serl_venv_rollout_wave', 'serl_venv_rollout_wave_noise']
 
 
 class BuildDesc(ctypes.Structure):
@@ -201,6 +201,8 @@ def lib():
     L.serl_venv_reset_wave_noise.argtypes = L.serl_venv_reset_noise.argtypes
     L.serl_venv_step_auto_wave_noise.argtypes = L.serl_venv_step_auto_noise.argtypes
     L.serl_venv_last_info.argtypes = [VP, VP]
+    L.serl_venv_rollout_wave.argtypes = L.serl_venv_rollout_general.argtypes
+    L.serl_venv_rollout_wave_noise.argtypes = L.serl_venv_rollout_general_noise.argtypes
     L.serl_host_philox.argtypes = [ctypes.c_uint64] + [ctypes.c_uint32] * 4 + [ctypes.POINTER(ctypes.c_uint32)]
     L.serl_host_uniform.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
     L.serl_td3_work_bytes.argtypes = [i32] * 6

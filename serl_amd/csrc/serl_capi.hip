@@ -98,6 +98,16 @@ struct SerlVwLaunchers { SERL_VW_LAUNCHERS(SERL_MEMBER, v) };
 SERL_VARIANTS(SERL_VW_VARIANT_DECL)
 static const SerlVwLaunchers k_vw_launchers[] = {SERL_VARIANTS(SERL_VW_VARIANT_ROW)};
 
+// CitationVecEnv.rollout with one wavefront per env (family_venvwr.hip: venv_wave_rollout.inc, plain and under SERL_VENV_NOISE), one record per code variant as above
+#define SERL_VWR_LAUNCHERS(X, v)                                                      \
+  X(SerlLaunchVenvRollout, rollout, serl_launch_venv_rollout_wave_##v)                \
+  X(SerlLaunchVenvRolloutNz, rollout_nz, serl_launch_venv_rollout_wave_noise_##v)
+struct SerlVwrLaunchers { SERL_VWR_LAUNCHERS(SERL_MEMBER, v) };
+#define SERL_VWR_VARIANT_DECL(v, code) SERL_VWR_LAUNCHERS(SERL_DECL, v)
+#define SERL_VWR_VARIANT_ROW(v, code) {SERL_VWR_LAUNCHERS(SERL_INIT, v)},
+SERL_VARIANTS(SERL_VWR_VARIANT_DECL)
+static const SerlVwrLaunchers k_vwr_launchers[] = {SERL_VARIANTS(SERL_VWR_VARIANT_ROW)};
+
 #include "serl_mixed.h"
 
 static void serl_launch_rollout_teamg(const SerlLaunchers &L, int groups, const RolloutArgs &a, int grid, hipStream_t stream)
@@ -904,7 +914,13 @@ static int serl_venv_launch(serl_ctx *c, const serl_venv_desc *d, bool step, Ven
     const int grid = (d->n_envs + wpb - 1) / wpb;
     v.d = *d;
     v.npad = serl_venv_npad(d->n_envs);
-    if (nz) {
+    if (rd) {      // K steps under the wave-cooperative actor (venv_wave_rollout.inc), which reads its shape as the lane forward does
+      const SerlVwrLaunchers &R = k_vwr_launchers[s.code];
+      a.d.state_dim = rd->state_dim; a.d.action_dim = rd->action_dim; a.d.hidden = rd->hidden;
+      a.d.num_layers = rd->num_layers; a.d.activation = rd->activation;
+      if (nz) R.rollout_nz(a, v, *au, *rd, *nz, grid, stream);
+      else R.rollout(a, v, *au, *rd, grid, stream);
+    } else if (nz) {
       if (au) W.step_auto_nz(a, v, *au, *nz, grid, stream);
       else W.reset_nz(a, v, *nz, grid, stream);
     } else if (au) W.step_auto(a, v, *au, grid, stream);
@@ -1153,7 +1169,7 @@ int serl_venv_rollout_noise(serl_ctx *c, const serl_venv_desc *d, const serl_ven
 }
 
 static int serl_venv_rollout_general_impl(const char *what, serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au,
-                                          const serl_venv_rollout_desc *rd, const serl_venv_noise_desc *nz, void *stream_)
+                                          const serl_venv_rollout_desc *rd, const serl_venv_noise_desc *nz, void *stream_, bool wave = false)
 {
   const std::string w(what);
   // (the descriptors first: none of these checks reads the context)
@@ -1182,7 +1198,7 @@ static int serl_venv_rollout_general_impl(const char *what, serl_ctx *c, const s
   HIP_TRY(hipSetDevice(c->device));
   VenvArgs v;
   memset(&v, 0, sizeof(v));
-  return serl_venv_launch(c, &dd, true, v, (hipStream_t)stream_, au, rd, true, nz);
+  return serl_venv_launch(c, &dd, true, v, (hipStream_t)stream_, au, rd, true, nz, wave);
 }
 
 int serl_venv_rollout_general(serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd, void *stream_)
@@ -1195,6 +1211,18 @@ int serl_venv_rollout_general_noise(serl_ctx *c, const serl_venv_desc *d, const 
 {
   { const int rc_ = serl_venv_noise_check("serl_venv_rollout_general_noise", d, rd, nz); if (rc_ != SERL_OK) return rc_; }
   return serl_venv_rollout_general_impl("serl_venv_rollout_general_noise", c, d, au, rd, nz, stream_);
+}
+
+int serl_venv_rollout_wave(serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd, void *stream_)
+{
+  return serl_venv_rollout_general_impl("serl_venv_rollout_wave", c, d, au, rd, nullptr, stream_, true);
+}
+
+int serl_venv_rollout_wave_noise(serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd,
+                                 const serl_venv_noise_desc *nz, void *stream_)
+{
+  { const int rc_ = serl_venv_noise_check("serl_venv_rollout_wave_noise", d, rd, nz); if (rc_ != SERL_OK) return rc_; }
+  return serl_venv_rollout_general_impl("serl_venv_rollout_wave_noise", c, d, au, rd, nz, stream_, true);
 }
 
 /* development aid (SERL_PROFILE=1): shader-clock cycles wave 0 of workgroup 0 spent in the actor forward, the

@@ -153,6 +153,7 @@ static __device__ __forceinline__ const double *serl_venvw_sensor_nz(const serl_
 }
 #endif
 
+#ifndef SERL_VENVW_HELPERS_ONLY      // (family_venvwr.hip takes the helpers above and brings the rollout kernels of venv_wave_rollout.inc)
 // reset() of the envs in the mask (serl_venv_reset_kernel_<v>)
 __global__ void __launch_bounds__(64 * CITW_MAX_WAVES) VW_KNAME(serl_venv_reset_wave_kernel_)(RolloutArgs a, VenvArgs v VW_NZ_PARAM)
 {
@@ -381,6 +382,7 @@ void VW_KNAME(serl_launch_venv_step_auto_wave_)(const RolloutArgs &a, const Venv
   hipLaunchKernelGGL(VW_KNAME(serl_venv_step_auto_wave_kernel_), dim3(grid), dim3(a.block), 0, stream, a, v, au, nz);
 }
 #endif
+#endif  // SERL_VENVW_HELPERS_ONLY
 #undef VW_SENSOR
 #undef VW_NZ_PARAM
 #undef VW_NZ_LOCALS

@@ -44,8 +44,9 @@ serl_venv_*_noise): no table, no host draw, a fresh realisation for every episod
 writes any episode's draws out as a table.
 
 `kernel='wave'` (serl_venv_*_wave) runs `reset` / `step` with one wavefront per env instead of one lane per env: the small-batch path, for one
-to a few hundred envs, where a lane call is pure latency.  Same results bit for bit in every output, same state buffer layout; `rollout()` refuses on such an env (the lane
-kernels' table3 interval cache is the one state field the wave kernels cannot reproduce).  `kernel='auto'` takes the wave path up to WAVE_MAX_ENVS envs; `env.last_step_kernel` says what the last call launched.
+to a few hundred envs, where a lane call is pure latency.  Same results bit for bit in every output, same state buffer layout; the lane rollout kernels are not run on such
+an env (their table3 interval cache is the one state field the wave kernels cannot reproduce): `rollout(..., path='fused')` runs the wave rollout kernel instead
+(serl_venv_rollout_wave, the actor on the wavefront), while the default path keeps to the step loop or raises.  `kernel='auto'` takes the wave path up to WAVE_MAX_ENVS envs; `env.last_step_kernel` says what the last call launched.
 """
 import ctypes
 import numpy as np
@@ -86,7 +87,8 @@ class CitationVecEnv:
     ref_pool      auto_reset with refs=None: training references drawn per env by every explicit reset; the episode the reset starts
                   flies row 0, the j-th restart after it row j % ref_pool (the pool recycles after ref_pool episodes).
     kernel        'lane' (default): one lane per env; 'wave': one wavefront per env for reset / step (small batches); 'auto': 'wave' up to
-                  WAVE_MAX_ENVS envs.  Every output is the same bit for bit; rollout() raises a ValueError on an env that steps on the wave kernels."""
+                  WAVE_MAX_ENVS envs.  Every output is the same bit for bit; on an env that steps on the wave kernels rollout(path='fused') runs the wave rollout kernel,
+                  and the default path raises a ValueError where it would have taken the lane kernel."""
 
     # device noise (serl_venv_noise_desc): the seed, the per-env count of episode starts, whether the sensor noise comes from the generator
     noise_seed = None
@@ -335,7 +337,7 @@ class CitationVecEnv:
         return self._obs, self._reward, self._done, {'x': self._x, 'ref': self._refk, 't': self._t, 'cost': self._cost}
 
     # ---- K policy-driven steps in one launch (serl_venv_rollout) ------------------------------------------------------------------
-    # 'fused' (serl_venv_rollout), 'fused-general' (serl_venv_rollout_general) or 'loop' (step by step with a torch forward) of the last rollout()
+    # 'fused' (serl_venv_rollout), 'fused-general' (serl_venv_rollout_general), 'fused-wave' (serl_venv_rollout_wave) or 'loop' (step by step with a torch forward) of the last rollout()
     last_rollout_path = None
     ROLLOUT_PATHS = ('auto', 'fused', 'loop')
 
@@ -350,6 +352,11 @@ class CitationVecEnv:
         configuration; an actor that fits this env, hidden a multiple of 4 in 4 .. 128, 0 .. 16 hidden layers, any activation."""
         return ((spec.state_dim, spec.action_dim) == (self.state_dim, self.action_dim) and
                 spec.hidden % 4 == 0 and 4 <= spec.hidden <= 128 and 0 <= spec.num_layers <= 16)
+
+    def fused_wave_ok(self, spec):
+        """True when rollout(path='fused') on an env that steps on the wave kernels can run `spec` actors inside the wave rollout kernel
+        (serl_venv_rollout_wave, one wavefront per env): the shapes of fused_general_ok, the lane kernel's 7 -> 32 .. -> 3 among them."""
+        return self.fused_general_ok(spec)
 
     def _check_rollout_args(self, policy, n_steps, spec, member_of_env, action_noise, path='auto'):
         """The argument checks of rollout() that need no device work -> (K, list of actor modules or None, NetSpec)."""
@@ -412,7 +419,10 @@ class CitationVecEnv:
                        of 4 up to 128, up to 16 hidden layers) where fused_general_ok; 'loop': always the step loop (A/B runs, tests;
                        on an env with device noise its forward is the kernels' own, serl_venv_actor_forward, for every shape a kernel takes:
                        there the paths agree bit for bit).
-                       `last_rollout_path` says 'fused', 'fused-general' or 'loop'."""
+                       On an env that steps on the wave kernels (kernel='wave' / 'auto') 'fused' runs the wave rollout kernel
+                       (serl_venv_rollout_wave: one wavefront per env, every shape of fused_wave_ok, bit for bit what the lane kernels
+                       compute); 'auto' there keeps to the step loop, and raises for the lane kernel's shape.
+                       `last_rollout_path` says 'fused', 'fused-general', 'fused-wave' or 'loop'."""
         dev_action = isinstance(action_noise, str)
         if dev_action:
             if action_noise != 'device':
@@ -439,12 +449,17 @@ class CitationVecEnv:
         if path == 'loop' or (path == 'auto' and not lane32):
             self.last_rollout_path = 'loop'
             return self._rollout_loop(policy, mods, spec, K, moe, noise, transitions, info, nz if dev_action else None)
-        if self._wave:
+        if self._wave and path == 'fused':      # K steps on the wave kernels themselves: one wavefront per env, the wave-cooperative actor
+            if not self.fused_wave_ok(spec):
+                raise ValueError("path='fused': no wave kernel runs a %d -> %d x %d -> %d actor (hidden: a multiple of 4 in 4 .. 128; 0 .. 16 "
+                                 "hidden layers)" % (spec.state_dim, spec.hidden, spec.num_layers, spec.action_dim))
+            lane32 = False
+        elif self._wave:
             # The lane step walks the table3 S-function's interval cache (IW[0..2] of the state) from a work word it never initialises, so what a
             # lane call leaves there depends on the compiled kernel and the wave calls cannot reproduce it (they leave the words alone).  No output
             # has been seen to depend on it, but the lane rollout kernels are not handed a state they did not write.
             raise ValueError("rollout in a kernel: this env steps on the wave kernels (kernel=%r), whose state the lane rollout kernels do not take over; "
-                             "make the env with kernel='lane', or take path='loop'" % (self.kernel,))
+                             "make the env with kernel='lane', or take path='fused' (the wave rollout kernel) or path='loop'" % (self.kernel,))
         w = self._packed_rows(policy, mods)
         out = self._rollout_buffers(K, transitions, info)
         rd = _capi.VenvRolloutDesc(state_dim=spec.state_dim, action_dim=spec.action_dim, hidden=spec.hidden, num_layers=spec.num_layers,
@@ -459,7 +474,7 @@ class CitationVecEnv:
             rd.x, rd.ref, rd.t, rd.cost = (out[k].data_ptr() for k in ('x', 'ref', 't', 'cost'))
         if transitions:
             rd.transitions = out['transitions'].data_ptr()
-        entry = 'serl_venv_rollout' if lane32 else 'serl_venv_rollout_general'
+        entry = 'serl_venv_rollout_wave' if self._wave else 'serl_venv_rollout' if lane32 else 'serl_venv_rollout_general'
         if nz is not None:
             entry += '_noise'
             _capi.check(getattr(self.lib, entry)(self.engine.ctx, ctypes.byref(self.desc), ctypes.byref(self.auto_desc), ctypes.byref(rd),
@@ -468,7 +483,7 @@ class CitationVecEnv:
             _capi.check(getattr(self.lib, entry)(self.engine.ctx, ctypes.byref(self.desc), ctypes.byref(self.auto_desc), ctypes.byref(rd),
                                                  self._stream()), entry)
         del w, moe, noise      # (freed memory is handed out again only to work ordered behind this launch on the same stream)
-        self.last_rollout_path = 'fused' if lane32 else 'fused-general'
+        self.last_rollout_path = 'fused-wave' if self._wave else 'fused' if lane32 else 'fused-general'
         return out
 
     def _packed_rows(self, policy, mods):

@@ -44,7 +44,13 @@ of the auto-reset leg, a fixed action, medians and [min .. max] of `reps` repeti
     auto_idle       `step` with auto_reset=True, no env finishing (its `idle`, auto version)
     auto_staggered  `step` with auto_reset=True, episodes of 32 steps at spread phases: 3 % of the envs finish per step (its `staggered`, auto version)
 -- and derives the env count up to which kernel='auto' should take the wave path: the largest measured N at which the wave median is below the lane
-median by more than the lane repetitions' own spread (max - min) in auto_idle and in auto_staggered.  `--kernel lane` or `--kernel wave` measures one."""
+median by more than the lane repetitions' own spread (max - min) in auto_idle and in auto_staggered.  `--kernel lane` or `--kernel wave` measures one.
+
+    python tools/bench_venv.py --rollout --kernel wave [--sizes 1,16,64,256,1024,4096] [--auto-steps 500] [--rollout-k 50] [--reps 5] [--out profiles/venv_rollout_wave_timing.json]
+runs the wave rollout leg: `rollout(actor, K, path='fused')` on CitationVecEnv(kernel='wave') (serl_venv_rollout_wave: one wavefront per env, the actor on
+the wavefront) against (a) `path='loop'` on the same kind of env, the only way to roll out there before, and (b) `path='fused'` on a kernel='lane' env (the
+lane rollout kernels) -- for the SERL50 actor and for hidden 72 x 3, with no env finishing (`idle`) and with 3 % of the envs finishing per step (`staggered`),
+medians and [min .. max] of `reps` repetitions after a warm-up, the three versions taking turns within each repetition."""
 import argparse, json, os, subprocess, sys
 import numpy as np
 import torch
@@ -291,6 +297,57 @@ def bench_rollout(eng, N, steps, K, warmup, reps, hidden=None, layers=3, path='f
     return out
 
 
+def bench_rollout_wave(eng, N, steps, K, warmup, reps, hidden=None, layers=3):
+    """One size and actor: the wave rollout kernel against the step loop on a wave env and against the lane rollout kernel, idle and staggered."""
+    dev = eng.device
+    fixed = torch.zeros(N, 3, dtype=torch.float32, device=dev)
+    actor = serl50_policy(dev) if hidden is None else seeded_policy(dev, hidden, layers)
+    L = 32
+    full = rs.tabulate(*rs.base_reference(20), 20)
+    table = np.ascontiguousarray(full[:L])
+    assert steps % K == 0 and warmup % K == 0 and steps + warmup < len(full)
+    versions = {'wave_fused': ('wave', 'fused'), 'wave_loop': ('wave', 'loop'), 'lane_fused': ('lane', 'fused')}
+    out = dict(N=N, steps=steps, K=K, reps=reps, warmup=warmup, hidden=32 if hidden is None else hidden, layers=layers)
+
+    def run(env, v, n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(n // K):
+            o = env.rollout(actor, K, path=versions[v][1])
+        e1.record()
+        e1.synchronize()
+        out.setdefault('paths', {})[v] = env.last_rollout_path
+        return e0.elapsed_time(e1), int(o['done'][-1].sum())
+
+    for name, refs, stagger_L in (('idle', full, 0), ('staggered', table, L)):
+        envs = {v: serl_amd.CitationVecEnv(N, mode='nominal', t_max=20, refs=refs, engine=eng, auto_reset=True, kernel=k) for v, (k, _) in versions.items()}
+        ms, fin = {v: [] for v in envs}, {}
+        order = list(envs.items())
+        with torch.no_grad():
+            for v, env in order:
+                if stagger_L:
+                    _stagger(env, stagger_L, fixed)
+                else:
+                    env.reset()
+                run(env, v, warmup)
+            for r in range(reps):
+                for v, env in order[r % 3:] + order[:r % 3]:      # the versions take turns at going first
+                    if not stagger_L:
+                        env.reset()      # idle: every repetition from a fresh episode, so that no env finishes
+                    m, fin[v] = run(env, v, steps)
+                    ms[v].append(m)
+        out[name] = {v: _summary(N, steps, ms[v]) for v in envs}
+        out[name]['finished_on_last_step'] = fin
+        w = out[name]['wave_fused']['us_per_step']
+        for other in ('wave_loop', 'lane_fused'):
+            o = out[name][other]['us_per_step']
+            out[name]['%s_over_wave_fused' % other] = round(o['median'] / w['median'], 3)
+            out[name]['%s_spread_us' % other] = round(o['max'] - o['min'], 2)
+            out[name]['wave_fused_wins_beyond_%s_spread' % other] = bool(o['median'] - w['median'] > o['max'] - o['min'])
+        del envs
+    return out
+
+
 def bench_device_noise(eng, N, steps, K, warmup, reps):
     """One size: the device generator against the table path, step(auto) and rollout(actor, K), every env live, 1 / 64 of them finishing per step."""
     dev = eng.device
@@ -367,7 +424,8 @@ def bench_noise_reset(eng, N):
     return out
 
 
-def kernel_report(stem='rollout_%s.o'):
+def kernel_report(stem='rollout_%s.o', noise_twins=False):
+    """noise_twins: the unit holds a kernel and its SERL_VENV_NOISE twin: the twin's record gets a key of its own"""
     rep = {}
     for v in ('nominal', 'ice', 'cg_timed', 'gust', 'test'):
         obj = os.path.join(ROOT, 'serl_amd', 'csrc', 'build', stem % v)
@@ -382,6 +440,8 @@ def kernel_report(stem='rollout_%s.o'):
             name = f['.name'].strip()
             kind = ('rollout_general' if 'venv_rollout_general' in name else 'rollout' if 'venv_rollout' in name else 'step_auto' if 'step_auto' in name
                     else 'step' if 'step' in name else 'reset')
+            if noise_twins and '_noise_' in name:
+                kind += '_noise'
             rep['%s_%s' % (kind, v)] = dict(vgpr=int(f['.vgpr_count']), vgpr_spill=int(f['.vgpr_spill_count']), sgpr_spill=int(f['.sgpr_spill_count']),
                                             lds_bytes=int(f['.group_segment_fixed_size']), scratch_bytes=int(f['.private_segment_fixed_size']))
     return rep
@@ -413,6 +473,24 @@ def main():
         args.out = os.path.join(ROOT, 'profiles', ('venv_rollout_general_timing.json' if args.hidden else 'venv_rollout_timing.json') if args.rollout
                                 else 'venv_auto_timing.json')
     eng = serl_amd.RolloutEngine(0)
+    if args.rollout and args.kernel is not None:
+        if args.kernel != 'wave':
+            ap.error("--rollout --kernel: 'wave' (the wave rollout leg)")
+        if args.out.endswith('venv_rollout_timing.json') or args.out.endswith('venv_rollout_general_timing.json'):
+            args.out = os.path.join(ROOT, 'profiles', 'venv_rollout_wave_timing.json')
+        sizes = [int(s) for s in (args.sizes if args.sizes != ap.get_default('sizes') else '1,16,64,256,1024,4096').split(',')]
+        steps = args.auto_steps if args.auto_steps != ap.get_default('auto_steps') else 500
+        shapes = [int(h) for h in args.hidden.split(',')] if args.hidden else [None, 72]      # the SERL50 actor and hidden 72 x 3
+        res = dict(tool='bench_venv --rollout --kernel wave', device=torch.cuda.get_device_name(0), source_hash=hip_build.source_hash(),
+                   results=[bench_rollout_wave(eng, N, steps, args.rollout_k, args.warmup, args.reps, H, args.layers) for H in shapes for N in sizes])
+        kernels_rep = kernel_report('rollout_venvwr_%s.o', noise_twins=True)      # (needs the build's objects: empty where only the library was shipped)
+        if kernels_rep:
+            res['kernels'] = kernels_rep
+        with open(args.out, 'w') as f:
+            json.dump(res, f, indent=1)
+            f.write('\n')
+        print(json.dumps(res))
+        return
     if args.kernel is not None:
         kernels = args.kernel.split(',')
         if not kernels or any(k not in ('lane', 'wave') for k in kernels) or len(set(kernels)) != len(kernels):
