@@ -129,7 +129,7 @@ def test_fused_rollout_families_on_the_scenarios(engine, key, kern):
 
 
 # ---- CitationVecEnv --------------------------------------------------------------------------------------------------------------------
-def _make_env(engine, key, scs, T, auto):
+def _make_env(engine, key, scs, T, auto, kernel='lane'):
     import serl_amd
     build, cfg, incr = key[:3]
     mode = 'PHlab_%s_%s' % (CFG_NAME[cfg], 'incremental' if incr else MODE_OF_BUILD[build])
@@ -138,12 +138,13 @@ def _make_env(engine, key, scs, T, auto):
     sn = np.stack([s['sensor_noise'] if s['sensor_noise'] is not None else np.zeros((T + 1, 7)) for s in scs])
     with_noise = any(s['sensor_noise'] is not None for s in scs) or build == 'gust'
     env = serl_amd.CitationVecEnv(N, mode=mode, t_max=scs[0]['t_max'], engine=engine, refs=np.stack([s['ref'] for s in scs]),
-                                  sensor_noise=sn if with_noise else False, auto_reset=auto)
+                                  sensor_noise=sn if with_noise else False, auto_reset=auto, kernel=kernel)
     assert (env.build, env.env_config, env.incremental, env.max_steps) == (build, cfg, incr, T)
     assert env._faults is None      # per-env fault rows: the descriptor's table, set as the constructor sets it for a fault mode
     env._faults = torch.from_numpy(np.array([G.fault_row(s['fault']) for s in scs])).to(env.device).contiguous()
     env.desc.faults = env._faults.data_ptr()
     obs0 = _np(env.reset(err0=np.array([s['err0'] or [0.0, 0.0, 0.0] for s in scs]), tick0=np.array([s['tick0'] or 0 for s in scs])))
+    assert env.last_step_kernel == kernel
     return env, obs0
 
 
@@ -169,12 +170,17 @@ STEP = _groups(extra=lambda s: (s['t_max'], 'f32' if s['kind'] == 'f32' else 'f6
 @pytest.mark.parametrize('auto', [False, True], ids=['step', 'auto'])
 @pytest.mark.parametrize('key', list(STEP), ids=[_id(k) for k in STEP])
 def test_env_step_kernels_on_the_scenarios(engine, key, auto):
+    step_case(engine, key, auto)
+
+
+def step_case(engine, key, auto, kernel='lane'):
+    """the scenarios of STEP[key] through step() of an env of the `kernel` family, one env per scenario -> the env behind its last step"""
     scs0 = STEP[key]
     T = max(len(s['ref']) for s in scs0)
     pairs = [_expected(s, T) for s in scs0]
     scs = [p for p, _ in pairs]
     N, S, A = len(scs), scs0[0]['S'], scs0[0]['A']
-    env, obs0 = _make_env(engine, key, scs, T, auto)
+    env, obs0 = _make_env(engine, key, scs, T, auto, kernel)
     dev = env.device
     acts = torch.from_numpy(np.ascontiguousarray(np.stack([_act_exec(s, T, A) for s in scs], axis=1))).to(dev)      # [T, N, A]
     assert acts.dtype == (torch.float32 if key[-1] == 'f32' else torch.float64)
@@ -193,6 +199,7 @@ def test_env_step_kernels_on_the_scenarios(engine, key, auto):
         for name in rec:
             if name in info:
                 rec[name][k].copy_(info[name])
+    assert env.last_step_kernel == kernel
     rec = {k: _np(v) for k, v in rec.items()}
     for e, (s, o) in enumerate(pairs):
         n, what = o['n'], '%s env %d %s' % ('auto' if auto else 'step', e, s['name'])
@@ -213,6 +220,7 @@ def test_env_step_kernels_on_the_scenarios(engine, key, auto):
         else:      # frozen behind done
             assert d[n - 1:].all() and (rec['reward'][n:, e] == 0.0).all(), what
             np.testing.assert_array_equal(rec['obs'][n:, e], np.tile(o['obs'][-1], (K - n, 1)), err_msg=what + ': frozen')
+    return env
 
 
 ROLL = _groups(lambda s: s['fused'], extra=lambda s: (s['t_max'], 'noise' if s['kind'] == 'noise' else 'plain'))
@@ -221,13 +229,19 @@ ROLL_CASES = [(key, shape) for key in ROLL for shape in (['lane32', 'general'] i
 
 @pytest.mark.parametrize('key,shape', ROLL_CASES, ids=['%s-%s' % (_id(k), s) for k, s in ROLL_CASES])
 def test_env_rollout_kernels_on_the_scenarios(engine, key, shape):
+    roll_case(engine, key, shape)
+
+
+def roll_case(engine, key, shape, kernel='lane'):
+    """the scenarios of ROLL[key] through rollout(path='fused') of an env of the `kernel` family: the 7-32x3-3 actor ('lane32') or the
+    one-layer hidden-16 actor ('general'); on a wave env both go through the one wave rollout kernel -> the env behind the launch"""
     import serl_amd
     scs0 = ROLL[key]
     T = max(len(s['ref']) for s in scs0)
     pairs = [_expected(s, T) for s in scs0]
     scs = [p for p, _ in pairs]
     N, S, A = len(scs), scs0[0]['S'], scs0[0]['A']
-    env, obs0 = _make_env(engine, key, scs, T, True)
+    env, obs0 = _make_env(engine, key, scs, T, True, kernel)
     H, L = (32, 3) if shape == 'lane32' else (16, 1)
     spec = serl_amd.NetSpec(S, A, H, L, 'tanh')
     K = T + 1
@@ -237,7 +251,7 @@ def test_env_rollout_kernels_on_the_scenarios(engine, key, shape):
         noise[:T] = np.stack([s['noise'] for s in scs], axis=1)
     w = torch.from_numpy(_weights(scs, S, A, H, L)).to(env.device)
     out = env.rollout(w, K, spec=spec, member_of_env=np.arange(N, dtype=np.int32), action_noise=noise, transitions=True, path='fused')
-    assert env.last_rollout_path == ('fused' if shape == 'lane32' else 'fused-general')
+    assert env.last_rollout_path == ('fused-wave' if kernel == 'wave' else 'fused' if shape == 'lane32' else 'fused-general')
     out = {k: _np(v) for k, v in out.items()}
     for e, (s, o) in enumerate(pairs):
         n, what = o['n'], '%s env %d %s' % (shape, e, s['name'])
@@ -255,3 +269,4 @@ def test_env_rollout_kernels_on_the_scenarios(engine, key, shape):
         assert not d[:n - 1].any() and d[n - 1], '%s: done first rises at step %d, not %d' % (what, int(np.argmax(d)), n - 1)
         assert out['ep_return'][n - 1, e] == o['fitness'] and out['ep_length'][n - 1, e] == n, what
         np.testing.assert_array_equal(out['obs'][n, e], _restart_obs(s, o), err_msg=what + ': obs0 of the restarted episode')
+    return env

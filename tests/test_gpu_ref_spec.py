@@ -46,23 +46,23 @@ def _layout(kind):
     return X.cycled()[:, None]
 
 
-def _make_env(engine, kind, auto, mode, t_max, tail=np.nan):
+def _make_env(engine, kind, auto, mode, t_max, tail=np.nan, kernel='lane'):
     import serl_amd
     rows = X.specs(tail=tail)
     lay = _layout(kind)
     if kind == 'pool':      # made to draw (refs=None); the reset is given rows, so it draws nothing, and the pool tensor is written after it
-        env = serl_amd.CitationVecEnv(N, mode=mode, t_max=t_max, engine=engine, auto_reset=True, ref_pool=2)
+        env = serl_amd.CitationVecEnv(N, mode=mode, t_max=t_max, engine=engine, auto_reset=True, ref_pool=2, kernel=kernel)
         env.reset(refs=np.ascontiguousarray(rows[lay[:, 0]]))
         pool = np.ascontiguousarray(rows[lay]).view(np.uint8).reshape(N, 2, -1)
         assert env._pool.shape == pool.shape
         env._pool.copy_(torch.from_numpy(pool))
     else:
         given = rows[lay[:1, 0]] if kind == 'shared' else rows[lay[:, 0]]      # (one row: stride 0)
-        env = serl_amd.CitationVecEnv(N, mode=mode, t_max=t_max, engine=engine, auto_reset=auto, refs=np.ascontiguousarray(given))
+        env = serl_amd.CitationVecEnv(N, mode=mode, t_max=t_max, engine=engine, auto_reset=auto, refs=np.ascontiguousarray(given), kernel=kernel)
         assert env._spec_shared == (kind == 'shared')
         env.reset()
     from serl_amd import refsignals as rs
-    assert env.max_steps == rs.n_steps_for(t_max)
+    assert env.max_steps == rs.n_steps_for(t_max) and env.last_step_kernel == kernel
     return env, lay
 
 
@@ -106,8 +106,9 @@ def _n_restarts(lay, K, T):
     return (K - AFTER) // T
 
 
-def _walk(env, kind, t_max, keys=('ref', 't')):
-    """zero actions through one episode (the pool: two) plus the restart and AFTER steps of the next; the plain env is reset as documented"""
+def _walk(env, kind, t_max, keys=('ref', 't'), kernel='lane'):
+    """zero actions through one episode (the pool: two) plus the restart and AFTER steps of the next; the plain env is reset as documented;
+    every step and reset must have run on the `kernel` family"""
     from serl_amd import refsignals as rs
     K = _episodes(kind) * rs.n_steps_for(t_max) + AFTER
     act = torch.zeros(N, 3, device=env.device)
@@ -117,8 +118,10 @@ def _walk(env, kind, t_max, keys=('ref', 't')):
         for k in keys:
             rec[k].append(info[k].clone())
         rec['done'].append(done.clone()); rec['obs'].append(obs.clone()); rec['reward'].append(rew.clone())
+        assert env.last_step_kernel == kernel
         if not env.auto_reset and bool(done.any()):
             env.reset(done)
+            assert env.last_step_kernel == kernel
     return {k: np.stack([_np(v) for v in vs]) for k, vs in rec.items()}
 
 
@@ -130,9 +133,13 @@ ENV_KINDS = [('step', 'rows'), ('step', 'shared'), ('auto', 'rows'), ('auto', 's
 @pytest.mark.parametrize('kernel_,kind', ENV_KINDS, ids=['%s-%s' % k for k in ENV_KINDS])
 def test_env_step_returns_the_generated_reference(engine, kernel_, kind, mode, t_max):
     """serl_venv_step / serl_venv_step_auto: info['ref'] of every step, through the restart (the pool: until its cursor is back on row 0)"""
+    step_ref_case(engine, kernel_, kind, mode, t_max)
+
+
+def step_ref_case(engine, kernel_, kind, mode, t_max, kernel='lane'):
     np.random.seed(5)      # (gust: the sensor-noise tables the resets draw)
-    env, lay = _make_env(engine, kind, kernel_ == 'auto', mode, t_max)
-    o = _walk(env, kind, t_max)
+    env, lay = _make_env(engine, kind, kernel_ == 'auto', mode, t_max, kernel=kernel)
+    o = _walk(env, kind, t_max, kernel=kernel)
     worst, epi = _check_refs(o['ref'], o['t'], o['done'], lay, t_max, '%s %s %s %g' % (kernel_, kind, mode, t_max), full=1.0)
     print('worst %.3f units' % worst)
     assert np.isfinite(o['obs']).all() and np.isfinite(o['reward']).all()
@@ -141,18 +148,19 @@ def test_env_step_returns_the_generated_reference(engine, kernel_, kind, mode, t
         assert (lay[:, 0] != lay[:, 1]).all()
 
 
-def _actor(engine, golden, which):
+def _actor(engine, golden, which, kernel='lane'):
+    """(weights, spec, members, the path rollout(path='fused') must report): on a wave env both shapes run the one wave rollout kernel"""
     if which == 'lane32':
         w = np.ascontiguousarray(golden('actors')['serl50'])
-        return torch.from_numpy(w).to(engine.device), _spec(NET32), len(w), 'fused'
+        return torch.from_numpy(w).to(engine.device), _spec(NET32), len(w), 'fused-wave' if kernel == 'wave' else 'fused'
     w = np.ascontiguousarray(make_weights(S72, 5, 31))
-    return torch.from_numpy(w).to(engine.device), spec_of(S72), len(w), 'fused-general'
+    return torch.from_numpy(w).to(engine.device), spec_of(S72), len(w), 'fused-wave' if kernel == 'wave' else 'fused-general'
 
 
-def _rollout(engine, golden, which, kind, mode, t_max, tail=np.nan):
+def _rollout(engine, golden, which, kind, mode, t_max, tail=np.nan, kernel='lane'):
     from serl_amd import refsignals as rs
-    env, lay = _make_env(engine, kind, True, mode, t_max, tail)
-    w, spec, M, path = _actor(engine, golden, which)
+    env, lay = _make_env(engine, kind, True, mode, t_max, tail, kernel)
+    w, spec, M, path = _actor(engine, golden, which, kernel)
     K = _episodes(kind) * rs.n_steps_for(t_max) + AFTER
     out = env.rollout(w, K, spec=spec, member_of_env=np.arange(N, dtype=np.int32) % M, transitions=True, path='fused')
     assert env.last_rollout_path == path
@@ -166,8 +174,12 @@ def _rollout(engine, golden, which, kind, mode, t_max, tail=np.nan):
 def test_env_rollout_returns_the_generated_reference(engine, golden, which, kind, mode, t_max):
     """serl_venv_rollout (the SERL50 shape: the lane-32 kernel) and serl_venv_rollout_general (hidden 72): 'ref' [K, N, 3] of one launch
     that flies an episode, restarts and flies on -- the actor in the loop, so the reference also feeds back into the flight"""
+    rollout_ref_case(engine, golden, which, kind, mode, t_max)
+
+
+def rollout_ref_case(engine, golden, which, kind, mode, t_max, kernel='lane'):
     np.random.seed(5)
-    env, lay, o = _rollout(engine, golden, which, kind, mode, t_max)
+    env, lay, o = _rollout(engine, golden, which, kind, mode, t_max, kernel=kernel)
     worst, epi = _check_refs(o['ref'], o['t'], o['done'], lay, t_max, '%s %s %s %g' % (which, kind, mode, t_max))
     print('worst %.3f units' % worst)
     assert np.isfinite(o['obs']).all() and np.isfinite(o['reward']).all()
@@ -178,13 +190,17 @@ def test_env_rollout_returns_the_generated_reference(engine, golden, which, kind
 @pytest.mark.parametrize('what', ['step', 'auto', 'pool', 'lane32', 'general'])
 def test_entries_past_n_are_not_read_by_the_env_kernels(engine, golden, what):
     """NaN against zero in the unused tails of t_* / a_*: every output of every step bit for bit"""
+    tails_case(engine, golden, what)
+
+
+def tails_case(engine, golden, what, kernel='lane'):
     runs = []
     for tail in (np.nan, 0.0):
         if what in ('lane32', 'general'):
-            _, _, o = _rollout(engine, golden, what, 'pool', 'nominal', X.T_MAX, tail)
+            _, _, o = _rollout(engine, golden, what, 'pool', 'nominal', X.T_MAX, tail, kernel)
         else:
-            env, _ = _make_env(engine, 'pool' if what == 'pool' else 'rows', what != 'step', 'nominal', X.T_MAX, tail)
-            o = _walk(env, 'pool' if what == 'pool' else 'rows', X.T_MAX, keys=('ref', 't', 'x', 'cost'))
+            env, _ = _make_env(engine, 'pool' if what == 'pool' else 'rows', what != 'step', 'nominal', X.T_MAX, tail, kernel)
+            o = _walk(env, 'pool' if what == 'pool' else 'rows', X.T_MAX, keys=('ref', 't', 'x', 'cost'), kernel=kernel)
         runs.append(o)
     assert set(runs[0]) == set(runs[1]) and np.isfinite(runs[0]['ref']).all()
     for k in runs[0]:

@@ -43,12 +43,13 @@ def _shape_of(mode, hidden, layers):
     return _shape(hidden, layers, 'tanh', cfg, incr)
 
 
-def _record(engine, mode, N, s, path, clock0=None):
+def _record(engine, mode, N, s, path, clock0=None, kernel='lane'):
     """the run: reset(), 12 steps, reset(every third env), 8 steps -> the env, the joined recording, the observations of the two resets
     (clock0: the first reset starts the model clocks there instead of at 0)"""
     import serl_amd
     refs = _tables(N)
-    env = serl_amd.CitationVecEnv(N, mode, t_max=T_SHORT, refs=refs, engine=engine, auto_reset=True, seed=SEED, sensor_noise='device')
+    env = serl_amd.CitationVecEnv(N, mode, t_max=T_SHORT, refs=refs, engine=engine, auto_reset=True, seed=SEED, sensor_noise='device',
+                                  kernel=kernel)
     assert (env.state_dim, env.action_dim) == (s['state_dim'], s['action_dim']) and env.max_steps == EP
     dev = env.device
     w = np.ascontiguousarray(make_weights(s, MEMBERS, 21))
@@ -58,6 +59,7 @@ def _record(engine, mode, N, s, path, clock0=None):
     roll = lambda K: env.rollout(wt, K, spec=spec_of(s), member_of_env=moe, action_noise='device', noise_sd=SD, noise_clip=CLIP,
                                  transitions=True, path=path)
     reset_obs = [_np(env.reset(tick0=clock0)).copy()]
+    assert env.last_step_kernel == kernel
     p1 = {k: _np(v) for k, v in roll(K1).items()}
     ran = env.last_rollout_path
     reset_obs.append(_np(env.reset(third)).copy())
@@ -70,11 +72,11 @@ def _record(engine, mode, N, s, path, clock0=None):
     return env, refs, w, moe, _np(third), rec, reset_obs, ran
 
 
-def _noise_free_twin(engine, mode, N, refs, third, rec, clock0=None):
+def _noise_free_twin(engine, mode, N, refs, third, rec, clock0=None, kernel='lane'):
     """the observations of an env without sensor noise on the recorded actions (the noise is added to what the model returns and never
     fed back, so the twin flies the same states)"""
     import serl_amd
-    twin = serl_amd.CitationVecEnv(N, mode, t_max=T_SHORT, refs=refs, engine=engine, auto_reset=True, sensor_noise=False)
+    twin = serl_amd.CitationVecEnv(N, mode, t_max=T_SHORT, refs=refs, engine=engine, auto_reset=True, sensor_noise=False, kernel=kernel)
     acts = torch.from_numpy(rec['actions']).to(twin.device)
     twin.reset(tick0=clock0)
     obs = []
@@ -82,6 +84,7 @@ def _noise_free_twin(engine, mode, N, refs, third, rec, clock0=None):
         if k == K1:
             twin.reset(torch.from_numpy(third).to(twin.device))
         obs.append(_np(twin.step(acts[k])[0]).copy())
+    assert twin.last_step_kernel == kernel
     return np.stack(obs)
 
 
@@ -93,13 +96,14 @@ def _switch_clocks(N):
     return 1978 + (np.arange(N) * 5 + 3) % 24
 
 
-def _replay_case(engine, mode, N, hidden, layers, path, want_path, clock0=None):
+def _replay_case(engine, mode, N, hidden, layers, path, want_path, clock0=None, kernel='lane'):
+    """-> the env that flew (made with kernel=`kernel`)"""
     import serl_amd
     from serl_amd import builds
     from oracle import rollout as R
     s = _shape_of(mode, hidden, layers)
     S, A = s['state_dim'], s['action_dim']
-    env, refs, w, moe, third, rec, reset_obs, ran = _record(engine, mode, N, s, path, clock0)
+    env, refs, w, moe, third, rec, reset_obs, ran = _record(engine, mode, N, s, path, clock0, kernel)
     assert ran == want_path
     K = K1 + K2
     done = rec['done']
@@ -160,9 +164,10 @@ def _replay_case(engine, mode, N, hidden, layers, path, want_path, clock0=None):
     print('%s %s: %d episodes, |action| < 1 in %.3f of the entries' % (mode, ran, len(eps), (np.abs(a) < 1.0).mean()))
     assert (np.abs(a) <= 1.0).all() and (np.abs(a) < 1.0).any(), 'every action is at +-1'
     assert not np.array_equal(a[:, 0], a[:, 1])
-    quiet = _noise_free_twin(engine, mode, N, refs, third, rec, clock0)
+    quiet = _noise_free_twin(engine, mode, N, refs, third, rec, clock0, kernel)
     assert (quiet != rec['obs_after']).any(-1).all(), 'an observation carries no sensor noise'
     assert np.isfinite(rec['obs_after']).all() and np.isfinite(rec['reward']).all()
+    return env
 
 
 @pytest.mark.parametrize('mode', ['noise', 'ice', 'cg-timed', 'gust', 'test', 'jr'])
@@ -233,20 +238,28 @@ def test_fill_applies_the_callers_bias_and_scale(engine):
 
 def test_step_auto_noise_applies_the_callers_bias_and_scale(engine):
     """reset and one serl_venv_step_auto_noise step with that row against the table path fed by the fill kernel with the same row"""
+    bias_and_scale_case(engine)
+
+
+def bias_and_scale_case(engine, wave=False):
+    """wave: serl_venv_reset_wave_noise / serl_venv_step_auto_wave_noise, still against the lane kernels' table path"""
     import serl_amd
     N = 70
     refs = _tables(N)
-    D = serl_amd.CitationVecEnv(N, 'noise', t_max=T_SHORT, refs=refs, engine=engine, auto_reset=True, seed=SEED, sensor_noise='device')
+    D = serl_amd.CitationVecEnv(N, 'noise', t_max=T_SHORT, refs=refs, engine=engine, auto_reset=True, seed=SEED, sensor_noise='device',
+                                kernel='wave' if wave else 'lane')
     D._nz_desc = lambda *a, **kw: _nz(D, sensor=1)
     table = _fill(engine, _nz(), 2, 7, np.arange(N), np.zeros(N), np.zeros(N), EP + 1)
     Tb = serl_amd.CitationVecEnv(N, 'noise', t_max=T_SHORT, refs=refs, engine=engine, sensor_noise=table)
     od, ot = D.reset(), Tb.reset()
+    assert D.last_step_kernel == ('wave' if wave else 'lane') and Tb.last_step_kernel == 'lane'
     assert torch.equal(od, ot)
     assert (_np(od)[:, 3] > 999.0).all()                    # p carries the large bias
     g = torch.Generator(device='cpu').manual_seed(9)
     a = ((torch.rand(N, 3, generator=g, dtype=torch.float64) * 2 - 1) * 0.6).to(D.device)
     od, rd, dd, idd = D.step(a)
     ot, rt, dt, itt = Tb.step(a)
+    assert D.last_step_kernel == ('wave' if wave else 'lane') and Tb.last_step_kernel == 'lane'
     assert torch.equal(od, ot) and torch.equal(rd, rt) and torch.equal(dd, dt) and not bool(dd.any())
     for key in ('x', 'ref', 't', 'cost'):
         assert torch.equal(idd[key], itt[key]), key
@@ -256,12 +269,13 @@ def test_step_auto_noise_applies_the_callers_bias_and_scale(engine):
 
 
 # ---- generator off: the noise entry points compute what their namesakes compute ------------------------------------------------------------
-def _pair(engine, N):
-    """a gust env with a generator state that draws nothing from it (seed= only: a sensor table, action tables), and one without"""
+def _pair(engine, N, wave=False):
+    """a gust env with a generator state that draws nothing from it (seed= only: a sensor table, action tables), and one without;
+    wave: both on the wave kernels"""
     import serl_amd
     from serl_amd import builds
     tab = np.stack([builds.sensor_noise_table(EP, np.random.RandomState(300 + e)) for e in range(N)])
-    kw = dict(t_max=T_SHORT, refs=_tables(N), engine=engine, auto_reset=True, sensor_noise=tab)
+    kw = dict(t_max=T_SHORT, refs=_tables(N), engine=engine, auto_reset=True, sensor_noise=tab, kernel='wave' if wave else 'lane')
     a, b = serl_amd.CitationVecEnv(N, 'gust', seed=SEED, **kw), serl_amd.CitationVecEnv(N, 'gust', **kw)
     assert a.noise_episode is not None and not a._dev_sensor and b.noise_episode is None
     return a, b
@@ -274,8 +288,12 @@ def _same_state(a, b):
 
 def test_generator_off_reset_and_step_equal_their_namesakes(engine):
     """serl_venv_reset_noise / serl_venv_step_auto_noise with nz->sensor = 0 against serl_venv_reset / serl_venv_step_auto"""
+    generator_off_step_case(engine)
+
+
+def generator_off_step_case(engine, wave=False):
     N = 70
-    a, b = _pair(engine, N)
+    a, b = _pair(engine, N, wave)
     dev = a.device
     third = torch.arange(N, device=dev) % 3 == 0
     g = torch.Generator(device='cpu').manual_seed(9)
@@ -291,6 +309,7 @@ def test_generator_off_reset_and_step_equal_their_namesakes(engine):
         oa, ra, da, ia = a.step(acts[k] if k % 2 else acts[k].float())
         ob, rb, db, ib = b.step(acts[k] if k % 2 else acts[k].float())
         assert torch.equal(oa, ob) and torch.equal(ra, rb) and torch.equal(da, db), k
+        assert a.last_step_kernel == b.last_step_kernel == ('wave' if wave else 'lane')
         assert ia.keys() == ib.keys()
         for key in ia:
             assert torch.equal(ia[key], ib[key]), (k, key)
@@ -306,8 +325,12 @@ def test_generator_off_rollout_equals_its_namesake(engine, hidden, layers, path,
     _rollout_general, key for key and in the env state.  The step loop of an env with a generator state runs the kernels' forward where
     the other env runs torch's (serl_amd/venv.py), so the 'loop' case flies a zero actor, whose action is 0 in both: what is compared is
     serl_venv_step_auto_noise against serl_venv_step_auto on the table's actions."""
+    generator_off_rollout_case(engine, hidden, layers, path, ran)
+
+
+def generator_off_rollout_case(engine, hidden, layers, path, ran, wave=False):
     N = 70 if path == 'fused' else 5
-    a, b = _pair(engine, N)
+    a, b = _pair(engine, N, wave)
     dev = a.device
     s = _shape(hidden, layers)
     w = torch.from_numpy(np.ascontiguousarray(make_weights(s, MEMBERS, 5))).to(dev)

@@ -219,19 +219,12 @@ def test_device_noise_equals_lane_and_loop(engine, mode):
     assert (np.abs(a) <= 1.0).all() and (np.abs(a) < 1.0).any()
 
 
-def test_device_noise_episodes_replay_on_the_oracle(engine, monkeypatch):
+def test_device_noise_episodes_replay_on_the_oracle(engine):
     """every episode the wave rollout kernel flew under device noise is reproduced on the CPU oracle from serl_amd.venv_noise's tables of (seed, env,
     episode ordinal): the check tests/test_gpu_venv_noise_replay.py makes of the lane kernels, on an env made with kernel='wave'"""
-    import serl_amd
     import test_gpu_venv_noise_replay as lane_test
-    made = []
-
-    def wave_env(*a, **kw):
-        made.append(serl_amd.venv.CitationVecEnv(*a, kernel='wave', **kw))
-        return made[-1]
-    monkeypatch.setattr(serl_amd, 'CitationVecEnv', wave_env)
-    lane_test._replay_case(engine, 'gust', 5, 8, 1, 'fused', 'fused-wave')
-    assert made and made[0]._wave and made[0].last_rollout_path == 'fused-wave'
+    env = lane_test._replay_case(engine, 'gust', 5, 8, 1, 'fused', 'fused-wave', kernel='wave')
+    assert env._wave and env.last_rollout_path == 'fused-wave'
 
 
 # ---- 5. frozen envs, mixing with step(), chaining ------------------------------------------------------------------------------------------

@@ -332,19 +332,13 @@ def test_device_noise_equals_lane(engine, mode):
     _same_state(lane, wave)
 
 
-def test_device_noise_replays_on_the_oracle(engine, monkeypatch):
+def test_device_noise_replays_on_the_oracle(engine):
     """the step loop of a device-noise env on the wave kernels: every episode it flew is replayed on the CPU oracle from (seed, env, episode ordinal)
-    through serl_amd.venv_noise -- the check tests/test_gpu_venv_noise_replay.py makes of the lane kernels"""
-    import serl_amd
+    through serl_amd.venv_noise -- the check tests/test_gpu_venv_noise_replay.py makes of the lane kernels (which asserts the family of the env and
+    of its noise-free twin)"""
     import test_gpu_venv_noise_replay as lane_test
-    made = []
-
-    def wave_env(*a, **kw):
-        made.append(serl_amd.venv.CitationVecEnv(*a, kernel='wave', **kw))
-        return made[-1]
-    monkeypatch.setattr(serl_amd, 'CitationVecEnv', wave_env)
-    lane_test._replay_case(engine, 'gust', 5, 8, 1, 'loop', 'loop')
-    assert made and all(e._wave for e in made) and made[-1].last_step_kernel == 'wave'
+    env = lane_test._replay_case(engine, 'gust', 5, 8, 1, 'loop', 'loop', kernel='wave')
+    assert env._wave and env.last_step_kernel == 'wave'
 
 
 # ---- 7. refusals that need a context -------------------------------------------------------------------------------------------------
