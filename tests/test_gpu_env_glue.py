@@ -43,11 +43,14 @@ _PADDED = {}
 
 
 def _expected(sc, T):
-    """(the scenario on its table padded with zero rows to T, its flight by the Python env): flown once, shared, never changed"""
+    """(the scenario on its table padded with zero rows to T, its flight by the Python env): flown once, shared, never changed.  A dict that is not
+    one of G.scenarios() (a changed copy under a name of its own) is flown by G.fly as it is."""
     if (sc['name'], T) not in _PADDED:
         n = len(sc['ref'])
+        stock = any(s is sc for s in G.scenarios())      # (the cache is keyed by name: a changed copy under a stock name would get, or leave, the wrong flight)
+        assert stock or sc['name'] not in [s['name'] for s in G.scenarios()], 'a changed copy of %s needs a name of its own' % sc['name']
         if n == T:
-            _PADDED[sc['name'], T] = sc, G.flown(sc['name'])
+            _PADDED[sc['name'], T] = sc, (G.flown(sc['name']) if stock else G.fly(sc))
         else:
             def pad(a, rows):
                 return None if a is None else np.concatenate([a, np.zeros((rows - len(a),) + a.shape[1:], a.dtype)])
@@ -91,13 +94,31 @@ FUSED_CASES = [(key, kern) for key in FUSED for kern in (ATT_KERNELS if (key[1],
 @pytest.mark.parametrize('key,kern', FUSED_CASES, ids=['%s-%s' % (_id(k), kn) for k, kn in FUSED_CASES])
 def test_fused_rollout_families_on_the_scenarios(engine, key, kern):
     build, cfg, incr, _, t_max = key
-    scs0 = FUSED[key]
+
+    def check_ran(eng):      # (what the kernel() block asserts on its way out, here right behind the launch)
+        if isinstance(kern, int):
+            ran(eng, 'lane', episodes_per_team=kern)
+        else:
+            ran(eng, *sorted(FAMILIES_OF_HINT[kern]))
+        if (cfg, incr) != (G.ATTITUDE, False):
+            ran(eng, 'teamx' if kern == 'team' else 'wavex')
+
+    with kernel(kern, engine):
+        fused_case(engine, FUSED[key], build, cfg, incr, t_max, dict(lanes_per_wave=kern if isinstance(kern, int) else 0), check_ran, what=str(kern))
+
+
+def fused_case(eng, scs0, build, cfg, incr, t_max, launch_kw, check_ran, H=32, L=3, what=''):
+    """ONE launch of `eng` that flies the scenarios `scs0` as its episodes 0, 1, ... in the order given.  A scenario may come more than once: every
+    episode has its own zero-weight S-HxL-A actor row, action-noise row and sensor-noise row, and flies on its table padded to the longest.
+    launch_kw: further keywords of RolloutEngine.rollout (kernel, lanes_per_wave); check_ran(eng) asserts WHAT was launched, right behind the launch.
+    Every episode is compared at ZERO tolerance with env_glue.fly of its padded scenario: length, states, executed command, rewards, transitions,
+    fitness, length_t, cost_steps.  -> the launch's outputs as arrays"""
     T = max(len(s['ref']) for s in scs0)
     pairs = [_expected(s, T) for s in scs0]
     scs = [p for p, _ in pairs]
     E = len(scs)
     S, A = scs[0]['S'], scs[0]['A']
-    net = dict(state_dim=S, action_dim=A, hidden=32, num_layers=3, activation='tanh')
+    net = dict(state_dim=S, action_dim=A, hidden=H, num_layers=L, activation='tanh')
     noise_rows = [s['noise'] for s in scs if s['kind'] == 'noise']
     noise_idx, j = [], 0
     for s in scs:
@@ -105,27 +126,27 @@ def test_fused_rollout_families_on_the_scenarios(engine, key, kern):
         j += s['kind'] == 'noise'
     sn, sn_idx = _sensor(scs, T)
     kw = dict(build=build, faults=np.array([G.fault_row(s['fault']) for s in scs]), t_max=t_max, traces=True, transitions=True, sync=False,
-              env_config=cfg, incremental=incr, lanes_per_wave=kern if isinstance(kern, int) else 0,
+              env_config=cfg, incremental=incr,
               err0=np.array([s['err0'] or [0.0, 0.0, 0.0] for s in scs]), tick0=np.array([s['tick0'] or 0 for s in scs]))
     if noise_rows:
         kw.update(action_noise=np.stack(noise_rows), noise_row=np.array(noise_idx, np.int32))
     if sn is not None:
         kw.update(sensor_noise=sn, sensor_row=sn_idx)
-    with kernel(kern, engine):
-        out = engine.rollout(torch.from_numpy(_weights(scs, S, A, 32, 3)), _spec(net), np.arange(E), np.stack([s['ref'] for s in scs]), **kw)
-    if (cfg, incr) != (G.ATTITUDE, False):
-        ran(engine, 'teamx' if kern == 'team' else 'wavex')
+    kw.update(launch_kw)
+    out = eng.rollout(torch.from_numpy(_weights(scs, S, A, H, L)), _spec(net), np.arange(E), np.stack([s['ref'] for s in scs]), **kw)
+    check_ran(eng)
     out = {k: _np(v) for k, v in out.items() if torch.is_tensor(v)}
     got = [{k: v[e] for k, v in out.items()} for e in range(E)]
     for e, (s, o) in enumerate(pairs):
-        g, n, what = got[e], o['n'], '%s %s' % (kern, s['name'])
-        assert g['length_steps'] == o['length_steps'], '%s: length %d, the Python env %d' % (what, g['length_steps'], o['length_steps'])
-        np.testing.assert_array_equal(g['states'][:n], o['states'], err_msg=what + ': states')
-        np.testing.assert_array_equal(g['actions'][:n, :A], o['actions'][:, :A], err_msg=what + ': executed command')
-        np.testing.assert_array_equal(g['rewards'][:n], o['rewards'], err_msg=what + ': rewards')
-        np.testing.assert_array_equal(g['transitions'][:n], o['transitions'], err_msg=what + ': transitions')
-        assert g['fitness'] == o['fitness'], '%s: fitness %r, the Python env %r' % (what, g['fitness'], o['fitness'])
-        assert g['length_t'] == o['length_t'] and g['cost_steps'] == o['cost_steps'], what
+        g, n, ep = got[e], o['n'], '%s episode %d %s' % (what, e, s['name'])
+        assert g['length_steps'] == o['length_steps'], '%s: length %d, the Python env %d' % (ep, g['length_steps'], o['length_steps'])
+        np.testing.assert_array_equal(g['states'][:n], o['states'], err_msg=ep + ': states')
+        np.testing.assert_array_equal(g['actions'][:n, :A], o['actions'][:, :A], err_msg=ep + ': executed command')
+        np.testing.assert_array_equal(g['rewards'][:n], o['rewards'], err_msg=ep + ': rewards')
+        np.testing.assert_array_equal(g['transitions'][:n], o['transitions'], err_msg=ep + ': transitions')
+        assert g['fitness'] == o['fitness'], '%s: fitness %r, the Python env %r' % (ep, g['fitness'], o['fitness'])
+        assert g['length_t'] == o['length_t'] and g['cost_steps'] == o['cost_steps'], ep
+    return out
 
 
 # ---- CitationVecEnv --------------------------------------------------------------------------------------------------------------------

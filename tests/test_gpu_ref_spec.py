@@ -231,20 +231,31 @@ def _batch(golden, t_max):
 def test_fused_families_fly_the_edge_specs_like_their_table(engine, golden, kern, t_max):
     """team, wave, lane (4 per wavefront), two episodes per wavefront, two per team: generated == the tabulate_specs table == zero tails
     == the oracle, bit for bit (across families: through the oracle)"""
+    fused_ref_case(engine, golden, kern, t_max)
+
+
+def fused_ref_case(engine, golden, kern, t_max, launch_kw=None, check_ran=lambda eng: None, what=None):
+    """the 70 episodes of _batch on `engine` under the hint `kern` (an int: that many lanes per wavefront; None: no hint); launch_kw: further keywords
+    of every rollout (kernel=, lanes_per_wave=), check_ran(engine) behind each of the three launches; what: the label of the messages (default: kern)"""
+    what = kern if what is None else what
     w, moe, idx, o = _batch(golden, t_max)
     rows, tab, _ = _tab(t_max)
     lanes = kern if isinstance(kern, int) else 0
     kw = dict(t_max=t_max, traces=True, lanes_per_wave=lanes)
+    kw.update(launch_kw or {})
     wt = torch.from_numpy(w)
     with kernel(kern, engine):
         a = engine.rollout(wt, _spec(NET32), moe, rows[idx], **kw)
+        check_ran(engine)
         b = engine.rollout(wt, _spec(NET32), moe, np.ascontiguousarray(tab[idx]), **kw)
+        check_ran(engine)
         z = engine.rollout(wt, _spec(NET32), moe, X.specs(tail=0.0)[idx], **kw)
+        check_ran(engine)
     for key in KEYS:
         got = _np(a[key])
-        np.testing.assert_array_equal(got, _np(b[key]), err_msg='%s: %s, generated against its table' % (kern, key))
-        np.testing.assert_array_equal(got, _np(z[key]), err_msg='%s: %s, NaN against zero tails' % (kern, key))
-        np.testing.assert_array_equal(got, o[key], err_msg='%s: %s against the oracle' % (kern, key))
+        np.testing.assert_array_equal(got, _np(b[key]), err_msg='%s: %s, generated against its table' % (what, key))
+        np.testing.assert_array_equal(got, _np(z[key]), err_msg='%s: %s, NaN against zero tails' % (what, key))
+        np.testing.assert_array_equal(got, o[key], err_msg='%s: %s against the oracle' % (what, key))
     assert np.isfinite(_np(a['fitness'])).all()
 
 
