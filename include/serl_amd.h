@@ -490,6 +490,47 @@ int serl_venv_rollout_wave(serl_ctx *ctx, const serl_venv_desc *desc, const serl
                            void *stream);
 int serl_venv_rollout_wave_noise(serl_ctx *ctx, const serl_venv_desc *desc, const serl_venv_auto_desc *au,
                                  const serl_venv_rollout_desc *ro, const serl_venv_noise_desc *nz, void *stream);
+/* ---- population rollouts with the sensor and exploration noise drawn inside the kernels (SERL_ABI_VERSION stays 9: nothing above has
+ * moved; this descriptor has a layout self-check of its own, serl_rollout_noise_layout) -------------------------------------------------
+ * serl_rollout with the generator of serl_venv_noise_desc in place of the pre-drawn tables desc->sensor_noise [rows][max_steps + 1][7] and
+ * desc->action_noise [rows][max_steps][3].  Counter, stream, block and entry conventions are exactly those documented at
+ * serl_venv_noise_desc: episode e draws with counter words (env[e], episode[e], entry, stream << 16 | block); sensor entry 0 belongs to
+ * initialize()'s step and entry k + 1 to env step k, the action entry is the env step k, of which the first action_dim columns are used.
+ * What serl_venv_noise_fill writes for (seed; env[e], episode[e]) with max_steps + 1 sensor entries (mode 2) is the table path's sensor
+ * row of that episode, and with max_steps action entries (mode 3) its action row: both paths return the same bits.
+ *   env / episode   counter words 0 and 1 per episode, so that a realisation does not depend on where an episode sits in a launch or on how
+ *                   a caller groups its episodes into launches, and so that a caller can number its generations
+ *   switches        with sensor = 1, desc->sensor_row[e] < 0 still means "episode e has no sensor noise" (NULL or >= 0: it draws); with
+ *                   action = 1 the same holds for desc->noise_row (the RL actor's exploration episode riding a population launch)
+ *   kernels         second instantiations of the lane-per-episode kernels (attitude task; csrc/family_lanern.hip) and of the
+ *                   one-wavefront-per-episode kernels (every env configuration; csrc/family_wavern.hip).  desc->lanes_per_wave > 0 runs the
+ *                   lane kernels; kernel_hint WAVE the wave / wavex kernels; AUTO the lane kernels wherever serl_rollout's AUTO picks them
+ *                   (hidden 32, attitude task, alone on the GPU, >= 80 x CUs episodes) and the wave / wavex kernels otherwise.  The team,
+ *                   half and work-queue kernels have no noise instantiation: between 4 x CUs and 80 x CUs episodes this path therefore runs
+ *                   one wavefront per episode and not the team4 queue launch serl_rollout would choose. */
+typedef struct serl_rollout_noise_desc {
+  uint64_t seed;
+  const int32_t *env;               /* DEVICE [n_episodes]: counter word 0 of episode e; NULL = e */
+  const int32_t *episode;           /* DEVICE [n_episodes]: counter word 1 of episode e; NULL = 0 */
+  int32_t sensor;                   /* 1 = sensor noise from the generator (desc->sensor_noise must then be NULL); 0 = as desc says */
+  int32_t pad0;
+  double sensor_bias[7];
+  double sensor_scale[7];
+  int32_t action;                   /* 1 = exploration noise from the generator (desc->action_noise must then be NULL); 0 = as desc says */
+  int32_t pad1;
+  double action_sd;                 /* >= 0 */
+  double action_clip;               /* >= 0 */
+} serl_rollout_noise_desc;
+/* layout self-check: sizeof(serl_rollout_noise_desc), then offsetof of each member in declaration order */
+int serl_rollout_noise_layout(int32_t *out, int32_t capacity);
+/* Asynchronous on `stream`, one launch.  Besides everything serl_rollout refuses, SERL_E_INVALID before any launch for a NULL nz, nz->sensor
+ * or nz->action other than 0 / 1, desc->sensor_noise together with nz->sensor, desc->action_noise together with nz->action, action_sd < 0
+ * or action_clip < 0 (or NaN); SERL_E_UNSUPPORTED before any launch where the kernel hint -- desc->kernel_hint, or SERL_KERNEL=... for a
+ * descriptor that says AUTO -- resolves to TEAM, TEAM2, TEAM4, HALF or LANEQ.  With nz->sensor = 0 and nz->action = 0 the call computes
+ * what serl_rollout computes.  serl_last_rollout_info records the family (LANE / WAVE / WAVEX) as for serl_rollout.  serl_rollout_multi
+ * takes no such descriptor. */
+int serl_rollout_noise(serl_ctx *ctx, const serl_rollout_desc *desc, const serl_rollout_noise_desc *nz, void *stream);
+
 /* the generator's bit-level parts on the host, compiled from the kernels' text (csrc/serl_rng.h) */
 void serl_host_philox(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t out4[4]);
 double serl_host_uniform(uint32_t w0, uint32_t w1);

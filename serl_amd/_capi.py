@@ -19,7 +19,8 @@ EXPORTS = ['serl_abi_version', 'serl_last_error', 'serl_param_count', 'serl_ctx_
            'serl_venv_noise_layout', 'serl_venv_reset_noise', 'serl_venv_step_auto_noise', 'serl_venv_rollout_noise',
            'serl_venv_rollout_general_noise', 'serl_venv_noise_fill', 'serl_venv_actor_forward', 'serl_host_philox', 'serl_host_uniform',
            'serl_venv_reset_wave', 'serl_venv_step_wave', 'serl_venv_step_auto_wave', 'serl_venv_reset_wave_noise', 'serl_venv_step_auto_wave_noise',
-           'serl_venv_last_info', 'serl_venv_rollout_wave', 'serl_venv_rollout_wave_noise']
+           'serl_venv_last_info', 'serl_venv_rollout_wave', 'serl_venv_rollout_wave_noise',
+           'serl_rollout_noise', 'serl_rollout_noise_layout']
 
 
 class BuildDesc(ctypes.Structure):
@@ -100,6 +101,18 @@ class VenvNoiseDesc(ctypes.Structure):
 def expected_venv_noise_layout():
     """What serl_venv_noise_layout() must return for VenvNoiseDesc to be right."""
     return [ctypes.sizeof(VenvNoiseDesc)] + [getattr(VenvNoiseDesc, n).offset for n, _ in VenvNoiseDesc._fields_]
+
+
+class RolloutNoiseDesc(ctypes.Structure):
+    """serl_rollout_noise_desc: sensor / exploration noise drawn inside the population rollout kernels (checked against the library by serl_rollout_noise_layout)"""
+    _fields_ = [('seed', ctypes.c_uint64), ('env', VP), ('episode', VP), ('sensor', ctypes.c_int32), ('pad0', ctypes.c_int32),
+                ('sensor_bias', ctypes.c_double * 7), ('sensor_scale', ctypes.c_double * 7), ('action', ctypes.c_int32), ('pad1', ctypes.c_int32),
+                ('action_sd', ctypes.c_double), ('action_clip', ctypes.c_double)]
+
+
+def expected_rollout_noise_layout():
+    """What serl_rollout_noise_layout() must return for RolloutNoiseDesc to be right."""
+    return [ctypes.sizeof(RolloutNoiseDesc)] + [getattr(RolloutNoiseDesc, n).offset for n, _ in RolloutNoiseDesc._fields_]
 
 
 class Td3Desc(ctypes.Structure):
@@ -203,6 +216,8 @@ def lib():
     L.serl_venv_last_info.argtypes = [VP, VP]
     L.serl_venv_rollout_wave.argtypes = L.serl_venv_rollout_general.argtypes
     L.serl_venv_rollout_wave_noise.argtypes = L.serl_venv_rollout_general_noise.argtypes
+    L.serl_rollout_noise.argtypes = [VP, ctypes.POINTER(RolloutDesc), ctypes.POINTER(RolloutNoiseDesc), VP]
+    L.serl_rollout_noise_layout.argtypes = [VP, ctypes.c_int32]
     L.serl_host_philox.argtypes = [ctypes.c_uint64] + [ctypes.c_uint32] * 4 + [ctypes.POINTER(ctypes.c_uint32)]
     L.serl_host_uniform.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
     L.serl_td3_work_bytes.argtypes = [i32] * 6
@@ -247,6 +262,12 @@ def lib():
     n = L.serl_venv_noise_layout(got, len(want))
     if n != len(want) or list(got) != want:
         raise RuntimeError('serl_amd: layout of the VenvNoiseDesc mirror differs from the library (serl_venv_noise_layout): library %s, binding %s'
+                           % (list(got)[:n], want))
+    want = expected_rollout_noise_layout()
+    got = (ctypes.c_int32 * len(want))()
+    n = L.serl_rollout_noise_layout(got, len(want))
+    if n != len(want) or list(got) != want:
+        raise RuntimeError('serl_amd: layout of the RolloutNoiseDesc mirror differs from the library (serl_rollout_noise_layout): library %s, binding %s'
                            % (list(got)[:n], want))
     _lib = L
     return L

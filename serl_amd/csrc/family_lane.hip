@@ -8,6 +8,9 @@
 #ifdef SERL_VENV_NOISE
 #include "serl_rng.h"
 #endif
+#ifdef SERL_ROLLOUT_NOISE
+#include "rollout_noise.h"
+#endif
 #define CIT_V(x) SERL_PASTE(SERL_PASTE(cit_, VARIANT), x)      // cit_<variant>x: the names gen/citation_<variant>_lane.inc defines
 #define CIT_RO_LO_W CIT_V(_RO_LO_W)
 #define CIT_RO_HI_W CIT_V(_RO_HI_W)
@@ -39,18 +42,24 @@ static_assert(8 * (CIT_RO_LDS_WORDS + CIT_V(_NSLOPE)) <= 160 * 1024, "tables + i
 #ifdef CIT_WITH_CMD_IN_MEMORY      // (A/B builds around gen files made with CITW_LANE_CMDMEM=1: measured slower)
 #define CIT_CMD_IN_MEMORY 1
 #endif
+#ifndef SERL_ROLLOUT_NOISE     // (family_lanern.hip: serl_rollout_noise_kernel_<v> alone -- the work-queue body has no noise instantiation)
 #define SERL_LANE_QUEUE 1      // (rollout_variant.inc: the work-queue kernel serl_rollout_laneq_kernel_<v> beside serl_rollout_kernel_<v>)
+#endif
 #define CIT_Y_IS_STATE 1      // (gen/citation_<variant>_lane.inc: `if (major) c->Y[i] = X[i]`, i < 12 -- the outputs of step() are the states in front of the integration)
 #include "citation_step_dev.h"
 #include "rollout_variant.inc"
+#ifndef SERL_ROLLOUT_NOISE
 #include "venv_variant.inc"
+#endif
 #undef CIT_NO_AXES
 #undef CIT_B_AT
 #undef SERL_FLAVOUR_LDS
 }  // namespace bdag
 
 #define SERL_V(x) SERL_PASTE(x, VARIANT)
-#ifdef SERL_VENV_NOISE      // family_lanenz.hip: the env kernels with the in-kernel noise generator, nothing else
+#ifdef SERL_ROLLOUT_NOISE   // family_lanern.hip: the episode kernel with the in-kernel noise generator, nothing else
+void SERL_V(serl_launch_rollout_noise_)(const RolloutArgs &a, const serl_rollout_noise_desc &nz, int grid, hipStream_t stream) { bdag::SERL_V(serl_launch_rollout_noise_)(a, nz, grid, stream); }
+#elif defined(SERL_VENV_NOISE)     // family_lanenz.hip: the env kernels with the in-kernel noise generator, nothing else
 #define SERL_VNZ(x) SERL_PASTE(SERL_PASTE(x, noise_), VARIANT)
 void SERL_VNZ(serl_launch_venv_reset_)(const RolloutArgs &a, const VenvArgs &v, const serl_venv_noise_desc &nz, int grid, hipStream_t stream) { bdag::SERL_VNZ(serl_launch_venv_reset_)(a, v, nz, grid, stream); }
 void SERL_VNZ(serl_launch_venv_step_auto_)(const RolloutArgs &a, const VenvArgs &v, const serl_venv_auto_desc &au, const serl_venv_noise_desc &nz, int grid, hipStream_t stream) { bdag::SERL_VNZ(serl_launch_venv_step_auto_)(a, v, au, nz, grid, stream); }

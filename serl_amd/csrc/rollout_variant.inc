@@ -8,7 +8,11 @@
 #ifndef SERL_VENV_NOISE      // (family_lanenz.hip instantiates venv_variant.inc alone: it needs serl_stage_and_index_<v> only)
 // All 64 lanes of a wavefront enter; lanes with `active` own one episode each.  The actor forward is
 // wave-cooperative (serl_actor_forward_wave), everything else is per lane.
+#ifdef SERL_ROLLOUT_NOISE      // (family_lanern.hip: the same text a second time, drawing where nz.sensor / nz.action say so -- rollout_noise.h)
+static __device__ void V_NAME(serl_wave_episodes_)(const RolloutArgs &a, const serl_rollout_noise_desc &nz, int e, bool active)
+#else
 static __device__ void V_NAME(serl_wave_episodes_)(const RolloutArgs &a, int e, bool active)
+#endif
 {
   const serl_rollout_desc &d = a.d;
   const int lane = threadIdx.x & 63;
@@ -31,6 +35,9 @@ static __device__ void V_NAME(serl_wave_episodes_)(const RolloutArgs &a, int e, 
   int k = 0, cost_steps = 0;
   unsigned member = 0;
   bool done = !active;
+#ifdef SERL_ROLLOUT_NOISE
+  SerlRolloutNoiseKey nzk = {false, false, 0, 0};
+#endif
 
   if (active) {
     if (d.faults) f = d.faults[e];
@@ -46,6 +53,9 @@ static __device__ void V_NAME(serl_wave_episodes_)(const RolloutArgs &a, int e, 
       const int nr = d.noise_row ? d.noise_row[e] : e;
       if (nr >= 0) noise = d.action_noise + (size_t)nr * d.max_steps * 3;
     }
+#ifdef SERL_ROLLOUT_NOISE
+    nzk = serl_rollout_noise_key(d, nz, e);
+#endif
     cit_reset(&ctx, a.ro, a.t3, a.x0, a.dw0, a.dyn_dt);
     if (d.tick0) { ctx.tick = (uint32_t)d.tick0[e]; ctx.t = (double)ctx.tick * ctx.dt; }   // initialize() leaves the clock running
     ctx.bslot = SERL_FLAVOUR_LDS ? ((threadIdx.x >> 6) * SERL_LDS_B_LANES_PER_WAVE + lane) * CIT_MAX_NB : 0;
@@ -58,6 +68,9 @@ static __device__ void V_NAME(serl_wave_episodes_)(const RolloutArgs &a, int e, 
       const double *sn = snoise;
       x[0] += sn[0]; x[1] += sn[1]; x[2] += sn[2]; x[4] += sn[3]; x[5] += sn[4]; x[6] += sn[5]; x[7] += sn[6];
     }
+#ifdef SERL_ROLLOUT_NOISE
+    if (nzk.sensor) serl_rollout_noise_sensor(nz, nzk, 0, x);
+#endif
     V0 = x[3];
     if (d.err0) for (int i = 0; i < 3; ++i) err[i] = d.err0[(size_t)e * 3 + i];
     obs[0] = err[0]; obs[1] = err[1]; obs[2] = err[2];
@@ -92,6 +105,17 @@ static __device__ void V_NAME(serl_wave_episodes_)(const RolloutArgs &a, int e, 
     if (done) continue;
     // ---- env step (envs/phlabenv.py:430-482), per lane
     double u[3];
+#ifdef SERL_ROLLOUT_NOISE
+    if (nzk.action) {      // the row entry of THIS lane's step k: the lanes of a wavefront are at different steps once episodes have ended
+      double dn[3];
+      serl_rollout_noise_action(nz, nzk, k, dn);
+      for (int i = 0; i < 3; ++i) {
+        double an = serl_clip((double)act[i] + dn[i], -1.0, 1.0);
+        u[i] = low + 0.5 * (an + 1.0) * (high - low);
+        act[i] = (float)an;
+      }
+    } else
+#endif
     if (noise) {
       for (int i = 0; i < 3; ++i) {
         double an = serl_clip((double)act[i] + noise[(size_t)k * 3 + i], -1.0, 1.0);
@@ -113,6 +137,9 @@ static __device__ void V_NAME(serl_wave_episodes_)(const RolloutArgs &a, int e, 
       const double *sn = snoise + (size_t)(k + 1) * 7;
       x[0] += sn[0]; x[1] += sn[1]; x[2] += sn[2]; x[4] += sn[3]; x[5] += sn[4]; x[6] += sn[5]; x[7] += sn[6];
     }
+#ifdef SERL_ROLLOUT_NOISE
+    if (nzk.sensor) serl_rollout_noise_sensor(nz, nzk, k + 1, x);
+#endif
     if (prof) { tc2 = __builtin_readcyclecounter(); pc_dyn += tc2 - tc1; }
     double rk[3];
     if (rspec) serl_ref_generate(rspec, t, d.t_max, rk[0], rk[1], rk[2]);
@@ -347,6 +374,18 @@ static __device__ __forceinline__ int V_NAME(serl_stage_and_index_)(const Rollou
 }
 
 #ifndef SERL_VENV_NOISE
+#ifdef SERL_ROLLOUT_NOISE      // (family_lanern.hip: the episode kernel with the generator, nothing else)
+__global__ void __launch_bounds__(SERL_BLOCK) V_NAME(serl_rollout_noise_kernel_)(RolloutArgs a, const serl_rollout_noise_desc nz)
+{
+  const int e = V_NAME(serl_stage_and_index_)(a);
+  V_NAME(serl_wave_episodes_)(a, nz, e < 0 ? 0 : e, e >= 0);
+}
+
+void V_NAME(serl_launch_rollout_noise_)(const RolloutArgs &a, const serl_rollout_noise_desc &nz, int grid, hipStream_t stream)
+{
+  hipLaunchKernelGGL(V_NAME(serl_rollout_noise_kernel_), dim3(grid), dim3(a.block), 0, stream, a, nz);
+}
+#else
 __global__ void __launch_bounds__(SERL_BLOCK) V_NAME(serl_rollout_kernel_)(RolloutArgs a)
 {
   const int e = V_NAME(serl_stage_and_index_)(a);
@@ -392,6 +431,7 @@ void V_NAME(serl_launch_rollout_laneq_)(const RolloutArgs &a, int grid, hipStrea
   hipLaunchKernelGGL(V_NAME(serl_rollout_laneq_kernel_), dim3(grid), dim3(a.block), 0, stream, a);
 }
 #endif
+#endif  // SERL_ROLLOUT_NOISE
 #endif
 #undef V_NAME
 #undef V_PASTE

@@ -62,8 +62,13 @@ static __device__ __forceinline__ void W_NAME(citw_reset_)(const int wv, CitwSta
 // X = false: the attitude task (7 observations, 3 actions) every BASELINE configuration uses.  X = true: observation set, number
 // of actions and incremental (rate) control from the descriptor (serl_rollout_desc.env_config / incremental;
 // envs/phlabenv.py:84-97,174-176,205-220,377-380) -- a second instantiation, so that the default path stays as it is.
+#ifdef SERL_ROLLOUT_NOISE      // (family_wavern.hip: the same text a second time, drawing where nz.sensor / nz.action say so -- rollout_noise.h; wave-uniform)
+template <bool X>
+static __device__ void W_NAME(serl_wave_episode_)(const RolloutArgs &a, const serl_rollout_noise_desc &nz, const int wv, int e)
+#else
 template <bool X>
 static __device__ void W_NAME(serl_wave_episode_)(const RolloutArgs &a, const int wv, int e)
+#endif
 {
   const serl_rollout_desc &d = a.d;
   const int lane = threadIdx.x & 63;
@@ -93,6 +98,9 @@ static __device__ void W_NAME(serl_wave_episode_)(const RolloutArgs &a, const in
     const int nr = d.noise_row ? d.noise_row[e] : e;
     if (nr >= 0) noise = d.action_noise + (size_t)nr * d.max_steps * 3;
   }
+#ifdef SERL_ROLLOUT_NOISE
+  const SerlRolloutNoiseKey nzk = serl_rollout_noise_key(d, nz, e);
+#endif
   CitwState s;
   double cmd[10], x[12], err[3] = {0, 0, 0}, obs[NO], u[3] = {0, 0, 0};
 #pragma unroll
@@ -148,6 +156,18 @@ static __device__ void W_NAME(serl_wave_episode_)(const RolloutArgs &a, const in
       }
       // ---- env step (envs/phlabenv.py:430-482), wave-uniform
       double scl[3] = {0.0, 0.0, 0.0};
+#ifdef SERL_ROLLOUT_NOISE
+      if (nzk.action) {      // every lane makes the same draw; the first A columns of the entry are used
+        double dn[3];
+        serl_rollout_noise_action(nz, nzk, k, dn);
+        for (int i = 0; i < 3; ++i) {
+          if (i >= A) continue;
+          double an = serl_clip((double)act[i] + dn[i], -1.0, 1.0);
+          scl[i] = low + 0.5 * (an + 1.0) * (high - low);
+          act[i] = (float)an;
+        }
+      } else
+#endif
       if (noise) {
         for (int i = 0; i < 3; ++i) {
           if (i >= A) continue;
@@ -174,6 +194,9 @@ static __device__ void W_NAME(serl_wave_episode_)(const RolloutArgs &a, const in
       const double *sn = snoise + (size_t)(k + 1) * 7;
       x[0] += sn[0]; x[1] += sn[1]; x[2] += sn[2]; x[4] += sn[3]; x[5] += sn[4]; x[6] += sn[5]; x[7] += sn[6];
     }
+#ifdef SERL_ROLLOUT_NOISE
+    if (nzk.sensor) serl_rollout_noise_sensor(nz, nzk, k + 1, x);      // (k == -1: entry 0, initialize()'s step)
+#endif
     if (prof) { tc2 = __builtin_readcyclecounter(); pc_dyn += tc2 - tc1; }
     if (k < 0) {
       V0 = x[3];
@@ -273,6 +296,35 @@ static __device__ __forceinline__ void W_NAME(citw_stage_)(const RolloutArgs &a)
 }
 
 #ifndef SERL_WAVE_STEP_ONLY
+#ifdef SERL_ROLLOUT_NOISE      // (family_wavern.hip: the two episode kernels with the generator, nothing else)
+__global__ void __launch_bounds__(64 * CITW_MAX_WAVES) W_NAME(serl_rollout_wave_noise_kernel_)(RolloutArgs a, const serl_rollout_noise_desc nz)
+{
+  W_NAME(citw_stage_)(a);
+  const int wave = threadIdx.x >> 6;
+  const int e = blockIdx.x * (blockDim.x >> 6) + wave;
+  if (e >= a.d.n_episodes) return;
+  W_NAME(serl_wave_episode_)<false>(a, nz, wave, e);
+}
+
+__global__ void __launch_bounds__(64 * CITW_MAX_WAVES) W_NAME(serl_rollout_wavex_noise_kernel_)(RolloutArgs a, const serl_rollout_noise_desc nz)
+{
+  W_NAME(citw_stage_)(a);
+  const int wave = threadIdx.x >> 6;
+  const int e = blockIdx.x * (blockDim.x >> 6) + wave;
+  if (e >= a.d.n_episodes) return;
+  W_NAME(serl_wave_episode_)<true>(a, nz, wave, e);
+}
+
+void W_NAME(serl_launch_rollout_wave_noise_)(const RolloutArgs &a, const serl_rollout_noise_desc &nz, int grid, hipStream_t stream)
+{
+  hipLaunchKernelGGL(W_NAME(serl_rollout_wave_noise_kernel_), dim3(grid), dim3(a.block), 0, stream, a, nz);
+}
+
+void W_NAME(serl_launch_rollout_wavex_noise_)(const RolloutArgs &a, const serl_rollout_noise_desc &nz, int grid, hipStream_t stream)
+{
+  hipLaunchKernelGGL(W_NAME(serl_rollout_wavex_noise_kernel_), dim3(grid), dim3(a.block), 0, stream, a, nz);
+}
+#else
 __global__ void __launch_bounds__(64 * CITW_MAX_WAVES) W_NAME(serl_rollout_wave_kernel_)(RolloutArgs a)
 {
 #ifdef CITW_PROFILE
@@ -327,6 +379,7 @@ void W_NAME(serl_launch_rollout_wavex_)(const RolloutArgs &a, int grid, hipStrea
 {
   hipLaunchKernelGGL(W_NAME(serl_rollout_wavex_kernel_), dim3(grid), dim3(a.block), 0, stream, a);
 }
+#endif  // SERL_ROLLOUT_NOISE
 #endif  // SERL_WAVE_STEP_ONLY
 #undef W_NAME
 #undef W_EVAL

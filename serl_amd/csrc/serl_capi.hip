@@ -108,6 +108,19 @@ struct SerlVwrLaunchers { SERL_VWR_LAUNCHERS(SERL_MEMBER, v) };
 SERL_VARIANTS(SERL_VWR_VARIANT_DECL)
 static const SerlVwrLaunchers k_vwr_launchers[] = {SERL_VARIANTS(SERL_VWR_VARIANT_ROW)};
 
+// the population rollout kernels with the in-kernel noise generator (family_lanern.hip, family_wavern.hip: rollout_variant.inc / rollout_wave.inc under
+// SERL_ROLLOUT_NOISE), one record per code variant as above
+typedef void SerlLaunchNz(const RolloutArgs &a, const serl_rollout_noise_desc &nz, int grid, hipStream_t stream);
+#define SERL_RN_LAUNCHERS(X, v)                                  \
+  X(SerlLaunchNz, lane, serl_launch_rollout_noise_##v)           \
+  X(SerlLaunchNz, wave, serl_launch_rollout_wave_noise_##v)      \
+  X(SerlLaunchNz, wavex, serl_launch_rollout_wavex_noise_##v)
+struct SerlRnLaunchers { SERL_RN_LAUNCHERS(SERL_MEMBER, v) };
+#define SERL_RN_VARIANT_DECL(v, code) SERL_RN_LAUNCHERS(SERL_DECL, v)
+#define SERL_RN_VARIANT_ROW(v, code) {SERL_RN_LAUNCHERS(SERL_INIT, v)},
+SERL_VARIANTS(SERL_RN_VARIANT_DECL)
+static const SerlRnLaunchers k_rn_launchers[] = {SERL_VARIANTS(SERL_RN_VARIANT_ROW)};
+
 #include "serl_mixed.h"
 
 static void serl_launch_rollout_teamg(const SerlLaunchers &L, int groups, const RolloutArgs &a, int grid, hipStream_t stream)
@@ -689,6 +702,79 @@ int serl_rollout(serl_ctx *c, const serl_rollout_desc *d, void *stream_)
   }
   if (timed) HIP_TRY(hipEventRecord(c->ev0, stream));
   L.lane(a, grid, stream);
+  HIP_TRY(hipGetLastError());
+  if (a.wt) HIP_TRY(hipEventRecord(c->wt_done[c->wt_slot_of_launch], stream));
+  serl_note_launch(c, SERL_FAMILY_LANE, grid, lanes, false, 0, true, 1, s.code);
+  if (timed) HIP_TRY(hipEventRecord(c->ev1, stream));
+  c->timed = timed;
+  return SERL_OK;
+}
+
+int serl_rollout_noise_layout(int32_t *out, int32_t capacity)
+{
+#define SERL_OFF(m) (int32_t)offsetof(serl_rollout_noise_desc, m)
+  const int32_t v[] = {(int32_t)sizeof(serl_rollout_noise_desc), SERL_OFF(seed), SERL_OFF(env), SERL_OFF(episode), SERL_OFF(sensor), SERL_OFF(pad0),
+                       SERL_OFF(sensor_bias), SERL_OFF(sensor_scale), SERL_OFF(action), SERL_OFF(pad1), SERL_OFF(action_sd), SERL_OFF(action_clip)};
+#undef SERL_OFF
+  const int32_t n = (int32_t)(sizeof(v) / sizeof(v[0]));
+  for (int32_t i = 0; out && i < n && i < capacity; ++i) out[i] = v[i];
+  return n;
+}
+
+// serl_rollout with the sensor / exploration noise drawn inside the kernels: the noise instantiations of the lane-per-episode kernel (lanes_per_wave > 0, or
+// AUTO where serl_rollout's AUTO runs the lane kernel) and of the one-wavefront-per-episode kernels (everything else; the team, half and work-queue kernels
+// have no such instantiation).  Launch geometry, weight regrouping, timing events and the launch record are serl_rollout's for the same family.
+int serl_rollout_noise(serl_ctx *c, const serl_rollout_desc *d, const serl_rollout_noise_desc *nz, void *stream_)
+{
+  int hint = SERL_KERNEL_AUTO;
+  { const int rc_ = serl_check_desc(c, d, &hint); if (rc_ != SERL_OK) return rc_; }
+  if (!nz) return fail(SERL_E_INVALID, "serl_rollout_noise: nz is NULL");
+  if ((nz->sensor != 0 && nz->sensor != 1) || (nz->action != 0 && nz->action != 1)) return fail(SERL_E_INVALID, "serl_rollout_noise: nz->sensor / nz->action must be 0 or 1");
+  if (d->sensor_noise && nz->sensor) return fail(SERL_E_INVALID, "serl_rollout_noise: desc->sensor_noise together with nz->sensor");
+  if (d->action_noise && nz->action) return fail(SERL_E_INVALID, "serl_rollout_noise: desc->action_noise together with nz->action");
+  if (!(nz->action_sd >= 0.0) || !(nz->action_clip >= 0.0)) return fail(SERL_E_INVALID, "serl_rollout_noise: nz->action_sd / nz->action_clip < 0");
+  if (hint != SERL_KERNEL_AUTO && hint != SERL_KERNEL_WAVE)
+    return fail(SERL_E_UNSUPPORTED, "serl_rollout_noise: the TEAM / TEAM2 / TEAM4 / HALF / LANEQ kernels have no noise instantiation (kernel_hint AUTO or WAVE, or lanes_per_wave > 0)");
+  const bool general_env = d->env_config != SERL_ENV_ATTITUDE || d->incremental != 0;
+  HIP_TRY(hipSetDevice(c->device));
+  const BuildSlot &s = c->slots[d->build_slot];
+  const SerlRnLaunchers &L = k_rn_launchers[s.code];
+  hipStream_t stream = (hipStream_t)stream_;
+  RolloutArgs a;
+  serl_fill_args(c, d, a);
+  a.e0 = 0; a.e_end = d->n_episodes;
+  const bool timed = d->concurrent_episodes <= 0;
+  const int together = d->n_episodes + (d->concurrent_episodes > 0 ? d->concurrent_episodes : 0);
+  int lanes = d->lanes_per_wave;
+  // where serl_rollout's AUTO runs the lane kernel (the saturating regime: from 80 episodes per CU on, the SERL50 actor shape, alone on the GPU)
+  if (!general_env && lanes <= 0 && hint == SERL_KERNEL_AUTO && d->concurrent_episodes <= 0 && serl_has_lane_kernel(s.code) && d->hidden == 32 &&
+      d->state_dim == 7 && d->action_dim == 3 && d->n_episodes >= 80 * c->num_cus)
+    lanes = 64;
+  if (lanes <= 0) {      // one wavefront per episode: wavex for the env configurations other than the attitude task
+    const int wpb = serl_wave_kernel_waves_per_block(c, together + (timed ? 0 : 16));
+    a.lanes = 1;
+    a.block = 64 * wpb;
+    const int grid = (d->n_episodes + wpb - 1) / wpb;
+    if (timed) HIP_TRY(hipEventRecord(c->ev0, stream));
+    (general_env ? L.wavex : L.wave)(a, *nz, grid, stream);
+    HIP_TRY(hipGetLastError());
+    serl_note_launch(c, general_env ? SERL_FAMILY_WAVEX : SERL_FAMILY_WAVE, grid, 1, false, 0, true, 1, s.code);
+    if (timed) HIP_TRY(hipEventRecord(c->ev1, stream));
+    c->timed = timed;
+    return SERL_OK;
+  }
+  if (lanes > 64) lanes = 64;
+  a.lanes = lanes;
+  const int waves = (d->n_episodes + lanes - 1) / lanes;
+  const int wpb = serl_waves_per_block(c, waves);
+  a.block = 64 * wpb;
+  const int grid = (waves + wpb - 1) / wpb;
+  if (c->env_lane_regroup && d->hidden == 32 && d->state_dim == 7 && d->action_dim == 3 && d->n_members <= (1 << 22)) {      // (rollout_device.h serl_lane_actor_ok)
+    const int rc = serl_regroup_weights(c, d, a, stream);
+    if (rc != SERL_OK) return rc;
+  }
+  if (timed) HIP_TRY(hipEventRecord(c->ev0, stream));
+  L.lane(a, *nz, grid, stream);
   HIP_TRY(hipGetLastError());
   if (a.wt) HIP_TRY(hipEventRecord(c->wt_done[c->wt_slot_of_launch], stream));
   serl_note_launch(c, SERL_FAMILY_LANE, grid, lanes, false, 0, true, 1, s.code);

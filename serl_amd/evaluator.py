@@ -38,6 +38,7 @@ class PopResult:
     rewards: Optional[torch.Tensor] = None     # f64 [E, T]
     transitions: Optional[torch.Tensor] = None  # f32 [E, T, 20]
     episode_member: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    noise_seed: Optional[int] = None           # evaluate_pop(sensor_noise='device'): the generator's seed (the one passed, or the one drawn)
     mixed_placement: Optional[dict] = None     # a mixed-fault sweep flown as ONE launch: how its workgroups were placed (RolloutEngine.mixed_placement:
                                                # decision 1 = census of the CU pairs, 2 = tickets -- the GPU was shared or the pair mapping collided --, 0 = blockIdx ranges)
 
@@ -99,12 +100,28 @@ class RolloutEngine:
     # ------------------------------------------------------------------------------------------
     def rollout(self, weights, spec: NetSpec, member_of_episode, ref, *, build='h2000_v90', faults=None,
                 err0=None, tick0=None, action_noise=None, noise_row=None, sensor_noise=None, sensor_row=None, t_max=80.0, traces=False,
-                transitions=False, lanes_per_wave=0, sync=True, concurrent_episodes=0, env_config=0, incremental=False, kernel=None, launch=True):
+                transitions=False, lanes_per_wave=0, sync=True, concurrent_episodes=0, env_config=0, incremental=False, kernel=None, launch=True,
+                noise_seed=None, noise_env=None, noise_episode=None, noise_sd=None, noise_clip=None):
         """Low-level: run len(member_of_episode) episodes.  weights f32 [M, >=P] (device or host),
         ref f64 [E, T, 3] or [T, 3] radians.  env_config / incremental: builds.env_config(name) (the attitude task by
         default; the per-episode tables keep their 3-column layouts, transitions have 2 S + A + 3 columns).
         Returns dict of device tensors.  launch=False: nothing is launched -- the prepared descriptor rides along as out['_desc'] for
-        rollout_multi (one launch for the descriptors of several builds)."""
+        rollout_multi (one launch for the descriptors of several builds).
+
+        sensor_noise='device' / action_noise='device': no table -- the kernels draw the noise themselves (C ABI serl_rollout_noise: the generator of
+        CitationVecEnv, csrc/serl_rng.h).  noise_seed (required, an integer in [0, 2^64)) is the key; noise_env / noise_episode i32 [E] are counter words
+        0 and 1 of every episode (None: the episode's index in this call / 0), so episode e draws what venv_noise(noise_seed, noise_env[e],
+        noise_episode[e], T + 1, 'sensor') and venv_noise(..., T, 'action', noise_sd=, noise_clip=) write out -- the rows the table path takes.
+        noise_sd / noise_clip (>= 0) belong to action_noise='device'.  sensor_row / noise_row i32 [E] keep their meaning as masks: < 0 = this episode
+        has no such noise.  Runs the lane kernels (lanes_per_wave > 0, or where the library's choice falls on them) or the wave / wavex kernels;
+        kernel= 'team', 'team2', 'team4', 'half', 'laneq' and launch=False are refused."""
+        dev_noise = self._check_device_noise(len(np.asarray(member_of_episode).reshape(-1)), sensor_noise, action_noise, sensor_row, noise_row, noise_seed,
+                                             noise_env, noise_episode, noise_sd, noise_clip, kernel if kernel is not None else getattr(self, 'kernel_hint', None), launch)
+        dev_sensor, dev_action = dev_noise is not None and dev_noise[0], dev_noise is not None and dev_noise[1]
+        if dev_sensor:
+            sensor_noise = None
+        if dev_action:
+            action_noise = None
         S_, A_ = builds.env_dims(env_config, incremental)
         if (spec.state_dim, spec.action_dim) != (S_, A_):
             raise ValueError('actor %d -> %d does not fit the env configuration (%d observations, %d actions)'
@@ -171,6 +188,22 @@ class RolloutEngine:
                 assert an.dim() == 3 and an.shape[1:] == (T, 3) and nr.numel() == E and int(nr.max()) < an.shape[0]
                 d.noise_row = nr.data_ptr(); keep.append(nr)
             d.action_noise = an.data_ptr(); keep.append(an)
+        nz = None
+        if dev_noise is not None:
+            if dev_sensor and sensor_row is not None:
+                sr = torch.as_tensor(np.asarray(sensor_row), dtype=torch.int32).to(dev).contiguous()
+                d.sensor_row = sr.data_ptr(); keep.append(sr)
+            if dev_action and noise_row is not None:
+                nr = torch.as_tensor(np.asarray(noise_row), dtype=torch.int32).to(dev).contiguous()
+                d.noise_row = nr.data_ptr(); keep.append(nr)
+            bias, scale = builds.sensor_bias_scale()
+            nz = _capi.RolloutNoiseDesc(seed=int(noise_seed), sensor=int(dev_sensor), sensor_bias=(ctypes.c_double * 7)(*bias),
+                                        sensor_scale=(ctypes.c_double * 7)(*scale), action=int(dev_action), action_sd=float(noise_sd or 0.0),
+                                        action_clip=float(noise_clip or 0.0))
+            for name, v in (('env', noise_env), ('episode', noise_episode)):
+                if v is not None:
+                    t = torch.as_tensor(np.asarray(v, dtype=np.int32).reshape(E)).to(dev).contiguous()
+                    setattr(nz, name, t.data_ptr()); keep.append(t)
         if traces:      # True: actions + states + rewards; 'actions': only the action trace (what calc_smoothness needs)
             out['actions'] = torch.zeros(E, T, 3, dtype=torch.float64, device=dev)
             d.actions = out['actions'].data_ptr()
@@ -186,7 +219,10 @@ class RolloutEngine:
             out['_desc'] = d
             return out
         stream = torch.cuda.current_stream(dev).cuda_stream
-        _capi.check(self.lib.serl_rollout(self.ctx, ctypes.byref(d), ctypes.c_void_p(stream)), 'serl_rollout')
+        if nz is not None:
+            _capi.check(self.lib.serl_rollout_noise(self.ctx, ctypes.byref(d), ctypes.byref(nz), ctypes.c_void_p(stream)), 'serl_rollout_noise')
+        else:
+            _capi.check(self.lib.serl_rollout(self.ctx, ctypes.byref(d), ctypes.c_void_p(stream)), 'serl_rollout')
         if sync:
             ms = ctypes.c_float()
             _capi.check(self.lib.serl_last_rollout_ms(self.ctx, ctypes.byref(ms)), 'serl_last_rollout_ms')
@@ -196,6 +232,38 @@ class RolloutEngine:
                 raise RuntimeError('reference table too short: %d episodes were still running after %d steps'
                                    % (int(bad.sum()), T))
         return out
+
+    @staticmethod
+    def _check_device_noise(E, sensor_noise, action_noise, sensor_row, noise_row, noise_seed, noise_env, noise_episode, noise_sd, noise_clip, kernel, launch):
+        """The argument checks of rollout()'s device-noise path, before any device work.  -> None (no generator in this call) or (sensor, action)."""
+        for name, v in (('sensor_noise', sensor_noise), ('action_noise', action_noise)):
+            if isinstance(v, str) and v != 'device':
+                raise ValueError("%s: None, a table or 'device', not %r" % (name, v))
+        dev_sensor, dev_action = isinstance(sensor_noise, str), isinstance(action_noise, str)
+        if dev_action:
+            if noise_sd is None or noise_clip is None or not float(noise_sd) >= 0.0 or not float(noise_clip) >= 0.0:
+                raise ValueError("action_noise='device' needs noise_sd >= 0 and noise_clip >= 0")
+        elif noise_sd is not None or noise_clip is not None:
+            raise ValueError("noise_sd / noise_clip belong to action_noise='device'")
+        if not (dev_sensor or dev_action):
+            if noise_seed is not None or noise_env is not None or noise_episode is not None:
+                raise ValueError("noise_seed / noise_env / noise_episode belong to sensor_noise='device' / action_noise='device'")
+            return None
+        if noise_seed is None or isinstance(noise_seed, bool) or int(noise_seed) != noise_seed or not 0 <= int(noise_seed) < 2**64:
+            raise ValueError('noise_seed: device noise needs an integer in [0, 2^64), not %r' % (noise_seed,))
+        for name, v in (('noise_env', noise_env), ('noise_episode', noise_episode)):
+            if v is not None:
+                a = np.asarray(v)
+                if a.shape != (E,) or a.dtype.kind not in 'iu' or (a.size and (a.min() < -2**31 or a.max() >= 2**31)):
+                    raise ValueError('%s: i32 [%d], not %s %s' % (name, E, a.dtype, a.shape))
+        for name, v, on in (('sensor_row', sensor_row, dev_sensor), ('noise_row', noise_row, dev_action)):
+            if on and v is not None and np.asarray(v).shape != (E,):
+                raise ValueError("%s: with device noise a mask i32 [%d] (< 0: the episode has no such noise), not %s" % (name, E, np.asarray(v).shape))
+        if kernel in ('team', 'team2', 'team4', 'half', 'laneq'):
+            raise ValueError("device noise runs the lane kernels (lanes_per_wave > 0) or the wave kernels (kernel='wave' / None), not kernel=%r" % (kernel,))
+        if not launch:
+            raise ValueError('device noise: launch=False (rollout_multi) takes no generator; one launch per build')
+        return dev_sensor, dev_action
 
     def rollout_multi(self, prepared):
         """ONE launch of ONE code object for the descriptors of several dynamics builds (C ABI v7 serl_rollout_multi: a mixed-fault population,
@@ -266,7 +334,7 @@ def _as_weights(actors, spec):
 def evaluate_pop(actors, *, mode='nominal', num_evals=3, refs=None, t_max=80, smooth_fitness=False,
                  spec: Optional[NetSpec] = None, engine: Optional[RolloutEngine] = None, traces=False,
                  transitions=False, err0=None, tick0=None, lanes_per_wave=0, need_smoothness=True,
-                 sensor_rng=None, concurrent=True, fused='auto', kernel=None) -> PopResult:
+                 sensor_rng=None, concurrent=True, fused='auto', kernel=None, sensor_noise=None, seed=None, noise_episode=0) -> PopResult:
     """Evaluate a whole population: `num_evals` episodes per member (agent.py:229-256).
 
     actors : sequence of Actor / GeneticAgent, or a packed f32 tensor [pop, P] (then pass `spec`)
@@ -294,7 +362,30 @@ def evaluate_pop(actors, *, mode='nominal', num_evals=3, refs=None, t_max=80, sm
     sensor_rng : modes 'noise' / 'gust' add the reference's sensor model to what step() returns; its randn draws
              come from this legacy generator (None = np.random, like the wrappers), one block of T + 1 steps per
              noisy episode in episode order, up front (builds.sensor_noise_table)
+    sensor_noise : 'device' = the sensor model's draws of the 'noise' / 'gust' episodes are made inside the kernels (RolloutEngine.rollout
+             sensor_noise='device'): no host table, no host draw.  Episode e (its index in this call, whatever build it flies in) draws
+             venv_noise(seed, e, noise_episode, T + 1); episodes of modes without a sensor model are masked out.  seed: an integer in [0, 2^64)
+             (None = drawn from np.random; PopResult.noise_seed reports it); noise_episode: counter word 1 of every episode, e.g. the
+             generation's number.  Several builds fly one launch per build (never serl_rollout_multi), on the lane or wave kernels.
+             None (default) = the host tables of sensor_rng, as before
     Episode order is member-major: e = member*num_evals + eval  (the reference's loop nest)."""
+    if sensor_noise is not None and sensor_noise != 'device':
+        raise ValueError("sensor_noise: None (host tables drawn from sensor_rng) or 'device', not %r" % (sensor_noise,))
+    dev_sensor = sensor_noise == 'device'
+    if not dev_sensor and (seed is not None or noise_episode != 0):
+        raise ValueError("seed / noise_episode belong to sensor_noise='device'")
+    if dev_sensor:
+        if sensor_rng is not None:
+            raise ValueError("sensor_rng draws the host tables; sensor_noise='device' takes seed=")
+        if seed is not None and (isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2**64):
+            raise ValueError('seed: an integer in [0, 2^64), not %r' % (seed,))
+        if isinstance(noise_episode, bool) or int(noise_episode) != noise_episode or not -2**31 <= int(noise_episode) < 2**31:
+            raise ValueError('noise_episode: an i32 integer, not %r' % (noise_episode,))
+        if (kernel if kernel is not None else getattr(engine, 'kernel_hint', None)) in ('team', 'team2', 'team4', 'half', 'laneq'):
+            raise ValueError("sensor_noise='device' runs the lane kernels (lanes_per_wave > 0) or the wave kernels (kernel='wave' / None), not kernel=%r" % (kernel,))
+        if seed is None:
+            seed = int(np.random.randint(0, 2**32)) << 32 | int(np.random.randint(0, 2**32))
+        seed = int(seed)
     engine = engine or default_engine()
     if spec is None:
         spec = spec_of(actors[0])
@@ -327,8 +418,8 @@ def evaluate_pop(actors, *, mode='nominal', num_evals=3, refs=None, t_max=80, sm
     # one kernel launch per dynamics build (be/jr/sa/se share the nominal build as per-episode fault rows; cg, ice,
     # cg-shift ... are builds of their own); launches are stream-ordered and their results scattered back
     T_ref = refsignals.n_steps_for(t_max) if generated else refs.shape[-2]
-    sensor = {e: builds.sensor_noise_table(T_ref, sensor_rng if sensor_rng is not None else np.random)
-              for e in range(E) if builds.has_sensor_noise(modes[e])}
+    sensor = {} if dev_sensor else {e: builds.sensor_noise_table(T_ref, sensor_rng if sensor_rng is not None else np.random)
+                                    for e in range(E) if builds.has_sensor_noise(modes[e])}
     groups = {}
     for e, (b, _) in enumerate(resolved):
         groups.setdefault(b, []).append(e)
@@ -352,6 +443,9 @@ def evaluate_pop(actors, *, mode='nominal', num_evals=3, refs=None, t_max=80, sm
             sn = np.stack([sensor[e] for e in noisy])
             pos = {e: j for j, e in enumerate(noisy)}
             sr = np.array([pos.get(e, -1) for e in idx], dtype=np.int32)
+        if dev_sensor and any(builds.has_sensor_noise(modes[e]) for e in idx):      # the draws are keyed by the episode's index in the CALL, not in its build's launch
+            sn, sr = 'device', np.array([0 if builds.has_sensor_noise(modes[e]) else -1 for e in idx], dtype=np.int32)
+            kw = dict(kw, noise_seed=seed, noise_env=np.asarray(idx, dtype=np.int32), noise_episode=np.full(len(idx), int(noise_episode), dtype=np.int32))
         with torch.cuda.stream(side):
             return engine.rollout(w, spec, moe[idx], (refs if (whole or len(refs) == 1) else refs[idx]) if generated else
                                   (refs if (whole or refs.dim() == 2) else refs[torch.as_tensor(idx)]), build=b,
@@ -365,7 +459,7 @@ def evaluate_pop(actors, *, mode='nominal', num_evals=3, refs=None, t_max=80, sm
     # whether the combination is eligible; if not, nothing was launched and the launches below run side by side as before.
     use_multi = False
     laneq = (kernel if kernel is not None else engine.kernel_hint) == 'laneq'      # (the library refuses it in serl_rollout_multi: one launch per build)
-    if not laneq and many and (fused is True or (fused == 'auto' and E > 2 * engine.num_cus)) and 2 <= len(groups) <= 4 and lanes_per_wave == 0 and env_cfg == 0 and not incremental and spec.hidden == 32:
+    if not laneq and not dev_sensor and many and (fused is True or (fused == 'auto' and E > 2 * engine.num_cus)) and 2 <= len(groups) <= 4 and lanes_per_wave == 0 and env_cfg == 0 and not incremental and spec.hidden == 32:
         prepared = [(np.asarray(idx), one_build(b, np.asarray(idx), cur, sync=False, launch=False)) for b, idx in groups.items()]
         if engine.rollout_multi([o for _, o in prepared]):
             use_multi = True
@@ -434,7 +528,7 @@ def evaluate_pop(actors, *, mode='nominal', num_evals=3, refs=None, t_max=80, sm
             engine._warned_tickets = True
             warnings.warn('serl_amd: the mixed-fault sweep placed its workgroups by tickets, not by the census of CU pairs (%s): the GPU was shared with '
                           'another launch or the instruction-cache pairs of this device are not (1,2)(3,4)(5,6)(7,8); expect ~10 %% less throughput' % placement)
-    return PopResult(mixed_placement=placement, fitness=fitness, returns=sh(ret), smoothness=sh(sm), length_steps=sh(ls),
+    return PopResult(mixed_placement=placement, noise_seed=seed if dev_sensor else None, fitness=fitness, returns=sh(ret), smoothness=sh(sm), length_steps=sh(ls),
                      length_t=sh(out['length_t'].cpu().numpy()), cost_steps=sh(out['cost_steps'].cpu().numpy()),
                      pop_fitness=pop_fitness, champion=int(np.argmax(pop_fitness)), worst=int(np.argmin(pop_fitness)),
                      kernel_ms=engine.last_kernel_ms,

@@ -81,7 +81,8 @@ def _episode(out, e, ref_row, smooth, smooth_fitness):
 
 def evaluate_generation(pop: Sequence, rl_agent=None, *, args, mode='nominal', t_max=20, refs=None, rl_noise=None,
                         engine: Optional[RolloutEngine] = None, replay_buffer=None, counters=None,
-                        store: bool = True, env_config=0, incremental=False, _defer_store: bool = False) -> GenerationResult:
+                        store: bool = True, env_config=0, incremental=False, _defer_store: bool = False,
+                        action_noise=None, noise_seed=None, noise_episode=0) -> GenerationResult:
     """Steps (1) and (4) of a generation in one launch.
 
     pop      : GeneticAgent / Actor sequence (one network shape); rl_agent: the RL learner's agent or None
@@ -89,11 +90,22 @@ def evaluate_generation(pop: Sequence, rl_agent=None, *, args, mode='nominal', t
     refs     : f64 [pop*num_evals (+1), T, 3] / [T, 3] radians (refsignals.tabulate), or refsignals.ref_specs rows
                [pop*num_evals (+1)] / [1] (generated in the kernel); None = base reference
     rl_noise : f64 [T, 3] clipped exploration noise; None = drawn here as agent.py:90-93 would
+    action_noise : 'device' = the RL actor's exploration noise is drawn inside the kernel instead (RolloutEngine.rollout action_noise='device' with
+               args.noise_sd / args.noise_clip; the population's episodes stay masked out): no host draw, no table.  noise_seed: an integer in
+               [0, 2^64) (None = drawn from np.random); noise_episode: counter word 1 of the draw, e.g. the generation's number -- the RL episode
+               draws venv_noise(noise_seed, pop*num_evals, noise_episode, T, 'action', noise_sd=, noise_clip=).  None (default) = the host draw
     store    : append the transitions of every member's last evaluation and of the RL episode to the buffers
     env_config / incremental : builds.env_config(name) for the other env configurations (the attitude task by default);
                DeviceReplay rings among the buffers must have been made with that configuration's dims (builds.env_dims)
     _defer_store : (evaluate_generation_sharded) stage the transitions but leave the buffers alone; the list of stored
                episodes and the staged rows come back as result.stored / result.staged"""
+    if action_noise is not None and action_noise != 'device':
+        raise ValueError("action_noise: None (the host draw, or rl_noise) or 'device', not %r" % (action_noise,))
+    dev_action = action_noise == 'device'
+    if dev_action and rl_noise is not None:
+        raise ValueError("rl_noise is the pre-drawn table; action_noise='device' takes noise_seed=")
+    if not dev_action and (noise_seed is not None or noise_episode != 0):
+        raise ValueError("noise_seed / noise_episode belong to action_noise='device'")
     engine = engine or default_engine()
     ne = int(args.num_evals)
     actors = [_actor_of(a) for a in pop]
@@ -140,8 +152,16 @@ def evaluate_generation(pop: Sequence, rl_agent=None, *, args, mode='nominal', t
         T = refs.shape[-2]
         if refs.dim() == 3:
             assert refs.shape[0] == Etot, 'one reference table per episode (pop*num_evals%s)' % (' + 1' if rl_agent is not None else '')
-    noise = None
-    if rl_agent is not None:
+    noise, nzkw = None, {}
+    if rl_agent is not None and dev_action:
+        if noise_seed is None:
+            noise_seed = int(np.random.randint(0, 2**32)) << 32 | int(np.random.randint(0, 2**32))
+        noise = 'device'
+        noise_row = np.full(Etot, -1, dtype=np.int32)
+        noise_row[-1] = 0
+        nzkw = dict(noise_seed=int(noise_seed), noise_episode=np.full(Etot, int(noise_episode), dtype=np.int32), noise_sd=float(args.noise_sd),
+                    noise_clip=float(args.noise_clip))
+    elif rl_agent is not None:
         if rl_noise is None:
             rl_noise = np.clip(args.noise_sd * np.random.randn(T, 3), -args.noise_clip, args.noise_clip)
         noise = np.asarray(rl_noise, dtype=np.float64).reshape(1, T, 3)
@@ -150,7 +170,7 @@ def evaluate_generation(pop: Sequence, rl_agent=None, *, args, mode='nominal', t
     build, row = builds.resolve_mode(mode)
     faults = None if row == builds.NOMINAL_ROW else [row] * Etot
     out = engine.rollout(pack_population(members), spec, moe, refs, build=build, faults=faults, action_noise=noise,
-                         noise_row=noise_row, t_max=t_max, traces=True, transitions=store, env_config=env_config, incremental=incremental)
+                         noise_row=noise_row, t_max=t_max, traces=True, transitions=store, env_config=env_config, incremental=incremental, **nzkw)
     ls = out['length_steps'].cpu().numpy()
     sm = metrics.calc_smoothness(out['actions'], np.abs(ls)).cpu().numpy()
     ret = out['fitness'].cpu().numpy()

@@ -18,7 +18,14 @@ The lane work queue (kernel_hint LANEQ) against today's lane family (lanes_per_w
 length: the population of tools/bench_refill.py (512 members, half shipped SERL50 actors, half untrained ones that leave the envelope within seconds), at
 1 x, 2 x and 4 x the resident lane slots (64 x 4 x CUs episodes), and one equal-length control (shipped actors only) at the largest size.  The three kernels
 alternate within every repetition; median, minimum and maximum of the kernel times (HIP events) are reported, env-steps/s = sum of length_steps over the
-median, and the three results are compared with torch.equal in the same run.  One JSON document, with the source hash, to --out."""
+median, and the three results are compared with torch.equal in the same run.  One JSON document, with the source hash, to --out.
+
+    python tools/bench_saturate.py --sensor-noise table|device [--episodes 65536] [--sn-kernel auto|wave] [--reps 5] [--out-json FILE]
+
+Mode 'noise' (the nominal build under the reference's sensor model, every episode noisy) on the same workload.  table: the host draws one
+builds.sensor_noise_table per episode from np.random ([episodes][steps + 1][7] f64), copies it to the device, and serl_rollout reads it; reported:
+host draw time, H2D time (once each) and the kernel times.  device: serl_rollout_noise draws inside the kernel; reported: the kernel times.  One JSON
+line per episode count with median / min / max of the kernel times; --out-json appends the line to a JSON list in FILE."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -39,6 +46,9 @@ ap.add_argument('--profile', action='store_true', help='with SERL_PROFILE=1 in t
 ap.add_argument('--mixed-lengths', action='store_true', help='the lane work queue against the lane family and the team4 queue launch on episodes of unequal length (see above)')
 ap.add_argument('--slots-x', default='1,2,4', help='--mixed-lengths: episode counts as multiples of the resident lane slots, 64 x 4 x CUs')
 ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'lane_queue_timing.json'), help='--mixed-lengths: where the JSON document goes')
+ap.add_argument('--sensor-noise', choices=['table', 'device'], default=None, help="mode 'noise': sensor noise from host-drawn tables or drawn inside the kernels (see above)")
+ap.add_argument('--sn-kernel', choices=['auto', 'wave'], default='auto', help='--sensor-noise: the kernel family (auto: what the library chooses)')
+ap.add_argument('--out-json', default=None, help='--sensor-noise: append the result lines to the JSON list in this file')
 a = ap.parse_args()
 eng = serl_amd.RolloutEngine(0)
 spec = serl_amd.NetSpec(7, 3, 32, 3, a.activation)
@@ -106,8 +116,60 @@ def mixed_lengths():
         f.write('\n')
 
 
+def sensor_noise():
+    from serl_amd import build as hip_build, builds
+    w = bench.make_population(a.members, 0, tag='serl50').to(eng.device)
+    ref = refsignals.tabulate(*refsignals.base_reference(a.t_max), a.t_max)
+    T = ref.shape[0]
+    kernel = None if a.sn_kernel == 'auto' else a.sn_kernel
+    for E in [int(x) for x in a.episodes.split(',')]:
+        moe = ((np.arange(E) % a.members) if a.order == 'interleaved' else (np.arange(E) // max(E // a.members, 1)) % a.members).astype(np.int32)
+        line = dict(what="mode 'noise', sensor noise %s" % ('from host tables' if a.sensor_noise == 'table' else 'drawn in the kernel'), sensor_noise=a.sensor_noise,
+                    kernel=a.sn_kernel, episodes=E, steps_per_episode=T, members=a.members, order=a.order, reps=a.reps, source_hash=hip_build.source_hash(),
+                    device=torch.cuda.get_device_name(0))
+        if a.sensor_noise == 'table':
+            t0 = time.perf_counter()
+            host = np.empty((E, T + 1, 7))
+            for e in range(E):
+                host[e] = builds.sensor_noise_table(T, np.random)
+            t1 = time.perf_counter()
+            sn = torch.from_numpy(host).to(eng.device)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            line.update(table_bytes=int(host.nbytes), host_draw_s=t1 - t0, h2d_s=t2 - t1)
+            del host
+            kw = dict(sensor_noise=sn)
+        else:
+            kw = dict(sensor_noise='device', noise_seed=0x5EED)
+        ms = []
+        for i in range(-1, a.reps):      # (-1: warm-up, not recorded)
+            out = eng.rollout(w, spec, moe, ref, t_max=a.t_max, kernel=kernel, **kw)
+            if i >= 0:
+                ms.append(eng.last_kernel_ms)
+        info = eng.last_rollout_info()
+        steps = int(out['length_steps'].abs().sum())
+        med = float(np.median(ms))
+        line.update(family=info['family'], workgroups=info['workgroups'], episodes_per_team_or_wave=info['episodes_per_team'], work_queue=info['work_queue'],
+                    kernel_ms=[round(v, 2) for v in ms], median_ms=round(med, 2), min_ms=round(min(ms), 2), max_ms=round(max(ms), 2),
+                    spread_ms=round(max(ms) - min(ms), 2), env_steps=steps, env_steps_per_s=steps / (med * 1e-3))
+        if a.sensor_noise == 'table':
+            line['end_to_end_s'] = line['host_draw_s'] + line['h2d_s'] + med * 1e-3
+        print(json.dumps(line), flush=True)
+        if a.out_json:
+            doc = json.load(open(a.out_json)) if os.path.exists(a.out_json) else []
+            doc.append(line)
+            os.makedirs(os.path.dirname(os.path.abspath(a.out_json)), exist_ok=True)
+            with open(a.out_json, 'w') as f:
+                json.dump(doc, f, indent=1)
+                f.write('\n')
+        kw.clear()
+
+
 if a.mixed_lengths:
     mixed_lengths()
+    sys.exit(0)
+if a.sensor_noise:
+    sensor_noise()
     sys.exit(0)
 w = bench.make_population(a.members, 0, tag='serl50').to(eng.device)
 ref = refsignals.tabulate(*refsignals.base_reference(a.t_max), a.t_max)
