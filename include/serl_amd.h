@@ -745,6 +745,14 @@ int64_t serl_td3_work_bytes(int32_t n_learners, int32_t state_dim, int32_t actio
 /* layout self-check like serl_abi_layout: sizeof(serl_td3_desc), then offsetof of each member in declaration order */
 int serl_td3_layout(int32_t *out, int32_t capacity);
 int serl_td3_train(serl_ctx *ctx, const serl_td3_desc *desc, void *stream);
+/* serl_td3_train with the three dense phases (Linear forward, backward to the input, weight gradient) on the f32-in / f32-accumulate
+ * matrix cores (v_mfma_f32_16x16x4_f32) instead of scalar fmaf; everything else is the same code.  Opt-in: serl_td3_train is
+ * unchanged.  Same descriptor, same checks in the same order with the same return codes, same serl_td3_work_bytes.  Contract: every
+ * array it writes -- the four rows, the four moment rows, adam_steps, td_loss, pg_loss -- equals what serl_td3_train writes for the
+ * same descriptor, bit for bit: the matrix instruction is an f32 fmaf chain in k order with one rounding per product, and each
+ * output element's chain is fed in the scalar kernel's order (serl_amd/csrc/serl_td3_mfma.h).  `work` is scratch for both; its
+ * contents after a call are unspecified and may differ between the two (columns of samples from `batch` on). */
+int serl_td3_train_mfma(serl_ctx *ctx, const serl_td3_desc *desc, void *stream);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,7 @@ EXPORTS = ['serl_abi_version', 'serl_last_error', 'serl_param_count', 'serl_ctx_
            'serl_smoothness', 'serl_smoothness_work_size', 'serl_ga_distill', 'serl_host_sample_slots',
            'serl_venv_state_bytes', 'serl_venv_reset', 'serl_venv_step', 'serl_venv_step_auto', 'serl_venv_auto_layout',
            'serl_venv_rollout', 'serl_venv_rollout_layout', 'serl_venv_rollout_general',
-           'serl_td3_train', 'serl_td3_work_bytes', 'serl_td3_param_count', 'serl_td3_layout',
+           'serl_td3_train', 'serl_td3_train_mfma', 'serl_td3_work_bytes', 'serl_td3_param_count', 'serl_td3_layout',
            'serl_venv_noise_layout', 'serl_venv_reset_noise', 'serl_venv_step_auto_noise', 'serl_venv_rollout_noise',
            'serl_venv_rollout_general_noise', 'serl_venv_noise_fill', 'serl_venv_actor_forward', 'serl_host_philox', 'serl_host_uniform',
            'serl_venv_reset_wave', 'serl_venv_step_wave', 'serl_venv_step_auto_wave', 'serl_venv_reset_wave_noise', 'serl_venv_step_auto_wave_noise',
@@ -200,6 +200,7 @@ def lib():
     L.serl_venv_rollout_layout.argtypes = [VP, ctypes.c_int32]
     L.serl_venv_rollout_general.argtypes = L.serl_venv_rollout.argtypes
     L.serl_td3_train.argtypes = [VP, ctypes.POINTER(Td3Desc), VP]
+    L.serl_td3_train_mfma.argtypes = L.serl_td3_train.argtypes
     NZ = ctypes.POINTER(VenvNoiseDesc)
     L.serl_venv_noise_layout.argtypes = [VP, ctypes.c_int32]
     L.serl_venv_reset_noise.argtypes = [VP, ctypes.POINTER(VenvDesc), VP, VP, NZ, VP]

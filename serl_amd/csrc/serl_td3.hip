@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "serl_ctx.h"
+#include "serl_td3_mfma.h"
 
 namespace {
 
@@ -209,6 +210,31 @@ __device__ __forceinline__ void dense_bwd_w(const Ctx &c, const float *D, const 
   }
 }
 
+// The dense phases of a kernel flavour: MFMA = false runs the scalar chains above, MFMA = true the same chains, element for element in
+// the same order, on the f32 matrix cores (serl_td3_mfma.h).  Everything else in this file is shared by both flavours.
+typedef td3_mfma::Dense<LP, NW> DenseMx;
+
+template <bool MFMA>
+__device__ __forceinline__ void dense_fwd_k(const Ctx &c, const float *W, const float *bias, int N, int K, const float *X, float *Y)
+{
+  if constexpr (MFMA) DenseMx::fwd(c.wave, c.lane, c.B, W, bias, N, K, X, Y);
+  else dense_fwd(c, W, bias, N, K, X, Y);
+}
+
+template <bool MFMA>
+__device__ __forceinline__ void dense_bwd_x_k(const Ctx &c, const float *W, int N, int K, const float *D, float *Xo)
+{
+  if constexpr (MFMA) DenseMx::bwd_x(c.wave, c.lane, c.B, W, N, K, D, Xo);
+  else dense_bwd_x(c, W, N, K, D, Xo);
+}
+
+template <bool MFMA>
+__device__ __forceinline__ void dense_bwd_w_k(const Ctx &c, const float *D, const float *X, int N, int K, float *gW, bool accum)
+{
+  if constexpr (MFMA) DenseMx::bwd_w(c.wave, c.lane, c.B4, D, X, N, K, gW, accum);
+  else dense_bwd_w(c, D, X, N, K, gW, accum);
+}
+
 // g1[i] (+)= sum_b D[i][b], and with tn: g2[i] (+)= sum_b D[i][b] tn[i][b]; one wavefront per row
 __device__ __forceinline__ void row_grads(const Ctx &c, const float *D, const float *tn, int N, float *g1, float *g2, bool accum)
 {
@@ -271,6 +297,7 @@ __device__ __forceinline__ void ln_act_bwd(const Ctx &c, float *D, const float *
 
 // forward pass of `net` (parameters w) on the global input x [K0][BP]; -> the LDS tile that holds the output rows.  With a tape the
 // outputs of every layer (and n, std of the LayerNorm ones) are kept for mlp_bwd.
+template <bool MFMA>
 __device__ __forceinline__ float *mlp_fwd(const Ctx &c, const Net &net, const float *w, const float *x, float *tape)
 {
   const int nl = net_layers(net), Wd = net_width(net);
@@ -280,7 +307,7 @@ __device__ __forceinline__ float *mlp_fwd(const Ctx &c, const Net &net, const fl
   __syncthreads();
   for (int l = 0; l < nl; ++l) {
     const Layer y = net_layer(net, l);
-    dense_fwd(c, w + y.oW, w + y.ob, y.N, y.K, Tin, Tout);
+    dense_fwd_k<MFMA>(c, w + y.oW, w + y.ob, y.N, y.K, Tin, Tout);
     __syncthreads();
     float *tn = tape ? tape + (size_t)(2 * l) * Wd * BP : nullptr, *th = tape ? tn + (size_t)Wd * BP : nullptr;
     float *tsd = tape ? tape + (size_t)2 * nl * Wd * BP + (size_t)l * BP : nullptr;
@@ -301,6 +328,7 @@ __device__ __forceinline__ float *mlp_fwd(const Ctx &c, const Net &net, const fl
 
 // backward pass from D = dL/d(the last Linear's output) (an LDS tile, rows of the last layer): parameter gradients to g (laid out
 // like the row; added to when accum), unless g is NULL; with want_dx the gradient of the input is returned (an LDS tile, K0 rows).
+template <bool MFMA>
 __device__ __forceinline__ float *mlp_bwd(const Ctx &c, const Net &net, const float *w, const float *x, const float *tape, float *D, float *g, bool accum,
                           bool want_dx)
 {
@@ -312,12 +340,12 @@ __device__ __forceinline__ float *mlp_bwd(const Ctx &c, const Net &net, const fl
     if (g) {
       stage(c, l == 0 ? x : tape + (size_t)(2 * (l - 1) + 1) * Wd * BP, y.K, X);
       __syncthreads();
-      dense_bwd_w(c, D, X, y.N, y.K, g + y.oW, accum);
+      dense_bwd_w_k<MFMA>(c, D, X, y.N, y.K, g + y.oW, accum);
       row_grads(c, D, nullptr, y.N, g + y.ob, nullptr, accum);
       __syncthreads();
     }
     if (l == 0 && !want_dx) break;
-    dense_bwd_x(c, w + y.oW, y.N, y.K, D, X);
+    dense_bwd_x_k<MFMA>(c, w + y.oW, y.N, y.K, D, X);
     __syncthreads();
     float *s = D; D = X; X = s;
     if (l == 0) break;
@@ -355,6 +383,7 @@ __device__ __forceinline__ void clip_adam(const Ctx &c, float *w, float *m, floa
   __syncthreads();
 }
 
+template <bool MFMA>
 __global__ void __launch_bounds__(NT) td3_kernel(Td3Args a)
 {
   extern __shared__ float lds[];
@@ -407,25 +436,25 @@ __global__ void __launch_bounds__(NT) td3_kernel(Td3Args a)
     const float rew = on ? row[2 * S + A] : 0.0f, done = on ? row[2 * S + A + 1] : 0.0f;
     // ---- target action and target Q (td3.py:137-146)
     {
-      const float *out = mlp_fwd(c, actor, wat, in_s2, nullptr);
+      const float *out = mlp_fwd<MFMA>(c, actor, wat, in_s2, nullptr);
       if (c.g == 0)
         for (int k = 0; k < A; ++k) {
           float nz = on ? tnoise[((size_t)u * B + b) * A + k] * d.noise_sd : 0.0f;
           nz = fminf(fmaxf(nz, -d.noise_clip), d.noise_clip);
           in_sa2[(S + k) * BP + b] = fminf(fmaxf(nz + out[k * LP + b], -1.0f), 1.0f);
         }
-      const float q1 = mlp_fwd(c, critic, wct, in_sa2, nullptr)[b];
-      const float q2 = mlp_fwd(c, critic, wct + Pc1, in_sa2, nullptr)[b];
+      const float q1 = mlp_fwd<MFMA>(c, critic, wct, in_sa2, nullptr)[b];
+      const float q2 = mlp_fwd<MFMA>(c, critic, wct + Pc1, in_sa2, nullptr)[b];
       if (c.g == 0) tq[b] = rew + d.gamma * (fminf(q1, q2) * (1.0f - done));
     }
     // ---- critic loss and gradients of both twins (td3.py:149-158)
     float td = 0.0f;
     for (int k = 0; k < 2; ++k) {
-      float *out = mlp_fwd(c, critic, wc + k * Pc1, in_sa, tape_c);
+      float *out = mlp_fwd<MFMA>(c, critic, wc + k * Pc1, in_sa, tape_c);
       const float e = (on && c.g == 0) ? out[b] - tq[b] : 0.0f;
       td += block_sum(c, e * e) * invB;
       if (c.g == 0) out[b] = 2.0f * e * invB;
-      mlp_bwd(c, critic, wc + k * Pc1, in_sa, tape_c, out, g + k * Pc1, false, false);
+      mlp_bwd<MFMA>(c, critic, wc + k * Pc1, in_sa, tape_c, out, g + k * Pc1, false, false);
     }
     ++step_c;
     clip_adam(c, wc, mc, vc, g, Pc, step_c, d.lr, d.max_grad_norm);
@@ -434,16 +463,16 @@ __global__ void __launch_bounds__(NT) td3_kernel(Td3Args a)
     // ---- actor update (td3.py:177-198) with the critic just stepped
     float pg;
     {
-      float *out = mlp_fwd(c, actor, wa, in_s, tape_a);
+      float *out = mlp_fwd<MFMA>(c, actor, wa, in_s, tape_a);
       float acur[4] = {0.0f, 0.0f, 0.0f, 0.0f}, abat[4] = {0.0f, 0.0f, 0.0f, 0.0f};
       for (int k = 0; k < A; ++k) { acur[k] = out[k * LP + b]; abat[k] = in_sa[(S + k) * BP + b]; }
       __syncthreads();
       if (c.g == 0)
         for (int j = 0; j < SA; ++j) in_sa2[j * BP + b] = j < S ? in_s[j * BP + b] : acur[j - S];
-      float *q = mlp_fwd(c, critic, wc, in_sa2, tape_c);
+      float *q = mlp_fwd<MFMA>(c, critic, wc, in_sa2, tape_c);
       float loss = (on && c.g == 0) ? -q[b] * invB : 0.0f;
       if (c.g == 0) q[b] = on ? -invB : 0.0f;
-      float *dx = mlp_bwd(c, critic, wc, in_sa2, tape_c, q, nullptr, false, true);
+      float *dx = mlp_bwd<MFMA>(c, critic, wc, in_sa2, tape_c, q, nullptr, false, true);
       float da[4];
       for (int k = 0; k < A; ++k) da[k] = dx[(S + k) * LP + b];
       __syncthreads();
@@ -455,13 +484,13 @@ __global__ void __launch_bounds__(NT) td3_kernel(Td3Args a)
         }
       if (c.g == 0)
         for (int k = 0; k < A; ++k) dx[k * LP + b] = da[k] * (1.0f - acur[k] * acur[k]);
-      mlp_bwd(c, actor, wa, in_s, tape_a, dx, g, false, false);
+      mlp_bwd<MFMA>(c, actor, wa, in_s, tape_a, dx, g, false, false);
       if (cnoise) {
         // state_bar = state + rand * eps_sd; lambda_s * mse(action_batch, actor(state_bar))
         if (c.g == 0)
           for (int j = 0; j < S; ++j)
             in_s2[j * BP + b] = on ? in_s[j * BP + b] + cnoise[((size_t)n_actor * B + b) * S + j] * d.eps_sd : 0.0f;
-        float *ob = mlp_fwd(c, actor, wa, in_s2, tape_a);
+        float *ob = mlp_fwd<MFMA>(c, actor, wa, in_s2, tape_a);
         float abar[4];
         for (int k = 0; k < A; ++k) abar[k] = ob[k * LP + b];
         __syncthreads();
@@ -471,7 +500,7 @@ __global__ void __launch_bounds__(NT) td3_kernel(Td3Args a)
             loss += d.lambda_s * df * df * invBA;
             ob[k * LP + b] = -d.lambda_s * 2.0f * df * invBA * (1.0f - abar[k] * abar[k]);
           }
-        mlp_bwd(c, actor, wa, in_s2, tape_a, ob, g, true, false);
+        mlp_bwd<MFMA>(c, actor, wa, in_s2, tape_a, ob, g, true, false);
       }
       pg = block_sum(c, loss);
     }
@@ -501,6 +530,45 @@ int64_t td3_work_floats(int S, int A, int H, int L)
 bool td3_shape_ok(int S, int A, int H, int L, int B)
 {
   return H >= 4 && H <= TILE_ROWS && H % 4 == 0 && L >= 0 && L <= 4 && S >= 1 && S <= 16 && A >= 1 && A <= 4 && B >= 1 && B <= BP;
+}
+
+// both entries: the checks in one order, then the launch of the flavour asked for; `fn` names the entry in serl_last_error()
+int td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream, bool mfma, const char *fn)
+{
+  const std::string who(fn);
+  if (!c || !d) return serl_fail(SERL_E_INVALID, who + ": NULL context or descriptor");
+  if (!d->actor || !d->actor_target || !d->actor_m || !d->actor_v || !d->critic || !d->critic_target || !d->critic_m || !d->critic_v ||
+      !d->adam_steps || !d->ring || !d->slots || !d->target_noise || !d->td_loss || !d->pg_loss || !d->work)
+    return serl_fail(SERL_E_INVALID, who + ": NULL array (only caps_noise may be NULL: CAPS off)");
+  if (d->state_dim < 1 || d->action_dim < 1 || d->hidden < 1 || d->num_layers < 0 || d->batch < 1 || d->activation < 0 || d->activation > 2)
+    return serl_fail(SERL_E_INVALID, who + ": network shape / minibatch / activation");
+  if (d->n_learners < 1 || d->n_updates < 0 || d->capacity < 1 || d->slot_cols < d->batch || d->policy_update_freq < 1 || d->iteration0 < 0)
+    return serl_fail(SERL_E_INVALID, who + ": n_learners >= 1, n_updates >= 0, capacity >= 1, slot_cols >= batch, policy_update_freq >= 1, iteration0 >= 0");
+  if ((long long)d->iteration0 + d->n_updates > 2147483646LL) return serl_fail(SERL_E_INVALID, who + ": iteration0 + n_updates overflows");
+  if (!(d->lr > 0.0f) || !(d->gamma >= 0.0f) || !(d->tau >= 0.0f && d->tau <= 1.0f) || !(d->noise_sd >= 0.0f) || !(d->noise_clip >= 0.0f) ||
+      !(d->max_grad_norm > 0.0f) || !(d->eps_sd >= 0.0f) || d->lambda_s != d->lambda_s || d->lambda_t != d->lambda_t)
+    return serl_fail(SERL_E_INVALID, who + ": lr > 0, gamma >= 0, 0 <= tau <= 1, noise_sd >= 0, noise_clip >= 0, max_grad_norm > 0, eps_sd >= 0");
+  if (!td3_shape_ok(d->state_dim, d->action_dim, d->hidden, d->num_layers, d->batch))
+    return serl_fail(SERL_E_UNSUPPORTED, who + ": compiled for hidden a multiple of 4 in 4 .. 128, 0 .. 4 hidden layers, state_dim 1 .. 16, "
+                                         "action_dim 1 .. 4, minibatches of 1 .. 128 rows; other shapes train in PyTorch");
+  const int Pa = serl_param_count(d->state_dim, d->hidden, d->num_layers, d->action_dim), Pc = serl_td3_param_count(d->state_dim, d->action_dim);
+  if (d->actor_stride < Pa || d->critic_stride < Pc) return serl_fail(SERL_E_INVALID, who + ": a row stride is smaller than its parameter count");
+  if (d->ring_stride < 0 || d->slots_stride < 0 || d->noise_stride < 0 || d->caps_stride < 0 || d->loss_stride < d->n_updates)
+    return serl_fail(SERL_E_INVALID, who + ": negative learner stride, or loss_stride < n_updates");
+  if (d->work_bytes < serl_td3_work_bytes(d->n_learners, d->state_dim, d->action_dim, d->hidden, d->num_layers, d->batch))
+    return serl_fail(SERL_E_INVALID, who + ": workspace smaller than serl_td3_work_bytes");
+  const size_t lds = td3_lds_bytes();
+  if (lds > (size_t)c->lds_per_block) return serl_fail(SERL_E_UNSUPPORTED, who + ": the activation tiles do not fit this device's LDS per workgroup");
+  if (d->n_updates == 0) return SERL_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  Td3Args a;
+  a.d = *d;
+  a.work_floats = td3_work_floats(d->state_dim, d->action_dim, d->hidden, d->num_layers);
+  auto kernel = mfma ? td3_kernel<true> : td3_kernel<false>;
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kernel, dim3(d->n_learners), dim3(NT), lds, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return SERL_OK;
 }
 
 }  // namespace
@@ -539,40 +607,8 @@ int serl_td3_layout(int32_t *out, int32_t capacity)
   return n;
 }
 
-int serl_td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream)
-{
-  if (!c || !d) return serl_fail(SERL_E_INVALID, "serl_td3_train: NULL context or descriptor");
-  if (!d->actor || !d->actor_target || !d->actor_m || !d->actor_v || !d->critic || !d->critic_target || !d->critic_m || !d->critic_v ||
-      !d->adam_steps || !d->ring || !d->slots || !d->target_noise || !d->td_loss || !d->pg_loss || !d->work)
-    return serl_fail(SERL_E_INVALID, "serl_td3_train: NULL array (only caps_noise may be NULL: CAPS off)");
-  if (d->state_dim < 1 || d->action_dim < 1 || d->hidden < 1 || d->num_layers < 0 || d->batch < 1 || d->activation < 0 || d->activation > 2)
-    return serl_fail(SERL_E_INVALID, "serl_td3_train: network shape / minibatch / activation");
-  if (d->n_learners < 1 || d->n_updates < 0 || d->capacity < 1 || d->slot_cols < d->batch || d->policy_update_freq < 1 || d->iteration0 < 0)
-    return serl_fail(SERL_E_INVALID, "serl_td3_train: n_learners >= 1, n_updates >= 0, capacity >= 1, slot_cols >= batch, policy_update_freq >= 1, iteration0 >= 0");
-  if ((long long)d->iteration0 + d->n_updates > 2147483646LL) return serl_fail(SERL_E_INVALID, "serl_td3_train: iteration0 + n_updates overflows");
-  if (!(d->lr > 0.0f) || !(d->gamma >= 0.0f) || !(d->tau >= 0.0f && d->tau <= 1.0f) || !(d->noise_sd >= 0.0f) || !(d->noise_clip >= 0.0f) ||
-      !(d->max_grad_norm > 0.0f) || !(d->eps_sd >= 0.0f) || d->lambda_s != d->lambda_s || d->lambda_t != d->lambda_t)
-    return serl_fail(SERL_E_INVALID, "serl_td3_train: lr > 0, gamma >= 0, 0 <= tau <= 1, noise_sd >= 0, noise_clip >= 0, max_grad_norm > 0, eps_sd >= 0");
-  if (!td3_shape_ok(d->state_dim, d->action_dim, d->hidden, d->num_layers, d->batch))
-    return serl_fail(SERL_E_UNSUPPORTED, "serl_td3_train: compiled for hidden a multiple of 4 in 4 .. 128, 0 .. 4 hidden layers, state_dim 1 .. 16, "
-                                         "action_dim 1 .. 4, minibatches of 1 .. 128 rows; other shapes train in PyTorch");
-  const int Pa = serl_param_count(d->state_dim, d->hidden, d->num_layers, d->action_dim), Pc = serl_td3_param_count(d->state_dim, d->action_dim);
-  if (d->actor_stride < Pa || d->critic_stride < Pc) return serl_fail(SERL_E_INVALID, "serl_td3_train: a row stride is smaller than its parameter count");
-  if (d->ring_stride < 0 || d->slots_stride < 0 || d->noise_stride < 0 || d->caps_stride < 0 || d->loss_stride < d->n_updates)
-    return serl_fail(SERL_E_INVALID, "serl_td3_train: negative learner stride, or loss_stride < n_updates");
-  if (d->work_bytes < serl_td3_work_bytes(d->n_learners, d->state_dim, d->action_dim, d->hidden, d->num_layers, d->batch))
-    return serl_fail(SERL_E_INVALID, "serl_td3_train: workspace smaller than serl_td3_work_bytes");
-  const size_t lds = td3_lds_bytes();
-  if (lds > (size_t)c->lds_per_block) return serl_fail(SERL_E_UNSUPPORTED, "serl_td3_train: the activation tiles do not fit this device's LDS per workgroup");
-  if (d->n_updates == 0) return SERL_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  Td3Args a;
-  a.d = *d;
-  a.work_floats = td3_work_floats(d->state_dim, d->action_dim, d->hidden, d->num_layers);
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(td3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(td3_kernel, dim3(d->n_learners), dim3(NT), lds, (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
-  return SERL_OK;
-}
+int serl_td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream) { return td3_train(c, d, stream, false, "serl_td3_train"); }
+
+int serl_td3_train_mfma(serl_ctx *c, const serl_td3_desc *d, void *stream) { return td3_train(c, d, stream, true, "serl_td3_train_mfma"); }
 
 }  // extern "C"

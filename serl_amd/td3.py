@@ -23,6 +23,9 @@ CAPS = {'lambda_s': 0.5, 'lambda_t': 0.1, 'eps_sd': 0.05}          # td3.py:115-
 # `train` takes the fused path by default because it was measured faster than the eager float32 loop on the same MI355X at the default
 # shape (hidden 72, 3 layers, minibatch 86, CAPS on): tools/bench_td3.py, profiles/td3_fused_timing.json.
 FUSED_DEFAULT = True
+# train(dense=...): the entry point of the library and what last_path reports.  'valu' is the default: 'mfma' gives the same bits and is
+# opt-in until profiles/td3_mfma_timing.json decides otherwise.
+DENSE = {'valu': ('serl_td3_train', 'fused'), 'mfma': ('serl_td3_train_mfma', 'fused-mfma')}
 
 
 class _QNet(nn.Module):
@@ -137,7 +140,7 @@ class TD3:
         _hard_update(self.actor_target, self.actor)
         _hard_update(self.critic_target, self.critic)
         self.caps_dict = dict(CAPS) if getattr(args, 'use_caps', False) else None
-        self.last_path = None                   # 'fused' / 'eager': what the most recent train() ran
+        self.last_path = None                   # 'fused' / 'fused-mfma' / 'eager': what the most recent train() ran
 
     # ---- one eager update (td3.py:123-198); also the fallback of train() -------------------------------------------------------------
     def update_parameters(self, batch, iteration, champion_policy=False, *, noise=None, caps_noise=None):
@@ -191,10 +194,17 @@ class TD3:
             return False
         return _capi.lib().serl_td3_work_bytes(1, a.state_dim, a.action_dim, a.hidden_size, a.num_layers, int(a.batch_size)) > 0
 
-    def train(self, replay, n_updates, *, iteration0, champion_target=False, rng=random, generator=None, fused=None):
+    def train(self, replay, n_updates, *, iteration0, champion_target=False, rng=random, generator=None, fused=None, dense='valu'):
         """n_updates consecutive updates on minibatches of args.batch_size rows of `replay` (a DeviceReplay), update u with iteration
         iteration0 + u + 1 -- the loop of Agent.train_rl.  -> {'PG_obj': mean(-pg), 'TD_loss': median(td)} like train_rl.
-        fused: None = the fused kernel where it runs (FUSED_DEFAULT), False = the eager loop, True = the kernel or an error."""
+        fused: None = the fused kernel where it runs (FUSED_DEFAULT), False = the eager loop, True = the kernel or an error.
+        dense: 'valu' = serl_td3_train; 'mfma' = serl_td3_train_mfma, the same kernel with its Linear layers on the f32 matrix cores --
+        bit for bit the same result (include/serl_amd.h), the kernel or an error, never the eager loop.  Anything else, or
+        dense='mfma' with fused=False, is a ValueError before a draw is taken from `rng` / `generator`."""
+        if dense not in DENSE:
+            raise ValueError('TD3.train: dense=%r (one of %s)' % (dense, ', '.join(repr(k) for k in DENSE)))
+        if dense != 'valu' and fused is not None and not fused:
+            raise ValueError('TD3.train: dense=%r selects a fused kernel, fused=False the eager loop' % (dense,))
         a = self.args
         n_updates, B = int(n_updates), int(a.batch_size)
         S, A = a.state_dim, a.action_dim
@@ -205,16 +215,18 @@ class TD3:
             return {'PG_obj': float('nan'), 'TD_loss': float('nan')}
         if len(replay) < B:
             raise ValueError('TD3.train: %d rows in the ring, minibatches of %d' % (len(replay), B))
+        can = self.fused_supported(replay.device)
+        if dense != 'valu' and not can:
+            raise RuntimeError('TD3.train(dense=%r): %s does not run this shape / device' % (dense, DENSE[dense][0]))
         slots = _replay.sample_many(len(replay), B, n_updates, rng)
         freq = int(a.policy_update_freq)
         tn, cn = draw_noise(n_updates, B, S, A, int(iteration0), freq, self.caps_dict is not None, generator)
-        can = self.fused_supported(replay.device)
         if fused and not can:
             raise RuntimeError('TD3.train(fused=True): serl_td3_train does not run this shape / device')
-        use = can and (FUSED_DEFAULT if fused is None else bool(fused))
+        use = can and (dense != 'valu' or (FUSED_DEFAULT if fused is None else bool(fused)))
         if use:
-            td, pg = self._train_fused(replay, slots, tn, cn, int(iteration0), not champion_target)
-            self.last_path = 'fused'
+            td, pg = self._train_fused(replay, slots, tn, cn, int(iteration0), not champion_target, DENSE[dense][0])
+            self.last_path = DENSE[dense][1]
         else:
             td, pg = self._train_eager(replay, slots, tn, cn, int(iteration0), champion_target)
             self.last_path = 'eager'
@@ -235,7 +247,7 @@ class TD3:
                 pg.append(float(pgl))
         return td, pg
 
-    def _train_fused(self, replay, slots, tn, cn, iteration0, update_actor_target):
+    def _train_fused(self, replay, slots, tn, cn, iteration0, update_actor_target, entry='serl_td3_train'):
         from . import _capi
         a, dev = self.args, replay.device
         L = _capi.lib()
@@ -272,7 +284,7 @@ class TD3:
                           (work.data_ptr() if cn_d is not None else None), caps_stride=0, td_loss=td.data_ptr(), pg_loss=pg.data_ptr(),
                           loss_stride=n, work=work.data_ptr(), work_bytes=wb)
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _capi.check(L.serl_td3_train(self.engine.ctx, ctypes.byref(d), stream), 'serl_td3_train')
+        _capi.check(getattr(L, entry)(self.engine.ctx, ctypes.byref(d), stream), entry)
         torch.cuda.synchronize(dev)
         unpack_into(self.actor, rows['actor'])
         unpack_into(self.actor_target, rows['actor_target'])

@@ -6,8 +6,13 @@ device='cuda') -- what a SERL user runs today.  Both get the same rows, ring, sl
 `--reps` timed repetitions (host wall clock around a synchronised run; the fused launch also by device events), reported as median and
 range.  Results go to profiles/td3_fused_timing.json.
 
+With --dense the two flavours of the fused kernel are compared instead -- serl_td3_train ('valu') and serl_td3_train_mfma ('mfma', the
+dense phases on the f32 matrix cores) -- in one process on the same inputs, alternating, device events only; the final rows of the
+flavours are checked to be equal.  Results, with the source hash, go to profiles/td3_mfma_timing.json.
+
   python tools/bench_td3.py                      # hidden 72 / 32 / 96, 3 layers, minibatch 86, CAPS on, 2 000 updates
   python tools/bench_td3.py --hidden 72 --updates 200 --eager-updates 50 --reps 3
+  python tools/bench_td3.py --dense valu,mfma    # the same shapes, both kernels
 """
 import argparse, ctypes, json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,8 +22,12 @@ import numpy as np
 import torch
 
 
-def fused_run(engine, d, n):
-    """-> (device ms, wall ms) of one serl_td3_train launch of n updates on fresh copies of the case's rows"""
+ENTRY = {'valu': 'serl_td3_train', 'mfma': 'serl_td3_train_mfma'}
+
+
+def fused_run(engine, d, n, dense='valu', rows_out=None):
+    """-> (device ms, wall ms) of one launch of n updates of serl_td3_train (dense='mfma': serl_td3_train_mfma) on fresh copies of the
+    case's rows; with rows_out (a dict) the four rows after the launch are left in it"""
     import td3_64 as T
     from serl_amd import _capi
     L = _capi.lib()
@@ -48,11 +57,13 @@ def fused_run(engine, d, n):
     torch.cuda.synchronize()
     w0 = time.perf_counter()
     e0.record()
-    _capi.check(L.serl_td3_train(engine.ctx, ctypes.byref(desc), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'serl_td3_train')
+    _capi.check(getattr(L, ENTRY[dense])(engine.ctx, ctypes.byref(desc), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), ENTRY[dense])
     e1.record()
     torch.cuda.synchronize()
     wall = (time.perf_counter() - w0) * 1e3
     assert torch.isfinite(td).all()
+    if rows_out is not None:
+        rows_out.update({k: rows[k].cpu().numpy() for k in T.ROWS}, td=td.cpu().numpy())
     return e0.elapsed_time(e1), wall
 
 
@@ -80,11 +91,16 @@ def main():
     ap.add_argument('--eager-updates', type=int, default=300, help='updates of one eager repetition (the loop is slow; ms per update is what is compared)')
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--only-fused', action='store_true', help='one fused launch per shape and nothing else (for a kernel trace)')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'td3_fused_timing.json'))
+    ap.add_argument('--dense', default=None, help="'valu,mfma': time the flavours of the fused kernel against each other (no eager loop)")
+    ap.add_argument('--out', default=None, help='default: profiles/td3_fused_timing.json, with --dense profiles/td3_mfma_timing.json')
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, 'profiles', 'td3_mfma_timing.json' if a.dense else 'td3_fused_timing.json')
     import serl_amd
     import td3_64 as T
     engine = serl_amd.RolloutEngine(0)
+    if a.dense:
+        return dense_main(a, engine)
     res = {'device': torch.cuda.get_device_name(0), 'batch': a.batch, 'layers': a.layers, 'updates': a.updates, 'eager_updates': a.eager_updates,
            'caps': True, 'policy_update_freq': 2, 'shapes': {}}
     for H in a.hidden:
@@ -107,6 +123,35 @@ def main():
         with open(a.out, 'w') as fh:
             json.dump(res, fh, indent=1)
         print(json.dumps(res))
+
+
+def dense_main(a, engine):
+    import td3_64 as T
+    from serl_amd import build as hip_build
+    flavours = a.dense.split(',')
+    assert flavours and all(f in ENTRY for f in flavours), a.dense
+    res = {'tool': 'bench_td3 --dense ' + a.dense, 'device': torch.cuda.get_device_name(0), 'source_hash': hip_build.source_hash(), 'batch': a.batch,
+           'layers': a.layers, 'updates': a.updates, 'reps': a.reps, 'caps': True, 'policy_update_freq': 2, 'activation': 'tanh', 'shapes': {}}
+    for H in a.hidden:
+        d = T.make_case((7, 3, H, a.layers, 'tanh', a.batch, 2, 0, a.updates, 1, 1, 'small'), seed=H)
+        rows = {f: {} for f in flavours}
+        for f in flavours:
+            fused_run(engine, d, min(a.updates, 50), f)                 # warm-up
+        ms = {f: [] for f in flavours}
+        for _ in range(a.reps):                                         # alternating: a drift of the clock hits both alike
+            for f in flavours:
+                ms[f].append(fused_run(engine, d, a.updates, f, rows[f])[0] / a.updates)
+        r = {f + '_ms_per_update_device': spread(ms[f]) for f in flavours}
+        same = all(np.array_equal(rows[f][k], rows[flavours[0]][k]) for f in flavours for k in rows[f])
+        r['rows_equal'] = bool(same)
+        if 'valu' in ms and 'mfma' in ms:
+            r['valu_over_mfma_median'] = r['valu_ms_per_update_device']['median'] / r['mfma_ms_per_update_device']['median']
+        res['shapes']['H%d_L%d_B%d' % (H, a.layers, a.batch)] = r
+        print('H %d  %s  rows equal: %s' % (H, '  '.join('%s %.4f [%.4f .. %.4f] ms/update' % (f, r[f + '_ms_per_update_device']['median'],
+              r[f + '_ms_per_update_device']['min'], r[f + '_ms_per_update_device']['max']) for f in flavours), same), flush=True)
+    with open(a.out, 'w') as fh:
+        json.dump(res, fh, indent=1)
+    print(json.dumps(res))
 
 
 if __name__ == '__main__':
