@@ -754,6 +754,48 @@ int serl_td3_train(serl_ctx *ctx, const serl_td3_desc *desc, void *stream);
  * contents after a call are unspecified and may differ between the two (columns of samples from `batch` on). */
 int serl_td3_train_mfma(serl_ctx *ctx, const serl_td3_desc *desc, void *stream);
 
+/* ---- the TD3 learner with its minibatch slots and its noise drawn inside the kernel (SERL_ABI_VERSION stays 9: nothing above has
+ * moved; this descriptor has a layout self-check of its own, serl_td3_rng_layout) ---------------------------------------------------
+ * serl_td3_train / _mfma with the counter-based generator of serl_venv_noise_desc (csrc/serl_rng.h) in place of the three tables: no
+ * table, no host draw, memory independent of n_updates, and a result that is a function of (seed, learner key, absolute iteration).
+ *   bits     Philox4x32-10, key = seed, counter = (learner key, iteration, index, stream << 16 | block); the learner key of learner p of
+ *            a launch is learner0 + p; iteration = iteration0 + u + 1, so two calls of n1 and n2 updates draw what one of n1 + n2 draws
+ *   slots    stream 2, block 0, index = step i: `batch` distinct rows of [0, n_rows), uniform over the subsets, by Floyd's algorithm.
+ *            Step i = 0 .. batch - 1: j = n_rows - batch + i, t = floor(w64 (j + 1) / 2^64) with w64 = w0 << 32 | w1 of the step's
+ *            four words; column i is t unless an earlier column holds t, else j.  Column b is sample b of the kernel.  Integer only
+ *   target   stream 3, index = sample b, blocks 0 .. 1 = 4 standard normals (the Box-Muller pairs of serl_venv_noise_desc), the first
+ *            action_dim cast to f32; * noise_sd and the clamp are applied where the table path applies them
+ *   caps     stream 4, index = sample b, blocks 0 .. 3 = 16 words; uniform j = (float)(word j >> 8) * 2^-24, in [0, 1) on torch.rand's
+ *            grid; the first state_dim are used.  Drawn at actor updates (iteration % policy_update_freq == 0) only
+ * Contract: every array serl_td3_train_rng writes -- the four rows, the four moment rows, adam_steps, td_loss, pg_loss -- equals, bit
+ * for bit, what serl_td3_train (dense 0) or serl_td3_train_mfma (dense 1) writes when fed the tables of serl_td3_rng_fill: the
+ * kernels are second instantiations of the same source that differ at the slot read and the two noise reads only. */
+typedef struct serl_td3_rng_desc {
+  uint64_t seed;
+  int32_t n_rows;      /* filled rows of the ring the slots are drawn from: batch <= n_rows <= capacity */
+  int32_t learner0;    /* learner p of the launch draws with key learner0 + p */
+  int32_t dense;       /* 0 = valu, 1 = mfma */
+  int32_t caps;        /* 0 = CAPS off (as caps_noise == NULL), 1 = on */
+} serl_td3_rng_desc;
+/* layout self-check: sizeof(serl_td3_rng_desc), then offsetof of each member in declaration order */
+int serl_td3_rng_layout(int32_t *out, int32_t capacity);
+/* Asynchronous on `stream`, one launch.  desc->slots, slot_cols, target_noise, caps_noise and slots_stride / noise_stride / caps_stride
+ * are ignored (the pointers may be NULL).  Every other check of serl_td3_train runs in the same order with the same codes; then
+ * SERL_E_INVALID before any device work for a NULL rng, n_rows < batch, n_rows > capacity, learner0 + n_learners past INT32_MAX, dense
+ * or caps other than 0 / 1.  The same serl_td3_work_bytes; n_updates == 0 leaves every buffer unchanged. */
+int serl_td3_train_rng(serl_ctx *ctx, const serl_td3_desc *desc, const serl_td3_rng_desc *rng, void *stream);
+/* The replay tool: the tables serl_td3_train needs to reproduce a serl_td3_train_rng call of learner `learner` of the launch (key
+ * rng->learner0 + learner), written by the kernels' own device functions.  slots i32 [n_updates][batch], target_noise f32
+ * [n_updates][batch][action_dim], caps_noise f32 [actor updates of the call][batch][state_dim] or NULL (not written); all DEVICE.
+ * rng->dense and rng->caps are not read.  SERL_E_INVALID for a NULL argument, state_dim outside 1 .. 16, action_dim outside 1 .. 4,
+ * batch outside 1 .. 128, rng->n_rows < batch, learner < 0, n_updates < 0, policy_update_freq < 1, iteration0 < 0. */
+int serl_td3_rng_fill(serl_ctx *ctx, const serl_td3_rng_desc *rng, int32_t learner, int32_t state_dim, int32_t action_dim, int32_t batch,
+                      int32_t iteration0, int32_t n_updates, int32_t policy_update_freq, int32_t *slots, float *target_noise,
+                      float *caps_noise, void *stream);
+/* the slot draw of (seed; learner key, iteration) on the host, compiled from the kernels' text (csrc/serl_rng.h): out i32 [batch], any
+ * 1 <= batch <= n_rows (batch^2 / 2 comparisons).  SERL_E_INVALID for a NULL out, batch < 1 or n_rows < batch. */
+int serl_host_td3_slots(uint64_t seed, int32_t learner, int32_t iteration, int32_t n_rows, int32_t batch, int32_t *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,8 @@ EXPORTS = ['serl_abi_version', 'serl_last_error', 'serl_param_count', 'serl_ctx_
            'serl_venv_rollout_general_noise', 'serl_venv_noise_fill', 'serl_venv_actor_forward', 'serl_host_philox', 'serl_host_uniform',
            'serl_venv_reset_wave', 'serl_venv_step_wave', 'serl_venv_step_auto_wave', 'serl_venv_reset_wave_noise', 'serl_venv_step_auto_wave_noise',
            'serl_venv_last_info', 'serl_venv_rollout_wave', 'serl_venv_rollout_wave_noise',
-           'serl_rollout_noise', 'serl_rollout_noise_layout']
+           'serl_rollout_noise', 'serl_rollout_noise_layout',
+           'serl_td3_train_rng', 'serl_td3_rng_layout', 'serl_td3_rng_fill', 'serl_host_td3_slots']
 
 
 class BuildDesc(ctypes.Structure):
@@ -134,6 +135,17 @@ def expected_td3_layout():
     return [ctypes.sizeof(Td3Desc)] + [getattr(Td3Desc, n).offset for n, _ in Td3Desc._fields_]
 
 
+class Td3RngDesc(ctypes.Structure):
+    """serl_td3_rng_desc: the fused TD3 learner's in-kernel generator (checked against the library by serl_td3_rng_layout)"""
+    _fields_ = [('seed', ctypes.c_uint64), ('n_rows', ctypes.c_int32), ('learner0', ctypes.c_int32), ('dense', ctypes.c_int32),
+                ('caps', ctypes.c_int32)]
+
+
+def expected_td3_rng_layout():
+    """What serl_td3_rng_layout() must return for Td3RngDesc to be right."""
+    return [ctypes.sizeof(Td3RngDesc)] + [getattr(Td3RngDesc, n).offset for n, _ in Td3RngDesc._fields_]
+
+
 # serl_rollout_desc.kernel_hint (enum serl_kernel_hint)
 KERNEL_HINTS = {None: 0, 'auto': 0, 'team': 1, 'wave': 2, 'half': 3, 'team2': 4, 'team4': 5, 'laneq': 6}
 ABI_VERSION = 9
@@ -224,6 +236,10 @@ def lib():
     L.serl_td3_work_bytes.argtypes = [i32] * 6
     L.serl_td3_param_count.argtypes = [ctypes.c_int, ctypes.c_int]
     L.serl_td3_layout.argtypes = [VP, ctypes.c_int32]
+    L.serl_td3_rng_layout.argtypes = [VP, ctypes.c_int32]
+    L.serl_td3_train_rng.argtypes = [VP, ctypes.POINTER(Td3Desc), ctypes.POINTER(Td3RngDesc), VP]
+    L.serl_td3_rng_fill.argtypes = [VP, ctypes.POINTER(Td3RngDesc)] + [i32] * 7 + [VP, VP, VP, VP]
+    L.serl_host_td3_slots.argtypes = [ctypes.c_uint64, i32, i32, i32, i32, VP]
     for f in EXPORTS:
         if f == 'serl_host_uniform':
             L.serl_host_uniform.restype = ctypes.c_double
@@ -245,6 +261,12 @@ def lib():
     n = L.serl_td3_layout(got, len(want))
     if n != len(want) or list(got) != want:
         raise RuntimeError('serl_amd: layout of the Td3Desc mirror differs from the library (serl_td3_layout): library %s, binding %s'
+                           % (list(got)[:n], want))
+    want = expected_td3_rng_layout()
+    got = (ctypes.c_int32 * len(want))()
+    n = L.serl_td3_rng_layout(got, len(want))
+    if n != len(want) or list(got) != want:
+        raise RuntimeError('serl_amd: layout of the Td3RngDesc mirror differs from the library (serl_td3_rng_layout): library %s, binding %s'
                            % (list(got)[:n], want))
     want = expected_venv_auto_layout()
     got = (ctypes.c_int32 * len(want))()

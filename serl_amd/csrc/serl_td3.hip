@@ -16,7 +16,9 @@
 // (row stride 132 floats).
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <type_traits>
 #include "serl_ctx.h"
+#include "serl_rng.h"
 #include "serl_td3_mfma.h"
 
 namespace {
@@ -34,6 +36,13 @@ struct Td3Args {
   serl_td3_desc d;
   int64_t work_floats;                  // per learner
 };
+
+// the generator flavours (serl_td3_train_rng): what replaces d.slots / d.target_noise / d.caps_noise
+struct Td3Rng {
+  uint64_t seed;
+  int n_rows, learner0, caps;
+};
+struct Td3ArgsRng : Td3Args { Td3Rng rg; };
 
 __device__ __forceinline__ float t_act(float v, int act)
 {
@@ -383,8 +392,48 @@ __device__ __forceinline__ void clip_adam(const Ctx &c, float *w, float *m, floa
   __syncthreads();
 }
 
-template <bool MFMA>
-__global__ void __launch_bounds__(NT) td3_kernel(Td3Args a)
+// The minibatch of (seed; key, iteration) by ONE wavefront: Floyd's algorithm as serl_rng.h defines it (serl_td3_slots_serial is the same
+// draw by one thread).  Lane l computes the candidates of steps l and l + 64 up front (two Philox calls), then the steps run in order:
+// the chosen rows are held across the lanes (column i in lane i & 63, register i >> 6), a candidate is broadcast by readlane and tested
+// against all of them by one ballot.  At most 128 steps.  out: LDS [B].
+__device__ __forceinline__ void td3_draw_slots(uint64_t seed, int key, int iteration, int n_rows, int B, int lane, int *out)
+{
+  const int j0 = n_rows - B;
+  const int t_lo = lane < B ? serl_td3_slot_candidate(seed, key, iteration, lane, j0 + lane) : 0;
+  const int t_hi = lane + 64 < B ? serl_td3_slot_candidate(seed, key, iteration, lane + 64, j0 + lane + 64) : 0;
+  int c_lo = -1, c_hi = -1;             // columns lane and lane + 64 once chosen (-1: not yet; rows are >= 0)
+  for (int i = 0; i < B; ++i) {
+    const int t = __shfl(i < 64 ? t_lo : t_hi, i & 63);
+    const bool taken = __ballot(c_lo == t || c_hi == t) != 0ull;
+    const int r = taken ? j0 + i : t;
+    if (lane == (i & 63)) {
+      if (i < 64) c_lo = r; else c_hi = r;
+    }
+  }
+  if (lane < B) out[lane] = c_lo;
+  if (lane + 64 < B) out[lane + 64] = c_hi;
+}
+
+// the target-policy noise of sample b: standard normals, the first A of four
+__device__ __forceinline__ void td3_draw_target(uint64_t seed, int key, int iteration, int b, float (&z)[4])
+{
+  double zd[2 * SERL_RNG_TD3_TARGET_BLOCKS];
+  serl_rng_normals<SERL_RNG_TD3_TARGET_BLOCKS>(seed, key, iteration, b, SERL_RNG_TD3_TARGET, zd);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) z[k] = (float)zd[k];
+}
+
+// uniform j of sample b's CAPS draw; w holds the block of the previous call (j ascending: one Philox call per four uniforms)
+__device__ __forceinline__ float td3_draw_caps(uint64_t seed, int key, int iteration, int b, int j, uint32_t (&w)[4])
+{
+  if ((j & 3) == 0) serl_rng_words(seed, key, iteration, b, SERL_RNG_TD3_CAPS, j >> 2, w);
+  return serl_td3_caps_uniform(w[j & 3]);
+}
+
+// RNG = false: slots and draws from the caller's tables (serl_td3_train / _mfma).  RNG = true: the same source, with the slot read from
+// an LDS array one wavefront fills at the top of each update and both draws generated in registers by the thread that would read them.
+template <bool MFMA, bool RNG>
+__global__ void __launch_bounds__(NT) td3_kernel(std::conditional_t<RNG, Td3ArgsRng, Td3Args> a)
 {
   extern __shared__ float lds[];
   const serl_td3_desc &d = a.d;
@@ -392,6 +441,10 @@ __global__ void __launch_bounds__(NT) td3_kernel(Td3Args a)
   Ctx c;
   c.T0 = lds; c.T1 = c.T0 + TILE_ROWS * LP; c.red4 = c.T1 + TILE_ROWS * LP; c.red = c.red4 + NG * BP;
   float *tq = c.red + 64;               // [BP] target Q
+  int *slot_l = reinterpret_cast<int *>(tq + BP);      // [BP] the minibatch's slots (RNG only: td3_lds_bytes)
+  Td3Rng rg = {};
+  if constexpr (RNG) rg = a.rg;
+  const int key = rg.learner0 + p;
   c.t = threadIdx.x; c.b = c.t & (BP - 1); c.g = __builtin_amdgcn_readfirstlane(c.t >> 7);
   c.wave = __builtin_amdgcn_readfirstlane(c.t >> 6); c.lane = c.t & 63;
   c.B = d.batch; c.B4 = (d.batch + 3) & ~3; c.act = d.activation;
@@ -405,9 +458,10 @@ __global__ void __launch_bounds__(NT) td3_kernel(Td3Args a)
   float *wc = d.critic + (size_t)p * d.critic_stride, *wct = d.critic_target + (size_t)p * d.critic_stride;
   float *mc = d.critic_m + (size_t)p * d.critic_stride, *vc = d.critic_v + (size_t)p * d.critic_stride;
   const float *ring = d.ring + (size_t)p * d.ring_stride;
-  const int32_t *slots = d.slots + (size_t)p * d.slots_stride;
-  const float *tnoise = d.target_noise + (size_t)p * d.noise_stride;
-  const float *cnoise = d.caps_noise ? d.caps_noise + (size_t)p * d.caps_stride : nullptr;
+  const int32_t *slots = RNG ? nullptr : d.slots + (size_t)p * d.slots_stride;
+  const float *tnoise = RNG ? nullptr : d.target_noise + (size_t)p * d.noise_stride;
+  // (RNG: `cnoise` is only the CAPS switch, as a table's presence is without it -- never read)
+  const float *cnoise = RNG ? (rg.caps ? d.ring : nullptr) : (d.caps_noise ? d.caps_noise + (size_t)p * d.caps_stride : nullptr);
   float *td_loss = d.td_loss + (size_t)p * d.loss_stride, *pg_loss = d.pg_loss + (size_t)p * d.loss_stride;
   // workspace of this learner: gradients | inputs s, s2, (s, a), (s2, a2) | the actor's tape | the critic's tape
   float *wk = (float *)d.work + (size_t)p * a.work_floats;
@@ -422,10 +476,14 @@ __global__ void __launch_bounds__(NT) td3_kernel(Td3Args a)
     const int iteration = d.iteration0 + u + 1;
     // ---- the minibatch: rows slots[u][0 .. B) of the ring; samples from B on are zeros
     const bool on = b < B;
-    int slot = on ? slots[(size_t)u * d.slot_cols + b] : 0;
+    if constexpr (RNG) {
+      if (c.wave == 0) td3_draw_slots(rg.seed, key, iteration, rg.n_rows, B, c.lane, slot_l);
+      __syncthreads();
+    }
+    int slot = on ? (RNG ? slot_l[b] : slots[(size_t)u * d.slot_cols + b]) : 0;
     slot = min(max(slot, 0), d.capacity - 1);
     const float *row = ring + (size_t)slot * RW;
-    __syncthreads();
+    if constexpr (!RNG) __syncthreads();
     if (c.g == 0) {
       for (int j = 0; j < S; ++j) {
         const float s = on ? row[j] : 0.0f, s2 = on ? row[SA + j] : 0.0f;
@@ -437,9 +495,13 @@ __global__ void __launch_bounds__(NT) td3_kernel(Td3Args a)
     // ---- target action and target Q (td3.py:137-146)
     {
       const float *out = mlp_fwd<MFMA>(c, actor, wat, in_s2, nullptr);
+      float tz[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      if constexpr (RNG) {
+        if (c.g == 0 && on) td3_draw_target(rg.seed, key, iteration, b, tz);
+      }
       if (c.g == 0)
         for (int k = 0; k < A; ++k) {
-          float nz = on ? tnoise[((size_t)u * B + b) * A + k] * d.noise_sd : 0.0f;
+          float nz = on ? (RNG ? tz[k] : tnoise[((size_t)u * B + b) * A + k]) * d.noise_sd : 0.0f;
           nz = fminf(fmaxf(nz, -d.noise_clip), d.noise_clip);
           in_sa2[(S + k) * BP + b] = fminf(fmaxf(nz + out[k * LP + b], -1.0f), 1.0f);
         }
@@ -487,9 +549,17 @@ __global__ void __launch_bounds__(NT) td3_kernel(Td3Args a)
       mlp_bwd<MFMA>(c, actor, wa, in_s, tape_a, dx, g, false, false);
       if (cnoise) {
         // state_bar = state + rand * eps_sd; lambda_s * mse(action_batch, actor(state_bar))
+        if constexpr (RNG) {
+          if (c.g == 0) {
+            uint32_t cw[4] = {0u, 0u, 0u, 0u};
+            for (int j = 0; j < S; ++j)
+              in_s2[j * BP + b] = on ? in_s[j * BP + b] + td3_draw_caps(rg.seed, key, iteration, b, j, cw) * d.eps_sd : 0.0f;
+          }
+        } else {
         if (c.g == 0)
           for (int j = 0; j < S; ++j)
             in_s2[j * BP + b] = on ? in_s[j * BP + b] + cnoise[((size_t)n_actor * B + b) * S + j] * d.eps_sd : 0.0f;
+        }
         float *ob = mlp_fwd<MFMA>(c, actor, wa, in_s2, tape_a);
         float abar[4];
         for (int k = 0; k < A; ++k) abar[k] = ob[k * LP + b];
@@ -517,7 +587,27 @@ __global__ void __launch_bounds__(NT) td3_kernel(Td3Args a)
   if (c.t == 0 && d.n_updates > 0) { d.adam_steps[2 * p] = step_c; d.adam_steps[2 * p + 1] = step_a; }
 }
 
-size_t td3_lds_bytes() { return ((size_t)2 * TILE_ROWS * LP + NG * BP + 64 + BP) * sizeof(float); }
+// what serl_td3_train_rng draws, written out as the tables serl_td3_train takes: one workgroup per update, the slots by its first
+// wavefront (td3_draw_slots), thread b the draws of sample b (td3_draw_target / td3_draw_caps)
+__global__ void __launch_bounds__(BP) td3_rng_fill_kernel(Td3Rng rg, int key, int S, int A, int B, int iteration0, int freq, int32_t *slots, float *tn,
+                                                          float *cn)
+{
+  __shared__ int slot_l[BP];
+  const int u = blockIdx.x, b = threadIdx.x, iteration = iteration0 + u + 1;
+  if (b < 64) td3_draw_slots(rg.seed, key, iteration, rg.n_rows, B, b, slot_l);
+  __syncthreads();
+  if (b >= B) return;
+  slots[(size_t)u * B + b] = slot_l[b];
+  float tz[4];
+  td3_draw_target(rg.seed, key, iteration, b, tz);
+  for (int k = 0; k < A; ++k) tn[((size_t)u * B + b) * A + k] = tz[k];
+  if (!cn || iteration % freq != 0) return;
+  const int n_actor = iteration / freq - iteration0 / freq - 1;      // actor updates of the call before this one
+  uint32_t cw[4] = {0u, 0u, 0u, 0u};
+  for (int j = 0; j < S; ++j) cn[((size_t)n_actor * B + b) * S + j] = td3_draw_caps(rg.seed, key, iteration, b, j, cw);
+}
+
+size_t td3_lds_bytes(bool rng) { return ((size_t)2 * TILE_ROWS * LP + NG * BP + 64 + BP + (rng ? BP : 0)) * sizeof(float); }
 
 int64_t td3_work_floats(int S, int A, int H, int L)
 {
@@ -532,17 +622,19 @@ bool td3_shape_ok(int S, int A, int H, int L, int B)
   return H >= 4 && H <= TILE_ROWS && H % 4 == 0 && L >= 0 && L <= 4 && S >= 1 && S <= 16 && A >= 1 && A <= 4 && B >= 1 && B <= BP;
 }
 
-// both entries: the checks in one order, then the launch of the flavour asked for; `fn` names the entry in serl_last_error()
-int td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream, bool mfma, const char *fn)
+// every entry: the checks in one order, then the launch of the flavour asked for; `fn` names the entry in serl_last_error().  With
+// `gen` (serl_td3_train_rng) the tables of the descriptor -- slots, slot_cols, target_noise, caps_noise and their strides -- are not
+// looked at, the generator's descriptor is checked last, and rg->dense picks the dense phases.
+int td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream, bool mfma, const char *fn, bool gen = false, const serl_td3_rng_desc *rg = nullptr)
 {
   const std::string who(fn);
   if (!c || !d) return serl_fail(SERL_E_INVALID, who + ": NULL context or descriptor");
   if (!d->actor || !d->actor_target || !d->actor_m || !d->actor_v || !d->critic || !d->critic_target || !d->critic_m || !d->critic_v ||
-      !d->adam_steps || !d->ring || !d->slots || !d->target_noise || !d->td_loss || !d->pg_loss || !d->work)
+      !d->adam_steps || !d->ring || (!gen && (!d->slots || !d->target_noise)) || !d->td_loss || !d->pg_loss || !d->work)
     return serl_fail(SERL_E_INVALID, who + ": NULL array (only caps_noise may be NULL: CAPS off)");
   if (d->state_dim < 1 || d->action_dim < 1 || d->hidden < 1 || d->num_layers < 0 || d->batch < 1 || d->activation < 0 || d->activation > 2)
     return serl_fail(SERL_E_INVALID, who + ": network shape / minibatch / activation");
-  if (d->n_learners < 1 || d->n_updates < 0 || d->capacity < 1 || d->slot_cols < d->batch || d->policy_update_freq < 1 || d->iteration0 < 0)
+  if (d->n_learners < 1 || d->n_updates < 0 || d->capacity < 1 || (!gen && d->slot_cols < d->batch) || d->policy_update_freq < 1 || d->iteration0 < 0)
     return serl_fail(SERL_E_INVALID, who + ": n_learners >= 1, n_updates >= 0, capacity >= 1, slot_cols >= batch, policy_update_freq >= 1, iteration0 >= 0");
   if ((long long)d->iteration0 + d->n_updates > 2147483646LL) return serl_fail(SERL_E_INVALID, who + ": iteration0 + n_updates overflows");
   if (!(d->lr > 0.0f) || !(d->gamma >= 0.0f) || !(d->tau >= 0.0f && d->tau <= 1.0f) || !(d->noise_sd >= 0.0f) || !(d->noise_clip >= 0.0f) ||
@@ -553,18 +645,36 @@ int td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream, bool mfma, cons
                                          "action_dim 1 .. 4, minibatches of 1 .. 128 rows; other shapes train in PyTorch");
   const int Pa = serl_param_count(d->state_dim, d->hidden, d->num_layers, d->action_dim), Pc = serl_td3_param_count(d->state_dim, d->action_dim);
   if (d->actor_stride < Pa || d->critic_stride < Pc) return serl_fail(SERL_E_INVALID, who + ": a row stride is smaller than its parameter count");
-  if (d->ring_stride < 0 || d->slots_stride < 0 || d->noise_stride < 0 || d->caps_stride < 0 || d->loss_stride < d->n_updates)
+  if (d->ring_stride < 0 || (!gen && (d->slots_stride < 0 || d->noise_stride < 0 || d->caps_stride < 0)) || d->loss_stride < d->n_updates)
     return serl_fail(SERL_E_INVALID, who + ": negative learner stride, or loss_stride < n_updates");
   if (d->work_bytes < serl_td3_work_bytes(d->n_learners, d->state_dim, d->action_dim, d->hidden, d->num_layers, d->batch))
     return serl_fail(SERL_E_INVALID, who + ": workspace smaller than serl_td3_work_bytes");
-  const size_t lds = td3_lds_bytes();
+  const size_t lds = td3_lds_bytes(gen);
   if (lds > (size_t)c->lds_per_block) return serl_fail(SERL_E_UNSUPPORTED, who + ": the activation tiles do not fit this device's LDS per workgroup");
+  if (gen) {
+    if (!rg) return serl_fail(SERL_E_INVALID, who + ": NULL generator descriptor");
+    if (rg->n_rows < d->batch || rg->n_rows > d->capacity) return serl_fail(SERL_E_INVALID, who + ": batch <= n_rows <= capacity");
+    if ((long long)rg->learner0 + d->n_learners > 2147483647LL) return serl_fail(SERL_E_INVALID, who + ": learner0 + n_learners overflows");
+    if (rg->dense != 0 && rg->dense != 1) return serl_fail(SERL_E_INVALID, who + ": dense must be 0 (valu) or 1 (mfma)");
+    if (rg->caps != 0 && rg->caps != 1) return serl_fail(SERL_E_INVALID, who + ": caps must be 0 or 1");
+    mfma = rg->dense == 1;
+  }
   if (d->n_updates == 0) return SERL_OK;
   HIP_TRY(hipSetDevice(c->device));
   Td3Args a;
   a.d = *d;
   a.work_floats = td3_work_floats(d->state_dim, d->action_dim, d->hidden, d->num_layers);
-  auto kernel = mfma ? td3_kernel<true> : td3_kernel<false>;
+  if (gen) {
+    Td3ArgsRng ar;
+    ar.d = a.d; ar.work_floats = a.work_floats;
+    ar.rg = {rg->seed, rg->n_rows, rg->learner0, rg->caps};
+    auto kernel = mfma ? td3_kernel<true, true> : td3_kernel<false, true>;
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kernel, dim3(d->n_learners), dim3(NT), lds, (hipStream_t)stream, ar);
+    HIP_TRY(hipGetLastError());
+    return SERL_OK;
+  }
+  auto kernel = mfma ? td3_kernel<true, false> : td3_kernel<false, false>;
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kernel, dim3(d->n_learners), dim3(NT), lds, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
@@ -610,5 +720,49 @@ int serl_td3_layout(int32_t *out, int32_t capacity)
 int serl_td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream) { return td3_train(c, d, stream, false, "serl_td3_train"); }
 
 int serl_td3_train_mfma(serl_ctx *c, const serl_td3_desc *d, void *stream) { return td3_train(c, d, stream, true, "serl_td3_train_mfma"); }
+
+int serl_td3_rng_layout(int32_t *out, int32_t capacity)
+{
+#define TD3_OFF(m) (int32_t)offsetof(serl_td3_rng_desc, m)
+  const int32_t v[] = {(int32_t)sizeof(serl_td3_rng_desc), TD3_OFF(seed), TD3_OFF(n_rows), TD3_OFF(learner0), TD3_OFF(dense), TD3_OFF(caps)};
+#undef TD3_OFF
+  const int n = (int)(sizeof(v) / sizeof(v[0]));
+  for (int i = 0; i < n && i < capacity; ++i)
+    if (out) out[i] = v[i];
+  return n;
+}
+
+int serl_td3_train_rng(serl_ctx *c, const serl_td3_desc *d, const serl_td3_rng_desc *rg, void *stream)
+{
+  return td3_train(c, d, stream, false, "serl_td3_train_rng", true, rg);
+}
+
+int serl_td3_rng_fill(serl_ctx *c, const serl_td3_rng_desc *rg, int32_t learner, int32_t state_dim, int32_t action_dim, int32_t batch,
+                      int32_t iteration0, int32_t n_updates, int32_t policy_update_freq, int32_t *slots, float *target_noise, float *caps_noise,
+                      void *stream)
+{
+  const std::string who("serl_td3_rng_fill");
+  if (!c || !rg || !slots || !target_noise) return serl_fail(SERL_E_INVALID, who + ": NULL argument (only caps_noise may be NULL: not written)");
+  if (state_dim < 1 || state_dim > 16 || action_dim < 1 || action_dim > 4 || batch < 1 || batch > BP)
+    return serl_fail(SERL_E_INVALID, who + ": state_dim 1 .. 16, action_dim 1 .. 4, batch 1 .. 128");
+  if (learner < 0 || n_updates < 0 || policy_update_freq < 1 || iteration0 < 0 || (long long)iteration0 + n_updates > 2147483646LL ||
+      (long long)rg->learner0 + learner > 2147483647LL)
+    return serl_fail(SERL_E_INVALID, who + ": learner >= 0, n_updates >= 0, policy_update_freq >= 1, iteration0 >= 0, no overflow");
+  if (rg->n_rows < batch) return serl_fail(SERL_E_INVALID, who + ": n_rows < batch");
+  if (n_updates == 0) return SERL_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const Td3Rng r = {rg->seed, rg->n_rows, rg->learner0, rg->caps};
+  hipLaunchKernelGGL(td3_rng_fill_kernel, dim3(n_updates), dim3(BP), 0, (hipStream_t)stream, r, (int)(rg->learner0 + learner), (int)state_dim,
+                     (int)action_dim, (int)batch, (int)iteration0, (int)policy_update_freq, slots, target_noise, caps_noise);
+  HIP_TRY(hipGetLastError());
+  return SERL_OK;
+}
+
+int serl_host_td3_slots(uint64_t seed, int32_t learner, int32_t iteration, int32_t n_rows, int32_t batch, int32_t *out)
+{
+  if (!out || batch < 1 || n_rows < batch) return serl_fail(SERL_E_INVALID, "serl_host_td3_slots: NULL out, batch < 1 or n_rows < batch");
+  serl_td3_slots_serial(seed, learner, iteration, n_rows, batch, out);
+  return SERL_OK;
+}
 
 }  // extern "C"

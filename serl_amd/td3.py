@@ -6,6 +6,10 @@ with it -- one update per frame of the generation, minibatches sampled from the 
 (serl_td3_train, include/serl_amd.h): the host draws the minibatch slots from python's `random` stream and the noise from a torch CPU
 generator in the order a CPU run of the reference consumes them, the device does the rest.  Without a GPU, or for a shape the kernel
 is not compiled for, `train` loops `update_parameters` over the same draws.
+
+`train(draws='device', seed=...)` takes no draw on the host at all: serl_td3_train_rng draws the slots and both kinds of noise inside the
+kernel from the counter-based generator of csrc/serl_rng.h, as a function of (seed, learner, iteration), and `td3_draws` writes the same
+draws out as tables (serl_td3_rng_fill) for a replay on the table path.
 """
 import ctypes
 import random
@@ -26,6 +30,9 @@ FUSED_DEFAULT = True
 # train(dense=...): the entry point of the library and what last_path reports.  'valu' is the default: 'mfma' gives the same bits and is
 # opt-in until profiles/td3_mfma_timing.json decides otherwise.
 DENSE = {'valu': ('serl_td3_train', 'fused'), 'mfma': ('serl_td3_train_mfma', 'fused-mfma')}
+# train(draws=...): 'host' = slots from `rng`, noise from `generator`, uploaded as tables (the default; profiles/td3_rng_timing.json
+# holds the measurements a later change decides from); 'device' = serl_td3_train_rng, last_path 'fused-rng' / 'fused-mfma-rng'.
+DRAWS = ('host', 'device')
 
 
 class _QNet(nn.Module):
@@ -122,6 +129,33 @@ def draw_noise(n_updates, batch, state_dim, action_dim, iteration0, policy_updat
     return tn, (torch.stack(cn) if cn else torch.zeros(0, batch, state_dim))
 
 
+def td3_draws(engine, *, seed, learner, iteration0, n_updates, batch, n_rows, state_dim, action_dim, policy_update_freq, caps, device=None):
+    """What TD3.train(draws='device', seed=seed, learner=learner) draws in n_updates updates from iteration0 on, minibatches of `batch` of
+    the first n_rows rows of a ring, written out by the kernels' own device functions (serl_td3_rng_fill)
+    -> (slots i32 [n, B], target_noise f32 [n, B, A], caps_noise f32 [actor updates, B, S] or None without `caps`), device tensors: the
+    tables with which serl_td3_train reproduces the call bit for bit."""
+    from . import _capi
+    dev = torch.device(engine.device if device is None else device)
+    n, B, S, A, freq, it0 = int(n_updates), int(batch), int(state_dim), int(action_dim), int(policy_update_freq), int(iteration0)
+    if n < 0 or freq < 1 or it0 < 0:
+        raise ValueError('td3_draws: n_updates >= 0, policy_update_freq >= 1, iteration0 >= 0')
+    k = (it0 + n) // freq - it0 // freq
+    slots = torch.zeros(n, B, dtype=torch.int32, device=dev)
+    tn = torch.zeros(n, B, A, dtype=torch.float32, device=dev)
+    cn = torch.zeros(k, B, S, dtype=torch.float32, device=dev) if caps else None
+    rd = _capi.Td3RngDesc(seed=_seed64(seed, 'td3_draws'), n_rows=int(n_rows), learner0=int(learner), dense=0, caps=int(bool(caps)))
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _capi.check(_capi.lib().serl_td3_rng_fill(engine.ctx, ctypes.byref(rd), 0, S, A, B, it0, n, freq, slots.data_ptr(), tn.data_ptr(),
+                                              cn.data_ptr() if cn is not None and k else None, stream), 'serl_td3_rng_fill')
+    return slots, tn, cn
+
+
+def _seed64(seed, who):
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2**64:
+        raise ValueError('%s: seed=%r (an integer in [0, 2^64))' % (who, seed))
+    return int(seed)
+
+
 class TD3:
     def __init__(self, args, engine=None):
         self.args = args
@@ -140,7 +174,8 @@ class TD3:
         _hard_update(self.actor_target, self.actor)
         _hard_update(self.critic_target, self.critic)
         self.caps_dict = dict(CAPS) if getattr(args, 'use_caps', False) else None
-        self.last_path = None                   # 'fused' / 'fused-mfma' / 'eager': what the most recent train() ran
+        self.last_path = None                   # 'fused' / 'fused-mfma' / 'fused-rng' / 'fused-mfma-rng' / 'eager': what the most recent train() ran
+        self.last_table_bytes = None            # bytes of the slot and noise tables the most recent fused train() put on the device
 
     # ---- one eager update (td3.py:123-198); also the fallback of train() -------------------------------------------------------------
     def update_parameters(self, batch, iteration, champion_policy=False, *, noise=None, caps_noise=None):
@@ -194,17 +229,34 @@ class TD3:
             return False
         return _capi.lib().serl_td3_work_bytes(1, a.state_dim, a.action_dim, a.hidden_size, a.num_layers, int(a.batch_size)) > 0
 
-    def train(self, replay, n_updates, *, iteration0, champion_target=False, rng=random, generator=None, fused=None, dense='valu'):
+    def train(self, replay, n_updates, *, iteration0, champion_target=False, rng=random, generator=None, fused=None, dense='valu',
+              draws='host', seed=None, learner=0):
         """n_updates consecutive updates on minibatches of args.batch_size rows of `replay` (a DeviceReplay), update u with iteration
         iteration0 + u + 1 -- the loop of Agent.train_rl.  -> {'PG_obj': mean(-pg), 'TD_loss': median(td)} like train_rl.
         fused: None = the fused kernel where it runs (FUSED_DEFAULT), False = the eager loop, True = the kernel or an error.
         dense: 'valu' = serl_td3_train; 'mfma' = serl_td3_train_mfma, the same kernel with its Linear layers on the f32 matrix cores --
         bit for bit the same result (include/serl_amd.h), the kernel or an error, never the eager loop.  Anything else, or
-        dense='mfma' with fused=False, is a ValueError before a draw is taken from `rng` / `generator`."""
+        dense='mfma' with fused=False, is a ValueError before a draw is taken from `rng` / `generator`.
+        draws: 'host' = as above.  'device' = serl_td3_train_rng: slots and noise are drawn inside the kernel as a function of (seed,
+        learner, iteration) -- seed an integer in [0, 2^64), learner the key of this learner among those that share the seed -- from the
+        first len(replay) rows of the ring; `rng` and `generator` are not touched and no table is allocated, so two calls of n1 and n2
+        updates equal one of n1 + n2, and td3_draws(...) replays the draws.  The kernel (with `dense` phases) or an error, never the
+        eager loop: an unknown `draws`, draws='device' without a seed or with fused=False is a ValueError, a shape or device the
+        kernel does not run a RuntimeError, all before anything is drawn."""
         if dense not in DENSE:
             raise ValueError('TD3.train: dense=%r (one of %s)' % (dense, ', '.join(repr(k) for k in DENSE)))
         if dense != 'valu' and fused is not None and not fused:
             raise ValueError('TD3.train: dense=%r selects a fused kernel, fused=False the eager loop' % (dense,))
+        if draws not in DRAWS:
+            raise ValueError('TD3.train: draws=%r (one of %s)' % (draws, ', '.join(repr(k) for k in DRAWS)))
+        if draws == 'device':
+            if seed is None:
+                raise ValueError("TD3.train: draws='device' needs seed= (an integer in [0, 2^64))")
+            if fused is not None and not fused:
+                raise ValueError("TD3.train: draws='device' selects a fused kernel, fused=False the eager loop")
+            seed = _seed64(seed, 'TD3.train')
+            if isinstance(learner, bool) or not isinstance(learner, (int, np.integer)) or not 0 <= int(learner) < 2**31 - 1:
+                raise ValueError('TD3.train: learner=%r (an integer in [0, 2^31 - 1))' % (learner,))
         a = self.args
         n_updates, B = int(n_updates), int(a.batch_size)
         S, A = a.state_dim, a.action_dim
@@ -218,6 +270,15 @@ class TD3:
         can = self.fused_supported(replay.device)
         if dense != 'valu' and not can:
             raise RuntimeError('TD3.train(dense=%r): %s does not run this shape / device' % (dense, DENSE[dense][0]))
+        if draws == 'device':
+            if not can:
+                raise RuntimeError("TD3.train(draws='device'): serl_td3_train_rng does not run this shape / device")
+            from . import _capi
+            rd = _capi.Td3RngDesc(seed=seed, n_rows=len(replay), learner0=int(learner), dense=int(dense == 'mfma'),
+                                  caps=int(self.caps_dict is not None))
+            td, pg = self._train_fused(replay, None, None, None, int(iteration0), not champion_target, 'serl_td3_train_rng', n_updates, rd)
+            self.last_path = DENSE[dense][1] + '-rng'
+            return {'PG_obj': float(np.mean([-x for x in pg])) if len(pg) else float('nan'), 'TD_loss': float(np.median(td))}
         slots = _replay.sample_many(len(replay), B, n_updates, rng)
         freq = int(a.policy_update_freq)
         tn, cn = draw_noise(n_updates, B, S, A, int(iteration0), freq, self.caps_dict is not None, generator)
@@ -247,11 +308,12 @@ class TD3:
                 pg.append(float(pgl))
         return td, pg
 
-    def _train_fused(self, replay, slots, tn, cn, iteration0, update_actor_target, entry='serl_td3_train'):
+    def _train_fused(self, replay, slots, tn, cn, iteration0, update_actor_target, entry='serl_td3_train', n_updates=None, rng_desc=None):
+        """rng_desc (a _capi.Td3RngDesc, entry 'serl_td3_train_rng'): n_updates updates with no table at all -- slots, tn, cn are None"""
         from . import _capi
         a, dev = self.args, replay.device
         L = _capi.lib()
-        n, B = slots.shape
+        n, B = (int(n_updates), int(a.batch_size)) if rng_desc is not None else slots.shape
         S, A = a.state_dim, a.action_dim
         ap, cp = list(self.actor.parameters()), list(self.critic.parameters())
         am, av, astep = _pack_adam(self.actor_optim, ap)
@@ -261,9 +323,12 @@ class TD3:
                                          critic=pack_critic(self.critic), critic_target=pack_critic(self.critic_target), critic_m=cm,
                                          critic_v=cv).items()}
         steps = torch.tensor([cstep, astep], dtype=torch.int32, device=dev)
-        sl = t(torch.from_numpy(np.ascontiguousarray(slots, dtype=np.int32)))
-        tn_d = t(tn.to(torch.float32))
-        cn_d = t(cn.to(torch.float32)) if cn is not None else None
+        sl = tn_d = cn_d = None
+        if rng_desc is None:
+            sl = t(torch.from_numpy(np.ascontiguousarray(slots, dtype=np.int32)))
+            tn_d = t(tn.to(torch.float32))
+            cn_d = t(cn.to(torch.float32)) if cn is not None else None
+        self.last_table_bytes = sum(x.numel() * x.element_size() for x in (sl, tn_d, cn_d) if x is not None)
         td = torch.zeros(n, dtype=torch.float32, device=dev)
         pg = torch.full((n,), float('nan'), dtype=torch.float32, device=dev)
         wb = int(L.serl_td3_work_bytes(1, S, A, a.hidden_size, a.num_layers, B))
@@ -279,12 +344,17 @@ class TD3:
                           actor_v=rows['actor_v'].data_ptr(), actor_stride=rows['actor'].numel(),
                           critic=rows['critic'].data_ptr(), critic_target=rows['critic_target'].data_ptr(),
                           critic_m=rows['critic_m'].data_ptr(), critic_v=rows['critic_v'].data_ptr(), critic_stride=rows['critic'].numel(),
-                          adam_steps=steps.data_ptr(), ring=replay.rows.data_ptr(), ring_stride=0, slots=sl.data_ptr(), slots_stride=0,
-                          target_noise=tn_d.data_ptr(), noise_stride=0, caps_noise=cn_d.data_ptr() if cn_d is not None and cn_d.numel() else
+                          adam_steps=steps.data_ptr(), ring=replay.rows.data_ptr(), ring_stride=0,
+                          slots=sl.data_ptr() if sl is not None else None, slots_stride=0,
+                          target_noise=tn_d.data_ptr() if tn_d is not None else None, noise_stride=0,
+                          caps_noise=cn_d.data_ptr() if cn_d is not None and cn_d.numel() else
                           (work.data_ptr() if cn_d is not None else None), caps_stride=0, td_loss=td.data_ptr(), pg_loss=pg.data_ptr(),
                           loss_stride=n, work=work.data_ptr(), work_bytes=wb)
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _capi.check(getattr(L, entry)(self.engine.ctx, ctypes.byref(d), stream), entry)
+        if rng_desc is not None:
+            _capi.check(L.serl_td3_train_rng(self.engine.ctx, ctypes.byref(d), ctypes.byref(rng_desc), stream), entry)
+        else:
+            _capi.check(getattr(L, entry)(self.engine.ctx, ctypes.byref(d), stream), entry)
         torch.cuda.synchronize(dev)
         unpack_into(self.actor, rows['actor'])
         unpack_into(self.actor_target, rows['actor_target'])
