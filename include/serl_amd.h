@@ -796,6 +796,22 @@ int serl_td3_rng_fill(serl_ctx *ctx, const serl_td3_rng_desc *rng, int32_t learn
  * 1 <= batch <= n_rows (batch^2 / 2 comparisons).  SERL_E_INVALID for a NULL out, batch < 1 or n_rows < batch. */
 int serl_host_td3_slots(uint64_t seed, int32_t learner, int32_t iteration, int32_t n_rows, int32_t batch, int32_t *out);
 
+/* ---- the launch planner on the host (SERL_ABI_VERSION stays 9: new symbols only) --------------------------------------------------
+ * WHAT serl_rollout / serl_rollout_noise (noise != 0) would launch for `desc` on a device of caps[0] CUs: the library's own decision
+ * (csrc/serl_plan.h), without a context or a device.  caps[7] = {CUs, SERL_KERNEL as enum serl_kernel_hint (0 = unset),
+ * SERL_WAVES_PER_BLOCK (-1 = unset), SERL_LANEQ_WAVES (-1), SERL_SPLIT_ACTOR (0), SERL_REMOTE_ACTOR (1), 1 unless SERL_LANE_WEIGHTS=rows}.
+ * Reads the integer fields of desc and the alignment of desc->weights, never what a pointer points to.  Runs the descriptor checks of
+ * serl_rollout that need no context, then the plan: returns the status serl_rollout would, message in serl_last_error.  out[0..7] = the
+ * words of serl_last_rollout_info with code = -1; out[8] threads per workgroup, [9] RolloutArgs.lanes, [10] first queued episode, [11]
+ * weights regrouped, [12] mailbox bytes zeroed, [13] timing events recorded, [14] episodes per launch, [15] 0.  All zero on a refusal.
+ * SERL_E_INVALID for a NULL argument, caps[0] < 1 or n_episodes < 1. */
+int serl_host_plan_rollout(const int32_t caps[7], const serl_rollout_desc *desc, int32_t noise, int32_t out[16]);
+/* ... of serl_dyn_open_loop */
+int serl_host_plan_dyn(const int32_t caps[7], int32_t n_episodes, int32_t lanes_per_wave, int32_t kernel_hint, int32_t out[16]);
+/* ... the workgroups serl_rollout_multi gives its n <= 4 parts of episodes[k] episodes under placement `place` (SERL_MIXED_PLACE): grids
+ * i32 [n], *queue = every part drains a work queue on its share of the CUs, *place_out = the placement the launch uses. */
+int serl_host_plan_multi(int32_t num_cus, int32_t n, const int32_t *episodes, int32_t place, int32_t *grids, int32_t *queue, int32_t *place_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,8 @@ EXPORTS = ['serl_abi_version', 'serl_last_error', 'serl_param_count', 'serl_ctx_
            'serl_venv_reset_wave', 'serl_venv_step_wave', 'serl_venv_step_auto_wave', 'serl_venv_reset_wave_noise', 'serl_venv_step_auto_wave_noise',
            'serl_venv_last_info', 'serl_venv_rollout_wave', 'serl_venv_rollout_wave_noise',
            'serl_rollout_noise', 'serl_rollout_noise_layout',
-           'serl_td3_train_rng', 'serl_td3_rng_layout', 'serl_td3_rng_fill', 'serl_host_td3_slots']
+           'serl_td3_train_rng', 'serl_td3_rng_layout', 'serl_td3_rng_fill', 'serl_host_td3_slots',
+           'serl_host_plan_rollout', 'serl_host_plan_dyn', 'serl_host_plan_multi']
 
 
 class BuildDesc(ctypes.Structure):
@@ -240,6 +241,9 @@ def lib():
     L.serl_td3_train_rng.argtypes = [VP, ctypes.POINTER(Td3Desc), ctypes.POINTER(Td3RngDesc), VP]
     L.serl_td3_rng_fill.argtypes = [VP, ctypes.POINTER(Td3RngDesc)] + [i32] * 7 + [VP, VP, VP, VP]
     L.serl_host_td3_slots.argtypes = [ctypes.c_uint64, i32, i32, i32, i32, VP]
+    L.serl_host_plan_rollout.argtypes = [_I, ctypes.POINTER(RolloutDesc), i32, _I]
+    L.serl_host_plan_dyn.argtypes = [_I, i32, i32, i32, _I]
+    L.serl_host_plan_multi.argtypes = [i32, i32, _I, i32, _I, _I, _I]
     for f in EXPORTS:
         if f == 'serl_host_uniform':
             L.serl_host_uniform.restype = ctypes.c_double

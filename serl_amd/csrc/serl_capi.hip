@@ -123,42 +123,46 @@ static const SerlRnLaunchers k_rn_launchers[] = {SERL_VARIANTS(SERL_RN_VARIANT_R
 
 #include "serl_mixed.h"
 
-static void serl_launch_rollout_teamg(const SerlLaunchers &L, int groups, const RolloutArgs &a, int grid, hipStream_t stream)
-{
-  // (two per team with a streamed actor -- hidden != 32 -- is a kernel of its own: six team wavefronts + two actor wavefronts)
-  (groups == 4 ? L.team4 : a.d.hidden != 32 ? L.team2s : L.team2)(a, grid, stream);
-}
+static_assert(SERL_PLAN_MAX_HIDDEN == SERL_MAX_HIDDEN && SERL_PLAN_MAIL_BYTES == sizeof(SerlMail) && SERL_PLAN_MIXED_MAX == SERL_MIXED_MAX,
+              "serl_plan.h restates these for the host-only planner");
 
-// Episodes per team, 0 = use another kernel.  Measured per env step: 21.6 us with one episode per team, 22.2 with two,
-// 25.6 with four (the scalar glue is paid once for all lane groups; only the lane-parallel passes multiply, and the team's
-// helpers share them), and one team fits a CU -- so up to 2 x CUs episodes run two per team and up to 4 x CUs four per team,
-// in ONE round of workgroups, against 57 us of the one-wavefront kernel (1 023 episodes: 39.2 M env-steps/s against 16).
-// H = 32 only.  kernel_hint SERL_KERNEL_TEAM2 / TEAM4 force it.
-static int serl_use_teamg(const serl_ctx *c, const serl_rollout_desc *d, int hint, int episodes)
+// The launcher of a planned family (serl_plan.h), looked up HERE and nowhere else: what a call launches and what serl_last_rollout_info records
+// are both the plan's.  nullptr: the entry has no kernel of that family.
+static SerlLaunch *SerlLaunchers::*serl_rollout_launcher(const SerlPlan &p)
 {
-  if (d->hidden != 32) {
-    // actors without one hidden row per lane (SERL10's 72, the TD3 actor's 96): the actor wavefront runs the episodes' forward
-    // passes one after the other -- two per team (~33 us per env step for the pair, actor-bound) beat one wavefront per episode
-    // (57 - 61 us) while every pair has a CU: CUs < episodes <= 2 x CUs; four per team would be slower than four lone wavefronts
-    if (hint == SERL_KERNEL_TEAM2) return 2;
-    if (hint != SERL_KERNEL_AUTO) return 0;
-    return (episodes > c->num_cus && episodes <= 2 * c->num_cus) ? 2 : 0;
+  switch (p.family) {
+    case SERL_FAMILY_TEAM: return &SerlLaunchers::team;
+    case SERL_FAMILY_TEAMS: return &SerlLaunchers::teams;
+    case SERL_FAMILY_TEAMS2: return &SerlLaunchers::teams2;
+    case SERL_FAMILY_TEAMR: return &SerlLaunchers::teamr;
+    case SERL_FAMILY_TEAMX: return &SerlLaunchers::teamx;
+    case SERL_FAMILY_TEAM2: return &SerlLaunchers::team2;
+    case SERL_FAMILY_TEAM2S: return &SerlLaunchers::team2s;
+    case SERL_FAMILY_TEAM4: return &SerlLaunchers::team4;
+    case SERL_FAMILY_HALF: return &SerlLaunchers::half;
+    case SERL_FAMILY_WAVE: return &SerlLaunchers::wave;
+    case SERL_FAMILY_WAVEX: return &SerlLaunchers::wavex;
+    case SERL_FAMILY_LANE: return p.laneq ? &SerlLaunchers::laneq : &SerlLaunchers::lane;
+    default: return nullptr;
   }
-  if (hint == SERL_KERNEL_TEAM2) return 2;
-  if (hint == SERL_KERNEL_TEAM4) return 4;
-  if (hint != SERL_KERNEL_AUTO) return 0;
-  if (episodes <= c->num_cus || episodes > 4 * c->num_cus) return 0;
-  return episodes <= 2 * c->num_cus ? 2 : 4;
 }
-
-// Beyond 4 x CUs episodes the team kernels still win when the launch has the GPU to itself: 4 x CUs episodes per 30.8 us
-// is the rate of the two-episodes-per-wavefront kernel (8 x CUs per 62.9 us) at half the granularity, and the remainder runs
-// at the rate of its own size class.  Side-by-side launches (concurrent_episodes > 0) split the CUs by episode share (below; a
-// team needs a whole CU).  H = 32 only; any kernel_hint other than AUTO switches it off.
-static bool serl_use_team_rounds(const serl_ctx *c, const serl_rollout_desc *d, int hint, int episodes)
+static SerlLaunchNz *SerlRnLaunchers::*serl_noise_launcher(const SerlPlan &p)
 {
-  if (d->hidden != 32 || hint != SERL_KERNEL_AUTO) return false;
-  return episodes > 4 * c->num_cus;
+  switch (p.family) {
+    case SERL_FAMILY_WAVE: return &SerlRnLaunchers::wave;
+    case SERL_FAMILY_WAVEX: return &SerlRnLaunchers::wavex;
+    case SERL_FAMILY_LANE: return p.laneq ? nullptr : &SerlRnLaunchers::lane;
+    default: return nullptr;
+  }
+}
+static SerlLaunchDyn *SerlLaunchers::*serl_dyn_launcher(const SerlPlan &p)
+{
+  switch (p.family) {
+    case SERL_FAMILY_TEAM: return &SerlLaunchers::dyn_team;
+    case SERL_FAMILY_WAVE: return &SerlLaunchers::dyn_wave;
+    case SERL_FAMILY_LANE: return &SerlLaunchers::dyn_lane;
+    default: return nullptr;
+  }
 }
 
 // Work-queue counter of ONE launch: a ring of counters, so that queue launches in flight on different streams (a mixed-fault sweep;
@@ -171,54 +175,6 @@ static int32_t *serl_next_queue_counter(serl_ctx *c)
   return p;
 }
 
-// The one-wavefront-per-episode kernel runs up to 4 x CUs episodes at once (one per SIMD); beyond that the launch needs a
-// second round of wavefronts, and packing two episodes into a wavefront (1.1 x the time per env step) is the better deal.
-// H = 32 only (the lane group of an episode holds one hidden row per lane).  kernel_hint SERL_KERNEL_HALF forces it.
-static bool serl_use_half(const serl_ctx *c, const serl_rollout_desc *d, int hint, int episodes)
-{
-  if (d->hidden != 32) return false;
-  if (hint != SERL_KERNEL_AUTO) return hint == SERL_KERNEL_HALF;
-  return episodes > 4 * c->num_cus;
-}
-
-// One episode per workgroup and one workgroup per CU (the LDS copy of the tables): a team finishes an env step in
-// ~0.37 of the time a lone wavefront needs (21.2 vs 57 us), but only one team fits a CU where four lone wavefronts
-// would: teams while every episode gets a CU of its own (measured: 320 episodes as teams 88 us, 400 alone 59 us),
-// lone wavefronts beyond.  kernel_hint SERL_KERNEL_TEAM forces it (any other hint excludes it).
-static bool serl_use_team(const serl_ctx *c, int hint, int episodes)
-{
-  if (hint != SERL_KERNEL_AUTO) return hint == SERL_KERNEL_TEAM;
-  return episodes <= c->num_cus;
-}
-
-// (rollout_device.h: serl_lds_actor_ok) the actor shape whose weights live in LDS for the episode
-static bool serl_lds_actor_shape(const serl_rollout_desc &d) { return d.hidden == 32 && d.num_layers <= 3 && d.state_dim == 7 && d.action_dim == 3; }
-
-// Round 6: streamed actors (hidden 65 .. 128: SERL10's 72, the TD3 actor's 96) of the attitude task with the actor in a workgroup of its own on another CU
-// (family_teamr.hip): two workgroups per episode, pairs (b, b + 8) of a group of sixteen.  Only while every workgroup of the launch -- and of the launches it
-// was told about -- can be resident at once: a team spins on its partner's mailbox.  0 = not eligible, else the grid.
-static int serl_remote_actor_grid(const serl_ctx *c, const serl_rollout_desc *d, int together)
-{
-  if (!c->env_remote_actor || (d->hidden != 72 && d->hidden != 96 && d->hidden != 128) || d->state_dim != 7 || d->action_dim != 3) return 0;      // (rollout_device.h serl_cu_actor_ok)
-  const int grid = 16 * ((d->n_episodes + 7) / 8), all = 16 * ((together + 7) / 8);
-  return all <= c->num_cus ? grid : 0;
-}
-
-static void serl_launch_rollout_team(const SerlLaunchers &L, const RolloutArgs &a, int grid, hipStream_t stream, bool split_actor = false)
-{
-  // (rollout_device.h: serl_lds_actor_ok) shapes whose weights the actor wavefront streams have a kernel of their own
-  const bool lds_actor = serl_lds_actor_shape(a.d);
-  // (development override SERL_SPLIT_ACTOR=1) two actor wavefronts share ONE forward pass beside a six-wavefront team: round 4
-  // built it for the shapes whose lone actor wavefront needed a whole step (H = 72: 43 k cycles) -- and then found that a
-  // shape-specialised forward (serl_actor_forward_big: 25 k) on ONE wavefront beside the seven-wavefront team is faster
-  const bool split = !lds_actor && split_actor && a.d.hidden > 64 && a.d.hidden <= 128;
-  (lds_actor ? L.team : split ? L.teams2 : L.teams)(a, grid, stream);
-}
-
-// The wave-cooperative kernels (one wavefront per episode, rollout_wave.inc) exist for every code variant; the
-// lane-per-episode kernels (rollout_variant.inc, lanes_per_wave > 0) for every code variant since round 6.
-static bool serl_has_wave_kernel(int code) { return code >= 0 && code < SERL_N_VARIANTS; }
-static bool serl_has_lane_kernel(int code) { return code >= 0 && code < SERL_N_VARIANTS; }
 
 // Lane-per-episode kernels (rollout_device.h serl_actor_forward_lane32_t): the population [members][stride] regrouped to [ceil(P / 4)][mpad][4], so that parameter
 // group g of 64 consecutive members is ONE run of 1 KB.  Reads run along a member's row, writes are 16 B pieces (30 MB for 2 048 SERL50 actors: microseconds in front of a
@@ -261,33 +217,73 @@ static int serl_regroup_weights(serl_ctx *c, const serl_rollout_desc *d, Rollout
   return SERL_OK;
 }
 
-// Wavefronts per workgroup of the wave-cooperative kernels: one per CU while there are no more episodes than CUs,
-// then up to four (one per SIMD) sharing the workgroup's LDS copy of the tables.
-static int serl_wave_kernel_waves_per_block(const serl_ctx *c, int episodes)
-{
-  if (c->env_waves_per_block >= 1 && c->env_waves_per_block <= 8) return c->env_waves_per_block;     // (8 only with a library built with -DCITW_MAX_WAVES=8)
-  int w = (episodes + c->num_cus - 1) / c->num_cus;
-  return w < 1 ? 1 : (w > 4 ? 4 : w);
-}
-
-// Wavefronts per workgroup.  One workgroup stages one LDS copy of the tables (94 KiB of the CU's 160 KiB), so
-// only one workgroup fits a CU: while there are no more wavefronts than CUs each gets a CU of its own (the
-// code streams through the instruction cache and co-resident waves slow each other down); beyond that, waves
-// share a CU four at a time (one per SIMD, each with the full 512-register budget).
-static int serl_waves_per_block(const serl_ctx *c, int waves)
-{
-  if (c->env_waves_per_block >= 1 && c->env_waves_per_block <= 4) return c->env_waves_per_block;
-  return waves <= c->num_cus ? 1 : 4;
-}
-
-// descriptor hint first, then the context's development override (SERL_KERNEL, read once by serl_ctx_create)
-static int serl_resolve_hint(const serl_ctx *c, int desc_hint) { return desc_hint != SERL_KERNEL_AUTO ? desc_hint : c->env_kernel; }
 
 // serl_last_rollout_info's record of a call (include/serl_amd.h)
 static void serl_note_launch(serl_ctx *c, int family, int grid, int per_team, bool queue, int actor_waves, bool streamed, int launches, int code)
 {
   const int32_t v[8] = {family, grid, per_team, queue ? 1 : 0, actor_waves, streamed ? 1 : 0, launches, code};
   for (int i = 0; i < 8; ++i) c->last_info[i] = v[i];
+}
+
+// RolloutArgs of n_episodes on a build's tables (what every launch path starts from) ...
+static void serl_fill_args(serl_ctx *c, int slot, int n_episodes, RolloutArgs &a)
+{
+  const BuildSlot &s = c->slots[slot];
+  memset(&a, 0, sizeof(a));
+  a.d.n_episodes = n_episodes;
+  a.ro = s.blob; a.t3 = s.blob + s.n_ro; a.x0 = a.t3 + 46; a.dw0 = a.x0 + 19;
+  a.dyn_dt = s.dt;
+}
+
+// ... of one descriptor
+static void serl_fill_args(serl_ctx *c, const serl_rollout_desc *d, RolloutArgs &a)
+{
+  serl_fill_args(c, d->build_slot, d->n_episodes, a);
+  a.d = *d;
+  a.jitter = c->env_jitter; a.jitter_sites = c->env_jitter_sites;
+}
+
+// Carries a plan out on `stream`: `launch(a, grid)` is the entry's kernel of the plan's family, `code` the build's code variant.  Everything the launch
+// needs goes in front of it first, then ev0: the kernel alone is timed.
+template <class Launch>
+static int serl_execute_plan(serl_ctx *c, const SerlPlan &p, RolloutArgs &a, int code, bool profile, hipStream_t stream, Launch launch)
+{
+  const serl_rollout_desc *d = &a.d;
+  a.lanes = p.lanes;
+  a.block = p.block;
+  if (profile && c->env_profile) {
+    if (!c->prof) HIP_TRY(hipMalloc((void **)&c->prof, 32 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(c->prof, 0, 32 * sizeof(unsigned long long), stream));
+    a.prof = c->prof;
+  }
+  if (p.regroup) {
+    const int rc = serl_regroup_weights(c, d, a, stream);
+    if (rc != SERL_OK) return rc;
+  }
+  a.q0 = p.q0;
+  if (p.queue) {
+    a.queue = serl_next_queue_counter(c);
+    HIP_TRY(hipMemsetAsync(a.queue, 0, sizeof(int32_t), stream));
+  }
+  if (p.mailbox) {
+    const size_t region = (size_t)c->caps.num_cus * sizeof(SerlMail);
+    if (!c->mail) HIP_TRY(hipMalloc(&c->mail, SERL_MAIL_REGIONS * region));
+    a.mail = (char *)c->mail + (size_t)c->mail_next * region;
+    c->mail_next = (c->mail_next + 1) % SERL_MAIL_REGIONS;
+    HIP_TRY(hipMemsetAsync(a.mail, 0, (size_t)p.mail_bytes, stream));
+  }
+  if (p.timed) HIP_TRY(hipEventRecord(c->ev0, stream));
+  for (int i = 0; i < p.launches; ++i) {
+    a.e0 = i * p.chunk;
+    a.e_end = a.e0 + p.chunk < d->n_episodes ? a.e0 + p.chunk : d->n_episodes;
+    launch(a, p.launches > 1 ? a.e_end - a.e0 : p.grid);
+    HIP_TRY(hipGetLastError());
+  }
+  if (p.regroup) HIP_TRY(hipEventRecord(c->wt_done[c->wt_slot_of_launch], stream));
+  serl_note_launch(c, p.family, p.grid, p.per_team, p.queue != 0, p.actor_waves, p.streamed != 0, p.launches, code);
+  if (p.timed) HIP_TRY(hipEventRecord(c->ev1, stream));
+  c->timed = p.timed != 0;
+  return SERL_OK;
 }
 
 extern "C" {
@@ -319,15 +315,8 @@ int serl_abi_layout(int32_t *out, int32_t capacity)
   return n;
 }
 
-// envs/phlabenv.py:84-97 (obs_idx per configuration), :213-220 (n_obs)
-int serl_env_action_dim(int env_config) { return env_config == SERL_ENV_SYMMETRIC ? 1 : 3; }
-int serl_env_state_dim(int env_config, int incremental)
-{
-  if (env_config < 0 || env_config > 2) return 0;
-  const int A = serl_env_action_dim(env_config);
-  const int nx = env_config == SERL_ENV_ATTITUDE ? 4 : (env_config == SERL_ENV_SYMMETRIC ? 1 : 10);
-  return A + nx + (incremental ? A : 0);
-}
+int serl_env_action_dim(int env_config) { return serl_plan_env_action_dim(env_config); }
+int serl_env_state_dim(int env_config, int incremental) { return serl_plan_env_state_dim(env_config, incremental); }
 const char *serl_last_error(void) { return g_err.c_str(); }
 
 int serl_ctx_create(int device, serl_ctx **out)
@@ -343,24 +332,24 @@ int serl_ctx_create(int device, serl_ctx **out)
   {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) {
-      if (prop.multiProcessorCount > 0) c->num_cus = prop.multiProcessorCount;
+      if (prop.multiProcessorCount > 0) c->caps.num_cus = prop.multiProcessorCount;
       if (prop.sharedMemPerBlockOptin > 0) c->lds_per_block = (int)prop.sharedMemPerBlockOptin;
     }
   }
   {   // development overrides: the library's only look at the process environment
     const char *e;
-    c->env_kernel = SERL_KERNEL_AUTO;
+    c->caps.env_kernel = SERL_KERNEL_AUTO;
     if ((e = getenv("SERL_KERNEL")) != nullptr) {
       const std::string k(e);
-      c->env_kernel = k == "team" ? SERL_KERNEL_TEAM : k == "team2" ? SERL_KERNEL_TEAM2 : k == "team4" ? SERL_KERNEL_TEAM4
+      c->caps.env_kernel = k == "team" ? SERL_KERNEL_TEAM : k == "team2" ? SERL_KERNEL_TEAM2 : k == "team4" ? SERL_KERNEL_TEAM4
                     : k == "wave" ? SERL_KERNEL_WAVE : k == "half" ? SERL_KERNEL_HALF : k == "laneq" ? SERL_KERNEL_LANEQ : SERL_KERNEL_AUTO;
     }
-    c->env_laneq_waves = (e = getenv("SERL_LANEQ_WAVES")) ? atoi(e) : -1;
-    c->env_waves_per_block = (e = getenv("SERL_WAVES_PER_BLOCK")) ? atoi(e) : -1;
+    c->caps.env_laneq_waves = (e = getenv("SERL_LANEQ_WAVES")) ? atoi(e) : -1;
+    c->caps.env_waves_per_block = (e = getenv("SERL_WAVES_PER_BLOCK")) ? atoi(e) : -1;
     c->env_profile = getenv("SERL_PROFILE") != nullptr;
-    c->env_split_actor = (e = getenv("SERL_SPLIT_ACTOR")) ? atoi(e) : 0;
-    c->env_remote_actor = (e = getenv("SERL_REMOTE_ACTOR")) ? atoi(e) : 1;
-    c->env_lane_regroup = ((e = getenv("SERL_LANE_WEIGHTS")) && !strcmp(e, "rows")) ? 0 : 1;
+    c->caps.env_split_actor = (e = getenv("SERL_SPLIT_ACTOR")) ? atoi(e) : 0;
+    c->caps.env_remote_actor = (e = getenv("SERL_REMOTE_ACTOR")) ? atoi(e) : 1;
+    c->caps.env_lane_regroup = ((e = getenv("SERL_LANE_WEIGHTS")) && !strcmp(e, "rows")) ? 0 : 1;
     c->env_mixed_place = (e = getenv("SERL_MIXED_PLACE")) ? atoi(e) : SERL_MIXED_PLACE_DEFAULT;
     c->env_jitter = (e = getenv("SERL_JITTER_SEED")) ? (unsigned)strtoul(e, nullptr, 0) : 0u;
     c->env_jitter_sites = (e = getenv("SERL_JITTER_SITES")) ? (unsigned)strtoul(e, nullptr, 0) : ~0u;
@@ -393,7 +382,7 @@ int serl_ctx_load_build(serl_ctx *c, int slot, const serl_build_desc *b)
 {
   if (!c || !b || slot < 0 || slot >= SERL_MAX_SLOTS) return fail(SERL_E_INVALID, "serl_ctx_load_build: bad argument");
   if (!b->ro || !b->t3 || !b->x0 || !b->dw0 || b->n_ro <= 0) return fail(SERL_E_INVALID, "serl_ctx_load_build: NULL table");
-  if (!serl_has_wave_kernel(b->code))
+  if (b->code < 0 || b->code >= SERL_N_VARIANTS)      // (every family has a kernel for every code variant with a row: the dispatch never asks again)
     return fail(SERL_E_UNSUPPORTED, "serl_ctx_load_build: dynamics code variant not compiled into this library");
   HIP_TRY(hipSetDevice(c->device));
   BuildSlot &s = c->slots[slot];
@@ -410,7 +399,7 @@ int serl_ctx_load_build(serl_ctx *c, int slot, const serl_build_desc *b)
   return SERL_OK;
 }
 
-int serl_param_count(int S, int H, int L, int A) { return H * S + H + L * (H * H + 3 * H) + A * H + A; }
+int serl_param_count(int S, int H, int L, int A) { return serl_plan_param_count(S, H, L, A); }
 
 // argument checks of serl_rollout / serl_rollout_multi; *hint_out = the resolved kernel hint
 static int serl_check_desc(serl_ctx *c, const serl_rollout_desc *d, int *hint_out)
@@ -421,293 +410,34 @@ static int serl_check_desc(serl_ctx *c, const serl_rollout_desc *d, int *hint_ou
   if (d->n_episodes <= 0) return fail(SERL_E_INVALID, "serl_rollout: n_episodes <= 0");
   if (!d->weights || !d->member_of_episode || (!d->ref && !d->ref_spec) || !d->fitness || !d->length_steps || !d->length_t || !d->cost_steps)
     return fail(SERL_E_INVALID, "serl_rollout: required device pointer is NULL");
-  const bool general_env = d->env_config != SERL_ENV_ATTITUDE || d->incremental != 0;
-  if (serl_env_state_dim(d->env_config, d->incremental) == 0)
-    return fail(SERL_E_INVALID, "serl_rollout: env_config must be SERL_ENV_ATTITUDE, SERL_ENV_SYMMETRIC or SERL_ENV_FULL");
-  if (d->state_dim != serl_env_state_dim(d->env_config, d->incremental) || d->action_dim != serl_env_action_dim(d->env_config))
-    return fail(SERL_E_INVALID, "serl_rollout: state_dim / action_dim do not match the env configuration (attitude 7 / 3, symmetric 2 / 1, full 13 / 3; incremental adds action_dim observations)");
-  if (general_env && (d->lanes_per_wave > 0 || serl_resolve_hint(c, d->kernel_hint) == SERL_KERNEL_LANEQ))
-    return fail(SERL_E_UNSUPPORTED, "serl_rollout: the lane-per-episode kernels exist for the attitude task only");
-  if (d->hidden < 2 || d->hidden > SERL_MAX_HIDDEN || d->num_layers < 0 || d->num_layers > 16)
-    return fail(SERL_E_UNSUPPORTED, "serl_rollout: hidden size / layer count out of range");
-  if (d->hidden % 4 != 0 || d->weight_stride % 4 != 0 || ((uintptr_t)d->weights & 15) != 0)
-    return fail(SERL_E_UNSUPPORTED, "serl_rollout: hidden size and weight_stride must be multiples of 4 and weights 16-byte aligned (dwordx4 row loads)");
-  if (d->activation < 0 || d->activation > 2) return fail(SERL_E_INVALID, "serl_rollout: activation");
-  if (d->weight_stride < serl_param_count(d->state_dim, d->hidden, d->num_layers, d->action_dim))
-    return fail(SERL_E_INVALID, "serl_rollout: weight_stride smaller than the parameter count");
-  if (d->max_steps <= 0) return fail(SERL_E_INVALID, "serl_rollout: max_steps");
-  if (d->kernel_hint < SERL_KERNEL_AUTO || d->kernel_hint > SERL_KERNEL_LANEQ) return fail(SERL_E_INVALID, "serl_rollout: kernel_hint");
-  // (LANEQ is the one hint lanes_per_wave > 0 does not switch off: there it is the lanes per wavefront of the work-queue kernel)
-  const int hint = (d->lanes_per_wave > 0 && serl_resolve_hint(c, d->kernel_hint) != SERL_KERNEL_LANEQ) ? SERL_KERNEL_AUTO : serl_resolve_hint(c, d->kernel_hint);
-  if (d->hidden != 32 && (hint == SERL_KERNEL_TEAM4 || hint == SERL_KERNEL_HALF))
-    return fail(SERL_E_UNSUPPORTED, "serl_rollout: kernel_hint TEAM4 / HALF needs hidden = 32 (other shapes: TEAM2, the actor wavefront runs the two episodes one after the other)");
-  *hint_out = hint;
-  return SERL_OK;
+  const char *message = "";
+  const int rc = serl_plan_check(&c->caps, d, hint_out, &message);
+  return rc == SERL_OK ? SERL_OK : fail(rc, message);
 }
 
-// RolloutArgs of one descriptor on its build's tables (what every launch path starts from)
-static void serl_fill_args(serl_ctx *c, const serl_rollout_desc *d, RolloutArgs &a)
+// serl_rollout and serl_rollout_noise (nz != NULL): check, plan, refuse if the plan refuses, execute
+static int serl_rollout_impl(serl_ctx *c, const serl_rollout_desc *d, const serl_rollout_noise_desc *nz, int hint, void *stream_)
 {
-  const BuildSlot &s = c->slots[d->build_slot];
-  memset(&a, 0, sizeof(a));
-  a.d = *d;
-  a.ro = s.blob; a.t3 = s.blob + s.n_ro; a.x0 = a.t3 + 46; a.dw0 = a.x0 + 19;
-  a.dyn_dt = s.dt;
-  a.jitter = c->env_jitter; a.jitter_sites = c->env_jitter_sites;
-  a.prof = nullptr;
+  const SerlPlan p = serl_plan_rollout(&c->caps, d, hint, nz != nullptr);
+  if (p.status != SERL_OK) return fail(p.status, p.message);
+  HIP_TRY(hipSetDevice(c->device));
+  const int code = c->slots[d->build_slot].code;
+  hipStream_t stream = (hipStream_t)stream_;
+  RolloutArgs a;
+  serl_fill_args(c, d, a);
+  if (nz) {
+    SerlLaunchNz *launch = k_rn_launchers[code].*serl_noise_launcher(p);
+    return serl_execute_plan(c, p, a, code, false, stream, [&](const RolloutArgs &a, int grid) { launch(a, *nz, grid, stream); });
+  }
+  SerlLaunch *launch = serl_launchers(code).*serl_rollout_launcher(p);
+  return serl_execute_plan(c, p, a, code, true, stream, [&](const RolloutArgs &a, int grid) { launch(a, grid, stream); });
 }
 
 int serl_rollout(serl_ctx *c, const serl_rollout_desc *d, void *stream_)
 {
   int hint = SERL_KERNEL_AUTO;
   { const int rc_ = serl_check_desc(c, d, &hint); if (rc_ != SERL_OK) return rc_; }
-  const bool general_env = d->env_config != SERL_ENV_ATTITUDE || d->incremental != 0;
-  HIP_TRY(hipSetDevice(c->device));
-  const BuildSlot &s = c->slots[d->build_slot];
-  const SerlLaunchers &L = serl_launchers(s.code);
-  hipStream_t stream = (hipStream_t)stream_;
-  RolloutArgs a;
-  memset(&a, 0, sizeof(a));
-  a.d = *d;
-  a.ro = s.blob; a.t3 = s.blob + s.n_ro; a.x0 = a.t3 + 46; a.dw0 = a.x0 + 19;
-  a.dyn_dt = s.dt;
-  a.jitter = c->env_jitter; a.jitter_sites = c->env_jitter_sites;
-  a.prof = nullptr;
-  if (c->env_profile) {
-    if (!c->prof) HIP_TRY(hipMalloc((void **)&c->prof, 32 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(c->prof, 0, 32 * sizeof(unsigned long long), stream));
-    a.prof = c->prof;
-  }
-  int lanes = d->lanes_per_wave;
-  // launches that share the GPU with others run on streams of their own: the context's one pair of timing events is
-  // not recorded for them (an event in flight on one stream must not be re-recorded on another)
-  const bool timed = d->concurrent_episodes <= 0;
-  const int together = d->n_episodes + (d->concurrent_episodes > 0 ? d->concurrent_episodes : 0);   // episodes sharing the GPU
-  a.e0 = 0; a.e_end = d->n_episodes;
-  if (general_env) {
-    // observation set / number of actions / incremental control from the descriptor: the team kernel while the episodes fit two
-    // rounds of workgroups (2 x ~23 us per env step against 57 of one wavefront per episode), one wavefront per episode beyond
-    if (!serl_has_wave_kernel(s.code)) return fail(SERL_E_UNSUPPORTED, "serl_rollout: code variant without a wave kernel");
-    if (hint != SERL_KERNEL_AUTO && hint != SERL_KERNEL_TEAM && hint != SERL_KERNEL_WAVE)
-      return fail(SERL_E_UNSUPPORTED, "serl_rollout: env configurations other than the attitude task run on the TEAM or WAVE kernels");
-    const bool team = hint != SERL_KERNEL_AUTO ? hint == SERL_KERNEL_TEAM : (d->concurrent_episodes <= 0 ? together <= 2 * c->num_cus : together <= c->num_cus);
-    if (timed) HIP_TRY(hipEventRecord(c->ev0, stream));
-    if (team) {
-      a.lanes = 1;
-      a.block = 512;
-      int launches = 0, last = 0;
-      for (int e0 = 0; e0 < d->n_episodes; e0 += c->num_cus) {
-        const int n = d->n_episodes - e0 < c->num_cus ? d->n_episodes - e0 : c->num_cus;
-        a.e0 = e0; a.e_end = e0 + n;
-        L.teamx(a, n, stream);
-        HIP_TRY(hipGetLastError());
-        ++launches; last = n;
-      }
-      serl_note_launch(c, SERL_FAMILY_TEAMX, last, 1, false, 1, true, launches, s.code);
-    } else {
-      const int wpb = serl_wave_kernel_waves_per_block(c, together + (timed ? 0 : 16));
-      a.lanes = 1;
-      a.block = 64 * wpb;
-      L.wavex(a, (d->n_episodes + wpb - 1) / wpb, stream);
-      HIP_TRY(hipGetLastError());
-      serl_note_launch(c, SERL_FAMILY_WAVEX, (d->n_episodes + wpb - 1) / wpb, 1, false, 0, true, 1, s.code);
-    }
-    if (timed) HIP_TRY(hipEventRecord(c->ev1, stream));
-    c->timed = timed;
-    return SERL_OK;
-  }
-  if (hint == SERL_KERNEL_LANEQ) {
-    // One episode per lane behind a work queue (rollout_variant.inc serl_rollout_laneq_kernel_<v>): at most W wavefronts -- four per workgroup, one workgroup per
-    // CU, which is what the LDS copy of the tables allows; beside other launches the launch's share of them -- and the episodes beyond their lane slots in the queue.
-    if (!serl_has_lane_kernel(s.code))
-      return fail(SERL_E_UNSUPPORTED, "serl_rollout: kernel_hint LANEQ (lane-per-episode kernels): unknown code variant");
-    lanes = (lanes <= 0 || lanes > 64) ? 64 : lanes;
-    long long W = 4LL * c->num_cus;
-    if (c->env_laneq_waves >= 1 && c->env_laneq_waves < W) W = c->env_laneq_waves;
-    if (d->concurrent_episodes > 0) W = W * d->n_episodes / together;
-    W = W < 1 ? 1 : W;
-    const int need = (d->n_episodes + lanes - 1) / lanes;
-    const int waves = need < W ? need : (int)W;
-    const int wpb = serl_waves_per_block(c, waves);
-    a.lanes = lanes;
-    a.block = 64 * wpb;
-    const int grid = (waves + wpb - 1) / wpb;
-    if (c->env_lane_regroup && d->hidden == 32 && d->state_dim == 7 && d->action_dim == 3 && d->n_members <= (1 << 22)) {      // (rollout_device.h serl_lane_actor_ok)
-      const int rc = serl_regroup_weights(c, d, a, stream);
-      if (rc != SERL_OK) return rc;
-    }
-    // the lane slots are those of `waves` wavefronts (a last workgroup may hold wavefronts beyond them: their lanes find no episode and leave)
-    const long long slots = (long long)waves * lanes;
-    if (d->n_episodes > slots) {
-      a.queue = serl_next_queue_counter(c);
-      a.q0 = (int32_t)slots;
-      HIP_TRY(hipMemsetAsync(a.queue, 0, sizeof(int32_t), stream));
-    } else {
-      a.queue = nullptr; a.q0 = d->n_episodes;
-    }
-    if (timed) HIP_TRY(hipEventRecord(c->ev0, stream));
-    L.laneq(a, grid, stream);
-    HIP_TRY(hipGetLastError());
-    if (a.wt) HIP_TRY(hipEventRecord(c->wt_done[c->wt_slot_of_launch], stream));
-    serl_note_launch(c, SERL_FAMILY_LANE, grid, lanes, a.queue != nullptr, 0, true, 1, s.code);
-    if (timed) HIP_TRY(hipEventRecord(c->ev1, stream));
-    c->timed = timed;
-    return SERL_OK;
-  }
-  if (lanes <= 0 && serl_use_team(c, hint, together)) {
-    a.lanes = 1;
-    a.block = 128;
-    if (timed) HIP_TRY(hipEventRecord(c->ev0, stream));
-    const int rgrid = serl_remote_actor_grid(c, d, together);
-    if (rgrid > 0) {
-      // mailboxes of this launch: a region of the ring, zeroed on the launch's stream in front of it
-      const size_t region = (size_t)c->num_cus * sizeof(SerlMail);
-      if (!c->mail) HIP_TRY(hipMalloc(&c->mail, SERL_MAIL_REGIONS * region));
-      a.mail = (char *)c->mail + (size_t)c->mail_next * region;
-      c->mail_next = (c->mail_next + 1) % SERL_MAIL_REGIONS;
-      HIP_TRY(hipMemsetAsync(a.mail, 0, (size_t)d->n_episodes * sizeof(SerlMail), stream));
-      a.block = 512;
-      if (timed) HIP_TRY(hipEventRecord(c->ev0, stream));      // (re-recorded behind the memset: the kernel alone is timed)
-      L.teamr(a, rgrid, stream);
-      HIP_TRY(hipGetLastError());
-      serl_note_launch(c, SERL_FAMILY_TEAMR, rgrid, 1, false, 4, true, 1, s.code);
-      if (timed) HIP_TRY(hipEventRecord(c->ev1, stream));
-      c->timed = timed;
-      return SERL_OK;
-    }
-    serl_launch_rollout_team(L, a, d->n_episodes, stream, c->env_split_actor != 0);
-    HIP_TRY(hipGetLastError());
-    {
-      const bool lds_actor = serl_lds_actor_shape(*d), split = !lds_actor && c->env_split_actor != 0 && d->hidden > 64 && d->hidden <= 128;
-      serl_note_launch(c, lds_actor ? SERL_FAMILY_TEAM : split ? SERL_FAMILY_TEAMS2 : SERL_FAMILY_TEAMS, d->n_episodes, 1, false, split ? 2 : 1, !lds_actor, 1, s.code);
-    }
-    if (timed) HIP_TRY(hipEventRecord(c->ev1, stream));
-    c->timed = timed;
-    return SERL_OK;
-  }
-  const int teamg = (lanes <= 0 && serl_has_wave_kernel(s.code)) ? serl_use_teamg(c, d, hint, together) : 0;
-  if (teamg) {
-    a.lanes = 1;
-    a.block = 512;
-    if (timed) HIP_TRY(hipEventRecord(c->ev0, stream));
-    // at most one team per CU; the episodes without a lane group at the start wait in the work queue (rollout_team_half.inc)
-    int grid = (d->n_episodes + teamg - 1) / teamg;
-    if (grid > c->num_cus && d->concurrent_episodes <= 0) {
-      grid = c->num_cus;
-      a.queue = serl_next_queue_counter(c);
-      a.q0 = grid * teamg;
-      HIP_TRY(hipMemsetAsync(a.queue, 0, sizeof(int32_t), stream));
-    } else {
-      a.queue = nullptr; a.q0 = d->n_episodes;
-    }
-    serl_launch_rollout_teamg(L, teamg, a, grid, stream);
-    HIP_TRY(hipGetLastError());
-    serl_note_launch(c, teamg == 4 ? SERL_FAMILY_TEAM4 : d->hidden != 32 ? SERL_FAMILY_TEAM2S : SERL_FAMILY_TEAM2, grid, teamg, a.queue != nullptr,
-                     (teamg == 2 && d->hidden != 32) ? 2 : 1, true /* the lane-group kernels' actor wavefronts stream the weights */, 1, s.code);
-    if (timed) HIP_TRY(hipEventRecord(c->ev1, stream));
-    c->timed = timed;
-    return SERL_OK;
-  }
-  // Round 6, the saturating regime: from 80 episodes per CU on, one episode per LANE -- 64 per wavefront, the lane's own actor in its registers over
-  // the regrouped weights (rollout_device.h serl_actor_forward_lane32_t), at most two tables in flight and hinted index searches in the generated evaluation
-  // (tools/dag/codegen_lane.py) -- outruns the queue launch of four-episode teams (episodes x 2 001 steps, M env-steps/s: 16 384: 47.4 against 49.1; 20 480: 53.0
-  // against 49.0; 32 768: 82.8; 65 536: 165.6 against 49.6; profiles/r06_saturate.jsonl).  The SERL50 actor shape, nominal / ice code, the attitude task, alone on the GPU.
-  if (lanes <= 0 && hint == SERL_KERNEL_AUTO && d->concurrent_episodes <= 0 && serl_has_lane_kernel(s.code) && d->hidden == 32 && d->state_dim == 7 &&
-      d->action_dim == 3 && d->n_episodes >= 80 * c->num_cus)
-    lanes = 64;
-  if (lanes <= 0 && serl_has_wave_kernel(s.code) && serl_use_team_rounds(c, d, hint, together)) {
-    // more than 4 x CUs episodes, alone on the GPU: rounds of 4 x CUs episodes (four per team, every CU busy), then the rest
-    // with whichever team kernel suits its count -- 4 x CUs + 2 episodes cost 30.8 + 21.6 us per env step, not 62.9
-    // ONE launch: a team of four lane groups per CU, the other episodes in the work queue (rollout_team_half.inc) -- a lane group
-    // takes the next episode when its own ends, so episodes of different lengths (training: untrained actors crash within
-    // seconds) keep every lane group busy instead of rounds that each wait for their longest episode.  (Round 2 ran rounds of
-    // 4 x CUs episodes; with equal-length episodes the tail of a queue run costs the four-per-team step where a round of its own
-    // could use the two-per-team kernel: 1 536 x 8 001 steps 7 % slower, any mix of lengths faster.)
-    a.lanes = 1;
-    a.block = 512;
-    if (timed) HIP_TRY(hipEventRecord(c->ev0, stream));
-    a.e0 = 0; a.e_end = d->n_episodes;
-    // alone on the GPU: a team on every CU.  Beside other launches (a mixed-fault sweep: one launch per dynamics build on streams of
-    // their own, each told the episodes of the others) the CUs are split by episode share, so that the teams of all launches are
-    // resident together and every launch drains its own queue at the four-per-team rate (round 3 fell back to two episodes per
-    // WAVEFRONT here: 24.1 M env-steps/s where the queue kernel gives 33.6 M on the nominal workload)
-    int grid = c->num_cus;
-    if (d->concurrent_episodes > 0) {
-      grid = (int)((long long)c->num_cus * d->n_episodes / together);
-      grid = grid < 1 ? 1 : grid;
-    }
-    if (grid * 4 >= d->n_episodes) {          // (a small share of a large sweep: every episode has a lane group, no queue)
-      grid = (d->n_episodes + 3) / 4;
-      a.queue = nullptr; a.q0 = d->n_episodes;
-    } else {
-      a.queue = serl_next_queue_counter(c);
-      a.q0 = 4 * grid;
-      HIP_TRY(hipMemsetAsync(a.queue, 0, sizeof(int32_t), stream));
-    }
-    L.team4(a, grid, stream);
-    HIP_TRY(hipGetLastError());
-    serl_note_launch(c, SERL_FAMILY_TEAM4, grid, 4, a.queue != nullptr, 1, true, 1, s.code);
-    if (timed) HIP_TRY(hipEventRecord(c->ev1, stream));
-    c->timed = timed;
-    return SERL_OK;
-  }
-  if (lanes <= 0 && serl_has_wave_kernel(s.code) && serl_use_half(c, d, hint, together)) {
-    const int waves = (d->n_episodes + 1) / 2;
-    int wpb = (waves + c->num_cus - 1) / c->num_cus;
-    wpb = wpb < 1 ? 1 : (wpb > 4 ? 4 : wpb);
-    a.lanes = 1;
-    a.block = 64 * wpb;
-    const int grid = (waves + wpb - 1) / wpb;
-    if (timed) HIP_TRY(hipEventRecord(c->ev0, stream));
-    L.half(a, grid, stream);
-    HIP_TRY(hipGetLastError());
-    serl_note_launch(c, SERL_FAMILY_HALF, grid, 2, false, 0, true, 1, s.code);
-    if (timed) HIP_TRY(hipEventRecord(c->ev1, stream));
-    c->timed = timed;
-    return SERL_OK;
-  }
-  if (lanes <= 0 && serl_has_wave_kernel(s.code)) {
-    // default: one wavefront per episode (model glue wave-uniform, look-ups / actor rows / ODE5 states per lane)
-    // side-by-side launches round their workgroup counts up separately: leave room for a few partial workgroups
-    const int wpb = serl_wave_kernel_waves_per_block(c, together + (timed ? 0 : 16));
-    a.lanes = 1;
-    a.block = 64 * wpb;
-    const int grid = (d->n_episodes + wpb - 1) / wpb;
-    if (timed) HIP_TRY(hipEventRecord(c->ev0, stream));
-    L.wave(a, grid, stream);
-    HIP_TRY(hipGetLastError());
-    serl_note_launch(c, SERL_FAMILY_WAVE, grid, 1, false, 0, true, 1, s.code);
-    if (timed) HIP_TRY(hipEventRecord(c->ev1, stream));
-    c->timed = timed;
-    return SERL_OK;
-  }
-  if (!serl_has_lane_kernel(s.code))
-    return fail(SERL_E_UNSUPPORTED, "serl_rollout: lanes_per_wave > 0 (lane-per-episode kernels): unknown code variant");
-  if (lanes <= 0) {
-    // A wavefront takes the same time per env step whether it carries 1 or 64 episodes, and wavefronts that
-    // share a CU slow each other down (measured: profiles/r01_microbench.md), so episodes are spread one
-    // wavefront per CU first (256 CUs) and only then packed into lanes.
-    lanes = (d->n_episodes + 255) / 256;
-    if (lanes < 1) lanes = 1;
-  }
-  if (lanes > 64) lanes = 64;
-  a.lanes = lanes;
-  const int waves = (d->n_episodes + lanes - 1) / lanes;
-  const int wpb = serl_waves_per_block(c, waves);
-  a.block = 64 * wpb;
-  const int grid = (waves + wpb - 1) / wpb;
-  if (c->env_lane_regroup && d->hidden == 32 && d->state_dim == 7 && d->action_dim == 3 && d->n_members <= (1 << 22)) {      // (rollout_device.h serl_lane_actor_ok)
-    const int rc = serl_regroup_weights(c, d, a, stream);
-    if (rc != SERL_OK) return rc;
-  }
-  if (timed) HIP_TRY(hipEventRecord(c->ev0, stream));
-  L.lane(a, grid, stream);
-  HIP_TRY(hipGetLastError());
-  if (a.wt) HIP_TRY(hipEventRecord(c->wt_done[c->wt_slot_of_launch], stream));
-  serl_note_launch(c, SERL_FAMILY_LANE, grid, lanes, false, 0, true, 1, s.code);
-  if (timed) HIP_TRY(hipEventRecord(c->ev1, stream));
-  c->timed = timed;
-  return SERL_OK;
+  return serl_rollout_impl(c, d, nullptr, hint, stream_);
 }
 
 int serl_rollout_noise_layout(int32_t *out, int32_t capacity)
@@ -721,9 +451,8 @@ int serl_rollout_noise_layout(int32_t *out, int32_t capacity)
   return n;
 }
 
-// serl_rollout with the sensor / exploration noise drawn inside the kernels: the noise instantiations of the lane-per-episode kernel (lanes_per_wave > 0, or
-// AUTO where serl_rollout's AUTO runs the lane kernel) and of the one-wavefront-per-episode kernels (everything else; the team, half and work-queue kernels
-// have no such instantiation).  Launch geometry, weight regrouping, timing events and the launch record are serl_rollout's for the same family.
+// serl_rollout with the sensor / exploration noise drawn inside the kernels.  Launch geometry, weight regrouping, timing events and the launch record are
+// serl_rollout's for the same family: one planner decides both (serl_plan.h serl_plan_rollout).
 int serl_rollout_noise(serl_ctx *c, const serl_rollout_desc *d, const serl_rollout_noise_desc *nz, void *stream_)
 {
   int hint = SERL_KERNEL_AUTO;
@@ -733,54 +462,7 @@ int serl_rollout_noise(serl_ctx *c, const serl_rollout_desc *d, const serl_rollo
   if (d->sensor_noise && nz->sensor) return fail(SERL_E_INVALID, "serl_rollout_noise: desc->sensor_noise together with nz->sensor");
   if (d->action_noise && nz->action) return fail(SERL_E_INVALID, "serl_rollout_noise: desc->action_noise together with nz->action");
   if (!(nz->action_sd >= 0.0) || !(nz->action_clip >= 0.0)) return fail(SERL_E_INVALID, "serl_rollout_noise: nz->action_sd / nz->action_clip < 0");
-  if (hint != SERL_KERNEL_AUTO && hint != SERL_KERNEL_WAVE)
-    return fail(SERL_E_UNSUPPORTED, "serl_rollout_noise: the TEAM / TEAM2 / TEAM4 / HALF / LANEQ kernels have no noise instantiation (kernel_hint AUTO or WAVE, or lanes_per_wave > 0)");
-  const bool general_env = d->env_config != SERL_ENV_ATTITUDE || d->incremental != 0;
-  HIP_TRY(hipSetDevice(c->device));
-  const BuildSlot &s = c->slots[d->build_slot];
-  const SerlRnLaunchers &L = k_rn_launchers[s.code];
-  hipStream_t stream = (hipStream_t)stream_;
-  RolloutArgs a;
-  serl_fill_args(c, d, a);
-  a.e0 = 0; a.e_end = d->n_episodes;
-  const bool timed = d->concurrent_episodes <= 0;
-  const int together = d->n_episodes + (d->concurrent_episodes > 0 ? d->concurrent_episodes : 0);
-  int lanes = d->lanes_per_wave;
-  // where serl_rollout's AUTO runs the lane kernel (the saturating regime: from 80 episodes per CU on, the SERL50 actor shape, alone on the GPU)
-  if (!general_env && lanes <= 0 && hint == SERL_KERNEL_AUTO && d->concurrent_episodes <= 0 && serl_has_lane_kernel(s.code) && d->hidden == 32 &&
-      d->state_dim == 7 && d->action_dim == 3 && d->n_episodes >= 80 * c->num_cus)
-    lanes = 64;
-  if (lanes <= 0) {      // one wavefront per episode: wavex for the env configurations other than the attitude task
-    const int wpb = serl_wave_kernel_waves_per_block(c, together + (timed ? 0 : 16));
-    a.lanes = 1;
-    a.block = 64 * wpb;
-    const int grid = (d->n_episodes + wpb - 1) / wpb;
-    if (timed) HIP_TRY(hipEventRecord(c->ev0, stream));
-    (general_env ? L.wavex : L.wave)(a, *nz, grid, stream);
-    HIP_TRY(hipGetLastError());
-    serl_note_launch(c, general_env ? SERL_FAMILY_WAVEX : SERL_FAMILY_WAVE, grid, 1, false, 0, true, 1, s.code);
-    if (timed) HIP_TRY(hipEventRecord(c->ev1, stream));
-    c->timed = timed;
-    return SERL_OK;
-  }
-  if (lanes > 64) lanes = 64;
-  a.lanes = lanes;
-  const int waves = (d->n_episodes + lanes - 1) / lanes;
-  const int wpb = serl_waves_per_block(c, waves);
-  a.block = 64 * wpb;
-  const int grid = (waves + wpb - 1) / wpb;
-  if (c->env_lane_regroup && d->hidden == 32 && d->state_dim == 7 && d->action_dim == 3 && d->n_members <= (1 << 22)) {      // (rollout_device.h serl_lane_actor_ok)
-    const int rc = serl_regroup_weights(c, d, a, stream);
-    if (rc != SERL_OK) return rc;
-  }
-  if (timed) HIP_TRY(hipEventRecord(c->ev0, stream));
-  L.lane(a, *nz, grid, stream);
-  HIP_TRY(hipGetLastError());
-  if (a.wt) HIP_TRY(hipEventRecord(c->wt_done[c->wt_slot_of_launch], stream));
-  serl_note_launch(c, SERL_FAMILY_LANE, grid, lanes, false, 0, true, 1, s.code);
-  if (timed) HIP_TRY(hipEventRecord(c->ev1, stream));
-  c->timed = timed;
-  return SERL_OK;
+  return serl_rollout_impl(c, d, nz, hint, stream_);
 }
 
 // Several descriptors -- one per dynamics build of a mixed-fault population -- in ONE launch of one code object (rollout_team4_mixed.hip).
@@ -803,7 +485,7 @@ int serl_rollout_multi(serl_ctx *c, int32_t n, const serl_rollout_desc *descs, v
       return fail(SERL_E_UNSUPPORTED, "serl_rollout_multi: attitude task, hidden 32, code variants nominal / ice, kernel_hint AUTO");
     together += d->n_episodes;
   }
-  if (together <= 2 * c->num_cus) return fail(SERL_E_UNSUPPORTED, "serl_rollout_multi: for more than 2 x CUs episodes (four per team)");
+  if (together <= 2 * c->caps.num_cus) return fail(SERL_E_UNSUPPORTED, "serl_rollout_multi: for more than 2 x CUs episodes (four per team)");
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t stream = (hipStream_t)stream_;
   SerlMixedArgs m;
@@ -823,30 +505,9 @@ int serl_rollout_multi(serl_ctx *c, int32_t n, const serl_rollout_desc *descs, v
     else HIP_TRY(hipEventCreateWithFlags(&c->mixed_ev[state_slot], hipEventDisableTiming));
     HIP_TRY(hipMemsetAsync(m.state, 0, SERL_MIXED_STATE * sizeof(int32_t), stream));
   }
-  const bool queue = together > 4 * c->num_cus;      // beyond four per CU: every part drains a work queue of its own on its share of the CUs
-  // workgroups of every part: one per four episodes, or (queue) the part's share of the CUs
-  int grids[SERL_MIXED_MAX], total_wg = 0;
-  for (int k = 0; k < n; ++k) {
-    const serl_rollout_desc *d = descs + k;
-    grids[k] = (d->n_episodes + 3) / 4;
-    if (queue) {
-      int share = (int)((long long)c->num_cus * d->n_episodes / together);
-      share = share < 1 ? 1 : share;
-      if (share * 4 < d->n_episodes) grids[k] = share;
-    }
-    total_wg += grids[k];
-  }
-  // The census placement needs every workgroup resident, one per CU (a team fills a CU's LDS).  The parts round up on their own -- 341 / 341 / 342
-  // episodes on 256 CUs are 86 + 86 + 86 = 258 workgroups, and a share bumped to 1 does the same in queue mode -- so the overflow is taken from the
-  // largest part, which drains the episodes it loses through its work queue.
-  while (total_wg > c->num_cus) {
-    int big = 0;
-    for (int k = 1; k < n; ++k) big = grids[k] > grids[big] ? k : big;
-    if (grids[big] <= 1) break;
-    const int cut = total_wg - c->num_cus < grids[big] - 1 ? total_wg - c->num_cus : grids[big] - 1;
-    grids[big] -= cut; total_wg -= cut;
-  }
-  if (total_wg > c->num_cus && m.place == 2) m.place = 1;      // (more parts than CUs: never all resident -- tickets at once instead of the census' time-out)
+  int32_t episodes[SERL_MIXED_MAX], grids[SERL_MIXED_MAX], queue = 0;
+  for (int k = 0; k < n; ++k) episodes[k] = descs[k].n_episodes;
+  serl_plan_multi(c->caps.num_cus, n, episodes, m.place, grids, &queue, &m.place);
   int wg = 0;
   for (int k = 0; k < n; ++k) {
     const serl_rollout_desc *d = descs + k;
@@ -888,59 +549,17 @@ int serl_dyn_open_loop(serl_ctx *c, int slot, int32_t n_episodes, int32_t T, con
                        int32_t lanes_per_wave, int32_t kernel_hint, void *stream_)
 {
   if (!c || !cmds || !states || n_episodes <= 0 || T <= 0) return fail(SERL_E_INVALID, "serl_dyn_open_loop: bad argument");
-  const int hint = lanes_per_wave > 0 ? SERL_KERNEL_AUTO : serl_resolve_hint(c, kernel_hint);
-  if (hint != SERL_KERNEL_AUTO && hint != SERL_KERNEL_TEAM && hint != SERL_KERNEL_WAVE)
-    return fail(SERL_E_UNSUPPORTED, "serl_dyn_open_loop: kernel_hint must be AUTO, TEAM or WAVE");
+  const SerlPlan p = serl_plan_dyn(&c->caps, n_episodes, lanes_per_wave, kernel_hint);
+  if (p.status != SERL_OK) return fail(p.status, p.message);
   if (slot < 0 || slot >= SERL_MAX_SLOTS || !c->slots[slot].loaded) return fail(SERL_E_INVALID, "serl_dyn_open_loop: build slot not loaded");
   HIP_TRY(hipSetDevice(c->device));
-  const BuildSlot &s = c->slots[slot];
-  const SerlLaunchers &L = serl_launchers(s.code);
-  RolloutArgs a;
-  memset(&a, 0, sizeof(a));
-  a.d.n_episodes = n_episodes;
-  a.ro = s.blob; a.t3 = s.blob + s.n_ro; a.x0 = a.t3 + 46; a.dw0 = a.x0 + 19;
-  a.dyn_dt = s.dt;
-  a.jitter = c->env_jitter; a.jitter_sites = c->env_jitter_sites;
   hipStream_t stream = (hipStream_t)stream_;
-  if (lanes_per_wave <= 0 && serl_use_team(c, hint, n_episodes)) {
-    a.lanes = 1;
-    a.block = 128;
-    HIP_TRY(hipEventRecord(c->ev0, stream));
-    L.dyn_team(a, cmds, states, T, n_episodes, stream);
-    HIP_TRY(hipGetLastError());
-    serl_note_launch(c, SERL_FAMILY_TEAM, n_episodes, 1, false, 0, false, 1, s.code);      // (dynamics only: the team without an actor wavefront)
-    HIP_TRY(hipEventRecord(c->ev1, stream));
-    c->timed = true;
-    return SERL_OK;
-  }
-  if (lanes_per_wave <= 0 && serl_has_wave_kernel(s.code)) {
-    const int wpb = serl_wave_kernel_waves_per_block(c, n_episodes);
-    a.lanes = 1;
-    a.block = 64 * wpb;
-    HIP_TRY(hipEventRecord(c->ev0, stream));
-    L.dyn_wave(a, cmds, states, T, (n_episodes + wpb - 1) / wpb, stream);
-    HIP_TRY(hipGetLastError());
-    serl_note_launch(c, SERL_FAMILY_WAVE, (n_episodes + wpb - 1) / wpb, 1, false, 0, false, 1, s.code);
-    HIP_TRY(hipEventRecord(c->ev1, stream));
-    c->timed = true;
-    return SERL_OK;
-  }
-  if (!serl_has_lane_kernel(s.code))
-    return fail(SERL_E_UNSUPPORTED, "serl_dyn_open_loop: lanes_per_wave > 0: unknown code variant");
-  int lanes = lanes_per_wave <= 0 ? (n_episodes + 255) / 256 : lanes_per_wave;
-  if (lanes > 64) lanes = 64;
-  a.lanes = lanes;
-  const int nwaves = (n_episodes + lanes - 1) / lanes;
-  const int wpb = serl_waves_per_block(c, nwaves);
-  a.block = 64 * wpb;
-  const int grid = (nwaves + wpb - 1) / wpb;
-  HIP_TRY(hipEventRecord(c->ev0, stream));
-  L.dyn_lane(a, cmds, states, T, grid, stream);
-  HIP_TRY(hipGetLastError());
-  serl_note_launch(c, SERL_FAMILY_LANE, grid, lanes, false, 0, false, 1, s.code);
-  HIP_TRY(hipEventRecord(c->ev1, stream));
-  c->timed = true;
-  return SERL_OK;
+  RolloutArgs a;
+  serl_fill_args(c, slot, n_episodes, a);
+  a.jitter = c->env_jitter; a.jitter_sites = c->env_jitter_sites;
+  const int code = c->slots[slot].code;
+  SerlLaunchDyn *launch = serl_launchers(code).*serl_dyn_launcher(p);
+  return serl_execute_plan(c, p, a, code, false, stream, [&](const RolloutArgs &a, int grid) { launch(a, cmds, states, T, grid, stream); });
 }
 
 // ---- the step-wise vector env (include/serl_amd.h, ABI v9) ----------------------------------------------------------------------
@@ -957,7 +576,7 @@ static int serl_venv_check(serl_ctx *c, const serl_venv_desc *d, const char *wha
   if (d->n_envs <= 0) return fail(SERL_E_INVALID, w + ": n_envs <= 0");
   if (d->build_slot < 0 || d->build_slot >= SERL_MAX_SLOTS || !c->slots[d->build_slot].loaded)
     return fail(SERL_E_INVALID, w + ": build slot not loaded");
-  if (!serl_has_lane_kernel(c->slots[d->build_slot].code)) return fail(SERL_E_UNSUPPORTED, w + ": unknown code variant");
+  if (c->slots[d->build_slot].code < 0 || c->slots[d->build_slot].code >= SERL_N_VARIANTS) return fail(SERL_E_UNSUPPORTED, w + ": unknown code variant");
   if (serl_env_state_dim(d->env_config, d->incremental) == 0)
     return fail(SERL_E_INVALID, w + ": env_config must be SERL_ENV_ATTITUDE, SERL_ENV_SYMMETRIC or SERL_ENV_FULL");
   if (d->state_dim != serl_env_state_dim(d->env_config, d->incremental) || d->action_dim != serl_env_action_dim(d->env_config))
@@ -979,66 +598,52 @@ static void serl_note_venv_launch(serl_ctx *c, int family, int grid, int waves_p
   c->last_venv_info[0] = family; c->last_venv_info[1] = grid; c->last_venv_info[2] = waves_per_block; c->last_venv_info[3] = code;
 }
 
-// the launch shape of serl_dyn_open_loop's lane kernels: lanes per wavefront from the batch, so that small batches still spread over the CUs
-static int serl_venv_launch(serl_ctx *c, const serl_venv_desc *d, bool step, VenvArgs &v, hipStream_t stream,
-                            const serl_venv_auto_desc *au = nullptr, const serl_venv_rollout_desc *rd = nullptr, bool general = false,
-                            const serl_venv_noise_desc *nz = nullptr, bool wave = false)
+// which env kernel a call launches, beside the descriptor and the VenvArgs
+struct SerlVenvCall {
+  bool step = false;                               // serl_venv_step (otherwise reset)
+  const serl_venv_auto_desc *au = nullptr;         // the step with auto-reset, or with rd: K steps
+  const serl_venv_rollout_desc *rd = nullptr;      // K steps under the in-kernel actor ...
+  bool general = false;                            // ... of any env configuration and actor shape (lane kernels)
+  const serl_venv_noise_desc *nz = nullptr;        // the instantiations with the in-kernel noise generator (there is no plain step among them)
+  bool wave = false;                               // one wavefront per env
+};
+
+static int serl_venv_launch(serl_ctx *c, const serl_venv_desc *d, VenvArgs &v, hipStream_t stream, const SerlVenvCall &k)
 {
-  const BuildSlot &s = c->slots[d->build_slot];
-  const SerlLaunchers &L = serl_launchers(s.code);
+  const int code = c->slots[d->build_slot].code;
+  const SerlPlan p = serl_plan_venv(&c->caps, d->n_envs, k.wave);
+  const int grid = p.grid;
   RolloutArgs a;
-  memset(&a, 0, sizeof(a));
-  a.d.n_episodes = d->n_envs;
-  a.ro = s.blob; a.t3 = s.blob + s.n_ro; a.x0 = a.t3 + 46; a.dw0 = a.x0 + 19;
-  a.dyn_dt = s.dt;
-  if (wave) {      // one wavefront per env (venv_wave.inc), the launch shape of the wave rollout kernels: the CUs fill before the workgroups do
-    const SerlVwLaunchers &W = k_vw_launchers[s.code];
-    int wpb = serl_wave_kernel_waves_per_block(c, d->n_envs);
-    if (wpb > 4) wpb = 4;
-    a.lanes = 1;
-    a.block = 64 * wpb;
-    const int grid = (d->n_envs + wpb - 1) / wpb;
-    v.d = *d;
-    v.npad = serl_venv_npad(d->n_envs);
-    if (rd) {      // K steps under the wave-cooperative actor (venv_wave_rollout.inc), which reads its shape as the lane forward does
-      const SerlVwrLaunchers &R = k_vwr_launchers[s.code];
-      a.d.state_dim = rd->state_dim; a.d.action_dim = rd->action_dim; a.d.hidden = rd->hidden;
-      a.d.num_layers = rd->num_layers; a.d.activation = rd->activation;
-      if (nz) R.rollout_nz(a, v, *au, *rd, *nz, grid, stream);
-      else R.rollout(a, v, *au, *rd, grid, stream);
-    } else if (nz) {
-      if (au) W.step_auto_nz(a, v, *au, *nz, grid, stream);
-      else W.reset_nz(a, v, *nz, grid, stream);
-    } else if (au) W.step_auto(a, v, *au, grid, stream);
-    else (step ? W.step : W.reset)(a, v, grid, stream);
-    HIP_TRY(hipGetLastError());
-    serl_note_venv_launch(c, SERL_FAMILY_WAVE, grid, wpb, s.code);
-    return SERL_OK;
-  }
-  int lanes = (d->n_envs + 255) / 256;
-  if (lanes > 64) lanes = 64;
-  a.lanes = lanes;
-  const int nwaves = (d->n_envs + lanes - 1) / lanes;
-  const int wpb = serl_waves_per_block(c, nwaves);
-  a.block = 64 * wpb;
-  const int grid = (nwaves + wpb - 1) / wpb;
+  serl_fill_args(c, d->build_slot, d->n_envs, a);
+  a.lanes = p.lanes;
+  a.block = p.block;
   v.d = *d;
   v.npad = serl_venv_npad(d->n_envs);
-  if (rd) {      // the actor shape the lane forward reads (rollout_device.h serl_actor_forward_lane32 / _lane_general)
-    a.d.state_dim = rd->state_dim; a.d.action_dim = rd->action_dim; a.d.hidden = rd->hidden;
-    a.d.num_layers = rd->num_layers; a.d.activation = rd->activation;
+  if (k.rd) {      // the actor shape the forward passes read (rollout_device.h serl_actor_forward_lane32 / _lane_general; venv_wave_rollout.inc reads it the same way)
+    a.d.state_dim = k.rd->state_dim; a.d.action_dim = k.rd->action_dim; a.d.hidden = k.rd->hidden;
+    a.d.num_layers = k.rd->num_layers; a.d.activation = k.rd->activation;
   }
-  if (nz) {      // (the same launch shapes around the noise instantiations; there is no plain step among them)
-    const SerlNzLaunchers &Z = k_nz_launchers[s.code];
-    if (rd) (general ? Z.rollout_general : Z.rollout)(a, v, *au, *rd, *nz, grid, stream);
-    else if (au) Z.step_auto(a, v, *au, *nz, grid, stream);
-    else Z.reset(a, v, *nz, grid, stream);
-  } else if (rd) {
-    (general ? L.venv_rollout_general : L.venv_rollout)(a, v, *au, *rd, grid, stream);
-  } else if (au) L.venv_step_auto(a, v, *au, grid, stream);
-  else (step ? L.venv_step : L.venv_reset)(a, v, grid, stream);
+  if (k.wave) {      // (venv_wave.inc, venv_wave_rollout.inc)
+    const SerlVwLaunchers &W = k_vw_launchers[code];
+    const SerlVwrLaunchers &R = k_vwr_launchers[code];
+    if (k.rd && k.nz) R.rollout_nz(a, v, *k.au, *k.rd, *k.nz, grid, stream);
+    else if (k.rd) R.rollout(a, v, *k.au, *k.rd, grid, stream);
+    else if (k.nz && k.au) W.step_auto_nz(a, v, *k.au, *k.nz, grid, stream);
+    else if (k.nz) W.reset_nz(a, v, *k.nz, grid, stream);
+    else if (k.au) W.step_auto(a, v, *k.au, grid, stream);
+    else (k.step ? W.step : W.reset)(a, v, grid, stream);
+  } else {
+    const SerlLaunchers &L = serl_launchers(code);
+    const SerlNzLaunchers &Z = k_nz_launchers[code];
+    if (k.rd && k.nz) (k.general ? Z.rollout_general : Z.rollout)(a, v, *k.au, *k.rd, *k.nz, grid, stream);
+    else if (k.rd) (k.general ? L.venv_rollout_general : L.venv_rollout)(a, v, *k.au, *k.rd, grid, stream);
+    else if (k.nz && k.au) Z.step_auto(a, v, *k.au, *k.nz, grid, stream);
+    else if (k.nz) Z.reset(a, v, *k.nz, grid, stream);
+    else if (k.au) L.venv_step_auto(a, v, *k.au, grid, stream);
+    else (k.step ? L.venv_step : L.venv_reset)(a, v, grid, stream);
+  }
   HIP_TRY(hipGetLastError());
-  serl_note_venv_launch(c, SERL_FAMILY_LANE, grid, wpb, s.code);
+  serl_note_venv_launch(c, p.family, grid, p.block / 64, code);
   return SERL_OK;
 }
 
@@ -1052,7 +657,9 @@ static int serl_venv_reset_impl(const char *w, serl_ctx *c, const serl_venv_desc
   memset(&v, 0, sizeof(v));
   v.mask = mask;
   v.obs = obs;
-  return serl_venv_launch(c, d, false, v, (hipStream_t)stream_, nullptr, nullptr, false, nz, wave);
+  SerlVenvCall k;
+  k.nz = nz; k.wave = wave;
+  return serl_venv_launch(c, d, v, (hipStream_t)stream_, k);
 }
 
 int serl_venv_reset(serl_ctx *c, const serl_venv_desc *d, const uint8_t *mask, double *obs, void *stream_)
@@ -1111,7 +718,9 @@ static int serl_venv_step_impl(const char *w, serl_ctx *c, const serl_venv_desc 
   memset(&v, 0, sizeof(v));
   v.actions = actions; v.actions_f64 = actions_f64;
   v.obs = obs; v.reward = reward; v.done = done; v.x = x; v.ref = ref; v.t = t; v.cost = cost;
-  return serl_venv_launch(c, d, true, v, (hipStream_t)stream_, nullptr, nullptr, false, nullptr, wave);
+  SerlVenvCall k;
+  k.step = true; k.wave = wave;
+  return serl_venv_launch(c, d, v, (hipStream_t)stream_, k);
 }
 
 int serl_venv_step(serl_ctx *c, const serl_venv_desc *d, const void *actions, int32_t actions_f64, double *obs,
@@ -1156,7 +765,9 @@ static int serl_venv_step_auto_impl(const char *w, serl_ctx *c, const serl_venv_
   memset(&v, 0, sizeof(v));
   v.actions = actions; v.actions_f64 = actions_f64;
   v.obs = obs; v.reward = reward; v.done = done; v.x = x; v.ref = ref; v.t = t; v.cost = cost;
-  return serl_venv_launch(c, &dd, true, v, (hipStream_t)stream_, au, nullptr, false, nz, wave);
+  SerlVenvCall k;
+  k.step = true; k.au = au; k.nz = nz; k.wave = wave;
+  return serl_venv_launch(c, &dd, v, (hipStream_t)stream_, k);
 }
 
 int serl_venv_step_auto(serl_ctx *c, const serl_venv_desc *d, const void *actions, int32_t actions_f64, double *obs,
@@ -1211,20 +822,21 @@ int serl_venv_rollout_layout(int32_t *out, int32_t capacity)
   return n;
 }
 
-static int serl_venv_rollout_impl(const char *what, serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd,
-                                  const serl_venv_noise_desc *nz, void *stream_)
+// What serl_venv_rollout_impl and serl_venv_rollout_general_impl check alike, around their own env / actor-shape refusals: the head ...
+// (the descriptors first: none of these checks reads the context)
+static int serl_venv_rollout_head(const std::string &w, serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd)
 {
-  const std::string w(what);
-  // (the descriptors first: none of these checks reads the context)
   if (!c || !d || !au || !rd) return fail(SERL_E_INVALID, w + ": NULL argument");
   if (!rd->obs || !rd->weights) return fail(SERL_E_INVALID, w + ": obs / weights is NULL");
   if (rd->n_steps < 1) return fail(SERL_E_INVALID, w + ": n_steps < 1");
   if (rd->n_members < 1) return fail(SERL_E_INVALID, w + ": n_members < 1");
-  if (d->env_config != SERL_ENV_ATTITUDE || d->incremental != 0)
-    return fail(SERL_E_INVALID, w + ": the attitude task without rate control only (env_config SERL_ENV_ATTITUDE, incremental 0)");
-  if (rd->hidden != 32 || rd->state_dim != 7 || rd->action_dim != 3)      // (rollout_device.h serl_lane_actor_ok)
-    return fail(SERL_E_INVALID, w + ": the in-kernel actor is 7 -> 32 .. -> 3 only (hidden 32, state_dim 7, action_dim 3)");
-  if (rd->num_layers < 0) return fail(SERL_E_INVALID, w + ": num_layers < 0");
+  return SERL_OK;
+}
+
+// ... and the tail, which ends in the launch
+static int serl_venv_rollout_tail(const std::string &w, serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd,
+                                  const serl_venv_noise_desc *nz, void *stream_, bool general, bool wave)
+{
   if (rd->activation != SERL_ACT_TANH && rd->activation != SERL_ACT_ELU && rd->activation != SERL_ACT_LEAKY_RELU)
     return fail(SERL_E_INVALID, w + ": unknown activation");
   if (rd->weight_stride < (int64_t)serl_param_count(rd->state_dim, rd->hidden, rd->num_layers, rd->action_dim) || (rd->weight_stride & 3) != 0 ||
@@ -1239,7 +851,22 @@ static int serl_venv_rollout_impl(const char *what, serl_ctx *c, const serl_venv
   HIP_TRY(hipSetDevice(c->device));
   VenvArgs v;
   memset(&v, 0, sizeof(v));
-  return serl_venv_launch(c, &dd, true, v, (hipStream_t)stream_, au, rd, false, nz);
+  SerlVenvCall k;
+  k.step = true; k.au = au; k.rd = rd; k.general = general; k.nz = nz; k.wave = wave;
+  return serl_venv_launch(c, &dd, v, (hipStream_t)stream_, k);
+}
+
+static int serl_venv_rollout_impl(const char *what, serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd,
+                                  const serl_venv_noise_desc *nz, void *stream_)
+{
+  const std::string w(what);
+  { const int rc_ = serl_venv_rollout_head(w, c, d, au, rd); if (rc_ != SERL_OK) return rc_; }
+  if (d->env_config != SERL_ENV_ATTITUDE || d->incremental != 0)
+    return fail(SERL_E_INVALID, w + ": the attitude task without rate control only (env_config SERL_ENV_ATTITUDE, incremental 0)");
+  if (rd->hidden != 32 || rd->state_dim != 7 || rd->action_dim != 3)      // (rollout_device.h serl_lane_actor_ok)
+    return fail(SERL_E_INVALID, w + ": the in-kernel actor is 7 -> 32 .. -> 3 only (hidden 32, state_dim 7, action_dim 3)");
+  if (rd->num_layers < 0) return fail(SERL_E_INVALID, w + ": num_layers < 0");
+  return serl_venv_rollout_tail(w, c, d, au, rd, nz, stream_, false, false);
 }
 
 int serl_venv_rollout(serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd, void *stream_)
@@ -1258,11 +885,7 @@ static int serl_venv_rollout_general_impl(const char *what, serl_ctx *c, const s
                                           const serl_venv_rollout_desc *rd, const serl_venv_noise_desc *nz, void *stream_, bool wave = false)
 {
   const std::string w(what);
-  // (the descriptors first: none of these checks reads the context)
-  if (!c || !d || !au || !rd) return fail(SERL_E_INVALID, w + ": NULL argument");
-  if (!rd->obs || !rd->weights) return fail(SERL_E_INVALID, w + ": obs / weights is NULL");
-  if (rd->n_steps < 1) return fail(SERL_E_INVALID, w + ": n_steps < 1");
-  if (rd->n_members < 1) return fail(SERL_E_INVALID, w + ": n_members < 1");
+  { const int rc_ = serl_venv_rollout_head(w, c, d, au, rd); if (rc_ != SERL_OK) return rc_; }
   if (serl_env_state_dim(d->env_config, d->incremental) == 0)
     return fail(SERL_E_INVALID, w + ": env_config must be SERL_ENV_ATTITUDE, SERL_ENV_SYMMETRIC or SERL_ENV_FULL");
   if (rd->state_dim != serl_env_state_dim(d->env_config, d->incremental) || rd->action_dim != serl_env_action_dim(d->env_config))
@@ -1270,21 +893,7 @@ static int serl_venv_rollout_general_impl(const char *what, serl_ctx *c, const s
   if (rd->hidden < 4 || rd->hidden > SERL_MAX_HIDDEN || rd->hidden % 4 != 0)
     return fail(SERL_E_UNSUPPORTED, w + ": hidden must be a multiple of 4 in 4 .. 128");
   if (rd->num_layers < 0 || rd->num_layers > 16) return fail(SERL_E_UNSUPPORTED, w + ": num_layers must be 0 .. 16");
-  if (rd->activation != SERL_ACT_TANH && rd->activation != SERL_ACT_ELU && rd->activation != SERL_ACT_LEAKY_RELU)
-    return fail(SERL_E_INVALID, w + ": unknown activation");
-  if (rd->weight_stride < (int64_t)serl_param_count(rd->state_dim, rd->hidden, rd->num_layers, rd->action_dim) || (rd->weight_stride & 3) != 0 ||
-      ((uintptr_t)rd->weights & 15) != 0)
-    return fail(SERL_E_INVALID, w + ": weight_stride below the parameter count or not a multiple of 4 floats, or weights not 16-byte aligned");
-  if (au->ref_pool && d->ref) return fail(SERL_E_INVALID, w + ": ref_pool together with desc->ref");
-  if (au->ref_pool && au->pool_rows < 1) return fail(SERL_E_INVALID, w + ": pool_rows < 1");
-  if (!au->run_return || !au->run_length || !au->cursor) return fail(SERL_E_INVALID, w + ": run_return / run_length / cursor is NULL");
-  serl_venv_desc dd = *d;
-  if (au->ref_pool) { dd.ref_spec = au->ref_pool; dd.ref_spec_stride = 1; }
-  { const int rc_ = serl_venv_check(c, &dd, w.c_str()); if (rc_ != SERL_OK) return rc_; }
-  HIP_TRY(hipSetDevice(c->device));
-  VenvArgs v;
-  memset(&v, 0, sizeof(v));
-  return serl_venv_launch(c, &dd, true, v, (hipStream_t)stream_, au, rd, true, nz, wave);
+  return serl_venv_rollout_tail(w, c, d, au, rd, nz, stream_, true, wave);
 }
 
 int serl_venv_rollout_general(serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd, void *stream_)
@@ -1309,6 +918,45 @@ int serl_venv_rollout_wave_noise(serl_ctx *c, const serl_venv_desc *d, const ser
 {
   { const int rc_ = serl_venv_noise_check("serl_venv_rollout_wave_noise", d, rd, nz); if (rc_ != SERL_OK) return rc_; }
   return serl_venv_rollout_general_impl("serl_venv_rollout_wave_noise", c, d, au, rd, nz, stream_, true);
+}
+
+// ---- the launch planner on the host (include/serl_amd.h): no context, no device ------------------------------------------------------
+static SerlCaps serl_caps_of(const int32_t v[7]) { return SerlCaps{v[0], v[1], v[2], v[3], v[4], v[5], v[6]}; }
+
+static int serl_plan_out(const SerlPlan &p, int32_t out[16])
+{
+  for (int i = 0; i < 16; ++i) out[i] = 0;
+  if (p.status != SERL_OK) return fail(p.status, p.message);
+  const int32_t v[16] = {p.family, p.grid, p.per_team, p.queue, p.actor_waves, p.streamed, p.launches, -1,
+                         p.block, p.lanes, p.q0, p.regroup, p.mail_bytes, p.timed, p.chunk, 0};
+  for (int i = 0; i < 16; ++i) out[i] = v[i];
+  return SERL_OK;
+}
+
+int serl_host_plan_rollout(const int32_t caps[7], const serl_rollout_desc *desc, int32_t noise, int32_t out[16])
+{
+  if (!caps || !desc || !out || caps[0] < 1 || desc->n_episodes < 1) return fail(SERL_E_INVALID, "serl_host_plan_rollout: bad argument");
+  const SerlCaps c = serl_caps_of(caps);
+  int hint = SERL_KERNEL_AUTO;
+  const char *message = "";
+  const int rc = serl_plan_check(&c, desc, &hint, &message);
+  if (rc != SERL_OK) { for (int i = 0; i < 16; ++i) out[i] = 0; return fail(rc, message); }
+  return serl_plan_out(serl_plan_rollout(&c, desc, hint, noise), out);
+}
+
+int serl_host_plan_dyn(const int32_t caps[7], int32_t n_episodes, int32_t lanes_per_wave, int32_t kernel_hint, int32_t out[16])
+{
+  if (!caps || !out || caps[0] < 1 || n_episodes < 1) return fail(SERL_E_INVALID, "serl_host_plan_dyn: bad argument");
+  const SerlCaps c = serl_caps_of(caps);
+  return serl_plan_out(serl_plan_dyn(&c, n_episodes, lanes_per_wave, kernel_hint), out);
+}
+
+int serl_host_plan_multi(int32_t num_cus, int32_t n, const int32_t *episodes, int32_t place, int32_t *grids, int32_t *queue, int32_t *place_out)
+{
+  if (num_cus < 1 || n < 1 || n > SERL_MIXED_MAX || !episodes || !grids || !queue || !place_out) return fail(SERL_E_INVALID, "serl_host_plan_multi: bad argument");
+  for (int k = 0; k < n; ++k) if (episodes[k] < 1) return fail(SERL_E_INVALID, "serl_host_plan_multi: bad argument");
+  serl_plan_multi(num_cus, n, episodes, place, grids, queue, place_out);
+  return SERL_OK;
 }
 
 /* development aid (SERL_PROFILE=1): shader-clock cycles wave 0 of workgroup 0 spent in the actor forward, the

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <string>
 #include "../../include/serl_amd.h"
+#include "serl_plan.h"
 
 #define SERL_MAX_SLOTS 16
 #define SERL_QUEUE_COUNTERS 64
@@ -31,13 +32,9 @@ struct BuildSlot {
 
 struct serl_ctx {
   int device = 0;
-  int num_cus = 256;                    // multiProcessorCount of this context's device
+  SerlCaps caps = serl_default_caps();  // what the launch planner reads (serl_plan.h): the device's CUs and the development overrides
   int lds_per_block = 65536;            // sharedMemPerBlockOptin
-  // environment overrides, read once when the context is made (-1 = not set)
-  int env_kernel = 0 /* serl_kernel_hint from SERL_KERNEL */, env_waves_per_block = -1, env_profile = 0;
-  int env_laneq_waves = -1;             // SERL_LANEQ_WAVES: cap on the wavefronts of a SERL_KERNEL_LANEQ launch (default 4 x CUs)
-  int env_split_actor = 0;              // SERL_SPLIT_ACTOR=1: streamed actors of one-episode teams (hidden > 64) on TWO actor wavefronts that share the forward pass
-                                        // (family_teams2.hip; measured slower than one wavefront with the specialised forward: profiles/r04_experiments.md)
+  int env_profile = 0;                  // SERL_PROFILE (environment overrides are read once when the context is made)
   unsigned env_jitter_sites = ~0u;      // SERL_JITTER_SITES: classes of sites that pause (citation_wave.h; all by default)
   int env_mixed_place = SERL_MIXED_PLACE_DEFAULT;      // SERL_MIXED_PLACE: how serl_rollout_multi places the parts' workgroups (serl_mixed.h)
   int32_t *mixed_state = nullptr;       // device [SERL_MIXED_STATES][SERL_MIXED_STATE]
@@ -50,10 +47,8 @@ struct serl_ctx {
   unsigned long long *prof = nullptr;   // device [32], allocated when SERL_PROFILE=1
   int32_t *queue = nullptr;             // device [SERL_QUEUE_COUNTERS]: work-queue counters of the multi-episode team kernels, one per LAUNCH (a ring)
   int queue_next = 0;
-  int env_remote_actor = 1;             // SERL_REMOTE_ACTOR=0: streamed actors of one-episode teams stay on the team's CU (family_team.hip serl_rollout_teams_kernel_; A/B)
   void *mail = nullptr;                 // device [SERL_MAIL_REGIONS][num_cus] SerlMail: team <-> remote actor workgroup (family_teamr.hip)
   int mail_next = 0;
-  int env_lane_regroup = 1;             // SERL_LANE_WEIGHTS=rows: the lane-per-episode kernels walk [members][P] rows instead of the regrouped copy (A/B)
   void *wt[SERL_WT_SLOTS] = {};         // lane-per-episode kernels: regrouped weights [ceil(P / 4)][members up to 64][4] of the launches in flight (a ring; grown on demand)
   size_t wt_cap[SERL_WT_SLOTS] = {};
   int wt_next = 0;

@@ -43,6 +43,42 @@ class PopResult:
                                                # decision 1 = census of the CU pairs, 2 = tickets -- the GPU was shared or the pair mapping collided --, 0 = blockIdx ranges)
 
 
+def _info_dict(out):
+    """serl_last_rollout_info's 8 words as RolloutEngine.last_rollout_info() returns them"""
+    return dict(family=_capi.FAMILIES[int(out[0])], workgroups=int(out[1]), episodes_per_team=int(out[2]), work_queue=bool(out[3]),
+                actor_wavefronts=int(out[4]), actor_streamed=bool(out[5]), launches=int(out[6]), code=int(out[7]))
+
+
+def planner_caps(num_cus, env=None):
+    """What a context on a device of `num_cus` CUs makes of the development overrides in `env` (a mapping such as os.environ; None = none set):
+    the caps[7] of serl_host_plan_rollout (include/serl_amd.h)."""
+    env = env or {}
+    num = lambda k, default: int(env[k]) if k in env else default
+    return [int(num_cus), _capi.KERNEL_HINTS.get(env.get('SERL_KERNEL'), 0), num('SERL_WAVES_PER_BLOCK', -1), num('SERL_LANEQ_WAVES', -1),
+            num('SERL_SPLIT_ACTOR', 0), num('SERL_REMOTE_ACTOR', 1), 0 if env.get('SERL_LANE_WEIGHTS') == 'rows' else 1]
+
+
+def plan_rollout(spec: Optional[NetSpec], n_episodes, *, num_cus=None, caps=None, lanes_per_wave=0, concurrent_episodes=0, kernel=None, env_config=0,
+                 incremental=False, n_members=1, noise=False, open_loop=False):
+    """WHAT RolloutEngine.rollout (noise=True: with device noise; open_loop=True: dynamics_open_loop, spec unused) would launch on a device of `num_cus`
+    CUs -- the library's own decision (C ABI serl_host_plan_rollout / serl_host_plan_dyn), no GPU needed.  caps: planner_caps(...) instead of num_cus, for
+    the development overrides.  Returns the dict of last_rollout_info() (code = -1: no build is involved) extended by block (threads per workgroup),
+    lanes, first_queued, regroup, mailbox_bytes, timed, episodes_per_launch.  A call the library would refuse raises RuntimeError with its status and text."""
+    L = _capi.lib()
+    caps = (ctypes.c_int32 * 7)(*(caps if caps is not None else planner_caps(num_cus)))
+    out = (ctypes.c_int32 * 16)()
+    if open_loop:
+        _capi.check(L.serl_host_plan_dyn(caps, int(n_episodes), int(lanes_per_wave), _capi.KERNEL_HINTS[kernel], out), 'serl_host_plan_dyn')
+    else:
+        d = _capi.RolloutDesc(state_dim=spec.state_dim, action_dim=spec.action_dim, hidden=spec.hidden, num_layers=spec.num_layers,
+                              activation=spec.activation_id, n_members=int(n_members), weight_stride=spec.row_stride, n_episodes=int(n_episodes), max_steps=1,
+                              lanes_per_wave=int(lanes_per_wave), kernel_hint=_capi.KERNEL_HINTS[kernel], concurrent_episodes=int(concurrent_episodes),
+                              env_config=int(env_config), incremental=int(bool(incremental)))
+        _capi.check(L.serl_host_plan_rollout(caps, ctypes.byref(d), int(bool(noise)), out), 'serl_host_plan_rollout')
+    return dict(_info_dict(out), block=int(out[8]), lanes=int(out[9]), first_queued=int(out[10]), regroup=bool(out[11]), mailbox_bytes=int(out[12]),
+                timed=bool(out[13]), episodes_per_launch=int(out[14]))
+
+
 class RolloutEngine:
     """One per process / GPU.  Not thread-safe (one HIP context, calls are stream-ordered)."""
 
@@ -285,8 +321,15 @@ class RolloutEngine:
         actor_wavefronts, actor_streamed, launches, code).  Does not wait for the device."""
         out = (ctypes.c_int32 * 8)()
         _capi.check(self.lib.serl_last_rollout_info(self.ctx, out), 'serl_last_rollout_info')
-        return dict(family=_capi.FAMILIES[int(out[0])], workgroups=int(out[1]), episodes_per_team=int(out[2]), work_queue=bool(out[3]),
-                    actor_wavefronts=int(out[4]), actor_streamed=bool(out[5]), launches=int(out[6]), code=int(out[7]))
+        return _info_dict(out)
+
+    def plan_rollout(self, spec, n_episodes, *, build='h2000_v90', kernel=None, **kw):
+        """plan_rollout() for this engine: its device's CUs, the development overrides of the process environment, its kernel_hint, and
+        `code` of `build` -- what last_rollout_info() reports after the same rollout(...) / dynamics_open_loop(...) call."""
+        import os
+        plan = plan_rollout(spec, n_episodes, caps=planner_caps(self.num_cus, os.environ), kernel=kernel if kernel is not None else self.kernel_hint, **kw)
+        plan['code'] = builds.CODE_IDS[builds.load(build)[1]['code']]
+        return plan
 
     def mixed_placement(self):
         """How the most recent rollout_multi launch placed its workgroups (development aid, include/serl_amd.h serl_debug_mixed_placement):
