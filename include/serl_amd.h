@@ -796,6 +796,61 @@ int serl_td3_rng_fill(serl_ctx *ctx, const serl_td3_rng_desc *rng, int32_t learn
  * 1 <= batch <= n_rows (batch^2 / 2 comparisons).  SERL_E_INVALID for a NULL out, batch < 1 or n_rows < batch. */
 int serl_host_td3_slots(uint64_t seed, int32_t learner, int32_t iteration, int32_t n_rows, int32_t batch, int32_t *out);
 
+/* ---- a group of independent TD3 learners in one launch (SERL_ABI_VERSION stays 9: new symbols only, nothing above has moved; the two
+ * structs have a layout self-check of their own, serl_td3_group_layout) -------------------------------------------------------------
+ * serl_td3_train_rng runs n_learners learners too, but with one ring allocation, one n_updates / iteration0 / n_rows and one set of
+ * hyper-parameters for all of them.  Independent experiments of one network shape -- several seeds, a few settings -- differ in all of
+ * these every generation.  serl_td3_train_group takes them per learner from a DEVICE array of rows: one workgroup per learner as
+ * before, no grid-wide synchronisation, no workgroup waiting on another, the workspace of serl_td3_work_bytes(n_learners, ...).
+ *   desc     shape, n_learners, batch, max_grad_norm, the eight state rows with their strides, adam_steps, td_loss / pg_loss /
+ *            loss_stride, work and work_bytes mean what they mean for serl_td3_train and get its checks, in its order, with its codes.
+ *            n_updates is the most any learner of the launch may run (a row's bound, and loss_stride's).  ring, ring_stride, capacity,
+ *            iteration0, policy_update_freq, update_actor_target, the eight hyper-parameters lr .. eps_sd and all table fields are
+ *            ignored and may be zero or NULL.
+ *   rows     one serl_td3_learner_row per learner.  Like serl_ref_spec rows, the library does NOT read them on the host (that would
+ *            take a synchronisation): workgroup p reads rows[p] once, checks it before it touches any other memory, and reports in
+ *            status[p] (DEVICE i32 [n_learners]): 0 = the learner ran, else the first failed check (enum serl_td3_row_status).  A
+ *            refused learner writes its status and nothing else; every other array of it stays bit for bit unchanged, and the other
+ *            learners of the launch are not affected.  A row with n_updates == 0 is valid and leaves all but its status unchanged.
+ *            The status array is the report: the return value only tells that the launch was made.
+ *   dense    0 = valu, 1 = mfma;  caps 0 = CAPS off for every learner (lambda_s, lambda_t, eps_sd must still pass the checks), 1 = on.
+ * Contract: every array learner p writes -- its four rows, its four moment rows, its adam_steps pair, td_loss[p] and pg_loss[p] --
+ * equals, bit for bit, what a single-learner serl_td3_train_rng call writes whose descriptor holds the row's ring, capacity, n_updates,
+ * iteration0, policy_update_freq, update_actor_target and hyper-parameters and whose rng = {seed, n_rows, learner0 = key, dense, caps}.
+ * The kernels are further instantiations of the one source: they differ from serl_td3_train_rng's where these values are read only.
+ * A learner's result does not depend on the other learners or on its place in the grid. */
+typedef struct serl_td3_learner_row {
+  const float *ring;                /* DEVICE f32 [capacity][2 S + A + 3], this learner's own */
+  uint64_t seed;                    /* with key: the generator's (seed, learner key) of serl_td3_rng_desc */
+  int32_t capacity, n_rows;         /* batch <= n_rows <= capacity: the filled rows the slots are drawn from */
+  int32_t n_updates, iteration0;    /* 0 <= n_updates <= desc->n_updates; iteration0 >= 0, iteration0 + n_updates <= INT32_MAX - 1 */
+  int32_t key;
+  int32_t policy_update_freq;       /* >= 1 */
+  int32_t update_actor_target, pad0;
+  float lr, gamma, tau, noise_sd, noise_clip, lambda_s, lambda_t, eps_sd;     /* the ranges serl_td3_train checks; none may be NaN */
+} serl_td3_learner_row;
+enum serl_td3_row_status {
+  SERL_TD3_ROW_OK = 0,
+  SERL_TD3_ROW_RING = 1,            /* ring is NULL */
+  SERL_TD3_ROW_UPDATES = 2,         /* n_updates < 0 or above desc->n_updates */
+  SERL_TD3_ROW_ITERATION = 3,       /* iteration0 < 0, or iteration0 + n_updates overflows */
+  SERL_TD3_ROW_ROWS = 4,            /* n_rows < batch or n_rows > capacity */
+  SERL_TD3_ROW_FREQ = 5,            /* policy_update_freq < 1 */
+  SERL_TD3_ROW_HYPER = 6            /* lr <= 0, gamma < 0, tau outside [0, 1], noise_sd / noise_clip / eps_sd < 0, or a NaN */
+};
+typedef struct serl_td3_group_desc {
+  const serl_td3_learner_row *rows; /* DEVICE [n_learners] */
+  int32_t *status;                  /* DEVICE i32 [n_learners], written by every workgroup */
+  int32_t dense;                    /* 0 = valu, 1 = mfma */
+  int32_t caps;                     /* 0 = CAPS off, 1 = on */
+} serl_td3_group_desc;
+/* layout self-check: sizeof(serl_td3_learner_row), offsetof of each member in declaration order, then the same of serl_td3_group_desc */
+int serl_td3_group_layout(int32_t *out, int32_t capacity);
+/* Asynchronous on `stream`, ONE launch (made for desc->n_updates == 0 too: the status is still written); nothing is allocated or
+ * synchronised.  SERL_E_INVALID / SERL_E_UNSUPPORTED for `desc` exactly where serl_td3_train_rng returns them for the fields that are
+ * not ignored; then SERL_E_INVALID for a NULL group, NULL rows or status, dense or caps other than 0 / 1; all with nothing launched. */
+int serl_td3_train_group(serl_ctx *ctx, const serl_td3_desc *desc, const serl_td3_group_desc *group, void *stream);
+
 /* ---- the launch planner on the host (SERL_ABI_VERSION stays 9: new symbols only) --------------------------------------------------
  * WHAT serl_rollout / serl_rollout_noise (noise != 0) would launch for `desc` on a device of caps[0] CUs: the library's own decision
  * (csrc/serl_plan.h), without a context or a device.  caps[7] = {CUs, SERL_KERNEL as enum serl_kernel_hint (0 = unset),

@@ -27,10 +27,10 @@ from .generation import evaluate_generation, validate_actor, GenerationResult
 from .replay import DeviceReplay
 from .ssne import SSNE
 from .venv import CitationVecEnv, venv_noise
-from .td3 import TD3, Critic, td3_draws
+from .td3 import TD3, TD3Group, Critic, td3_draws
 from .actor import pack_critic, unpack_critic
 from . import refsignals, metrics, ga, distributed, builds, replay, ssne, td3
 
 __all__ = ['Actor', 'GeneticAgent', 'pack_actor', 'pack_population', 'NetSpec', 'Episode', 'RolloutEngine',
            'evaluate_pop', 'validate_pop', 'make_evaluate', 'PopResult', 'evaluate_generation', 'validate_actor',
-           'GenerationResult', 'DeviceReplay', 'SSNE', 'CitationVecEnv', 'venv_noise', 'TD3', 'Critic', 'td3_draws', 'pack_critic', 'unpack_critic', 'td3', 'replay', 'ssne', 'refsignals', 'metrics', 'ga', 'distributed', 'builds']
+           'GenerationResult', 'DeviceReplay', 'SSNE', 'CitationVecEnv', 'venv_noise', 'TD3', 'TD3Group', 'Critic', 'td3_draws', 'pack_critic', 'unpack_critic', 'td3', 'replay', 'ssne', 'refsignals', 'metrics', 'ga', 'distributed', 'builds']

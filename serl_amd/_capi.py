@@ -22,7 +22,8 @@ EXPORTS = ['serl_abi_version', 'serl_last_error', 'serl_param_count', 'serl_ctx_
            'serl_venv_last_info', 'serl_venv_rollout_wave', 'serl_venv_rollout_wave_noise',
            'serl_rollout_noise', 'serl_rollout_noise_layout',
            'serl_td3_train_rng', 'serl_td3_rng_layout', 'serl_td3_rng_fill', 'serl_host_td3_slots',
-           'serl_host_plan_rollout', 'serl_host_plan_dyn', 'serl_host_plan_multi']
+           'serl_host_plan_rollout', 'serl_host_plan_dyn', 'serl_host_plan_multi',
+           'serl_td3_train_group', 'serl_td3_group_layout']
 
 
 class BuildDesc(ctypes.Structure):
@@ -147,6 +148,29 @@ def expected_td3_rng_layout():
     return [ctypes.sizeof(Td3RngDesc)] + [getattr(Td3RngDesc, n).offset for n, _ in Td3RngDesc._fields_]
 
 
+class Td3LearnerRow(ctypes.Structure):
+    """serl_td3_learner_row: one learner of a serl_td3_train_group launch, read on the DEVICE (checked against the library by serl_td3_group_layout)"""
+    _fields_ = ([('ring', VP), ('seed', ctypes.c_uint64)] +
+                [(n, ctypes.c_int32) for n in ('capacity', 'n_rows', 'n_updates', 'iteration0', 'key', 'policy_update_freq',
+                                               'update_actor_target', 'pad0')] +
+                [(n, ctypes.c_float) for n in ('lr', 'gamma', 'tau', 'noise_sd', 'noise_clip', 'lambda_s', 'lambda_t', 'eps_sd')])
+
+
+class Td3GroupDesc(ctypes.Structure):
+    """serl_td3_group_desc: the rows and the status array of a serl_td3_train_group launch"""
+    _fields_ = [('rows', VP), ('status', VP), ('dense', ctypes.c_int32), ('caps', ctypes.c_int32)]
+
+
+def expected_td3_group_layout():
+    """What serl_td3_group_layout() must return for Td3LearnerRow and Td3GroupDesc to be right."""
+    return sum(([ctypes.sizeof(T)] + [getattr(T, n).offset for n, _ in T._fields_] for T in (Td3LearnerRow, Td3GroupDesc)), [])
+
+
+# enum serl_td3_row_status: what a workgroup of serl_td3_train_group writes to status[p]
+TD3_ROW_STATUS = {0: 'ok', 1: 'ring is NULL', 2: 'n_updates < 0 or above the launch\'s', 3: 'iteration0 < 0 or iteration0 + n_updates overflows',
+                  4: 'n_rows < batch or n_rows > capacity', 5: 'policy_update_freq < 1', 6: 'a hyper-parameter out of range or NaN'}
+
+
 # serl_rollout_desc.kernel_hint (enum serl_kernel_hint)
 KERNEL_HINTS = {None: 0, 'auto': 0, 'team': 1, 'wave': 2, 'half': 3, 'team2': 4, 'team4': 5, 'laneq': 6}
 ABI_VERSION = 9
@@ -241,6 +265,8 @@ def lib():
     L.serl_td3_train_rng.argtypes = [VP, ctypes.POINTER(Td3Desc), ctypes.POINTER(Td3RngDesc), VP]
     L.serl_td3_rng_fill.argtypes = [VP, ctypes.POINTER(Td3RngDesc)] + [i32] * 7 + [VP, VP, VP, VP]
     L.serl_host_td3_slots.argtypes = [ctypes.c_uint64, i32, i32, i32, i32, VP]
+    L.serl_td3_group_layout.argtypes = [VP, ctypes.c_int32]
+    L.serl_td3_train_group.argtypes = [VP, ctypes.POINTER(Td3Desc), ctypes.POINTER(Td3GroupDesc), VP]
     L.serl_host_plan_rollout.argtypes = [_I, ctypes.POINTER(RolloutDesc), i32, _I]
     L.serl_host_plan_dyn.argtypes = [_I, i32, i32, i32, _I]
     L.serl_host_plan_multi.argtypes = [i32, i32, _I, i32, _I, _I, _I]
@@ -272,6 +298,12 @@ def lib():
     if n != len(want) or list(got) != want:
         raise RuntimeError('serl_amd: layout of the Td3RngDesc mirror differs from the library (serl_td3_rng_layout): library %s, binding %s'
                            % (list(got)[:n], want))
+    want = expected_td3_group_layout()
+    got = (ctypes.c_int32 * len(want))()
+    n = L.serl_td3_group_layout(got, len(want))
+    if n != len(want) or list(got) != want:
+        raise RuntimeError('serl_amd: layout of the Td3LearnerRow / Td3GroupDesc mirrors differs from the library (serl_td3_group_layout): '
+                           'library %s, binding %s' % (list(got)[:n], want))
     want = expected_venv_auto_layout()
     got = (ctypes.c_int32 * len(want))()
     n = L.serl_venv_auto_layout(got, len(want))

@@ -43,6 +43,59 @@ struct Td3Rng {
   int n_rows, learner0, caps;
 };
 struct Td3ArgsRng : Td3Args { Td3Rng rg; };
+// the group flavours (serl_td3_train_group): what is per launch above is per learner here, one row each
+struct Td3ArgsGroup : Td3Args {
+  const serl_td3_learner_row *rows;
+  int32_t *status;
+  int caps;
+};
+template <bool RNG, bool GROUP>
+using Td3KernelArgs = std::conditional_t<GROUP, Td3ArgsGroup, std::conditional_t<RNG, Td3ArgsRng, Td3Args>>;
+
+// a learner's row in registers (the group flavours); members named like the descriptor's and the generator's they stand in for
+struct Td3Learner {
+  const float *ring;
+  uint64_t seed;
+  int capacity, n_rows, n_updates, iteration0, key, policy_update_freq, update_actor_target, caps;
+  float lr, gamma, tau, noise_sd, noise_clip, lambda_s, lambda_t, eps_sd;
+};
+
+__device__ __forceinline__ int uniform_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ float uniform_f(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+__device__ __forceinline__ uint64_t uniform_u64(uint64_t v)
+{
+  return (uint64_t)(uint32_t)uniform_i((int)(uint32_t)v) | (uint64_t)(uint32_t)uniform_i((int)(uint32_t)(v >> 32)) << 32;
+}
+
+// a learner's row, read once, every value in scalar registers
+__device__ __forceinline__ Td3Learner td3_read_row(const serl_td3_learner_row *row, int caps)
+{
+  Td3Learner q;
+  q.ring = reinterpret_cast<const float *>(uniform_u64(reinterpret_cast<uint64_t>(row->ring)));
+  q.seed = uniform_u64(row->seed);
+  q.capacity = uniform_i(row->capacity); q.n_rows = uniform_i(row->n_rows); q.n_updates = uniform_i(row->n_updates);
+  q.iteration0 = uniform_i(row->iteration0); q.key = uniform_i(row->key); q.policy_update_freq = uniform_i(row->policy_update_freq);
+  q.update_actor_target = uniform_i(row->update_actor_target); q.caps = caps;
+  q.lr = uniform_f(row->lr); q.gamma = uniform_f(row->gamma); q.tau = uniform_f(row->tau); q.noise_sd = uniform_f(row->noise_sd);
+  q.noise_clip = uniform_f(row->noise_clip); q.lambda_s = uniform_f(row->lambda_s); q.lambda_t = uniform_f(row->lambda_t);
+  q.eps_sd = uniform_f(row->eps_sd);
+  return q;
+}
+
+// The host cannot read a device row without a synchronisation: the checks td3_train makes of the same values in a descriptor, made by
+// the learner's workgroup.  -> 0, or the code of the first check that fails (enum serl_td3_row_status)
+__device__ __forceinline__ int td3_check_row(const Td3Learner &q, int batch, int max_updates)
+{
+  if (!q.ring) return SERL_TD3_ROW_RING;
+  if (q.n_updates < 0 || q.n_updates > max_updates) return SERL_TD3_ROW_UPDATES;
+  if (q.iteration0 < 0 || (long long)q.iteration0 + q.n_updates > 2147483646LL) return SERL_TD3_ROW_ITERATION;
+  if (q.n_rows < batch || q.n_rows > q.capacity) return SERL_TD3_ROW_ROWS;
+  if (q.policy_update_freq < 1) return SERL_TD3_ROW_FREQ;
+  if (!(q.lr > 0.0f) || !(q.gamma >= 0.0f) || !(q.tau >= 0.0f && q.tau <= 1.0f) || !(q.noise_sd >= 0.0f) || !(q.noise_clip >= 0.0f) ||
+      !(q.eps_sd >= 0.0f) || q.lambda_s != q.lambda_s || q.lambda_t != q.lambda_t)
+    return SERL_TD3_ROW_HYPER;
+  return SERL_TD3_ROW_OK;
+}
 
 __device__ __forceinline__ float t_act(float v, int act)
 {
@@ -432,9 +485,13 @@ __device__ __forceinline__ float td3_draw_caps(uint64_t seed, int key, int itera
 
 // RNG = false: slots and draws from the caller's tables (serl_td3_train / _mfma).  RNG = true: the same source, with the slot read from
 // an LDS array one wavefront fills at the top of each update and both draws generated in registers by the thread that would read them.
-template <bool MFMA, bool RNG>
-__global__ void __launch_bounds__(NT) td3_kernel(std::conditional_t<RNG, Td3ArgsRng, Td3Args> a)
+// GROUP = true (with RNG; serl_td3_train_group): the same source again, with what is one value per launch elsewhere -- the ring, the
+// counts, the hyper-parameters, the generator's seed and key -- taken from the learner's row, which the workgroup reads and checks
+// itself before it touches any other memory.
+template <bool MFMA, bool RNG, bool GROUP = false>
+__global__ void __launch_bounds__(NT) td3_kernel(Td3KernelArgs<RNG, GROUP> a)
 {
+  static_assert(RNG || !GROUP, "the group flavours draw inside the kernel");
   extern __shared__ float lds[];
   const serl_td3_desc &d = a.d;
   const int p = blockIdx.x;
@@ -443,8 +500,18 @@ __global__ void __launch_bounds__(NT) td3_kernel(std::conditional_t<RNG, Td3Args
   float *tq = c.red + 64;               // [BP] target Q
   int *slot_l = reinterpret_cast<int *>(tq + BP);      // [BP] the minibatch's slots (RNG only: td3_lds_bytes)
   Td3Rng rg = {};
-  if constexpr (RNG) rg = a.rg;
-  const int key = rg.learner0 + p;
+  if constexpr (RNG && !GROUP) rg = a.rg;
+  // a value that is the learner's own in a group launch and the launch's otherwise: the choice is made when the flavour is compiled
+#define TD3_MY(m) (GROUP ? my.m : d.m)
+#define TD3_MY_RNG(m) (GROUP ? my.m : rg.m)
+  Td3Learner my = {};
+  if constexpr (GROUP) {
+    my = td3_read_row(a.rows + p, a.caps);
+    const int refused = td3_check_row(my, d.batch, d.n_updates);
+    if (threadIdx.x == 0) a.status[p] = refused;
+    if (refused != SERL_TD3_ROW_OK) return;
+  }
+  const int key = GROUP ? my.key : rg.learner0 + p;
   c.t = threadIdx.x; c.b = c.t & (BP - 1); c.g = __builtin_amdgcn_readfirstlane(c.t >> 7);
   c.wave = __builtin_amdgcn_readfirstlane(c.t >> 6); c.lane = c.t & 63;
   c.B = d.batch; c.B4 = (d.batch + 3) & ~3; c.act = d.activation;
@@ -457,11 +524,11 @@ __global__ void __launch_bounds__(NT) td3_kernel(std::conditional_t<RNG, Td3Args
   float *ma = d.actor_m + (size_t)p * d.actor_stride, *va = d.actor_v + (size_t)p * d.actor_stride;
   float *wc = d.critic + (size_t)p * d.critic_stride, *wct = d.critic_target + (size_t)p * d.critic_stride;
   float *mc = d.critic_m + (size_t)p * d.critic_stride, *vc = d.critic_v + (size_t)p * d.critic_stride;
-  const float *ring = d.ring + (size_t)p * d.ring_stride;
+  const float *ring = GROUP ? my.ring : d.ring + (size_t)p * d.ring_stride;
   const int32_t *slots = RNG ? nullptr : d.slots + (size_t)p * d.slots_stride;
   const float *tnoise = RNG ? nullptr : d.target_noise + (size_t)p * d.noise_stride;
   // (RNG: `cnoise` is only the CAPS switch, as a table's presence is without it -- never read)
-  const float *cnoise = RNG ? (rg.caps ? d.ring : nullptr) : (d.caps_noise ? d.caps_noise + (size_t)p * d.caps_stride : nullptr);
+  const float *cnoise = RNG ? (TD3_MY_RNG(caps) ? TD3_MY(ring) : nullptr) : (d.caps_noise ? d.caps_noise + (size_t)p * d.caps_stride : nullptr);
   float *td_loss = d.td_loss + (size_t)p * d.loss_stride, *pg_loss = d.pg_loss + (size_t)p * d.loss_stride;
   // workspace of this learner: gradients | inputs s, s2, (s, a), (s2, a2) | the actor's tape | the critic's tape
   float *wk = (float *)d.work + (size_t)p * a.work_floats;
@@ -472,16 +539,16 @@ __global__ void __launch_bounds__(NT) td3_kernel(std::conditional_t<RNG, Td3Args
   int n_actor = 0;
   const float invB = 1.0f / (float)B, invBA = 1.0f / (float)(B * A);
 
-  for (int u = 0; u < d.n_updates; ++u) {
-    const int iteration = d.iteration0 + u + 1;
+  for (int u = 0; u < TD3_MY(n_updates); ++u) {
+    const int iteration = TD3_MY(iteration0) + u + 1;
     // ---- the minibatch: rows slots[u][0 .. B) of the ring; samples from B on are zeros
     const bool on = b < B;
     if constexpr (RNG) {
-      if (c.wave == 0) td3_draw_slots(rg.seed, key, iteration, rg.n_rows, B, c.lane, slot_l);
+      if (c.wave == 0) td3_draw_slots(TD3_MY_RNG(seed), key, iteration, TD3_MY_RNG(n_rows), B, c.lane, slot_l);
       __syncthreads();
     }
     int slot = on ? (RNG ? slot_l[b] : slots[(size_t)u * d.slot_cols + b]) : 0;
-    slot = min(max(slot, 0), d.capacity - 1);
+    slot = min(max(slot, 0), TD3_MY(capacity) - 1);
     const float *row = ring + (size_t)slot * RW;
     if constexpr (!RNG) __syncthreads();
     if (c.g == 0) {
@@ -497,17 +564,17 @@ __global__ void __launch_bounds__(NT) td3_kernel(std::conditional_t<RNG, Td3Args
       const float *out = mlp_fwd<MFMA>(c, actor, wat, in_s2, nullptr);
       float tz[4] = {0.0f, 0.0f, 0.0f, 0.0f};
       if constexpr (RNG) {
-        if (c.g == 0 && on) td3_draw_target(rg.seed, key, iteration, b, tz);
+        if (c.g == 0 && on) td3_draw_target(TD3_MY_RNG(seed), key, iteration, b, tz);
       }
       if (c.g == 0)
         for (int k = 0; k < A; ++k) {
-          float nz = on ? (RNG ? tz[k] : tnoise[((size_t)u * B + b) * A + k]) * d.noise_sd : 0.0f;
-          nz = fminf(fmaxf(nz, -d.noise_clip), d.noise_clip);
+          float nz = on ? (RNG ? tz[k] : tnoise[((size_t)u * B + b) * A + k]) * TD3_MY(noise_sd) : 0.0f;
+          nz = fminf(fmaxf(nz, -TD3_MY(noise_clip)), TD3_MY(noise_clip));
           in_sa2[(S + k) * BP + b] = fminf(fmaxf(nz + out[k * LP + b], -1.0f), 1.0f);
         }
       const float q1 = mlp_fwd<MFMA>(c, critic, wct, in_sa2, nullptr)[b];
       const float q2 = mlp_fwd<MFMA>(c, critic, wct + Pc1, in_sa2, nullptr)[b];
-      if (c.g == 0) tq[b] = rew + d.gamma * (fminf(q1, q2) * (1.0f - done));
+      if (c.g == 0) tq[b] = rew + TD3_MY(gamma) * (fminf(q1, q2) * (1.0f - done));
     }
     // ---- critic loss and gradients of both twins (td3.py:149-158)
     float td = 0.0f;
@@ -519,9 +586,9 @@ __global__ void __launch_bounds__(NT) td3_kernel(std::conditional_t<RNG, Td3Args
       mlp_bwd<MFMA>(c, critic, wc + k * Pc1, in_sa, tape_c, out, g + k * Pc1, false, false);
     }
     ++step_c;
-    clip_adam(c, wc, mc, vc, g, Pc, step_c, d.lr, d.max_grad_norm);
+    clip_adam(c, wc, mc, vc, g, Pc, step_c, TD3_MY(lr), d.max_grad_norm);
     if (c.t == 0) td_loss[u] = td;
-    if (iteration % d.policy_update_freq != 0) continue;
+    if (iteration % TD3_MY(policy_update_freq) != 0) continue;
     // ---- actor update (td3.py:177-198) with the critic just stepped
     float pg;
     {
@@ -541,8 +608,8 @@ __global__ void __launch_bounds__(NT) td3_kernel(std::conditional_t<RNG, Td3Args
       if (cnoise && on && c.g == 0)
         for (int k = 0; k < A; ++k) {
           const float df = abat[k] - acur[k];
-          loss += d.lambda_t * df * df * invBA;
-          da[k] -= d.lambda_t * 2.0f * df * invBA;
+          loss += TD3_MY(lambda_t) * df * df * invBA;
+          da[k] -= TD3_MY(lambda_t) * 2.0f * df * invBA;
         }
       if (c.g == 0)
         for (int k = 0; k < A; ++k) dx[k * LP + b] = da[k] * (1.0f - acur[k] * acur[k]);
@@ -553,12 +620,12 @@ __global__ void __launch_bounds__(NT) td3_kernel(std::conditional_t<RNG, Td3Args
           if (c.g == 0) {
             uint32_t cw[4] = {0u, 0u, 0u, 0u};
             for (int j = 0; j < S; ++j)
-              in_s2[j * BP + b] = on ? in_s[j * BP + b] + td3_draw_caps(rg.seed, key, iteration, b, j, cw) * d.eps_sd : 0.0f;
+              in_s2[j * BP + b] = on ? in_s[j * BP + b] + td3_draw_caps(TD3_MY_RNG(seed), key, iteration, b, j, cw) * TD3_MY(eps_sd) : 0.0f;
           }
         } else {
         if (c.g == 0)
           for (int j = 0; j < S; ++j)
-            in_s2[j * BP + b] = on ? in_s[j * BP + b] + cnoise[((size_t)n_actor * B + b) * S + j] * d.eps_sd : 0.0f;
+            in_s2[j * BP + b] = on ? in_s[j * BP + b] + cnoise[((size_t)n_actor * B + b) * S + j] * TD3_MY(eps_sd) : 0.0f;
         }
         float *ob = mlp_fwd<MFMA>(c, actor, wa, in_s2, tape_a);
         float abar[4];
@@ -567,25 +634,27 @@ __global__ void __launch_bounds__(NT) td3_kernel(std::conditional_t<RNG, Td3Args
         if (c.g == 0)
           for (int k = 0; k < A; ++k) {
             const float df = on ? abat[k] - abar[k] : 0.0f;
-            loss += d.lambda_s * df * df * invBA;
-            ob[k * LP + b] = -d.lambda_s * 2.0f * df * invBA * (1.0f - abar[k] * abar[k]);
+            loss += TD3_MY(lambda_s) * df * df * invBA;
+            ob[k * LP + b] = -TD3_MY(lambda_s) * 2.0f * df * invBA * (1.0f - abar[k] * abar[k]);
           }
         mlp_bwd<MFMA>(c, actor, wa, in_s2, tape_a, ob, g, true, false);
       }
       pg = block_sum(c, loss);
     }
     ++step_a; ++n_actor;
-    clip_adam(c, wa, ma, va, g, Pa, step_a, d.lr, d.max_grad_norm);
+    clip_adam(c, wa, ma, va, g, Pa, step_a, TD3_MY(lr), d.max_grad_norm);
     if (c.t == 0) pg_loss[u] = pg;
     // ---- soft updates (mod_utils.py:25-28): target = target * (1 - tau) + param * tau
-    const float tau = d.tau;
+    const float tau = TD3_MY(tau);
     for (int e = c.t; e < Pc; e += NT) wct[e] = wct[e] * (1.0f - tau) + wc[e] * tau;
-    if (d.update_actor_target)
+    if (TD3_MY(update_actor_target))
       for (int e = c.t; e < Pa; e += NT) wat[e] = wat[e] * (1.0f - tau) + wa[e] * tau;
     __syncthreads();
   }
-  if (c.t == 0 && d.n_updates > 0) { d.adam_steps[2 * p] = step_c; d.adam_steps[2 * p + 1] = step_a; }
+  if (c.t == 0 && TD3_MY(n_updates) > 0) { d.adam_steps[2 * p] = step_c; d.adam_steps[2 * p + 1] = step_a; }
 }
+#undef TD3_MY
+#undef TD3_MY_RNG
 
 // what serl_td3_train_rng draws, written out as the tables serl_td3_train takes: one workgroup per update, the slots by its first
 // wavefront (td3_draw_slots), thread b the draws of sample b (td3_draw_target / td3_draw_caps)
@@ -624,33 +693,54 @@ bool td3_shape_ok(int S, int A, int H, int L, int B)
 
 // every entry: the checks in one order, then the launch of the flavour asked for; `fn` names the entry in serl_last_error().  With
 // `gen` (serl_td3_train_rng) the tables of the descriptor -- slots, slot_cols, target_noise, caps_noise and their strides -- are not
-// looked at, the generator's descriptor is checked last, and rg->dense picks the dense phases.
-int td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream, bool mfma, const char *fn, bool gen = false, const serl_td3_rng_desc *rg = nullptr)
+// looked at, the generator's descriptor is checked last, and rg->dense picks the dense phases.  With `group` (serl_td3_train_group; gen
+// too) what a learner's row holds -- ring, ring_stride, capacity, iteration0, policy_update_freq, update_actor_target and the eight
+// hyper-parameters -- is not looked at either: the row's workgroup checks it (td3_check_row); the group descriptor takes the generator's
+// place, and the launch is made for n_updates == 0 too, since the status array is the report.
+int td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream, bool mfma, const char *fn, bool gen = false, const serl_td3_rng_desc *rg = nullptr,
+              bool group = false, const serl_td3_group_desc *gd = nullptr)
 {
   const std::string who(fn);
   if (!c || !d) return serl_fail(SERL_E_INVALID, who + ": NULL context or descriptor");
   if (!d->actor || !d->actor_target || !d->actor_m || !d->actor_v || !d->critic || !d->critic_target || !d->critic_m || !d->critic_v ||
-      !d->adam_steps || !d->ring || (!gen && (!d->slots || !d->target_noise)) || !d->td_loss || !d->pg_loss || !d->work)
+      !d->adam_steps || (!group && !d->ring) || (!gen && (!d->slots || !d->target_noise)) || !d->td_loss || !d->pg_loss || !d->work)
     return serl_fail(SERL_E_INVALID, who + ": NULL array (only caps_noise may be NULL: CAPS off)");
   if (d->state_dim < 1 || d->action_dim < 1 || d->hidden < 1 || d->num_layers < 0 || d->batch < 1 || d->activation < 0 || d->activation > 2)
     return serl_fail(SERL_E_INVALID, who + ": network shape / minibatch / activation");
-  if (d->n_learners < 1 || d->n_updates < 0 || d->capacity < 1 || (!gen && d->slot_cols < d->batch) || d->policy_update_freq < 1 || d->iteration0 < 0)
+  if (d->n_learners < 1 || d->n_updates < 0 || (!group && d->capacity < 1) || (!gen && d->slot_cols < d->batch) ||
+      (!group && (d->policy_update_freq < 1 || d->iteration0 < 0)))
     return serl_fail(SERL_E_INVALID, who + ": n_learners >= 1, n_updates >= 0, capacity >= 1, slot_cols >= batch, policy_update_freq >= 1, iteration0 >= 0");
-  if ((long long)d->iteration0 + d->n_updates > 2147483646LL) return serl_fail(SERL_E_INVALID, who + ": iteration0 + n_updates overflows");
-  if (!(d->lr > 0.0f) || !(d->gamma >= 0.0f) || !(d->tau >= 0.0f && d->tau <= 1.0f) || !(d->noise_sd >= 0.0f) || !(d->noise_clip >= 0.0f) ||
-      !(d->max_grad_norm > 0.0f) || !(d->eps_sd >= 0.0f) || d->lambda_s != d->lambda_s || d->lambda_t != d->lambda_t)
+  if (!group && (long long)d->iteration0 + d->n_updates > 2147483646LL) return serl_fail(SERL_E_INVALID, who + ": iteration0 + n_updates overflows");
+  if (!(d->max_grad_norm > 0.0f) ||
+      (!group && (!(d->lr > 0.0f) || !(d->gamma >= 0.0f) || !(d->tau >= 0.0f && d->tau <= 1.0f) || !(d->noise_sd >= 0.0f) || !(d->noise_clip >= 0.0f) ||
+                  !(d->eps_sd >= 0.0f) || d->lambda_s != d->lambda_s || d->lambda_t != d->lambda_t)))
     return serl_fail(SERL_E_INVALID, who + ": lr > 0, gamma >= 0, 0 <= tau <= 1, noise_sd >= 0, noise_clip >= 0, max_grad_norm > 0, eps_sd >= 0");
   if (!td3_shape_ok(d->state_dim, d->action_dim, d->hidden, d->num_layers, d->batch))
     return serl_fail(SERL_E_UNSUPPORTED, who + ": compiled for hidden a multiple of 4 in 4 .. 128, 0 .. 4 hidden layers, state_dim 1 .. 16, "
                                          "action_dim 1 .. 4, minibatches of 1 .. 128 rows; other shapes train in PyTorch");
   const int Pa = serl_param_count(d->state_dim, d->hidden, d->num_layers, d->action_dim), Pc = serl_td3_param_count(d->state_dim, d->action_dim);
   if (d->actor_stride < Pa || d->critic_stride < Pc) return serl_fail(SERL_E_INVALID, who + ": a row stride is smaller than its parameter count");
-  if (d->ring_stride < 0 || (!gen && (d->slots_stride < 0 || d->noise_stride < 0 || d->caps_stride < 0)) || d->loss_stride < d->n_updates)
+  if ((!group && d->ring_stride < 0) || (!gen && (d->slots_stride < 0 || d->noise_stride < 0 || d->caps_stride < 0)) || d->loss_stride < d->n_updates)
     return serl_fail(SERL_E_INVALID, who + ": negative learner stride, or loss_stride < n_updates");
   if (d->work_bytes < serl_td3_work_bytes(d->n_learners, d->state_dim, d->action_dim, d->hidden, d->num_layers, d->batch))
     return serl_fail(SERL_E_INVALID, who + ": workspace smaller than serl_td3_work_bytes");
   const size_t lds = td3_lds_bytes(gen);
   if (lds > (size_t)c->lds_per_block) return serl_fail(SERL_E_UNSUPPORTED, who + ": the activation tiles do not fit this device's LDS per workgroup");
+  if (group) {
+    if (!gd || !gd->rows || !gd->status) return serl_fail(SERL_E_INVALID, who + ": NULL group descriptor, rows or status");
+    if (gd->dense != 0 && gd->dense != 1) return serl_fail(SERL_E_INVALID, who + ": dense must be 0 (valu) or 1 (mfma)");
+    if (gd->caps != 0 && gd->caps != 1) return serl_fail(SERL_E_INVALID, who + ": caps must be 0 or 1");
+    HIP_TRY(hipSetDevice(c->device));
+    Td3ArgsGroup ag;
+    ag.d = *d;
+    ag.work_floats = td3_work_floats(d->state_dim, d->action_dim, d->hidden, d->num_layers);
+    ag.rows = gd->rows; ag.status = gd->status; ag.caps = gd->caps;
+    auto kernel = gd->dense == 1 ? td3_kernel<true, true, true> : td3_kernel<false, true, true>;
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kernel, dim3(d->n_learners), dim3(NT), lds, (hipStream_t)stream, ag);
+    HIP_TRY(hipGetLastError());
+    return SERL_OK;
+  }
   if (gen) {
     if (!rg) return serl_fail(SERL_E_INVALID, who + ": NULL generator descriptor");
     if (rg->n_rows < d->batch || rg->n_rows > d->capacity) return serl_fail(SERL_E_INVALID, who + ": batch <= n_rows <= capacity");
@@ -735,6 +825,29 @@ int serl_td3_rng_layout(int32_t *out, int32_t capacity)
 int serl_td3_train_rng(serl_ctx *c, const serl_td3_desc *d, const serl_td3_rng_desc *rg, void *stream)
 {
   return td3_train(c, d, stream, false, "serl_td3_train_rng", true, rg);
+}
+
+int serl_td3_group_layout(int32_t *out, int32_t capacity)
+{
+#define TD3_OFF(m) (int32_t)offsetof(serl_td3_learner_row, m)
+#define TD3_GOFF(m) (int32_t)offsetof(serl_td3_group_desc, m)
+  const int32_t v[] = {
+    (int32_t)sizeof(serl_td3_learner_row),
+    TD3_OFF(ring), TD3_OFF(seed), TD3_OFF(capacity), TD3_OFF(n_rows), TD3_OFF(n_updates), TD3_OFF(iteration0), TD3_OFF(key),
+    TD3_OFF(policy_update_freq), TD3_OFF(update_actor_target), TD3_OFF(pad0), TD3_OFF(lr), TD3_OFF(gamma), TD3_OFF(tau), TD3_OFF(noise_sd),
+    TD3_OFF(noise_clip), TD3_OFF(lambda_s), TD3_OFF(lambda_t), TD3_OFF(eps_sd),
+    (int32_t)sizeof(serl_td3_group_desc), TD3_GOFF(rows), TD3_GOFF(status), TD3_GOFF(dense), TD3_GOFF(caps)};
+#undef TD3_OFF
+#undef TD3_GOFF
+  const int n = (int)(sizeof(v) / sizeof(v[0]));
+  for (int i = 0; i < n && i < capacity; ++i)
+    if (out) out[i] = v[i];
+  return n;
+}
+
+int serl_td3_train_group(serl_ctx *c, const serl_td3_desc *d, const serl_td3_group_desc *gd, void *stream)
+{
+  return td3_train(c, d, stream, false, "serl_td3_train_group", true, nullptr, true, gd);
 }
 
 int serl_td3_rng_fill(serl_ctx *c, const serl_td3_rng_desc *rg, int32_t learner, int32_t state_dim, int32_t action_dim, int32_t batch,

@@ -10,6 +10,10 @@ is not compiled for, `train` loops `update_parameters` over the same draws.
 `train(draws='device', seed=...)` takes no draw on the host at all: serl_td3_train_rng draws the slots and both kinds of noise inside the
 kernel from the counter-based generator of csrc/serl_rng.h, as a function of (seed, learner, iteration), and `td3_draws` writes the same
 draws out as tables (serl_td3_rng_fill) for a replay on the table path.
+
+`TD3Group(learners).train(replays, n_updates, iteration0=..., seed=...)` runs the updates of several independent learners of one network
+shape -- seeds, hyper-parameter settings -- as ONE launch (serl_td3_train_group), each learner where its own train(draws='device') would
+put it.
 """
 import ctypes
 import random
@@ -366,3 +370,159 @@ class TD3:
             _unpack_adam(self.actor_optim, ap, rows['actor_m'], rows['actor_v'], astep)
         td, pg = td.cpu().numpy(), pg.cpu().numpy()
         return list(td), [x for x in pg if not np.isnan(x)]
+
+
+# what the learners of a TD3Group must share: one launch has one network shape, one minibatch size and CAPS on or off for all
+GROUP_SHARED = ('state_dim', 'action_dim', 'hidden_size', 'num_layers', 'activation_actor', 'batch_size')
+
+
+class TD3Group:
+    """K independent `TD3` learners of one network shape -- several seeds, a few hyper-parameter settings -- whose generations' updates run
+    as ONE launch (serl_td3_train_group, include/serl_amd.h): one workgroup per learner, each with its own ring, fill, update count,
+    iteration, seed, key and hyper-parameters.  Every learner ends bit for bit where its own
+    `TD3.train(replay, n, iteration0=..., draws='device', seed=..., learner=key, dense=...)` would have put it."""
+
+    def __init__(self, learners):
+        learners = list(learners)
+        if not learners:
+            raise ValueError('TD3Group: no learners')
+        for i, t in enumerate(learners):
+            if not isinstance(t, TD3):
+                raise ValueError('TD3Group: learner %d is %r, not a serl_amd.TD3' % (i, type(t).__name__))
+        first = learners[0]
+        for i, t in enumerate(learners[1:], 1):
+            for f in GROUP_SHARED:
+                x, y = getattr(first.args, f), getattr(t.args, f)
+                if f == 'activation_actor':
+                    x, y = str(x).lower(), str(y).lower()
+                if x != y:
+                    raise ValueError('TD3Group: learner %d differs from learner 0 in %s (%r, %r)' % (i, f, y, x))
+            if (first.caps_dict is None) != (t.caps_dict is None):
+                raise ValueError('TD3Group: learner %d differs from learner 0 in use_caps (CAPS is on for all learners of a launch or for none)' % i)
+            x, y = (None if e is None else torch.device(e.device) for e in (first.engine, t.engine))
+            if x != y:
+                raise ValueError('TD3Group: learner %d differs from learner 0 in device (the engines are on %s and %s)' % (i, y, x))
+        self.learners = learners
+
+    def __len__(self):
+        return len(self.learners)
+
+    def _each(self, v, what):
+        """a scalar for all learners, or one value per learner"""
+        K = len(self.learners)
+        if isinstance(v, (str, bytes)) or not hasattr(v, '__len__'):
+            return [v] * K
+        if len(v) != K:
+            raise ValueError('TD3Group.train: %d values of %s for %d learners' % (len(v), what, K))
+        return list(v)
+
+    def train(self, replays, n_updates, *, iteration0, seed, key=None, champion_target=False, dense='valu'):
+        """Learner i runs n_updates[i] updates on minibatches of the first len(replays[i]) rows of its ring from iteration0[i] on, with the
+        in-kernel draws of (seed[i], key[i]) -- `key` defaults to the learner's index -- and its own args / caps_dict.  n_updates,
+        iteration0, seed, key and champion_target are scalars (for all) or sequences of one value per learner.
+        -> a list of {'PG_obj', 'TD_loss'} like TD3.train's (NaN for a learner with no updates).  Everything is checked on the host
+        before any device work (ValueError); it is the kernel or a RuntimeError, never the eager loop; one launch, one synchronisation."""
+        from . import _capi
+        who, K = 'TD3Group.train', len(self.learners)
+        if dense not in DENSE:
+            raise ValueError('%s: dense=%r (one of %s)' % (who, dense, ', '.join(repr(k) for k in DENSE)))
+        replays = list(replays)
+        if len(replays) != K:
+            raise ValueError('%s: %d rings for %d learners' % (who, len(replays), K))
+        is_int = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer))
+        ns, its = self._each(n_updates, 'n_updates'), self._each(iteration0, 'iteration0')
+        seeds, champs = self._each(seed, 'seed'), self._each(champion_target, 'champion_target')
+        keys = list(range(K)) if key is None else self._each(key, 'key')
+        a0 = self.learners[0].args
+        S, A, B = a0.state_dim, a0.action_dim, int(a0.batch_size)
+        for i, (t, r) in enumerate(zip(self.learners, replays)):
+            if not is_int(ns[i]) or ns[i] < 0:
+                raise ValueError('%s: learner %d: n_updates=%r (an integer >= 0)' % (who, i, ns[i]))
+            if not is_int(its[i]) or its[i] < 0 or int(its[i]) + int(ns[i]) > 2**31 - 2:
+                raise ValueError('%s: learner %d: iteration0=%r (an integer >= 0, iteration0 + n_updates below 2^31 - 1)' % (who, i, its[i]))
+            seeds[i] = _seed64(seeds[i], '%s: learner %d' % (who, i))
+            if not is_int(keys[i]) or not 0 <= int(keys[i]) < 2**31 - 1:
+                raise ValueError('%s: learner %d: key=%r (an integer in [0, 2^31 - 1))' % (who, i, keys[i]))
+            if (r.state_dim, r.action_dim) != (S, A):
+                raise ValueError('%s: learner %d: the ring holds rows of state_dim %d, action_dim %d, the learners take %d, %d'
+                                 % (who, i, r.state_dim, r.action_dim, S, A))
+            if len(r) < B:
+                raise ValueError('%s: learner %d: %d rows in the ring, minibatches of %d' % (who, i, len(r), B))
+        ns, its, keys = [int(x) for x in ns], [int(x) for x in its], [int(x) for x in keys]
+        seen = {}
+        for i in range(K):
+            if seen.setdefault((seeds[i], keys[i]), i) != i:
+                raise ValueError('%s: learners %d and %d share (seed, key) = (%d, %d): they would draw the same minibatches and noise'
+                                 % (who, seen[(seeds[i], keys[i])], i, seeds[i], keys[i]))
+        dev = torch.device(replays[0].device)
+        if any(torch.device(r.device) != dev for r in replays) or not all(t.fused_supported(dev) for t in self.learners):
+            raise RuntimeError('%s: serl_td3_train_group does not run this shape / device (there is no eager fall-back)' % who)
+        nmax = max(ns)
+        nan = {'PG_obj': float('nan'), 'TD_loss': float('nan')}
+        if nmax == 0:
+            return [dict(nan) for _ in range(K)]
+        L = _capi.lib()
+        engine = self.learners[0].engine
+        packed = {k: [] for k in ('actor', 'actor_target', 'actor_m', 'actor_v', 'critic', 'critic_target', 'critic_m', 'critic_v')}
+        steps, params = [], []
+        for t in self.learners:
+            ap, cp = list(t.actor.parameters()), list(t.critic.parameters())
+            am, av, astep = _pack_adam(t.actor_optim, ap)
+            cm, cv, cstep = _pack_adam(t.critic_optim, cp)
+            for k, v in dict(actor=pack_actor(t.actor), actor_target=pack_actor(t.actor_target), actor_m=am, actor_v=av, critic=pack_critic(t.critic),
+                             critic_target=pack_critic(t.critic_target), critic_m=cm, critic_v=cv).items():
+                packed[k].append(v.detach().to(torch.float32).cpu())
+            steps.append([cstep, astep])
+            params.append((ap, cp))
+        rows = {k: torch.stack(v).contiguous().to(dev) for k, v in packed.items()}
+        steps = torch.tensor(steps, dtype=torch.int32, device=dev)
+        table = (_capi.Td3LearnerRow * K)()
+        for i, (t, r) in enumerate(zip(self.learners, replays)):
+            a, c = t.args, t.caps_dict or {'lambda_s': 0.0, 'lambda_t': 0.0, 'eps_sd': 0.0}
+            table[i] = _capi.Td3LearnerRow(ring=r.rows.data_ptr(), seed=seeds[i], capacity=r.capacity, n_rows=len(r), n_updates=ns[i], iteration0=its[i],
+                                           key=keys[i], policy_update_freq=int(a.policy_update_freq), update_actor_target=int(not champs[i]),
+                                           lr=a.lr, gamma=a.gamma, tau=a.tau, noise_sd=a.noise_sd, noise_clip=a.noise_clip, lambda_s=c['lambda_s'],
+                                           lambda_t=c['lambda_t'], eps_sd=c['eps_sd'])
+        table_d = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+        status = torch.full((K,), -1, dtype=torch.int32, device=dev)
+        td = torch.zeros(K, nmax, dtype=torch.float32, device=dev)
+        pg = torch.full((K, nmax), float('nan'), dtype=torch.float32, device=dev)
+        wb = int(L.serl_td3_work_bytes(K, S, A, a0.hidden_size, a0.num_layers, B))
+        work = torch.empty(wb // 4, dtype=torch.float32, device=dev)
+        d = _capi.Td3Desc(state_dim=S, action_dim=A, hidden=a0.hidden_size, num_layers=a0.num_layers,
+                          activation=ACTIVATION_IDS[a0.activation_actor.lower()], n_learners=K, batch=B, n_updates=nmax, max_grad_norm=MAX_GRAD_NORM,
+                          actor=rows['actor'].data_ptr(), actor_target=rows['actor_target'].data_ptr(), actor_m=rows['actor_m'].data_ptr(),
+                          actor_v=rows['actor_v'].data_ptr(), actor_stride=rows['actor'].stride(0),
+                          critic=rows['critic'].data_ptr(), critic_target=rows['critic_target'].data_ptr(),
+                          critic_m=rows['critic_m'].data_ptr(), critic_v=rows['critic_v'].data_ptr(), critic_stride=rows['critic'].stride(0),
+                          adam_steps=steps.data_ptr(), td_loss=td.data_ptr(), pg_loss=pg.data_ptr(), loss_stride=nmax, work=work.data_ptr(),
+                          work_bytes=wb)
+        gd = _capi.Td3GroupDesc(rows=table_d.data_ptr(), status=status.data_ptr(), dense=int(dense == 'mfma'),
+                                caps=int(self.learners[0].caps_dict is not None))
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _capi.check(L.serl_td3_train_group(engine.ctx, ctypes.byref(d), ctypes.byref(gd), stream), 'serl_td3_train_group')
+        torch.cuda.synchronize(dev)
+        bad = [(i, int(s)) for i, s in enumerate(status.cpu().tolist()) if s != 0]
+        if bad:
+            raise RuntimeError('%s: serl_td3_train_group refused %s; no learner was changed' % (who, ', '.join(
+                'learner %d (%s)' % (i, _capi.TD3_ROW_STATUS.get(s, 'status %d' % s)) for i, s in bad)))
+        steps, td, pg = steps.cpu().tolist(), td.cpu().numpy(), pg.cpu().numpy()
+        out = []
+        for i, t in enumerate(self.learners):
+            t.last_path = DENSE[dense][1] + '-group-rng'
+            if ns[i] == 0:                      # (as TD3.train: nothing of the learner is touched)
+                out.append(dict(nan))
+                continue
+            ap, cp = params[i]
+            unpack_into(t.actor, rows['actor'][i])
+            unpack_into(t.actor_target, rows['actor_target'][i])
+            unpack_critic(t.critic, rows['critic'][i])
+            unpack_critic(t.critic_target, rows['critic_target'][i])
+            cstep, astep = steps[i]
+            _unpack_adam(t.critic_optim, cp, rows['critic_m'][i], rows['critic_v'][i], cstep)
+            if astep:
+                _unpack_adam(t.actor_optim, ap, rows['actor_m'][i], rows['actor_v'][i], astep)
+            t.last_table_bytes = 0
+            pgs = [x for x in pg[i, :ns[i]] if not np.isnan(x)]
+            out.append({'PG_obj': float(np.mean([-x for x in pgs])) if pgs else float('nan'), 'TD_loss': float(np.median(td[i, :ns[i]]))})
+        return out

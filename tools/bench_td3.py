@@ -21,6 +21,16 @@ tables so that all four compute the same rows (checked); (b) wall time of TD3.tr
 bytes of tables each mode put on the device.  Hidden 72 unless --hidden says otherwise.  Results go to profiles/td3_rng_timing.json.
 
   python tools/bench_td3.py --draws host,device  # 2 000 updates per launch; TD3.train at 2 000 and 20 000 updates
+
+With --group K learners of the benchmark shape (hidden 72 unless --hidden says otherwise), each with its own rows, ring, seed and key, run
+their --updates updates as ONE serl_td3_train_group launch, against K back-to-back single-learner serl_td3_train_rng launches on the same
+buffers -- what the library offered before the group entry.  Both dense flavours, the two versions alternating in one process, device
+events, median [min .. max] of --reps repetitions after a warm-up; the rows of the two versions are checked to be equal.  The
+back-to-back version costs K launches per repetition: --serial-max bounds the K up to which it is run (beyond it only the group launch
+is timed, and the result says so).  --kernel-regs takes the output of tools/kernel_regs.sh for the record.  Results go to
+profiles/td3_group_timing.json, rewritten after every K.
+
+  python tools/bench_td3.py --group 1,2,4,8,16,32,64,128,256
 """
 import argparse, ctypes, json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -112,16 +122,21 @@ def main():
     ap.add_argument('--dense', default=None, help="'valu,mfma': time the flavours of the fused kernel against each other (no eager loop)")
     ap.add_argument('--draws', default=None, help="'host,device': time the table path against the in-kernel generator (kernels and TD3.train)")
     ap.add_argument('--train-updates', type=int, nargs='*', default=[2000, 20000], help='with --draws: updates of one TD3.train call')
+    ap.add_argument('--group', default=None, help="'1,2,4,...': K learners in one serl_td3_train_group launch against K serl_td3_train_rng launches")
+    ap.add_argument('--serial-max', type=int, default=None, help='with --group: the largest K whose K back-to-back launches are run (default: all)')
+    ap.add_argument('--kernel-regs', default=None, help='with --group: a file holding the output of tools/kernel_regs.sh <serl_td3 object> td3_kernel')
     ap.add_argument('--out', default=None, help='default: profiles/td3_fused_timing.json, with --dense profiles/td3_mfma_timing.json, '
                                                 'with --draws profiles/td3_rng_timing.json')
     a = ap.parse_args()
     if a.hidden is None:
-        a.hidden = [72] if a.draws else [72, 32, 96]
+        a.hidden = [72] if a.draws or a.group else [72, 32, 96]
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'td3_rng_timing.json' if a.draws else 'td3_mfma_timing.json' if a.dense else 'td3_fused_timing.json')
+        a.out = os.path.join(ROOT, 'profiles', 'td3_group_timing.json' if a.group else 'td3_rng_timing.json' if a.draws else 'td3_mfma_timing.json' if a.dense else 'td3_fused_timing.json')
     import serl_amd
     import td3_64 as T
     engine = serl_amd.RolloutEngine(0)
+    if a.group:
+        return group_main(a, engine)
     if a.draws:
         return draws_main(a, engine)
     if a.dense:
@@ -245,6 +260,106 @@ def draws_main(a, engine):
         res['shapes']['H%d_L%d_B%d' % (H, a.layers, a.batch)] = r
     with open(a.out, 'w') as fh:
         json.dump(res, fh, indent=1)
+    print(json.dumps(res))
+
+
+def group_main(a, engine):
+    import td3_64 as T
+    from serl_amd import _capi
+    from serl_amd import build as hip_build
+    L = _capi.lib()
+    dev = engine.device
+    Ks = [int(k) for k in a.group.split(',')]
+    assert Ks and min(Ks) >= 1, a.group
+    seed, n, B, Ly = 20261020, a.updates, a.batch, a.layers
+    regs = [ln.strip() for ln in open(a.kernel_regs)] if a.kernel_regs else None
+    res = {'tool': 'bench_td3 --group ' + a.group, 'device': torch.cuda.get_device_name(0), 'source_hash': hip_build.source_hash(), 'batch': B,
+           'layers': Ly, 'updates_per_learner': n, 'reps': a.reps, 'caps': True, 'policy_update_freq': 2, 'activation': 'tanh', 'seed': seed,
+           'serial_max': a.serial_max, 'kernel_resources': regs,
+           'what': 'ms of ONE launch of K learners (group) and of K back-to-back single-learner launches (serial), device events; per_update = '
+                   'ms / updates_per_learner: the time one more update of EVERY learner costs', 'shapes': {}}
+    stream = lambda: ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    for H in a.hidden:
+        d = T.make_case((7, 3, H, Ly, 'tanh', B, 2, 0, 4, 1, 1, 'small'), seed=H)
+        cap = d['ring'].shape[0]
+        shape = res['shapes'].setdefault('H%d_L%d_B%d' % (H, Ly, B), {})
+        for K in Ks:
+            t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+            init = {k: t(np.tile(d[k], (K, 1))) for k in T.ROWS}
+            rings = t(np.tile(d['ring'], (K, 1, 1)))
+            wb = int(L.serl_td3_work_bytes(K, 7, 3, H, Ly, B))
+            work = torch.empty(wb // 4, dtype=torch.float32, device=dev)
+            table = (_capi.Td3LearnerRow * K)()
+            for i in range(K):
+                table[i] = _capi.Td3LearnerRow(ring=rings[i].data_ptr(), seed=seed, capacity=cap, n_rows=cap, n_updates=n, iteration0=0, key=i,
+                                               policy_update_freq=2, update_actor_target=1, lr=T.LR, gamma=T.GAMMA, tau=T.TAU, noise_sd=T.NOISE_SD,
+                                               noise_clip=T.NOISE_CLIP, **T.CAPS)
+            table_d = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+
+            def run(version, dense, n_, rows_out=None):
+                rows = {k: v.clone() for k, v in init.items()}
+                for k in T.MOMENTS:
+                    rows[k] = torch.zeros_like(rows[k.split('_')[0]])
+                steps = torch.zeros(K, 2, dtype=torch.int32, device=dev)
+                td, pg = torch.zeros(K, n_, device=dev), torch.zeros(K, n_, device=dev)
+                status = torch.full((K,), -1, dtype=torch.int32, device=dev)
+
+                def desc(first, k):
+                    return _capi.Td3Desc(
+                        state_dim=7, action_dim=3, hidden=H, num_layers=Ly, activation=0, n_learners=k, batch=B, n_updates=n_, capacity=cap,
+                        policy_update_freq=2, iteration0=0, update_actor_target=1, lr=T.LR, gamma=T.GAMMA, tau=T.TAU, noise_sd=T.NOISE_SD,
+                        noise_clip=T.NOISE_CLIP, lambda_s=T.CAPS['lambda_s'], lambda_t=T.CAPS['lambda_t'], eps_sd=T.CAPS['eps_sd'], max_grad_norm=T.MAX_NORM,
+                        actor=rows['actor'][first].data_ptr(), actor_target=rows['actor_target'][first].data_ptr(),
+                        actor_m=rows['actor_m'][first].data_ptr(), actor_v=rows['actor_v'][first].data_ptr(), actor_stride=rows['actor'].stride(0),
+                        critic=rows['critic'][first].data_ptr(), critic_target=rows['critic_target'][first].data_ptr(),
+                        critic_m=rows['critic_m'][first].data_ptr(), critic_v=rows['critic_v'][first].data_ptr(),
+                        critic_stride=rows['critic'].stride(0), adam_steps=steps[first].data_ptr(), ring=rings[first].data_ptr(),
+                        td_loss=td[first].data_ptr(), pg_loss=pg[first].data_ptr(), loss_stride=n_, work=work.data_ptr(), work_bytes=wb)
+                if n_ != n:                                              # (the warm-up: fewer updates in every row)
+                    short = (_capi.Td3LearnerRow * K).from_buffer_copy(bytes(table))
+                    for i in range(K):
+                        short[i].n_updates = n_
+                    tb = torch.frombuffer(bytearray(bytes(short)), dtype=torch.uint8).to(dev)
+                else:
+                    tb = table_d
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                if version == 'group':
+                    gd = _capi.Td3GroupDesc(rows=tb.data_ptr(), status=status.data_ptr(), dense=int(dense == 'mfma'), caps=1)
+                    _capi.check(L.serl_td3_train_group(engine.ctx, ctypes.byref(desc(0, K)), ctypes.byref(gd), stream()), 'serl_td3_train_group')
+                else:
+                    for i in range(K):
+                        rd = _capi.Td3RngDesc(seed=seed, n_rows=cap, learner0=i, dense=int(dense == 'mfma'), caps=1)
+                        _capi.check(L.serl_td3_train_rng(engine.ctx, ctypes.byref(desc(i, 1)), ctypes.byref(rd), stream()), 'serl_td3_train_rng')
+                e1.record()
+                torch.cuda.synchronize()
+                assert torch.isfinite(td).all() and (version != 'group' or int(status.abs().max()) == 0)
+                if rows_out is not None:
+                    rows_out.update({k: rows[k].cpu().numpy() for k in T.ROWS}, td=td.cpu().numpy())
+                return e0.elapsed_time(e1)
+
+            serial = a.serial_max is None or K <= a.serial_max
+            runs = [(v, f) for v in (('group', 'serial') if serial else ('group',)) for f in ('valu', 'mfma')]
+            for v, f in runs:
+                run(v, f, min(n, 50))                                    # warm-up
+            ms, rows = {k: [] for k in runs}, {k: {} for k in runs}
+            for _ in range(a.reps):                                      # alternating: a drift of the clock hits all alike
+                for k in runs:
+                    ms[k].append(run(k[0], k[1], n, rows[k]))
+            r = {'%s_%s_ms' % k: spread(ms[k]) for k in runs}
+            r.update({'%s_%s_ms_per_update' % k: spread([x / n for x in ms[k]]) for k in runs})
+            r['serial_measured'] = serial
+            r['rows_equal'] = bool(all(np.array_equal(rows[k][x], rows[runs[0]][x]) for k in runs for x in rows[k]))
+            for f in ('valu', 'mfma'):
+                r['%s_learner_updates_per_s' % f] = K * n / (r['group_%s_ms' % f]['median'] * 1e-3)
+                if serial:
+                    r['%s_serial_over_group_median' % f] = r['serial_%s_ms' % f]['median'] / r['group_%s_ms' % f]['median']
+            shape['K%d' % K] = r
+            print('H %d K %3d  %s  rows equal: %s' % (H, K, '  '.join('%s/%s %.1f [%.1f .. %.1f] ms' % (k[0], k[1], statistics.median(ms[k]), min(ms[k]),
+                  max(ms[k])) for k in runs), r['rows_equal']), flush=True)
+            with open(a.out, 'w') as fh:
+                json.dump(res, fh, indent=1)
     print(json.dumps(res))
 
 
