@@ -851,6 +851,47 @@ int serl_td3_group_layout(int32_t *out, int32_t capacity);
  * not ignored; then SERL_E_INVALID for a NULL group, NULL rows or status, dense or caps other than 0 / 1; all with nothing launched. */
 int serl_td3_train_group(serl_ctx *ctx, const serl_td3_desc *desc, const serl_td3_group_desc *group, void *stream);
 
+/* ---- the TD3 learner on minibatches of up to 512 rows (SERL_ABI_VERSION stays 9: new symbols only, nothing above has moved; the struct
+ * has a layout self-check of its own, serl_td3_big_layout) ---------------------------------------------------------------------------
+ * The entries above are compiled for batch 1 .. 128 and keep refusing 129 (SERL_E_UNSUPPORTED; serl_td3_work_bytes 0).
+ * serl_td3_train_big takes the same serl_td3_desc with batch 1 .. 512: further instantiations of the one kernel source that walk the
+ * minibatch in chunks of 128 samples, chunk c = samples 128 c .. min(batch, 128 c + 128) - 1 (columns 128 c .. of a slots row, rows
+ * 128 c .. of a noise block, index b of the generator), at most four, the last one possibly partial.  One workgroup per learner,
+ * __syncthreads only, no workgroup waits on another.
+ * Summation contract.  Everything per sample (gather, forward and backward passes, LayerNorm, the target, the CAPS terms, the draws) is
+ * computed per chunk exactly as the entries above compute it for a minibatch of that chunk's size.  Every sum over the samples of the
+ * minibatch -- a weight, bias, LayerNorm gain or bias gradient, td_loss, pg_loss -- is
+ *     ((P0 + P1) + P2) + P3        (as many terms as there are chunks; f32, one rounding per +)
+ * where Pc is the partial sum over chunk c's samples in the order the entries above use for a minibatch of that size (a sample at or
+ * past `batch` reaches no sum), with every term already scaled by the means' divisors 1 / batch and 1 / (batch * A) -- the minibatch's,
+ * not the chunk's.  td_loss sums the partials chunk by chunk, within a chunk critic 1's then critic 2's:
+ *     td = 0 + P0(Q1) + P0(Q2) + P1(Q1) + P1(Q2) + ..      with Pc(Qk) = (sum over chunk c of (Qk - target_q)^2) * (1 / batch)
+ * The norm clip, Adam and the soft updates run once per update over the whole minibatch's gradients.  Consequences: with batch <= 128
+ * every array written equals, bit for bit, what serl_td3_train / _mfma / _rng writes; dense 1 equals dense 0 bit for bit at every
+ * batch; in-kernel draws equal the tables of serl_td3_rng_fill_big bit for bit; against float64 the agreement is to rounding.
+ *   rng      NULL = slots and noise from desc's tables (slot_cols >= batch).  Else the generator of serl_td3_train_rng with the same
+ *            checks; desc's table fields are ignored; rng->dense must equal `dense`.  The slot draw is serl_host_td3_slots' for any batch.
+ *   dense    0 = valu, 1 = mfma
+ *   work     serl_td3_big_work_bytes(n_learners, S, A, hidden, num_layers, batch): the gradients once, inputs and tapes per chunk --
+ *            serl_td3_work_bytes' value up to batch 128, about four times that at 512; 0 = shape not compiled (batch outside 1 .. 512,
+ *            or a network shape serl_td3_work_bytes refuses). */
+typedef struct serl_td3_big_desc {
+  const serl_td3_rng_desc *rng;     /* HOST; NULL = tables */
+  int32_t dense;                    /* 0 = valu, 1 = mfma */
+  int32_t pad0;
+} serl_td3_big_desc;
+/* layout self-check: sizeof(serl_td3_big_desc), then offsetof of each member in declaration order */
+int serl_td3_big_layout(int32_t *out, int32_t capacity);
+int64_t serl_td3_big_work_bytes(int32_t n_learners, int32_t state_dim, int32_t action_dim, int32_t hidden, int32_t num_layers, int32_t batch);
+/* Asynchronous on `stream`, one launch.  SERL_E_INVALID for a NULL big or dense other than 0 / 1; then the checks of serl_td3_train
+ * (rng == NULL) or serl_td3_train_rng in their order with their codes, with batch up to 512 (513: SERL_E_UNSUPPORTED) and the workspace
+ * of serl_td3_big_work_bytes; all before any device work.  n_updates == 0 leaves every buffer unchanged. */
+int serl_td3_train_big(serl_ctx *ctx, const serl_td3_desc *desc, const serl_td3_big_desc *big, void *stream);
+/* serl_td3_rng_fill for batch 1 .. 512: the tables with which serl_td3_train_big (rng == NULL) reproduces a call with rng != NULL */
+int serl_td3_rng_fill_big(serl_ctx *ctx, const serl_td3_rng_desc *rng, int32_t learner, int32_t state_dim, int32_t action_dim, int32_t batch,
+                          int32_t iteration0, int32_t n_updates, int32_t policy_update_freq, int32_t *slots, float *target_noise,
+                          float *caps_noise, void *stream);
+
 /* ---- the launch planner on the host (SERL_ABI_VERSION stays 9: new symbols only) --------------------------------------------------
  * WHAT serl_rollout / serl_rollout_noise (noise != 0) would launch for `desc` on a device of caps[0] CUs: the library's own decision
  * (csrc/serl_plan.h), without a context or a device.  caps[7] = {CUs, SERL_KERNEL as enum serl_kernel_hint (0 = unset),

@@ -23,7 +23,8 @@ EXPORTS = ['serl_abi_version', 'serl_last_error', 'serl_param_count', 'serl_ctx_
            'serl_rollout_noise', 'serl_rollout_noise_layout',
            'serl_td3_train_rng', 'serl_td3_rng_layout', 'serl_td3_rng_fill', 'serl_host_td3_slots',
            'serl_host_plan_rollout', 'serl_host_plan_dyn', 'serl_host_plan_multi',
-           'serl_td3_train_group', 'serl_td3_group_layout']
+           'serl_td3_train_group', 'serl_td3_group_layout',
+           'serl_td3_train_big', 'serl_td3_big_layout', 'serl_td3_big_work_bytes', 'serl_td3_rng_fill_big']
 
 
 class BuildDesc(ctypes.Structure):
@@ -166,6 +167,16 @@ def expected_td3_group_layout():
     return sum(([ctypes.sizeof(T)] + [getattr(T, n).offset for n, _ in T._fields_] for T in (Td3LearnerRow, Td3GroupDesc)), [])
 
 
+class Td3BigDesc(ctypes.Structure):
+    """serl_td3_big_desc: the dense flavour and the optional generator of a serl_td3_train_big call (checked by serl_td3_big_layout)"""
+    _fields_ = [('rng', ctypes.POINTER(Td3RngDesc)), ('dense', ctypes.c_int32), ('pad0', ctypes.c_int32)]
+
+
+def expected_td3_big_layout():
+    """What serl_td3_big_layout() must return for Td3BigDesc to be right."""
+    return [ctypes.sizeof(Td3BigDesc)] + [getattr(Td3BigDesc, n).offset for n, _ in Td3BigDesc._fields_]
+
+
 # enum serl_td3_row_status: what a workgroup of serl_td3_train_group writes to status[p]
 TD3_ROW_STATUS = {0: 'ok', 1: 'ring is NULL', 2: 'n_updates < 0 or above the launch\'s', 3: 'iteration0 < 0 or iteration0 + n_updates overflows',
                   4: 'n_rows < batch or n_rows > capacity', 5: 'policy_update_freq < 1', 6: 'a hyper-parameter out of range or NaN'}
@@ -267,6 +278,10 @@ def lib():
     L.serl_host_td3_slots.argtypes = [ctypes.c_uint64, i32, i32, i32, i32, VP]
     L.serl_td3_group_layout.argtypes = [VP, ctypes.c_int32]
     L.serl_td3_train_group.argtypes = [VP, ctypes.POINTER(Td3Desc), ctypes.POINTER(Td3GroupDesc), VP]
+    L.serl_td3_big_layout.argtypes = [VP, ctypes.c_int32]
+    L.serl_td3_big_work_bytes.argtypes = [i32] * 6
+    L.serl_td3_train_big.argtypes = [VP, ctypes.POINTER(Td3Desc), ctypes.POINTER(Td3BigDesc), VP]
+    L.serl_td3_rng_fill_big.argtypes = L.serl_td3_rng_fill.argtypes
     L.serl_host_plan_rollout.argtypes = [_I, ctypes.POINTER(RolloutDesc), i32, _I]
     L.serl_host_plan_dyn.argtypes = [_I, i32, i32, i32, _I]
     L.serl_host_plan_multi.argtypes = [i32, i32, _I, i32, _I, _I, _I]
@@ -276,7 +291,7 @@ def lib():
         elif f == 'serl_host_philox':
             L.serl_host_philox.restype = None
         elif f not in ('serl_last_error',):
-            getattr(L, f).restype = ctypes.c_longlong if f in ('serl_host_sample_slots', 'serl_venv_state_bytes', 'serl_td3_work_bytes') else ctypes.c_int
+            getattr(L, f).restype = ctypes.c_longlong if f in ('serl_host_sample_slots', 'serl_venv_state_bytes', 'serl_td3_work_bytes', 'serl_td3_big_work_bytes') else ctypes.c_int
     if L.serl_abi_version() != ABI_VERSION:
         raise RuntimeError('serl_amd: ABI version mismatch (library %d, binding %d): rebuild with `python serl_amd/build.py`'
                            % (L.serl_abi_version(), ABI_VERSION))
@@ -304,6 +319,12 @@ def lib():
     if n != len(want) or list(got) != want:
         raise RuntimeError('serl_amd: layout of the Td3LearnerRow / Td3GroupDesc mirrors differs from the library (serl_td3_group_layout): '
                            'library %s, binding %s' % (list(got)[:n], want))
+    want = expected_td3_big_layout()
+    got = (ctypes.c_int32 * len(want))()
+    n = L.serl_td3_big_layout(got, len(want))
+    if n != len(want) or list(got) != want:
+        raise RuntimeError('serl_amd: layout of the Td3BigDesc mirror differs from the library (serl_td3_big_layout): library %s, binding %s'
+                           % (list(got)[:n], want))
     want = expected_venv_auto_layout()
     got = (ctypes.c_int32 * len(want))()
     n = L.serl_venv_auto_layout(got, len(want))

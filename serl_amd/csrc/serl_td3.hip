@@ -25,7 +25,8 @@ namespace {
 
 constexpr int NT = 512;                 // threads per workgroup
 constexpr int NW = NT / 64;             // wavefronts
-constexpr int BP = 128;                 // samples per row of a global activation array = the largest minibatch
+constexpr int BP = 128;                 // samples per row of a global activation array = the largest minibatch but for the chunked flavours
+constexpr int BIG_B = 512;              // the largest minibatch of the chunked flavours (serl_td3_train_big): four chunks of BP samples
 constexpr int NG = NT / BP;             // output groups
 constexpr int LP = 132;                 // floats per row of an LDS tile (128 samples + 4: consecutive rows start 4 banks apart)
 constexpr int TILE_ROWS = 128;          // the widest layer
@@ -467,6 +468,33 @@ __device__ __forceinline__ void td3_draw_slots(uint64_t seed, int key, int itera
   if (lane + 64 < B) out[lane + 64] = c_hi;
 }
 
+// td3_draw_slots with NR registers per lane instead of two: at most 64 NR steps (the chunked flavours: BIG_B / 64 = 8).  Lane l computes
+// the candidates of steps l, l + 64, .. up front, column i is held in lane i & 63, register i >> 6; the same draw, step for step.
+template <int NR>
+__device__ __forceinline__ void td3_draw_slots_n(uint64_t seed, int key, int iteration, int n_rows, int B, int lane, int *out)
+{
+  const int j0 = n_rows - B;
+  int cand[NR], col[NR];                // col: columns lane + 64 r once chosen (-1: not yet; rows are >= 0)
+#pragma unroll
+  for (int r = 0; r < NR; ++r) {
+    cand[r] = lane + 64 * r < B ? serl_td3_slot_candidate(seed, key, iteration, lane + 64 * r, j0 + lane + 64 * r) : 0;
+    col[r] = -1;
+  }
+#pragma unroll
+  for (int r = 0; r < NR; ++r)
+    for (int i = 64 * r; i < min(B, 64 * r + 64); ++i) {
+      const int t = __shfl(cand[r], i & 63);
+      bool held = false;
+#pragma unroll
+      for (int q = 0; q <= r; ++q) held |= col[q] == t;
+      const bool taken = __ballot(held) != 0ull;
+      if (lane == (i & 63)) col[r] = taken ? j0 + i : t;
+    }
+#pragma unroll
+  for (int r = 0; r < NR; ++r)
+    if (lane + 64 * r < B) out[lane + 64 * r] = col[r];
+}
+
 // the target-policy noise of sample b: standard normals, the first A of four
 __device__ __forceinline__ void td3_draw_target(uint64_t seed, int key, int iteration, int b, float (&z)[4])
 {
@@ -656,6 +684,185 @@ __global__ void __launch_bounds__(NT) td3_kernel(Td3KernelArgs<RNG, GROUP> a)
 #undef TD3_MY
 #undef TD3_MY_RNG
 
+// The chunked flavours (serl_td3_train_big): td3_kernel's updates on minibatches of up to BIG_B rows, walked in chunks of BP samples
+// (the last one may be partial).  Everything per sample -- the gather, the forward and backward passes, the draws -- runs per chunk with
+// the thread map, the tiles and the device functions above, c.B / c.B4 / c.live being the chunk's; every chunk has its own inputs and
+// tapes in the workspace; a batch sum (a gradient, a loss) is chunk 0's partial sum, then + chunk 1's, + chunk 2's, + chunk 3's
+// (include/serl_amd.h states the order); the means divide by the minibatch's B; the clip, Adam and the soft updates run once, after the
+// last chunk.  With one chunk every operation is td3_kernel's in td3_kernel's order.  A kernel of its own rather than a fourth template
+// parameter of td3_kernel: routing both through one body changed the registers and the code of the six existing instantiations.
+template <bool MFMA, bool RNG>
+__global__ void __launch_bounds__(NT) td3_kernel_big(Td3KernelArgs<RNG, false> a)
+{
+  extern __shared__ float lds[];
+  const serl_td3_desc &d = a.d;
+  const int p = blockIdx.x;
+  Ctx c;
+  c.T0 = lds; c.T1 = c.T0 + TILE_ROWS * LP; c.red4 = c.T1 + TILE_ROWS * LP; c.red = c.red4 + NG * BP;
+  float *tq = c.red + 64;               // [BP] target Q
+  int *slot_l = reinterpret_cast<int *>(tq + BP);      // [BIG_B] the minibatch's slots (RNG only: td3_lds_bytes)
+  Td3Rng rg = {};
+  if constexpr (RNG) rg = a.rg;
+  const int key = rg.learner0 + p;
+  c.t = threadIdx.x; c.b = c.t & (BP - 1); c.g = __builtin_amdgcn_readfirstlane(c.t >> 7);
+  c.wave = __builtin_amdgcn_readfirstlane(c.t >> 6); c.lane = c.t & 63;
+  c.B = d.batch; c.B4 = (d.batch + 3) & ~3; c.act = d.activation;
+  c.live = (c.b & 64) < c.B;
+  const int S = d.state_dim, A = d.action_dim, SA = S + A, RW = 2 * S + A + 3, B = d.batch, b = c.b;
+  const Net actor = {0, S, d.hidden, d.num_layers, A}, critic = {1, S, d.hidden, d.num_layers, A};
+  const int Pa = d.hidden * S + d.hidden + d.num_layers * (d.hidden * d.hidden + 3 * d.hidden) + A * d.hidden + A;
+  const int Pc1 = HC * SA + 3 * HC + HC * HC + 3 * HC + HC + 1, Pc = 2 * Pc1;
+  float *wa = d.actor + (size_t)p * d.actor_stride, *wat = d.actor_target + (size_t)p * d.actor_stride;
+  float *ma = d.actor_m + (size_t)p * d.actor_stride, *va = d.actor_v + (size_t)p * d.actor_stride;
+  float *wc = d.critic + (size_t)p * d.critic_stride, *wct = d.critic_target + (size_t)p * d.critic_stride;
+  float *mc = d.critic_m + (size_t)p * d.critic_stride, *vc = d.critic_v + (size_t)p * d.critic_stride;
+  const float *ring = d.ring + (size_t)p * d.ring_stride;
+  const int32_t *slots = RNG ? nullptr : d.slots + (size_t)p * d.slots_stride;
+  const float *tnoise = RNG ? nullptr : d.target_noise + (size_t)p * d.noise_stride;
+  // (RNG: `cnoise` is only the CAPS switch, as a table's presence is without it -- never read)
+  const float *cnoise = RNG ? (rg.caps ? d.ring : nullptr) : (d.caps_noise ? d.caps_noise + (size_t)p * d.caps_stride : nullptr);
+  float *td_loss = d.td_loss + (size_t)p * d.loss_stride, *pg_loss = d.pg_loss + (size_t)p * d.loss_stride;
+  // workspace of this learner: gradients | per chunk: inputs s, s2, (s, a), (s2, a2) | the actor's tape | the critic's tape
+  float *wk = (float *)d.work + (size_t)p * a.work_floats;
+  float *g = wk;
+  float *in_s = g + ((max(Pa, Pc) + 3) & ~3), *in_s2 = in_s + MAX_IN * BP, *in_sa = in_s2 + MAX_IN * BP, *in_sa2 = in_sa + MAX_IN * BP;
+  float *tape_a = in_sa2 + MAX_IN * BP, *tape_c = tape_a + tape_floats(d.num_layers + 2, d.hidden);
+  int step_c = d.adam_steps[2 * p], step_a = d.adam_steps[2 * p + 1];
+  int n_actor = 0;
+  const float invB = 1.0f / (float)B, invBA = 1.0f / (float)(B * A);
+  const int n_chunks = (B + BP - 1) / BP;
+  int b0 = 0;                           // the first sample of the chunk at hand; sample b of the chunk is sample b0 + b of the minibatch
+  // the chunk's share of the minibatch into c and its region of the workspace into the six pointers above
+  auto enter_chunk = [&](int ch) {
+    const int64_t chunk_floats = 4 * MAX_IN * BP + tape_floats(d.num_layers + 2, d.hidden) + tape_floats(3, HC);
+    b0 = ch * BP;
+    c.B = min(BP, B - b0); c.B4 = (c.B + 3) & ~3; c.live = (c.b & 64) < c.B;
+    in_s = g + ((max(Pa, Pc) + 3) & ~3) + ch * chunk_floats; in_s2 = in_s + MAX_IN * BP; in_sa = in_s2 + MAX_IN * BP; in_sa2 = in_sa + MAX_IN * BP;
+    tape_a = in_sa2 + MAX_IN * BP; tape_c = tape_a + tape_floats(d.num_layers + 2, d.hidden);
+  };
+
+  for (int u = 0; u < d.n_updates; ++u) {
+    const int iteration = d.iteration0 + u + 1;
+    if constexpr (RNG) {
+      if (c.wave == 0) td3_draw_slots_n<BIG_B / 64>(rg.seed, key, iteration, rg.n_rows, B, c.lane, slot_l);
+      __syncthreads();
+    }
+    float td = 0.0f;
+    for (int ch = 0; ch < n_chunks; ++ch) {
+      enter_chunk(ch);
+      // ---- the minibatch: rows slots[u][0 .. B) of the ring; samples from B on are zeros
+      const bool on = b0 + b < B;
+      int slot = on ? (RNG ? slot_l[b0 + b] : slots[(size_t)u * d.slot_cols + b0 + b]) : 0;
+      slot = min(max(slot, 0), d.capacity - 1);
+      const float *row = ring + (size_t)slot * RW;
+      if constexpr (!RNG) __syncthreads();
+      if (c.g == 0) {
+        for (int j = 0; j < S; ++j) {
+          const float s = on ? row[j] : 0.0f, s2 = on ? row[SA + j] : 0.0f;
+          in_s[j * BP + b] = s; in_sa[j * BP + b] = s; in_s2[j * BP + b] = s2; in_sa2[j * BP + b] = s2;
+        }
+        for (int k = 0; k < A; ++k) in_sa[(S + k) * BP + b] = on ? row[S + k] : 0.0f;
+      }
+      const float rew = on ? row[2 * S + A] : 0.0f, done = on ? row[2 * S + A + 1] : 0.0f;
+      // ---- target action and target Q (td3.py:137-146)
+      {
+        const float *out = mlp_fwd<MFMA>(c, actor, wat, in_s2, nullptr);
+        float tz[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if constexpr (RNG) {
+          if (c.g == 0 && on) td3_draw_target(rg.seed, key, iteration, b0 + b, tz);
+        }
+        if (c.g == 0)
+          for (int k = 0; k < A; ++k) {
+            float nz = on ? (RNG ? tz[k] : tnoise[((size_t)u * B + b0 + b) * A + k]) * d.noise_sd : 0.0f;
+            nz = fminf(fmaxf(nz, -d.noise_clip), d.noise_clip);
+            in_sa2[(S + k) * BP + b] = fminf(fmaxf(nz + out[k * LP + b], -1.0f), 1.0f);
+          }
+        const float q1 = mlp_fwd<MFMA>(c, critic, wct, in_sa2, nullptr)[b];
+        const float q2 = mlp_fwd<MFMA>(c, critic, wct + Pc1, in_sa2, nullptr)[b];
+        if (c.g == 0) tq[b] = rew + d.gamma * (fminf(q1, q2) * (1.0f - done));
+      }
+      // ---- critic loss and gradients of both twins (td3.py:149-158); from the second chunk on they are added to
+      for (int k = 0; k < 2; ++k) {
+        float *out = mlp_fwd<MFMA>(c, critic, wc + k * Pc1, in_sa, tape_c);
+        const float e = (on && c.g == 0) ? out[b] - tq[b] : 0.0f;
+        td += block_sum(c, e * e) * invB;
+        if (c.g == 0) out[b] = 2.0f * e * invB;
+        mlp_bwd<MFMA>(c, critic, wc + k * Pc1, in_sa, tape_c, out, g + k * Pc1, ch > 0, false);
+      }
+    }
+    ++step_c;
+    clip_adam(c, wc, mc, vc, g, Pc, step_c, d.lr, d.max_grad_norm);
+    if (c.t == 0) td_loss[u] = td;
+    if (iteration % d.policy_update_freq != 0) continue;
+    // ---- actor update (td3.py:177-198) with the critic just stepped
+    float pg = 0.0f;
+    for (int ch = 0; ch < n_chunks; ++ch) {
+      enter_chunk(ch);
+      const bool on = b0 + b < B;
+      float *out = mlp_fwd<MFMA>(c, actor, wa, in_s, tape_a);
+      float acur[4] = {0.0f, 0.0f, 0.0f, 0.0f}, abat[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      for (int k = 0; k < A; ++k) { acur[k] = out[k * LP + b]; abat[k] = in_sa[(S + k) * BP + b]; }
+      __syncthreads();
+      if (c.g == 0)
+        for (int j = 0; j < SA; ++j) in_sa2[j * BP + b] = j < S ? in_s[j * BP + b] : acur[j - S];
+      float *q = mlp_fwd<MFMA>(c, critic, wc, in_sa2, tape_c);
+      float loss = (on && c.g == 0) ? -q[b] * invB : 0.0f;
+      if (c.g == 0) q[b] = on ? -invB : 0.0f;
+      float *dx = mlp_bwd<MFMA>(c, critic, wc, in_sa2, tape_c, q, nullptr, false, true);
+      float da[4];
+      for (int k = 0; k < A; ++k) da[k] = dx[(S + k) * LP + b];
+      __syncthreads();
+      if (cnoise && on && c.g == 0)
+        for (int k = 0; k < A; ++k) {
+          const float df = abat[k] - acur[k];
+          loss += d.lambda_t * df * df * invBA;
+          da[k] -= d.lambda_t * 2.0f * df * invBA;
+        }
+      if (c.g == 0)
+        for (int k = 0; k < A; ++k) dx[k * LP + b] = da[k] * (1.0f - acur[k] * acur[k]);
+      mlp_bwd<MFMA>(c, actor, wa, in_s, tape_a, dx, g, ch > 0, false);
+      if (cnoise) {
+        // state_bar = state + rand * eps_sd; lambda_s * mse(action_batch, actor(state_bar))
+        if constexpr (RNG) {
+          if (c.g == 0) {
+            uint32_t cw[4] = {0u, 0u, 0u, 0u};
+            for (int j = 0; j < S; ++j)
+              in_s2[j * BP + b] = on ? in_s[j * BP + b] + td3_draw_caps(rg.seed, key, iteration, b0 + b, j, cw) * d.eps_sd : 0.0f;
+          }
+        } else {
+          if (c.g == 0)
+            for (int j = 0; j < S; ++j)
+              in_s2[j * BP + b] = on ? in_s[j * BP + b] + cnoise[((size_t)n_actor * B + b0 + b) * S + j] * d.eps_sd : 0.0f;
+        }
+        float *ob = mlp_fwd<MFMA>(c, actor, wa, in_s2, tape_a);
+        float abar[4];
+        for (int k = 0; k < A; ++k) abar[k] = ob[k * LP + b];
+        __syncthreads();
+        if (c.g == 0)
+          for (int k = 0; k < A; ++k) {
+            const float df = on ? abat[k] - abar[k] : 0.0f;
+            loss += d.lambda_s * df * df * invBA;
+            ob[k * LP + b] = -d.lambda_s * 2.0f * df * invBA * (1.0f - abar[k] * abar[k]);
+          }
+        mlp_bwd<MFMA>(c, actor, wa, in_s2, tape_a, ob, g, true, false);
+      }
+      const float chunk_pg = block_sum(c, loss);
+      pg = ch == 0 ? chunk_pg : pg + chunk_pg;
+    }
+    ++step_a; ++n_actor;
+    clip_adam(c, wa, ma, va, g, Pa, step_a, d.lr, d.max_grad_norm);
+    if (c.t == 0) pg_loss[u] = pg;
+    // ---- soft updates (mod_utils.py:25-28): target = target * (1 - tau) + param * tau
+    const float tau = d.tau;
+    for (int e = c.t; e < Pc; e += NT) wct[e] = wct[e] * (1.0f - tau) + wc[e] * tau;
+    if (d.update_actor_target)
+      for (int e = c.t; e < Pa; e += NT) wat[e] = wat[e] * (1.0f - tau) + wa[e] * tau;
+    __syncthreads();
+  }
+  if (c.t == 0 && d.n_updates > 0) { d.adam_steps[2 * p] = step_c; d.adam_steps[2 * p + 1] = step_a; }
+}
+
+
 // what serl_td3_train_rng draws, written out as the tables serl_td3_train takes: one workgroup per update, the slots by its first
 // wavefront (td3_draw_slots), thread b the draws of sample b (td3_draw_target / td3_draw_caps)
 __global__ void __launch_bounds__(BP) td3_rng_fill_kernel(Td3Rng rg, int key, int S, int A, int B, int iteration0, int freq, int32_t *slots, float *tn,
@@ -676,19 +883,42 @@ __global__ void __launch_bounds__(BP) td3_rng_fill_kernel(Td3Rng rg, int key, in
   for (int j = 0; j < S; ++j) cn[((size_t)n_actor * B + b) * S + j] = td3_draw_caps(rg.seed, key, iteration, b, j, cw);
 }
 
-size_t td3_lds_bytes(bool rng) { return ((size_t)2 * TILE_ROWS * LP + NG * BP + 64 + BP + (rng ? BP : 0)) * sizeof(float); }
+// td3_rng_fill_kernel for the chunked flavours: BIG_B threads, td3_draw_slots_n
+__global__ void __launch_bounds__(BIG_B) td3_rng_fill_big_kernel(Td3Rng rg, int key, int S, int A, int B, int iteration0, int freq, int32_t *slots,
+                                                                 float *tn, float *cn)
+{
+  __shared__ int slot_l[BIG_B];
+  const int u = blockIdx.x, b = threadIdx.x, iteration = iteration0 + u + 1;
+  if (b < 64) td3_draw_slots_n<BIG_B / 64>(rg.seed, key, iteration, rg.n_rows, B, b, slot_l);
+  __syncthreads();
+  if (b >= B) return;
+  slots[(size_t)u * B + b] = slot_l[b];
+  float tz[4];
+  td3_draw_target(rg.seed, key, iteration, b, tz);
+  for (int k = 0; k < A; ++k) tn[((size_t)u * B + b) * A + k] = tz[k];
+  if (!cn || iteration % freq != 0) return;
+  const int n_actor = iteration / freq - iteration0 / freq - 1;
+  uint32_t cw[4] = {0u, 0u, 0u, 0u};
+  for (int j = 0; j < S; ++j) cn[((size_t)n_actor * B + b) * S + j] = td3_draw_caps(rg.seed, key, iteration, b, j, cw);
+}
 
-int64_t td3_work_floats(int S, int A, int H, int L)
+size_t td3_lds_bytes(bool rng, bool big = false)
+{
+  return ((size_t)2 * TILE_ROWS * LP + NG * BP + 64 + BP + (rng ? (big ? BIG_B : BP) : 0)) * sizeof(float);
+}
+
+// per learner; `chunks` chunks of BP samples (1 but for the chunked flavours): the gradients once, inputs and tapes per chunk
+int64_t td3_work_floats(int S, int A, int H, int L, int chunks = 1)
 {
   const int64_t Pa = (int64_t)H * S + H + (int64_t)L * (H * H + 3 * H) + A * H + A;
   const int64_t Pc = 2 * ((int64_t)HC * (S + A) + 3 * HC + HC * HC + 3 * HC + HC + 1);
   const int64_t gmax = ((Pa > Pc ? Pa : Pc) + 3) & ~(int64_t)3;
-  return gmax + 4 * MAX_IN * BP + tape_floats(L + 2, H) + tape_floats(3, HC);
+  return gmax + chunks * (4 * MAX_IN * BP + tape_floats(L + 2, H) + tape_floats(3, HC));
 }
 
-bool td3_shape_ok(int S, int A, int H, int L, int B)
+bool td3_shape_ok(int S, int A, int H, int L, int B, int max_batch = BP)
 {
-  return H >= 4 && H <= TILE_ROWS && H % 4 == 0 && L >= 0 && L <= 4 && S >= 1 && S <= 16 && A >= 1 && A <= 4 && B >= 1 && B <= BP;
+  return H >= 4 && H <= TILE_ROWS && H % 4 == 0 && L >= 0 && L <= 4 && S >= 1 && S <= 16 && A >= 1 && A <= 4 && B >= 1 && B <= max_batch;
 }
 
 // every entry: the checks in one order, then the launch of the flavour asked for; `fn` names the entry in serl_last_error().  With
@@ -696,9 +926,11 @@ bool td3_shape_ok(int S, int A, int H, int L, int B)
 // looked at, the generator's descriptor is checked last, and rg->dense picks the dense phases.  With `group` (serl_td3_train_group; gen
 // too) what a learner's row holds -- ring, ring_stride, capacity, iteration0, policy_update_freq, update_actor_target and the eight
 // hyper-parameters -- is not looked at either: the row's workgroup checks it (td3_check_row); the group descriptor takes the generator's
-// place, and the launch is made for n_updates == 0 too, since the status array is the report.
+// place, and the launch is made for n_updates == 0 too, since the status array is the report.  With `big` (serl_td3_train_big; not with
+// group) the minibatch may have up to BIG_B rows, the workspace is that of serl_td3_big_work_bytes, the chunked flavours are launched,
+// and with gen rg->dense must name the flavour `mfma` asks for.
 int td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream, bool mfma, const char *fn, bool gen = false, const serl_td3_rng_desc *rg = nullptr,
-              bool group = false, const serl_td3_group_desc *gd = nullptr)
+              bool group = false, const serl_td3_group_desc *gd = nullptr, bool big = false)
 {
   const std::string who(fn);
   if (!c || !d) return serl_fail(SERL_E_INVALID, who + ": NULL context or descriptor");
@@ -715,16 +947,18 @@ int td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream, bool mfma, cons
       (!group && (!(d->lr > 0.0f) || !(d->gamma >= 0.0f) || !(d->tau >= 0.0f && d->tau <= 1.0f) || !(d->noise_sd >= 0.0f) || !(d->noise_clip >= 0.0f) ||
                   !(d->eps_sd >= 0.0f) || d->lambda_s != d->lambda_s || d->lambda_t != d->lambda_t)))
     return serl_fail(SERL_E_INVALID, who + ": lr > 0, gamma >= 0, 0 <= tau <= 1, noise_sd >= 0, noise_clip >= 0, max_grad_norm > 0, eps_sd >= 0");
-  if (!td3_shape_ok(d->state_dim, d->action_dim, d->hidden, d->num_layers, d->batch))
+  if (!td3_shape_ok(d->state_dim, d->action_dim, d->hidden, d->num_layers, d->batch, big ? BIG_B : BP))
     return serl_fail(SERL_E_UNSUPPORTED, who + ": compiled for hidden a multiple of 4 in 4 .. 128, 0 .. 4 hidden layers, state_dim 1 .. 16, "
-                                         "action_dim 1 .. 4, minibatches of 1 .. 128 rows; other shapes train in PyTorch");
+                                         "action_dim 1 .. 4, minibatches of 1 .. " + (big ? "512" : "128") + " rows; other shapes train in PyTorch");
   const int Pa = serl_param_count(d->state_dim, d->hidden, d->num_layers, d->action_dim), Pc = serl_td3_param_count(d->state_dim, d->action_dim);
   if (d->actor_stride < Pa || d->critic_stride < Pc) return serl_fail(SERL_E_INVALID, who + ": a row stride is smaller than its parameter count");
   if ((!group && d->ring_stride < 0) || (!gen && (d->slots_stride < 0 || d->noise_stride < 0 || d->caps_stride < 0)) || d->loss_stride < d->n_updates)
     return serl_fail(SERL_E_INVALID, who + ": negative learner stride, or loss_stride < n_updates");
-  if (d->work_bytes < serl_td3_work_bytes(d->n_learners, d->state_dim, d->action_dim, d->hidden, d->num_layers, d->batch))
-    return serl_fail(SERL_E_INVALID, who + ": workspace smaller than serl_td3_work_bytes");
-  const size_t lds = td3_lds_bytes(gen);
+  const int chunks = big ? (d->batch + BP - 1) / BP : 1;
+  const int64_t work_floats = td3_work_floats(d->state_dim, d->action_dim, d->hidden, d->num_layers, chunks);
+  if (d->work_bytes < (int64_t)d->n_learners * work_floats * (int64_t)sizeof(float))
+    return serl_fail(SERL_E_INVALID, who + ": workspace smaller than " + (big ? "serl_td3_big_work_bytes" : "serl_td3_work_bytes"));
+  const size_t lds = td3_lds_bytes(gen, big);
   if (lds > (size_t)c->lds_per_block) return serl_fail(SERL_E_UNSUPPORTED, who + ": the activation tiles do not fit this device's LDS per workgroup");
   if (group) {
     if (!gd || !gd->rows || !gd->status) return serl_fail(SERL_E_INVALID, who + ": NULL group descriptor, rows or status");
@@ -733,7 +967,7 @@ int td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream, bool mfma, cons
     HIP_TRY(hipSetDevice(c->device));
     Td3ArgsGroup ag;
     ag.d = *d;
-    ag.work_floats = td3_work_floats(d->state_dim, d->action_dim, d->hidden, d->num_layers);
+    ag.work_floats = work_floats;
     ag.rows = gd->rows; ag.status = gd->status; ag.caps = gd->caps;
     auto kernel = gd->dense == 1 ? td3_kernel<true, true, true> : td3_kernel<false, true, true>;
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -747,26 +981,49 @@ int td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream, bool mfma, cons
     if ((long long)rg->learner0 + d->n_learners > 2147483647LL) return serl_fail(SERL_E_INVALID, who + ": learner0 + n_learners overflows");
     if (rg->dense != 0 && rg->dense != 1) return serl_fail(SERL_E_INVALID, who + ": dense must be 0 (valu) or 1 (mfma)");
     if (rg->caps != 0 && rg->caps != 1) return serl_fail(SERL_E_INVALID, who + ": caps must be 0 or 1");
+    if (big && (rg->dense == 1) != mfma) return serl_fail(SERL_E_INVALID, who + ": the generator's dense differs from the big descriptor's");
     mfma = rg->dense == 1;
   }
   if (d->n_updates == 0) return SERL_OK;
   HIP_TRY(hipSetDevice(c->device));
   Td3Args a;
   a.d = *d;
-  a.work_floats = td3_work_floats(d->state_dim, d->action_dim, d->hidden, d->num_layers);
+  a.work_floats = work_floats;
   if (gen) {
     Td3ArgsRng ar;
     ar.d = a.d; ar.work_floats = a.work_floats;
     ar.rg = {rg->seed, rg->n_rows, rg->learner0, rg->caps};
-    auto kernel = mfma ? td3_kernel<true, true> : td3_kernel<false, true>;
+    auto kernel = big ? (mfma ? td3_kernel_big<true, true> : td3_kernel_big<false, true>) : (mfma ? td3_kernel<true, true> : td3_kernel<false, true>);
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kernel, dim3(d->n_learners), dim3(NT), lds, (hipStream_t)stream, ar);
     HIP_TRY(hipGetLastError());
     return SERL_OK;
   }
-  auto kernel = mfma ? td3_kernel<true, false> : td3_kernel<false, false>;
+  auto kernel = big ? (mfma ? td3_kernel_big<true, false> : td3_kernel_big<false, false>) : (mfma ? td3_kernel<true, false> : td3_kernel<false, false>);
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kernel, dim3(d->n_learners), dim3(NT), lds, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return SERL_OK;
+}
+
+// serl_td3_rng_fill / _big: one set of checks, then the fill kernel of BP or BIG_B threads per update
+int td3_rng_fill(serl_ctx *c, const serl_td3_rng_desc *rg, int32_t learner, int32_t state_dim, int32_t action_dim, int32_t batch, int32_t iteration0,
+                 int32_t n_updates, int32_t policy_update_freq, int32_t *slots, float *target_noise, float *caps_noise, void *stream, bool big, const char *fn)
+{
+  const std::string who(fn);
+  if (!c || !rg || !slots || !target_noise) return serl_fail(SERL_E_INVALID, who + ": NULL argument (only caps_noise may be NULL: not written)");
+  if (state_dim < 1 || state_dim > 16 || action_dim < 1 || action_dim > 4 || batch < 1 || batch > (big ? BIG_B : BP))
+    return serl_fail(SERL_E_INVALID, who + ": state_dim 1 .. 16, action_dim 1 .. 4, batch 1 .. " + (big ? "512" : "128"));
+  if (learner < 0 || n_updates < 0 || policy_update_freq < 1 || iteration0 < 0 || (long long)iteration0 + n_updates > 2147483646LL ||
+      (long long)rg->learner0 + learner > 2147483647LL)
+    return serl_fail(SERL_E_INVALID, who + ": learner >= 0, n_updates >= 0, policy_update_freq >= 1, iteration0 >= 0, no overflow");
+  if (rg->n_rows < batch) return serl_fail(SERL_E_INVALID, who + ": n_rows < batch");
+  if (n_updates == 0) return SERL_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const Td3Rng r = {rg->seed, rg->n_rows, rg->learner0, rg->caps};
+  hipLaunchKernelGGL(big ? td3_rng_fill_big_kernel : td3_rng_fill_kernel, dim3(n_updates), dim3(big ? BIG_B : BP), 0, (hipStream_t)stream, r,
+                     (int)(rg->learner0 + learner), (int)state_dim, (int)action_dim, (int)batch, (int)iteration0, (int)policy_update_freq, slots,
+                     target_noise, caps_noise);
   HIP_TRY(hipGetLastError());
   return SERL_OK;
 }
@@ -854,21 +1111,40 @@ int serl_td3_rng_fill(serl_ctx *c, const serl_td3_rng_desc *rg, int32_t learner,
                       int32_t iteration0, int32_t n_updates, int32_t policy_update_freq, int32_t *slots, float *target_noise, float *caps_noise,
                       void *stream)
 {
-  const std::string who("serl_td3_rng_fill");
-  if (!c || !rg || !slots || !target_noise) return serl_fail(SERL_E_INVALID, who + ": NULL argument (only caps_noise may be NULL: not written)");
-  if (state_dim < 1 || state_dim > 16 || action_dim < 1 || action_dim > 4 || batch < 1 || batch > BP)
-    return serl_fail(SERL_E_INVALID, who + ": state_dim 1 .. 16, action_dim 1 .. 4, batch 1 .. 128");
-  if (learner < 0 || n_updates < 0 || policy_update_freq < 1 || iteration0 < 0 || (long long)iteration0 + n_updates > 2147483646LL ||
-      (long long)rg->learner0 + learner > 2147483647LL)
-    return serl_fail(SERL_E_INVALID, who + ": learner >= 0, n_updates >= 0, policy_update_freq >= 1, iteration0 >= 0, no overflow");
-  if (rg->n_rows < batch) return serl_fail(SERL_E_INVALID, who + ": n_rows < batch");
-  if (n_updates == 0) return SERL_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  const Td3Rng r = {rg->seed, rg->n_rows, rg->learner0, rg->caps};
-  hipLaunchKernelGGL(td3_rng_fill_kernel, dim3(n_updates), dim3(BP), 0, (hipStream_t)stream, r, (int)(rg->learner0 + learner), (int)state_dim,
-                     (int)action_dim, (int)batch, (int)iteration0, (int)policy_update_freq, slots, target_noise, caps_noise);
-  HIP_TRY(hipGetLastError());
-  return SERL_OK;
+  return td3_rng_fill(c, rg, learner, state_dim, action_dim, batch, iteration0, n_updates, policy_update_freq, slots, target_noise, caps_noise, stream,
+                      false, "serl_td3_rng_fill");
+}
+
+int serl_td3_rng_fill_big(serl_ctx *c, const serl_td3_rng_desc *rg, int32_t learner, int32_t state_dim, int32_t action_dim, int32_t batch,
+                          int32_t iteration0, int32_t n_updates, int32_t policy_update_freq, int32_t *slots, float *target_noise, float *caps_noise,
+                          void *stream)
+{
+  return td3_rng_fill(c, rg, learner, state_dim, action_dim, batch, iteration0, n_updates, policy_update_freq, slots, target_noise, caps_noise, stream,
+                      true, "serl_td3_rng_fill_big");
+}
+
+int64_t serl_td3_big_work_bytes(int32_t n_learners, int32_t state_dim, int32_t action_dim, int32_t hidden, int32_t num_layers, int32_t batch)
+{
+  if (n_learners < 1 || !td3_shape_ok(state_dim, action_dim, hidden, num_layers, batch, BIG_B)) return 0;
+  return (int64_t)n_learners * td3_work_floats(state_dim, action_dim, hidden, num_layers, (batch + BP - 1) / BP) * (int64_t)sizeof(float);
+}
+
+int serl_td3_big_layout(int32_t *out, int32_t capacity)
+{
+#define TD3_OFF(m) (int32_t)offsetof(serl_td3_big_desc, m)
+  const int32_t v[] = {(int32_t)sizeof(serl_td3_big_desc), TD3_OFF(rng), TD3_OFF(dense), TD3_OFF(pad0)};
+#undef TD3_OFF
+  const int n = (int)(sizeof(v) / sizeof(v[0]));
+  for (int i = 0; i < n && i < capacity; ++i)
+    if (out) out[i] = v[i];
+  return n;
+}
+
+int serl_td3_train_big(serl_ctx *c, const serl_td3_desc *d, const serl_td3_big_desc *bd, void *stream)
+{
+  if (!bd) return serl_fail(SERL_E_INVALID, "serl_td3_train_big: NULL big descriptor");
+  if (bd->dense != 0 && bd->dense != 1) return serl_fail(SERL_E_INVALID, "serl_td3_train_big: dense must be 0 (valu) or 1 (mfma)");
+  return td3_train(c, d, stream, bd->dense == 1, "serl_td3_train_big", bd->rng != nullptr, bd->rng, false, nullptr, true);
 }
 
 int serl_host_td3_slots(uint64_t seed, int32_t learner, int32_t iteration, int32_t n_rows, int32_t batch, int32_t *out)

@@ -37,6 +37,9 @@ DENSE = {'valu': ('serl_td3_train', 'fused'), 'mfma': ('serl_td3_train_mfma', 'f
 # train(draws=...): 'host' = slots from `rng`, noise from `generator`, uploaded as tables (the default; profiles/td3_rng_timing.json
 # holds the measurements a later change decides from); 'device' = serl_td3_train_rng, last_path 'fused-rng' / 'fused-mfma-rng'.
 DRAWS = ('host', 'device')
+# minibatches of more rows than serl_td3_train takes (up to 512) run on serl_td3_train_big when asked for by name -- fused=True,
+# dense='mfma' or draws='device'; last_path gains '-big' after the dense flavour.  fused=None keeps the eager loop for them.
+FUSED_MAX_BATCH = 128
 
 
 class _QNet(nn.Module):
@@ -137,7 +140,7 @@ def td3_draws(engine, *, seed, learner, iteration0, n_updates, batch, n_rows, st
     """What TD3.train(draws='device', seed=seed, learner=learner) draws in n_updates updates from iteration0 on, minibatches of `batch` of
     the first n_rows rows of a ring, written out by the kernels' own device functions (serl_td3_rng_fill)
     -> (slots i32 [n, B], target_noise f32 [n, B, A], caps_noise f32 [actor updates, B, S] or None without `caps`), device tensors: the
-    tables with which serl_td3_train reproduces the call bit for bit."""
+    tables with which serl_td3_train reproduces the call bit for bit (batch > 128: serl_td3_rng_fill_big, the tables of serl_td3_train_big)."""
     from . import _capi
     dev = torch.device(engine.device if device is None else device)
     n, B, S, A, freq, it0 = int(n_updates), int(batch), int(state_dim), int(action_dim), int(policy_update_freq), int(iteration0)
@@ -149,8 +152,9 @@ def td3_draws(engine, *, seed, learner, iteration0, n_updates, batch, n_rows, st
     cn = torch.zeros(k, B, S, dtype=torch.float32, device=dev) if caps else None
     rd = _capi.Td3RngDesc(seed=_seed64(seed, 'td3_draws'), n_rows=int(n_rows), learner0=int(learner), dense=0, caps=int(bool(caps)))
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _capi.check(_capi.lib().serl_td3_rng_fill(engine.ctx, ctypes.byref(rd), 0, S, A, B, it0, n, freq, slots.data_ptr(), tn.data_ptr(),
-                                              cn.data_ptr() if cn is not None and k else None, stream), 'serl_td3_rng_fill')
+    entry = 'serl_td3_rng_fill_big' if B > FUSED_MAX_BATCH else 'serl_td3_rng_fill'
+    _capi.check(getattr(_capi.lib(), entry)(engine.ctx, ctypes.byref(rd), 0, S, A, B, it0, n, freq, slots.data_ptr(), tn.data_ptr(),
+                                            cn.data_ptr() if cn is not None and k else None, stream), entry)
     return slots, tn, cn
 
 
@@ -179,6 +183,7 @@ class TD3:
         _hard_update(self.critic_target, self.critic)
         self.caps_dict = dict(CAPS) if getattr(args, 'use_caps', False) else None
         self.last_path = None                   # 'fused' / 'fused-mfma' / 'fused-rng' / 'fused-mfma-rng' / 'eager': what the most recent train() ran
+                                                # (batch_size > 128 on the kernel: 'fused-big' / 'fused-mfma-big' / 'fused-big-rng' / 'fused-mfma-big-rng')
         self.last_table_bytes = None            # bytes of the slot and noise tables the most recent fused train() put on the device
 
     # ---- one eager update (td3.py:123-198); also the fallback of train() -------------------------------------------------------------
@@ -233,6 +238,16 @@ class TD3:
             return False
         return _capi.lib().serl_td3_work_bytes(1, a.state_dim, a.action_dim, a.hidden_size, a.num_layers, int(a.batch_size)) > 0
 
+    def fused_big_supported(self, device):
+        """would serl_td3_train_big (minibatches of up to 512 rows, in chunks of 128) run this learner's shape on `device`?"""
+        from . import _capi
+        a = self.args
+        if torch.device(device).type != 'cuda' or self.engine is None or not torch.cuda.is_available():
+            return False
+        if a.activation_actor.lower() not in ACTIVATION_IDS:
+            return False
+        return _capi.lib().serl_td3_big_work_bytes(1, a.state_dim, a.action_dim, a.hidden_size, a.num_layers, int(a.batch_size)) > 0
+
     def train(self, replay, n_updates, *, iteration0, champion_target=False, rng=random, generator=None, fused=None, dense='valu',
               draws='host', seed=None, learner=0):
         """n_updates consecutive updates on minibatches of args.batch_size rows of `replay` (a DeviceReplay), update u with iteration
@@ -246,7 +261,10 @@ class TD3:
         first len(replay) rows of the ring; `rng` and `generator` are not touched and no table is allocated, so two calls of n1 and n2
         updates equal one of n1 + n2, and td3_draws(...) replays the draws.  The kernel (with `dense` phases) or an error, never the
         eager loop: an unknown `draws`, draws='device' without a seed or with fused=False is a ValueError, a shape or device the
-        kernel does not run a RuntimeError, all before anything is drawn."""
+        kernel does not run a RuntimeError, all before anything is drawn.
+        batch_size 129 .. 512: fused=True, dense='mfma' and draws='device' run serl_td3_train_big (last_path 'fused-big',
+        'fused-mfma-big', 'fused-big-rng', 'fused-mfma-big-rng') where fused_big_supported, else they are the RuntimeError above;
+        fused=None stays the eager loop.  A refused fused=True is raised before anything is drawn too."""
         if dense not in DENSE:
             raise ValueError('TD3.train: dense=%r (one of %s)' % (dense, ', '.join(repr(k) for k in DENSE)))
         if dense != 'valu' and fused is not None and not fused:
@@ -272,26 +290,29 @@ class TD3:
         if len(replay) < B:
             raise ValueError('TD3.train: %d rows in the ring, minibatches of %d' % (len(replay), B))
         can = self.fused_supported(replay.device)
-        if dense != 'valu' and not can:
+        big = B > FUSED_MAX_BATCH and self.fused_big_supported(replay.device)      # (then `can` is False)
+        if dense != 'valu' and not (can or big):
             raise RuntimeError('TD3.train(dense=%r): %s does not run this shape / device' % (dense, DENSE[dense][0]))
         if draws == 'device':
-            if not can:
+            if not (can or big):
                 raise RuntimeError("TD3.train(draws='device'): serl_td3_train_rng does not run this shape / device")
             from . import _capi
             rd = _capi.Td3RngDesc(seed=seed, n_rows=len(replay), learner0=int(learner), dense=int(dense == 'mfma'),
                                   caps=int(self.caps_dict is not None))
-            td, pg = self._train_fused(replay, None, None, None, int(iteration0), not champion_target, 'serl_td3_train_rng', n_updates, rd)
-            self.last_path = DENSE[dense][1] + '-rng'
+            td, pg = self._train_fused(replay, None, None, None, int(iteration0), not champion_target,
+                                       'serl_td3_train_big' if big else 'serl_td3_train_rng', n_updates, rd, dense)
+            self.last_path = DENSE[dense][1] + ('-big' if big else '') + '-rng'
             return {'PG_obj': float(np.mean([-x for x in pg])) if len(pg) else float('nan'), 'TD_loss': float(np.median(td))}
+        if fused and not (can or big):
+            raise RuntimeError('TD3.train(fused=True): serl_td3_train does not run this shape / device')
         slots = _replay.sample_many(len(replay), B, n_updates, rng)
         freq = int(a.policy_update_freq)
         tn, cn = draw_noise(n_updates, B, S, A, int(iteration0), freq, self.caps_dict is not None, generator)
-        if fused and not can:
-            raise RuntimeError('TD3.train(fused=True): serl_td3_train does not run this shape / device')
-        use = can and (dense != 'valu' or (FUSED_DEFAULT if fused is None else bool(fused)))
+        use = (can and (dense != 'valu' or (FUSED_DEFAULT if fused is None else bool(fused)))) or (big and (dense != 'valu' or bool(fused)))
         if use:
-            td, pg = self._train_fused(replay, slots, tn, cn, int(iteration0), not champion_target, DENSE[dense][0])
-            self.last_path = DENSE[dense][1]
+            td, pg = self._train_fused(replay, slots, tn, cn, int(iteration0), not champion_target,
+                                       'serl_td3_train_big' if big else DENSE[dense][0], dense=dense)
+            self.last_path = DENSE[dense][1] + ('-big' if big else '')
         else:
             td, pg = self._train_eager(replay, slots, tn, cn, int(iteration0), champion_target)
             self.last_path = 'eager'
@@ -312,8 +333,10 @@ class TD3:
                 pg.append(float(pgl))
         return td, pg
 
-    def _train_fused(self, replay, slots, tn, cn, iteration0, update_actor_target, entry='serl_td3_train', n_updates=None, rng_desc=None):
-        """rng_desc (a _capi.Td3RngDesc, entry 'serl_td3_train_rng'): n_updates updates with no table at all -- slots, tn, cn are None"""
+    def _train_fused(self, replay, slots, tn, cn, iteration0, update_actor_target, entry='serl_td3_train', n_updates=None, rng_desc=None,
+                     dense='valu'):
+        """rng_desc (a _capi.Td3RngDesc, entry 'serl_td3_train_rng'): n_updates updates with no table at all -- slots, tn, cn are None.
+        entry 'serl_td3_train_big': with the tables or with rng_desc, `dense` phases, the workspace of serl_td3_big_work_bytes"""
         from . import _capi
         a, dev = self.args, replay.device
         L = _capi.lib()
@@ -335,7 +358,8 @@ class TD3:
         self.last_table_bytes = sum(x.numel() * x.element_size() for x in (sl, tn_d, cn_d) if x is not None)
         td = torch.zeros(n, dtype=torch.float32, device=dev)
         pg = torch.full((n,), float('nan'), dtype=torch.float32, device=dev)
-        wb = int(L.serl_td3_work_bytes(1, S, A, a.hidden_size, a.num_layers, B))
+        big = entry == 'serl_td3_train_big'
+        wb = int((L.serl_td3_big_work_bytes if big else L.serl_td3_work_bytes)(1, S, A, a.hidden_size, a.num_layers, B))
         work = torch.empty(wb // 4, dtype=torch.float32, device=dev)
         c = self.caps_dict or {'lambda_s': 0.0, 'lambda_t': 0.0, 'eps_sd': 0.0}
         d = _capi.Td3Desc(state_dim=S, action_dim=A, hidden=a.hidden_size, num_layers=a.num_layers,
@@ -355,7 +379,10 @@ class TD3:
                           (work.data_ptr() if cn_d is not None else None), caps_stride=0, td_loss=td.data_ptr(), pg_loss=pg.data_ptr(),
                           loss_stride=n, work=work.data_ptr(), work_bytes=wb)
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        if rng_desc is not None:
+        if big:
+            bd = _capi.Td3BigDesc(rng=ctypes.pointer(rng_desc) if rng_desc is not None else None, dense=int(dense == 'mfma'))
+            _capi.check(L.serl_td3_train_big(self.engine.ctx, ctypes.byref(d), ctypes.byref(bd), stream), entry)
+        elif rng_desc is not None:
             _capi.check(L.serl_td3_train_rng(self.engine.ctx, ctypes.byref(d), ctypes.byref(rng_desc), stream), entry)
         else:
             _capi.check(getattr(L, entry)(self.engine.ctx, ctypes.byref(d), stream), entry)

@@ -31,6 +31,14 @@ is timed, and the result says so).  --kernel-regs takes the output of tools/kern
 profiles/td3_group_timing.json, rewritten after every K.
 
   python tools/bench_td3.py --group 1,2,4,8,16,32,64,128,256
+
+With --batch B1,B2,... (a list) the chunked kernel serl_td3_train_big is timed at each minibatch size in both dense flavours, against the
+eager float32 loop at the same size (what a user with such a minibatch gets by default) and, up to 128 rows, against the unchanged
+serl_td3_train / _mfma on the same inputs -- the cost of the chunk loop at one chunk.  Rings of 640 rows (tests/td3_big.py), hidden 72
+unless --hidden says otherwise, the protocol of --dense: one process, alternating, device events, median [min .. max] of --reps
+repetitions after a warm-up.  Results, with ms per sample, go to profiles/td3_batch_timing.json.
+
+  python tools/bench_td3.py --batch 86,128,256,512
 """
 import argparse, ctypes, json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -43,10 +51,10 @@ import torch
 ENTRY = {'valu': 'serl_td3_train', 'mfma': 'serl_td3_train_mfma'}
 
 
-def fused_run(engine, d, n, dense='valu', rows_out=None, rng_seed=None):
+def fused_run(engine, d, n, dense='valu', rows_out=None, rng_seed=None, big=False):
     """-> (device ms, wall ms) of one launch of n updates of serl_td3_train (dense='mfma': serl_td3_train_mfma) on fresh copies of the
     case's rows; with rows_out (a dict) the four rows after the launch are left in it.  With rng_seed the launch is serl_td3_train_rng
-    with that seed, slots from all rows of the case's ring, and no table is uploaded."""
+    with that seed, slots from all rows of the case's ring, and no table is uploaded.  big: serl_td3_train_big (tables) instead."""
     import td3_64 as T
     from serl_amd import _capi
     L = _capi.lib()
@@ -62,7 +70,7 @@ def fused_run(engine, d, n, dense='valu', rows_out=None, rng_seed=None):
         slots, tn = t(d['slots'][:n]), t(d['tn'][:n])
         cn = t(d['cn']) if d['caps'] else None
     td, pg = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
-    wb = int(L.serl_td3_work_bytes(1, d['S'], d['A'], d['H'], d['L'], d['B']))
+    wb = int((L.serl_td3_big_work_bytes if big else L.serl_td3_work_bytes)(1, d['S'], d['A'], d['H'], d['L'], d['B']))
     work = torch.empty(wb // 4, dtype=torch.float32, device=dev)
     desc = _capi.Td3Desc(state_dim=d['S'], action_dim=d['A'], hidden=d['H'], num_layers=d['L'], activation={'tanh': 0, 'elu': 1, 'relu': 2}[d['act']],
                          n_learners=1, batch=d['B'], n_updates=n, capacity=ring.shape[0], slot_cols=d['B'], policy_update_freq=d['freq'],
@@ -81,7 +89,10 @@ def fused_run(engine, d, n, dense='valu', rows_out=None, rng_seed=None):
     w0 = time.perf_counter()
     e0.record()
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    if rng_seed is None:
+    if big:
+        bd = _capi.Td3BigDesc(rng=None, dense=int(dense == 'mfma'))
+        _capi.check(L.serl_td3_train_big(engine.ctx, ctypes.byref(desc), ctypes.byref(bd), stream), 'serl_td3_train_big')
+    elif rng_seed is None:
         _capi.check(getattr(L, ENTRY[dense])(engine.ctx, ctypes.byref(desc), stream), ENTRY[dense])
     else:
         rd = _capi.Td3RngDesc(seed=rng_seed, n_rows=ring.shape[0], learner0=0, dense=int(dense == 'mfma'), caps=int(bool(d['caps'])))
@@ -114,7 +125,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--hidden', type=int, nargs='*', default=None, help='default: 72 32 96; with --draws 72')
     ap.add_argument('--layers', type=int, default=3)
-    ap.add_argument('--batch', type=int, default=86)
+    ap.add_argument('--batch', default='86', help="a minibatch size; a list 'B1,B2,...' times serl_td3_train_big at each (see above)")
     ap.add_argument('--updates', type=int, default=2000)
     ap.add_argument('--eager-updates', type=int, default=300, help='updates of one eager repetition (the loop is slow; ms per update is what is compared)')
     ap.add_argument('--reps', type=int, default=5)
@@ -128,13 +139,17 @@ def main():
     ap.add_argument('--out', default=None, help='default: profiles/td3_fused_timing.json, with --dense profiles/td3_mfma_timing.json, '
                                                 'with --draws profiles/td3_rng_timing.json')
     a = ap.parse_args()
+    batches = [int(b) for b in a.batch.split(',')] if ',' in a.batch else None
+    a.batch = int(a.batch) if batches is None else batches[0]
     if a.hidden is None:
-        a.hidden = [72] if a.draws or a.group else [72, 32, 96]
+        a.hidden = [72] if a.draws or a.group or batches else [72, 32, 96]
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'td3_group_timing.json' if a.group else 'td3_rng_timing.json' if a.draws else 'td3_mfma_timing.json' if a.dense else 'td3_fused_timing.json')
+        a.out = os.path.join(ROOT, 'profiles', 'td3_batch_timing.json' if batches else 'td3_group_timing.json' if a.group else 'td3_rng_timing.json' if a.draws else 'td3_mfma_timing.json' if a.dense else 'td3_fused_timing.json')
     import serl_amd
     import td3_64 as T
     engine = serl_amd.RolloutEngine(0)
+    if batches:
+        return batch_main(a, engine, batches)
     if a.group:
         return group_main(a, engine)
     if a.draws:
@@ -191,6 +206,45 @@ def dense_main(a, engine):
               r[f + '_ms_per_update_device']['min'], r[f + '_ms_per_update_device']['max']) for f in flavours), same), flush=True)
     with open(a.out, 'w') as fh:
         json.dump(res, fh, indent=1)
+    print(json.dumps(res))
+
+
+def batch_main(a, engine, batches):
+    import td3_big as TB
+    from serl_amd import _capi, build as hip_build
+    H = a.hidden[0]
+    res = {'tool': 'bench_td3 --batch ' + ','.join(str(b) for b in batches), 'device': torch.cuda.get_device_name(0),
+           'source_hash': hip_build.source_hash(), 'hidden': H, 'layers': a.layers, 'updates': a.updates, 'eager_updates': a.eager_updates,
+           'reps': a.reps, 'caps': True, 'policy_update_freq': 2, 'activation': 'tanh', 'ring_rows': TB.RING_ROWS, 'batches': {}}
+    for B in batches:
+        d = TB.make_case((7, 3, H, a.layers, 'tanh', B, 2, 0, a.updates, 1, 1, 'small'), seed=H)
+        runs = [('big_' + f, dict(dense=f, big=True)) for f in ENTRY] + ([(f, dict(dense=f)) for f in ENTRY] if B <= 128 else [])
+        rows = {k: {} for k, _ in runs}
+        for _, kw in runs:
+            fused_run(engine, d, min(a.updates, 50), **kw)              # warm-up
+        eager_run(d, 20)
+        ms = {k: [] for k, _ in runs}
+        eager = []
+        for _ in range(a.reps):                                         # alternating: a drift of the clock hits all alike
+            for k, kw in runs:
+                ms[k].append(fused_run(engine, d, a.updates, rows_out=rows[k], **kw)[0] / a.updates)
+            eager.append(eager_run(d, a.eager_updates) / a.eager_updates)
+        r = {k + '_ms_per_update_device': spread(ms[k]) for k in ms}
+        r['eager_f32_ms_per_update_wall'] = spread(eager)
+        r['rows_equal'] = bool(all(np.array_equal(rows[k][x], rows['big_valu'][x]) for k in rows for x in rows[k]))
+        for f in ENTRY:
+            m = r['big_%s_ms_per_update_device' % f]['median']
+            r['big_%s_us_per_sample' % f] = 1e3 * m / B
+            r['eager_over_big_%s_median' % f] = r['eager_f32_ms_per_update_wall']['median'] / m
+            if B <= 128:
+                r['big_over_old_%s_median' % f] = m / r[f + '_ms_per_update_device']['median']
+        r['work_bytes'] = int(_capi.lib().serl_td3_big_work_bytes(1, 7, 3, H, a.layers, B))
+        res['batches']['B%d' % B] = r
+        print('B %d  %s  eager %.3f ms/update  rows equal: %s' % (B, '  '.join('%s %.4f [%.4f .. %.4f]' % (
+            k, r[k + '_ms_per_update_device']['median'], r[k + '_ms_per_update_device']['min'], r[k + '_ms_per_update_device']['max']) for k in ms),
+            r['eager_f32_ms_per_update_wall']['median'], r['rows_equal']), flush=True)
+        with open(a.out, 'w') as fh:
+            json.dump(res, fh, indent=1)
     print(json.dumps(res))
 
 
