@@ -16,7 +16,6 @@
 // (row stride 132 floats).
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <type_traits>
 #include "serl_ctx.h"
 #include "serl_rng.h"
 #include "serl_td3_mfma.h"
@@ -33,27 +32,23 @@ constexpr int TILE_ROWS = 128;          // the widest layer
 constexpr int HC = 64;                  // hidden units of the critic (td3.py:24)
 constexpr int MAX_IN = 20;              // S + A at most
 
-struct Td3Args {
-  serl_td3_desc d;
-  int64_t work_floats;                  // per learner
-};
-
 // the generator flavours (serl_td3_train_rng): what replaces d.slots / d.target_noise / d.caps_noise
 struct Td3Rng {
   uint64_t seed;
   int n_rows, learner0, caps;
 };
-struct Td3ArgsRng : Td3Args { Td3Rng rg; };
-// the group flavours (serl_td3_train_group): what is per launch above is per learner here, one row each
-struct Td3ArgsGroup : Td3Args {
-  const serl_td3_learner_row *rows;
-  int32_t *status;
-  int caps;
-};
-template <bool RNG, bool GROUP>
-using Td3KernelArgs = std::conditional_t<GROUP, Td3ArgsGroup, std::conditional_t<RNG, Td3ArgsRng, Td3Args>>;
 
-// a learner's row in registers (the group flavours); members named like the descriptor's and the generator's they stand in for
+// what every learner kernel is launched with; a flavour reads the members its source of values has
+struct Td3Args {
+  serl_td3_desc d;
+  int64_t work_floats;                  // per learner
+  Td3Rng rg;                            // the generator flavours
+  const serl_td3_learner_row *rows;     // the group flavours (serl_td3_train_group): what is per launch above is per learner here, one row each
+  int32_t *status;
+};
+
+// What one learner's updates run on, in scalar registers: the group flavours fill it from the learner's row (td3_read_row), the others
+// from the descriptor and the generator (td3_read_desc); members named like the descriptor's and the generator's they stand in for.
 struct Td3Learner {
   const float *ring;
   uint64_t seed;
@@ -80,6 +75,19 @@ __device__ __forceinline__ Td3Learner td3_read_row(const serl_td3_learner_row *r
   q.lr = uniform_f(row->lr); q.gamma = uniform_f(row->gamma); q.tau = uniform_f(row->tau); q.noise_sd = uniform_f(row->noise_sd);
   q.noise_clip = uniform_f(row->noise_clip); q.lambda_s = uniform_f(row->lambda_s); q.lambda_t = uniform_f(row->lambda_t);
   q.eps_sd = uniform_f(row->eps_sd);
+  return q;
+}
+
+// learner p of a launch whose values are the launch's: kernel arguments, scalar as they come
+__device__ __forceinline__ Td3Learner td3_read_desc(const serl_td3_desc &d, const Td3Rng &rg, int p)
+{
+  Td3Learner q;
+  q.ring = d.ring + (size_t)p * d.ring_stride;
+  q.seed = rg.seed;
+  q.capacity = d.capacity; q.n_rows = rg.n_rows; q.n_updates = d.n_updates; q.iteration0 = d.iteration0; q.key = rg.learner0 + p;
+  q.policy_update_freq = d.policy_update_freq; q.update_actor_target = d.update_actor_target; q.caps = rg.caps;
+  q.lr = d.lr; q.gamma = d.gamma; q.tau = d.tau; q.noise_sd = d.noise_sd; q.noise_clip = d.noise_clip; q.lambda_s = d.lambda_s;
+  q.lambda_t = d.lambda_t; q.eps_sd = d.eps_sd;
   return q;
 }
 
@@ -143,6 +151,30 @@ __device__ __forceinline__ Layer net_layer(const Net &n, int l)
 
 // floats of a tape: per layer the normalised values n [W][BP] and the outputs h [W][BP], then the standard deviations [layers][BP]
 __host__ __device__ inline int64_t tape_floats(int layers, int width) { return ((int64_t)2 * layers * width + layers) * BP; }
+
+// parameters of a packed actor row and of ONE twin of a packed critic row (the shapes the entries accept: far below 2^31)
+__host__ __device__ inline int actor_params(int S, int A, int H, int L) { return H * S + H + L * (H * H + 3 * H) + A * H + A; }
+__host__ __device__ inline int twin_params(int S, int A) { return HC * (S + A) + 3 * HC + HC * HC + 3 * HC + HC + 1; }
+
+// A learner's workspace: gradients | per chunk of BP samples: inputs s, s2, (s, a), (s2, a2) | the actor's tape | the critic's tape.
+// The host sizes it and the kernels carve it with these two.
+__host__ __device__ inline int grad_floats(int S, int A, int H, int L)
+{
+  const int Pa = actor_params(S, A, H, L), Pc = 2 * twin_params(S, A);
+  return ((Pa > Pc ? Pa : Pc) + 3) & ~3;
+}
+__host__ __device__ inline int64_t chunk_floats(int H, int L) { return 4 * MAX_IN * BP + tape_floats(L + 2, H) + tape_floats(3, HC); }
+
+struct Td3Work { float *g, *in_s, *in_s2, *in_sa, *in_sa2, *tape_a, *tape_c; };
+
+__device__ __forceinline__ Td3Work td3_carve(float *wk, int S, int A, int H, int L, int chunk)
+{
+  Td3Work k;
+  k.g = wk;
+  k.in_s = wk + grad_floats(S, A, H, L) + chunk * chunk_floats(H, L); k.in_s2 = k.in_s + MAX_IN * BP; k.in_sa = k.in_s2 + MAX_IN * BP;
+  k.in_sa2 = k.in_sa + MAX_IN * BP; k.tape_a = k.in_sa2 + MAX_IN * BP; k.tape_c = k.tape_a + tape_floats(L + 2, H);
+  return k;
+}
 
 struct Ctx {
   float *T0, *T1;               // LDS tiles [TILE_ROWS][LP]
@@ -390,10 +422,11 @@ __device__ __forceinline__ float *mlp_fwd(const Ctx &c, const Net &net, const fl
 }
 
 // backward pass from D = dL/d(the last Linear's output) (an LDS tile, rows of the last layer): parameter gradients to g (laid out
-// like the row; added to when accum), unless g is NULL; with want_dx the gradient of the input is returned (an LDS tile, K0 rows).
+// like the row; added to when accum), unless g is NULL; with DX_INPUT the gradient of the input is returned (an LDS tile, K0 rows).
+enum Dx { DX_NONE, DX_INPUT };
 template <bool MFMA>
 __device__ __forceinline__ float *mlp_bwd(const Ctx &c, const Net &net, const float *w, const float *x, const float *tape, float *D, float *g, bool accum,
-                          bool want_dx)
+                          Dx dx)
 {
   const int nl = net_layers(net), Wd = net_width(net);
   float *X = D == c.T0 ? c.T1 : c.T0;
@@ -407,7 +440,7 @@ __device__ __forceinline__ float *mlp_bwd(const Ctx &c, const Net &net, const fl
       row_grads(c, D, nullptr, y.N, g + y.ob, nullptr, accum);
       __syncthreads();
     }
-    if (l == 0 && !want_dx) break;
+    if (l == 0 && dx == DX_NONE) break;
     dense_bwd_x_k<MFMA>(c, w + y.oW, y.N, y.K, D, X);
     __syncthreads();
     float *s = D; D = X; X = s;
@@ -447,29 +480,10 @@ __device__ __forceinline__ void clip_adam(const Ctx &c, float *w, float *m, floa
 }
 
 // The minibatch of (seed; key, iteration) by ONE wavefront: Floyd's algorithm as serl_rng.h defines it (serl_td3_slots_serial is the same
-// draw by one thread).  Lane l computes the candidates of steps l and l + 64 up front (two Philox calls), then the steps run in order:
-// the chosen rows are held across the lanes (column i in lane i & 63, register i >> 6), a candidate is broadcast by readlane and tested
-// against all of them by one ballot.  At most 128 steps.  out: LDS [B].
-__device__ __forceinline__ void td3_draw_slots(uint64_t seed, int key, int iteration, int n_rows, int B, int lane, int *out)
-{
-  const int j0 = n_rows - B;
-  const int t_lo = lane < B ? serl_td3_slot_candidate(seed, key, iteration, lane, j0 + lane) : 0;
-  const int t_hi = lane + 64 < B ? serl_td3_slot_candidate(seed, key, iteration, lane + 64, j0 + lane + 64) : 0;
-  int c_lo = -1, c_hi = -1;             // columns lane and lane + 64 once chosen (-1: not yet; rows are >= 0)
-  for (int i = 0; i < B; ++i) {
-    const int t = __shfl(i < 64 ? t_lo : t_hi, i & 63);
-    const bool taken = __ballot(c_lo == t || c_hi == t) != 0ull;
-    const int r = taken ? j0 + i : t;
-    if (lane == (i & 63)) {
-      if (i < 64) c_lo = r; else c_hi = r;
-    }
-  }
-  if (lane < B) out[lane] = c_lo;
-  if (lane + 64 < B) out[lane + 64] = c_hi;
-}
-
-// td3_draw_slots with NR registers per lane instead of two: at most 64 NR steps (the chunked flavours: BIG_B / 64 = 8).  Lane l computes
-// the candidates of steps l, l + 64, .. up front, column i is held in lane i & 63, register i >> 6; the same draw, step for step.
+// draw by one thread).  Lane l computes the candidates of steps l, l + 64, .. up front (NR Philox calls), then the steps run in order: the
+// chosen rows are held across the lanes (column i in lane i & 63, register i >> 6), a candidate is broadcast by readlane and tested
+// against all of them by one ballot.  At most 64 NR steps: NR = 2 for minibatches of up to BP rows, BIG_B / 64 = 8 for the chunked
+// flavours -- the same draw, step for step.  out: LDS [B].
 template <int NR>
 __device__ __forceinline__ void td3_draw_slots_n(uint64_t seed, int key, int iteration, int n_rows, int B, int lane, int *out)
 {
@@ -511,366 +525,270 @@ __device__ __forceinline__ float td3_draw_caps(uint64_t seed, int key, int itera
   return serl_td3_caps_uniform(w[j & 3]);
 }
 
+// what the phases of a learner's update share; filled once at the top of the kernel
+struct Td3Run {
+  Td3Learner my;
+  Net actor, critic;
+  int S, A, B, Pa, Pc1;                 // B: rows of the minibatch; Pa, Pc1: parameters of the actor, of one twin
+  float *wa, *wat, *ma, *va, *wc, *wct, *mc, *vc;
+  const int32_t *slots;                 // the caller's tables (RNG = false)
+  const float *tnoise, *cnoise;
+  int slot_cols;
+  bool caps;                            // CAPS on: the generator's switch, or the presence of the caller's table
+  float *tq;                            // LDS [BP] target Q
+  int *slot_l;                          // LDS [BP] or [BIG_B] the minibatch's slots (RNG only: td3_lds_bytes)
+  float max_grad_norm, invB, invBA;
+};
+
+// One chunk of BP samples of the minibatch (the only one but in the chunked flavours): sample b of the chunk is sample b0 + b of the
+// minibatch, c.B / c.B4 / c.live are the chunk's, k its region of the workspace; gradients are added to from the second chunk on.
+struct Td3Chunk {
+  Ctx c;
+  Td3Work k;
+  int b0;
+  bool on, accum;                       // on: this thread's sample is one of the minibatch
+};
+
+// ---- the minibatch: rows slots[u][0 .. B) of the ring; samples from B on are zeros
+template <bool RNG>
+__device__ __forceinline__ void td3_gather(const Td3Run &r, const Td3Chunk &h, int u, float &rew, float &done)
+{
+  const Ctx &c = h.c;
+  const int S = r.S, A = r.A, SA = S + A, b = c.b;
+  const bool on = h.on;
+  float *in_s = h.k.in_s, *in_s2 = h.k.in_s2, *in_sa = h.k.in_sa, *in_sa2 = h.k.in_sa2;
+  int slot = on ? (RNG ? r.slot_l[h.b0 + b] : r.slots[(size_t)u * r.slot_cols + h.b0 + b]) : 0;
+  slot = min(max(slot, 0), r.my.capacity - 1);
+  const float *row = r.my.ring + (size_t)slot * (2 * S + A + 3);
+  if constexpr (!RNG) __syncthreads();
+  if (c.g == 0) {
+    for (int j = 0; j < S; ++j) {
+      const float s = on ? row[j] : 0.0f, s2 = on ? row[SA + j] : 0.0f;
+      in_s[j * BP + b] = s; in_sa[j * BP + b] = s; in_s2[j * BP + b] = s2; in_sa2[j * BP + b] = s2;
+    }
+    for (int k = 0; k < A; ++k) in_sa[(S + k) * BP + b] = on ? row[S + k] : 0.0f;
+  }
+  rew = on ? row[2 * S + A] : 0.0f; done = on ? row[2 * S + A + 1] : 0.0f;
+}
+
+// ---- target action and target Q (td3.py:137-146) -> r.tq
+template <bool MFMA, bool RNG>
+__device__ __forceinline__ void td3_target(const Td3Run &r, const Td3Chunk &h, int u, int iteration, float rew, float done)
+{
+  const Ctx &c = h.c;
+  const int S = r.S, A = r.A, B = r.B, b = c.b;
+  const bool on = h.on;
+  float *in_sa2 = h.k.in_sa2;
+  const float *out = mlp_fwd<MFMA>(c, r.actor, r.wat, h.k.in_s2, nullptr);
+  float tz[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  if constexpr (RNG) {
+    if (c.g == 0 && on) td3_draw_target(r.my.seed, r.my.key, iteration, h.b0 + b, tz);
+  }
+  if (c.g == 0)
+    for (int k = 0; k < A; ++k) {
+      float nz = on ? (RNG ? tz[k] : r.tnoise[((size_t)u * B + h.b0 + b) * A + k]) * r.my.noise_sd : 0.0f;
+      nz = fminf(fmaxf(nz, -r.my.noise_clip), r.my.noise_clip);
+      in_sa2[(S + k) * BP + b] = fminf(fmaxf(nz + out[k * LP + b], -1.0f), 1.0f);
+    }
+  const float q1 = mlp_fwd<MFMA>(c, r.critic, r.wct, in_sa2, nullptr)[b];
+  const float q2 = mlp_fwd<MFMA>(c, r.critic, r.wct + r.Pc1, in_sa2, nullptr)[b];
+  if (c.g == 0) r.tq[b] = rew + r.my.gamma * (fminf(q1, q2) * (1.0f - done));
+}
+
+// ---- critic loss and gradients of both twins (td3.py:149-158); the chunk's share of the loss is added to td
+template <bool MFMA>
+__device__ __forceinline__ void td3_critic(const Td3Run &r, const Td3Chunk &h, float &td)
+{
+  const Ctx &c = h.c;
+  const int b = c.b;
+  for (int k = 0; k < 2; ++k) {
+    float *out = mlp_fwd<MFMA>(c, r.critic, r.wc + k * r.Pc1, h.k.in_sa, h.k.tape_c);
+    const float e = (h.on && c.g == 0) ? out[b] - r.tq[b] : 0.0f;
+    td += block_sum(c, e * e) * r.invB;
+    if (c.g == 0) out[b] = 2.0f * e * r.invB;
+    mlp_bwd<MFMA>(c, r.critic, r.wc + k * r.Pc1, h.k.in_sa, h.k.tape_c, out, h.k.g + k * r.Pc1, h.accum, DX_NONE);
+  }
+}
+
+// ---- actor loss and gradients (td3.py:177-198) with the critic just stepped, both CAPS terms -> the chunk's share of the loss
+template <bool MFMA, bool RNG>
+__device__ __forceinline__ float td3_actor(const Td3Run &r, const Td3Chunk &h, int iteration, int n_actor)
+{
+  const Ctx &c = h.c;
+  const int S = r.S, A = r.A, SA = S + A, B = r.B, b = c.b;
+  const bool on = h.on;
+  const float invB = r.invB, invBA = r.invBA;
+  float *g = h.k.g, *in_s = h.k.in_s, *in_s2 = h.k.in_s2, *in_sa = h.k.in_sa, *in_sa2 = h.k.in_sa2, *tape_a = h.k.tape_a, *tape_c = h.k.tape_c;
+  float *out = mlp_fwd<MFMA>(c, r.actor, r.wa, in_s, tape_a);
+  float acur[4] = {0.0f, 0.0f, 0.0f, 0.0f}, abat[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  for (int k = 0; k < A; ++k) { acur[k] = out[k * LP + b]; abat[k] = in_sa[(S + k) * BP + b]; }
+  __syncthreads();
+  if (c.g == 0)
+    for (int j = 0; j < SA; ++j) in_sa2[j * BP + b] = j < S ? in_s[j * BP + b] : acur[j - S];
+  float *q = mlp_fwd<MFMA>(c, r.critic, r.wc, in_sa2, tape_c);
+  float loss = (on && c.g == 0) ? -q[b] * invB : 0.0f;
+  if (c.g == 0) q[b] = on ? -invB : 0.0f;
+  float *dx = mlp_bwd<MFMA>(c, r.critic, r.wc, in_sa2, tape_c, q, nullptr, false, DX_INPUT);
+  float da[4];
+  for (int k = 0; k < A; ++k) da[k] = dx[(S + k) * LP + b];
+  __syncthreads();
+  if (r.caps && on && c.g == 0)
+    for (int k = 0; k < A; ++k) {
+      const float df = abat[k] - acur[k];
+      loss += r.my.lambda_t * df * df * invBA;
+      da[k] -= r.my.lambda_t * 2.0f * df * invBA;
+    }
+  if (c.g == 0)
+    for (int k = 0; k < A; ++k) dx[k * LP + b] = da[k] * (1.0f - acur[k] * acur[k]);
+  mlp_bwd<MFMA>(c, r.actor, r.wa, in_s, tape_a, dx, g, h.accum, DX_NONE);
+  if (r.caps) {
+    // state_bar = state + rand * eps_sd; lambda_s * mse(action_batch, actor(state_bar))
+    if (c.g == 0) {
+      uint32_t cw[4] = {0u, 0u, 0u, 0u};
+      for (int j = 0; j < S; ++j) {
+        float z = 0.0f;                 // (a sample past the minibatch neither draws nor reads the table: its row is not there)
+        if (on) {
+          if constexpr (RNG) z = td3_draw_caps(r.my.seed, r.my.key, iteration, h.b0 + b, j, cw);
+          else z = r.cnoise[((size_t)n_actor * B + h.b0 + b) * S + j];
+        }
+        in_s2[j * BP + b] = on ? in_s[j * BP + b] + z * r.my.eps_sd : 0.0f;
+      }
+    }
+    float *ob = mlp_fwd<MFMA>(c, r.actor, r.wa, in_s2, tape_a);
+    float abar[4];
+    for (int k = 0; k < A; ++k) abar[k] = ob[k * LP + b];
+    __syncthreads();
+    if (c.g == 0)
+      for (int k = 0; k < A; ++k) {
+        const float df = on ? abat[k] - abar[k] : 0.0f;
+        loss += r.my.lambda_s * df * df * invBA;
+        ob[k * LP + b] = -r.my.lambda_s * 2.0f * df * invBA * (1.0f - abar[k] * abar[k]);
+      }
+    mlp_bwd<MFMA>(c, r.actor, r.wa, in_s2, tape_a, ob, g, true, DX_NONE);
+  }
+  return block_sum(c, loss);
+}
+
+// ---- once per actor update: soft updates (mod_utils.py:25-28): target = target * (1 - tau) + param * tau
+__device__ __forceinline__ void td3_soft_updates(const Td3Run &r, int t)
+{
+  const float tau = r.my.tau;
+  for (int e = t; e < 2 * r.Pc1; e += NT) r.wct[e] = r.wct[e] * (1.0f - tau) + r.wc[e] * tau;
+  if (r.my.update_actor_target)
+    for (int e = t; e < r.Pa; e += NT) r.wat[e] = r.wat[e] * (1.0f - tau) + r.wa[e] * tau;
+  __syncthreads();
+}
+
+// The learner kernel, one workgroup per learner, every flavour an instantiation of this one update.
 // RNG = false: slots and draws from the caller's tables (serl_td3_train / _mfma).  RNG = true: the same source, with the slot read from
 // an LDS array one wavefront fills at the top of each update and both draws generated in registers by the thread that would read them.
 // GROUP = true (with RNG; serl_td3_train_group): the same source again, with what is one value per launch elsewhere -- the ring, the
 // counts, the hyper-parameters, the generator's seed and key -- taken from the learner's row, which the workgroup reads and checks
 // itself before it touches any other memory.
-template <bool MFMA, bool RNG, bool GROUP = false>
-__global__ void __launch_bounds__(NT) td3_kernel(Td3KernelArgs<RNG, GROUP> a)
+// BIG = true (the chunked flavours, serl_td3_train_big): minibatches of up to BIG_B rows, walked in chunks of BP samples (the last one
+// may be partial).  Everything per sample -- the gather, the forward and backward passes, the draws -- runs per chunk with the thread
+// map, the tiles and the device functions above; every chunk has its own inputs and tapes in the workspace; a batch sum (a gradient, a
+// loss) is chunk 0's partial sum, then + chunk 1's, + chunk 2's, + chunk 3's (include/serl_amd.h states the order); the means divide by
+// the minibatch's B; the clip, Adam and the soft updates run once, after the last chunk.  BIG = false is the one chunk at sample 0 that
+// nothing is added to, known when the flavour is compiled.
+template <bool MFMA, bool RNG, bool GROUP, bool BIG>
+__global__ void __launch_bounds__(NT) td3_kernel(Td3Args a)
 {
   static_assert(RNG || !GROUP, "the group flavours draw inside the kernel");
+  static_assert(!(GROUP && BIG), "groups run minibatches of up to BP rows");
   extern __shared__ float lds[];
   const serl_td3_desc &d = a.d;
   const int p = blockIdx.x;
-  Ctx c;
-  c.T0 = lds; c.T1 = c.T0 + TILE_ROWS * LP; c.red4 = c.T1 + TILE_ROWS * LP; c.red = c.red4 + NG * BP;
-  float *tq = c.red + 64;               // [BP] target Q
-  int *slot_l = reinterpret_cast<int *>(tq + BP);      // [BP] the minibatch's slots (RNG only: td3_lds_bytes)
-  Td3Rng rg = {};
-  if constexpr (RNG && !GROUP) rg = a.rg;
-  // a value that is the learner's own in a group launch and the launch's otherwise: the choice is made when the flavour is compiled
-#define TD3_MY(m) (GROUP ? my.m : d.m)
-#define TD3_MY_RNG(m) (GROUP ? my.m : rg.m)
-  Td3Learner my = {};
+  Td3Run r;
   if constexpr (GROUP) {
-    my = td3_read_row(a.rows + p, a.caps);
-    const int refused = td3_check_row(my, d.batch, d.n_updates);
+    r.my = td3_read_row(a.rows + p, a.rg.caps);
+    const int refused = td3_check_row(r.my, d.batch, d.n_updates);
     if (threadIdx.x == 0) a.status[p] = refused;
     if (refused != SERL_TD3_ROW_OK) return;
+  } else {
+    r.my = td3_read_desc(d, a.rg, p);
   }
-  const int key = GROUP ? my.key : rg.learner0 + p;
-  c.t = threadIdx.x; c.b = c.t & (BP - 1); c.g = __builtin_amdgcn_readfirstlane(c.t >> 7);
-  c.wave = __builtin_amdgcn_readfirstlane(c.t >> 6); c.lane = c.t & 63;
-  c.B = d.batch; c.B4 = (d.batch + 3) & ~3; c.act = d.activation;
-  c.live = (c.b & 64) < c.B;
-  const int S = d.state_dim, A = d.action_dim, SA = S + A, RW = 2 * S + A + 3, B = d.batch, b = c.b;
-  const Net actor = {0, S, d.hidden, d.num_layers, A}, critic = {1, S, d.hidden, d.num_layers, A};
-  const int Pa = d.hidden * S + d.hidden + d.num_layers * (d.hidden * d.hidden + 3 * d.hidden) + A * d.hidden + A;
-  const int Pc1 = HC * SA + 3 * HC + HC * HC + 3 * HC + HC + 1, Pc = 2 * Pc1;
-  float *wa = d.actor + (size_t)p * d.actor_stride, *wat = d.actor_target + (size_t)p * d.actor_stride;
-  float *ma = d.actor_m + (size_t)p * d.actor_stride, *va = d.actor_v + (size_t)p * d.actor_stride;
-  float *wc = d.critic + (size_t)p * d.critic_stride, *wct = d.critic_target + (size_t)p * d.critic_stride;
-  float *mc = d.critic_m + (size_t)p * d.critic_stride, *vc = d.critic_v + (size_t)p * d.critic_stride;
-  const float *ring = GROUP ? my.ring : d.ring + (size_t)p * d.ring_stride;
-  const int32_t *slots = RNG ? nullptr : d.slots + (size_t)p * d.slots_stride;
-  const float *tnoise = RNG ? nullptr : d.target_noise + (size_t)p * d.noise_stride;
-  // (RNG: `cnoise` is only the CAPS switch, as a table's presence is without it -- never read)
-  const float *cnoise = RNG ? (TD3_MY_RNG(caps) ? TD3_MY(ring) : nullptr) : (d.caps_noise ? d.caps_noise + (size_t)p * d.caps_stride : nullptr);
-  float *td_loss = d.td_loss + (size_t)p * d.loss_stride, *pg_loss = d.pg_loss + (size_t)p * d.loss_stride;
-  // workspace of this learner: gradients | inputs s, s2, (s, a), (s2, a2) | the actor's tape | the critic's tape
-  float *wk = (float *)d.work + (size_t)p * a.work_floats;
-  float *g = wk;
-  float *in_s = g + ((max(Pa, Pc) + 3) & ~3), *in_s2 = in_s + MAX_IN * BP, *in_sa = in_s2 + MAX_IN * BP, *in_sa2 = in_sa + MAX_IN * BP;
-  float *tape_a = in_sa2 + MAX_IN * BP, *tape_c = tape_a + tape_floats(d.num_layers + 2, d.hidden);
-  int step_c = d.adam_steps[2 * p], step_a = d.adam_steps[2 * p + 1];
-  int n_actor = 0;
-  const float invB = 1.0f / (float)B, invBA = 1.0f / (float)(B * A);
-
-  for (int u = 0; u < TD3_MY(n_updates); ++u) {
-    const int iteration = TD3_MY(iteration0) + u + 1;
-    // ---- the minibatch: rows slots[u][0 .. B) of the ring; samples from B on are zeros
-    const bool on = b < B;
-    if constexpr (RNG) {
-      if (c.wave == 0) td3_draw_slots(TD3_MY_RNG(seed), key, iteration, TD3_MY_RNG(n_rows), B, c.lane, slot_l);
-      __syncthreads();
-    }
-    int slot = on ? (RNG ? slot_l[b] : slots[(size_t)u * d.slot_cols + b]) : 0;
-    slot = min(max(slot, 0), TD3_MY(capacity) - 1);
-    const float *row = ring + (size_t)slot * RW;
-    if constexpr (!RNG) __syncthreads();
-    if (c.g == 0) {
-      for (int j = 0; j < S; ++j) {
-        const float s = on ? row[j] : 0.0f, s2 = on ? row[SA + j] : 0.0f;
-        in_s[j * BP + b] = s; in_sa[j * BP + b] = s; in_s2[j * BP + b] = s2; in_sa2[j * BP + b] = s2;
-      }
-      for (int k = 0; k < A; ++k) in_sa[(S + k) * BP + b] = on ? row[S + k] : 0.0f;
-    }
-    const float rew = on ? row[2 * S + A] : 0.0f, done = on ? row[2 * S + A + 1] : 0.0f;
-    // ---- target action and target Q (td3.py:137-146)
-    {
-      const float *out = mlp_fwd<MFMA>(c, actor, wat, in_s2, nullptr);
-      float tz[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-      if constexpr (RNG) {
-        if (c.g == 0 && on) td3_draw_target(TD3_MY_RNG(seed), key, iteration, b, tz);
-      }
-      if (c.g == 0)
-        for (int k = 0; k < A; ++k) {
-          float nz = on ? (RNG ? tz[k] : tnoise[((size_t)u * B + b) * A + k]) * TD3_MY(noise_sd) : 0.0f;
-          nz = fminf(fmaxf(nz, -TD3_MY(noise_clip)), TD3_MY(noise_clip));
-          in_sa2[(S + k) * BP + b] = fminf(fmaxf(nz + out[k * LP + b], -1.0f), 1.0f);
-        }
-      const float q1 = mlp_fwd<MFMA>(c, critic, wct, in_sa2, nullptr)[b];
-      const float q2 = mlp_fwd<MFMA>(c, critic, wct + Pc1, in_sa2, nullptr)[b];
-      if (c.g == 0) tq[b] = rew + TD3_MY(gamma) * (fminf(q1, q2) * (1.0f - done));
-    }
-    // ---- critic loss and gradients of both twins (td3.py:149-158)
-    float td = 0.0f;
-    for (int k = 0; k < 2; ++k) {
-      float *out = mlp_fwd<MFMA>(c, critic, wc + k * Pc1, in_sa, tape_c);
-      const float e = (on && c.g == 0) ? out[b] - tq[b] : 0.0f;
-      td += block_sum(c, e * e) * invB;
-      if (c.g == 0) out[b] = 2.0f * e * invB;
-      mlp_bwd<MFMA>(c, critic, wc + k * Pc1, in_sa, tape_c, out, g + k * Pc1, false, false);
-    }
-    ++step_c;
-    clip_adam(c, wc, mc, vc, g, Pc, step_c, TD3_MY(lr), d.max_grad_norm);
-    if (c.t == 0) td_loss[u] = td;
-    if (iteration % TD3_MY(policy_update_freq) != 0) continue;
-    // ---- actor update (td3.py:177-198) with the critic just stepped
-    float pg;
-    {
-      float *out = mlp_fwd<MFMA>(c, actor, wa, in_s, tape_a);
-      float acur[4] = {0.0f, 0.0f, 0.0f, 0.0f}, abat[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-      for (int k = 0; k < A; ++k) { acur[k] = out[k * LP + b]; abat[k] = in_sa[(S + k) * BP + b]; }
-      __syncthreads();
-      if (c.g == 0)
-        for (int j = 0; j < SA; ++j) in_sa2[j * BP + b] = j < S ? in_s[j * BP + b] : acur[j - S];
-      float *q = mlp_fwd<MFMA>(c, critic, wc, in_sa2, tape_c);
-      float loss = (on && c.g == 0) ? -q[b] * invB : 0.0f;
-      if (c.g == 0) q[b] = on ? -invB : 0.0f;
-      float *dx = mlp_bwd<MFMA>(c, critic, wc, in_sa2, tape_c, q, nullptr, false, true);
-      float da[4];
-      for (int k = 0; k < A; ++k) da[k] = dx[(S + k) * LP + b];
-      __syncthreads();
-      if (cnoise && on && c.g == 0)
-        for (int k = 0; k < A; ++k) {
-          const float df = abat[k] - acur[k];
-          loss += TD3_MY(lambda_t) * df * df * invBA;
-          da[k] -= TD3_MY(lambda_t) * 2.0f * df * invBA;
-        }
-      if (c.g == 0)
-        for (int k = 0; k < A; ++k) dx[k * LP + b] = da[k] * (1.0f - acur[k] * acur[k]);
-      mlp_bwd<MFMA>(c, actor, wa, in_s, tape_a, dx, g, false, false);
-      if (cnoise) {
-        // state_bar = state + rand * eps_sd; lambda_s * mse(action_batch, actor(state_bar))
-        if constexpr (RNG) {
-          if (c.g == 0) {
-            uint32_t cw[4] = {0u, 0u, 0u, 0u};
-            for (int j = 0; j < S; ++j)
-              in_s2[j * BP + b] = on ? in_s[j * BP + b] + td3_draw_caps(TD3_MY_RNG(seed), key, iteration, b, j, cw) * TD3_MY(eps_sd) : 0.0f;
-          }
-        } else {
-        if (c.g == 0)
-          for (int j = 0; j < S; ++j)
-            in_s2[j * BP + b] = on ? in_s[j * BP + b] + cnoise[((size_t)n_actor * B + b) * S + j] * TD3_MY(eps_sd) : 0.0f;
-        }
-        float *ob = mlp_fwd<MFMA>(c, actor, wa, in_s2, tape_a);
-        float abar[4];
-        for (int k = 0; k < A; ++k) abar[k] = ob[k * LP + b];
-        __syncthreads();
-        if (c.g == 0)
-          for (int k = 0; k < A; ++k) {
-            const float df = on ? abat[k] - abar[k] : 0.0f;
-            loss += TD3_MY(lambda_s) * df * df * invBA;
-            ob[k * LP + b] = -TD3_MY(lambda_s) * 2.0f * df * invBA * (1.0f - abar[k] * abar[k]);
-          }
-        mlp_bwd<MFMA>(c, actor, wa, in_s2, tape_a, ob, g, true, false);
-      }
-      pg = block_sum(c, loss);
-    }
-    ++step_a; ++n_actor;
-    clip_adam(c, wa, ma, va, g, Pa, step_a, TD3_MY(lr), d.max_grad_norm);
-    if (c.t == 0) pg_loss[u] = pg;
-    // ---- soft updates (mod_utils.py:25-28): target = target * (1 - tau) + param * tau
-    const float tau = TD3_MY(tau);
-    for (int e = c.t; e < Pc; e += NT) wct[e] = wct[e] * (1.0f - tau) + wc[e] * tau;
-    if (TD3_MY(update_actor_target))
-      for (int e = c.t; e < Pa; e += NT) wat[e] = wat[e] * (1.0f - tau) + wa[e] * tau;
-    __syncthreads();
-  }
-  if (c.t == 0 && TD3_MY(n_updates) > 0) { d.adam_steps[2 * p] = step_c; d.adam_steps[2 * p + 1] = step_a; }
-}
-#undef TD3_MY
-#undef TD3_MY_RNG
-
-// The chunked flavours (serl_td3_train_big): td3_kernel's updates on minibatches of up to BIG_B rows, walked in chunks of BP samples
-// (the last one may be partial).  Everything per sample -- the gather, the forward and backward passes, the draws -- runs per chunk with
-// the thread map, the tiles and the device functions above, c.B / c.B4 / c.live being the chunk's; every chunk has its own inputs and
-// tapes in the workspace; a batch sum (a gradient, a loss) is chunk 0's partial sum, then + chunk 1's, + chunk 2's, + chunk 3's
-// (include/serl_amd.h states the order); the means divide by the minibatch's B; the clip, Adam and the soft updates run once, after the
-// last chunk.  With one chunk every operation is td3_kernel's in td3_kernel's order.  A kernel of its own rather than a fourth template
-// parameter of td3_kernel: routing both through one body changed the registers and the code of the six existing instantiations.
-template <bool MFMA, bool RNG>
-__global__ void __launch_bounds__(NT) td3_kernel_big(Td3KernelArgs<RNG, false> a)
-{
-  extern __shared__ float lds[];
-  const serl_td3_desc &d = a.d;
-  const int p = blockIdx.x;
+  const Td3Learner &my = r.my;
   Ctx c;
   c.T0 = lds; c.T1 = c.T0 + TILE_ROWS * LP; c.red4 = c.T1 + TILE_ROWS * LP; c.red = c.red4 + NG * BP;
-  float *tq = c.red + 64;               // [BP] target Q
-  int *slot_l = reinterpret_cast<int *>(tq + BP);      // [BIG_B] the minibatch's slots (RNG only: td3_lds_bytes)
-  Td3Rng rg = {};
-  if constexpr (RNG) rg = a.rg;
-  const int key = rg.learner0 + p;
+  r.tq = c.red + 64;
+  r.slot_l = reinterpret_cast<int *>(r.tq + BP);
   c.t = threadIdx.x; c.b = c.t & (BP - 1); c.g = __builtin_amdgcn_readfirstlane(c.t >> 7);
   c.wave = __builtin_amdgcn_readfirstlane(c.t >> 6); c.lane = c.t & 63;
   c.B = d.batch; c.B4 = (d.batch + 3) & ~3; c.act = d.activation;
   c.live = (c.b & 64) < c.B;
-  const int S = d.state_dim, A = d.action_dim, SA = S + A, RW = 2 * S + A + 3, B = d.batch, b = c.b;
-  const Net actor = {0, S, d.hidden, d.num_layers, A}, critic = {1, S, d.hidden, d.num_layers, A};
-  const int Pa = d.hidden * S + d.hidden + d.num_layers * (d.hidden * d.hidden + 3 * d.hidden) + A * d.hidden + A;
-  const int Pc1 = HC * SA + 3 * HC + HC * HC + 3 * HC + HC + 1, Pc = 2 * Pc1;
-  float *wa = d.actor + (size_t)p * d.actor_stride, *wat = d.actor_target + (size_t)p * d.actor_stride;
-  float *ma = d.actor_m + (size_t)p * d.actor_stride, *va = d.actor_v + (size_t)p * d.actor_stride;
-  float *wc = d.critic + (size_t)p * d.critic_stride, *wct = d.critic_target + (size_t)p * d.critic_stride;
-  float *mc = d.critic_m + (size_t)p * d.critic_stride, *vc = d.critic_v + (size_t)p * d.critic_stride;
-  const float *ring = d.ring + (size_t)p * d.ring_stride;
-  const int32_t *slots = RNG ? nullptr : d.slots + (size_t)p * d.slots_stride;
-  const float *tnoise = RNG ? nullptr : d.target_noise + (size_t)p * d.noise_stride;
-  // (RNG: `cnoise` is only the CAPS switch, as a table's presence is without it -- never read)
-  const float *cnoise = RNG ? (rg.caps ? d.ring : nullptr) : (d.caps_noise ? d.caps_noise + (size_t)p * d.caps_stride : nullptr);
+  const int S = d.state_dim, A = d.action_dim, B = d.batch;
+  r.S = S; r.A = A; r.B = B;
+  r.actor = {0, S, d.hidden, d.num_layers, A}; r.critic = {1, S, d.hidden, d.num_layers, A};
+  r.Pa = actor_params(S, A, d.hidden, d.num_layers); r.Pc1 = twin_params(S, A);
+  r.wa = d.actor + (size_t)p * d.actor_stride; r.wat = d.actor_target + (size_t)p * d.actor_stride;
+  r.ma = d.actor_m + (size_t)p * d.actor_stride; r.va = d.actor_v + (size_t)p * d.actor_stride;
+  r.wc = d.critic + (size_t)p * d.critic_stride; r.wct = d.critic_target + (size_t)p * d.critic_stride;
+  r.mc = d.critic_m + (size_t)p * d.critic_stride; r.vc = d.critic_v + (size_t)p * d.critic_stride;
+  r.slots = RNG ? nullptr : d.slots + (size_t)p * d.slots_stride;
+  r.slot_cols = d.slot_cols;
+  r.tnoise = RNG ? nullptr : d.target_noise + (size_t)p * d.noise_stride;
+  r.cnoise = RNG || !d.caps_noise ? nullptr : d.caps_noise + (size_t)p * d.caps_stride;
+  r.caps = RNG ? my.caps != 0 : d.caps_noise != nullptr;
+  r.max_grad_norm = d.max_grad_norm; r.invB = 1.0f / (float)B; r.invBA = 1.0f / (float)(B * A);
   float *td_loss = d.td_loss + (size_t)p * d.loss_stride, *pg_loss = d.pg_loss + (size_t)p * d.loss_stride;
-  // workspace of this learner: gradients | per chunk: inputs s, s2, (s, a), (s2, a2) | the actor's tape | the critic's tape
   float *wk = (float *)d.work + (size_t)p * a.work_floats;
-  float *g = wk;
-  float *in_s = g + ((max(Pa, Pc) + 3) & ~3), *in_s2 = in_s + MAX_IN * BP, *in_sa = in_s2 + MAX_IN * BP, *in_sa2 = in_sa + MAX_IN * BP;
-  float *tape_a = in_sa2 + MAX_IN * BP, *tape_c = tape_a + tape_floats(d.num_layers + 2, d.hidden);
+  const int Pc = 2 * r.Pc1;
   int step_c = d.adam_steps[2 * p], step_a = d.adam_steps[2 * p + 1];
   int n_actor = 0;
-  const float invB = 1.0f / (float)B, invBA = 1.0f / (float)(B * A);
-  const int n_chunks = (B + BP - 1) / BP;
-  int b0 = 0;                           // the first sample of the chunk at hand; sample b of the chunk is sample b0 + b of the minibatch
-  // the chunk's share of the minibatch into c and its region of the workspace into the six pointers above
-  auto enter_chunk = [&](int ch) {
-    const int64_t chunk_floats = 4 * MAX_IN * BP + tape_floats(d.num_layers + 2, d.hidden) + tape_floats(3, HC);
-    b0 = ch * BP;
-    c.B = min(BP, B - b0); c.B4 = (c.B + 3) & ~3; c.live = (c.b & 64) < c.B;
-    in_s = g + ((max(Pa, Pc) + 3) & ~3) + ch * chunk_floats; in_s2 = in_s + MAX_IN * BP; in_sa = in_s2 + MAX_IN * BP; in_sa2 = in_sa + MAX_IN * BP;
-    tape_a = in_sa2 + MAX_IN * BP; tape_c = tape_a + tape_floats(d.num_layers + 2, d.hidden);
+  const int n_chunks = BIG ? (B + BP - 1) / BP : 1;
+  auto chunk = [&](int ch) {
+    Td3Chunk h;
+    h.c = c;
+    h.b0 = BIG ? ch * BP : 0;
+    if constexpr (BIG) { h.c.B = min(BP, B - h.b0); h.c.B4 = (h.c.B + 3) & ~3; h.c.live = (c.b & 64) < h.c.B; }
+    h.k = td3_carve(wk, S, A, d.hidden, d.num_layers, BIG ? ch : 0);
+    h.on = h.b0 + c.b < B;
+    h.accum = BIG && ch > 0;
+    return h;
   };
 
-  for (int u = 0; u < d.n_updates; ++u) {
-    const int iteration = d.iteration0 + u + 1;
+  for (int u = 0; u < my.n_updates; ++u) {
+    const int iteration = my.iteration0 + u + 1;
     if constexpr (RNG) {
-      if (c.wave == 0) td3_draw_slots_n<BIG_B / 64>(rg.seed, key, iteration, rg.n_rows, B, c.lane, slot_l);
+      if (c.wave == 0) td3_draw_slots_n<(BIG ? BIG_B : BP) / 64>(my.seed, my.key, iteration, my.n_rows, B, c.lane, r.slot_l);
       __syncthreads();
     }
     float td = 0.0f;
     for (int ch = 0; ch < n_chunks; ++ch) {
-      enter_chunk(ch);
-      // ---- the minibatch: rows slots[u][0 .. B) of the ring; samples from B on are zeros
-      const bool on = b0 + b < B;
-      int slot = on ? (RNG ? slot_l[b0 + b] : slots[(size_t)u * d.slot_cols + b0 + b]) : 0;
-      slot = min(max(slot, 0), d.capacity - 1);
-      const float *row = ring + (size_t)slot * RW;
-      if constexpr (!RNG) __syncthreads();
-      if (c.g == 0) {
-        for (int j = 0; j < S; ++j) {
-          const float s = on ? row[j] : 0.0f, s2 = on ? row[SA + j] : 0.0f;
-          in_s[j * BP + b] = s; in_sa[j * BP + b] = s; in_s2[j * BP + b] = s2; in_sa2[j * BP + b] = s2;
-        }
-        for (int k = 0; k < A; ++k) in_sa[(S + k) * BP + b] = on ? row[S + k] : 0.0f;
-      }
-      const float rew = on ? row[2 * S + A] : 0.0f, done = on ? row[2 * S + A + 1] : 0.0f;
-      // ---- target action and target Q (td3.py:137-146)
-      {
-        const float *out = mlp_fwd<MFMA>(c, actor, wat, in_s2, nullptr);
-        float tz[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if constexpr (RNG) {
-          if (c.g == 0 && on) td3_draw_target(rg.seed, key, iteration, b0 + b, tz);
-        }
-        if (c.g == 0)
-          for (int k = 0; k < A; ++k) {
-            float nz = on ? (RNG ? tz[k] : tnoise[((size_t)u * B + b0 + b) * A + k]) * d.noise_sd : 0.0f;
-            nz = fminf(fmaxf(nz, -d.noise_clip), d.noise_clip);
-            in_sa2[(S + k) * BP + b] = fminf(fmaxf(nz + out[k * LP + b], -1.0f), 1.0f);
-          }
-        const float q1 = mlp_fwd<MFMA>(c, critic, wct, in_sa2, nullptr)[b];
-        const float q2 = mlp_fwd<MFMA>(c, critic, wct + Pc1, in_sa2, nullptr)[b];
-        if (c.g == 0) tq[b] = rew + d.gamma * (fminf(q1, q2) * (1.0f - done));
-      }
-      // ---- critic loss and gradients of both twins (td3.py:149-158); from the second chunk on they are added to
-      for (int k = 0; k < 2; ++k) {
-        float *out = mlp_fwd<MFMA>(c, critic, wc + k * Pc1, in_sa, tape_c);
-        const float e = (on && c.g == 0) ? out[b] - tq[b] : 0.0f;
-        td += block_sum(c, e * e) * invB;
-        if (c.g == 0) out[b] = 2.0f * e * invB;
-        mlp_bwd<MFMA>(c, critic, wc + k * Pc1, in_sa, tape_c, out, g + k * Pc1, ch > 0, false);
-      }
+      const Td3Chunk h = chunk(ch);
+      float rew, done;
+      td3_gather<RNG>(r, h, u, rew, done);
+      td3_target<MFMA, RNG>(r, h, u, iteration, rew, done);
+      td3_critic<MFMA>(r, h, td);
     }
     ++step_c;
-    clip_adam(c, wc, mc, vc, g, Pc, step_c, d.lr, d.max_grad_norm);
+    clip_adam(c, r.wc, r.mc, r.vc, wk, Pc, step_c, my.lr, r.max_grad_norm);
     if (c.t == 0) td_loss[u] = td;
-    if (iteration % d.policy_update_freq != 0) continue;
-    // ---- actor update (td3.py:177-198) with the critic just stepped
+    if (iteration % my.policy_update_freq != 0) continue;
     float pg = 0.0f;
     for (int ch = 0; ch < n_chunks; ++ch) {
-      enter_chunk(ch);
-      const bool on = b0 + b < B;
-      float *out = mlp_fwd<MFMA>(c, actor, wa, in_s, tape_a);
-      float acur[4] = {0.0f, 0.0f, 0.0f, 0.0f}, abat[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-      for (int k = 0; k < A; ++k) { acur[k] = out[k * LP + b]; abat[k] = in_sa[(S + k) * BP + b]; }
-      __syncthreads();
-      if (c.g == 0)
-        for (int j = 0; j < SA; ++j) in_sa2[j * BP + b] = j < S ? in_s[j * BP + b] : acur[j - S];
-      float *q = mlp_fwd<MFMA>(c, critic, wc, in_sa2, tape_c);
-      float loss = (on && c.g == 0) ? -q[b] * invB : 0.0f;
-      if (c.g == 0) q[b] = on ? -invB : 0.0f;
-      float *dx = mlp_bwd<MFMA>(c, critic, wc, in_sa2, tape_c, q, nullptr, false, true);
-      float da[4];
-      for (int k = 0; k < A; ++k) da[k] = dx[(S + k) * LP + b];
-      __syncthreads();
-      if (cnoise && on && c.g == 0)
-        for (int k = 0; k < A; ++k) {
-          const float df = abat[k] - acur[k];
-          loss += d.lambda_t * df * df * invBA;
-          da[k] -= d.lambda_t * 2.0f * df * invBA;
-        }
-      if (c.g == 0)
-        for (int k = 0; k < A; ++k) dx[k * LP + b] = da[k] * (1.0f - acur[k] * acur[k]);
-      mlp_bwd<MFMA>(c, actor, wa, in_s, tape_a, dx, g, ch > 0, false);
-      if (cnoise) {
-        // state_bar = state + rand * eps_sd; lambda_s * mse(action_batch, actor(state_bar))
-        if constexpr (RNG) {
-          if (c.g == 0) {
-            uint32_t cw[4] = {0u, 0u, 0u, 0u};
-            for (int j = 0; j < S; ++j)
-              in_s2[j * BP + b] = on ? in_s[j * BP + b] + td3_draw_caps(rg.seed, key, iteration, b0 + b, j, cw) * d.eps_sd : 0.0f;
-          }
-        } else {
-          if (c.g == 0)
-            for (int j = 0; j < S; ++j)
-              in_s2[j * BP + b] = on ? in_s[j * BP + b] + cnoise[((size_t)n_actor * B + b0 + b) * S + j] * d.eps_sd : 0.0f;
-        }
-        float *ob = mlp_fwd<MFMA>(c, actor, wa, in_s2, tape_a);
-        float abar[4];
-        for (int k = 0; k < A; ++k) abar[k] = ob[k * LP + b];
-        __syncthreads();
-        if (c.g == 0)
-          for (int k = 0; k < A; ++k) {
-            const float df = on ? abat[k] - abar[k] : 0.0f;
-            loss += d.lambda_s * df * df * invBA;
-            ob[k * LP + b] = -d.lambda_s * 2.0f * df * invBA * (1.0f - abar[k] * abar[k]);
-          }
-        mlp_bwd<MFMA>(c, actor, wa, in_s2, tape_a, ob, g, true, false);
-      }
-      const float chunk_pg = block_sum(c, loss);
+      const float chunk_pg = td3_actor<MFMA, RNG>(r, chunk(ch), iteration, n_actor);
       pg = ch == 0 ? chunk_pg : pg + chunk_pg;
     }
     ++step_a; ++n_actor;
-    clip_adam(c, wa, ma, va, g, Pa, step_a, d.lr, d.max_grad_norm);
+    clip_adam(c, r.wa, r.ma, r.va, wk, r.Pa, step_a, my.lr, r.max_grad_norm);
     if (c.t == 0) pg_loss[u] = pg;
-    // ---- soft updates (mod_utils.py:25-28): target = target * (1 - tau) + param * tau
-    const float tau = d.tau;
-    for (int e = c.t; e < Pc; e += NT) wct[e] = wct[e] * (1.0f - tau) + wc[e] * tau;
-    if (d.update_actor_target)
-      for (int e = c.t; e < Pa; e += NT) wat[e] = wat[e] * (1.0f - tau) + wa[e] * tau;
-    __syncthreads();
+    td3_soft_updates(r, c.t);
   }
-  if (c.t == 0 && d.n_updates > 0) { d.adam_steps[2 * p] = step_c; d.adam_steps[2 * p + 1] = step_a; }
+  if (c.t == 0 && my.n_updates > 0) { d.adam_steps[2 * p] = step_c; d.adam_steps[2 * p + 1] = step_a; }
 }
 
-
-// what serl_td3_train_rng draws, written out as the tables serl_td3_train takes: one workgroup per update, the slots by its first
-// wavefront (td3_draw_slots), thread b the draws of sample b (td3_draw_target / td3_draw_caps)
-__global__ void __launch_bounds__(BP) td3_rng_fill_kernel(Td3Rng rg, int key, int S, int A, int B, int iteration0, int freq, int32_t *slots, float *tn,
-                                                          float *cn)
+// what serl_td3_train_rng draws, written out as the tables serl_td3_train takes: one workgroup of THREADS (BP; BIG_B for the chunked
+// flavours' tables) per update, the slots by its first wavefront (td3_draw_slots_n), thread b the draws of sample b (td3_draw_target /
+// td3_draw_caps)
+template <int THREADS>
+__global__ void __launch_bounds__(THREADS) td3_rng_fill_kernel(Td3Rng rg, int key, int S, int A, int B, int iteration0, int freq, int32_t *slots,
+                                                               float *tn, float *cn)
 {
-  __shared__ int slot_l[BP];
+  __shared__ int slot_l[THREADS];
   const int u = blockIdx.x, b = threadIdx.x, iteration = iteration0 + u + 1;
-  if (b < 64) td3_draw_slots(rg.seed, key, iteration, rg.n_rows, B, b, slot_l);
+  if (b < 64) td3_draw_slots_n<THREADS / 64>(rg.seed, key, iteration, rg.n_rows, B, b, slot_l);
   __syncthreads();
   if (b >= B) return;
   slots[(size_t)u * B + b] = slot_l[b];
@@ -883,99 +801,99 @@ __global__ void __launch_bounds__(BP) td3_rng_fill_kernel(Td3Rng rg, int key, in
   for (int j = 0; j < S; ++j) cn[((size_t)n_actor * B + b) * S + j] = td3_draw_caps(rg.seed, key, iteration, b, j, cw);
 }
 
-// td3_rng_fill_kernel for the chunked flavours: BIG_B threads, td3_draw_slots_n
-__global__ void __launch_bounds__(BIG_B) td3_rng_fill_big_kernel(Td3Rng rg, int key, int S, int A, int B, int iteration0, int freq, int32_t *slots,
-                                                                 float *tn, float *cn)
+// slot_rows: the slot array of the generator flavours (BP, or BIG_B for the chunked ones), 0 with tables
+size_t td3_lds_bytes(int slot_rows)
 {
-  __shared__ int slot_l[BIG_B];
-  const int u = blockIdx.x, b = threadIdx.x, iteration = iteration0 + u + 1;
-  if (b < 64) td3_draw_slots_n<BIG_B / 64>(rg.seed, key, iteration, rg.n_rows, B, b, slot_l);
-  __syncthreads();
-  if (b >= B) return;
-  slots[(size_t)u * B + b] = slot_l[b];
-  float tz[4];
-  td3_draw_target(rg.seed, key, iteration, b, tz);
-  for (int k = 0; k < A; ++k) tn[((size_t)u * B + b) * A + k] = tz[k];
-  if (!cn || iteration % freq != 0) return;
-  const int n_actor = iteration / freq - iteration0 / freq - 1;
-  uint32_t cw[4] = {0u, 0u, 0u, 0u};
-  for (int j = 0; j < S; ++j) cn[((size_t)n_actor * B + b) * S + j] = td3_draw_caps(rg.seed, key, iteration, b, j, cw);
-}
-
-size_t td3_lds_bytes(bool rng, bool big = false)
-{
-  return ((size_t)2 * TILE_ROWS * LP + NG * BP + 64 + BP + (rng ? (big ? BIG_B : BP) : 0)) * sizeof(float);
+  return ((size_t)2 * TILE_ROWS * LP + NG * BP + 64 + BP + slot_rows) * sizeof(float);
 }
 
 // per learner; `chunks` chunks of BP samples (1 but for the chunked flavours): the gradients once, inputs and tapes per chunk
-int64_t td3_work_floats(int S, int A, int H, int L, int chunks = 1)
-{
-  const int64_t Pa = (int64_t)H * S + H + (int64_t)L * (H * H + 3 * H) + A * H + A;
-  const int64_t Pc = 2 * ((int64_t)HC * (S + A) + 3 * HC + HC * HC + 3 * HC + HC + 1);
-  const int64_t gmax = ((Pa > Pc ? Pa : Pc) + 3) & ~(int64_t)3;
-  return gmax + chunks * (4 * MAX_IN * BP + tape_floats(L + 2, H) + tape_floats(3, HC));
-}
+int64_t td3_work_floats(int S, int A, int H, int L, int chunks = 1) { return grad_floats(S, A, H, L) + chunks * chunk_floats(H, L); }
 
 bool td3_shape_ok(int S, int A, int H, int L, int B, int max_batch = BP)
 {
   return H >= 4 && H <= TILE_ROWS && H % 4 == 0 && L >= 0 && L <= 4 && S >= 1 && S <= 16 && A >= 1 && A <= 4 && B >= 1 && B <= max_batch;
 }
 
-// every entry: the checks in one order, then the launch of the flavour asked for; `fn` names the entry in serl_last_error().  With
-// `gen` (serl_td3_train_rng) the tables of the descriptor -- slots, slot_cols, target_noise, caps_noise and their strides -- are not
-// looked at, the generator's descriptor is checked last, and rg->dense picks the dense phases.  With `group` (serl_td3_train_group; gen
-// too) what a learner's row holds -- ring, ring_stride, capacity, iteration0, policy_update_freq, update_actor_target and the eight
-// hyper-parameters -- is not looked at either: the row's workgroup checks it (td3_check_row); the group descriptor takes the generator's
-// place, and the launch is made for n_updates == 0 too, since the status array is the report.  With `big` (serl_td3_train_big; not with
-// group) the minibatch may have up to BIG_B rows, the workspace is that of serl_td3_big_work_bytes, the chunked flavours are launched,
-// and with gen rg->dense must name the flavour `mfma` asks for.
-int td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream, bool mfma, const char *fn, bool gen = false, const serl_td3_rng_desc *rg = nullptr,
-              bool group = false, const serl_td3_group_desc *gd = nullptr, bool big = false)
+// What an entry point asks of td3_train: its name for serl_last_error(), where a learner's values and draws come from, and the flavour.
+//   TABLES     the descriptor holds everything (serl_td3_train / _mfma; _big without a generator)
+//   GENERATOR  slots and noise are drawn in the kernel: the descriptor's tables -- slots, slot_cols, target_noise, caps_noise and their
+//              strides -- are not looked at, `rng` is checked last and rng->dense picks the dense phases (serl_td3_train_rng; _big)
+//   GROUP      drawn in the kernel too, and what a learner's row holds -- ring, ring_stride, capacity, iteration0, policy_update_freq,
+//              update_actor_target and the eight hyper-parameters -- is not looked at either: the row's workgroup checks it
+//              (td3_check_row); `group` takes the generator's place, and the launch is made for n_updates == 0 too, since the status
+//              array is the report (serl_td3_train_group)
+// big (serl_td3_train_big; not with GROUP): the minibatch may have up to BIG_B rows, the workspace is that of serl_td3_big_work_bytes,
+// the chunked flavours are launched, and with GENERATOR rng->dense must name the flavour `mfma` asks for.
+enum Td3Source { TD3_TABLES, TD3_GENERATOR, TD3_GROUP };
+struct Td3Call {
+  const char *fn;
+  Td3Source source;
+  const serl_td3_rng_desc *rng = nullptr;
+  const serl_td3_group_desc *group = nullptr;
+  bool mfma = false, big = false;
+};
+
+// the ten learner kernels by [big][group][rng][mfma]; a flavour that does not exist is NULL
+typedef void (*Td3Kernel)(Td3Args);
+#define TD3_K(rng, group, big) {td3_kernel<false, rng, group, big>, td3_kernel<true, rng, group, big>}
+const Td3Kernel TD3_KERNELS[2][2][2][2] = {{{TD3_K(false, false, false), TD3_K(true, false, false)}, {{nullptr, nullptr}, TD3_K(true, true, false)}},
+                                           {{TD3_K(false, false, true), TD3_K(true, false, true)}, {{nullptr, nullptr}, {nullptr, nullptr}}}};
+#undef TD3_K
+
+int td3_launch(Td3Kernel kernel, const Td3Args &a, size_t lds, void *stream)
 {
-  const std::string who(fn);
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kernel, dim3(a.d.n_learners), dim3(NT), lds, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return SERL_OK;
+}
+
+// every entry: the checks in one order, then the launch of the flavour asked for
+int td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream, const Td3Call &call)
+{
+  const std::string who(call.fn);
+  const bool tables = call.source == TD3_TABLES;        // the descriptor's tables are read
+  const bool own = call.source != TD3_GROUP;            // the descriptor's ring, counts and hyper-parameters are the learners'
+  const bool big = call.big;
   if (!c || !d) return serl_fail(SERL_E_INVALID, who + ": NULL context or descriptor");
   if (!d->actor || !d->actor_target || !d->actor_m || !d->actor_v || !d->critic || !d->critic_target || !d->critic_m || !d->critic_v ||
-      !d->adam_steps || (!group && !d->ring) || (!gen && (!d->slots || !d->target_noise)) || !d->td_loss || !d->pg_loss || !d->work)
+      !d->adam_steps || (own && !d->ring) || (tables && (!d->slots || !d->target_noise)) || !d->td_loss || !d->pg_loss || !d->work)
     return serl_fail(SERL_E_INVALID, who + ": NULL array (only caps_noise may be NULL: CAPS off)");
   if (d->state_dim < 1 || d->action_dim < 1 || d->hidden < 1 || d->num_layers < 0 || d->batch < 1 || d->activation < 0 || d->activation > 2)
     return serl_fail(SERL_E_INVALID, who + ": network shape / minibatch / activation");
-  if (d->n_learners < 1 || d->n_updates < 0 || (!group && d->capacity < 1) || (!gen && d->slot_cols < d->batch) ||
-      (!group && (d->policy_update_freq < 1 || d->iteration0 < 0)))
+  if (d->n_learners < 1 || d->n_updates < 0 || (own && d->capacity < 1) || (tables && d->slot_cols < d->batch) ||
+      (own && (d->policy_update_freq < 1 || d->iteration0 < 0)))
     return serl_fail(SERL_E_INVALID, who + ": n_learners >= 1, n_updates >= 0, capacity >= 1, slot_cols >= batch, policy_update_freq >= 1, iteration0 >= 0");
-  if (!group && (long long)d->iteration0 + d->n_updates > 2147483646LL) return serl_fail(SERL_E_INVALID, who + ": iteration0 + n_updates overflows");
+  if (own && (long long)d->iteration0 + d->n_updates > 2147483646LL) return serl_fail(SERL_E_INVALID, who + ": iteration0 + n_updates overflows");
   if (!(d->max_grad_norm > 0.0f) ||
-      (!group && (!(d->lr > 0.0f) || !(d->gamma >= 0.0f) || !(d->tau >= 0.0f && d->tau <= 1.0f) || !(d->noise_sd >= 0.0f) || !(d->noise_clip >= 0.0f) ||
-                  !(d->eps_sd >= 0.0f) || d->lambda_s != d->lambda_s || d->lambda_t != d->lambda_t)))
+      (own && (!(d->lr > 0.0f) || !(d->gamma >= 0.0f) || !(d->tau >= 0.0f && d->tau <= 1.0f) || !(d->noise_sd >= 0.0f) || !(d->noise_clip >= 0.0f) ||
+               !(d->eps_sd >= 0.0f) || d->lambda_s != d->lambda_s || d->lambda_t != d->lambda_t)))
     return serl_fail(SERL_E_INVALID, who + ": lr > 0, gamma >= 0, 0 <= tau <= 1, noise_sd >= 0, noise_clip >= 0, max_grad_norm > 0, eps_sd >= 0");
   if (!td3_shape_ok(d->state_dim, d->action_dim, d->hidden, d->num_layers, d->batch, big ? BIG_B : BP))
     return serl_fail(SERL_E_UNSUPPORTED, who + ": compiled for hidden a multiple of 4 in 4 .. 128, 0 .. 4 hidden layers, state_dim 1 .. 16, "
                                          "action_dim 1 .. 4, minibatches of 1 .. " + (big ? "512" : "128") + " rows; other shapes train in PyTorch");
   const int Pa = serl_param_count(d->state_dim, d->hidden, d->num_layers, d->action_dim), Pc = serl_td3_param_count(d->state_dim, d->action_dim);
   if (d->actor_stride < Pa || d->critic_stride < Pc) return serl_fail(SERL_E_INVALID, who + ": a row stride is smaller than its parameter count");
-  if ((!group && d->ring_stride < 0) || (!gen && (d->slots_stride < 0 || d->noise_stride < 0 || d->caps_stride < 0)) || d->loss_stride < d->n_updates)
+  if ((own && d->ring_stride < 0) || (tables && (d->slots_stride < 0 || d->noise_stride < 0 || d->caps_stride < 0)) || d->loss_stride < d->n_updates)
     return serl_fail(SERL_E_INVALID, who + ": negative learner stride, or loss_stride < n_updates");
-  const int chunks = big ? (d->batch + BP - 1) / BP : 1;
-  const int64_t work_floats = td3_work_floats(d->state_dim, d->action_dim, d->hidden, d->num_layers, chunks);
-  if (d->work_bytes < (int64_t)d->n_learners * work_floats * (int64_t)sizeof(float))
+  Td3Args a = {};
+  a.d = *d;
+  a.work_floats = td3_work_floats(d->state_dim, d->action_dim, d->hidden, d->num_layers, big ? (d->batch + BP - 1) / BP : 1);
+  if (d->work_bytes < (int64_t)d->n_learners * a.work_floats * (int64_t)sizeof(float))
     return serl_fail(SERL_E_INVALID, who + ": workspace smaller than " + (big ? "serl_td3_big_work_bytes" : "serl_td3_work_bytes"));
-  const size_t lds = td3_lds_bytes(gen, big);
+  const size_t lds = td3_lds_bytes(tables ? 0 : big ? BIG_B : BP);
   if (lds > (size_t)c->lds_per_block) return serl_fail(SERL_E_UNSUPPORTED, who + ": the activation tiles do not fit this device's LDS per workgroup");
-  if (group) {
+  bool mfma = call.mfma;
+  if (call.source == TD3_GROUP) {
+    const serl_td3_group_desc *gd = call.group;
     if (!gd || !gd->rows || !gd->status) return serl_fail(SERL_E_INVALID, who + ": NULL group descriptor, rows or status");
     if (gd->dense != 0 && gd->dense != 1) return serl_fail(SERL_E_INVALID, who + ": dense must be 0 (valu) or 1 (mfma)");
     if (gd->caps != 0 && gd->caps != 1) return serl_fail(SERL_E_INVALID, who + ": caps must be 0 or 1");
-    HIP_TRY(hipSetDevice(c->device));
-    Td3ArgsGroup ag;
-    ag.d = *d;
-    ag.work_floats = work_floats;
-    ag.rows = gd->rows; ag.status = gd->status; ag.caps = gd->caps;
-    auto kernel = gd->dense == 1 ? td3_kernel<true, true, true> : td3_kernel<false, true, true>;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kernel, dim3(d->n_learners), dim3(NT), lds, (hipStream_t)stream, ag);
-    HIP_TRY(hipGetLastError());
-    return SERL_OK;
-  }
-  if (gen) {
+    mfma = gd->dense == 1;
+    a.rows = gd->rows; a.status = gd->status; a.rg.caps = gd->caps;
+  } else if (call.source == TD3_GENERATOR) {
+    const serl_td3_rng_desc *rg = call.rng;
     if (!rg) return serl_fail(SERL_E_INVALID, who + ": NULL generator descriptor");
     if (rg->n_rows < d->batch || rg->n_rows > d->capacity) return serl_fail(SERL_E_INVALID, who + ": batch <= n_rows <= capacity");
     if ((long long)rg->learner0 + d->n_learners > 2147483647LL) return serl_fail(SERL_E_INVALID, who + ": learner0 + n_learners overflows");
@@ -983,27 +901,11 @@ int td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream, bool mfma, cons
     if (rg->caps != 0 && rg->caps != 1) return serl_fail(SERL_E_INVALID, who + ": caps must be 0 or 1");
     if (big && (rg->dense == 1) != mfma) return serl_fail(SERL_E_INVALID, who + ": the generator's dense differs from the big descriptor's");
     mfma = rg->dense == 1;
+    a.rg = {rg->seed, rg->n_rows, rg->learner0, rg->caps};
   }
-  if (d->n_updates == 0) return SERL_OK;
+  if (d->n_updates == 0 && own) return SERL_OK;
   HIP_TRY(hipSetDevice(c->device));
-  Td3Args a;
-  a.d = *d;
-  a.work_floats = work_floats;
-  if (gen) {
-    Td3ArgsRng ar;
-    ar.d = a.d; ar.work_floats = a.work_floats;
-    ar.rg = {rg->seed, rg->n_rows, rg->learner0, rg->caps};
-    auto kernel = big ? (mfma ? td3_kernel_big<true, true> : td3_kernel_big<false, true>) : (mfma ? td3_kernel<true, true> : td3_kernel<false, true>);
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kernel, dim3(d->n_learners), dim3(NT), lds, (hipStream_t)stream, ar);
-    HIP_TRY(hipGetLastError());
-    return SERL_OK;
-  }
-  auto kernel = big ? (mfma ? td3_kernel_big<true, false> : td3_kernel_big<false, false>) : (mfma ? td3_kernel<true, false> : td3_kernel<false, false>);
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kernel, dim3(d->n_learners), dim3(NT), lds, (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
-  return SERL_OK;
+  return td3_launch(TD3_KERNELS[big][!own][!tables][mfma], a, lds, stream);
 }
 
 // serl_td3_rng_fill / _big: one set of checks, then the fill kernel of BP or BIG_B threads per update
@@ -1021,11 +923,20 @@ int td3_rng_fill(serl_ctx *c, const serl_td3_rng_desc *rg, int32_t learner, int3
   if (n_updates == 0) return SERL_OK;
   HIP_TRY(hipSetDevice(c->device));
   const Td3Rng r = {rg->seed, rg->n_rows, rg->learner0, rg->caps};
-  hipLaunchKernelGGL(big ? td3_rng_fill_big_kernel : td3_rng_fill_kernel, dim3(n_updates), dim3(big ? BIG_B : BP), 0, (hipStream_t)stream, r,
+  hipLaunchKernelGGL(big ? td3_rng_fill_kernel<BIG_B> : td3_rng_fill_kernel<BP>, dim3(n_updates), dim3(big ? BIG_B : BP), 0, (hipStream_t)stream, r,
                      (int)(rg->learner0 + learner), (int)state_dim, (int)action_dim, (int)batch, (int)iteration0, (int)policy_update_freq, slots,
                      target_noise, caps_noise);
   HIP_TRY(hipGetLastError());
   return SERL_OK;
+}
+
+// what a layout function answers: the n values of v, up to `capacity` of them copied to out when given
+template <int N>
+int td3_layout_out(const int32_t (&v)[N], int32_t *out, int32_t capacity)
+{
+  for (int i = 0; i < N && i < capacity; ++i)
+    if (out) out[i] = v[i];
+  return N;
 }
 
 }  // namespace
@@ -1035,7 +946,7 @@ extern "C" {
 int serl_td3_param_count(int state_dim, int action_dim)
 {
   if (state_dim < 1 || action_dim < 1) return 0;
-  return 2 * (HC * (state_dim + action_dim) + 3 * HC + HC * HC + 3 * HC + HC + 1);
+  return 2 * twin_params(state_dim, action_dim);
 }
 
 int64_t serl_td3_work_bytes(int32_t n_learners, int32_t state_dim, int32_t action_dim, int32_t hidden, int32_t num_layers, int32_t batch)
@@ -1058,30 +969,29 @@ int serl_td3_layout(int32_t *out, int32_t capacity)
     TD3_OFF(noise_stride), TD3_OFF(caps_noise), TD3_OFF(caps_stride), TD3_OFF(td_loss), TD3_OFF(pg_loss), TD3_OFF(loss_stride),
     TD3_OFF(work), TD3_OFF(work_bytes)};
 #undef TD3_OFF
-  const int n = (int)(sizeof(v) / sizeof(v[0]));
-  for (int i = 0; i < n && i < capacity; ++i)
-    if (out) out[i] = v[i];
-  return n;
+  return td3_layout_out(v, out, capacity);
 }
 
-int serl_td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream) { return td3_train(c, d, stream, false, "serl_td3_train"); }
+int serl_td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream) { return td3_train(c, d, stream, {"serl_td3_train", TD3_TABLES}); }
 
-int serl_td3_train_mfma(serl_ctx *c, const serl_td3_desc *d, void *stream) { return td3_train(c, d, stream, true, "serl_td3_train_mfma"); }
+int serl_td3_train_mfma(serl_ctx *c, const serl_td3_desc *d, void *stream)
+{
+  Td3Call call = {"serl_td3_train_mfma", TD3_TABLES};
+  call.mfma = true;
+  return td3_train(c, d, stream, call);
+}
 
 int serl_td3_rng_layout(int32_t *out, int32_t capacity)
 {
 #define TD3_OFF(m) (int32_t)offsetof(serl_td3_rng_desc, m)
   const int32_t v[] = {(int32_t)sizeof(serl_td3_rng_desc), TD3_OFF(seed), TD3_OFF(n_rows), TD3_OFF(learner0), TD3_OFF(dense), TD3_OFF(caps)};
 #undef TD3_OFF
-  const int n = (int)(sizeof(v) / sizeof(v[0]));
-  for (int i = 0; i < n && i < capacity; ++i)
-    if (out) out[i] = v[i];
-  return n;
+  return td3_layout_out(v, out, capacity);
 }
 
 int serl_td3_train_rng(serl_ctx *c, const serl_td3_desc *d, const serl_td3_rng_desc *rg, void *stream)
 {
-  return td3_train(c, d, stream, false, "serl_td3_train_rng", true, rg);
+  return td3_train(c, d, stream, {"serl_td3_train_rng", TD3_GENERATOR, rg});
 }
 
 int serl_td3_group_layout(int32_t *out, int32_t capacity)
@@ -1096,15 +1006,12 @@ int serl_td3_group_layout(int32_t *out, int32_t capacity)
     (int32_t)sizeof(serl_td3_group_desc), TD3_GOFF(rows), TD3_GOFF(status), TD3_GOFF(dense), TD3_GOFF(caps)};
 #undef TD3_OFF
 #undef TD3_GOFF
-  const int n = (int)(sizeof(v) / sizeof(v[0]));
-  for (int i = 0; i < n && i < capacity; ++i)
-    if (out) out[i] = v[i];
-  return n;
+  return td3_layout_out(v, out, capacity);
 }
 
 int serl_td3_train_group(serl_ctx *c, const serl_td3_desc *d, const serl_td3_group_desc *gd, void *stream)
 {
-  return td3_train(c, d, stream, false, "serl_td3_train_group", true, nullptr, true, gd);
+  return td3_train(c, d, stream, {"serl_td3_train_group", TD3_GROUP, nullptr, gd});
 }
 
 int serl_td3_rng_fill(serl_ctx *c, const serl_td3_rng_desc *rg, int32_t learner, int32_t state_dim, int32_t action_dim, int32_t batch,
@@ -1134,17 +1041,16 @@ int serl_td3_big_layout(int32_t *out, int32_t capacity)
 #define TD3_OFF(m) (int32_t)offsetof(serl_td3_big_desc, m)
   const int32_t v[] = {(int32_t)sizeof(serl_td3_big_desc), TD3_OFF(rng), TD3_OFF(dense), TD3_OFF(pad0)};
 #undef TD3_OFF
-  const int n = (int)(sizeof(v) / sizeof(v[0]));
-  for (int i = 0; i < n && i < capacity; ++i)
-    if (out) out[i] = v[i];
-  return n;
+  return td3_layout_out(v, out, capacity);
 }
 
 int serl_td3_train_big(serl_ctx *c, const serl_td3_desc *d, const serl_td3_big_desc *bd, void *stream)
 {
   if (!bd) return serl_fail(SERL_E_INVALID, "serl_td3_train_big: NULL big descriptor");
   if (bd->dense != 0 && bd->dense != 1) return serl_fail(SERL_E_INVALID, "serl_td3_train_big: dense must be 0 (valu) or 1 (mfma)");
-  return td3_train(c, d, stream, bd->dense == 1, "serl_td3_train_big", bd->rng != nullptr, bd->rng, false, nullptr, true);
+  Td3Call call = {"serl_td3_train_big", bd->rng ? TD3_GENERATOR : TD3_TABLES, bd->rng};
+  call.mfma = bd->dense == 1; call.big = true;
+  return td3_train(c, d, stream, call);
 }
 
 int serl_host_td3_slots(uint64_t seed, int32_t learner, int32_t iteration, int32_t n_rows, int32_t batch, int32_t *out)

@@ -121,6 +121,80 @@ def _unpack_adam(optim, params, m, v, step):
         off += n
 
 
+# ---- what TD3.train and TD3Group.train share: a launch of K learners (K = 1 for TD3.train) -----------------------------------------------
+ROWS = ('actor', 'actor_target', 'actor_m', 'actor_v', 'critic', 'critic_target', 'critic_m', 'critic_v')
+_NAN = {'PG_obj': float('nan'), 'TD_loss': float('nan')}
+
+
+def _names(dense, big=False, rng=False, group=False):
+    """-> (the library's entry point, what last_path reports) of a fused launch"""
+    entry = 'serl_td3_train_group' if group else 'serl_td3_train_big' if big else 'serl_td3_train_rng' if rng else DENSE[dense][0]
+    return entry, DENSE[dense][1] + ('-big' if big else '') + ('-group' if group else '') + ('-rng' if rng or group else '')
+
+
+def _pack(learners, dev):
+    """-> (rows, steps): the eight packed f32 rows of the learners, [K, parameters] each on `dev`, and the Adam steps taken, i32 [K, 2]
+    (critic, actor)"""
+    packed, steps = {k: [] for k in ROWS}, []
+    for t in learners:
+        am, av, astep = _pack_adam(t.actor_optim, list(t.actor.parameters()))
+        cm, cv, cstep = _pack_adam(t.critic_optim, list(t.critic.parameters()))
+        for k, v in zip(ROWS, (pack_actor(t.actor), pack_actor(t.actor_target), am, av,
+                               pack_critic(t.critic), pack_critic(t.critic_target), cm, cv)):
+            packed[k].append(v.detach().to(torch.float32).cpu())
+        steps.append([cstep, astep])
+    return {k: torch.stack(v).contiguous().to(dev) for k, v in packed.items()}, torch.tensor(steps, dtype=torch.int32, device=dev)
+
+
+def _unpack(t, rows, steps, i):
+    """row i of what _pack made, after a launch, back into learner t; steps: [K][2] integers.  The actor's optimiser is only written
+    once it has stepped (as the eager loop leaves it untouched until the first actor update)."""
+    unpack_into(t.actor, rows['actor'][i])
+    unpack_into(t.actor_target, rows['actor_target'][i])
+    unpack_critic(t.critic, rows['critic'][i])
+    unpack_critic(t.critic_target, rows['critic_target'][i])
+    cstep, astep = (int(x) for x in steps[i])
+    _unpack_adam(t.critic_optim, list(t.critic.parameters()), rows['critic_m'][i], rows['critic_v'][i], cstep)
+    if astep:
+        _unpack_adam(t.actor_optim, list(t.actor.parameters()), rows['actor_m'][i], rows['actor_v'][i], astep)
+
+
+def _learner_fields(t, replay, iteration0, update_actor_target):
+    """what is a learner's own in a launch, under the names Td3Desc (one learner's values for the launch) and Td3LearnerRow (a group's
+    row) share"""
+    a, c = t.args, t.caps_dict or {'lambda_s': 0.0, 'lambda_t': 0.0, 'eps_sd': 0.0}
+    return dict(capacity=replay.capacity, iteration0=int(iteration0), policy_update_freq=int(a.policy_update_freq),
+                update_actor_target=int(bool(update_actor_target)), lr=a.lr, gamma=a.gamma, tau=a.tau, noise_sd=a.noise_sd,
+                noise_clip=a.noise_clip, lambda_s=c['lambda_s'], lambda_t=c['lambda_t'], eps_sd=c['eps_sd'])
+
+
+def _describe(args, n, rows, steps, td, pg, work, **per_launch):
+    """the Td3Desc of a launch of the K learners packed in `rows` (network shape and minibatch from `args`), at most n updates each, losses
+    to td / pg [K, n], workspace `work`; per_launch: the fields only some entry points read (_learner_fields, the ring, the tables)"""
+    from . import _capi
+    ptr = lambda x: x.data_ptr()
+    return _capi.Td3Desc(state_dim=args.state_dim, action_dim=args.action_dim, hidden=args.hidden_size, num_layers=args.num_layers,
+                         activation=ACTIVATION_IDS[args.activation_actor.lower()], n_learners=rows['actor'].shape[0],
+                         batch=int(args.batch_size), n_updates=n, max_grad_norm=MAX_GRAD_NORM,
+                         actor_stride=rows['actor'].stride(0), critic_stride=rows['critic'].stride(0), **{k: ptr(rows[k]) for k in ROWS},
+                         adam_steps=ptr(steps), td_loss=ptr(td), pg_loss=ptr(pg), loss_stride=n, work=ptr(work),
+                         work_bytes=work.numel() * work.element_size(), **per_launch)
+
+
+def _outputs(L, args, K, n, big, dev):
+    """-> (td zeros [K, n], pg NaN [K, n], the workspace of the launch) on `dev`"""
+    wb = int((L.serl_td3_big_work_bytes if big else L.serl_td3_work_bytes)(K, args.state_dim, args.action_dim, args.hidden_size, args.num_layers,
+                                                                        int(args.batch_size)))
+    return (torch.zeros(K, n, dtype=torch.float32, device=dev), torch.full((K, n), float('nan'), dtype=torch.float32, device=dev),
+            torch.empty(wb // 4, dtype=torch.float32, device=dev))
+
+
+def _reduce(td, pg):
+    """the losses of a learner's updates -> {'PG_obj': mean(-pg), 'TD_loss': median(td)} like train_rl; pg: NaN where the actor did not step"""
+    pg = [x for x in pg if not np.isnan(x)]
+    return {'PG_obj': float(np.mean([-x for x in pg])) if len(pg) else float('nan'), 'TD_loss': float(np.median(td))}
+
+
 def draw_noise(n_updates, batch, state_dim, action_dim, iteration0, policy_update_freq, caps, generator=None):
     """The draws of n_updates consecutive update_parameters calls from a torch CPU generator, in the order a CPU run of the reference
     consumes them: per update randn [B, A] (the target-policy noise, td3.py:138), and at actor updates with CAPS rand [B, S]
@@ -228,25 +302,23 @@ class TD3:
         return pgl, td_data
 
     # ---- a generation's updates ---------------------------------------------------------------------------------------------------------
-    def fused_supported(self, device):
-        """would serl_td3_train run this learner's shape on `device`?"""
+    def _supported(self, device, work_bytes):
+        """would the kernels whose workspace `work_bytes` (a function of the library) sizes run this learner's shape on `device`?"""
         from . import _capi
         a = self.args
         if torch.device(device).type != 'cuda' or self.engine is None or not torch.cuda.is_available():
             return False
         if a.activation_actor.lower() not in ACTIVATION_IDS:
             return False
-        return _capi.lib().serl_td3_work_bytes(1, a.state_dim, a.action_dim, a.hidden_size, a.num_layers, int(a.batch_size)) > 0
+        return getattr(_capi.lib(), work_bytes)(1, a.state_dim, a.action_dim, a.hidden_size, a.num_layers, int(a.batch_size)) > 0
+
+    def fused_supported(self, device):
+        """would serl_td3_train run this learner's shape on `device`?"""
+        return self._supported(device, 'serl_td3_work_bytes')
 
     def fused_big_supported(self, device):
         """would serl_td3_train_big (minibatches of up to 512 rows, in chunks of 128) run this learner's shape on `device`?"""
-        from . import _capi
-        a = self.args
-        if torch.device(device).type != 'cuda' or self.engine is None or not torch.cuda.is_available():
-            return False
-        if a.activation_actor.lower() not in ACTIVATION_IDS:
-            return False
-        return _capi.lib().serl_td3_big_work_bytes(1, a.state_dim, a.action_dim, a.hidden_size, a.num_layers, int(a.batch_size)) > 0
+        return self._supported(device, 'serl_td3_big_work_bytes')
 
     def train(self, replay, n_updates, *, iteration0, champion_target=False, rng=random, generator=None, fused=None, dense='valu',
               draws='host', seed=None, learner=0):
@@ -286,7 +358,7 @@ class TD3:
             raise ValueError('TD3.train: the ring holds rows of state_dim %d, action_dim %d, the learner takes %d, %d'
                              % (replay.state_dim, replay.action_dim, S, A))
         if n_updates <= 0:
-            return {'PG_obj': float('nan'), 'TD_loss': float('nan')}
+            return dict(_NAN)
         if len(replay) < B:
             raise ValueError('TD3.train: %d rows in the ring, minibatches of %d' % (len(replay), B))
         can = self.fused_supported(replay.device)
@@ -299,24 +371,17 @@ class TD3:
             from . import _capi
             rd = _capi.Td3RngDesc(seed=seed, n_rows=len(replay), learner0=int(learner), dense=int(dense == 'mfma'),
                                   caps=int(self.caps_dict is not None))
-            td, pg = self._train_fused(replay, None, None, None, int(iteration0), not champion_target,
-                                       'serl_td3_train_big' if big else 'serl_td3_train_rng', n_updates, rd, dense)
-            self.last_path = DENSE[dense][1] + ('-big' if big else '') + '-rng'
-            return {'PG_obj': float(np.mean([-x for x in pg])) if len(pg) else float('nan'), 'TD_loss': float(np.median(td))}
+            return self._train_fused(replay, n_updates, int(iteration0), not champion_target, dense=dense, big=big, rng_desc=rd)
         if fused and not (can or big):
             raise RuntimeError('TD3.train(fused=True): serl_td3_train does not run this shape / device')
         slots = _replay.sample_many(len(replay), B, n_updates, rng)
-        freq = int(a.policy_update_freq)
-        tn, cn = draw_noise(n_updates, B, S, A, int(iteration0), freq, self.caps_dict is not None, generator)
+        tn, cn = draw_noise(n_updates, B, S, A, int(iteration0), int(a.policy_update_freq), self.caps_dict is not None, generator)
         use = (can and (dense != 'valu' or (FUSED_DEFAULT if fused is None else bool(fused)))) or (big and (dense != 'valu' or bool(fused)))
         if use:
-            td, pg = self._train_fused(replay, slots, tn, cn, int(iteration0), not champion_target,
-                                       'serl_td3_train_big' if big else DENSE[dense][0], dense=dense)
-            self.last_path = DENSE[dense][1] + ('-big' if big else '')
-        else:
-            td, pg = self._train_eager(replay, slots, tn, cn, int(iteration0), champion_target)
-            self.last_path = 'eager'
-        return {'PG_obj': float(np.mean([-x for x in pg])) if len(pg) else float('nan'), 'TD_loss': float(np.median(td))}
+            return self._train_fused(replay, n_updates, int(iteration0), not champion_target, dense=dense, big=big, tables=(slots, tn, cn))
+        td, pg = self._train_eager(replay, slots, tn, cn, int(iteration0), champion_target)
+        self.last_path = 'eager'
+        return _reduce(td, pg)
 
     def _train_eager(self, replay, slots, tn, cn, iteration0, champion_target):
         td, pg, k = [], [], 0
@@ -333,70 +398,36 @@ class TD3:
                 pg.append(float(pgl))
         return td, pg
 
-    def _train_fused(self, replay, slots, tn, cn, iteration0, update_actor_target, entry='serl_td3_train', n_updates=None, rng_desc=None,
-                     dense='valu'):
-        """rng_desc (a _capi.Td3RngDesc, entry 'serl_td3_train_rng'): n_updates updates with no table at all -- slots, tn, cn are None.
-        entry 'serl_td3_train_big': with the tables or with rng_desc, `dense` phases, the workspace of serl_td3_big_work_bytes"""
+    def _train_fused(self, replay, n_updates, iteration0, update_actor_target, *, dense, big, tables=None, rng_desc=None):
+        """The K = 1 launch: n_updates updates with `dense` phases, on serl_td3_train_big when `big`, drawing from `tables` (slots, tn, cn of
+        the host) or inside the kernel with rng_desc (a _capi.Td3RngDesc; no table at all).  -> {'PG_obj', 'TD_loss'}"""
         from . import _capi
-        a, dev = self.args, replay.device
-        L = _capi.lib()
-        n, B = (int(n_updates), int(a.batch_size)) if rng_desc is not None else slots.shape
-        S, A = a.state_dim, a.action_dim
-        ap, cp = list(self.actor.parameters()), list(self.critic.parameters())
-        am, av, astep = _pack_adam(self.actor_optim, ap)
-        cm, cv, cstep = _pack_adam(self.critic_optim, cp)
+        dev, L = replay.device, _capi.lib()
+        entry, path = _names(dense, big, rng=rng_desc is not None)
         t = lambda x: x.contiguous().to(dev)
-        rows = {k: t(v) for k, v in dict(actor=pack_actor(self.actor), actor_target=pack_actor(self.actor_target), actor_m=am, actor_v=av,
-                                         critic=pack_critic(self.critic), critic_target=pack_critic(self.critic_target), critic_m=cm,
-                                         critic_v=cv).items()}
-        steps = torch.tensor([cstep, astep], dtype=torch.int32, device=dev)
-        sl = tn_d = cn_d = None
+        rows, steps = _pack([self], dev)
+        td, pg, work = _outputs(L, self.args, 1, n_updates, big, dev)
+        draws = {}
         if rng_desc is None:
-            sl = t(torch.from_numpy(np.ascontiguousarray(slots, dtype=np.int32)))
-            tn_d = t(tn.to(torch.float32))
-            cn_d = t(cn.to(torch.float32)) if cn is not None else None
-        self.last_table_bytes = sum(x.numel() * x.element_size() for x in (sl, tn_d, cn_d) if x is not None)
-        td = torch.zeros(n, dtype=torch.float32, device=dev)
-        pg = torch.full((n,), float('nan'), dtype=torch.float32, device=dev)
-        big = entry == 'serl_td3_train_big'
-        wb = int((L.serl_td3_big_work_bytes if big else L.serl_td3_work_bytes)(1, S, A, a.hidden_size, a.num_layers, B))
-        work = torch.empty(wb // 4, dtype=torch.float32, device=dev)
-        c = self.caps_dict or {'lambda_s': 0.0, 'lambda_t': 0.0, 'eps_sd': 0.0}
-        d = _capi.Td3Desc(state_dim=S, action_dim=A, hidden=a.hidden_size, num_layers=a.num_layers,
-                          activation=ACTIVATION_IDS[a.activation_actor.lower()], n_learners=1, batch=B, n_updates=n,
-                          capacity=replay.capacity, slot_cols=B, policy_update_freq=int(a.policy_update_freq), iteration0=iteration0,
-                          update_actor_target=int(bool(update_actor_target)), lr=a.lr, gamma=a.gamma, tau=a.tau, noise_sd=a.noise_sd,
-                          noise_clip=a.noise_clip, lambda_s=c['lambda_s'], lambda_t=c['lambda_t'], eps_sd=c['eps_sd'],
-                          max_grad_norm=MAX_GRAD_NORM,
-                          actor=rows['actor'].data_ptr(), actor_target=rows['actor_target'].data_ptr(), actor_m=rows['actor_m'].data_ptr(),
-                          actor_v=rows['actor_v'].data_ptr(), actor_stride=rows['actor'].numel(),
-                          critic=rows['critic'].data_ptr(), critic_target=rows['critic_target'].data_ptr(),
-                          critic_m=rows['critic_m'].data_ptr(), critic_v=rows['critic_v'].data_ptr(), critic_stride=rows['critic'].numel(),
-                          adam_steps=steps.data_ptr(), ring=replay.rows.data_ptr(), ring_stride=0,
-                          slots=sl.data_ptr() if sl is not None else None, slots_stride=0,
-                          target_noise=tn_d.data_ptr() if tn_d is not None else None, noise_stride=0,
-                          caps_noise=cn_d.data_ptr() if cn_d is not None and cn_d.numel() else
-                          (work.data_ptr() if cn_d is not None else None), caps_stride=0, td_loss=td.data_ptr(), pg_loss=pg.data_ptr(),
-                          loss_stride=n, work=work.data_ptr(), work_bytes=wb)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            sl, tn, cn = tables
+            sl, tn = t(torch.from_numpy(np.ascontiguousarray(sl, dtype=np.int32))), t(tn.to(torch.float32))
+            cn = t(cn.to(torch.float32)) if cn is not None else None
+            draws = dict(slots=sl.data_ptr(), slot_cols=sl.shape[1], target_noise=tn.data_ptr(),
+                         caps_noise=None if cn is None else cn.data_ptr() if cn.numel() else work.data_ptr())
+            tables = (sl, tn, cn)               # (alive until the synchronisation)
+        self.last_table_bytes = sum(x.numel() * x.element_size() for x in tables or () if x is not None)
+        d = _describe(self.args, n_updates, rows, steps, td, pg, work, ring=replay.rows.data_ptr(), **draws,
+                      **_learner_fields(self, replay, iteration0, update_actor_target))
+        args = [ctypes.byref(d)]
         if big:
-            bd = _capi.Td3BigDesc(rng=ctypes.pointer(rng_desc) if rng_desc is not None else None, dense=int(dense == 'mfma'))
-            _capi.check(L.serl_td3_train_big(self.engine.ctx, ctypes.byref(d), ctypes.byref(bd), stream), entry)
+            args.append(ctypes.byref(_capi.Td3BigDesc(rng=ctypes.pointer(rng_desc) if rng_desc is not None else None, dense=int(dense == 'mfma'))))
         elif rng_desc is not None:
-            _capi.check(L.serl_td3_train_rng(self.engine.ctx, ctypes.byref(d), ctypes.byref(rng_desc), stream), entry)
-        else:
-            _capi.check(getattr(L, entry)(self.engine.ctx, ctypes.byref(d), stream), entry)
+            args.append(ctypes.byref(rng_desc))
+        _capi.check(getattr(L, entry)(self.engine.ctx, *args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), entry)
         torch.cuda.synchronize(dev)
-        unpack_into(self.actor, rows['actor'])
-        unpack_into(self.actor_target, rows['actor_target'])
-        unpack_critic(self.critic, rows['critic'])
-        unpack_critic(self.critic_target, rows['critic_target'])
-        cstep, astep = (int(x) for x in steps.cpu())
-        _unpack_adam(self.critic_optim, cp, rows['critic_m'], rows['critic_v'], cstep)
-        if astep:
-            _unpack_adam(self.actor_optim, ap, rows['actor_m'], rows['actor_v'], astep)
-        td, pg = td.cpu().numpy(), pg.cpu().numpy()
-        return list(td), [x for x in pg if not np.isnan(x)]
+        _unpack(self, rows, steps.cpu().tolist(), 0)
+        self.last_path = path
+        return _reduce(td[0].cpu().numpy(), pg[0].cpu().numpy())
 
 
 # what the learners of a TD3Group must share: one launch has one network shape, one minibatch size and CAPS on or off for all
@@ -485,49 +516,23 @@ class TD3Group:
         if any(torch.device(r.device) != dev for r in replays) or not all(t.fused_supported(dev) for t in self.learners):
             raise RuntimeError('%s: serl_td3_train_group does not run this shape / device (there is no eager fall-back)' % who)
         nmax = max(ns)
-        nan = {'PG_obj': float('nan'), 'TD_loss': float('nan')}
         if nmax == 0:
-            return [dict(nan) for _ in range(K)]
+            return [dict(_NAN) for _ in range(K)]
         L = _capi.lib()
-        engine = self.learners[0].engine
-        packed = {k: [] for k in ('actor', 'actor_target', 'actor_m', 'actor_v', 'critic', 'critic_target', 'critic_m', 'critic_v')}
-        steps, params = [], []
-        for t in self.learners:
-            ap, cp = list(t.actor.parameters()), list(t.critic.parameters())
-            am, av, astep = _pack_adam(t.actor_optim, ap)
-            cm, cv, cstep = _pack_adam(t.critic_optim, cp)
-            for k, v in dict(actor=pack_actor(t.actor), actor_target=pack_actor(t.actor_target), actor_m=am, actor_v=av, critic=pack_critic(t.critic),
-                             critic_target=pack_critic(t.critic_target), critic_m=cm, critic_v=cv).items():
-                packed[k].append(v.detach().to(torch.float32).cpu())
-            steps.append([cstep, astep])
-            params.append((ap, cp))
-        rows = {k: torch.stack(v).contiguous().to(dev) for k, v in packed.items()}
-        steps = torch.tensor(steps, dtype=torch.int32, device=dev)
+        entry, path = _names(dense, group=True)
+        rows, steps = _pack(self.learners, dev)
         table = (_capi.Td3LearnerRow * K)()
         for i, (t, r) in enumerate(zip(self.learners, replays)):
-            a, c = t.args, t.caps_dict or {'lambda_s': 0.0, 'lambda_t': 0.0, 'eps_sd': 0.0}
-            table[i] = _capi.Td3LearnerRow(ring=r.rows.data_ptr(), seed=seeds[i], capacity=r.capacity, n_rows=len(r), n_updates=ns[i], iteration0=its[i],
-                                           key=keys[i], policy_update_freq=int(a.policy_update_freq), update_actor_target=int(not champs[i]),
-                                           lr=a.lr, gamma=a.gamma, tau=a.tau, noise_sd=a.noise_sd, noise_clip=a.noise_clip, lambda_s=c['lambda_s'],
-                                           lambda_t=c['lambda_t'], eps_sd=c['eps_sd'])
+            table[i] = _capi.Td3LearnerRow(ring=r.rows.data_ptr(), seed=seeds[i], n_rows=len(r), n_updates=ns[i], key=keys[i],
+                                           **_learner_fields(t, r, its[i], not champs[i]))
         table_d = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
         status = torch.full((K,), -1, dtype=torch.int32, device=dev)
-        td = torch.zeros(K, nmax, dtype=torch.float32, device=dev)
-        pg = torch.full((K, nmax), float('nan'), dtype=torch.float32, device=dev)
-        wb = int(L.serl_td3_work_bytes(K, S, A, a0.hidden_size, a0.num_layers, B))
-        work = torch.empty(wb // 4, dtype=torch.float32, device=dev)
-        d = _capi.Td3Desc(state_dim=S, action_dim=A, hidden=a0.hidden_size, num_layers=a0.num_layers,
-                          activation=ACTIVATION_IDS[a0.activation_actor.lower()], n_learners=K, batch=B, n_updates=nmax, max_grad_norm=MAX_GRAD_NORM,
-                          actor=rows['actor'].data_ptr(), actor_target=rows['actor_target'].data_ptr(), actor_m=rows['actor_m'].data_ptr(),
-                          actor_v=rows['actor_v'].data_ptr(), actor_stride=rows['actor'].stride(0),
-                          critic=rows['critic'].data_ptr(), critic_target=rows['critic_target'].data_ptr(),
-                          critic_m=rows['critic_m'].data_ptr(), critic_v=rows['critic_v'].data_ptr(), critic_stride=rows['critic'].stride(0),
-                          adam_steps=steps.data_ptr(), td_loss=td.data_ptr(), pg_loss=pg.data_ptr(), loss_stride=nmax, work=work.data_ptr(),
-                          work_bytes=wb)
+        td, pg, work = _outputs(L, a0, K, nmax, False, dev)
+        d = _describe(a0, nmax, rows, steps, td, pg, work)
         gd = _capi.Td3GroupDesc(rows=table_d.data_ptr(), status=status.data_ptr(), dense=int(dense == 'mfma'),
                                 caps=int(self.learners[0].caps_dict is not None))
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _capi.check(L.serl_td3_train_group(engine.ctx, ctypes.byref(d), ctypes.byref(gd), stream), 'serl_td3_train_group')
+        _capi.check(getattr(L, entry)(self.learners[0].engine.ctx, ctypes.byref(d), ctypes.byref(gd), stream), entry)
         torch.cuda.synchronize(dev)
         bad = [(i, int(s)) for i, s in enumerate(status.cpu().tolist()) if s != 0]
         if bad:
@@ -536,20 +541,11 @@ class TD3Group:
         steps, td, pg = steps.cpu().tolist(), td.cpu().numpy(), pg.cpu().numpy()
         out = []
         for i, t in enumerate(self.learners):
-            t.last_path = DENSE[dense][1] + '-group-rng'
+            t.last_path = path
             if ns[i] == 0:                      # (as TD3.train: nothing of the learner is touched)
-                out.append(dict(nan))
+                out.append(dict(_NAN))
                 continue
-            ap, cp = params[i]
-            unpack_into(t.actor, rows['actor'][i])
-            unpack_into(t.actor_target, rows['actor_target'][i])
-            unpack_critic(t.critic, rows['critic'][i])
-            unpack_critic(t.critic_target, rows['critic_target'][i])
-            cstep, astep = steps[i]
-            _unpack_adam(t.critic_optim, cp, rows['critic_m'][i], rows['critic_v'][i], cstep)
-            if astep:
-                _unpack_adam(t.actor_optim, ap, rows['actor_m'][i], rows['actor_v'][i], astep)
+            _unpack(t, rows, steps, i)
             t.last_table_bytes = 0
-            pgs = [x for x in pg[i, :ns[i]] if not np.isnan(x)]
-            out.append({'PG_obj': float(np.mean([-x for x in pgs])) if pgs else float('nan'), 'TD_loss': float(np.median(td[i, :ns[i]]))})
+            out.append(_reduce(td[i, :ns[i]], pg[i, :ns[i]]))
         return out

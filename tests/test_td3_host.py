@@ -232,3 +232,70 @@ def test_td3_fits_the_host_adaptors():
     assert torch.isfinite(mse) and not torch.equal(serl_amd.pack_actor(child), before)
     pgl, td = t.update_parameters((torch.randn(16, 7), torch.rand(16, 3), torch.randn(16, 7), torch.randn(16, 1), torch.zeros(16, 1)), 2)
     assert pgl is not None and np.isfinite(td)
+
+
+@pytest.mark.parametrize('shape', [(2, 1, 4, 0, 1), (7, 3, 72, 3, 86)], ids=['S2A1_H4L0', 'S7A3_H72L3'])
+def test_one_packer_and_descriptor_for_td3_and_group(shape):
+    """What TD3.train and TD3Group.train share, on CPU tensors: a TD3Group of one learner packs the rows and the steps and describes the
+    launch as that learner's own TD3 path does -- every scalar field of the Td3Desc, a learner's own values in the descriptor on one side
+    and in its Td3LearnerRow on the other -- and packing followed by unpacking leaves parameters, targets and both Adam states as they were"""
+    import serl_amd
+    from serl_amd import _capi, td3
+    S, A, H, L, B = shape
+    torch.manual_seed(S + H)
+    fresh, stepped = serl_amd.TD3(_args(S, A, H, L, 'elu', B), None), serl_amd.TD3(_args(S, A, H, L, 'elu', B), None)
+    for it in (1, 2, 3):                # the critic has stepped three times, the actor (every second iteration) once
+        stepped.update_parameters((torch.randn(B, S), torch.rand(B, A), torch.randn(B, S), torch.randn(B, 1), torch.zeros(B, 1)), it)
+    with torch.no_grad():               # (a target that differs from its network)
+        for p in stepped.actor_target.parameters():
+            p.add_(0.25)
+    for t, want_steps in ((fresh, [0, 0]), (stepped, [3, 1])):
+        ring = serl_amd.DeviceReplay(300, 'cpu', None, S, A)
+        n, lib = 13, _capi.lib()
+        launches = []
+        for learners in ([t], serl_amd.TD3Group([t]).learners):
+            rows, steps = td3._pack(learners, 'cpu')
+            td, pg, work = td3._outputs(lib, learners[0].args, 1, n, False, 'cpu')
+            launches.append((rows, steps, td, pg, work))
+        own = td3._learner_fields(t, ring, 4, True)
+        d_one = td3._describe(t.args, n, *launches[0], ring=ring.rows.data_ptr(), slot_cols=B, **own)
+        d_grp = td3._describe(t.args, n, *launches[1])
+        row = _capi.Td3LearnerRow(ring=ring.rows.data_ptr(), seed=5, n_rows=len(ring), n_updates=n, key=0, **own)
+        # the rows and the steps
+        (rows, steps), (rows_g, steps_g) = launches[0][:2], launches[1][:2]
+        assert set(rows) == set(rows_g) == set(td3.ROWS) and steps.tolist() == steps_g.tolist() == [want_steps]
+        Pa, Pc = T.actor_param_count(S, A, H, L), T.critic_param_count(S, A)
+        for k in td3.ROWS:
+            assert rows[k].shape == (1, Pa if k.startswith('actor') else Pc) and rows[k].dtype == torch.float32 and torch.equal(rows[k], rows_g[k]), k
+        assert torch.equal(rows['actor'][0], serl_amd.pack_actor(t.actor)) and torch.equal(rows['critic_target'][0], serl_amd.pack_critic(t.critic_target))
+        assert bool(rows['critic_m'].any()) == bool(want_steps[0]) and bool(rows['actor_v'].any()) == bool(want_steps[1])
+        # every scalar of the descriptor
+        scalars = [f for f, ty in _capi.Td3Desc._fields_ if ty in (ctypes.c_int32, ctypes.c_float, ctypes.c_int64) and not f.startswith('pad')]
+        assert {'state_dim', 'batch', 'n_updates', 'n_learners', 'actor_stride', 'critic_stride', 'loss_stride', 'work_bytes', 'max_grad_norm', 'lr',
+                'capacity', 'policy_update_freq'} <= set(scalars)
+        for f in scalars:
+            if f in own:
+                assert getattr(d_one, f) == getattr(row, f) and getattr(d_grp, f) == 0, f
+            elif f != 'slot_cols':
+                assert getattr(d_one, f) == getattr(d_grp, f), f
+        assert (d_one.state_dim, d_one.action_dim, d_one.hidden, d_one.num_layers, d_one.activation, d_one.n_learners, d_one.batch, d_one.n_updates) \
+            == (S, A, H, L, 1, 1, B, n)
+        assert (d_one.actor_stride, d_one.critic_stride, d_one.loss_stride, d_one.max_grad_norm) == (Pa, Pc, n, 10.0)
+        assert d_one.work_bytes == lib.serl_td3_work_bytes(1, S, A, H, L, B) > 0
+        assert (d_one.capacity, d_one.iteration0, d_one.policy_update_freq, d_one.update_actor_target) == (300, 4, 2, 1)
+        assert d_one.lr == pytest.approx(T.LR) and d_one.lambda_s == pytest.approx(0.5) and d_one.eps_sd == pytest.approx(0.05)
+        # pack, then unpack: nothing moves
+        nets = lambda: [p.detach().clone() for m in (t.actor, t.actor_target, t.critic, t.critic_target) for p in m.parameters()]
+        adam = lambda o, m: [{k: v.clone() for k, v in o.state.get(p, {}).items()} for p in m.parameters()]
+        before = nets(), adam(t.critic_optim, t.critic), adam(t.actor_optim, t.actor)
+        td3._unpack(t, rows, steps.tolist(), 0)
+        after = nets(), adam(t.critic_optim, t.critic), adam(t.actor_optim, t.actor)
+        assert all(torch.equal(x, y) for x, y in zip(before[0], after[0]))
+        for was, now, step in zip(before[1:], after[1:], want_steps):
+            for x, y in zip(was, now):
+                if x:
+                    assert set(x) == set(y) == {'step', 'exp_avg', 'exp_avg_sq'} and float(x['step']) == float(y['step']) == step
+                    assert torch.equal(x['exp_avg'], y['exp_avg']) and torch.equal(x['exp_avg_sq'], y['exp_avg_sq'])
+                else:                   # no state yet: what Adam would start from, or nothing
+                    assert step == 0 and (not y or (float(y['step']) == 0 and not y['exp_avg'].any() and not y['exp_avg_sq'].any()))
+        assert bool(t.actor_optim.state) == bool(want_steps[1])         # the actor's optimiser is only written once it has stepped
