@@ -892,6 +892,58 @@ int serl_td3_rng_fill_big(serl_ctx *ctx, const serl_td3_rng_desc *rng, int32_t l
                           int32_t iteration0, int32_t n_updates, int32_t policy_update_freq, int32_t *slots, float *target_noise,
                           float *caps_noise, void *stream);
 
+/* ---- the TD3 learner with a large minibatch's chunks on parallel workgroups (SERL_ABI_VERSION stays 9: new symbols only, nothing above
+ * has moved; the struct has a layout self-check of its own, serl_td3_wide_layout) ---------------------------------------------------
+ * serl_td3_train_big walks the G = ceil(batch / 128) chunks of a minibatch one after the other on the learner's one workgroup.
+ * serl_td3_train_wide takes the same serl_td3_desc (batch 1 .. 512) and runs a grid of G x n_learners workgroups: workgroup (ch, p) owns
+ * chunk ch of learner p for the whole call and runs everything per sample of that chunk; workgroup (0, p) alone adds the chunks'
+ * partial sums, runs the norm clip, Adam and the soft updates and stores the losses and adam_steps.
+ * Summation contract: serl_td3_train_big's.  A workgroup writes its partial gradient vectors and loss terms with nothing added to them;
+ * workgroup 0 adds them in exactly the order that kernel's passes add to its one vector: a critic gradient ((P0 + P1) + P2) + P3; an
+ * actor gradient with CAPS on  M0 + C0 + M1 + C1 + ..  left to right (Mc: chunk c's main pass, Cc: its spatial CAPS pass; Mc and Cc are
+ * never added to each other first); td = 0 + P0(Q1) + P0(Q2) + P1(Q1) + ..; pg = P0 + P1 + ..; the clip norm over the summed vector
+ * with one workgroup's thread stride.  So every array written equals serl_td3_train_big's bit for bit, and with batch <= 128
+ * serl_td3_train / _mfma / _rng's (G = 1: one workgroup per learner that waits on nothing).
+ * Hand-overs (G > 1), per update: A every workgroup's critic partials and TD terms -> workgroup 0; B the stepped critic -> every
+ * workgroup; at actor updates C the actor partials and pg terms -> workgroup 0; D the stepped actor and both targets -> every
+ * workgroup (B and D are left out when nothing follows them).  Producer: its stores drained, the workgroup's barrier, one lane's
+ * agent-scope release fence, then that lane's relaxed agent-scope atomic on the learner's word -- an add to the arrival count (A, C) or
+ * a store of the epoch, which counts the learner's B / D hand-overs of the call from 1 (never 0).  Consumer: one wavefront polls the
+ * word relaxed with s_sleep, then one agent-scope acquire fence, its loads drained, the workgroup's barrier, and only then plain vector
+ * loads of what was handed over.  The polled words and a time-out word, 16 bytes per learner, stand at the start of `work` and are
+ * zeroed on the stream (hipMemsetAsync) before every launch.  Every spin is bounded by 4 s of the 100 MHz wall clock: the workgroup
+ * whose wait expires writes the hand-over's code to the time-out word, every workgroup of that learner sees it at its next poll and
+ * returns, and status[p] holds the code -- whatever the rows of that learner hold then is unfinished.  A launch cannot hang.
+ *   rng, dense  as in serl_td3_big_desc
+ *   status      DEVICE i32 [n_learners]: 0 = the learner ran, else enum serl_td3_wide_status.  Written by the kernel only (not by a call
+ *               with n_updates == 0 or a refused one); read it behind the stream's synchronisation.
+ *   work        serl_td3_wide_work_bytes(n_learners, S, A, hidden, num_layers, batch) =
+ *                   serl_td3_big_work_bytes(...) + n_learners * (G * (3 * gf + 4) * 4 + 16)   bytes
+ *               with gf = max(actor parameters, serl_td3_param_count(S, A)) rounded up to a multiple of 4: per chunk three partial gradient
+ *               vectors (critic, actor main pass, actor CAPS pass) and four loss words, per learner the 16-byte synchronisation block;
+ *               a multiple of 16; 0 where serl_td3_big_work_bytes is 0.  The library zeroes the synchronisation blocks itself. */
+typedef struct serl_td3_wide_desc {
+  const serl_td3_rng_desc *rng;     /* HOST; NULL = tables */
+  int32_t *status;                  /* DEVICE [n_learners] */
+  int32_t dense;                    /* 0 = valu, 1 = mfma */
+  int32_t pad0;
+} serl_td3_wide_desc;
+enum serl_td3_wide_status {
+  SERL_TD3_WIDE_OK = 0,
+  SERL_TD3_WIDE_A = 1,              /* a wait of hand-over A ran out of time */
+  SERL_TD3_WIDE_B = 2,
+  SERL_TD3_WIDE_C = 3,
+  SERL_TD3_WIDE_D = 4
+};
+/* layout self-check: sizeof(serl_td3_wide_desc), then offsetof of each member in declaration order */
+int serl_td3_wide_layout(int32_t *out, int32_t capacity);
+int64_t serl_td3_wide_work_bytes(int32_t n_learners, int32_t state_dim, int32_t action_dim, int32_t hidden, int32_t num_layers, int32_t batch);
+/* Asynchronous on `stream`: one memset of the synchronisation blocks and one launch.  SERL_E_INVALID for a NULL wide, dense other than
+ * 0 / 1 or a NULL status; then the checks of serl_td3_train_big in their order with their codes (the workspace that of
+ * serl_td3_wide_work_bytes); then SERL_E_UNSUPPORTED when n_learners * G exceeds the device's CU count (the workgroups wait on each
+ * other, so all must be resident: one per CU by LDS size); all before any device work.  n_updates == 0 leaves every buffer unchanged. */
+int serl_td3_train_wide(serl_ctx *ctx, const serl_td3_desc *desc, const serl_td3_wide_desc *wide, void *stream);
+
 /* ---- the launch planner on the host (SERL_ABI_VERSION stays 9: new symbols only) --------------------------------------------------
  * WHAT serl_rollout / serl_rollout_noise (noise != 0) would launch for `desc` on a device of caps[0] CUs: the library's own decision
  * (csrc/serl_plan.h), without a context or a device.  caps[7] = {CUs, SERL_KERNEL as enum serl_kernel_hint (0 = unset),

@@ -24,7 +24,8 @@ EXPORTS = ['serl_abi_version', 'serl_last_error', 'serl_param_count', 'serl_ctx_
            'serl_td3_train_rng', 'serl_td3_rng_layout', 'serl_td3_rng_fill', 'serl_host_td3_slots',
            'serl_host_plan_rollout', 'serl_host_plan_dyn', 'serl_host_plan_multi',
            'serl_td3_train_group', 'serl_td3_group_layout',
-           'serl_td3_train_big', 'serl_td3_big_layout', 'serl_td3_big_work_bytes', 'serl_td3_rng_fill_big']
+           'serl_td3_train_big', 'serl_td3_big_layout', 'serl_td3_big_work_bytes', 'serl_td3_rng_fill_big',
+           'serl_td3_train_wide', 'serl_td3_wide_layout', 'serl_td3_wide_work_bytes']
 
 
 class BuildDesc(ctypes.Structure):
@@ -177,6 +178,22 @@ def expected_td3_big_layout():
     return [ctypes.sizeof(Td3BigDesc)] + [getattr(Td3BigDesc, n).offset for n, _ in Td3BigDesc._fields_]
 
 
+class Td3WideDesc(ctypes.Structure):
+    """serl_td3_wide_desc: the optional generator, the status array and the dense flavour of a serl_td3_train_wide call (checked by
+    serl_td3_wide_layout)"""
+    _fields_ = [('rng', ctypes.POINTER(Td3RngDesc)), ('status', VP), ('dense', ctypes.c_int32), ('pad0', ctypes.c_int32)]
+
+
+def expected_td3_wide_layout():
+    """What serl_td3_wide_layout() must return for Td3WideDesc to be right."""
+    return [ctypes.sizeof(Td3WideDesc)] + [getattr(Td3WideDesc, n).offset for n, _ in Td3WideDesc._fields_]
+
+
+# enum serl_td3_wide_status: what serl_td3_train_wide leaves in status[p] -- 0, or the hand-over whose wait ran out of time
+TD3_WIDE_STATUS = {0: 'ran', 1: 'hand-over A (critic partials to workgroup 0)', 2: 'hand-over B (the stepped critic to every workgroup)',
+                   3: 'hand-over C (actor partials to workgroup 0)', 4: 'hand-over D (the stepped actor and the targets to every workgroup)'}
+
+
 # enum serl_td3_row_status: what a workgroup of serl_td3_train_group writes to status[p]
 TD3_ROW_STATUS = {0: 'ok', 1: 'ring is NULL', 2: 'n_updates < 0 or above the launch\'s', 3: 'iteration0 < 0 or iteration0 + n_updates overflows',
                   4: 'n_rows < batch or n_rows > capacity', 5: 'policy_update_freq < 1', 6: 'a hyper-parameter out of range or NaN'}
@@ -282,6 +299,9 @@ def lib():
     L.serl_td3_big_work_bytes.argtypes = [i32] * 6
     L.serl_td3_train_big.argtypes = [VP, ctypes.POINTER(Td3Desc), ctypes.POINTER(Td3BigDesc), VP]
     L.serl_td3_rng_fill_big.argtypes = L.serl_td3_rng_fill.argtypes
+    L.serl_td3_wide_layout.argtypes = [VP, ctypes.c_int32]
+    L.serl_td3_wide_work_bytes.argtypes = [i32] * 6
+    L.serl_td3_train_wide.argtypes = [VP, ctypes.POINTER(Td3Desc), ctypes.POINTER(Td3WideDesc), VP]
     L.serl_host_plan_rollout.argtypes = [_I, ctypes.POINTER(RolloutDesc), i32, _I]
     L.serl_host_plan_dyn.argtypes = [_I, i32, i32, i32, _I]
     L.serl_host_plan_multi.argtypes = [i32, i32, _I, i32, _I, _I, _I]
@@ -291,7 +311,7 @@ def lib():
         elif f == 'serl_host_philox':
             L.serl_host_philox.restype = None
         elif f not in ('serl_last_error',):
-            getattr(L, f).restype = ctypes.c_longlong if f in ('serl_host_sample_slots', 'serl_venv_state_bytes', 'serl_td3_work_bytes', 'serl_td3_big_work_bytes') else ctypes.c_int
+            getattr(L, f).restype = ctypes.c_longlong if f in ('serl_host_sample_slots', 'serl_venv_state_bytes', 'serl_td3_work_bytes', 'serl_td3_big_work_bytes', 'serl_td3_wide_work_bytes') else ctypes.c_int
     if L.serl_abi_version() != ABI_VERSION:
         raise RuntimeError('serl_amd: ABI version mismatch (library %d, binding %d): rebuild with `python serl_amd/build.py`'
                            % (L.serl_abi_version(), ABI_VERSION))
@@ -324,6 +344,12 @@ def lib():
     n = L.serl_td3_big_layout(got, len(want))
     if n != len(want) or list(got) != want:
         raise RuntimeError('serl_amd: layout of the Td3BigDesc mirror differs from the library (serl_td3_big_layout): library %s, binding %s'
+                           % (list(got)[:n], want))
+    want = expected_td3_wide_layout()
+    got = (ctypes.c_int32 * len(want))()
+    n = L.serl_td3_wide_layout(got, len(want))
+    if n != len(want) or list(got) != want:
+        raise RuntimeError('serl_amd: layout of the Td3WideDesc mirror differs from the library (serl_td3_wide_layout): library %s, binding %s'
                            % (list(got)[:n], want))
     want = expected_venv_auto_layout()
     got = (ctypes.c_int32 * len(want))()

@@ -7,7 +7,7 @@
 // pre-drawn, parameters and Adam moments live in global memory (four rows plus gradients of a 17 k-parameter actor and a 10 k-parameter
 // critic do not fit an LDS; they stay L2-resident), activations move through two LDS tiles in [feature][sample] layout, and what the
 // backward passes need again is kept on a tape in the caller's workspace in the same layout.  Phases are separated by __syncthreads
-// only; no workgroup ever waits on another.  f32 like torch; summation orders are this file's (agreement with float64 to rounding,
+// only; no workgroup ever waits on another (but in the wide flavours, td3_signal / td3_wait below).  f32 like torch; summation orders are this file's (agreement with float64 to rounding,
 // tests/test_gpu_td3.py).
 //
 // Thread map of the dense phases (512 threads): sample b = t & 127, output group g = t >> 7 (uniform per wavefront, so a weight is
@@ -547,6 +547,8 @@ struct Td3Chunk {
   Td3Work k;
   int b0;
   bool on, accum;                       // on: this thread's sample is one of the minibatch
+  float *g_caps;                        // where the spatial CAPS pass puts its gradients: k.g, added to what the main pass left there
+  bool accum_caps;                      // -- but in the wide flavours, a vector of its own that nothing is added to
 };
 
 // ---- the minibatch: rows slots[u][0 .. B) of the ring; samples from B on are zeros
@@ -595,16 +597,19 @@ __device__ __forceinline__ void td3_target(const Td3Run &r, const Td3Chunk &h, i
   if (c.g == 0) r.tq[b] = rew + r.my.gamma * (fminf(q1, q2) * (1.0f - done));
 }
 
-// ---- critic loss and gradients of both twins (td3.py:149-158); the chunk's share of the loss is added to td
+// ---- critic loss and gradients of both twins (td3.py:149-158); the chunk's share of the loss is added to td, twin by twin; `terms`
+// (thread 0 only; NULL but in the wide flavours) gets the two twins' terms one by one, for another workgroup to add in that order
 template <bool MFMA>
-__device__ __forceinline__ void td3_critic(const Td3Run &r, const Td3Chunk &h, float &td)
+__device__ __forceinline__ void td3_critic(const Td3Run &r, const Td3Chunk &h, float &td, float *terms = nullptr)
 {
   const Ctx &c = h.c;
   const int b = c.b;
   for (int k = 0; k < 2; ++k) {
     float *out = mlp_fwd<MFMA>(c, r.critic, r.wc + k * r.Pc1, h.k.in_sa, h.k.tape_c);
     const float e = (h.on && c.g == 0) ? out[b] - r.tq[b] : 0.0f;
-    td += block_sum(c, e * e) * r.invB;
+    const float term = block_sum(c, e * e) * r.invB;
+    td += term;
+    if (terms && c.t == 0) terms[k] = term;
     if (c.g == 0) out[b] = 2.0f * e * r.invB;
     mlp_bwd<MFMA>(c, r.critic, r.wc + k * r.Pc1, h.k.in_sa, h.k.tape_c, out, h.k.g + k * r.Pc1, h.accum, DX_NONE);
   }
@@ -664,7 +669,7 @@ __device__ __forceinline__ float td3_actor(const Td3Run &r, const Td3Chunk &h, i
         loss += r.my.lambda_s * df * df * invBA;
         ob[k * LP + b] = -r.my.lambda_s * 2.0f * df * invBA * (1.0f - abar[k] * abar[k]);
       }
-    mlp_bwd<MFMA>(c, r.actor, r.wa, in_s2, tape_a, ob, g, true, DX_NONE);
+    mlp_bwd<MFMA>(c, r.actor, r.wa, in_s2, tape_a, ob, h.g_caps, h.accum_caps, DX_NONE);
   }
   return block_sum(c, loss);
 }
@@ -676,6 +681,75 @@ __device__ __forceinline__ void td3_soft_updates(const Td3Run &r, int t)
   for (int e = t; e < 2 * r.Pc1; e += NT) r.wct[e] = r.wct[e] * (1.0f - tau) + r.wc[e] * tau;
   if (r.my.update_actor_target)
     for (int e = t; e < r.Pa; e += NT) r.wat[e] = r.wat[e] * (1.0f - tau) + r.wa[e] * tau;
+  __syncthreads();
+}
+
+// ---- the wide flavours (serl_td3_train_wide): chunk ch of learner p on a workgroup of its own, grid (chunks, learners) ---------------
+// Behind the chunked flavours' workspace a learner has, per chunk, three partial gradient vectors of grad_floats each -- the critic's,
+// the actor's main pass, the actor's spatial CAPS pass -- and WIDE_LOSS_WORDS floats: the two twins' TD terms, the chunk's pg term.
+// In front of all learners' workspaces stand WIDE_SYNC_WORDS words per learner, zeroed by the launch function before every launch:
+// arrivals (workgroups 1 .. at workgroup 0), epoch (workgroup 0 to the others), the time-out word, one spare.
+constexpr int WIDE_SYNC_WORDS = 4;
+constexpr int WIDE_LOSS_WORDS = 4;
+constexpr unsigned long long WIDE_SPIN_TICKS = 400000000ull;   // 4 s of wall_clock64's 100 MHz: the other workgroups may not be resident yet
+__host__ __device__ inline int64_t wide_chunk_floats(int S, int A, int H, int L) { return (int64_t)3 * grad_floats(S, A, H, L) + WIDE_LOSS_WORDS; }
+
+// The producer's side of a hand-over: every wavefront's stores have left it, the workgroup has met, then ONE lane releases at agent
+// scope and bumps (add) or sets the word the other side polls.
+__device__ __forceinline__ void td3_signal(const Ctx &c, unsigned *word, bool add, unsigned value)
+{
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (c.t == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (add) __hip_atomic_fetch_add(word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else __hip_atomic_store(word, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// The consumer's side: wavefront 0 polls the word relaxed until it has reached `target`, then ONE agent-scope acquire, its loads
+// drained, and the workgroup's barrier before any other wavefront loads what was handed over.  The spin is bounded: after
+// WIDE_SPIN_TICKS the time-out word is set to `code` (the first one to expire wins), and a set time-out word ends every wait of the
+// learner.  -> 0, or the time-out word (uniform over the workgroup, through c.red[NW])
+__device__ __forceinline__ unsigned td3_wait(const Ctx &c, unsigned *word, unsigned target, unsigned *tmo, unsigned code)
+{
+  if (c.wave == 0) {
+    unsigned lost = 0;
+    const unsigned long long t0 = wall_clock64();
+    while ((int)(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) < 0) {
+      lost = __hip_atomic_load(tmo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (lost) break;
+      if (wall_clock64() - t0 > WIDE_SPIN_TICKS) {
+        unsigned seen = 0;
+        if (c.lane == 0 && !__hip_atomic_compare_exchange_strong(tmo, &seen, code, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+          code = seen;
+        lost = (unsigned)uniform_i((int)code);
+        break;
+      }
+      __builtin_amdgcn_s_sleep(8);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (c.lane == 0) c.red[NW] = __uint_as_float(lost);
+  }
+  __syncthreads();
+  return __float_as_uint(c.red[NW]);
+}
+
+// Workgroup 0 of a wide learner: g[e] = the chunks' partial vectors added in serl_td3_train_big's order -- chunk 0's, + chunk 1's, ..;
+// with `second`, per chunk first `part` (the main pass), then `second` (the CAPS pass), as that kernel's passes add to one vector
+__device__ __forceinline__ void td3_reduce(const Ctx &c, float *g, const float *part, const float *second, int64_t stride, int G, int P)
+{
+  for (int e = c.t; e < P; e += NT) {
+    float s = part[e];
+    if (second) s += second[e];
+    for (int ch = 1; ch < G; ++ch) {
+      s += part[ch * stride + e];
+      if (second) s += second[ch * stride + e];
+    }
+    g[e] = s;
+  }
   __syncthreads();
 }
 
@@ -691,14 +765,26 @@ __device__ __forceinline__ void td3_soft_updates(const Td3Run &r, int t)
 // loss) is chunk 0's partial sum, then + chunk 1's, + chunk 2's, + chunk 3's (include/serl_amd.h states the order); the means divide by
 // the minibatch's B; the clip, Adam and the soft updates run once, after the last chunk.  BIG = false is the one chunk at sample 0 that
 // nothing is added to, known when the flavour is compiled.
-template <bool MFMA, bool RNG, bool GROUP, bool BIG>
+// WIDE = true (with BIG; serl_td3_train_wide): the same chunks, chunk ch of learner p on workgroup (ch, p) of a grid (chunks, learners)
+// for the whole call.  A workgroup runs the per-sample phases of its chunk only and writes partial sums nothing is added to; workgroup 0
+// of the learner adds them up in the chunked flavours' order (td3_reduce, and the loss terms one by one) and alone runs the clip, Adam,
+// the soft updates and the stores of the losses.  Four hand-overs per update (td3_signal / td3_wait):
+//   A  every workgroup's critic partials and TD terms -> workgroup 0        B  the stepped critic -> every workgroup
+//   C  (actor updates) the actor partials and pg terms -> workgroup 0       D  the stepped actor and the targets -> every workgroup
+// B is left out when nothing follows it (no actor step, last update), D behind the last update.  A minibatch of one chunk runs as the
+// chunked flavour does, with no hand-over at all.
+enum Td3Handover { TD3_HO_A = SERL_TD3_WIDE_A, TD3_HO_B = SERL_TD3_WIDE_B, TD3_HO_C = SERL_TD3_WIDE_C, TD3_HO_D = SERL_TD3_WIDE_D };
+
+template <bool MFMA, bool RNG, bool GROUP, bool BIG, bool WIDE = false>
 __global__ void __launch_bounds__(NT) td3_kernel(Td3Args a)
 {
   static_assert(RNG || !GROUP, "the group flavours draw inside the kernel");
   static_assert(!(GROUP && BIG), "groups run minibatches of up to BP rows");
+  static_assert(BIG || !WIDE, "the wide flavours are chunked ones");
   extern __shared__ float lds[];
   const serl_td3_desc &d = a.d;
-  const int p = blockIdx.x;
+  const int p = WIDE ? blockIdx.y : blockIdx.x;
+  const int my_ch = WIDE ? blockIdx.x : 0;
   Td3Run r;
   if constexpr (GROUP) {
     r.my = td3_read_row(a.rows + p, a.rg.caps);
@@ -732,12 +818,22 @@ __global__ void __launch_bounds__(NT) td3_kernel(Td3Args a)
   r.caps = RNG ? my.caps != 0 : d.caps_noise != nullptr;
   r.max_grad_norm = d.max_grad_norm; r.invB = 1.0f / (float)B; r.invBA = 1.0f / (float)(B * A);
   float *td_loss = d.td_loss + (size_t)p * d.loss_stride, *pg_loss = d.pg_loss + (size_t)p * d.loss_stride;
-  float *wk = (float *)d.work + (size_t)p * a.work_floats;
+  float *wk = (float *)d.work + (WIDE ? (size_t)WIDE_SYNC_WORDS * d.n_learners : 0) + (size_t)p * a.work_floats;
   const int Pc = 2 * r.Pc1;
   int step_c = d.adam_steps[2 * p], step_a = d.adam_steps[2 * p + 1];
   int n_actor = 0;
   const int n_chunks = BIG ? (B + BP - 1) / BP : 1;
-  auto chunk = [&](int ch) {
+  // the wide flavours: this workgroup's chunk only; `spread`: the learner has more workgroups than this one, which is `lead` when it is
+  // workgroup 0; part: the chunks' partial vectors and loss terms behind the chunked flavours' workspace
+  const int ch0 = WIDE ? my_ch : 0, ch1 = WIDE ? my_ch + 1 : n_chunks;
+  const bool spread = WIDE && n_chunks > 1, lead = !WIDE || my_ch == 0;
+  const int gf = grad_floats(S, A, d.hidden, d.num_layers);
+  const int64_t part_stride = wide_chunk_floats(S, A, d.hidden, d.num_layers);
+  float *part = wk + gf + n_chunks * chunk_floats(d.hidden, d.num_layers);
+  float *my_part = part + my_ch * part_stride;
+  unsigned *sync = reinterpret_cast<unsigned *>(d.work) + WIDE_SYNC_WORDS * p;
+  unsigned arrivals = 0, epoch = 0;             // what workgroup 0 waits for next in sync[0], the others in sync[1]; sync[2]: the time-out word
+  auto chunk = [&](int ch, bool actor_phase) {
     Td3Chunk h;
     h.c = c;
     h.b0 = BIG ? ch * BP : 0;
@@ -745,7 +841,27 @@ __global__ void __launch_bounds__(NT) td3_kernel(Td3Args a)
     h.k = td3_carve(wk, S, A, d.hidden, d.num_layers, BIG ? ch : 0);
     h.on = h.b0 + c.b < B;
     h.accum = BIG && ch > 0;
+    h.g_caps = h.k.g; h.accum_caps = true;
+    if constexpr (WIDE) {
+      if (spread) { h.accum = false; h.k.g = my_part + (actor_phase ? gf : 0); h.g_caps = my_part + 2 * gf; h.accum_caps = false; }
+    }
     return h;
+  };
+  // hand-over `code` of a spread learner, towards workgroup 0 (in) or from it; -> false: a wait of the learner ran out of time, the
+  // status says so and the workgroup is done
+  auto handover = [&](bool in, unsigned code) {
+    unsigned lost = 0;
+    if (in) {
+      arrivals += n_chunks - 1;
+      if (lead) lost = td3_wait(c, sync, arrivals, sync + 2, code);
+      else td3_signal(c, sync, true, 0u);
+    } else {
+      ++epoch;
+      if (lead) td3_signal(c, sync + 1, false, epoch);
+      else lost = td3_wait(c, sync + 1, epoch, sync + 2, code);
+    }
+    if (lost && c.t == 0) a.status[p] = (int32_t)lost;
+    return lost == 0;
   };
 
   for (int u = 0; u < my.n_updates; ++u) {
@@ -755,28 +871,63 @@ __global__ void __launch_bounds__(NT) td3_kernel(Td3Args a)
       __syncthreads();
     }
     float td = 0.0f;
-    for (int ch = 0; ch < n_chunks; ++ch) {
-      const Td3Chunk h = chunk(ch);
+    for (int ch = ch0; ch < ch1; ++ch) {
+      const Td3Chunk h = chunk(ch, false);
       float rew, done;
       td3_gather<RNG>(r, h, u, rew, done);
       td3_target<MFMA, RNG>(r, h, u, iteration, rew, done);
-      td3_critic<MFMA>(r, h, td);
+      td3_critic<MFMA>(r, h, td, spread ? my_part + 3 * gf : nullptr);
+    }
+    if constexpr (WIDE) {
+      if (spread) {
+        if (!handover(true, TD3_HO_A)) return;
+        if (lead) {
+          td3_reduce(c, wk, part, nullptr, part_stride, n_chunks, Pc);
+          td = 0.0f;
+          for (int ch = 0; ch < n_chunks; ++ch) { td += part[ch * part_stride + 3 * gf]; td += part[ch * part_stride + 3 * gf + 1]; }
+        }
+      }
     }
     ++step_c;
-    clip_adam(c, r.wc, r.mc, r.vc, wk, Pc, step_c, my.lr, r.max_grad_norm);
-    if (c.t == 0) td_loss[u] = td;
-    if (iteration % my.policy_update_freq != 0) continue;
+    if (lead) {
+      clip_adam(c, r.wc, r.mc, r.vc, wk, Pc, step_c, my.lr, r.max_grad_norm);
+      if (c.t == 0) td_loss[u] = td;
+    }
+    const bool actor_step = iteration % my.policy_update_freq == 0;
+    if constexpr (WIDE) {
+      if (spread && (actor_step || u + 1 < my.n_updates) && !handover(false, TD3_HO_B)) return;
+    }
+    if (!actor_step) continue;
     float pg = 0.0f;
-    for (int ch = 0; ch < n_chunks; ++ch) {
-      const float chunk_pg = td3_actor<MFMA, RNG>(r, chunk(ch), iteration, n_actor);
-      pg = ch == 0 ? chunk_pg : pg + chunk_pg;
+    for (int ch = ch0; ch < ch1; ++ch) {
+      const float chunk_pg = td3_actor<MFMA, RNG>(r, chunk(ch, true), iteration, n_actor);
+      pg = ch == ch0 ? chunk_pg : pg + chunk_pg;
+    }
+    if constexpr (WIDE) {
+      if (spread) {
+        if (c.t == 0) my_part[3 * gf + 2] = pg;
+        if (!handover(true, TD3_HO_C)) return;
+        if (lead) {
+          td3_reduce(c, wk, part + gf, r.caps ? part + 2 * gf : nullptr, part_stride, n_chunks, r.Pa);
+          pg = part[3 * gf + 2];
+          for (int ch = 1; ch < n_chunks; ++ch) pg += part[ch * part_stride + 3 * gf + 2];
+        }
+      }
     }
     ++step_a; ++n_actor;
-    clip_adam(c, r.wa, r.ma, r.va, wk, r.Pa, step_a, my.lr, r.max_grad_norm);
-    if (c.t == 0) pg_loss[u] = pg;
-    td3_soft_updates(r, c.t);
+    if (lead) {
+      clip_adam(c, r.wa, r.ma, r.va, wk, r.Pa, step_a, my.lr, r.max_grad_norm);
+      if (c.t == 0) pg_loss[u] = pg;
+      td3_soft_updates(r, c.t);
+    }
+    if constexpr (WIDE) {
+      if (spread && u + 1 < my.n_updates && !handover(false, TD3_HO_D)) return;
+    }
   }
-  if (c.t == 0 && my.n_updates > 0) { d.adam_steps[2 * p] = step_c; d.adam_steps[2 * p + 1] = step_a; }
+  if (lead && c.t == 0 && my.n_updates > 0) {
+    d.adam_steps[2 * p] = step_c; d.adam_steps[2 * p + 1] = step_a;
+    if constexpr (WIDE) a.status[p] = 0;
+  }
 }
 
 // what serl_td3_train_rng draws, written out as the tables serl_td3_train takes: one workgroup of THREADS (BP; BIG_B for the chunked
@@ -825,26 +976,33 @@ bool td3_shape_ok(int S, int A, int H, int L, int B, int max_batch = BP)
 //              array is the report (serl_td3_train_group)
 // big (serl_td3_train_big; not with GROUP): the minibatch may have up to BIG_B rows, the workspace is that of serl_td3_big_work_bytes,
 // the chunked flavours are launched, and with GENERATOR rng->dense must name the flavour `mfma` asks for.
+// wide (serl_td3_train_wide; with big): the workspace is that of serl_td3_wide_work_bytes, the launch is refused when its workgroups
+// outnumber the device's CUs, the learners' synchronisation words are zeroed on the stream and the wide flavours are launched on a grid
+// (chunks, learners); `status` is the learners' report.
 enum Td3Source { TD3_TABLES, TD3_GENERATOR, TD3_GROUP };
 struct Td3Call {
   const char *fn;
   Td3Source source;
   const serl_td3_rng_desc *rng = nullptr;
   const serl_td3_group_desc *group = nullptr;
-  bool mfma = false, big = false;
+  bool mfma = false, big = false, wide = false;
+  int32_t *status = nullptr;
 };
 
-// the ten learner kernels by [big][group][rng][mfma]; a flavour that does not exist is NULL
+// the ten learner kernels of one workgroup per learner by [big][group][rng][mfma]; a flavour that does not exist is NULL
 typedef void (*Td3Kernel)(Td3Args);
 #define TD3_K(rng, group, big) {td3_kernel<false, rng, group, big>, td3_kernel<true, rng, group, big>}
 const Td3Kernel TD3_KERNELS[2][2][2][2] = {{{TD3_K(false, false, false), TD3_K(true, false, false)}, {{nullptr, nullptr}, TD3_K(true, true, false)}},
                                            {{TD3_K(false, false, true), TD3_K(true, false, true)}, {{nullptr, nullptr}, {nullptr, nullptr}}}};
 #undef TD3_K
+// the four wide kernels by [rng][mfma]
+const Td3Kernel TD3_WIDE_KERNELS[2][2] = {{td3_kernel<false, false, false, true, true>, td3_kernel<true, false, false, true, true>},
+                                          {td3_kernel<false, true, false, true, true>, td3_kernel<true, true, false, true, true>}};
 
-int td3_launch(Td3Kernel kernel, const Td3Args &a, size_t lds, void *stream)
+int td3_launch(Td3Kernel kernel, const Td3Args &a, size_t lds, void *stream, dim3 grid)
 {
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kernel, dim3(a.d.n_learners), dim3(NT), lds, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(kernel, grid, dim3(NT), lds, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return SERL_OK;
 }
@@ -879,9 +1037,12 @@ int td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream, const Td3Call &
     return serl_fail(SERL_E_INVALID, who + ": negative learner stride, or loss_stride < n_updates");
   Td3Args a = {};
   a.d = *d;
-  a.work_floats = td3_work_floats(d->state_dim, d->action_dim, d->hidden, d->num_layers, big ? (d->batch + BP - 1) / BP : 1);
-  if (d->work_bytes < (int64_t)d->n_learners * a.work_floats * (int64_t)sizeof(float))
-    return serl_fail(SERL_E_INVALID, who + ": workspace smaller than " + (big ? "serl_td3_big_work_bytes" : "serl_td3_work_bytes"));
+  const int chunks = big ? (d->batch + BP - 1) / BP : 1;
+  a.work_floats = td3_work_floats(d->state_dim, d->action_dim, d->hidden, d->num_layers, chunks) +
+                  (call.wide ? chunks * wide_chunk_floats(d->state_dim, d->action_dim, d->hidden, d->num_layers) : 0);
+  if (d->work_bytes < (int64_t)d->n_learners * (a.work_floats + (call.wide ? WIDE_SYNC_WORDS : 0)) * (int64_t)sizeof(float))
+    return serl_fail(SERL_E_INVALID, who + ": workspace smaller than " +
+                                         (call.wide ? "serl_td3_wide_work_bytes" : big ? "serl_td3_big_work_bytes" : "serl_td3_work_bytes"));
   const size_t lds = td3_lds_bytes(tables ? 0 : big ? BIG_B : BP);
   if (lds > (size_t)c->lds_per_block) return serl_fail(SERL_E_UNSUPPORTED, who + ": the activation tiles do not fit this device's LDS per workgroup");
   bool mfma = call.mfma;
@@ -903,9 +1064,17 @@ int td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream, const Td3Call &
     mfma = rg->dense == 1;
     a.rg = {rg->seed, rg->n_rows, rg->learner0, rg->caps};
   }
+  if (call.wide && (int64_t)d->n_learners * chunks > c->caps.num_cus)
+    return serl_fail(SERL_E_UNSUPPORTED, who + ": n_learners x chunks workgroups wait on each other and must all be resident: more than the device's CUs");
   if (d->n_updates == 0 && own) return SERL_OK;
   HIP_TRY(hipSetDevice(c->device));
-  return td3_launch(TD3_KERNELS[big][!own][!tables][mfma], a, lds, stream);
+  if (call.wide) {
+    // (one workgroup per CU by LDS size; a learner of one chunk polls nothing, but the block is zeroed all the same)
+    a.status = call.status;
+    HIP_TRY(hipMemsetAsync(d->work, 0, (size_t)d->n_learners * WIDE_SYNC_WORDS * sizeof(uint32_t), (hipStream_t)stream));
+    return td3_launch(TD3_WIDE_KERNELS[!tables][mfma], a, lds, stream, dim3(chunks, d->n_learners));
+  }
+  return td3_launch(TD3_KERNELS[big][!own][!tables][mfma], a, lds, stream, dim3(d->n_learners));
 }
 
 // serl_td3_rng_fill / _big: one set of checks, then the fill kernel of BP or BIG_B threads per update
@@ -1050,6 +1219,32 @@ int serl_td3_train_big(serl_ctx *c, const serl_td3_desc *d, const serl_td3_big_d
   if (bd->dense != 0 && bd->dense != 1) return serl_fail(SERL_E_INVALID, "serl_td3_train_big: dense must be 0 (valu) or 1 (mfma)");
   Td3Call call = {"serl_td3_train_big", bd->rng ? TD3_GENERATOR : TD3_TABLES, bd->rng};
   call.mfma = bd->dense == 1; call.big = true;
+  return td3_train(c, d, stream, call);
+}
+
+int64_t serl_td3_wide_work_bytes(int32_t n_learners, int32_t state_dim, int32_t action_dim, int32_t hidden, int32_t num_layers, int32_t batch)
+{
+  const int64_t big = serl_td3_big_work_bytes(n_learners, state_dim, action_dim, hidden, num_layers, batch);
+  if (big == 0) return 0;
+  const int chunks = (batch + BP - 1) / BP;
+  return big + (int64_t)n_learners * (chunks * wide_chunk_floats(state_dim, action_dim, hidden, num_layers) + WIDE_SYNC_WORDS) * (int64_t)sizeof(float);
+}
+
+int serl_td3_wide_layout(int32_t *out, int32_t capacity)
+{
+#define TD3_OFF(m) (int32_t)offsetof(serl_td3_wide_desc, m)
+  const int32_t v[] = {(int32_t)sizeof(serl_td3_wide_desc), TD3_OFF(rng), TD3_OFF(status), TD3_OFF(dense), TD3_OFF(pad0)};
+#undef TD3_OFF
+  return td3_layout_out(v, out, capacity);
+}
+
+int serl_td3_train_wide(serl_ctx *c, const serl_td3_desc *d, const serl_td3_wide_desc *wd, void *stream)
+{
+  if (!wd) return serl_fail(SERL_E_INVALID, "serl_td3_train_wide: NULL wide descriptor");
+  if (wd->dense != 0 && wd->dense != 1) return serl_fail(SERL_E_INVALID, "serl_td3_train_wide: dense must be 0 (valu) or 1 (mfma)");
+  if (!wd->status) return serl_fail(SERL_E_INVALID, "serl_td3_train_wide: NULL status");
+  Td3Call call = {"serl_td3_train_wide", wd->rng ? TD3_GENERATOR : TD3_TABLES, wd->rng};
+  call.mfma = wd->dense == 1; call.big = true; call.wide = true; call.status = wd->status;
   return td3_train(c, d, stream, call);
 }
 

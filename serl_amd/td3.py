@@ -40,6 +40,9 @@ DRAWS = ('host', 'device')
 # minibatches of more rows than serl_td3_train takes (up to 512) run on serl_td3_train_big when asked for by name -- fused=True,
 # dense='mfma' or draws='device'; last_path gains '-big' after the dense flavour.  fused=None keeps the eager loop for them.
 FUSED_MAX_BATCH = 128
+# train(chunks=...): 'serial' = as above (the default); 'parallel' = serl_td3_train_wide, the chunks of 128 samples of a minibatch of up to
+# 512 rows on workgroups of their own, bit for bit serl_td3_train_big's result; last_path 'fused-wide' / 'fused-mfma-wide' (+ '-rng').
+CHUNKS = ('serial', 'parallel')
 
 
 class _QNet(nn.Module):
@@ -126,10 +129,12 @@ ROWS = ('actor', 'actor_target', 'actor_m', 'actor_v', 'critic', 'critic_target'
 _NAN = {'PG_obj': float('nan'), 'TD_loss': float('nan')}
 
 
-def _names(dense, big=False, rng=False, group=False):
+def _names(dense, big=False, rng=False, group=False, wide=False):
     """-> (the library's entry point, what last_path reports) of a fused launch"""
-    entry = 'serl_td3_train_group' if group else 'serl_td3_train_big' if big else 'serl_td3_train_rng' if rng else DENSE[dense][0]
-    return entry, DENSE[dense][1] + ('-big' if big else '') + ('-group' if group else '') + ('-rng' if rng or group else '')
+    entry = ('serl_td3_train_group' if group else 'serl_td3_train_wide' if wide else 'serl_td3_train_big' if big else
+             'serl_td3_train_rng' if rng else DENSE[dense][0])
+    return entry, (DENSE[dense][1] + ('-wide' if wide else '-big' if big else '') + ('-group' if group else '') +
+                   ('-rng' if rng or group else ''))
 
 
 def _pack(learners, dev):
@@ -181,10 +186,10 @@ def _describe(args, n, rows, steps, td, pg, work, **per_launch):
                          work_bytes=work.numel() * work.element_size(), **per_launch)
 
 
-def _outputs(L, args, K, n, big, dev):
+def _outputs(L, args, K, n, big, dev, wide=False):
     """-> (td zeros [K, n], pg NaN [K, n], the workspace of the launch) on `dev`"""
-    wb = int((L.serl_td3_big_work_bytes if big else L.serl_td3_work_bytes)(K, args.state_dim, args.action_dim, args.hidden_size, args.num_layers,
-                                                                        int(args.batch_size)))
+    size = L.serl_td3_wide_work_bytes if wide else L.serl_td3_big_work_bytes if big else L.serl_td3_work_bytes
+    wb = int(size(K, args.state_dim, args.action_dim, args.hidden_size, args.num_layers, int(args.batch_size)))
     return (torch.zeros(K, n, dtype=torch.float32, device=dev), torch.full((K, n), float('nan'), dtype=torch.float32, device=dev),
             torch.empty(wb // 4, dtype=torch.float32, device=dev))
 
@@ -320,8 +325,13 @@ class TD3:
         """would serl_td3_train_big (minibatches of up to 512 rows, in chunks of 128) run this learner's shape on `device`?"""
         return self._supported(device, 'serl_td3_big_work_bytes')
 
+    def fused_wide_supported(self, device):
+        """would serl_td3_train_wide (minibatches of up to 512 rows, their chunks of 128 on parallel workgroups) run this learner's shape on
+        `device`?"""
+        return self._supported(device, 'serl_td3_wide_work_bytes')
+
     def train(self, replay, n_updates, *, iteration0, champion_target=False, rng=random, generator=None, fused=None, dense='valu',
-              draws='host', seed=None, learner=0):
+              draws='host', seed=None, learner=0, chunks='serial'):
         """n_updates consecutive updates on minibatches of args.batch_size rows of `replay` (a DeviceReplay), update u with iteration
         iteration0 + u + 1 -- the loop of Agent.train_rl.  -> {'PG_obj': mean(-pg), 'TD_loss': median(td)} like train_rl.
         fused: None = the fused kernel where it runs (FUSED_DEFAULT), False = the eager loop, True = the kernel or an error.
@@ -336,7 +346,18 @@ class TD3:
         kernel does not run a RuntimeError, all before anything is drawn.
         batch_size 129 .. 512: fused=True, dense='mfma' and draws='device' run serl_td3_train_big (last_path 'fused-big',
         'fused-mfma-big', 'fused-big-rng', 'fused-mfma-big-rng') where fused_big_supported, else they are the RuntimeError above;
-        fused=None stays the eager loop.  A refused fused=True is raised before anything is drawn too."""
+        fused=None stays the eager loop.  A refused fused=True is raised before anything is drawn too.
+        chunks: 'serial' = as above.  'parallel' = serl_td3_train_wide for every batch_size in 1 .. 512: the minibatch's chunks of 128
+        samples run on workgroups of their own and end bit for bit where serl_td3_train_big ends (include/serl_amd.h); with `dense` and
+        `draws` as above, last_path 'fused-wide', 'fused-mfma-wide', 'fused-wide-rng' or 'fused-mfma-wide-rng'.  The kernel or an
+        error, never the eager loop: an unknown `chunks`, or 'parallel' with fused=False, is a ValueError, a shape or device
+        serl_td3_wide_work_bytes refuses a RuntimeError, both before anything is drawn; a hand-over of the kernel that ran out of time
+        is a RuntimeError that names it, and nothing is copied back into the modules."""
+        if chunks not in CHUNKS:
+            raise ValueError('TD3.train: chunks=%r (one of %s)' % (chunks, ', '.join(repr(k) for k in CHUNKS)))
+        wide = chunks == 'parallel'
+        if wide and fused is not None and not fused:
+            raise ValueError("TD3.train: chunks='parallel' selects a fused kernel, fused=False the eager loop")
         if dense not in DENSE:
             raise ValueError('TD3.train: dense=%r (one of %s)' % (dense, ', '.join(repr(k) for k in DENSE)))
         if dense != 'valu' and fused is not None and not fused:
@@ -363,6 +384,8 @@ class TD3:
             raise ValueError('TD3.train: %d rows in the ring, minibatches of %d' % (len(replay), B))
         can = self.fused_supported(replay.device)
         big = B > FUSED_MAX_BATCH and self.fused_big_supported(replay.device)      # (then `can` is False)
+        if wide and not self.fused_wide_supported(replay.device):
+            raise RuntimeError("TD3.train(chunks='parallel'): serl_td3_train_wide does not run this shape / device")
         if dense != 'valu' and not (can or big):
             raise RuntimeError('TD3.train(dense=%r): %s does not run this shape / device' % (dense, DENSE[dense][0]))
         if draws == 'device':
@@ -371,14 +394,15 @@ class TD3:
             from . import _capi
             rd = _capi.Td3RngDesc(seed=seed, n_rows=len(replay), learner0=int(learner), dense=int(dense == 'mfma'),
                                   caps=int(self.caps_dict is not None))
-            return self._train_fused(replay, n_updates, int(iteration0), not champion_target, dense=dense, big=big, rng_desc=rd)
+            return self._train_fused(replay, n_updates, int(iteration0), not champion_target, dense=dense, big=big, wide=wide, rng_desc=rd)
         if fused and not (can or big):
             raise RuntimeError('TD3.train(fused=True): serl_td3_train does not run this shape / device')
         slots = _replay.sample_many(len(replay), B, n_updates, rng)
         tn, cn = draw_noise(n_updates, B, S, A, int(iteration0), int(a.policy_update_freq), self.caps_dict is not None, generator)
         use = (can and (dense != 'valu' or (FUSED_DEFAULT if fused is None else bool(fused)))) or (big and (dense != 'valu' or bool(fused)))
-        if use:
-            return self._train_fused(replay, n_updates, int(iteration0), not champion_target, dense=dense, big=big, tables=(slots, tn, cn))
+        if use or wide:
+            return self._train_fused(replay, n_updates, int(iteration0), not champion_target, dense=dense, big=big, wide=wide,
+                                     tables=(slots, tn, cn))
         td, pg = self._train_eager(replay, slots, tn, cn, int(iteration0), champion_target)
         self.last_path = 'eager'
         return _reduce(td, pg)
@@ -398,15 +422,16 @@ class TD3:
                 pg.append(float(pgl))
         return td, pg
 
-    def _train_fused(self, replay, n_updates, iteration0, update_actor_target, *, dense, big, tables=None, rng_desc=None):
-        """The K = 1 launch: n_updates updates with `dense` phases, on serl_td3_train_big when `big`, drawing from `tables` (slots, tn, cn of
-        the host) or inside the kernel with rng_desc (a _capi.Td3RngDesc; no table at all).  -> {'PG_obj', 'TD_loss'}"""
+    def _train_fused(self, replay, n_updates, iteration0, update_actor_target, *, dense, big, wide=False, tables=None, rng_desc=None):
+        """The K = 1 launch: n_updates updates with `dense` phases, on serl_td3_train_big when `big`, on serl_td3_train_wide when `wide`,
+        drawing from `tables` (slots, tn, cn of the host) or inside the kernel with rng_desc (a _capi.Td3RngDesc; no table at all).
+        -> {'PG_obj', 'TD_loss'}"""
         from . import _capi
         dev, L = replay.device, _capi.lib()
-        entry, path = _names(dense, big, rng=rng_desc is not None)
+        entry, path = _names(dense, big, rng=rng_desc is not None, wide=wide)
         t = lambda x: x.contiguous().to(dev)
         rows, steps = _pack([self], dev)
-        td, pg, work = _outputs(L, self.args, 1, n_updates, big, dev)
+        td, pg, work = _outputs(L, self.args, 1, n_updates, big, dev, wide)
         draws = {}
         if rng_desc is None:
             sl, tn, cn = tables
@@ -419,12 +444,20 @@ class TD3:
         d = _describe(self.args, n_updates, rows, steps, td, pg, work, ring=replay.rows.data_ptr(), **draws,
                       **_learner_fields(self, replay, iteration0, update_actor_target))
         args = [ctypes.byref(d)]
-        if big:
+        if wide:
+            status = torch.full((1,), -1, dtype=torch.int32, device=dev)
+            args.append(ctypes.byref(_capi.Td3WideDesc(rng=ctypes.pointer(rng_desc) if rng_desc is not None else None, status=status.data_ptr(),
+                                                       dense=int(dense == 'mfma'))))
+        elif big:
             args.append(ctypes.byref(_capi.Td3BigDesc(rng=ctypes.pointer(rng_desc) if rng_desc is not None else None, dense=int(dense == 'mfma'))))
         elif rng_desc is not None:
             args.append(ctypes.byref(rng_desc))
         _capi.check(getattr(L, entry)(self.engine.ctx, *args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), entry)
         torch.cuda.synchronize(dev)
+        if wide and int(status[0]) != 0:
+            s = int(status[0])
+            raise RuntimeError('TD3.train: serl_td3_train_wide gave up: %s ran out of time; the learner was not changed'
+                               % _capi.TD3_WIDE_STATUS.get(s, 'status %d' % s))
         _unpack(self, rows, steps.cpu().tolist(), 0)
         self.last_path = path
         return _reduce(td[0].cpu().numpy(), pg[0].cpu().numpy())

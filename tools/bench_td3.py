@@ -51,10 +51,11 @@ import torch
 ENTRY = {'valu': 'serl_td3_train', 'mfma': 'serl_td3_train_mfma'}
 
 
-def fused_run(engine, d, n, dense='valu', rows_out=None, rng_seed=None, big=False):
+def fused_run(engine, d, n, dense='valu', rows_out=None, rng_seed=None, big=False, wide=False):
     """-> (device ms, wall ms) of one launch of n updates of serl_td3_train (dense='mfma': serl_td3_train_mfma) on fresh copies of the
     case's rows; with rows_out (a dict) the four rows after the launch are left in it.  With rng_seed the launch is serl_td3_train_rng
-    with that seed, slots from all rows of the case's ring, and no table is uploaded.  big: serl_td3_train_big (tables) instead."""
+    with that seed, slots from all rows of the case's ring, and no table is uploaded.  big: serl_td3_train_big (tables) instead; wide: serl_td3_train_wide
+    (tables), its status checked."""
     import td3_64 as T
     from serl_amd import _capi
     L = _capi.lib()
@@ -70,7 +71,8 @@ def fused_run(engine, d, n, dense='valu', rows_out=None, rng_seed=None, big=Fals
         slots, tn = t(d['slots'][:n]), t(d['tn'][:n])
         cn = t(d['cn']) if d['caps'] else None
     td, pg = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
-    wb = int((L.serl_td3_big_work_bytes if big else L.serl_td3_work_bytes)(1, d['S'], d['A'], d['H'], d['L'], d['B']))
+    wb = int((L.serl_td3_wide_work_bytes if wide else L.serl_td3_big_work_bytes if big else L.serl_td3_work_bytes)(1, d['S'], d['A'], d['H'], d['L'], d['B']))
+    status = torch.full((1,), -1, dtype=torch.int32, device=dev)
     work = torch.empty(wb // 4, dtype=torch.float32, device=dev)
     desc = _capi.Td3Desc(state_dim=d['S'], action_dim=d['A'], hidden=d['H'], num_layers=d['L'], activation={'tanh': 0, 'elu': 1, 'relu': 2}[d['act']],
                          n_learners=1, batch=d['B'], n_updates=n, capacity=ring.shape[0], slot_cols=d['B'], policy_update_freq=d['freq'],
@@ -89,7 +91,10 @@ def fused_run(engine, d, n, dense='valu', rows_out=None, rng_seed=None, big=Fals
     w0 = time.perf_counter()
     e0.record()
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    if big:
+    if wide:
+        wd = _capi.Td3WideDesc(rng=None, status=status.data_ptr(), dense=int(dense == 'mfma'))
+        _capi.check(L.serl_td3_train_wide(engine.ctx, ctypes.byref(desc), ctypes.byref(wd), stream), 'serl_td3_train_wide')
+    elif big:
         bd = _capi.Td3BigDesc(rng=None, dense=int(dense == 'mfma'))
         _capi.check(L.serl_td3_train_big(engine.ctx, ctypes.byref(desc), ctypes.byref(bd), stream), 'serl_td3_train_big')
     elif rng_seed is None:
@@ -100,7 +105,7 @@ def fused_run(engine, d, n, dense='valu', rows_out=None, rng_seed=None, big=Fals
     e1.record()
     torch.cuda.synchronize()
     wall = (time.perf_counter() - w0) * 1e3
-    assert torch.isfinite(td).all()
+    assert torch.isfinite(td).all() and (not wide or int(status[0]) == 0), status
     if rows_out is not None:
         rows_out.update({k: rows[k].cpu().numpy() for k in T.ROWS}, td=td.cpu().numpy())
     return e0.elapsed_time(e1), wall
@@ -126,6 +131,8 @@ def main():
     ap.add_argument('--hidden', type=int, nargs='*', default=None, help='default: 72 32 96; with --draws 72')
     ap.add_argument('--layers', type=int, default=3)
     ap.add_argument('--batch', default='86', help="a minibatch size; a list 'B1,B2,...' times serl_td3_train_big at each (see above)")
+    ap.add_argument('--chunks', default=None, help="'serial,parallel' with a --batch list: serl_td3_train_big against serl_td3_train_wide at each size "
+                                                   '(-> profiles/td3_wide_timing.json)')
     ap.add_argument('--updates', type=int, default=2000)
     ap.add_argument('--eager-updates', type=int, default=300, help='updates of one eager repetition (the loop is slow; ms per update is what is compared)')
     ap.add_argument('--reps', type=int, default=5)
@@ -144,10 +151,13 @@ def main():
     if a.hidden is None:
         a.hidden = [72] if a.draws or a.group or batches else [72, 32, 96]
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'td3_batch_timing.json' if batches else 'td3_group_timing.json' if a.group else 'td3_rng_timing.json' if a.draws else 'td3_mfma_timing.json' if a.dense else 'td3_fused_timing.json')
+        a.out = os.path.join(ROOT, 'profiles', 'td3_wide_timing.json' if a.chunks else 'td3_batch_timing.json' if batches else 'td3_group_timing.json' if a.group else 'td3_rng_timing.json' if a.draws else 'td3_mfma_timing.json' if a.dense else 'td3_fused_timing.json')
     import serl_amd
     import td3_64 as T
     engine = serl_amd.RolloutEngine(0)
+    if a.chunks:
+        assert batches and sorted(a.chunks.split(',')) == ['parallel', 'serial'], '--chunks serial,parallel needs a --batch list'
+        return chunks_main(a, engine, batches)
     if batches:
         return batch_main(a, engine, batches)
     if a.group:
@@ -245,6 +255,52 @@ def batch_main(a, engine, batches):
             r['eager_f32_ms_per_update_wall']['median'], r['rows_equal']), flush=True)
         with open(a.out, 'w') as fh:
             json.dump(res, fh, indent=1)
+    print(json.dumps(res))
+
+
+def chunks_main(a, engine, batches):
+    """the protocol of batch_main without the eager loop: at each size serl_td3_train_big (serial) and serl_td3_train_wide (parallel) in
+    both dense flavours, and serl_td3_train / _mfma where they run, alternating in one process, final rows compared"""
+    import td3_big as TB
+    from serl_amd import _capi, build as hip_build
+    H = a.hidden[0]
+    res = {'tool': 'bench_td3 --batch %s --chunks serial,parallel' % ','.join(str(b) for b in batches), 'device': torch.cuda.get_device_name(0),
+           'source_hash': hip_build.source_hash(), 'hidden': H, 'layers': a.layers, 'updates': a.updates, 'reps': a.reps, 'caps': True,
+           'policy_update_freq': 2, 'activation': 'tanh', 'ring_rows': TB.RING_ROWS, 'batches': {}}
+    for B in batches:
+        d = TB.make_case((7, 3, H, a.layers, 'tanh', B, 2, 0, a.updates, 1, 1, 'small'), seed=H)
+        runs = ([('serial_' + f, dict(dense=f, big=True)) for f in ENTRY] + [('parallel_' + f, dict(dense=f, wide=True)) for f in ENTRY] +
+                ([(f, dict(dense=f)) for f in ENTRY] if B <= 128 else []))
+        rows = {k: {} for k, _ in runs}
+        for _, kw in runs:
+            fused_run(engine, d, min(a.updates, 50), **kw)              # warm-up
+        ms = {k: [] for k, _ in runs}
+        for _ in range(a.reps):                                         # alternating: a drift of the clock hits all alike
+            for k, kw in runs:
+                ms[k].append(fused_run(engine, d, a.updates, rows_out=rows[k], **kw)[0] / a.updates)
+        r = {k + '_ms_per_update_device': spread(ms[k]) for k in ms}
+        r['rows_equal'] = bool(all(np.array_equal(rows[k][x], rows['serial_valu'][x]) for k in rows for x in rows[k]))
+        for f in ENTRY:
+            s_, p_ = r['serial_%s_ms_per_update_device' % f], r['parallel_%s_ms_per_update_device' % f]
+            r['serial_%s_us_per_sample' % f], r['parallel_%s_us_per_sample' % f] = 1e3 * s_['median'] / B, 1e3 * p_['median'] / B
+            r['serial_over_parallel_%s_median' % f] = s_['median'] / p_['median']
+            r['parallel_%s_median_below_serial_min' % f] = bool(p_['median'] < s_['min'])
+            if B <= 128:
+                o = r[f + '_ms_per_update_device']
+                r['parallel_%s_median_inside_old_spread' % f] = bool(o['min'] <= p_['median'] <= o['max'])
+        r['work_bytes'] = int(_capi.lib().serl_td3_wide_work_bytes(1, 7, 3, H, a.layers, B))
+        res['batches']['B%d' % B] = r
+        print('B %d  %s  rows equal: %s' % (B, '  '.join('%s %.4f [%.4f .. %.4f]' % (
+            k, r[k + '_ms_per_update_device']['median'], r[k + '_ms_per_update_device']['min'], r[k + '_ms_per_update_device']['max']) for k in ms),
+            r['rows_equal']), flush=True)
+    # the hand-over cost per update, as a DIFFERENCE of two timings of this run (no counter): wide at the largest size minus the 128-row time
+    if 'B128' in res['batches'] and len(batches) > 1:
+        big_b = 'B%d' % max(batches)
+        for f in ENTRY:
+            res['handover_ms_per_update_%s_%s_minus_B128' % (f, big_b)] = (
+                res['batches'][big_b]['parallel_%s_ms_per_update_device' % f]['median'] - res['batches']['B128']['parallel_%s_ms_per_update_device' % f]['median'])
+    with open(a.out, 'w') as fh:
+        json.dump(res, fh, indent=1)
     print(json.dumps(res))
 
 
