@@ -836,7 +836,13 @@ enum serl_td3_row_status {
   SERL_TD3_ROW_ITERATION = 3,       /* iteration0 < 0, or iteration0 + n_updates overflows */
   SERL_TD3_ROW_ROWS = 4,            /* n_rows < batch or n_rows > capacity */
   SERL_TD3_ROW_FREQ = 5,            /* policy_update_freq < 1 */
-  SERL_TD3_ROW_HYPER = 6            /* lr <= 0, gamma < 0, tau outside [0, 1], noise_sd / noise_clip / eps_sd < 0, or a NaN */
+  SERL_TD3_ROW_HYPER = 6,           /* lr <= 0, gamma < 0, tau outside [0, 1], noise_sd / noise_clip / eps_sd < 0, or a NaN */
+  /* serl_td3_train_group_wide only: the row passed its checks, then a wait of the learner's hand-over A .. D ran out of time
+   * (16 + enum serl_td3_wide_status, so that the one status word tells the two kinds of report apart) */
+  SERL_TD3_ROW_HANDOVER_A = 17,
+  SERL_TD3_ROW_HANDOVER_B = 18,
+  SERL_TD3_ROW_HANDOVER_C = 19,
+  SERL_TD3_ROW_HANDOVER_D = 20
 };
 typedef struct serl_td3_group_desc {
   const serl_td3_learner_row *rows; /* DEVICE [n_learners] */
@@ -943,6 +949,40 @@ int64_t serl_td3_wide_work_bytes(int32_t n_learners, int32_t state_dim, int32_t 
  * serl_td3_wide_work_bytes); then SERL_E_UNSUPPORTED when n_learners * G exceeds the device's CU count (the workgroups wait on each
  * other, so all must be resident: one per CU by LDS size); all before any device work.  n_updates == 0 leaves every buffer unchanged. */
 int serl_td3_train_wide(serl_ctx *ctx, const serl_td3_desc *desc, const serl_td3_wide_desc *wide, void *stream);
+
+/* ---- a group of independent TD3 learners on minibatches of up to 512 rows, chunks serial or parallel (SERL_ABI_VERSION stays 9: two new
+ * symbols and four enumerators, no struct added or moved) -------------------------------------------------------------------------------
+ * serl_td3_train_group is compiled for batch 1 .. 128.  These two take its descriptors -- the same serl_td3_desc with everything a row
+ * holds ignored, the same serl_td3_group_desc and serl_td3_learner_row -- with batch 1 .. 512, G = ceil(batch / 128) chunks:
+ *   serl_td3_train_group_big    one workgroup per learner that walks the chunks one after the other, as serl_td3_train_big does;
+ *                               workspace serl_td3_big_work_bytes(n_learners, ...), laid out per learner as that entry lays it out.
+ *   serl_td3_train_group_wide   a grid of G x n_learners workgroups, workgroup (ch, p) on chunk ch of learner p with serl_td3_train_wide's
+ *                               hand-overs inside the learner; workspace serl_td3_wide_work_bytes(n_learners, ...): the 16-byte
+ *                               synchronisation blocks of all learners first (zeroed on the stream before the launch), then per learner
+ *                               what serl_td3_train_wide lays out.
+ * Further instantiations of the one kernel source.  No workgroup of one learner ever waits on a workgroup of another, and there is no
+ * grid-wide synchronisation.
+ * Rows and status.  Every workgroup of learner p reads rows[p] and checks it itself before it touches any other memory; the check is a
+ * function of the row and the descriptor alone, so the G workgroups of a learner agree without talking.  A refused learner's workgroups
+ * all return at once: they write nothing, the synchronisation words included, and none of them is ever waited for; workgroup (0, p) alone
+ * writes status[p].  The learners of a launch run their own rows' n_updates, 0 included: every hand-over of a learner is decided from its
+ * own row's count (B is left out when nothing follows, D behind ITS last update), so all its workgroups leave behind the same hand-over;
+ * a learner with n_updates == 0 makes none and leaves everything but its status unchanged, adam_steps too.
+ * status[p] (enum serl_td3_row_status): 0 = the row was accepted and the learner ran to its end; 1 .. 6 = the first failed check, nothing
+ * of the learner written; SERL_TD3_ROW_HANDOVER_A .. _D (serl_td3_train_group_wide only) = the row was accepted, then a wait of that
+ * hand-over ran out of serl_td3_train_wide's bounded spin: that learner's rows are unfinished, the others are not affected.
+ * Contract: every array learner p writes -- its four rows, its four moment rows, its adam_steps pair, td_loss[p], pg_loss[p] -- equals,
+ * bit for bit, what a single-learner serl_td3_train_big call (for serl_td3_train_group_wide: serl_td3_train_wide) writes whose
+ * descriptor holds the row's ring, capacity, n_updates, iteration0, policy_update_freq, update_actor_target and hyper-parameters and
+ * whose rng = {seed, n_rows, learner0 = key, dense, caps}.  Through the contracts of those two it is also what the other of the two
+ * writes, and with batch <= 128 what serl_td3_train_group writes.  A learner's result depends neither on the other learners nor on its
+ * place in the grid.
+ * Asynchronous on `stream`; the launch is made for desc->n_updates == 0 too (the status array is the report).  The checks are
+ * serl_td3_train_group's in its order with its codes, with batch up to 512 (513: SERL_E_UNSUPPORTED) and the workspaces above; then, for
+ * serl_td3_train_group_wide, SERL_E_UNSUPPORTED when n_learners * G exceeds the device's CU count (the workgroups of a learner wait on
+ * each other, so all must be resident); all with nothing launched.  serl_last_error() names the entry. */
+int serl_td3_train_group_big(serl_ctx *ctx, const serl_td3_desc *desc, const serl_td3_group_desc *group, void *stream);
+int serl_td3_train_group_wide(serl_ctx *ctx, const serl_td3_desc *desc, const serl_td3_group_desc *group, void *stream);
 
 /* ---- the launch planner on the host (SERL_ABI_VERSION stays 9: new symbols only) --------------------------------------------------
  * WHAT serl_rollout / serl_rollout_noise (noise != 0) would launch for `desc` on a device of caps[0] CUs: the library's own decision

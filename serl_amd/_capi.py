@@ -25,7 +25,8 @@ EXPORTS = ['serl_abi_version', 'serl_last_error', 'serl_param_count', 'serl_ctx_
            'serl_host_plan_rollout', 'serl_host_plan_dyn', 'serl_host_plan_multi',
            'serl_td3_train_group', 'serl_td3_group_layout',
            'serl_td3_train_big', 'serl_td3_big_layout', 'serl_td3_big_work_bytes', 'serl_td3_rng_fill_big',
-           'serl_td3_train_wide', 'serl_td3_wide_layout', 'serl_td3_wide_work_bytes']
+           'serl_td3_train_wide', 'serl_td3_wide_layout', 'serl_td3_wide_work_bytes',
+           'serl_td3_train_group_big', 'serl_td3_train_group_wide']
 
 
 class BuildDesc(ctypes.Structure):
@@ -197,6 +198,10 @@ TD3_WIDE_STATUS = {0: 'ran', 1: 'hand-over A (critic partials to workgroup 0)', 
 # enum serl_td3_row_status: what a workgroup of serl_td3_train_group writes to status[p]
 TD3_ROW_STATUS = {0: 'ok', 1: 'ring is NULL', 2: 'n_updates < 0 or above the launch\'s', 3: 'iteration0 < 0 or iteration0 + n_updates overflows',
                   4: 'n_rows < batch or n_rows > capacity', 5: 'policy_update_freq < 1', 6: 'a hyper-parameter out of range or NaN'}
+# SERL_TD3_ROW_HANDOVER_A .. _D (serl_td3_train_group_wide): the row was accepted, then a wait of the learner's hand-over ran out of time
+TD3_ROW_HANDOVER0 = 16
+TD3_ROW_TIMEOUTS = tuple(TD3_ROW_HANDOVER0 + s for s in sorted(TD3_WIDE_STATUS) if s)
+TD3_ROW_STATUS.update({TD3_ROW_HANDOVER0 + s: what + ' ran out of time' for s, what in TD3_WIDE_STATUS.items() if s})
 
 
 # serl_rollout_desc.kernel_hint (enum serl_kernel_hint)
@@ -302,6 +307,8 @@ def lib():
     L.serl_td3_wide_layout.argtypes = [VP, ctypes.c_int32]
     L.serl_td3_wide_work_bytes.argtypes = [i32] * 6
     L.serl_td3_train_wide.argtypes = [VP, ctypes.POINTER(Td3Desc), ctypes.POINTER(Td3WideDesc), VP]
+    L.serl_td3_train_group_big.argtypes = L.serl_td3_train_group.argtypes
+    L.serl_td3_train_group_wide.argtypes = L.serl_td3_train_group.argtypes
     L.serl_host_plan_rollout.argtypes = [_I, ctypes.POINTER(RolloutDesc), i32, _I]
     L.serl_host_plan_dyn.argtypes = [_I, i32, i32, i32, _I]
     L.serl_host_plan_multi.argtypes = [i32, i32, _I, i32, _I, _I, _I]

@@ -756,7 +756,7 @@ __device__ __forceinline__ void td3_reduce(const Ctx &c, float *g, const float *
 // The learner kernel, one workgroup per learner, every flavour an instantiation of this one update.
 // RNG = false: slots and draws from the caller's tables (serl_td3_train / _mfma).  RNG = true: the same source, with the slot read from
 // an LDS array one wavefront fills at the top of each update and both draws generated in registers by the thread that would read them.
-// GROUP = true (with RNG; serl_td3_train_group): the same source again, with what is one value per launch elsewhere -- the ring, the
+// GROUP = true (with RNG; serl_td3_train_group, with BIG / WIDE _group_big / _group_wide): the same source again, with what is one value per launch elsewhere -- the ring, the
 // counts, the hyper-parameters, the generator's seed and key -- taken from the learner's row, which the workgroup reads and checks
 // itself before it touches any other memory.
 // BIG = true (the chunked flavours, serl_td3_train_big): minibatches of up to BIG_B rows, walked in chunks of BP samples (the last one
@@ -773,13 +773,17 @@ __device__ __forceinline__ void td3_reduce(const Ctx &c, float *g, const float *
 //   C  (actor updates) the actor partials and pg terms -> workgroup 0       D  the stepped actor and the targets -> every workgroup
 // B is left out when nothing follows it (no actor step, last update), D behind the last update.  A minibatch of one chunk runs as the
 // chunked flavour does, with no hand-over at all.
+// In a group (GROUP with WIDE) status[p] is the row check's word too, so a time-out is reported with a code above the check's
+// (SERL_TD3_ROW_HANDOVER_A ..); every condition above is decided from the learner's own row, so that all workgroups of a learner leave
+// the loop behind the same hand-over, and a learner with no updates makes none.
 enum Td3Handover { TD3_HO_A = SERL_TD3_WIDE_A, TD3_HO_B = SERL_TD3_WIDE_B, TD3_HO_C = SERL_TD3_WIDE_C, TD3_HO_D = SERL_TD3_WIDE_D };
+static_assert(SERL_TD3_ROW_HANDOVER_B - SERL_TD3_ROW_HANDOVER_A == TD3_HO_B - TD3_HO_A && SERL_TD3_ROW_HANDOVER_C - SERL_TD3_ROW_HANDOVER_A == TD3_HO_C - TD3_HO_A &&
+              SERL_TD3_ROW_HANDOVER_D - SERL_TD3_ROW_HANDOVER_A == TD3_HO_D - TD3_HO_A, "a group's time-out codes follow the single learner's, offset");
 
 template <bool MFMA, bool RNG, bool GROUP, bool BIG, bool WIDE = false>
 __global__ void __launch_bounds__(NT) td3_kernel(Td3Args a)
 {
   static_assert(RNG || !GROUP, "the group flavours draw inside the kernel");
-  static_assert(!(GROUP && BIG), "groups run minibatches of up to BP rows");
   static_assert(BIG || !WIDE, "the wide flavours are chunked ones");
   extern __shared__ float lds[];
   const serl_td3_desc &d = a.d;
@@ -789,7 +793,8 @@ __global__ void __launch_bounds__(NT) td3_kernel(Td3Args a)
   if constexpr (GROUP) {
     r.my = td3_read_row(a.rows + p, a.rg.caps);
     const int refused = td3_check_row(r.my, d.batch, d.n_updates);
-    if (threadIdx.x == 0) a.status[p] = refused;
+    // (a wide group: all workgroups of the learner read the same row and decide alike without talking; the lead reports)
+    if (threadIdx.x == 0 && my_ch == 0) a.status[p] = refused;
     if (refused != SERL_TD3_ROW_OK) return;
   } else {
     r.my = td3_read_desc(d, a.rg, p);
@@ -850,6 +855,7 @@ __global__ void __launch_bounds__(NT) td3_kernel(Td3Args a)
   // hand-over `code` of a spread learner, towards workgroup 0 (in) or from it; -> false: a wait of the learner ran out of time, the
   // status says so and the workgroup is done
   auto handover = [&](bool in, unsigned code) {
+    if constexpr (GROUP) code += SERL_TD3_ROW_HANDOVER_A - TD3_HO_A;
     unsigned lost = 0;
     if (in) {
       arrivals += n_chunks - 1;
@@ -926,7 +932,7 @@ __global__ void __launch_bounds__(NT) td3_kernel(Td3Args a)
   }
   if (lead && c.t == 0 && my.n_updates > 0) {
     d.adam_steps[2 * p] = step_c; d.adam_steps[2 * p + 1] = step_a;
-    if constexpr (WIDE) a.status[p] = 0;
+    if constexpr (WIDE && !GROUP) a.status[p] = 0;      // (a group's status is the row check's, written at the top)
   }
 }
 
@@ -974,11 +980,11 @@ bool td3_shape_ok(int S, int A, int H, int L, int B, int max_batch = BP)
 //              update_actor_target and the eight hyper-parameters -- is not looked at either: the row's workgroup checks it
 //              (td3_check_row); `group` takes the generator's place, and the launch is made for n_updates == 0 too, since the status
 //              array is the report (serl_td3_train_group)
-// big (serl_td3_train_big; not with GROUP): the minibatch may have up to BIG_B rows, the workspace is that of serl_td3_big_work_bytes,
+// big (serl_td3_train_big; with GROUP serl_td3_train_group_big): the minibatch may have up to BIG_B rows, the workspace is that of serl_td3_big_work_bytes,
 // the chunked flavours are launched, and with GENERATOR rng->dense must name the flavour `mfma` asks for.
-// wide (serl_td3_train_wide; with big): the workspace is that of serl_td3_wide_work_bytes, the launch is refused when its workgroups
+// wide (serl_td3_train_wide; with GROUP serl_td3_train_group_wide; with big): the workspace is that of serl_td3_wide_work_bytes, the launch is refused when its workgroups
 // outnumber the device's CUs, the learners' synchronisation words are zeroed on the stream and the wide flavours are launched on a grid
-// (chunks, learners); `status` is the learners' report.
+// (chunks, learners); `status` is the learners' report (a group's is its descriptor's, which the row checks write too).
 enum Td3Source { TD3_TABLES, TD3_GENERATOR, TD3_GROUP };
 struct Td3Call {
   const char *fn;
@@ -989,15 +995,17 @@ struct Td3Call {
   int32_t *status = nullptr;
 };
 
-// the ten learner kernels of one workgroup per learner by [big][group][rng][mfma]; a flavour that does not exist is NULL
+// the twelve learner kernels of one workgroup per learner by [big][group][rng][mfma]; a flavour that does not exist is NULL (a group
+// draws inside the kernel)
 typedef void (*Td3Kernel)(Td3Args);
 #define TD3_K(rng, group, big) {td3_kernel<false, rng, group, big>, td3_kernel<true, rng, group, big>}
 const Td3Kernel TD3_KERNELS[2][2][2][2] = {{{TD3_K(false, false, false), TD3_K(true, false, false)}, {{nullptr, nullptr}, TD3_K(true, true, false)}},
-                                           {{TD3_K(false, false, true), TD3_K(true, false, true)}, {{nullptr, nullptr}, {nullptr, nullptr}}}};
+                                           {{TD3_K(false, false, true), TD3_K(true, false, true)}, {{nullptr, nullptr}, TD3_K(true, true, true)}}};
 #undef TD3_K
-// the four wide kernels by [rng][mfma]
-const Td3Kernel TD3_WIDE_KERNELS[2][2] = {{td3_kernel<false, false, false, true, true>, td3_kernel<true, false, false, true, true>},
-                                          {td3_kernel<false, true, false, true, true>, td3_kernel<true, true, false, true, true>}};
+// the six wide kernels by [group][rng][mfma]
+const Td3Kernel TD3_WIDE_KERNELS[2][2][2] = {{{td3_kernel<false, false, false, true, true>, td3_kernel<true, false, false, true, true>},
+                                              {td3_kernel<false, true, false, true, true>, td3_kernel<true, true, false, true, true>}},
+                                             {{nullptr, nullptr}, {td3_kernel<false, true, true, true, true>, td3_kernel<true, true, true, true, true>}}};
 
 int td3_launch(Td3Kernel kernel, const Td3Args &a, size_t lds, void *stream, dim3 grid)
 {
@@ -1070,9 +1078,9 @@ int td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream, const Td3Call &
   HIP_TRY(hipSetDevice(c->device));
   if (call.wide) {
     // (one workgroup per CU by LDS size; a learner of one chunk polls nothing, but the block is zeroed all the same)
-    a.status = call.status;
+    if (own) a.status = call.status;
     HIP_TRY(hipMemsetAsync(d->work, 0, (size_t)d->n_learners * WIDE_SYNC_WORDS * sizeof(uint32_t), (hipStream_t)stream));
-    return td3_launch(TD3_WIDE_KERNELS[!tables][mfma], a, lds, stream, dim3(chunks, d->n_learners));
+    return td3_launch(TD3_WIDE_KERNELS[!own][!tables][mfma], a, lds, stream, dim3(chunks, d->n_learners));
   }
   return td3_launch(TD3_KERNELS[big][!own][!tables][mfma], a, lds, stream, dim3(d->n_learners));
 }
@@ -1181,6 +1189,20 @@ int serl_td3_group_layout(int32_t *out, int32_t capacity)
 int serl_td3_train_group(serl_ctx *c, const serl_td3_desc *d, const serl_td3_group_desc *gd, void *stream)
 {
   return td3_train(c, d, stream, {"serl_td3_train_group", TD3_GROUP, nullptr, gd});
+}
+
+int serl_td3_train_group_big(serl_ctx *c, const serl_td3_desc *d, const serl_td3_group_desc *gd, void *stream)
+{
+  Td3Call call = {"serl_td3_train_group_big", TD3_GROUP, nullptr, gd};
+  call.big = true;
+  return td3_train(c, d, stream, call);
+}
+
+int serl_td3_train_group_wide(serl_ctx *c, const serl_td3_desc *d, const serl_td3_group_desc *gd, void *stream)
+{
+  Td3Call call = {"serl_td3_train_group_wide", TD3_GROUP, nullptr, gd};
+  call.big = true; call.wide = true;
+  return td3_train(c, d, stream, call);
 }
 
 int serl_td3_rng_fill(serl_ctx *c, const serl_td3_rng_desc *rg, int32_t learner, int32_t state_dim, int32_t action_dim, int32_t batch,

@@ -13,7 +13,9 @@ draws out as tables (serl_td3_rng_fill) for a replay on the table path.
 
 `TD3Group(learners).train(replays, n_updates, iteration0=..., seed=...)` runs the updates of several independent learners of one network
 shape -- seeds, hyper-parameter settings -- as ONE launch (serl_td3_train_group), each learner where its own train(draws='device') would
-put it.
+put it.  Minibatches of 129 .. 512 rows run on serl_td3_train_group_big, one workgroup per learner walking the chunks of 128 samples, and
+`chunks='parallel'` puts every chunk of every learner on a workgroup of its own (serl_td3_train_group_wide), as TD3.train's `chunks` does
+for one learner.
 """
 import ctypes
 import random
@@ -131,8 +133,8 @@ _NAN = {'PG_obj': float('nan'), 'TD_loss': float('nan')}
 
 def _names(dense, big=False, rng=False, group=False, wide=False):
     """-> (the library's entry point, what last_path reports) of a fused launch"""
-    entry = ('serl_td3_train_group' if group else 'serl_td3_train_wide' if wide else 'serl_td3_train_big' if big else
-             'serl_td3_train_rng' if rng else DENSE[dense][0])
+    entry = (('serl_td3_train_group_wide' if wide else 'serl_td3_train_group_big' if big else 'serl_td3_train_group') if group else
+             'serl_td3_train_wide' if wide else 'serl_td3_train_big' if big else 'serl_td3_train_rng' if rng else DENSE[dense][0])
     return entry, (DENSE[dense][1] + ('-wide' if wide else '-big' if big else '') + ('-group' if group else '') +
                    ('-rng' if rng or group else ''))
 
@@ -470,8 +472,10 @@ GROUP_SHARED = ('state_dim', 'action_dim', 'hidden_size', 'num_layers', 'activat
 class TD3Group:
     """K independent `TD3` learners of one network shape -- several seeds, a few hyper-parameter settings -- whose generations' updates run
     as ONE launch (serl_td3_train_group, include/serl_amd.h): one workgroup per learner, each with its own ring, fill, update count,
-    iteration, seed, key and hyper-parameters.  Every learner ends bit for bit where its own
-    `TD3.train(replay, n, iteration0=..., draws='device', seed=..., learner=key, dense=...)` would have put it."""
+    iteration, seed, key and hyper-parameters.  batch_size 1 .. 512: above 128 rows the launch is serl_td3_train_group_big (chunks of 128
+    samples, one after the other on the learner's workgroup), and train(chunks='parallel') is serl_td3_train_group_wide at every
+    batch_size (K x ceil(batch_size / 128) workgroups, which must not outnumber the device's CUs).  Every learner ends bit for bit where
+    its own `TD3.train(replay, n, iteration0=..., draws='device', seed=..., learner=key, dense=..., chunks=...)` would have put it."""
 
     def __init__(self, learners):
         learners = list(learners)
@@ -507,16 +511,26 @@ class TD3Group:
             raise ValueError('TD3Group.train: %d values of %s for %d learners' % (len(v), what, K))
         return list(v)
 
-    def train(self, replays, n_updates, *, iteration0, seed, key=None, champion_target=False, dense='valu'):
+    def train(self, replays, n_updates, *, iteration0, seed, key=None, champion_target=False, dense='valu', chunks='serial'):
         """Learner i runs n_updates[i] updates on minibatches of the first len(replays[i]) rows of its ring from iteration0[i] on, with the
         in-kernel draws of (seed[i], key[i]) -- `key` defaults to the learner's index -- and its own args / caps_dict.  n_updates,
         iteration0, seed, key and champion_target are scalars (for all) or sequences of one value per learner.
         -> a list of {'PG_obj', 'TD_loss'} like TD3.train's (NaN for a learner with no updates).  Everything is checked on the host
-        before any device work (ValueError); it is the kernel or a RuntimeError, never the eager loop; one launch, one synchronisation."""
+        before any device work (ValueError); it is the kernel or a RuntimeError, never the eager loop; one launch, one synchronisation.
+        chunks: 'serial' (the default) = one workgroup per learner: serl_td3_train_group up to batch_size 128 (last_path
+        'fused-group-rng' / 'fused-mfma-group-rng'), serl_td3_train_group_big for 129 .. 512 where every learner's fused_big_supported
+        ('fused-big-group-rng' / 'fused-mfma-big-group-rng').  'parallel' = serl_td3_train_group_wide for every batch_size in 1 .. 512
+        where fused_wide_supported and K x ceil(batch_size / 128) workgroups do not outnumber the device's CUs ('fused-wide-group-rng' /
+        'fused-mfma-wide-group-rng'); bit for bit the serial result.  An unknown `chunks` is a ValueError; a shape, device or CU count
+        the entry refuses is a RuntimeError that says which limit was hit; both before any device work, with no learner touched.  A
+        learner whose hand-over ran out of time in the kernel is a RuntimeError that names learner and hand-over; nothing is unpacked
+        into any module then."""
         from . import _capi
         who, K = 'TD3Group.train', len(self.learners)
         if dense not in DENSE:
             raise ValueError('%s: dense=%r (one of %s)' % (who, dense, ', '.join(repr(k) for k in DENSE)))
+        if chunks not in CHUNKS:
+            raise ValueError('%s: chunks=%r (one of %s)' % (who, chunks, ', '.join(repr(k) for k in CHUNKS)))
         replays = list(replays)
         if len(replays) != K:
             raise ValueError('%s: %d rings for %d learners' % (who, len(replays), K))
@@ -546,13 +560,26 @@ class TD3Group:
                 raise ValueError('%s: learners %d and %d share (seed, key) = (%d, %d): they would draw the same minibatches and noise'
                                  % (who, seen[(seeds[i], keys[i])], i, seeds[i], keys[i]))
         dev = torch.device(replays[0].device)
-        if any(torch.device(r.device) != dev for r in replays) or not all(t.fused_supported(dev) for t in self.learners):
-            raise RuntimeError('%s: serl_td3_train_group does not run this shape / device (there is no eager fall-back)' % who)
+        wide, big = chunks == 'parallel', chunks == 'serial' and B > FUSED_MAX_BATCH
+        entry, path = _names(dense, big=big, group=True, wide=wide)
+        can = 'fused_wide_supported' if wide else 'fused_big_supported' if big else 'fused_supported'
+        if (any(torch.device(r.device) != dev for r in replays) or dev.type != 'cuda' or not torch.cuda.is_available() or
+                any(t.engine is None for t in self.learners)):
+            raise RuntimeError('%s: %s runs on one CUDA device, with learners that have an engine; the rings are on %s (there is no eager fall-back)'
+                               % (who, entry, ', '.join(sorted({str(r.device) for r in replays}))))
+        if not all(getattr(t, can)(dev) for t in self.learners):
+            raise RuntimeError('%s: %s is not compiled for this shape: hidden a multiple of 4 in 4 .. 128, at most 4 hidden layers, state_dim '
+                               '<= 16, action_dim <= 4, a known activation, batch_size <= %d (there is no eager fall-back)'
+                               % (who, entry, FUSED_MAX_BATCH if can == 'fused_supported' else 512))
+        if wide:
+            cus, G = torch.cuda.get_device_properties(dev).multi_processor_count, (B + FUSED_MAX_BATCH - 1) // FUSED_MAX_BATCH
+            if K * G > cus:
+                raise RuntimeError("%s: chunks='parallel' needs %d learners x %d chunks = %d resident workgroups, the device has %d CUs "
+                                   '(there is no eager fall-back)' % (who, K, G, K * G, cus))
         nmax = max(ns)
         if nmax == 0:
             return [dict(_NAN) for _ in range(K)]
         L = _capi.lib()
-        entry, path = _names(dense, group=True)
         rows, steps = _pack(self.learners, dev)
         table = (_capi.Td3LearnerRow * K)()
         for i, (t, r) in enumerate(zip(self.learners, replays)):
@@ -560,7 +587,7 @@ class TD3Group:
                                            **_learner_fields(t, r, its[i], not champs[i]))
         table_d = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
         status = torch.full((K,), -1, dtype=torch.int32, device=dev)
-        td, pg, work = _outputs(L, a0, K, nmax, False, dev)
+        td, pg, work = _outputs(L, a0, K, nmax, big, dev, wide)
         d = _describe(a0, nmax, rows, steps, td, pg, work)
         gd = _capi.Td3GroupDesc(rows=table_d.data_ptr(), status=status.data_ptr(), dense=int(dense == 'mfma'),
                                 caps=int(self.learners[0].caps_dict is not None))
@@ -569,8 +596,9 @@ class TD3Group:
         torch.cuda.synchronize(dev)
         bad = [(i, int(s)) for i, s in enumerate(status.cpu().tolist()) if s != 0]
         if bad:
-            raise RuntimeError('%s: serl_td3_train_group refused %s; no learner was changed' % (who, ', '.join(
-                'learner %d (%s)' % (i, _capi.TD3_ROW_STATUS.get(s, 'status %d' % s)) for i, s in bad)))
+            raise RuntimeError('%s: %s %s %s; no learner was changed' % (
+                who, entry, 'gave up on' if any(s in _capi.TD3_ROW_TIMEOUTS for _, s in bad) else 'refused',
+                ', '.join('learner %d (%s)' % (i, _capi.TD3_ROW_STATUS.get(s, 'status %d' % s)) for i, s in bad)))
         steps, td, pg = steps.cpu().tolist(), td.cpu().numpy(), pg.cpu().numpy()
         out = []
         for i, t in enumerate(self.learners):

@@ -39,6 +39,17 @@ unless --hidden says otherwise, the protocol of --dense: one process, alternatin
 repetitions after a warm-up.  Results, with ms per sample, go to profiles/td3_batch_timing.json.
 
   python tools/bench_td3.py --batch 86,128,256,512
+
+With --group K1,K2,... AND a --batch list (or one size above 128) the group launches of large minibatches are timed: ONE
+serl_td3_train_group_big launch (chunks 'serial') or serl_td3_train_group_wide launch ('parallel') of K learners against K back-to-back
+single-learner generator launches of the entry points the library had before them, on the same buffers -- serl_td3_train_big for serial,
+serl_td3_train_wide for parallel.  --chunks picks the versions (default serial,parallel); all of them alternate in one process, both
+dense flavours, device events, --reps repetitions after a warm-up; the final rows of every version of a (K, B) must be equal, and the
+tool stops if they are not.  A parallel launch whose K x chunks workgroups outnumber the CUs is not run (the library refuses it), and the
+result says so; --serial-max bounds the back-to-back legs.  The K = 1 rows are also the generator flavours' time at these sizes.
+Results go to profiles/td3_group_big_timing.json, rewritten after every (K, B).
+
+  python tools/bench_td3.py --group 1,8,32 --batch 256,512 --updates 100
 """
 import argparse, ctypes, json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -150,11 +161,14 @@ def main():
     a.batch = int(a.batch) if batches is None else batches[0]
     if a.hidden is None:
         a.hidden = [72] if a.draws or a.group or batches else [72, 32, 96]
+    group_big = bool(a.group) and (batches is not None or a.batch > 128 or a.chunks is not None)
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'td3_wide_timing.json' if a.chunks else 'td3_batch_timing.json' if batches else 'td3_group_timing.json' if a.group else 'td3_rng_timing.json' if a.draws else 'td3_mfma_timing.json' if a.dense else 'td3_fused_timing.json')
+        a.out = os.path.join(ROOT, 'profiles', 'td3_group_big_timing.json' if group_big else 'td3_wide_timing.json' if a.chunks else 'td3_batch_timing.json' if batches else 'td3_group_timing.json' if a.group else 'td3_rng_timing.json' if a.draws else 'td3_mfma_timing.json' if a.dense else 'td3_fused_timing.json')
     import serl_amd
     import td3_64 as T
     engine = serl_amd.RolloutEngine(0)
+    if group_big:
+        return group_big_main(a, engine, batches or [a.batch])
     if a.chunks:
         assert batches and sorted(a.chunks.split(',')) == ['parallel', 'serial'], '--chunks serial,parallel needs a --batch list'
         return chunks_main(a, engine, batches)
@@ -470,6 +484,121 @@ def group_main(a, engine):
                   max(ms[k])) for k in runs), r['rows_equal']), flush=True)
             with open(a.out, 'w') as fh:
                 json.dump(res, fh, indent=1)
+    print(json.dumps(res))
+
+
+def group_big_main(a, engine, batches):
+    import td3_64 as T
+    import td3_big as TB
+    from serl_amd import _capi, build as hip_build
+    L = _capi.lib()
+    dev = engine.device
+    Ks = [int(k) for k in a.group.split(',')]
+    modes = (a.chunks or 'serial,parallel').split(',')
+    assert Ks and min(Ks) >= 1 and modes and all(m in ('serial', 'parallel') for m in modes) and all(1 <= B <= 512 for B in batches), (a.group, a.chunks)
+    seed, n, Ly = 20261020, a.updates, a.layers
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    regs = [ln.strip() for ln in open(a.kernel_regs)] if a.kernel_regs else None
+    GROUP = {'serial': 'serl_td3_train_group_big', 'parallel': 'serl_td3_train_group_wide'}
+    SINGLE = {'serial': 'serl_td3_train_big', 'parallel': 'serl_td3_train_wide'}
+    SIZE = {'serial': L.serl_td3_big_work_bytes, 'parallel': L.serl_td3_wide_work_bytes}
+    res = {'tool': 'bench_td3 --group %s --batch %s --chunks %s' % (a.group, ','.join(str(B) for B in batches), ','.join(modes)),
+           'device': torch.cuda.get_device_name(0), 'compute_units': cus, 'source_hash': hip_build.source_hash(), 'layers': Ly, 'updates_per_learner': n,
+           'reps': a.reps, 'caps': True, 'policy_update_freq': 2, 'activation': 'tanh', 'seed': seed, 'serial_max': a.serial_max, 'kernel_resources': regs,
+           'what': 'ms of ONE launch of K learners (group_<chunks>: %s / %s) and of K back-to-back single-learner generator launches of the '
+                   'entries the library had before (single_<chunks>: %s / %s), device events; per_update = ms / updates_per_learner: the time one '
+                   'more update of EVERY learner costs.  The K1 single rows are the generator flavours of serl_td3_train_big / _wide at this '
+                   'minibatch size.' % (GROUP['serial'], GROUP['parallel'], SINGLE['serial'], SINGLE['parallel']), 'shapes': {}}
+    stream = lambda: ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    for H in a.hidden:
+        for B in batches:
+            d = TB.make_case((7, 3, H, Ly, 'tanh', B, 2, 0, 4, 1, 1, 'small'), seed=H)
+            cap, G = d['ring'].shape[0], (B + 127) // 128
+            shape = res['shapes'].setdefault('H%d_L%d_B%d' % (H, Ly, B), {})
+            for K in Ks:
+                t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+                init = {k: t(np.tile(d[k], (K, 1))) for k in T.ROWS}
+                rings = t(np.tile(d['ring'], (K, 1, 1)))
+                wb = {m: int(SIZE[m](K, 7, 3, H, Ly, B)) for m in modes}
+                wb1 = {m: int(SIZE[m](1, 7, 3, H, Ly, B)) for m in modes}
+                work = torch.empty(max(wb.values()) // 4, dtype=torch.float32, device=dev)
+
+                def table(n_):
+                    rows = (_capi.Td3LearnerRow * K)()
+                    for i in range(K):
+                        rows[i] = _capi.Td3LearnerRow(ring=rings[i].data_ptr(), seed=seed, capacity=cap, n_rows=cap, n_updates=n_, iteration0=0, key=i,
+                                                      policy_update_freq=2, update_actor_target=1, lr=T.LR, gamma=T.GAMMA, tau=T.TAU, noise_sd=T.NOISE_SD,
+                                                      noise_clip=T.NOISE_CLIP, **T.CAPS)
+                    return torch.frombuffer(bytearray(bytes(rows)), dtype=torch.uint8).to(dev)
+                tables = {n: table(n), min(n, 20): table(min(n, 20))}
+
+                def run(version, mode, dense, n_, rows_out=None):
+                    rows = {k: v.clone() for k, v in init.items()}
+                    for k in T.MOMENTS:
+                        rows[k] = torch.zeros_like(rows[k.split('_')[0]])
+                    steps = torch.zeros(K, 2, dtype=torch.int32, device=dev)
+                    td, pg = torch.zeros(K, n_, device=dev), torch.zeros(K, n_, device=dev)
+                    status = torch.full((K,), -1, dtype=torch.int32, device=dev)
+                    mf = int(dense == 'mfma')
+
+                    def desc(first, k, work_bytes):
+                        return _capi.Td3Desc(
+                            state_dim=7, action_dim=3, hidden=H, num_layers=Ly, activation=0, n_learners=k, batch=B, n_updates=n_, capacity=cap,
+                            policy_update_freq=2, iteration0=0, update_actor_target=1, lr=T.LR, gamma=T.GAMMA, tau=T.TAU, noise_sd=T.NOISE_SD,
+                            noise_clip=T.NOISE_CLIP, lambda_s=T.CAPS['lambda_s'], lambda_t=T.CAPS['lambda_t'], eps_sd=T.CAPS['eps_sd'], max_grad_norm=T.MAX_NORM,
+                            actor=rows['actor'][first].data_ptr(), actor_target=rows['actor_target'][first].data_ptr(),
+                            actor_m=rows['actor_m'][first].data_ptr(), actor_v=rows['actor_v'][first].data_ptr(), actor_stride=rows['actor'].stride(0),
+                            critic=rows['critic'][first].data_ptr(), critic_target=rows['critic_target'][first].data_ptr(),
+                            critic_m=rows['critic_m'][first].data_ptr(), critic_v=rows['critic_v'][first].data_ptr(),
+                            critic_stride=rows['critic'].stride(0), adam_steps=steps[first].data_ptr(), ring=rings[first].data_ptr(),
+                            td_loss=td[first].data_ptr(), pg_loss=pg[first].data_ptr(), loss_stride=n_, work=work.data_ptr(), work_bytes=work_bytes)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    e0.record()
+                    if version == 'group':
+                        gd = _capi.Td3GroupDesc(rows=tables[n_].data_ptr(), status=status.data_ptr(), dense=mf, caps=1)
+                        _capi.check(getattr(L, GROUP[mode])(engine.ctx, ctypes.byref(desc(0, K, wb[mode])), ctypes.byref(gd), stream()), GROUP[mode])
+                    else:
+                        for i in range(K):
+                            rd = _capi.Td3RngDesc(seed=seed, n_rows=cap, learner0=i, dense=mf, caps=1)
+                            x = (_capi.Td3WideDesc(rng=ctypes.pointer(rd), status=status[i].data_ptr(), dense=mf) if mode == 'parallel' else
+                                 _capi.Td3BigDesc(rng=ctypes.pointer(rd), dense=mf))
+                            _capi.check(getattr(L, SINGLE[mode])(engine.ctx, ctypes.byref(desc(i, 1, wb1[mode])), ctypes.byref(x), stream()), SINGLE[mode])
+                    e1.record()
+                    torch.cuda.synchronize()
+                    assert torch.isfinite(td).all() and ((version, mode) == ('single', 'serial') or int(status.abs().max()) == 0), status
+                    if rows_out is not None:
+                        rows_out.update({k: rows[k].cpu().numpy() for k in T.ROWS}, td=td.cpu().numpy(), pg=pg.cpu().numpy(), steps=steps.cpu().numpy())
+                    return e0.elapsed_time(e1)
+
+                single = a.serial_max is None or K <= a.serial_max
+                fits = {m: m == 'serial' or K * G <= cus for m in modes}
+                runs = [(v, m, f) for m in modes if fits[m] for v in (('group', 'single') if single else ('group',)) for f in ('valu', 'mfma')]
+                for k in runs:
+                    run(*k, min(n, 20))                                  # warm-up
+                ms, rows = {k: [] for k in runs}, {k: {} for k in runs}
+                for _ in range(a.reps):                                  # alternating: a drift of the clock hits all alike
+                    for k in runs:
+                        ms[k].append(run(*k, n, rows[k]))
+                r = {'%s_%s_%s_ms' % k: spread(ms[k]) for k in runs}
+                r.update({'%s_%s_%s_ms_per_update' % k: spread([x / n for x in ms[k]]) for k in runs})
+                r['single_measured'] = single
+                r['parallel_measured'] = fits.get('parallel', False)
+                r['workgroups'] = {m: K * (G if m == 'parallel' else 1) for m in modes}
+                r['rows_equal'] = bool(all(np.array_equal(rows[k][x], rows[runs[0]][x]) for k in runs for x in rows[k]))
+                for m, f in ((m, f) for m in modes if fits[m] for f in ('valu', 'mfma')):
+                    r['%s_%s_learner_updates_per_s' % (m, f)] = K * n / (r['group_%s_%s_ms' % (m, f)]['median'] * 1e-3)
+                    if single:
+                        r['%s_%s_single_over_group_median' % (m, f)] = r['single_%s_%s_ms' % (m, f)]['median'] / r['group_%s_%s_ms' % (m, f)]['median']
+                if all(fits[m] for m in ('serial', 'parallel') if m in modes) and len(modes) == 2:
+                    for f in ('valu', 'mfma'):
+                        r['%s_group_serial_over_group_parallel_median' % f] = r['group_serial_%s_ms' % f]['median'] / r['group_parallel_%s_ms' % f]['median']
+                shape['K%d' % K] = r
+                print('H %d B %d K %3d  %s  rows equal: %s' % (H, B, K, '  '.join('%s/%s/%s %.1f [%.1f .. %.1f] ms' % (k + (statistics.median(ms[k]), min(ms[k]),
+                      max(ms[k]))) for k in runs), r['rows_equal']), flush=True)
+                with open(a.out, 'w') as fh:
+                    json.dump(res, fh, indent=1)
+                assert r['rows_equal'], 'the versions of K %d, B %d differ in their final rows' % (K, B)
     print(json.dumps(res))
 
 
