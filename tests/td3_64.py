@@ -17,6 +17,14 @@ CAPS = dict(lambda_s=0.5, lambda_t=0.1, eps_sd=0.05)
 BETA1, BETA2, EPS = 0.9, 0.999, 1e-8
 HC = 64
 RING_ROWS = 160
+# what td3_literal / td3_explicit64 run with unless told otherwise: the constants above (tests/td3_hp.py varies them one at a time)
+DEFAULT_HP = dict(lr=LR, gamma=GAMMA, tau=TAU, noise_sd=NOISE_SD, noise_clip=NOISE_CLIP, max_norm=MAX_NORM, **CAPS)
+
+
+def hyper(hp=None):
+    """DEFAULT_HP with the fields of `hp` (a dict of some of lr, gamma, tau, noise_sd, noise_clip, max_norm, lambda_s, lambda_t, eps_sd)"""
+    assert hp is None or set(hp) <= set(DEFAULT_HP), hp
+    return dict(DEFAULT_HP, **(hp or {}))
 
 # ---- the grid ---------------------------------------------------------------------------------------------------------------------
 # A covering set: minibatches of 1, 3, 64, 65, 86, 127, 128 rows (one and two wavefronts of samples, the edges of both, the default);
@@ -105,10 +113,12 @@ MOMENTS = ('actor_m', 'actor_v', 'critic_m', 'critic_v')
 
 
 # ---- the contract, literally ----------------------------------------------------------------------------------------------------------
-def td3_literal(d, dtype=torch.float64, device='cpu', n=None):
+def td3_literal(d, dtype=torch.float64, device='cpu', n=None, hp=None, steps0=(0, 0), moments0=None):
     """td3.py:123-198 step by step on the project's Actor / Critic modules in `dtype` with torch.optim.Adam and
-    nn.utils.clip_grad_norm_, the draws replaced by the given ones.  -> dict: the four rows, Adam's moments (float64 arrays), td [n],
-    pg [n] (NaN where the actor was not updated), clip_c / clip_a (per critic / actor step: was the norm clip active)"""
+    nn.utils.clip_grad_norm_, the draws replaced by the given ones.  hp: see hyper().  steps0 = (critic, actor) steps taken before and
+    moments0 = {a name of MOMENTS: its packed row}: loaded into the optimisers' state dicts (an optimiser with neither starts empty).
+    -> dict: the four rows, Adam's moments (float64 arrays), td [n], pg [n] (NaN where the actor was not updated), clip_c / clip_a (per
+    critic / actor step: was the norm clip active)"""
     from serl_amd.actor import Actor, unpack_into, unpack_critic
     from serl_amd.td3 import Critic
     S, A = d['S'], d['A']
@@ -124,8 +134,17 @@ def td3_literal(d, dtype=torch.float64, device='cpu', n=None):
         m.to(dtype)
         unpack_critic(m, torch.from_numpy(d[k].astype(np.float64)))
         m.to(device)
-    a_opt = torch.optim.Adam(actor.parameters(), lr=LR)
-    c_opt = torch.optim.Adam(critic.parameters(), lr=LR)
+    hp = hyper(hp)
+    a_opt = torch.optim.Adam(actor.parameters(), lr=hp['lr'])
+    c_opt = torch.optim.Adam(critic.parameters(), lr=hp['lr'])
+    for opt, m, key, step in ((c_opt, critic, 'critic', steps0[0]), (a_opt, actor, 'actor', steps0[1])):
+        if step or moments0 is not None:
+            off = 0
+            for p in m.parameters():
+                row = lambda k: torch.from_numpy(np.asarray(moments0[k], np.float64)[off:off + p.numel()]).to(dtype).view(p.shape).to(device).clone()
+                opt.state[p] = dict(step=torch.tensor(float(step)), exp_avg=row(key + '_m') if moments0 is not None else torch.zeros_like(p),
+                                    exp_avg_sq=row(key + '_v') if moments0 is not None else torch.zeros_like(p))
+                off += p.numel()
     ring = torch.from_numpy(d['ring']).to(dtype).to(device)
     tn = torch.from_numpy(d['tn']).to(dtype).to(device)
     cn = torch.from_numpy(d['cn']).to(dtype).to(device) if d['caps'] else None
@@ -136,17 +155,17 @@ def td3_literal(d, dtype=torch.float64, device='cpu', n=None):
         state, action, next_state = rows[:, :S], rows[:, S:S + A], rows[:, S + A:2 * S + A]
         reward, done = rows[:, 2 * S + A:2 * S + A + 1], rows[:, 2 * S + A + 1:2 * S + A + 2]
         with torch.no_grad():
-            noise = (tn[u] * NOISE_SD).clamp(-NOISE_CLIP, NOISE_CLIP)
+            noise = (tn[u] * hp['noise_sd']).clamp(-hp['noise_clip'], hp['noise_clip'])
             next_action = torch.clamp(noise + actor_t(next_state), -1, 1)
             tq1, tq2 = critic_t(next_state, next_action)
             next_q = torch.min(tq1, tq2) * (1 - done)
-            target_q = reward + (GAMMA * next_q).detach()
+            target_q = reward + (hp['gamma'] * next_q).detach()
         q1, q2 = critic(state, action)
         loss = F.mse_loss(q1, target_q) + F.mse_loss(q2, target_q)
         c_opt.zero_grad()
         loss.backward()
-        norm = torch.nn.utils.clip_grad_norm_(critic.parameters(), MAX_NORM)
-        clip_c.append(bool(MAX_NORM / (float(norm) + 1e-6) < 1.0))
+        norm = torch.nn.utils.clip_grad_norm_(critic.parameters(), hp['max_norm'])
+        clip_c.append(bool(hp['max_norm'] / (float(norm) + 1e-6) < 1.0))
         c_opt.step()
         td.append(float(loss.detach()))
         pg.append(float('nan'))
@@ -156,20 +175,20 @@ def td3_literal(d, dtype=torch.float64, device='cpu', n=None):
             pgl = -torch.mean(est_q1)
             if d['caps']:
                 now = actor(state)
-                state_bar = state + cn[k] * CAPS['eps_sd']
+                state_bar = state + cn[k] * hp['eps_sd']
                 bar = actor(state_bar)
-                pgl = pgl + (CAPS['lambda_t'] * F.mse_loss(action, now) + CAPS['lambda_s'] * F.mse_loss(action, bar))
+                pgl = pgl + (hp['lambda_t'] * F.mse_loss(action, now) + hp['lambda_s'] * F.mse_loss(action, bar))
             k += 1
             pgl.backward()
-            norm = torch.nn.utils.clip_grad_norm_(actor.parameters(), MAX_NORM)
-            clip_a.append(bool(MAX_NORM / (float(norm) + 1e-6) < 1.0))
+            norm = torch.nn.utils.clip_grad_norm_(actor.parameters(), hp['max_norm'])
+            clip_a.append(bool(hp['max_norm'] / (float(norm) + 1e-6) < 1.0))
             a_opt.step()
             with torch.no_grad():
                 if d['uat']:
                     for t, p in zip(actor_t.parameters(), actor.parameters()):
-                        t.copy_(t * (1.0 - TAU) + p * TAU)
+                        t.copy_(t * (1.0 - hp['tau']) + p * hp['tau'])
                 for t, p in zip(critic_t.parameters(), critic.parameters()):
-                    t.copy_(t * (1.0 - TAU) + p * TAU)
+                    t.copy_(t * (1.0 - hp['tau']) + p * hp['tau'])
             pg[-1] = float(pgl.detach())
     flat = lambda ps: torch.cat([p.detach().reshape(-1) for p in ps]).double().cpu().numpy()
 
@@ -185,12 +204,23 @@ def td3_literal(d, dtype=torch.float64, device='cpu', n=None):
 # ---- the same loop written out, with switches for planted mistakes ------------------------------------------------------------------
 MISTAKES = ('clip_per_critic', 'clip_always', 'no_done', 'max_of_twins', 'noise_unclamped', 'actor_every_step', 'champion_target_updated',
             'tau_swapped', 'biased_std', 'no_bias_correction', 'no_caps', 'q2_actor_loss')
+# Mistakes that only a run away from DEFAULT_HP / from a cold start can show (at the defaults each of them IS the reference, so they are
+# kept apart from MISTAKES, which tests/test_td3_host.py walks on the default grid): a field replaced by today's constant
+# (gamma_fixed, tau_fixed, noise_fixed = noise_sd and noise_clip, eps_sd_fixed), lambda_s and lambda_t swapped, the ACTOR's clip at
+# MAX_NORM whatever hp['max_norm'] says, Adam's bias corrections counted from 0 whatever steps0 says.  tests/test_td3_hp_host.py walks them.
+HP_MISTAKES = ('gamma_fixed', 'tau_fixed', 'noise_fixed', 'lambdas_swapped', 'eps_sd_fixed', 'actor_clip_fixed', 'steps_restart')
 
 
-def td3_explicit64(d, mistake=None):
+def td3_explicit64(d, mistake=None, hp=None, steps0=(0, 0), moments0=None):
     """td3_literal in float64 with the forward passes, the losses, the clip, Adam and the soft updates written out on the packed rows,
-    and at most one of MISTAKES planted.  With mistake=None it is the reference (tests/test_td3_host.py checks that)."""
-    assert mistake is None or mistake in MISTAKES, mistake
+    and at most one of MISTAKES / HP_MISTAKES planted.  With mistake=None it is the reference (tests/test_td3_host.py checks that)."""
+    assert mistake is None or mistake in MISTAKES + HP_MISTAKES, mistake
+    hp = hyper(hp)
+    gamma = GAMMA if mistake == 'gamma_fixed' else hp['gamma']
+    tau = TAU if mistake == 'tau_fixed' else hp['tau']
+    noise_sd, noise_clip = (NOISE_SD, NOISE_CLIP) if mistake == 'noise_fixed' else (hp['noise_sd'], hp['noise_clip'])
+    lambda_s, lambda_t = (hp['lambda_t'], hp['lambda_s']) if mistake == 'lambdas_swapped' else (hp['lambda_s'], hp['lambda_t'])
+    eps_sd = CAPS['eps_sd'] if mistake == 'eps_sd_fixed' else hp['eps_sd']
     S, A, H, L, B = d['S'], d['A'], d['H'], d['L'], d['B']
     corr = 0 if mistake == 'biased_std' else 1
     act = {'tanh': torch.tanh, 'elu': F.elu, 'relu': lambda v: F.leaky_relu(v, 0.01)}[d['act']]
@@ -232,15 +262,17 @@ def td3_explicit64(d, mistake=None):
     wa, wat, wc, wct = f64('actor').requires_grad_(True), f64('actor_target'), f64('critic').requires_grad_(True), f64('critic_target')
     ring, tn = f64('ring'), f64('tn')
     cn = f64('cn') if d['caps'] else None
-    st = {k: [torch.zeros_like(w), torch.zeros_like(w), 0] for k, w in (('a', wa), ('c', wc))}
+    m0 = lambda k, w: torch.zeros_like(w) if moments0 is None else torch.from_numpy(np.asarray(moments0[k], np.float64)).clone()
+    st = {k: [m0(key + '_m', w), m0(key + '_v', w), 0 if mistake == 'steps_restart' else int(step)]
+          for k, key, w, step in (('a', 'actor', wa, steps0[1]), ('c', 'critic', wc, steps0[0]))}
 
-    def clip(g, parts):
+    def clip(g, parts, max_norm):
         """the joint clip over g; the planted per-critic clip treats `parts` equal pieces separately"""
         g = g.clone()
         P = g.numel() // parts
         for k in range(parts):
             seg = g[k * P:(k + 1) * P]
-            coef = MAX_NORM / (seg.norm() + 1e-6)
+            coef = max_norm / (seg.norm() + 1e-6)
             active = bool(coef < 1.0)
             if active or mistake == 'clip_always':
                 seg.mul_(coef)
@@ -253,9 +285,9 @@ def td3_explicit64(d, mistake=None):
         s[1] = BETA2 * s[1] + (1 - BETA2) * g * g
         with torch.no_grad():
             if mistake == 'no_bias_correction':
-                w -= LR * s[0] / (s[1].sqrt() + EPS)
+                w -= hp['lr'] * s[0] / (s[1].sqrt() + EPS)
             else:
-                w -= LR / (1 - BETA1 ** s[2]) * s[0] / (s[1].sqrt() / np.sqrt(1 - BETA2 ** s[2]) + EPS)
+                w -= hp['lr'] / (1 - BETA1 ** s[2]) * s[0] / (s[1].sqrt() / np.sqrt(1 - BETA2 ** s[2]) + EPS)
 
     td, pg, clip_c, clip_a, k = [], [], [], [], 0
     for u in range(d['n']):
@@ -264,19 +296,19 @@ def td3_explicit64(d, mistake=None):
         state, action, next_state = rows[:, :S], rows[:, S:S + A], rows[:, S + A:2 * S + A]
         reward, done = rows[:, 2 * S + A:2 * S + A + 1], rows[:, 2 * S + A + 1:2 * S + A + 2]
         with torch.no_grad():
-            noise = tn[u] * NOISE_SD
+            noise = tn[u] * noise_sd
             if mistake != 'noise_unclamped':
-                noise = noise.clamp(-NOISE_CLIP, NOISE_CLIP)
+                noise = noise.clamp(-noise_clip, noise_clip)
             x2 = torch.cat((next_state, torch.clamp(noise + actor_f(wat, next_state), -1, 1)), 1)
             tq1, tq2 = critic_f(wct, x2, 0), critic_f(wct, x2, 1)
             nq = torch.max(tq1, tq2) if mistake == 'max_of_twins' else torch.min(tq1, tq2)
             if mistake != 'no_done':
                 nq = nq * (1 - done)
-            target_q = reward + GAMMA * nq
+            target_q = reward + gamma * nq
         x = torch.cat((state, action), 1)
         loss = ((critic_f(wc, x, 0) - target_q) ** 2).sum() / B + ((critic_f(wc, x, 1) - target_q) ** 2).sum() / B
         g, = torch.autograd.grad(loss, wc)
-        g, active = clip(g, 2 if mistake == 'clip_per_critic' else 1)
+        g, active = clip(g, 2 if mistake == 'clip_per_critic' else 1, hp['max_norm'])
         clip_c.append(active)
         adam('c', wc, g)
         td.append(float(loss.detach()))
@@ -286,14 +318,14 @@ def td3_explicit64(d, mistake=None):
             pgl = -critic_f(wc, torch.cat((state, a_now), 1), 1 if mistake == 'q2_actor_loss' else 0).sum() / B
             if d['caps']:
                 if mistake != 'no_caps':
-                    bar = actor_f(wa, state + cn[min(k, len(cn) - 1)] * CAPS['eps_sd'])
-                    pgl = pgl + CAPS['lambda_t'] * ((action - a_now) ** 2).sum() / (B * A) + CAPS['lambda_s'] * ((action - bar) ** 2).sum() / (B * A)
+                    bar = actor_f(wa, state + cn[min(k, len(cn) - 1)] * eps_sd)
+                    pgl = pgl + lambda_t * ((action - a_now) ** 2).sum() / (B * A) + lambda_s * ((action - bar) ** 2).sum() / (B * A)
             k += 1
             g, = torch.autograd.grad(pgl, wa)
-            g, active = clip(g, 1)
+            g, active = clip(g, 1, MAX_NORM if mistake == 'actor_clip_fixed' else hp['max_norm'])
             clip_a.append(active)
             adam('a', wa, g)
-            t1, t2 = (TAU, 1.0 - TAU) if mistake == 'tau_swapped' else (1.0 - TAU, TAU)
+            t1, t2 = (tau, 1.0 - tau) if mistake == 'tau_swapped' else (1.0 - tau, tau)
             with torch.no_grad():
                 if d['uat'] or mistake == 'champion_target_updated':
                     wat = wat * t1 + wa * t2
@@ -344,22 +376,24 @@ MOM_REL = {'tanh': 1.8e-4, 'elu': 1e-4, 'relu': 1.5e-5}
 FWD_TOL = 5.5e-7
 
 
-def check(got, ref, d, what=''):
-    """assert an f32 result (rows, moments, td, pg) against the float64 run `ref` of case dict `d`; -> the deviations"""
+def check(got, ref, d, what='', tol=None):
+    """assert an f32 result (rows, moments, td, pg) against the float64 run `ref` of case dict `d`; -> the deviations.  tol: None = the
+    bounds above, or dict(rel=, mom=, fwd=) of a case that has bounds of its own (tests/td3_hp.py)"""
     dev, moved = deviations(got, ref, d)
     act = d['act']
+    rel, mom, fwd = (tol['rel'], tol['mom'], tol['fwd']) if tol is not None else (TOL_REL[act], MOM_REL[act], FWD_TOL)
     assert moved['actor'] > MIN_MOVED and moved['critic'] > MIN_MOVED, (what, moved)
     print('TD3_DEV %-60s %s' % (what, ' '.join('%s %.2g' % (k, v) for k, v in dev.items())))
     for k in ROWS:
         assert np.isfinite(np.asarray(got[k])).all(), (what, k)
         net = k.split('_')[0]
-        assert dev[k] <= TOL_REL[act] + TOL_ABS / moved[net], '%s: %s deviates by %.3g x moved (%.3g) > %.3g' % (what, k, dev[k], moved[net], TOL_REL[act])
+        assert dev[k] <= rel + TOL_ABS / moved[net], '%s: %s deviates by %.3g x moved (%.3g) > %.3g' % (what, k, dev[k], moved[net], rel)
     for k in MOMENTS:
-        assert dev[k] <= MOM_REL[act], '%s: %s deviates by %.3g of its largest entry > %.3g' % (what, k, dev[k], MOM_REL[act])
+        assert dev[k] <= mom, '%s: %s deviates by %.3g of its largest entry > %.3g' % (what, k, dev[k], mom)
     e = abs(float(got['td'][0]) - ref['td'][0]) / max(abs(ref['td'][0]), 1.0)
-    assert e <= FWD_TOL, '%s: td_loss[0] %.9g against %.9g (%.3g > %.3g)' % (what, got['td'][0], ref['td'][0], e, FWD_TOL)
+    assert e <= fwd, '%s: td_loss[0] %.9g against %.9g (%.3g > %.3g)' % (what, got['td'][0], ref['td'][0], e, fwd)
     i = first_pg(ref)
     if i is not None:
         e = abs(float(got['pg'][i]) - ref['pg'][i]) / max(abs(ref['pg'][i]), 1.0)
-        assert e <= FWD_TOL, '%s: pg_loss[%d] %.9g against %.9g (%.3g > %.3g)' % (what, i, got['pg'][i], ref['pg'][i], e, FWD_TOL)
+        assert e <= fwd, '%s: pg_loss[%d] %.9g against %.9g (%.3g > %.3g)' % (what, i, got['pg'][i], ref['pg'][i], e, fwd)
     return dev
