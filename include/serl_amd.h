@@ -671,6 +671,22 @@ int serl_smoothness(serl_ctx *ctx, const double *actions, int64_t episode_stride
 int serl_ga_distill(serl_ctx *ctx, float *child, int64_t stride, int32_t n_pairs, int32_t state_dim, int32_t hidden, int32_t num_layers,
                     int32_t action_dim, int32_t activation, const float *states, const float *targets, const float *keep, int32_t rows,
                     const int32_t *slots, int32_t steps, const int32_t *n_steps, const int32_t *batch, float lr, void *stream);
+/* The same training loop for every actor shape the TD3 learner takes (SERL_ABI_VERSION stays 9: an added entry point): hidden a
+ * multiple of 4 in 4 .. 128, 0 .. 4 hidden layers, state_dim 1 .. 16, action_dim 1 .. 4, the three activations, minibatches of
+ * 1 .. 128 rows -- hidden 32 x 3 included.  SERL_E_UNSUPPORTED otherwise, nothing touched.  Arguments and semantics are
+ * serl_ga_distill's (a slot outside [0, rows) is clamped into it; n_steps[p] == 0 leaves row p bit for bit unchanged; columns past the
+ * row and rows outside the launch are not written; an all-dropped minibatch takes its Adam step with zero gradients), plus
+ *   work   DEVICE scratch of serl_ga_distill_general_work_bytes(n_pairs, ..) bytes: per pair the gradients, Adam's two moments (zeroed
+ *          by the kernel), the gathered minibatch and the backward pass's tape.  The child row itself is trained in place in `child`:
+ *          at these shapes parameters, gradients and moments no longer fit the LDS serl_ga_distill keeps them in.
+ *   dense  0 = the dense phases on the VALU, 1 = on the f32 matrix cores (v_mfma_f32_16x16x4_f32); the two give the same bits.
+ * One workgroup per pair, built from the learner's phases (serl_td3_train); n_pairs == 0 is the probe "would this shape run here?",
+ * for which `work` may be NULL.  serl_ga_distill_general_work_bytes returns 0 for a shape that is refused or n_pairs < 1. */
+int64_t serl_ga_distill_general_work_bytes(int32_t n_pairs, int32_t state_dim, int32_t action_dim, int32_t hidden, int32_t num_layers);
+int serl_ga_distill_general(serl_ctx *ctx, float *child, int64_t stride, int32_t n_pairs, int32_t state_dim, int32_t hidden,
+                            int32_t num_layers, int32_t action_dim, int32_t activation, const float *states, const float *targets,
+                            const float *keep, int32_t rows, const int32_t *slots, int32_t steps, const int32_t *n_steps,
+                            const int32_t *batch, float lr, void *work, int64_t work_bytes, int32_t dense, void *stream);
 /* Host helper (no GPU work): the rows `random.sample(memory, k)` of base/core/replay_memory.py:72-73,83-85 picks from n
  * transitions in `calls` consecutive calls, replayed from the generator's raw 32-bit outputs (CPython's selection
  * algorithm: set-based above its set-size threshold, pool-based below).  Returns the number of outputs consumed,

@@ -26,7 +26,8 @@ EXPORTS = ['serl_abi_version', 'serl_last_error', 'serl_param_count', 'serl_ctx_
            'serl_td3_train_group', 'serl_td3_group_layout',
            'serl_td3_train_big', 'serl_td3_big_layout', 'serl_td3_big_work_bytes', 'serl_td3_rng_fill_big',
            'serl_td3_train_wide', 'serl_td3_wide_layout', 'serl_td3_wide_work_bytes',
-           'serl_td3_train_group_big', 'serl_td3_train_group_wide']
+           'serl_td3_train_group_big', 'serl_td3_train_group_wide',
+           'serl_ga_distill_general', 'serl_ga_distill_general_work_bytes']
 
 
 class BuildDesc(ctypes.Structure):
@@ -260,6 +261,8 @@ def lib():
     L.serl_smoothness.argtypes = [VP, VP, ctypes.c_int64, VP, i32, i32, ctypes.c_double, VP, VP, VP]
     L.serl_smoothness_work_size.argtypes = [i32, i32]
     L.serl_ga_distill.argtypes = [VP, VP, ctypes.c_int64, i32, i32, i32, i32, i32, i32, VP, VP, VP, i32, VP, i32, VP, VP, ctypes.c_float, VP]
+    L.serl_ga_distill_general.argtypes = L.serl_ga_distill.argtypes[:-1] + [VP, ctypes.c_int64, i32, VP]
+    L.serl_ga_distill_general_work_bytes.argtypes = [i32] * 5
     L.serl_host_sample_slots.argtypes = [VP, ctypes.c_longlong, i32, i32, i32, VP, i32]
     L.serl_venv_state_bytes.argtypes = [i32]
     L.serl_venv_reset.argtypes = [VP, ctypes.POINTER(VenvDesc), VP, VP, VP]
@@ -318,7 +321,7 @@ def lib():
         elif f == 'serl_host_philox':
             L.serl_host_philox.restype = None
         elif f not in ('serl_last_error',):
-            getattr(L, f).restype = ctypes.c_longlong if f in ('serl_host_sample_slots', 'serl_venv_state_bytes', 'serl_td3_work_bytes', 'serl_td3_big_work_bytes', 'serl_td3_wide_work_bytes') else ctypes.c_int
+            getattr(L, f).restype = ctypes.c_longlong if f in ('serl_host_sample_slots', 'serl_venv_state_bytes', 'serl_td3_work_bytes', 'serl_td3_big_work_bytes', 'serl_td3_wide_work_bytes', 'serl_ga_distill_general_work_bytes') else ctypes.c_int
     if L.serl_abi_version() != ABI_VERSION:
         raise RuntimeError('serl_amd: ABI version mismatch (library %d, binding %d): rebuild with `python serl_amd/build.py`'
                            % (L.serl_abi_version(), ABI_VERSION))

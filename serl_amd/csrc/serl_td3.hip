@@ -456,21 +456,26 @@ __device__ __forceinline__ float *mlp_bwd(const Ctx &c, const Net &net, const fl
   return D;
 }
 
-// nn.utils.clip_grad_norm_ (coef = max_norm / (norm + 1e-6), applied when below 1) and torch.optim.Adam's step `step` (defaults)
+// nn.utils.clip_grad_norm_ (coef = max_norm / (norm + 1e-6), applied when below 1) and torch.optim.Adam's step `step` (defaults).
+// CLIP = false (the distillation, serl_distill_general.inc) is the same step on the gradients as they are: no norm, max_norm not read.
+template <bool CLIP = true>
 __device__ __forceinline__ void clip_adam(const Ctx &c, float *w, float *m, float *v, const float *g, int P, int step, float lr, float max_norm)
 {
-  float s = 0.0f;
-  for (int e = c.t; e < P; e += NT) s = fmaf(g[e], g[e], s);
-  const float norm = sqrtf(block_sum(c, s));
-  float coef = max_norm / (norm + 1e-6f);
-  if (!(coef < 1.0f)) coef = 1.0f;
+  float coef = 1.0f;
+  if constexpr (CLIP) {
+    float s = 0.0f;
+    for (int e = c.t; e < P; e += NT) s = fmaf(g[e], g[e], s);
+    const float norm = sqrtf(block_sum(c, s));
+    coef = max_norm / (norm + 1e-6f);
+    if (!(coef < 1.0f)) coef = 1.0f;
+  }
   const double b1t = pow(0.9, (double)step), b2t = pow(0.999, (double)step);
   const float step_size = (float)((double)lr / (1.0 - b1t));
   const float bc2_sqrt = (float)sqrt(1.0 - b2t);
   // (1 - beta as torch forms them: in double, rounded once -- 1.0f - 0.999f is off by 1.3e-5 of its value)
   const float beta2 = 0.999f, omb1 = (float)(1.0 - 0.9), omb2 = (float)(1.0 - 0.999), eps = 1e-8f;
   for (int e = c.t; e < P; e += NT) {
-    const float ge = g[e] * coef;
+    const float ge = CLIP ? g[e] * coef : g[e];
     const float m1 = m[e] + (ge - m[e]) * omb1;
     const float v1 = v[e] * beta2 + ge * ge * omb2;
     m[e] = m1; v[e] = v1;
@@ -1116,6 +1121,8 @@ int td3_layout_out(const int32_t (&v)[N], int32_t *out, int32_t capacity)
   return N;
 }
 
+#include "serl_distill_general.inc"
+
 }  // namespace
 
 extern "C" {
@@ -1268,6 +1275,21 @@ int serl_td3_train_wide(serl_ctx *c, const serl_td3_desc *d, const serl_td3_wide
   Td3Call call = {"serl_td3_train_wide", wd->rng ? TD3_GENERATOR : TD3_TABLES, wd->rng};
   call.mfma = wd->dense == 1; call.big = true; call.wide = true; call.status = wd->status;
   return td3_train(c, d, stream, call);
+}
+
+int64_t serl_ga_distill_general_work_bytes(int32_t n_pairs, int32_t state_dim, int32_t action_dim, int32_t hidden, int32_t num_layers)
+{
+  if (n_pairs < 1 || !td3_shape_ok(state_dim, action_dim, hidden, num_layers, 1)) return 0;
+  return (int64_t)n_pairs * distill_g_work_floats(state_dim, action_dim, hidden, num_layers) * (int64_t)sizeof(float);
+}
+
+int serl_ga_distill_general(serl_ctx *c, float *child, int64_t stride, int32_t n_pairs, int32_t state_dim, int32_t hidden, int32_t num_layers,
+                            int32_t action_dim, int32_t activation, const float *states, const float *targets, const float *keep, int32_t rows,
+                            const int32_t *slots, int32_t steps, const int32_t *n_steps, const int32_t *batch, float lr, void *work,
+                            int64_t work_bytes, int32_t dense, void *stream)
+{
+  return distill_general(c, child, stride, n_pairs, state_dim, hidden, num_layers, action_dim, activation, states, targets, keep, rows, slots, steps,
+                         n_steps, batch, lr, work, work_bytes, dense, stream);
 }
 
 int serl_host_td3_slots(uint64_t seed, int32_t learner, int32_t iteration, int32_t n_rows, int32_t batch, int32_t *out)

@@ -121,29 +121,75 @@ def _batched_forward(spec, rows, states):
     return torch.tanh(torch.baddbmm(b[:, None, :], h, W.transpose(1, 2)))
 
 
-def distil_batch(args, engine, spec, weights, pairs, buffers, critic, rng=random):
+KERNELS = ('serl50', 'general', 'auto')
+DENSE = ('valu', 'mfma')
+
+
+def _probe(engine, spec, weights, general):
+    """the n_pairs = 0 call of serl_ga_distill / serl_ga_distill_general: would the kernel run this shape on this device?  Launches
+    nothing and consumes no draw."""
+    import ctypes
+    from . import _capi
+    z = ctypes.c_void_p(0)
+    one = torch.zeros(4, dtype=torch.int32, device=weights.device)
+    a = (engine.ctx, weights.data_ptr(), weights.stride(0), 0, spec.state_dim, spec.hidden, spec.num_layers, spec.action_dim,
+         spec.activation_id, weights.data_ptr(), weights.data_ptr(), weights.data_ptr(), 1, one.data_ptr(), 0, one.data_ptr(),
+         one.data_ptr(), ctypes.c_float(1e-3))
+    if general:
+        return _capi.lib().serl_ga_distill_general(*a, z, 0, 0, z) == 0
+    return _capi.lib().serl_ga_distill(*a, z) == 0
+
+
+def distil_batch(args, engine, spec, weights, pairs, buffers, critic, rng=random, kernel='serl50', dense='valu', info=None):
     """All distillation crossovers of an epoch: pairs [(first, second)] in the reference's order ->
     [(child row, child buffer, empty critical buffer)].  Host draws (buffer shuffle, the throw-away initialisation, the
     minibatches) happen pair by pair in the reference's order; the parents' actions and the critic's Q-filter are evaluated
-    once per pair over the child's whole buffer; the 12 x (len // 128) Adam steps of all pairs run in ONE kernel launch
-    (serl_ga_distill).  Shapes the kernel is not compiled for train pair by pair in PyTorch (distilation_crossover)."""
+    once per pair over the child's whole buffer; the 12 x (len // 128) Adam steps of all pairs run in ONE kernel launch.
+
+    kernel  'serl50' (default): serl_ga_distill, compiled for hidden 32 x 3 (training state in LDS); every other shape trains pair
+            by pair in PyTorch (distilation_crossover).
+            'general': serl_ga_distill_general for every shape it accepts (the TD3 learner's actor shapes: hidden a multiple of 4
+            in 4 .. 128, 0 .. 4 hidden layers, S <= 16, A <= 4 -- hidden 32 x 3 included); it is that kernel or a RuntimeError,
+            never PyTorch (the convention of TD3.train(dense=...)).
+            'auto': serl_ga_distill where it runs, else serl_ga_distill_general where it runs, else PyTorch.
+    dense   the dense phases of the general kernel: 'valu' or 'mfma' (the f32 matrix cores; the same bits).  'mfma' with 'serl50' is
+            a ValueError: that kernel has no such phases.
+    info    a dict that receives info['path']: 'fused' | 'fused-general' | 'fused-general-mfma' | 'torch'.
+    The draws from `rng` and torch's generator are the same on every path; a bad `kernel` / `dense` and a refused 'general' raise
+    before any of them.  The default stays 'serl50' until the measurements of tools/bench_distill.py
+    (profiles/distill_general_timing.json) have been weighed: whether it becomes 'auto' is decided from them, not here."""
     import ctypes
     import numpy as np
     from . import _capi
+    if kernel not in KERNELS:
+        raise ValueError('distil_batch: kernel must be one of %s, not %r' % (', '.join(KERNELS), kernel))
+    if dense not in DENSE:
+        raise ValueError('distil_batch: dense must be one of %s, not %r' % (', '.join(DENSE), dense))
+    if kernel == 'serl50' and dense != 'valu':
+        raise ValueError('distil_batch: dense=%r needs kernel=\'general\' or \'auto\' (serl_ga_distill has no matrix-core phases)' % dense)
     if critic is None:
         raise ValueError('distilation_crossover needs the learner\'s critic: SSNE(args, engine, spec, critic=...)')
     dev = weights.device
-    fused = dev.type == 'cuda' and spec.hidden == 32 and spec.num_layers == 3 and spec.state_dim <= 16 and spec.action_dim <= 4
-    if fused and pairs:
-        # probe before any host draw is consumed: n_pairs = 0 returns SERL_E_UNSUPPORTED when the training state does not fit
-        # this device's LDS per workgroup (the fused kernel needs ~158 KB), and then the pairs train one by one in PyTorch
-        z = ctypes.c_void_p(0)
-        one = torch.zeros(4, dtype=torch.int32, device=dev)
-        rc = _capi.lib().serl_ga_distill(engine.ctx, weights.data_ptr(), weights.stride(0), 0, spec.state_dim, spec.hidden, spec.num_layers,
-                                         spec.action_dim, spec.activation_id, weights.data_ptr(), weights.data_ptr(), weights.data_ptr(), 1,
-                                         one.data_ptr(), 0, one.data_ptr(), one.data_ptr(), ctypes.c_float(1e-3), z)
-        fused = rc == 0
-    if not fused or not pairs:
+    general_path = 'fused-general-mfma' if dense == 'mfma' else 'fused-general'
+    path = 'torch'
+    if kernel == 'general':
+        if dev.type != 'cuda' or not _probe(engine, spec, weights, True):
+            raise RuntimeError('distil_batch(kernel=\'general\'): serl_ga_distill_general does not run %r on %s%s' % (
+                spec, dev, (': ' + _capi.lib().serl_last_error().decode()) if dev.type == 'cuda' else ''))
+        path = general_path
+    else:
+        fused = dev.type == 'cuda' and spec.hidden == 32 and spec.num_layers == 3 and spec.state_dim <= 16 and spec.action_dim <= 4
+        if fused and pairs:
+            # probe before any host draw is consumed: n_pairs = 0 returns SERL_E_UNSUPPORTED when the training state does not fit
+            # this device's LDS per workgroup (the fused kernel needs ~158 KB), and then the pairs train one by one in PyTorch
+            fused = _probe(engine, spec, weights, False)
+        if fused:
+            path = 'fused'
+        elif kernel == 'auto' and dev.type == 'cuda' and _probe(engine, spec, weights, True):
+            path = general_path
+    if info is not None:
+        info['path'] = path
+    if path == 'torch' or not pairs:
         return [distilation_crossover(args, engine, spec, weights, f, s, buffers, critic, rng) for f, s in pairs]
     P, S, A = spec.param_count, spec.state_dim, spec.action_dim
     cap = int(args.individual_bs)
@@ -183,8 +229,14 @@ def distil_batch(args, engine, spec, weights, pairs, buffers, critic, rng=random
     ns_t = torch.tensor(nsteps, dtype=torch.int32, device=dev)
     bt_t = torch.tensor(batch, dtype=torch.int32, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
-    _capi.check(_capi.lib().serl_ga_distill(engine.ctx, child.data_ptr(), child.stride(0), K, S, spec.hidden, spec.num_layers, A,
-                                            spec.activation_id, states.data_ptr(), targets.data_ptr(), keep.data_ptr(), states.shape[1],
-                                            sl_t.data_ptr(), sl.shape[1], ns_t.data_ptr(), bt_t.data_ptr(), ctypes.c_float(1e-3),
-                                            ctypes.c_void_p(stream)), 'serl_ga_distill')
+    launch = (engine.ctx, child.data_ptr(), child.stride(0), K, S, spec.hidden, spec.num_layers, A, spec.activation_id, states.data_ptr(),
+              targets.data_ptr(), keep.data_ptr(), states.shape[1], sl_t.data_ptr(), sl.shape[1], ns_t.data_ptr(), bt_t.data_ptr(),
+              ctypes.c_float(1e-3))
+    if path == 'fused':
+        _capi.check(_capi.lib().serl_ga_distill(*launch, ctypes.c_void_p(stream)), 'serl_ga_distill')
+    else:
+        nbytes = int(_capi.lib().serl_ga_distill_general_work_bytes(K, S, A, spec.hidden, spec.num_layers))
+        work = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=dev)
+        _capi.check(_capi.lib().serl_ga_distill_general(*launch, work.data_ptr(), nbytes, int(dense == 'mfma'), ctypes.c_void_p(stream)),
+                    'serl_ga_distill_general')
     return [(child[k, :P], bufs[k], bufs[k].like()) for k in range(K)]

@@ -118,10 +118,14 @@ class SSNE:
     args     : the reference's Parameters fields (pop_size, elite_fraction, mutation_prob, mutation_mag, mut_type,
                distil_crossover, distil_type, crossover_prob, mutation_batch_size, individual_bs)
     critic   : callable (state, action) -> (q1, q2) on the device (TD3's critic); needed for distillation only
-    record   : optional list receiving the operator calls (kind, a, b) -- the index decisions the tests pin"""
+    record   : optional list receiving the operator calls (kind, a, b) -- the index decisions the tests pin
+    distil_kernel, distil_dense : which kernel trains an epoch's distillation children and its dense phases, passed to
+               distill.distil_batch (kernel=, dense=; checked there); what ran is kept in last_distil_path"""
 
-    def __init__(self, args, engine, spec, critic=None, record=None):
+    def __init__(self, args, engine, spec, critic=None, record=None, distil_kernel='serl50', distil_dense='valu'):
         self.args, self.engine, self.spec, self.critic, self.record = args, engine, spec, critic, record
+        self.distil_kernel, self.distil_dense = distil_kernel, distil_dense
+        self.last_distil_path = None           # info['path'] of the last distil_batch
         self.population_size = args.pop_size
         self.num_elitists = max(int(args.elite_fraction * args.pop_size), 1)
         self.rl_policy = None
@@ -173,7 +177,11 @@ class SSNE:
     def distilation_crossovers(self, weights, pairs, buffers):
         """independent distillations [(first, second)] -> children, trained together (distill.distil_batch)"""
         from . import distill
-        return distill.distil_batch(self.args, self.engine, self.spec, weights, pairs, buffers, self.critic)
+        info = {}
+        children = distill.distil_batch(self.args, self.engine, self.spec, weights, pairs, buffers, self.critic, kernel=self.distil_kernel,
+                                        dense=self.distil_dense, info=info)
+        self.last_distil_path = info['path']
+        return children
 
     # ---- the generation update ------------------------------------------------------------------------------------
     def epoch(self, weights, fitness_evals, bcs_evals=None, buffers=None, critical=None):
