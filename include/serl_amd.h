@@ -667,7 +667,11 @@ int serl_smoothness(serl_ctx *ctx, const double *actions, int64_t episode_stride
  * the parents and the critic contribute; they do not depend on the child and are computed once by the caller.
  * child: f32 [n_pairs][stride], in = the second parent's parameters, out = the trained child.  states [n_pairs][rows][S],
  * targets [n_pairs][rows][A], keep [n_pairs][rows], slots i32 [n_pairs][steps][128].  Compiled for hidden 32 x 3 layers
- * (SERL_E_UNSUPPORTED otherwise). */
+ * (SERL_E_UNSUPPORTED otherwise).
+ * What the device tables hold is clamped, never trusted with an address: a slot into [0, rows), batch[p] into [0, 128] (0: every
+ * step is a minibatch with no kept row -- an Adam step with zero gradients, which from zero moments leaves the row bit for bit as
+ * it was), n_steps[p] into [0, steps].  keep is a flag, not a weight: a row is kept when keep != 0 as f32 compares -- 2, -1, 0.5
+ * and a subnormal keep it exactly as 1 does, +0 and -0 drop it. */
 int serl_ga_distill(serl_ctx *ctx, float *child, int64_t stride, int32_t n_pairs, int32_t state_dim, int32_t hidden, int32_t num_layers,
                     int32_t action_dim, int32_t activation, const float *states, const float *targets, const float *keep, int32_t rows,
                     const int32_t *slots, int32_t steps, const int32_t *n_steps, const int32_t *batch, float lr, void *stream);
@@ -675,10 +679,15 @@ int serl_ga_distill(serl_ctx *ctx, float *child, int64_t stride, int32_t n_pairs
  * multiple of 4 in 4 .. 128, 0 .. 4 hidden layers, state_dim 1 .. 16, action_dim 1 .. 4, the three activations, minibatches of
  * 1 .. 128 rows -- hidden 32 x 3 included.  SERL_E_UNSUPPORTED otherwise, nothing touched.  Arguments and semantics are
  * serl_ga_distill's (a slot outside [0, rows) is clamped into it; n_steps[p] == 0 leaves row p bit for bit unchanged; columns past the
- * row and rows outside the launch are not written; an all-dropped minibatch takes its Adam step with zero gradients), plus
+ * row and rows outside the launch are not written; an all-dropped minibatch takes its Adam step with zero gradients; batch[p],
+ * n_steps[p] and keep are read by serl_ga_distill's rules above, n_steps[p] <= 0 writing nothing), plus
+ *   lr     > 0 (SERL_E_INVALID otherwise, NaN included); `stride` >= the row's parameter count, any remainder by 4: `child` and its
+ *          rows need the alignment of a float only.
  *   work   DEVICE scratch of serl_ga_distill_general_work_bytes(n_pairs, ..) bytes: per pair the gradients, Adam's two moments (zeroed
  *          by the kernel), the gathered minibatch and the backward pass's tape.  The child row itself is trained in place in `child`:
- *          at these shapes parameters, gradients and moments no longer fit the LDS serl_ga_distill keeps them in.
+ *          at these shapes parameters, gradients and moments no longer fit the LDS serl_ga_distill keeps them in.  Aligned as a
+ *          float (4 B), no more; what it holds on entry does not matter (NaN included), and no byte beyond work_bytes is touched.
+ *          NULL or too small: SERL_E_INVALID, nothing launched.
  *   dense  0 = the dense phases on the VALU, 1 = on the f32 matrix cores (v_mfma_f32_16x16x4_f32); the two give the same bits.
  * One workgroup per pair, built from the learner's phases (serl_td3_train); n_pairs == 0 is the probe "would this shape run here?",
  * for which `work` may be NULL.  serl_ga_distill_general_work_bytes returns 0 for a shape that is refused or n_pairs < 1. */

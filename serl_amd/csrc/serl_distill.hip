@@ -41,7 +41,7 @@ struct DistillArgs {
   int64_t stride;
   const float *states;          // [pairs][rows][S]   the child's buffer
   const float *targets;         // [pairs][rows][A]   the better parent's action per state
-  const float *keep;            // [pairs][rows]      1 = the Q-filter keeps the state, 0 = dropped
+  const float *keep;            // [pairs][rows]      != 0 (1) = the Q-filter keeps the state, +-0 = dropped
   const int32_t *slots;         // [pairs][steps][batch] rows of the minibatches, in the reference's sampling order
   const int32_t *n_steps;       // [pairs]
   const int32_t *batch;         // [pairs] (<= 128)
@@ -108,7 +108,8 @@ __global__ void __launch_bounds__(DB) distill_kernel(DistillArgs a)
   float *row = a.child + (size_t)p * a.stride;
   for (int e = t; e < P4; e += DB) { w[e] = e < P ? row[e] : 0.0f; g[e] = 0.0f; am[e] = 0.0f; av[e] = 0.0f; }
   __syncthreads();
-  const int steps = a.n_steps[p], B = a.batch[p];
+  // (what the caller's tables hold is clamped, never trusted: n_steps into [0, steps], batch into [0, DB], a slot into [0, rows))
+  const int steps = min(max(a.n_steps[p], 0), a.steps), B = min(max(a.batch[p], 0), DB);
   const float *st_p = a.states + (size_t)p * a.rows * S;
   const float *tg_p = a.targets + (size_t)p * a.rows * A;
   const float *kp_p = a.keep + (size_t)p * a.rows;
@@ -137,11 +138,11 @@ __global__ void __launch_bounds__(DB) distill_kernel(DistillArgs a)
 
   for (int step = 0; step < steps; ++step) {
     const bool live = t < B;
-    const int slot = live ? sl_p[(size_t)step * DB + t] : 0;
+    const int slot = live ? min(max(sl_p[(size_t)step * DB + t], 0), a.rows - 1) : 0;
     float s[DS_MAX];
 #pragma unroll
     for (int j = 0; j < DS_MAX; ++j) s[j] = (live && j < S) ? st_p[(size_t)slot * S + j] : 0.0f;
-    const float keep = live ? kp_p[slot] : 0.0f;
+    const float keep = (live && kp_p[slot] != 0.0f) ? 1.0f : 0.0f;        // a flag, not a weight: any value but +-0 keeps the row
     // ---------------- forward (genetic_agent.py:104, LayerNorm mod_utils.py:47-50)
     float mean[L], sd[L];
 #pragma unroll 2

@@ -7,7 +7,10 @@
 // vectors alone are 4 x 16 995 floats = 272 KB at S 7, A 3).  Here the child's row is trained in place in global memory, gradients and moments
 // live in the caller's workspace beside the gathered inputs and the tape (all L2-resident: < 1 MB per pair), and only the activations
 // of the layer at hand are in LDS (the learner's two tiles).  The semantics are serl_distill.hip's, restated in tests/distill64.py:
-//   * the rows of step `step` are slots[pair][step][0 .. B); a slot outside [0, rows) is clamped into it
+//   * the rows of step `step` are slots[pair][step][0 .. B); a slot outside [0, rows) is clamped into it, batch[pair] into [0, BP] and
+//     n_steps[pair] into [0, steps]: what the caller's tables hold is never trusted with an address
+//   * keep is a flag, not a weight: a row is kept when keep != 0 as f32 compares (2, -1, 0.5 and a subnormal keep it like 1 does; +0
+//     and -0 drop it)
 //   * loss = sum((out - target)^2) + mean(out^2) over the rows the keep mask keeps, the mean over kept x A
 //   * a minibatch with no kept row takes its Adam step with zero gradients
 //   * torch.optim.Adam's defaults with bias correction, no gradient clipping
@@ -29,7 +32,8 @@ struct DistillGArgs {
   float lr;
 };
 
-// a pair's workspace: gradients | first moments | second moments | the gathered states [S][BP] | the tape
+// a pair's workspace: gradients | first moments | second moments | the gathered states [S][BP] | the tape.  Every access to it is one
+// float wide: the workspace needs the alignment of a float (4 B) and no more, and so does the child row (f4u above is 4 B aligned).
 __host__ __device__ inline int distill_g_param_floats(int S, int A, int H, int L) { return (actor_params(S, A, H, L) + 3) & ~3; }
 __host__ __device__ inline int64_t distill_g_work_floats(int S, int A, int H, int L)
 {

@@ -130,9 +130,12 @@ class _EluGradExpm1(torch.autograd.Function):
         return g * torch.where(v > 0, torch.ones_like(v), torch.expm1(v))
 
 
-def distill_explicit64(d, mistake=None, lr=LR):
+def distill_explicit64(d, mistake=None, lr=LR, weight_by_keep=False, moments=None, return_moments=False):
     """distill64 with the forward pass, the loss and Adam written out in float64 (like distill._batched_forward), and at most one of
-    MISTAKES planted.  With mistake=None it is the reference (tests/test_distill_host.py checks that)."""
+    MISTAKES planted.  With mistake=None it is the reference (tests/test_distill_host.py checks that).
+    Two more mistakes, for tests/distill_general_edges.py, as arguments (the defaults are the contract): weight_by_keep -- a kept row's
+    terms of the loss are multiplied by its keep value instead of counted once; moments = (m, v) -- Adam's moments start from these
+    instead of zero.  return_moments: -> (parameters, m, v)."""
     assert mistake is None or mistake in MISTAKES, mistake
     s, B, n_steps = d['s'], d['B'], d['n_steps']
     S, A, H, L, actn = s['state_dim'], s['action_dim'], s['hidden'], s['num_layers'], s['activation']
@@ -167,6 +170,8 @@ def distill_explicit64(d, mistake=None, lr=LR):
         return torch.tanh(h @ W.T + b)
 
     m1, v1 = torch.zeros_like(w), torch.zeros_like(w)
+    if moments is not None:
+        m1, v1 = (torch.from_numpy(np.asarray(x, np.float64)).clone() for x in moments)
     t = 0
     for step in range(n_steps):
         idx = torch.from_numpy(d['slots'][step, :B].astype(np.int64))
@@ -177,9 +182,10 @@ def distill_explicit64(d, mistake=None, lr=LR):
         g = torch.zeros_like(w)                   # an all-dropped minibatch: no term reaches a weight
         if n:
             out = forward(st[idx])
-            loss = torch.sum((out - tg[idx]) ** 2)
+            kw = kp[idx][:, None] if weight_by_keep else 1.0
+            loss = torch.sum(kw * (out - tg[idx]) ** 2)
             if mistake != 'no_mean_term':
-                loss = loss + torch.sum(out ** 2) / ((B if mistake == 'mean_over_B' else n) * A)
+                loss = loss + torch.sum(kw * out ** 2) / ((B if mistake == 'mean_over_B' else n) * A)
             g, = torch.autograd.grad(loss, w)
         t += 1
         with torch.no_grad():
@@ -189,6 +195,8 @@ def distill_explicit64(d, mistake=None, lr=LR):
                 w -= lr * m1 / (v1.sqrt() + EPS)
             else:
                 w -= lr / (1 - BETA1 ** t) * m1 / (v1.sqrt() / np.sqrt(1 - BETA2 ** t) + EPS)
+    if return_moments:
+        return w.detach().numpy(), m1.numpy(), v1.numpy()
     return w.detach().numpy()
 
 

@@ -23,11 +23,14 @@ def _call(engine, child_ptr, stride, n_pairs, S, A, act_id, states, targets, kee
     return rc
 
 
-def _launch(engine, cases, n_steps=None, extra_rows=1, extra_steps=0, extra_cols=0):
+def _launch(engine, cases, n_steps=None, extra_rows=1, extra_steps=0, extra_cols=0, batch=None, n_steps_arg=None, unused_slot=None):
     """one launch for the pairs `cases` (make_case dicts of one shape) -> (child [K + 2, stride] after the launch, the same before).
     The launch covers rows 1 .. K of the child tensor; stride = the row's floats rounded up to 4 plus extra_cols.  Buffers are padded to
     the longest pair plus extra_rows rows of NaN, minibatch tables to the most steps plus extra_steps; every unused slot (columns from B
-    on, steps beyond a pair's n_steps) names a NaN row: a kernel that read one would return NaN."""
+    on, steps beyond a pair's n_steps) names a NaN row: a kernel that read one would return NaN.
+    For tests/test_gpu_distill_general_edges.py (the defaults are the above): batch, n_steps_arg -- what the kernel is handed per pair
+    in place of the pairs' B and of n_steps (the tables are still filled by those); unused_slot -- the value of every unused table
+    entry, and then neither it nor what the pairs' own tables hold needs to name a row."""
     from serl_amd.actor import ACTIVATION_IDS
     s = cases[0]['s']
     S, A, P = s['state_dim'], s['action_dim'], len(cases[0]['row'])
@@ -39,19 +42,20 @@ def _launch(engine, cases, n_steps=None, extra_rows=1, extra_steps=0, extra_cols
     st = np.full((K, rows, S), np.nan, np.float32)
     tg = np.full((K, rows, A), np.nan, np.float32)
     kp = np.ones((K, rows), np.float32)
-    sl = np.full((K, steps, 128), rows - 1, np.int32)
+    sl = np.full((K, steps, 128), rows - 1 if unused_slot is None else unused_slot, np.int32)
     child = np.full((K + 2, stride), 7.25, np.float32)
     for k, d in enumerate(cases):
         n = len(d['keep'])
         st[k, :n], tg[k, :n], kp[k, :n] = d['states'], d['targets'], d['keep']
         sl[k, :n_steps[k], :d['B']] = d['slots'][:n_steps[k], :d['B']]
         child[1 + k, :P] = d['row']
-    assert (sl >= 0).all() and (sl < rows).all()
+    assert unused_slot is not None or ((sl >= 0).all() and (sl < rows).all())
     dev = engine.device
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     ch = t(child)
     rc = _call(engine, ch[1].data_ptr(), stride, K, S, A, ACTIVATION_IDS[s['activation']], t(st), t(tg), t(kp), t(sl),
-               t(np.array(n_steps, np.int32)), t(np.array([d['B'] for d in cases], np.int32)))
+               t(np.array(n_steps if n_steps_arg is None else n_steps_arg, np.int32)),
+               t(np.array([d['B'] for d in cases] if batch is None else batch, np.int32)))
     assert rc == 0, rc
     return ch.cpu().numpy(), child
 

@@ -15,25 +15,36 @@ import distill64_shapes as G
 pytestmark = pytest.mark.gpu
 
 
-def _call(engine, child_ptr, stride, n_pairs, H, L, S, A, act_id, states, targets, keep, slots, n_steps, batch, dense=0, work='sized'):
+def _call(engine, child_ptr, stride, n_pairs, H, L, S, A, act_id, states, targets, keep, slots, n_steps, batch, dense=0, work='sized', lr=D.LR):
     """serl_ga_distill_general on device tensors (as distill.distil_batch calls it) -> status code; synchronised.  work='sized': a
-    workspace of serl_ga_distill_general_work_bytes, or none where that is 0 (a refused shape, the probe)."""
+    workspace of serl_ga_distill_general_work_bytes, or none where that is 0 (a refused shape, the probe); work = a float32 device
+    tensor: the caller's workspace, all of it and no more (tests/test_gpu_distill_general_edges.py)."""
     from serl_amd import _capi
     stream = torch.cuda.current_stream(engine.device).cuda_stream
-    nbytes = int(_capi.lib().serl_ga_distill_general_work_bytes(n_pairs, S, A, H, L))
-    wk = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=engine.device) if nbytes > 0 else None
+    if isinstance(work, torch.Tensor):
+        assert work.dtype == torch.float32 and work.is_contiguous()
+        wk, nbytes = work, 4 * work.numel()
+    else:
+        nbytes = int(_capi.lib().serl_ga_distill_general_work_bytes(n_pairs, S, A, H, L))
+        wk = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=engine.device) if nbytes > 0 else None
     rc = _capi.lib().serl_ga_distill_general(engine.ctx, child_ptr, stride, n_pairs, S, H, L, A, act_id, states.data_ptr(), targets.data_ptr(),
                                              keep.data_ptr(), states.shape[1], slots.data_ptr(), slots.shape[1], n_steps.data_ptr(),
-                                             batch.data_ptr(), ctypes.c_float(D.LR), wk.data_ptr() if wk is not None else None,
+                                             batch.data_ptr(), ctypes.c_float(lr), wk.data_ptr() if wk is not None else None,
                                              max(nbytes, 0), dense, ctypes.c_void_p(stream))
     torch.cuda.synchronize()
     return rc
 
 
-def _launch(engine, cases, dense=0, n_steps=None, extra_rows=1, extra_steps=0, extra_cols=0):
+def _launch(engine, cases, dense=0, n_steps=None, extra_rows=1, extra_steps=0, extra_cols=0, batch=None, n_steps_arg=None, lr=D.LR,
+            stride=None, work='sized', child_offset=0, unused_slot=None):
     """tests/test_gpu_distill.py::_launch for the general kernel: one launch for the pairs `cases` (make_case dicts of one shape) ->
     (child [K + 2, stride] after the launch, the same before).  The launch covers rows 1 .. K; buffers are padded with rows of NaN,
-    and every unused slot (columns from B on, steps beyond a pair's n_steps) names a NaN row: a kernel that read one would return NaN."""
+    and every unused slot (columns from B on, steps beyond a pair's n_steps) names a NaN row: a kernel that read one would return NaN.
+    For tests/test_gpu_distill_general_edges.py (the defaults are the above): batch, n_steps_arg -- what the kernel is handed per pair
+    in place of the pairs' B and of n_steps (the tables are still filled by those); lr; stride -- the row stride in floats, whatever
+    its remainder by 4; work -- _call's; child_offset -- the child tensor starts that many floats into its allocation (they are checked
+    to stay as they were); unused_slot -- the value of every unused table entry, and then neither it nor what the pairs' own tables
+    hold needs to name a row (with extra_rows = 0 there is no NaN row either)."""
     from serl_amd.actor import ACTIVATION_IDS
     s = cases[0]['s']
     S, A, H, L, P = s['state_dim'], s['action_dim'], s['hidden'], s['num_layers'], len(cases[0]['row'])
@@ -41,25 +52,29 @@ def _launch(engine, cases, dense=0, n_steps=None, extra_rows=1, extra_steps=0, e
     n_steps = [d['n_steps'] for d in cases] if n_steps is None else n_steps
     rows = max(len(d['keep']) for d in cases) + extra_rows
     steps = max(max(n_steps), 1) + extra_steps
-    stride = (P + 3) // 4 * 4 + extra_cols
+    stride = (P + 3) // 4 * 4 + extra_cols if stride is None else stride
     st = np.full((K, rows, S), np.nan, np.float32)
     tg = np.full((K, rows, A), np.nan, np.float32)
     kp = np.ones((K, rows), np.float32)
-    sl = np.full((K, steps, 128), rows - 1, np.int32)
-    child = np.full((K + 2, stride), 7.25, np.float32)
+    sl = np.full((K, steps, 128), rows - 1 if unused_slot is None else unused_slot, np.int32)
+    flat = np.full(child_offset + (K + 2) * stride, 7.25, np.float32)
+    child = flat[child_offset:].reshape(K + 2, stride)
     for k, d in enumerate(cases):
         n = len(d['keep'])
         st[k, :n], tg[k, :n], kp[k, :n] = d['states'], d['targets'], d['keep']
         sl[k, :n_steps[k], :d['B']] = d['slots'][:n_steps[k], :d['B']]
         child[1 + k, :P] = d['row']
-    assert (sl >= 0).all() and (sl < rows).all()
+    assert unused_slot is not None or ((sl >= 0).all() and (sl < rows).all())
     dev = engine.device
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    ch = t(child)
+    fl = t(flat)
+    ch = fl[child_offset:].view(K + 2, stride)
     rc = _call(engine, ch[1].data_ptr(), stride, K, H, L, S, A, ACTIVATION_IDS[s['activation']], t(st), t(tg), t(kp), t(sl),
-               t(np.array(n_steps, np.int32)), t(np.array([d['B'] for d in cases], np.int32)), dense)
+               t(np.array(n_steps if n_steps_arg is None else n_steps_arg, np.int32)),
+               t(np.array([d['B'] for d in cases] if batch is None else batch, np.int32)), dense, work, lr)
     assert rc == 0, rc
-    return ch.cpu().numpy(), child
+    assert (fl[:child_offset] == 7.25).all()
+    return ch.cpu().numpy(), child.copy()
 
 
 _REF, _RUN = {}, {}
