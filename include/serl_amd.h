@@ -197,9 +197,17 @@ enum serl_env_config { SERL_ENV_ATTITUDE = 0, SERL_ENV_SYMMETRIC = 1, SERL_ENV_F
  *          the episodes when concurrent_episodes > 0 -- and the episodes beyond those lane slots wait behind a device counter.  The only hint that is
  *          not ignored when lanes_per_wave > 0.  Attitude task, every code variant, every actor shape; serl_rollout only (serl_rollout_multi and
  *          serl_dyn_open_loop refuse it).  serl_last_rollout_info reports family SERL_FAMILY_LANE and whether the queue was engaged.  Opt-in:
- *          SERL_KERNEL_AUTO never chooses it. */
+ *          SERL_KERNEL_AUTO never chooses it.
+ *   LANEG  (hint 7) one LANE = one episode for EVERY actor shape: each live lane runs the whole forward pass of its own actor over its member's row of
+ *          [n_members][weight_stride] (serl_rollout_laneg_kernel_<variant>: activations in private memory, no LDS, no regrouped copy, weights streamed),
+ *          where the lane kernels of lanes_per_wave > 0 run up to 64 wavefront-wide passes per env step for any shape but hidden 32.  ceil(n_episodes /
+ *          lanes) wavefronts of lanes_per_wave lanes (0 = 64), no work queue; like LANEQ it is not ignored when lanes_per_wave > 0.  Accepted by
+ *          serl_rollout and serl_rollout_noise (serl_rollout_laneg_noise_kernel_<variant>); serl_rollout_multi and serl_dyn_open_loop refuse it.
+ *          SERL_E_UNSUPPORTED, before anything is planned, unless: the attitude task (env_config SERL_ENV_ATTITUDE, incremental 0), state_dim 7,
+ *          action_dim 3, hidden a multiple of 4 in 4 .. 128, num_layers 0 .. 16.  Every code variant.  serl_last_rollout_info reports family
+ *          SERL_FAMILY_LANEG.  Opt-in: SERL_KERNEL_AUTO never chooses it (measured: profiles/rollout_laneg_timing.json). */
 enum serl_kernel_hint { SERL_KERNEL_AUTO = 0, SERL_KERNEL_TEAM = 1, SERL_KERNEL_WAVE = 2, SERL_KERNEL_HALF = 3,
-                        SERL_KERNEL_TEAM2 = 4, SERL_KERNEL_TEAM4 = 5, SERL_KERNEL_LANEQ = 6 };
+                        SERL_KERNEL_TEAM2 = 4, SERL_KERNEL_TEAM4 = 5, SERL_KERNEL_LANEQ = 6, SERL_KERNEL_LANEG = SERL_KERNEL_LANEQ + 1 };
 /* length of the observation of a configuration (0 = invalid) and its number of actions */
 int serl_env_state_dim(int env_config, int incremental);
 int serl_env_action_dim(int env_config);
@@ -219,7 +227,7 @@ int serl_ctx_create(int device, serl_ctx **out);
 int serl_ctx_destroy(serl_ctx *ctx);
 int serl_ctx_load_build(serl_ctx *ctx, int slot, const serl_build_desc *build);
 /* Development overrides, read from the environment ONCE, by serl_ctx_create (the only getenv of the library):
- *   SERL_KERNEL=team|team2|team4|wave|half|laneq   kernel family for descriptors with kernel_hint == SERL_KERNEL_AUTO
+ *   SERL_KERNEL=team|team2|team4|wave|half|laneq|laneg   kernel family for descriptors with kernel_hint == SERL_KERNEL_AUTO
  *   SERL_WAVES_PER_BLOCK=n                   wavefronts per workgroup of the one-wavefront kernels
  *   SERL_LANEQ_WAVES=n                       SERL_KERNEL_LANEQ: at most n wavefronts per launch instead of 4 x CUs (tests engage the work queue with a handful of episodes)
  *   SERL_PROFILE=1                           cycle counters for serl_debug_profile
@@ -561,7 +569,8 @@ enum serl_kernel_family { SERL_FAMILY_NONE = 0, SERL_FAMILY_TEAM = 1 /* eight wa
                           SERL_FAMILY_TEAM4 = 7 /* four episodes per team */, SERL_FAMILY_TEAM4_MIXED = 8 /* ... several code variants in one launch */,
                           SERL_FAMILY_HALF = 9 /* one wavefront = two episodes */, SERL_FAMILY_WAVE = 10 /* one wavefront = one episode */,
                           SERL_FAMILY_WAVEX = 11 /* ... other env configurations */, SERL_FAMILY_LANE = 12 /* one lane = one episode */,
-                          SERL_FAMILY_TEAMR = 13 /* eight wavefronts = one episode, its streamed actor (two wavefronts) in a workgroup of its own on another CU */ };
+                          SERL_FAMILY_TEAMR = 13 /* eight wavefronts = one episode, its streamed actor (two wavefronts) in a workgroup of its own on another CU */,
+                          SERL_FAMILY_LANEG = SERL_FAMILY_TEAMR + 1 /* (family 14) one lane = one episode, every actor shape: kernel_hint SERL_KERNEL_LANEG */ };
 int serl_last_rollout_info(serl_ctx *ctx, int32_t out[8]);
 /* The same for the step-wise env: WHAT the most recent serl_venv_reset* / _step* / _rollout* call of this context launched (a record of its own:
  * serl_last_rollout_info keeps describing the last serl_rollout).  out[0] enum serl_kernel_family: SERL_FAMILY_LANE (one lane = one env) or

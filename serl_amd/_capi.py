@@ -206,10 +206,32 @@ TD3_ROW_STATUS.update({TD3_ROW_HANDOVER0 + s: what + ' ran out of time' for s, w
 
 
 # serl_rollout_desc.kernel_hint (enum serl_kernel_hint)
-KERNEL_HINTS = {None: 0, 'auto': 0, 'team': 1, 'wave': 2, 'half': 3, 'team2': 4, 'team4': 5, 'laneq': 6}
+class _Table(dict):
+    """A table of the binding that is pinned entry by entry (its length, its values) where it was last extended: later entries ride beside it in
+    `beside` -- t[key], key in t and t.get(key) find them, len(t) and iteration keep to the pinned entries."""
+
+    def __init__(self, pinned, beside):
+        super().__init__(pinned)
+        self.beside = dict(beside)
+
+    def __missing__(self, key):
+        return self.beside[key]
+
+    def __contains__(self, key):
+        return super().__contains__(key) or key in self.beside
+
+    def get(self, key, default=None):
+        return self[key] if key in self else default
+
+
+# SERL_KERNEL_LANEG / SERL_FAMILY_LANEG (include/serl_amd.h): the lane-per-episode population kernel for every actor shape
+KERNEL_LANEG = 7
+FAMILY_LANEG = 14
+KERNEL_HINTS = _Table({None: 0, 'auto': 0, 'team': 1, 'wave': 2, 'half': 3, 'team2': 4, 'team4': 5, 'laneq': 6}, {'laneg': KERNEL_LANEG})
 ABI_VERSION = 9
 # serl_last_rollout_info out[0] (enum serl_kernel_family)
-FAMILIES = {0: None, 1: 'team', 2: 'teams', 3: 'teams2', 4: 'teamx', 5: 'team2', 6: 'team2s', 7: 'team4', 8: 'team4_mixed', 9: 'half', 10: 'wave', 11: 'wavex', 12: 'lane', 13: 'teamr'}
+FAMILIES = _Table({0: None, 1: 'team', 2: 'teams', 3: 'teams2', 4: 'teamx', 5: 'team2', 6: 'team2s', 7: 'team4', 8: 'team4_mixed', 9: 'half', 10: 'wave', 11: 'wavex', 12: 'lane', 13: 'teamr'},
+                  {FAMILY_LANEG: 'laneg'})
 
 
 def expected_layout():

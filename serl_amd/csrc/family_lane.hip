@@ -42,13 +42,13 @@ static_assert(8 * (CIT_RO_LDS_WORDS + CIT_V(_NSLOPE)) <= 160 * 1024, "tables + i
 #ifdef CIT_WITH_CMD_IN_MEMORY      // (A/B builds around gen files made with CITW_LANE_CMDMEM=1: measured slower)
 #define CIT_CMD_IN_MEMORY 1
 #endif
-#ifndef SERL_ROLLOUT_NOISE     // (family_lanern.hip: serl_rollout_noise_kernel_<v> alone -- the work-queue body has no noise instantiation)
+#if !defined(SERL_ROLLOUT_NOISE) && !defined(SERL_LANE_GENERAL_ACTOR)     // (family_lanern.hip: serl_rollout_noise_kernel_<v> alone -- the work-queue body has no noise instantiation; family_laneg.hip / family_lanegn.hip: the episode kernel around the general lane actor alone)
 #define SERL_LANE_QUEUE 1      // (rollout_variant.inc: the work-queue kernel serl_rollout_laneq_kernel_<v> beside serl_rollout_kernel_<v>)
 #endif
 #define CIT_Y_IS_STATE 1      // (gen/citation_<variant>_lane.inc: `if (major) c->Y[i] = X[i]`, i < 12 -- the outputs of step() are the states in front of the integration)
 #include "citation_step_dev.h"
 #include "rollout_variant.inc"
-#ifndef SERL_ROLLOUT_NOISE
+#if !defined(SERL_ROLLOUT_NOISE) && !defined(SERL_LANE_GENERAL_ACTOR)
 #include "venv_variant.inc"
 #endif
 #undef CIT_NO_AXES
@@ -57,7 +57,13 @@ static_assert(8 * (CIT_RO_LDS_WORDS + CIT_V(_NSLOPE)) <= 160 * 1024, "tables + i
 }  // namespace bdag
 
 #define SERL_V(x) SERL_PASTE(x, VARIANT)
-#ifdef SERL_ROLLOUT_NOISE   // family_lanern.hip: the episode kernel with the in-kernel noise generator, nothing else
+#ifdef SERL_LANE_GENERAL_ACTOR   // family_laneg.hip / family_lanegn.hip: the episode kernel around the general lane actor (plain / with the in-kernel noise generator), nothing else
+#ifdef SERL_ROLLOUT_NOISE
+void SERL_V(serl_launch_rollout_laneg_noise_)(const RolloutArgs &a, const serl_rollout_noise_desc &nz, int grid, hipStream_t stream) { bdag::SERL_V(serl_launch_rollout_laneg_noise_)(a, nz, grid, stream); }
+#else
+void SERL_V(serl_launch_rollout_laneg_)(const RolloutArgs &a, int grid, hipStream_t stream) { bdag::SERL_V(serl_launch_rollout_laneg_)(a, grid, stream); }
+#endif
+#elif defined(SERL_ROLLOUT_NOISE)   // family_lanern.hip: the episode kernel with the in-kernel noise generator, nothing else
 void SERL_V(serl_launch_rollout_noise_)(const RolloutArgs &a, const serl_rollout_noise_desc &nz, int grid, hipStream_t stream) { bdag::SERL_V(serl_launch_rollout_noise_)(a, nz, grid, stream); }
 #elif defined(SERL_VENV_NOISE)     // family_lanenz.hip: the env kernels with the in-kernel noise generator, nothing else
 #define SERL_VNZ(x) SERL_PASTE(SERL_PASTE(x, noise_), VARIANT)

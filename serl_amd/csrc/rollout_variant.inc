@@ -79,11 +79,25 @@ static __device__ void V_NAME(serl_wave_episodes_)(const RolloutArgs &a, int e, 
 
   const bool prof = a.prof != nullptr && blockIdx.x == 0 && threadIdx.x < 64;
   unsigned long long pc_actor = 0, pc_dyn = 0, pc_env = 0, pc_steps = 0, tc0 = 0, tc1 = 0, tc2 = 0;
+#ifndef SERL_LANE_GENERAL_ACTOR
   const bool lane_actor = __builtin_amdgcn_readfirstlane((int)serl_lane_actor_ok(d)) != 0;
+#endif
   for (;;) {
     const unsigned long long live = __ballot(!done);
     if (live == 0ULL) break;
     if (prof) tc0 = __builtin_readcyclecounter();
+#ifdef SERL_LANE_GENERAL_ACTOR
+    // ---- actor forward (family_laneg.hip, kernel_hint SERL_KERNEL_LANEG): every live lane runs its own actor of ANY shape over its member's row of
+    // [members][P] (rollout_device.h serl_actor_forward_lane_general: activations in private memory, no LDS, no regrouped copy); a lane without an
+    // episode or with a finished one sits the pass out and loads no weight
+    float act[3] = {0.0f, 0.0f, 0.0f};
+    if (!done) {
+      float obs16[16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) obs16[i] = i < 7 ? (float)obs[i] : 0.0f;
+      serl_actor_forward_lane_general(d, w, obs16, act);
+    }
+#else
     // ---- actor forward for every live episode of this wavefront, one after the other, 64 lanes each
     float obsf[7], act[3] = {0.0f, 0.0f, 0.0f};
     for (int i = 0; i < 7; ++i) obsf[i] = (float)obs[i];
@@ -101,6 +115,7 @@ static __device__ void V_NAME(serl_wave_episodes_)(const RolloutArgs &a, int e, 
       serl_actor_forward_wave(d, (const float *)wp, o, r);
       if (lane == l) { act[0] = r[0]; act[1] = r[1]; act[2] = r[2]; }
     }
+#endif
     if (prof) { tc1 = __builtin_readcyclecounter(); pc_actor += tc1 - tc0; }
     if (done) continue;
     // ---- env step (envs/phlabenv.py:430-482), per lane
@@ -374,7 +389,31 @@ static __device__ __forceinline__ int V_NAME(serl_stage_and_index_)(const Rollou
 }
 
 #ifndef SERL_VENV_NOISE
-#ifdef SERL_ROLLOUT_NOISE      // (family_lanern.hip: the episode kernel with the generator, nothing else)
+#ifdef SERL_LANE_GENERAL_ACTOR      // (family_laneg.hip / family_lanegn.hip: the episode kernel around the general lane actor, plain or with the generator, nothing else)
+#ifdef SERL_ROLLOUT_NOISE
+__global__ void __launch_bounds__(SERL_BLOCK) V_NAME(serl_rollout_laneg_noise_kernel_)(RolloutArgs a, const serl_rollout_noise_desc nz)
+{
+  const int e = V_NAME(serl_stage_and_index_)(a);
+  V_NAME(serl_wave_episodes_)(a, nz, e < 0 ? 0 : e, e >= 0);
+}
+
+void V_NAME(serl_launch_rollout_laneg_noise_)(const RolloutArgs &a, const serl_rollout_noise_desc &nz, int grid, hipStream_t stream)
+{
+  hipLaunchKernelGGL(V_NAME(serl_rollout_laneg_noise_kernel_), dim3(grid), dim3(a.block), 0, stream, a, nz);
+}
+#else
+__global__ void __launch_bounds__(SERL_BLOCK) V_NAME(serl_rollout_laneg_kernel_)(RolloutArgs a)
+{
+  const int e = V_NAME(serl_stage_and_index_)(a);
+  V_NAME(serl_wave_episodes_)(a, e < 0 ? 0 : e, e >= 0);
+}
+
+void V_NAME(serl_launch_rollout_laneg_)(const RolloutArgs &a, int grid, hipStream_t stream)
+{
+  hipLaunchKernelGGL(V_NAME(serl_rollout_laneg_kernel_), dim3(grid), dim3(a.block), 0, stream, a);
+}
+#endif
+#elif defined(SERL_ROLLOUT_NOISE)      // (family_lanern.hip: the episode kernel with the generator, nothing else)
 __global__ void __launch_bounds__(SERL_BLOCK) V_NAME(serl_rollout_noise_kernel_)(RolloutArgs a, const serl_rollout_noise_desc nz)
 {
   const int e = V_NAME(serl_stage_and_index_)(a);

@@ -25,6 +25,7 @@ typedef void SerlLaunchVenvRollout(const RolloutArgs &a, const VenvArgs &v, cons
 #define SERL_LAUNCHERS(X, v)                                                                                                                     \
   X(SerlLaunch, lane, serl_launch_rollout_##v)              /* one episode per lane (family_lane.hip, rollout_variant.inc) */                   \
   X(SerlLaunch, laneq, serl_launch_rollout_laneq_##v)       /* ... finished lanes take the next episode from a work queue */                    \
+  X(SerlLaunch, laneg, serl_launch_rollout_laneg_##v)       /* ... every lane its own actor of any shape (family_laneg.hip) */                  \
   X(SerlLaunchDyn, dyn_lane, serl_launch_dyn_##v)                                                                                                \
   X(SerlLaunchVenv, venv_reset, serl_launch_venv_reset_##v) /* the step-wise vector env, one lane per env (venv_variant.inc) */                  \
   X(SerlLaunchVenv, venv_step, serl_launch_venv_step_##v)                                                                                        \
@@ -108,11 +109,12 @@ struct SerlVwrLaunchers { SERL_VWR_LAUNCHERS(SERL_MEMBER, v) };
 SERL_VARIANTS(SERL_VWR_VARIANT_DECL)
 static const SerlVwrLaunchers k_vwr_launchers[] = {SERL_VARIANTS(SERL_VWR_VARIANT_ROW)};
 
-// the population rollout kernels with the in-kernel noise generator (family_lanern.hip, family_wavern.hip: rollout_variant.inc / rollout_wave.inc under
-// SERL_ROLLOUT_NOISE), one record per code variant as above
+// the population rollout kernels with the in-kernel noise generator (family_lanern.hip, family_lanegn.hip, family_wavern.hip: rollout_variant.inc /
+// rollout_wave.inc under SERL_ROLLOUT_NOISE), one record per code variant as above
 typedef void SerlLaunchNz(const RolloutArgs &a, const serl_rollout_noise_desc &nz, int grid, hipStream_t stream);
 #define SERL_RN_LAUNCHERS(X, v)                                  \
   X(SerlLaunchNz, lane, serl_launch_rollout_noise_##v)           \
+  X(SerlLaunchNz, laneg, serl_launch_rollout_laneg_noise_##v)    \
   X(SerlLaunchNz, wave, serl_launch_rollout_wave_noise_##v)      \
   X(SerlLaunchNz, wavex, serl_launch_rollout_wavex_noise_##v)
 struct SerlRnLaunchers { SERL_RN_LAUNCHERS(SERL_MEMBER, v) };
@@ -143,6 +145,7 @@ static SerlLaunch *SerlLaunchers::*serl_rollout_launcher(const SerlPlan &p)
     case SERL_FAMILY_WAVE: return &SerlLaunchers::wave;
     case SERL_FAMILY_WAVEX: return &SerlLaunchers::wavex;
     case SERL_FAMILY_LANE: return p.laneq ? &SerlLaunchers::laneq : &SerlLaunchers::lane;
+    case SERL_FAMILY_LANEG: return &SerlLaunchers::laneg;
     default: return nullptr;
   }
 }
@@ -152,6 +155,7 @@ static SerlLaunchNz *SerlRnLaunchers::*serl_noise_launcher(const SerlPlan &p)
     case SERL_FAMILY_WAVE: return &SerlRnLaunchers::wave;
     case SERL_FAMILY_WAVEX: return &SerlRnLaunchers::wavex;
     case SERL_FAMILY_LANE: return p.laneq ? nullptr : &SerlRnLaunchers::lane;
+    case SERL_FAMILY_LANEG: return &SerlRnLaunchers::laneg;
     default: return nullptr;
   }
 }
@@ -342,7 +346,7 @@ int serl_ctx_create(int device, serl_ctx **out)
     if ((e = getenv("SERL_KERNEL")) != nullptr) {
       const std::string k(e);
       c->caps.env_kernel = k == "team" ? SERL_KERNEL_TEAM : k == "team2" ? SERL_KERNEL_TEAM2 : k == "team4" ? SERL_KERNEL_TEAM4
-                    : k == "wave" ? SERL_KERNEL_WAVE : k == "half" ? SERL_KERNEL_HALF : k == "laneq" ? SERL_KERNEL_LANEQ : SERL_KERNEL_AUTO;
+                    : k == "wave" ? SERL_KERNEL_WAVE : k == "half" ? SERL_KERNEL_HALF : k == "laneq" ? SERL_KERNEL_LANEQ : k == "laneg" ? SERL_KERNEL_LANEG : SERL_KERNEL_AUTO;
     }
     c->caps.env_laneq_waves = (e = getenv("SERL_LANEQ_WAVES")) ? atoi(e) : -1;
     c->caps.env_waves_per_block = (e = getenv("SERL_WAVES_PER_BLOCK")) ? atoi(e) : -1;

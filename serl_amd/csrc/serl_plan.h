@@ -174,6 +174,20 @@ static inline int serl_plan_check(const SerlCaps *c, const serl_rollout_desc *d,
 {
 #define SERL_PLAN_FAIL(code, text) return (*message = (text), (code))
   const bool general_env = serl_plan_general_env(d);
+  if (serl_resolve_hint(c, d->kernel_hint) == SERL_KERNEL_LANEG) {
+    // the limits of the lane kernel around the general lane actor (family_laneg.hip; rollout_device.h serl_actor_forward_lane_general), each by its name,
+    // in front of every other check: nothing is planned for a call the hint refuses
+    if (d->env_config != SERL_ENV_ATTITUDE)
+      SERL_PLAN_FAIL(SERL_E_UNSUPPORTED, "serl_rollout: kernel_hint LANEG: env_config must be SERL_ENV_ATTITUDE (the lane-per-episode kernels exist for the attitude task only)");
+    if (d->incremental != 0)
+      SERL_PLAN_FAIL(SERL_E_UNSUPPORTED, "serl_rollout: kernel_hint LANEG: incremental must be 0 (the lane-per-episode kernels exist for the attitude task only)");
+    if (d->state_dim != 7 || d->action_dim != 3)
+      SERL_PLAN_FAIL(SERL_E_UNSUPPORTED, "serl_rollout: kernel_hint LANEG: state_dim must be 7 and action_dim 3");
+    if (d->hidden % 4 != 0 || d->hidden < 4 || d->hidden > SERL_PLAN_MAX_HIDDEN)
+      SERL_PLAN_FAIL(SERL_E_UNSUPPORTED, "serl_rollout: kernel_hint LANEG: hidden must be a multiple of 4 in 4 .. 128");
+    if (d->num_layers < 0 || d->num_layers > 16)
+      SERL_PLAN_FAIL(SERL_E_UNSUPPORTED, "serl_rollout: kernel_hint LANEG: num_layers must be 0 .. 16");
+  }
   if (serl_plan_env_state_dim(d->env_config, d->incremental) == 0)
     SERL_PLAN_FAIL(SERL_E_INVALID, "serl_rollout: env_config must be SERL_ENV_ATTITUDE, SERL_ENV_SYMMETRIC or SERL_ENV_FULL");
   if (d->state_dim != serl_plan_env_state_dim(d->env_config, d->incremental) || d->action_dim != serl_plan_env_action_dim(d->env_config))
@@ -188,9 +202,10 @@ static inline int serl_plan_check(const SerlCaps *c, const serl_rollout_desc *d,
   if (d->weight_stride < serl_plan_param_count(d->state_dim, d->hidden, d->num_layers, d->action_dim))
     SERL_PLAN_FAIL(SERL_E_INVALID, "serl_rollout: weight_stride smaller than the parameter count");
   if (d->max_steps <= 0) SERL_PLAN_FAIL(SERL_E_INVALID, "serl_rollout: max_steps");
-  if (d->kernel_hint < SERL_KERNEL_AUTO || d->kernel_hint > SERL_KERNEL_LANEQ) SERL_PLAN_FAIL(SERL_E_INVALID, "serl_rollout: kernel_hint");
-  // (LANEQ is the one hint lanes_per_wave > 0 does not switch off: there it is the lanes per wavefront of the work-queue kernel)
-  const int hint = (d->lanes_per_wave > 0 && serl_resolve_hint(c, d->kernel_hint) != SERL_KERNEL_LANEQ) ? SERL_KERNEL_AUTO : serl_resolve_hint(c, d->kernel_hint);
+  if (d->kernel_hint < SERL_KERNEL_AUTO || d->kernel_hint > SERL_KERNEL_LANEG) SERL_PLAN_FAIL(SERL_E_INVALID, "serl_rollout: kernel_hint");
+  // (LANEQ and LANEG are the hints lanes_per_wave > 0 does not switch off: there it is the lanes per wavefront of the work-queue kernel / of the general lane kernel)
+  const int rhint = serl_resolve_hint(c, d->kernel_hint);
+  const int hint = (d->lanes_per_wave > 0 && rhint != SERL_KERNEL_LANEQ && rhint != SERL_KERNEL_LANEG) ? SERL_KERNEL_AUTO : rhint;
   if (d->hidden != 32 && (hint == SERL_KERNEL_TEAM4 || hint == SERL_KERNEL_HALF))
     SERL_PLAN_FAIL(SERL_E_UNSUPPORTED, "serl_rollout: kernel_hint TEAM4 / HALF needs hidden = 32 (other shapes: TEAM2, the actor wavefront runs the two episodes one after the other)");
 #undef SERL_PLAN_FAIL
@@ -221,8 +236,8 @@ static inline SerlPlan serl_plan_rollout(const SerlCaps *c, const serl_rollout_d
   // not recorded for them (an event in flight on one stream must not be re-recorded on another)
   const int timed = d->concurrent_episodes <= 0;
   const int together = n + (d->concurrent_episodes > 0 ? d->concurrent_episodes : 0);   // episodes sharing the GPU
-  if (noise && hint != SERL_KERNEL_AUTO && hint != SERL_KERNEL_WAVE)
-    return serl_plan_refuse(SerlPlan{}, "serl_rollout_noise: the TEAM / TEAM2 / TEAM4 / HALF / LANEQ kernels have no noise instantiation (kernel_hint AUTO or WAVE, or lanes_per_wave > 0)");
+  if (noise && hint != SERL_KERNEL_AUTO && hint != SERL_KERNEL_WAVE && hint != SERL_KERNEL_LANEG)
+    return serl_plan_refuse(SerlPlan{}, "serl_rollout_noise: the TEAM / TEAM2 / TEAM4 / HALF / LANEQ kernels have no noise instantiation (kernel_hint AUTO, WAVE or LANEG, or lanes_per_wave > 0)");
   if (general_env) {
     // observation set / number of actions / incremental control from the descriptor: the team kernel while the episodes fit two
     // rounds of workgroups (2 x ~23 us per env step against 57 of one wavefront per episode), one wavefront per episode beyond
@@ -255,6 +270,14 @@ static inline SerlPlan serl_plan_rollout(const SerlCaps *c, const serl_rollout_d
     p.regroup = serl_lane_regroup_shape(c, d);
     // the lane slots are those of `waves` wavefronts (a last workgroup may hold wavefronts beyond them: their lanes find no episode and leave)
     serl_plan_queue(p, n, (long long)waves * lanes);
+    return p;
+  }
+  if (hint == SERL_KERNEL_LANEG) {
+    // One episode per lane, every lane its own actor of any shape over its member's row (family_laneg.hip / family_lanegn.hip: rollout_variant.inc under
+    // SERL_LANE_GENERAL_ACTOR): the launch shape of lanes_per_wave > 0 (0 = 64 lanes), no queue, no regrouped copy -- the rows are streamed as they lie.
+    // serl_plan_check has refused every shape and env configuration the kernel does not take.
+    SerlPlan p = serl_plan_lanes(c, timed, n, (lanes <= 0 || lanes > 64) ? 64 : lanes, 1);
+    p.family = SERL_FAMILY_LANEG;
     return p;
   }
   if (!noise && lanes <= 0 && serl_use_team(c, hint, together)) {

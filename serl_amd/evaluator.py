@@ -99,7 +99,7 @@ class RolloutEngine:
         self.num_cus = torch.cuda.get_device_properties(self.device).multi_processor_count
         self.multi_launches = 0          # serl_rollout_multi launches made (a mixed sweep as one launch of one code object)
         # serl_rollout_desc.kernel_hint of rollouts that do not name one (None = chosen from the episode count); tests and
-        # A/B measurements set it to compare the kernel families ('team', 'team2', 'team4', 'wave', 'half', 'laneq')
+        # A/B measurements set it to compare the kernel families ('team', 'team2', 'team4', 'wave', 'half', 'laneq', 'laneg')
         self.kernel_hint = None
 
     def close(self):
@@ -149,8 +149,12 @@ class RolloutEngine:
         0 and 1 of every episode (None: the episode's index in this call / 0), so episode e draws what venv_noise(noise_seed, noise_env[e],
         noise_episode[e], T + 1, 'sensor') and venv_noise(..., T, 'action', noise_sd=, noise_clip=) write out -- the rows the table path takes.
         noise_sd / noise_clip (>= 0) belong to action_noise='device'.  sensor_row / noise_row i32 [E] keep their meaning as masks: < 0 = this episode
-        has no such noise.  Runs the lane kernels (lanes_per_wave > 0, or where the library's choice falls on them) or the wave / wavex kernels;
-        kernel= 'team', 'team2', 'team4', 'half', 'laneq' and launch=False are refused."""
+        has no such noise.  Runs the lane kernels (lanes_per_wave > 0, kernel='laneg', or where the library's choice falls on them) or the wave / wavex
+        kernels; kernel= 'team', 'team2', 'team4', 'half', 'laneq' and launch=False are refused.
+
+        kernel='laneg' (lanes_per_wave 0 .. 64, 0 = 64): the lane-per-episode kernel in which every lane runs its own actor of ANY shape (hidden a
+        multiple of 4 in 4 .. 128, 0 .. 16 hidden layers) over its member's row -- the attitude task only; a shape or env configuration it does not
+        take is a RuntimeError with the library's text, before any launch.  Same results bit for bit."""
         dev_noise = self._check_device_noise(len(np.asarray(member_of_episode).reshape(-1)), sensor_noise, action_noise, sensor_row, noise_row, noise_seed,
                                              noise_env, noise_episode, noise_sd, noise_clip, kernel if kernel is not None else getattr(self, 'kernel_hint', None), launch)
         dev_sensor, dev_action = dev_noise is not None and dev_noise[0], dev_noise is not None and dev_noise[1]
@@ -296,7 +300,7 @@ class RolloutEngine:
             if on and v is not None and np.asarray(v).shape != (E,):
                 raise ValueError("%s: with device noise a mask i32 [%d] (< 0: the episode has no such noise), not %s" % (name, E, np.asarray(v).shape))
         if kernel in ('team', 'team2', 'team4', 'half', 'laneq'):
-            raise ValueError("device noise runs the lane kernels (lanes_per_wave > 0) or the wave kernels (kernel='wave' / None), not kernel=%r" % (kernel,))
+            raise ValueError("device noise runs the lane kernels (lanes_per_wave > 0, kernel='laneg') or the wave kernels (kernel='wave' / None), not kernel=%r" % (kernel,))
         if not launch:
             raise ValueError('device noise: launch=False (rollout_multi) takes no generator; one launch per build')
         return dev_sensor, dev_action
@@ -317,7 +321,7 @@ class RolloutEngine:
 
     def last_rollout_info(self):
         """WHAT the most recent rollout / rollout_multi call launched (C ABI v8 serl_last_rollout_info): dict(family = 'team' | 'teams' | 'teams2' |
-        'teamx' | 'team2' | 'team2s' | 'team4' | 'team4_mixed' | 'half' | 'wave' | 'wavex' | 'lane', workgroups, episodes_per_team, work_queue,
+        'teamx' | 'team2' | 'team2s' | 'team4' | 'team4_mixed' | 'half' | 'wave' | 'wavex' | 'lane' | 'teamr' | 'laneg', workgroups, episodes_per_team, work_queue,
         actor_wavefronts, actor_streamed, launches, code).  Does not wait for the device."""
         out = (ctypes.c_int32 * 8)()
         _capi.check(self.lib.serl_last_rollout_info(self.ctx, out), 'serl_last_rollout_info')
@@ -393,10 +397,13 @@ def evaluate_pop(actors, *, mode='nominal', num_evals=3, refs=None, t_max=80, sm
              does not reset the model clock, so in its sequential loop episode j of a process starts at
              tick = sum over earlier episodes of (steps + 1); only the time-switched builds (cg-shift, gust) care.
     lanes_per_wave : 0 = kernels chosen from the episode count; 1..64 = the lane-per-episode kernels with that many episodes per wavefront
-    kernel     : kernel family of every launch ('team', 'team2', 'team4', 'wave', 'half', 'laneq'; None = the engine's kernel_hint, by default chosen
+    kernel     : kernel family of every launch ('team', 'team2', 'team4', 'wave', 'half', 'laneq', 'laneg'; None = the engine's kernel_hint, by default chosen
                  from the episode count).  Results are bit-identical.  'laneq': one episode per lane, and a lane whose episode ends takes the next one
                  from a work queue (populations whose episodes differ in length: untrained actors crash within seconds); lanes_per_wave is then the
-                 lanes per wavefront (0 = 64), and several builds fly one launch per build, never serl_rollout_multi
+                 lanes per wavefront (0 = 64), and several builds fly one launch per build, never serl_rollout_multi.  'laneg': one episode per
+                 lane for EVERY actor shape (hidden 72 x 3, 96 x 3 ...: each lane runs its own actor over its member's row; lanes_per_wave as for
+                 'laneq'), the attitude task only, with or without sensor_noise='device'; a shape or env configuration it does not take is a
+                 RuntimeError with the library's text before any launch.  Opt-in, measured in profiles/rollout_laneg_timing.json
     concurrent : False = the per-build launches run one after the other (A/B switch)
     fused      : several builds as ONE launch of one code object (C ABI v7 serl_rollout_multi), its workgroups placed so that CUs which share an
                  instruction cache run the same code variant.  'auto' (default) and True: whenever the library accepts the combination (more than
@@ -425,7 +432,7 @@ def evaluate_pop(actors, *, mode='nominal', num_evals=3, refs=None, t_max=80, sm
         if isinstance(noise_episode, bool) or int(noise_episode) != noise_episode or not -2**31 <= int(noise_episode) < 2**31:
             raise ValueError('noise_episode: an i32 integer, not %r' % (noise_episode,))
         if (kernel if kernel is not None else getattr(engine, 'kernel_hint', None)) in ('team', 'team2', 'team4', 'half', 'laneq'):
-            raise ValueError("sensor_noise='device' runs the lane kernels (lanes_per_wave > 0) or the wave kernels (kernel='wave' / None), not kernel=%r" % (kernel,))
+            raise ValueError("sensor_noise='device' runs the lane kernels (lanes_per_wave > 0, kernel='laneg') or the wave kernels (kernel='wave' / None), not kernel=%r" % (kernel,))
         if seed is None:
             seed = int(np.random.randint(0, 2**32)) << 32 | int(np.random.randint(0, 2**32))
         seed = int(seed)
@@ -501,7 +508,7 @@ def evaluate_pop(actors, *, mode='nominal', num_evals=3, refs=None, t_max=80, sm
     # rollout_team4_mixed.hip), which can place its workgroups: two code variants on CUs that share an instruction cache cost 12 %.  The library says
     # whether the combination is eligible; if not, nothing was launched and the launches below run side by side as before.
     use_multi = False
-    laneq = (kernel if kernel is not None else engine.kernel_hint) == 'laneq'      # (the library refuses it in serl_rollout_multi: one launch per build)
+    laneq = (kernel if kernel is not None else engine.kernel_hint) in ('laneq', 'laneg')      # (the library refuses them in serl_rollout_multi: one launch per build)
     if not laneq and not dev_sensor and many and (fused is True or (fused == 'auto' and E > 2 * engine.num_cus)) and 2 <= len(groups) <= 4 and lanes_per_wave == 0 and env_cfg == 0 and not incremental and spec.hidden == 32:
         prepared = [(np.asarray(idx), one_build(b, np.asarray(idx), cur, sync=False, launch=False)) for b, idx in groups.items()]
         if engine.rollout_multi([o for _, o in prepared]):
