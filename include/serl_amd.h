@@ -538,6 +538,21 @@ int serl_rollout_noise_layout(int32_t *out, int32_t capacity);
  * what serl_rollout computes.  serl_last_rollout_info records the family (LANE / WAVE / WAVEX) as for serl_rollout.  serl_rollout_multi
  * takes no such descriptor. */
 int serl_rollout_noise(serl_ctx *ctx, const serl_rollout_desc *desc, const serl_rollout_noise_desc *nz, void *stream);
+/* serl_rollout (nz == NULL: no generator) / serl_rollout_noise (nz != NULL) of kernel_hint SERL_KERNEL_LANEG over a REGROUPED copy of the weights: in front
+ * of the launch the population [n_members][weight_stride] is copied to [ceil(P / 4)][roundup(n_members, 64)][4] (parameter p of member m at float
+ * ((p >> 2) * members + m) * 4 + (p & 3)), and every lane reads its member's 16 bytes of a group at a wave-uniform base: 64 lanes whose members are
+ * consecutive read one run of 1 KB per load where the rows of LANEG cost 64 cache lines (serl_rollout_lanegt_kernel_<variant> /
+ * serl_rollout_lanegt_noise_kernel_<variant>; the arithmetic, and so every result, is LANEG's bit for bit).  Opt-in; kernel_hint LANEG through serl_rollout
+ * keeps streaming the rows.
+ * MEMORY: one copy is ceil(P / 4) x roundup(n_members, 64) x 16 bytes, P = serl_param_count(...) -- 7.75 GB for 65 536 members of hidden 96 x 3 layers
+ * (4.46 GB at 72 x 3; 1.11 GB at 72 x 3 for 16 384), 4.4 MB for 50 members of 72 x 3 -- and up to SERL_WT_SLOTS = 4 copies live at once: the copy of a launch goes into a ring of
+ * four slots that the context keeps (each grown to the largest copy it has held, freed by serl_ctx_destroy), so that launches in flight on different streams
+ * never share one; the fifth launch waits on its stream for the launch that used its slot.  serl_last_rollout_weights reports the size.  A failed
+ * allocation is SERL_E_HIP.
+ * Runs the checks of serl_rollout (and, with nz, of serl_rollout_noise), then SERL_E_UNSUPPORTED before any launch unless the kernel hint -- desc->kernel_hint,
+ * or SERL_KERNEL=... for a descriptor that says AUTO -- resolves to SERL_KERNEL_LANEG ("only the LANEG kernels read a regrouped copy through this entry"),
+ * and unless n_members <= 1 << 22 (a lane's 32-bit offset into a group).  serl_last_rollout_info reports family SERL_FAMILY_LANEG as for the rows. */
+int serl_rollout_regrouped(serl_ctx *ctx, const serl_rollout_desc *desc, const serl_rollout_noise_desc *nz /* NULL: no generator */, void *stream);
 
 /* the generator's bit-level parts on the host, compiled from the kernels' text (csrc/serl_rng.h) */
 void serl_host_philox(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t out4[4]);
@@ -572,6 +587,11 @@ enum serl_kernel_family { SERL_FAMILY_NONE = 0, SERL_FAMILY_TEAM = 1 /* eight wa
                           SERL_FAMILY_TEAMR = 13 /* eight wavefronts = one episode, its streamed actor (two wavefronts) in a workgroup of its own on another CU */,
                           SERL_FAMILY_LANEG = SERL_FAMILY_TEAMR + 1 /* (family 14) one lane = one episode, every actor shape: kernel_hint SERL_KERNEL_LANEG */ };
 int serl_last_rollout_info(serl_ctx *ctx, int32_t out[8]);
+/* Host-side record of the weights the most recent rollout launch read (the launch serl_last_rollout_info describes): out[0] 1 = a regrouped copy
+ * [groups][padded members][4] was made in front of it (serl_rollout_regrouped; the hidden-32 lane kernels of lanes_per_wave > 0), 0 = the rows as they lie;
+ * out[1] members padded to a multiple of 64, out[2] groups = ceil(P / 4), out[3] bytes of the copy = out[1] x out[2] x 16 (all 0 when out[0] is 0).  Does
+ * not wait for the device.  SERL_E_INVALID before the first launch. */
+int serl_last_rollout_weights(serl_ctx *ctx, int64_t out[4]);
 /* The same for the step-wise env: WHAT the most recent serl_venv_reset* / _step* / _rollout* call of this context launched (a record of its own:
  * serl_last_rollout_info keeps describing the last serl_rollout).  out[0] enum serl_kernel_family: SERL_FAMILY_LANE (one lane = one env) or
  * SERL_FAMILY_WAVE (one wavefront = one env, the `_wave` entry points); out[1] workgroups; out[2] wavefronts per workgroup; out[3] enum serl_dyn_code.
@@ -1028,6 +1048,10 @@ int serl_td3_train_group_wide(serl_ctx *ctx, const serl_td3_desc *desc, const se
  * weights regrouped, [12] mailbox bytes zeroed, [13] timing events recorded, [14] episodes per launch, [15] 0.  All zero on a refusal.
  * SERL_E_INVALID for a NULL argument, caps[0] < 1 or n_episodes < 1. */
 int serl_host_plan_rollout(const int32_t caps[7], const serl_rollout_desc *desc, int32_t noise, int32_t out[16]);
+/* ... of serl_rollout_regrouped (noise != 0: with a noise descriptor): the words of serl_host_plan_rollout for the same descriptor with out[11] == 1, and
+ * the refusals of the entry point (a hint that does not resolve to LANEG, n_members > 1 << 22, everything LANEG refuses).  caps[6] == 0
+ * (SERL_LANE_WEIGHTS=rows) does not apply: the caller asked for the copy by name. */
+int serl_host_plan_rollout_regrouped(const int32_t caps[7], const serl_rollout_desc *desc, int32_t noise, int32_t out[16]);
 /* ... of serl_dyn_open_loop */
 int serl_host_plan_dyn(const int32_t caps[7], int32_t n_episodes, int32_t lanes_per_wave, int32_t kernel_hint, int32_t out[16]);
 /* ... the workgroups serl_rollout_multi gives its n <= 4 parts of episodes[k] episodes under placement `place` (SERL_MIXED_PLACE): grids

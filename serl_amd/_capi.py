@@ -27,7 +27,8 @@ EXPORTS = ['serl_abi_version', 'serl_last_error', 'serl_param_count', 'serl_ctx_
            'serl_td3_train_big', 'serl_td3_big_layout', 'serl_td3_big_work_bytes', 'serl_td3_rng_fill_big',
            'serl_td3_train_wide', 'serl_td3_wide_layout', 'serl_td3_wide_work_bytes',
            'serl_td3_train_group_big', 'serl_td3_train_group_wide',
-           'serl_ga_distill_general', 'serl_ga_distill_general_work_bytes']
+           'serl_ga_distill_general', 'serl_ga_distill_general_work_bytes',
+           'serl_rollout_regrouped', 'serl_host_plan_rollout_regrouped', 'serl_last_rollout_weights']
 
 
 class BuildDesc(ctypes.Structure):
@@ -336,6 +337,9 @@ def lib():
     L.serl_td3_train_group_wide.argtypes = L.serl_td3_train_group.argtypes
     L.serl_host_plan_rollout.argtypes = [_I, ctypes.POINTER(RolloutDesc), i32, _I]
     L.serl_host_plan_dyn.argtypes = [_I, i32, i32, i32, _I]
+    L.serl_rollout_regrouped.argtypes = [VP, ctypes.POINTER(RolloutDesc), ctypes.POINTER(RolloutNoiseDesc), VP]
+    L.serl_host_plan_rollout_regrouped.argtypes = L.serl_host_plan_rollout.argtypes
+    L.serl_last_rollout_weights.argtypes = [VP, ctypes.POINTER(ctypes.c_int64)]
     L.serl_host_plan_multi.argtypes = [i32, i32, _I, i32, _I, _I, _I]
     for f in EXPORTS:
         if f == 'serl_host_uniform':

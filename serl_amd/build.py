@@ -13,7 +13,7 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 # index = serl_dyn_code (include/serl_amd.h): csrc/serl_variant.h turns -DSERL_DYN=<code> into the variant's names and generated files
 VARIANTS = ['nominal', 'ice', 'cg_timed', 'gust', 'test']
 # kernel families: csrc/family_<f>.hip, compiled once per code variant into build/rollout_<f>_<variant>.o (the lane family: rollout_<variant>.o)
-FAMILIES = ['lane', 'lanenz', 'lanern', 'laneg', 'lanegn', 'venvw', 'venvwr', 'wave', 'wavern', 'half', 'team', 'teamr', 'teams2', 'team2', 'team2s', 'team4']      # (lanenz: the env kernels of the lane units with the in-kernel noise generator; venvw: the env kernels with one wavefront per env; venvwr: their rollout kernels; lanern / wavern: the population rollout kernels of the lane / wave units with the generator; laneg / lanegn: the lane population kernel around the general lane actor -- kernel_hint LANEG --, plain / with the generator)
+FAMILIES = ['lane', 'lanenz', 'lanern', 'laneg', 'lanegn', 'lanegt', 'lanegtn', 'venvw', 'venvwr', 'wave', 'wavern', 'half', 'team', 'teamr', 'teams2', 'team2', 'team2s', 'team4']      # (lanenz: the env kernels of the lane units with the in-kernel noise generator; venvw: the env kernels with one wavefront per env; venvwr: their rollout kernels; lanern / wavern: the population rollout kernels of the lane / wave units with the generator; laneg / lanegn: the lane population kernel around the general lane actor -- kernel_hint LANEG --, plain / with the generator; lanegt / lanegtn: the same two over the regrouped copy of the weights -- serl_rollout_regrouped)
 # object stem -> (source, defines)
 UNITS = {s: (s + '.hip', []) for s in ('serl_capi', 'serl_ga', 'serl_metrics', 'serl_distill', 'serl_td3', 'serl_noise')}
 UNITS.update({('rollout_' if f == 'lane' else 'rollout_%s_' % f) + v: ('family_%s.hip' % f, ['-DSERL_DYN=%d' % code])

@@ -57,7 +57,13 @@ static_assert(8 * (CIT_RO_LDS_WORDS + CIT_V(_NSLOPE)) <= 160 * 1024, "tables + i
 }  // namespace bdag
 
 #define SERL_V(x) SERL_PASTE(x, VARIANT)
-#ifdef SERL_LANE_GENERAL_ACTOR   // family_laneg.hip / family_lanegn.hip: the episode kernel around the general lane actor (plain / with the in-kernel noise generator), nothing else
+#if defined(SERL_LANE_GENERAL_ACTOR) && defined(SERL_LANE_REGROUPED_WEIGHTS)   // family_lanegt.hip / family_lanegtn.hip: that kernel over the regrouped copy of the weights (plain / with the generator), nothing else
+#ifdef SERL_ROLLOUT_NOISE
+void SERL_V(serl_launch_rollout_lanegt_noise_)(const RolloutArgs &a, const serl_rollout_noise_desc &nz, int grid, hipStream_t stream) { bdag::SERL_V(serl_launch_rollout_lanegt_noise_)(a, nz, grid, stream); }
+#else
+void SERL_V(serl_launch_rollout_lanegt_)(const RolloutArgs &a, int grid, hipStream_t stream) { bdag::SERL_V(serl_launch_rollout_lanegt_)(a, grid, stream); }
+#endif
+#elif defined(SERL_LANE_GENERAL_ACTOR)   // family_laneg.hip / family_lanegn.hip: the episode kernel around the general lane actor (plain / with the in-kernel noise generator), nothing else
 #ifdef SERL_ROLLOUT_NOISE
 void SERL_V(serl_launch_rollout_laneg_noise_)(const RolloutArgs &a, const serl_rollout_noise_desc &nz, int grid, hipStream_t stream) { bdag::SERL_V(serl_launch_rollout_laneg_noise_)(a, nz, grid, stream); }
 #else

@@ -1540,6 +1540,184 @@ static __device__ void serl_actor_forward_lane32_t(const serl_rollout_desc &dd, 
   }
 }
 
+// ---- serl_actor_forward_lane_general over the REGROUPED weights (family_lanegt.hip / family_lanegtn.hip: serl_rollout_regrouped) ------------------------
+// Every actor shape of the lane population kernel (state_dim 7, action_dim 3, hidden a multiple of 4 in 4 .. 128, 0 .. 16 hidden layers) with the addresses of
+// serl_actor_forward_lane32_t: parameter p of member m lives at wt[((p >> 2) * wt_members + m) * 4 + (p & 3)], every load is one dwordx4 at a wave-uniform
+// 64-bit group base (an SGPR pair) + the lane's 32-bit offset member x 16 B, so the 64 lanes of a wavefront whose members are consecutive read one run of
+// 1 KB where the row version asks for 64 cache lines.  The group stride wt_members x 16 B is multiplied on the scalar side in 64 bits: ceil(P / 4) x mpad x
+// 16 B is 7.75 GB for 65 536 members of 96 x 3.
+// The layout property this rests on (tests/test_rollout_lanegt_host.py checks it for every shape): with S = 7, A = 3 and H % 4 == 0 every tensor of the packed
+// layout starts at a multiple of four floats -- 7 H, 7 H + H = 8 H, H x H + 3 H per hidden layer, rows of H, 3 H in front of the output bias -- so no group
+// straddles two tensors or two rows of H; a block of four first-layer rows is 28 floats = exactly seven groups (rows i .. i + 3 start at float 28 (i / 4)),
+// which turns the row version's scalar row[r * S + jc] loads into seven dwordx4 loads per block; and the output bias is elements 0 .. 2 of the last group,
+// whose fourth element serl_regroup_weights_kernel writes as zero (P = 4 g + 3).
+// The arithmetic is serl_actor_forward_lane_general's, operation for operation and in the same order -- p[r][j & 3] fma chains over ascending j in the first
+// layer, serl_lane_rows' four partial sums per row with the H - 4 clamp, the zero-padded 16-wide LayerNorm trees, gm * (h - mean) / den + bt, det_tanhf --:
+// bit-identical.  A trip of serl_lane_rows_t issues the same 4 R + 4 loads together as a trip of serl_lane_rows.
+typedef const __attribute__((address_space(1))) char *serl_gbytes;
+// a group base as an SGPR pair: the two readfirstlanes keep the 64-bit group arithmetic (group index x stride) on the scalar side and apart from the lane's
+// offset -- without them the compiler adds the offset to the base first and multiplies per lane --, so that the load is global_load_dwordx4 v, v_off, s[base:base+1]
+static __device__ __forceinline__ serl_gbytes serl_group_base(const serl_gbytes p)
+{
+  const uint64_t v = (uint64_t)p;
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+  return (serl_gbytes)(((uint64_t)hi << 32) | (uint64_t)lo);
+}
+// the lane's 32-bit offset, handed to the loads of ONE basic block: instruction selection folds base + zext(offset) into the load's address only where it
+// sees the zero-extension in the block of the load, and a loop-invariant one is hoisted out of every loop (the empty statement pins it where it stands)
+static __device__ __forceinline__ unsigned serl_lane_offset(unsigned moff)
+{
+  asm volatile("" : "+v"(moff));
+  return moff;
+}
+template <int R>
+static __device__ __forceinline__ void serl_lane_rows_t(const serl_gbytes rows, const uint64_t gs, const unsigned moff, const int H, const float *h, float (&out)[R])
+{
+  // rows: the group base of row 0's first group; row r's group q lies (r * H / 4 + q) groups on
+  const int Hq = H >> 2;
+  float p[R][4];
+#pragma unroll
+  for (int r = 0; r < R; ++r) { p[r][0] = 0.0f; p[r][1] = 0.0f; p[r][2] = 0.0f; p[r][3] = 0.0f; }
+#pragma nounroll
+  for (int j = 0; j < H; j += 16) {
+    serl_v4f hv[4], wv[R][4];
+    const unsigned mo = serl_lane_offset(moff);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int jq = j + 4 * q < H ? j + 4 * q : H - 4;
+      hv[q] = *(const serl_v4f *)(h + jq);
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const serl_gbytes gp = serl_group_base(rows + (uint64_t)(unsigned)(r * Hq + (jq >> 2)) * gs);      // (wave-uniform: scalar 64-bit)
+        wv[r][q] = *(serl_gptr4)(gp + mo);
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if (j + 4 * q < H) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          p[r][0] = __builtin_fmaf(wv[r][q].x, hv[q].x, p[r][0]); p[r][1] = __builtin_fmaf(wv[r][q].y, hv[q].y, p[r][1]);
+          p[r][2] = __builtin_fmaf(wv[r][q].z, hv[q].z, p[r][2]); p[r][3] = __builtin_fmaf(wv[r][q].w, hv[q].w, p[r][3]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r) out[r] = (p[r][0] + p[r][1]) + (p[r][2] + p[r][3]);
+}
+static __device__ void serl_actor_forward_lane_general_t(const serl_rollout_desc &dd, const float *wt, const int wt_members, const unsigned member, const float (&obs)[16],
+                                                         float (&act_out)[3])
+{
+  constexpr int S = 7;
+  const int H = __builtin_amdgcn_readfirstlane(dd.hidden), L = __builtin_amdgcn_readfirstlane(dd.num_layers);
+  const int act = __builtin_amdgcn_readfirstlane(dd.activation);
+  const int Hq = H >> 2;
+  const serl_gbytes base = (serl_gbytes)wt;
+  const uint64_t gs = (uint64_t)(unsigned)__builtin_amdgcn_readfirstlane(wt_members) * 16u;      // bytes from group g to group g + 1 (wave-uniform, 64-bit products)
+  const unsigned moff = member * 16u;                                                              // (serl_rollout_regrouped takes at most 2^22 members)
+  auto at = [&](const int g) -> serl_gbytes { return base + (uint64_t)(unsigned)g * gs; };
+  auto ld4 = [&](const serl_gbytes gp, const unsigned mo) -> serl_v4f { return *(serl_gptr4)(serl_group_base(gp) + mo); };
+  __attribute__((aligned(16))) float hbuf[2][SERL_MAX_HIDDEN];
+  float *h0 = hbuf[0], *h1 = hbuf[1];
+  // ---- Linear(7, H) act: rows i .. i + 3 = 28 floats = groups 7 (i / 4) .. 7 (i / 4) + 6, the bias group 7 H / 4 + i / 4
+  {
+    const int b0 = S * Hq;
+#pragma nounroll
+    for (int i = 0; i < H; i += 4) {
+      float p[4][4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { p[r][0] = 0.0f; p[r][1] = 0.0f; p[r][2] = 0.0f; p[r][3] = 0.0f; }
+      const serl_gbytes gw = at(S * (i >> 2));
+      const unsigned mo = serl_lane_offset(moff);
+      float wf[4 * S];      // (all loads of the four rows first)
+#pragma unroll
+      for (int g = 0; g < S; ++g) {
+        const serl_v4f v = ld4(gw + (uint64_t)g * gs, mo);
+        wf[4 * g] = v.x; wf[4 * g + 1] = v.y; wf[4 * g + 2] = v.z; wf[4 * g + 3] = v.w;
+      }
+      const serl_v4f bv = ld4(at(b0 + (i >> 2)), mo);
+#pragma unroll
+      for (int j = 0; j < S; ++j) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) p[r][j & 3] = __builtin_fmaf(wf[r * S + j], obs[j], p[r][j & 3]);
+      }
+      serl_v4f t;
+      t.x = serl_act(bv.x + ((p[0][0] + p[0][1]) + (p[0][2] + p[0][3])), act);
+      t.y = serl_act(bv.y + ((p[1][0] + p[1][1]) + (p[1][2] + p[1][3])), act);
+      t.z = serl_act(bv.z + ((p[2][0] + p[2][1]) + (p[2][2] + p[2][3])), act);
+      t.w = serl_act(bv.w + ((p[3][0] + p[3][1]) + (p[3][2] + p[3][3])), act);
+      *(serl_v4f *)(h0 + i) = t;
+    }
+  }
+  const int lgroups = Hq * H + 3 * Hq, hid = S * Hq + Hq;      // groups per hidden layer, first group of the first hidden layer
+  const serl_v4f zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma nounroll
+  for (int l = 0; l < L; ++l) {
+    const int Wl = hid + l * lgroups, bl = Wl + Hq * H;       // groups: weights (row r = groups r H / 4 ..), then bias / gamma / beta (H / 4 groups each)
+#pragma nounroll
+    for (int i = 0; i < H; i += 4) {
+      float t[4];
+      serl_lane_rows_t<4>(at(Wl + i * Hq), gs, moff, H, h0, t);
+      const serl_v4f bv = ld4(at(bl + (i >> 2)), serl_lane_offset(moff));
+      serl_v4f o;
+      o.x = bv.x + t[0]; o.y = bv.y + t[1]; o.z = bv.z + t[2]; o.w = bv.w + t[3];
+      *(serl_v4f *)(h1 + i) = o;
+    }
+    // LayerNorm: the two sums block by block of 16 rows (the last block zero padded: H % 4 == 0, so whole groups of four)
+    float sum = 0.0f;
+#pragma nounroll
+    for (int b = 0; b < H; b += 16) {
+      serl_v4f v[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[q] = b + 4 * q < H ? *(const serl_v4f *)(h1 + b + 4 * q) : zero4;
+      const float t = serl_tree16_v4(v[0], v[1], v[2], v[3]);
+      sum = b == 0 ? t : sum + t;
+    }
+    const float mean = sum / (float)H;
+    float var = 0.0f;
+#pragma nounroll
+    for (int b = 0; b < H; b += 16) {
+      serl_v4f v[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        v[q] = zero4;
+        if (b + 4 * q < H) {
+          const serl_v4f hv = *(const serl_v4f *)(h1 + b + 4 * q);
+          const float d0 = hv.x - mean, d1 = hv.y - mean, d2 = hv.z - mean, d3 = hv.w - mean;
+          v[q].x = d0 * d0; v[q].y = d1 * d1; v[q].z = d2 * d2; v[q].w = d3 * d3;
+        }
+      }
+      const float t = serl_tree16_v4(v[0], v[1], v[2], v[3]);
+      var = b == 0 ? t : var + t;
+    }
+    const float den = sqrtf(var / (float)(H - 1)) + 1e-6f;
+#pragma nounroll
+    for (int i = 0; i < H; i += 4) {
+      const serl_v4f hv = *(const serl_v4f *)(h1 + i);
+      const serl_gbytes gg = at(bl + Hq + (i >> 2));
+      const unsigned mo = serl_lane_offset(moff);
+      const serl_v4f gm = ld4(gg, mo), bt = ld4(gg + (uint64_t)(unsigned)Hq * gs, mo);
+      serl_v4f t;
+      t.x = serl_act(gm.x * (hv.x - mean) / den + bt.x, act);
+      t.y = serl_act(gm.y * (hv.y - mean) / den + bt.y, act);
+      t.z = serl_act(gm.z * (hv.z - mean) / den + bt.z, act);
+      t.w = serl_act(gm.w * (hv.w - mean) / den + bt.w, act);
+      *(serl_v4f *)(h0 + i) = t;
+    }
+  }
+  // ---- Linear(H, 3) tanh: rows of H / 4 groups, the bias in elements 0 .. 2 of the last group of the copy
+  const int outl = hid + L * lgroups;
+  const serl_v4f ob = ld4(at(outl + 3 * Hq), serl_lane_offset(moff));
+  const float ob3[3] = {ob.x, ob.y, ob.z};
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    float t[1];
+    serl_lane_rows_t<1>(at(outl + i * Hq), gs, moff, H, h0, t);
+    act_out[i] = det_tanhf(ob3[i] + t[0]);
+  }
+}
+
 // ---- two episodes per wavefront (rollout_half.inc, rollout_team_half.inc) -------------------------------------------------
 // Actor forward for H = 32, one episode per half-wavefront: lane gl of a half owns hidden row gl of ITS episode's member.
 // Same arithmetic as serl_actor_forward_small<32> (include/serl_amd.h): dot products as four interleaved fma partial sums

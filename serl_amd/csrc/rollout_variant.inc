@@ -95,7 +95,11 @@ static __device__ void V_NAME(serl_wave_episodes_)(const RolloutArgs &a, int e, 
       float obs16[16];
 #pragma unroll
       for (int i = 0; i < 16; ++i) obs16[i] = i < 7 ? (float)obs[i] : 0.0f;
+#ifdef SERL_LANE_REGROUPED_WEIGHTS      // (family_lanegt.hip / family_lanegtn.hip, serl_rollout_regrouped: the same forward over the regrouped copy [P / 4][members][4])
+      serl_actor_forward_lane_general_t(d, a.wt, a.wt_members, member, obs16, act);
+#else
       serl_actor_forward_lane_general(d, w, obs16, act);
+#endif
     }
 #else
     // ---- actor forward for every live episode of this wavefront, one after the other, 64 lanes each
@@ -389,7 +393,31 @@ static __device__ __forceinline__ int V_NAME(serl_stage_and_index_)(const Rollou
 }
 
 #ifndef SERL_VENV_NOISE
-#ifdef SERL_LANE_GENERAL_ACTOR      // (family_laneg.hip / family_lanegn.hip: the episode kernel around the general lane actor, plain or with the generator, nothing else)
+#if defined(SERL_LANE_GENERAL_ACTOR) && defined(SERL_LANE_REGROUPED_WEIGHTS)      // (family_lanegt.hip / family_lanegtn.hip: that kernel over the regrouped copy of the weights, plain or with the generator, nothing else)
+#ifdef SERL_ROLLOUT_NOISE
+__global__ void __launch_bounds__(SERL_BLOCK) V_NAME(serl_rollout_lanegt_noise_kernel_)(RolloutArgs a, const serl_rollout_noise_desc nz)
+{
+  const int e = V_NAME(serl_stage_and_index_)(a);
+  V_NAME(serl_wave_episodes_)(a, nz, e < 0 ? 0 : e, e >= 0);
+}
+
+void V_NAME(serl_launch_rollout_lanegt_noise_)(const RolloutArgs &a, const serl_rollout_noise_desc &nz, int grid, hipStream_t stream)
+{
+  hipLaunchKernelGGL(V_NAME(serl_rollout_lanegt_noise_kernel_), dim3(grid), dim3(a.block), 0, stream, a, nz);
+}
+#else
+__global__ void __launch_bounds__(SERL_BLOCK) V_NAME(serl_rollout_lanegt_kernel_)(RolloutArgs a)
+{
+  const int e = V_NAME(serl_stage_and_index_)(a);
+  V_NAME(serl_wave_episodes_)(a, e < 0 ? 0 : e, e >= 0);
+}
+
+void V_NAME(serl_launch_rollout_lanegt_)(const RolloutArgs &a, int grid, hipStream_t stream)
+{
+  hipLaunchKernelGGL(V_NAME(serl_rollout_lanegt_kernel_), dim3(grid), dim3(a.block), 0, stream, a);
+}
+#endif
+#elif defined(SERL_LANE_GENERAL_ACTOR)      // (family_laneg.hip / family_lanegn.hip: the episode kernel around the general lane actor, plain or with the generator, nothing else)
 #ifdef SERL_ROLLOUT_NOISE
 __global__ void __launch_bounds__(SERL_BLOCK) V_NAME(serl_rollout_laneg_noise_kernel_)(RolloutArgs a, const serl_rollout_noise_desc nz)
 {

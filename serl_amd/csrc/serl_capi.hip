@@ -26,6 +26,7 @@ typedef void SerlLaunchVenvRollout(const RolloutArgs &a, const VenvArgs &v, cons
   X(SerlLaunch, lane, serl_launch_rollout_##v)              /* one episode per lane (family_lane.hip, rollout_variant.inc) */                   \
   X(SerlLaunch, laneq, serl_launch_rollout_laneq_##v)       /* ... finished lanes take the next episode from a work queue */                    \
   X(SerlLaunch, laneg, serl_launch_rollout_laneg_##v)       /* ... every lane its own actor of any shape (family_laneg.hip) */                  \
+  X(SerlLaunch, lanegt, serl_launch_rollout_lanegt_##v)     /* ... over the regrouped copy of the weights (family_lanegt.hip) */                \
   X(SerlLaunchDyn, dyn_lane, serl_launch_dyn_##v)                                                                                                \
   X(SerlLaunchVenv, venv_reset, serl_launch_venv_reset_##v) /* the step-wise vector env, one lane per env (venv_variant.inc) */                  \
   X(SerlLaunchVenv, venv_step, serl_launch_venv_step_##v)                                                                                        \
@@ -109,12 +110,13 @@ struct SerlVwrLaunchers { SERL_VWR_LAUNCHERS(SERL_MEMBER, v) };
 SERL_VARIANTS(SERL_VWR_VARIANT_DECL)
 static const SerlVwrLaunchers k_vwr_launchers[] = {SERL_VARIANTS(SERL_VWR_VARIANT_ROW)};
 
-// the population rollout kernels with the in-kernel noise generator (family_lanern.hip, family_lanegn.hip, family_wavern.hip: rollout_variant.inc /
+// the population rollout kernels with the in-kernel noise generator (family_lanern.hip, family_lanegn.hip, family_lanegtn.hip, family_wavern.hip: rollout_variant.inc /
 // rollout_wave.inc under SERL_ROLLOUT_NOISE), one record per code variant as above
 typedef void SerlLaunchNz(const RolloutArgs &a, const serl_rollout_noise_desc &nz, int grid, hipStream_t stream);
 #define SERL_RN_LAUNCHERS(X, v)                                  \
   X(SerlLaunchNz, lane, serl_launch_rollout_noise_##v)           \
   X(SerlLaunchNz, laneg, serl_launch_rollout_laneg_noise_##v)    \
+  X(SerlLaunchNz, lanegt, serl_launch_rollout_lanegt_noise_##v)  \
   X(SerlLaunchNz, wave, serl_launch_rollout_wave_noise_##v)      \
   X(SerlLaunchNz, wavex, serl_launch_rollout_wavex_noise_##v)
 struct SerlRnLaunchers { SERL_RN_LAUNCHERS(SERL_MEMBER, v) };
@@ -145,7 +147,7 @@ static SerlLaunch *SerlLaunchers::*serl_rollout_launcher(const SerlPlan &p)
     case SERL_FAMILY_WAVE: return &SerlLaunchers::wave;
     case SERL_FAMILY_WAVEX: return &SerlLaunchers::wavex;
     case SERL_FAMILY_LANE: return p.laneq ? &SerlLaunchers::laneq : &SerlLaunchers::lane;
-    case SERL_FAMILY_LANEG: return &SerlLaunchers::laneg;
+    case SERL_FAMILY_LANEG: return p.regroup ? &SerlLaunchers::lanegt : &SerlLaunchers::laneg;      // (regroup: serl_rollout_regrouped alone plans it for this family)
     default: return nullptr;
   }
 }
@@ -155,7 +157,7 @@ static SerlLaunchNz *SerlRnLaunchers::*serl_noise_launcher(const SerlPlan &p)
     case SERL_FAMILY_WAVE: return &SerlRnLaunchers::wave;
     case SERL_FAMILY_WAVEX: return &SerlRnLaunchers::wavex;
     case SERL_FAMILY_LANE: return p.laneq ? nullptr : &SerlRnLaunchers::lane;
-    case SERL_FAMILY_LANEG: return &SerlRnLaunchers::laneg;
+    case SERL_FAMILY_LANEG: return p.regroup ? &SerlRnLaunchers::lanegt : &SerlRnLaunchers::laneg;
     default: return nullptr;
   }
 }
@@ -218,6 +220,8 @@ static int serl_regroup_weights(serl_ctx *c, const serl_rollout_desc *d, Rollout
   HIP_TRY(hipGetLastError());
   a.wt = (const float *)c->wt[slot];
   a.wt_members = mpad;
+  const int64_t rec[4] = {1, mpad, groups, (int64_t)bytes};      // serl_last_rollout_weights: serl_note_launch makes it the launch's record
+  for (int i = 0; i < 4; ++i) c->wt_pending[i] = rec[i];
   return SERL_OK;
 }
 
@@ -227,6 +231,8 @@ static void serl_note_launch(serl_ctx *c, int family, int grid, int per_team, bo
 {
   const int32_t v[8] = {family, grid, per_team, queue ? 1 : 0, actor_waves, streamed ? 1 : 0, launches, code};
   for (int i = 0; i < 8; ++i) c->last_info[i] = v[i];
+  // serl_last_rollout_weights: the copy serl_regroup_weights made for THIS launch, zeros for a launch that regrouped nothing
+  for (int i = 0; i < 4; ++i) { c->last_weights[i] = c->wt_pending[i]; c->wt_pending[i] = 0; }
 }
 
 // RolloutArgs of n_episodes on a build's tables (what every launch path starts from) ...
@@ -260,6 +266,7 @@ static int serl_execute_plan(serl_ctx *c, const SerlPlan &p, RolloutArgs &a, int
     HIP_TRY(hipMemsetAsync(c->prof, 0, 32 * sizeof(unsigned long long), stream));
     a.prof = c->prof;
   }
+  for (int i = 0; i < 4; ++i) c->wt_pending[i] = 0;
   if (p.regroup) {
     const int rc = serl_regroup_weights(c, d, a, stream);
     if (rc != SERL_OK) return rc;
@@ -420,9 +427,9 @@ static int serl_check_desc(serl_ctx *c, const serl_rollout_desc *d, int *hint_ou
 }
 
 // serl_rollout and serl_rollout_noise (nz != NULL): check, plan, refuse if the plan refuses, execute
-static int serl_rollout_impl(serl_ctx *c, const serl_rollout_desc *d, const serl_rollout_noise_desc *nz, int hint, void *stream_)
+static int serl_rollout_impl(serl_ctx *c, const serl_rollout_desc *d, const serl_rollout_noise_desc *nz, int hint, void *stream_, bool regrouped = false)
 {
-  const SerlPlan p = serl_plan_rollout(&c->caps, d, hint, nz != nullptr);
+  const SerlPlan p = regrouped ? serl_plan_rollout_regrouped(&c->caps, d, hint, nz != nullptr) : serl_plan_rollout(&c->caps, d, hint, nz != nullptr);
   if (p.status != SERL_OK) return fail(p.status, p.message);
   HIP_TRY(hipSetDevice(c->device));
   const int code = c->slots[d->build_slot].code;
@@ -455,18 +462,36 @@ int serl_rollout_noise_layout(int32_t *out, int32_t capacity)
   return n;
 }
 
+// the argument checks of serl_rollout_noise behind serl_check_desc's
+static int serl_check_noise(const serl_rollout_desc *d, const serl_rollout_noise_desc *nz)
+{
+  if (!nz) return fail(SERL_E_INVALID, "serl_rollout_noise: nz is NULL");
+  if ((nz->sensor != 0 && nz->sensor != 1) || (nz->action != 0 && nz->action != 1)) return fail(SERL_E_INVALID, "serl_rollout_noise: nz->sensor / nz->action must be 0 or 1");
+  if (d->sensor_noise && nz->sensor) return fail(SERL_E_INVALID, "serl_rollout_noise: desc->sensor_noise together with nz->sensor");
+  if (d->action_noise && nz->action) return fail(SERL_E_INVALID, "serl_rollout_noise: desc->action_noise together with nz->action");
+  if (!(nz->action_sd >= 0.0) || !(nz->action_clip >= 0.0)) return fail(SERL_E_INVALID, "serl_rollout_noise: nz->action_sd / nz->action_clip < 0");
+  return SERL_OK;
+}
+
 // serl_rollout with the sensor / exploration noise drawn inside the kernels.  Launch geometry, weight regrouping, timing events and the launch record are
 // serl_rollout's for the same family: one planner decides both (serl_plan.h serl_plan_rollout).
 int serl_rollout_noise(serl_ctx *c, const serl_rollout_desc *d, const serl_rollout_noise_desc *nz, void *stream_)
 {
   int hint = SERL_KERNEL_AUTO;
   { const int rc_ = serl_check_desc(c, d, &hint); if (rc_ != SERL_OK) return rc_; }
-  if (!nz) return fail(SERL_E_INVALID, "serl_rollout_noise: nz is NULL");
-  if ((nz->sensor != 0 && nz->sensor != 1) || (nz->action != 0 && nz->action != 1)) return fail(SERL_E_INVALID, "serl_rollout_noise: nz->sensor / nz->action must be 0 or 1");
-  if (d->sensor_noise && nz->sensor) return fail(SERL_E_INVALID, "serl_rollout_noise: desc->sensor_noise together with nz->sensor");
-  if (d->action_noise && nz->action) return fail(SERL_E_INVALID, "serl_rollout_noise: desc->action_noise together with nz->action");
-  if (!(nz->action_sd >= 0.0) || !(nz->action_clip >= 0.0)) return fail(SERL_E_INVALID, "serl_rollout_noise: nz->action_sd / nz->action_clip < 0");
+  { const int rc_ = serl_check_noise(d, nz); if (rc_ != SERL_OK) return rc_; }
   return serl_rollout_impl(c, d, nz, hint, stream_);
+}
+
+// serl_rollout (nz == NULL) / serl_rollout_noise of kernel_hint SERL_KERNEL_LANEG over a REGROUPED copy of the weights (family_lanegt.hip / family_lanegtn.hip:
+// rollout_device.h serl_actor_forward_lane_general_t): the same checks, then the LANEG plan with regroup = 1 (serl_plan.h serl_plan_rollout_regrouped), carried
+// out by serl_execute_plan as every plan -- the copy goes into the ring of SERL_WT_SLOTS slots the hidden-32 lane kernels use.
+int serl_rollout_regrouped(serl_ctx *c, const serl_rollout_desc *d, const serl_rollout_noise_desc *nz, void *stream_)
+{
+  int hint = SERL_KERNEL_AUTO;
+  { const int rc_ = serl_check_desc(c, d, &hint); if (rc_ != SERL_OK) return rc_; }
+  if (nz) { const int rc_ = serl_check_noise(d, nz); if (rc_ != SERL_OK) return rc_; }
+  return serl_rollout_impl(c, d, nz, hint, stream_, true);
 }
 
 // Several descriptors -- one per dynamics build of a mixed-fault population -- in ONE launch of one code object (rollout_team4_mixed.hip).
@@ -948,6 +973,17 @@ int serl_host_plan_rollout(const int32_t caps[7], const serl_rollout_desc *desc,
   return serl_plan_out(serl_plan_rollout(&c, desc, hint, noise), out);
 }
 
+int serl_host_plan_rollout_regrouped(const int32_t caps[7], const serl_rollout_desc *desc, int32_t noise, int32_t out[16])
+{
+  if (!caps || !desc || !out || caps[0] < 1 || desc->n_episodes < 1) return fail(SERL_E_INVALID, "serl_host_plan_rollout_regrouped: bad argument");
+  const SerlCaps c = serl_caps_of(caps);
+  int hint = SERL_KERNEL_AUTO;
+  const char *message = "";
+  const int rc = serl_plan_check(&c, desc, &hint, &message);
+  if (rc != SERL_OK) { for (int i = 0; i < 16; ++i) out[i] = 0; return fail(rc, message); }
+  return serl_plan_out(serl_plan_rollout_regrouped(&c, desc, hint, noise), out);
+}
+
 int serl_host_plan_dyn(const int32_t caps[7], int32_t n_episodes, int32_t lanes_per_wave, int32_t kernel_hint, int32_t out[16])
 {
   if (!caps || !out || caps[0] < 1 || n_episodes < 1) return fail(SERL_E_INVALID, "serl_host_plan_dyn: bad argument");
@@ -1000,6 +1036,14 @@ int serl_last_rollout_info(serl_ctx *c, int32_t out[8])
   if (!c || !out) return fail(SERL_E_INVALID, "serl_last_rollout_info: NULL argument");
   if (c->last_info[0] == SERL_FAMILY_NONE) return fail(SERL_E_INVALID, "serl_last_rollout_info: no rollout recorded");
   for (int i = 0; i < 8; ++i) out[i] = c->last_info[i];
+  return SERL_OK;
+}
+
+int serl_last_rollout_weights(serl_ctx *c, int64_t out[4])
+{
+  if (!c || !out) return fail(SERL_E_INVALID, "serl_last_rollout_weights: NULL argument");
+  if (c->last_info[0] == SERL_FAMILY_NONE) return fail(SERL_E_INVALID, "serl_last_rollout_weights: no rollout recorded");
+  for (int i = 0; i < 4; ++i) out[i] = c->last_weights[i];
   return SERL_OK;
 }
 

@@ -54,6 +54,8 @@ struct serl_ctx {
   int wt_next = 0;
   hipEvent_t wt_done[SERL_WT_SLOTS] = {};      // recorded behind the launch that reads a copy: the next launch to take the slot waits for it on ITS stream (no host wait)
   int wt_slot_of_launch = -1;
+  int64_t wt_pending[4] = {};           // the copy serl_regroup_weights made for the launch being carried out (serl_note_launch moves it into last_weights)
+  int64_t last_weights[4] = {};         // serl_last_rollout_weights: {regrouped 0 / 1, padded members, groups, bytes of the copy} of the most recent rollout launch
   int32_t last_venv_info[4] = {};       // serl_venv_last_info: what the most recent step-wise env call launched (family, workgroups, wavefronts per workgroup, code)
   int32_t last_info[8] = {};            // serl_last_rollout_info: what the most recent rollout call launched (family, workgroups, episodes per team, queue, actor wavefronts, streamed, launches, code)
 };

@@ -351,6 +351,21 @@ static inline SerlPlan serl_plan_rollout(const SerlCaps *c, const serl_rollout_d
   return p;
 }
 
+// serl_rollout_regrouped: the LANEG plan with the weights regrouped in front of the launch (family_lanegt.hip / family_lanegtn.hip read the copy; the family
+// reported stays SERL_FAMILY_LANEG).  The caller asked for the copy by name, so SERL_LANE_WEIGHTS=rows (caps env_lane_regroup == 0) does not apply.
+// `hint`: serl_plan_check's, which has refused every shape and env configuration the LANEG kernels do not take.
+#define SERL_PLAN_REGROUP_MAX_MEMBERS (1 << 22)      // (rollout_device.h serl_actor_forward_lane_general_t: the lane's 32-bit byte offset member x 16)
+static inline SerlPlan serl_plan_rollout_regrouped(const SerlCaps *c, const serl_rollout_desc *d, int hint, int noise)
+{
+  if (hint != SERL_KERNEL_LANEG)
+    return serl_plan_refuse(SerlPlan{}, "serl_rollout_regrouped: only the LANEG kernels read a regrouped copy through this entry (kernel_hint SERL_KERNEL_LANEG; the hidden-32 lane kernels of lanes_per_wave > 0 regroup on their own)");
+  if (d->n_members > SERL_PLAN_REGROUP_MAX_MEMBERS)
+    return serl_plan_refuse(SerlPlan{}, "serl_rollout_regrouped: n_members must be at most 1 << 22 = 4 194 304 (a lane addresses its member's 16 bytes of a group with a 32-bit offset)");
+  SerlPlan p = serl_plan_rollout(c, d, hint, noise);
+  if (p.status == SERL_OK) p.regroup = 1;
+  return p;
+}
+
 // serl_dyn_open_loop: the dynamics alone (the team without an actor wavefront, one wavefront or one lane per episode); always timed
 static inline SerlPlan serl_plan_dyn(const SerlCaps *c, int n_episodes, int lanes_per_wave, int kernel_hint)
 {

@@ -58,12 +58,29 @@ def planner_caps(num_cus, env=None):
             num('SERL_SPLIT_ACTOR', 0), num('SERL_REMOTE_ACTOR', 1), 0 if env.get('SERL_LANE_WEIGHTS') == 'rows' else 1]
 
 
+def check_lane_weights(lane_weights, kernel):
+    """The `lane_weights` keyword of rollout() / plan_rollout() / evaluate_pop(), checked before the library is called: None / 'rows' = the call as it is
+    without the keyword; 'regrouped' = kernel='laneg' over a regrouped copy of the weights (C ABI serl_rollout_regrouped), which needs that kernel.
+    `kernel`: the call's, or the engine's kernel_hint where the call names none.  -> True for 'regrouped'."""
+    if lane_weights not in (None, 'rows', 'regrouped'):
+        raise ValueError("lane_weights: None, 'rows' or 'regrouped', not %r" % (lane_weights,))
+    if lane_weights != 'regrouped':
+        return False
+    if kernel != 'laneg':
+        raise ValueError("lane_weights='regrouped' needs kernel='laneg' (only the LANEG kernels read a regrouped copy on request), not kernel=%r" % (kernel,))
+    return True
+
+
 def plan_rollout(spec: Optional[NetSpec], n_episodes, *, num_cus=None, caps=None, lanes_per_wave=0, concurrent_episodes=0, kernel=None, env_config=0,
-                 incremental=False, n_members=1, noise=False, open_loop=False):
+                 incremental=False, n_members=1, noise=False, open_loop=False, lane_weights=None):
     """WHAT RolloutEngine.rollout (noise=True: with device noise; open_loop=True: dynamics_open_loop, spec unused) would launch on a device of `num_cus`
     CUs -- the library's own decision (C ABI serl_host_plan_rollout / serl_host_plan_dyn), no GPU needed.  caps: planner_caps(...) instead of num_cus, for
     the development overrides.  Returns the dict of last_rollout_info() (code = -1: no build is involved) extended by block (threads per workgroup),
-    lanes, first_queued, regroup, mailbox_bytes, timed, episodes_per_launch.  A call the library would refuse raises RuntimeError with its status and text."""
+    lanes, first_queued, regroup, mailbox_bytes, timed, episodes_per_launch.  A call the library would refuse raises RuntimeError with its status and text.
+    lane_weights='regrouped' (kernel='laneg' only, else ValueError): the plan of serl_rollout_regrouped -- the same words with regroup True."""
+    regrouped = check_lane_weights(lane_weights, kernel)
+    if regrouped and open_loop:
+        raise ValueError("lane_weights='regrouped': the dynamics alone read no weights")
     L = _capi.lib()
     caps = (ctypes.c_int32 * 7)(*(caps if caps is not None else planner_caps(num_cus)))
     out = (ctypes.c_int32 * 16)()
@@ -74,7 +91,10 @@ def plan_rollout(spec: Optional[NetSpec], n_episodes, *, num_cus=None, caps=None
                               activation=spec.activation_id, n_members=int(n_members), weight_stride=spec.row_stride, n_episodes=int(n_episodes), max_steps=1,
                               lanes_per_wave=int(lanes_per_wave), kernel_hint=_capi.KERNEL_HINTS[kernel], concurrent_episodes=int(concurrent_episodes),
                               env_config=int(env_config), incremental=int(bool(incremental)))
-        _capi.check(L.serl_host_plan_rollout(caps, ctypes.byref(d), int(bool(noise)), out), 'serl_host_plan_rollout')
+        if regrouped:
+            _capi.check(L.serl_host_plan_rollout_regrouped(caps, ctypes.byref(d), int(bool(noise)), out), 'serl_host_plan_rollout_regrouped')
+        else:
+            _capi.check(L.serl_host_plan_rollout(caps, ctypes.byref(d), int(bool(noise)), out), 'serl_host_plan_rollout')
     return dict(_info_dict(out), block=int(out[8]), lanes=int(out[9]), first_queued=int(out[10]), regroup=bool(out[11]), mailbox_bytes=int(out[12]),
                 timed=bool(out[13]), episodes_per_launch=int(out[14]))
 
@@ -137,7 +157,7 @@ class RolloutEngine:
     def rollout(self, weights, spec: NetSpec, member_of_episode, ref, *, build='h2000_v90', faults=None,
                 err0=None, tick0=None, action_noise=None, noise_row=None, sensor_noise=None, sensor_row=None, t_max=80.0, traces=False,
                 transitions=False, lanes_per_wave=0, sync=True, concurrent_episodes=0, env_config=0, incremental=False, kernel=None, launch=True,
-                noise_seed=None, noise_env=None, noise_episode=None, noise_sd=None, noise_clip=None):
+                noise_seed=None, noise_env=None, noise_episode=None, noise_sd=None, noise_clip=None, lane_weights=None):
         """Low-level: run len(member_of_episode) episodes.  weights f32 [M, >=P] (device or host),
         ref f64 [E, T, 3] or [T, 3] radians.  env_config / incremental: builds.env_config(name) (the attitude task by
         default; the per-episode tables keep their 3-column layouts, transitions have 2 S + A + 3 columns).
@@ -154,7 +174,16 @@ class RolloutEngine:
 
         kernel='laneg' (lanes_per_wave 0 .. 64, 0 = 64): the lane-per-episode kernel in which every lane runs its own actor of ANY shape (hidden a
         multiple of 4 in 4 .. 128, 0 .. 16 hidden layers) over its member's row -- the attitude task only; a shape or env configuration it does not
-        take is a RuntimeError with the library's text, before any launch.  Same results bit for bit."""
+        take is a RuntimeError with the library's text, before any launch.  Same results bit for bit.
+
+        lane_weights='regrouped' (kernel='laneg' only -- the call's or the engine's kernel_hint --, else ValueError before the library is called; None /
+        'rows': the call as it is without the keyword): the same kernel over a copy of the population regrouped to [ceil(P / 4)][members up to 64][4] in
+        front of the launch (C ABI serl_rollout_regrouped), where 64 lanes with consecutive members read one run of 1 KB per load instead of 64 cache
+        lines.  Same results bit for bit, with or without device noise.  One copy is ceil(P / 4) x roundup(members, 64) x 16 bytes and up to four live
+        at once (7.75 GB each for 65 536 members of 96 x 3): last_rollout_weights() reports it.  Measured in profiles/rollout_lanegt_timing.json."""
+        regrouped = check_lane_weights(lane_weights, kernel if kernel is not None else getattr(self, 'kernel_hint', None))
+        if regrouped and not launch:
+            raise ValueError("lane_weights='regrouped': launch=False (rollout_multi) regroups nothing; one launch per build")
         dev_noise = self._check_device_noise(len(np.asarray(member_of_episode).reshape(-1)), sensor_noise, action_noise, sensor_row, noise_row, noise_seed,
                                              noise_env, noise_episode, noise_sd, noise_clip, kernel if kernel is not None else getattr(self, 'kernel_hint', None), launch)
         dev_sensor, dev_action = dev_noise is not None and dev_noise[0], dev_noise is not None and dev_noise[1]
@@ -259,7 +288,10 @@ class RolloutEngine:
             out['_desc'] = d
             return out
         stream = torch.cuda.current_stream(dev).cuda_stream
-        if nz is not None:
+        if regrouped:
+            _capi.check(self.lib.serl_rollout_regrouped(self.ctx, ctypes.byref(d), ctypes.byref(nz) if nz is not None else None, ctypes.c_void_p(stream)),
+                        'serl_rollout_regrouped')
+        elif nz is not None:
             _capi.check(self.lib.serl_rollout_noise(self.ctx, ctypes.byref(d), ctypes.byref(nz), ctypes.c_void_p(stream)), 'serl_rollout_noise')
         else:
             _capi.check(self.lib.serl_rollout(self.ctx, ctypes.byref(d), ctypes.c_void_p(stream)), 'serl_rollout')
@@ -327,6 +359,14 @@ class RolloutEngine:
         _capi.check(self.lib.serl_last_rollout_info(self.ctx, out), 'serl_last_rollout_info')
         return _info_dict(out)
 
+    def last_rollout_weights(self):
+        """WHICH weights the most recent rollout launch read (C ABI serl_last_rollout_weights): dict(regrouped = 1 when a regrouped copy was made in front
+        of it -- lane_weights='regrouped', or the hidden-32 lane kernels of lanes_per_wave > 0 -- else 0, padded_members, groups, bytes of the copy; zeros
+        without a copy).  Does not wait for the device."""
+        out = (ctypes.c_int64 * 4)()
+        _capi.check(self.lib.serl_last_rollout_weights(self.ctx, out), 'serl_last_rollout_weights')
+        return dict(regrouped=int(out[0]), padded_members=int(out[1]), groups=int(out[2]), bytes=int(out[3]))
+
     def plan_rollout(self, spec, n_episodes, *, build='h2000_v90', kernel=None, **kw):
         """plan_rollout() for this engine: its device's CUs, the development overrides of the process environment, its kernel_hint, and
         `code` of `build` -- what last_rollout_info() reports after the same rollout(...) / dynamics_open_loop(...) call."""
@@ -381,7 +421,7 @@ def _as_weights(actors, spec):
 def evaluate_pop(actors, *, mode='nominal', num_evals=3, refs=None, t_max=80, smooth_fitness=False,
                  spec: Optional[NetSpec] = None, engine: Optional[RolloutEngine] = None, traces=False,
                  transitions=False, err0=None, tick0=None, lanes_per_wave=0, need_smoothness=True,
-                 sensor_rng=None, concurrent=True, fused='auto', kernel=None, sensor_noise=None, seed=None, noise_episode=0) -> PopResult:
+                 sensor_rng=None, concurrent=True, fused='auto', kernel=None, sensor_noise=None, seed=None, noise_episode=0, lane_weights=None) -> PopResult:
     """Evaluate a whole population: `num_evals` episodes per member (agent.py:229-256).
 
     actors : sequence of Actor / GeneticAgent, or a packed f32 tensor [pop, P] (then pass `spec`)
@@ -404,6 +444,11 @@ def evaluate_pop(actors, *, mode='nominal', num_evals=3, refs=None, t_max=80, sm
                  lane for EVERY actor shape (hidden 72 x 3, 96 x 3 ...: each lane runs its own actor over its member's row; lanes_per_wave as for
                  'laneq'), the attitude task only, with or without sensor_noise='device'; a shape or env configuration it does not take is a
                  RuntimeError with the library's text before any launch.  Opt-in, measured in profiles/rollout_laneg_timing.json
+    lane_weights : 'regrouped' (kernel='laneg' only, else ValueError) = every launch reads a copy of the population regrouped to
+                 [ceil(P / 4)][members up to 64][4], made in front of it (RolloutEngine.rollout lane_weights=): the member-major episode order of this
+                 function puts consecutive members on consecutive lanes, which is what the copy is laid out for.  Costs ceil(P / 4) x roundup(pop, 64)
+                 x 16 bytes per launch in flight.  Same results bit for bit.  None / 'rows' (default): the rows as they lie.  Measured in
+                 profiles/rollout_lanegt_timing.json
     concurrent : False = the per-build launches run one after the other (A/B switch)
     fused      : several builds as ONE launch of one code object (C ABI v7 serl_rollout_multi), its workgroups placed so that CUs which share an
                  instruction cache run the same code variant.  'auto' (default) and True: whenever the library accepts the combination (more than
@@ -422,6 +467,7 @@ def evaluate_pop(actors, *, mode='nominal', num_evals=3, refs=None, t_max=80, sm
     if sensor_noise is not None and sensor_noise != 'device':
         raise ValueError("sensor_noise: None (host tables drawn from sensor_rng) or 'device', not %r" % (sensor_noise,))
     dev_sensor = sensor_noise == 'device'
+    regrouped = check_lane_weights(lane_weights, kernel if kernel is not None else getattr(engine, 'kernel_hint', None))
     if not dev_sensor and (seed is not None or noise_episode != 0):
         raise ValueError("seed / noise_episode belong to sensor_noise='device'")
     if dev_sensor:
@@ -502,7 +548,7 @@ def evaluate_pop(actors, *, mode='nominal', num_evals=3, refs=None, t_max=80, sm
                                   faults=faults, err0=None if err0 is None else err0[idx],
                                   tick0=None if tick0 is None else tick0[idx], t_max=t_max, sensor_noise=sn, sensor_row=sr,
                                   traces=want, transitions=transitions, lanes_per_wave=lanes_per_wave, env_config=env_cfg, incremental=incremental,
-                                  kernel=kernel, **kw)
+                                  kernel=kernel, lane_weights='regrouped' if regrouped else None, **kw)
 
     # Several builds of the attitude task with the LDS-sized actor shape: ONE launch of ONE code object (C ABI v7 serl_rollout_multi,
     # rollout_team4_mixed.hip), which can place its workgroups: two code variants on CUs that share an instruction cache cost 12 %.  The library says
