@@ -12,6 +12,7 @@
 #pragma once
 #include <type_traits>
 #include "../../include/serl_amd.h"
+#include "env_glue.h"      // statements of the env step that every kernel family shares (fault row, noise rows, sensor add, observation)
 #ifndef CITW_T            // phase-profile marks (citation_wave.h, -DCITW_PROFILE builds); no-ops elsewhere
 #define CITW_T(k) ((void)0)
 #define CITW_T0() ((void)0)
@@ -1921,9 +1922,4 @@ static __device__ __forceinline__ void serl_actor_forward_lds(const serl_rollout
 {
   SerlNoSync none;
   serl_actor_forward_lds<false>(dd, lw, obs, act_out, none);
-}
-
-static __device__ __forceinline__ double serl_clip(double v, double lo, double hi)
-{
-  return v < lo ? lo : (v > hi ? hi : v);
 }

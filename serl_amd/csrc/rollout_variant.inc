@@ -393,71 +393,39 @@ static __device__ __forceinline__ int V_NAME(serl_stage_and_index_)(const Rollou
 }
 
 #ifndef SERL_VENV_NOISE
-#if defined(SERL_LANE_GENERAL_ACTOR) && defined(SERL_LANE_REGROUPED_WEIGHTS)      // (family_lanegt.hip / family_lanegtn.hip: that kernel over the regrouped copy of the weights, plain or with the generator, nothing else)
+// One episode kernel and its launcher per unit, the same two bodies under the unit's name: serl_rollout_<stem>kernel_<v> / serl_launch_rollout_<stem><v>, with the
+// generator's descriptor behind the arguments in the noise units
 #ifdef SERL_ROLLOUT_NOISE
-__global__ void __launch_bounds__(SERL_BLOCK) V_NAME(serl_rollout_lanegt_noise_kernel_)(RolloutArgs a, const serl_rollout_noise_desc nz)
-{
-  const int e = V_NAME(serl_stage_and_index_)(a);
-  V_NAME(serl_wave_episodes_)(a, nz, e < 0 ? 0 : e, e >= 0);
-}
-
-void V_NAME(serl_launch_rollout_lanegt_noise_)(const RolloutArgs &a, const serl_rollout_noise_desc &nz, int grid, hipStream_t stream)
-{
-  hipLaunchKernelGGL(V_NAME(serl_rollout_lanegt_noise_kernel_), dim3(grid), dim3(a.block), 0, stream, a, nz);
-}
+#define V_NZ_PARAM , const serl_rollout_noise_desc nz
+#define V_NZ_REF , const serl_rollout_noise_desc &nz
+#define V_NZ_ARG , nz
 #else
-__global__ void __launch_bounds__(SERL_BLOCK) V_NAME(serl_rollout_lanegt_kernel_)(RolloutArgs a)
-{
-  const int e = V_NAME(serl_stage_and_index_)(a);
-  V_NAME(serl_wave_episodes_)(a, e < 0 ? 0 : e, e >= 0);
-}
-
-void V_NAME(serl_launch_rollout_lanegt_)(const RolloutArgs &a, int grid, hipStream_t stream)
-{
-  hipLaunchKernelGGL(V_NAME(serl_rollout_lanegt_kernel_), dim3(grid), dim3(a.block), 0, stream, a);
-}
+#define V_NZ_PARAM
+#define V_NZ_REF
+#define V_NZ_ARG
 #endif
-#elif defined(SERL_LANE_GENERAL_ACTOR)      // (family_laneg.hip / family_lanegn.hip: the episode kernel around the general lane actor, plain or with the generator, nothing else)
-#ifdef SERL_ROLLOUT_NOISE
-__global__ void __launch_bounds__(SERL_BLOCK) V_NAME(serl_rollout_laneg_noise_kernel_)(RolloutArgs a, const serl_rollout_noise_desc nz)
-{
-  const int e = V_NAME(serl_stage_and_index_)(a);
-  V_NAME(serl_wave_episodes_)(a, nz, e < 0 ? 0 : e, e >= 0);
-}
-
-void V_NAME(serl_launch_rollout_laneg_noise_)(const RolloutArgs &a, const serl_rollout_noise_desc &nz, int grid, hipStream_t stream)
-{
-  hipLaunchKernelGGL(V_NAME(serl_rollout_laneg_noise_kernel_), dim3(grid), dim3(a.block), 0, stream, a, nz);
-}
-#else
-__global__ void __launch_bounds__(SERL_BLOCK) V_NAME(serl_rollout_laneg_kernel_)(RolloutArgs a)
-{
-  const int e = V_NAME(serl_stage_and_index_)(a);
-  V_NAME(serl_wave_episodes_)(a, e < 0 ? 0 : e, e >= 0);
-}
-
-void V_NAME(serl_launch_rollout_laneg_)(const RolloutArgs &a, int grid, hipStream_t stream)
-{
-  hipLaunchKernelGGL(V_NAME(serl_rollout_laneg_kernel_), dim3(grid), dim3(a.block), 0, stream, a);
-}
-#endif
+#define V_EPISODE_KERNEL(stem)                                                                                                                   \
+  __global__ void __launch_bounds__(SERL_BLOCK) V_NAME(V_PASTE(V_PASTE(serl_rollout_, stem), kernel_))(RolloutArgs a V_NZ_PARAM)                  \
+  {                                                                                                                                              \
+    const int e = V_NAME(serl_stage_and_index_)(a);                                                                                              \
+    V_NAME(serl_wave_episodes_)(a V_NZ_ARG, e < 0 ? 0 : e, e >= 0);                                                                              \
+  }                                                                                                                                              \
+  void V_NAME(V_PASTE(serl_launch_rollout_, stem))(const RolloutArgs &a V_NZ_REF, int grid, hipStream_t stream)                                   \
+  {                                                                                                                                              \
+    hipLaunchKernelGGL(V_NAME(V_PASTE(V_PASTE(serl_rollout_, stem), kernel_)), dim3(grid), dim3(a.block), 0, stream, a V_NZ_ARG);                 \
+  }
+#if defined(SERL_LANE_GENERAL_ACTOR) && defined(SERL_LANE_REGROUPED_WEIGHTS) && defined(SERL_ROLLOUT_NOISE)      // (family_lanegtn.hip: the general lane actor over the regrouped copy of the weights, with the generator, nothing else)
+V_EPISODE_KERNEL(lanegt_noise_)
+#elif defined(SERL_LANE_GENERAL_ACTOR) && defined(SERL_LANE_REGROUPED_WEIGHTS)      // (family_lanegt.hip: the same, plain)
+V_EPISODE_KERNEL(lanegt_)
+#elif defined(SERL_LANE_GENERAL_ACTOR) && defined(SERL_ROLLOUT_NOISE)      // (family_lanegn.hip: the episode kernel around the general lane actor with the generator, nothing else)
+V_EPISODE_KERNEL(laneg_noise_)
+#elif defined(SERL_LANE_GENERAL_ACTOR)      // (family_laneg.hip: the same, plain)
+V_EPISODE_KERNEL(laneg_)
 #elif defined(SERL_ROLLOUT_NOISE)      // (family_lanern.hip: the episode kernel with the generator, nothing else)
-__global__ void __launch_bounds__(SERL_BLOCK) V_NAME(serl_rollout_noise_kernel_)(RolloutArgs a, const serl_rollout_noise_desc nz)
-{
-  const int e = V_NAME(serl_stage_and_index_)(a);
-  V_NAME(serl_wave_episodes_)(a, nz, e < 0 ? 0 : e, e >= 0);
-}
-
-void V_NAME(serl_launch_rollout_noise_)(const RolloutArgs &a, const serl_rollout_noise_desc &nz, int grid, hipStream_t stream)
-{
-  hipLaunchKernelGGL(V_NAME(serl_rollout_noise_kernel_), dim3(grid), dim3(a.block), 0, stream, a, nz);
-}
+V_EPISODE_KERNEL(noise_)
 #else
-__global__ void __launch_bounds__(SERL_BLOCK) V_NAME(serl_rollout_kernel_)(RolloutArgs a)
-{
-  const int e = V_NAME(serl_stage_and_index_)(a);
-  V_NAME(serl_wave_episodes_)(a, e < 0 ? 0 : e, e >= 0);
-}
+V_EPISODE_KERNEL()
 
 // dynamics only: initialize() then T calls of step(cmd[k]) per episode (test / micro-benchmark entry)
 __global__ void __launch_bounds__(SERL_BLOCK) V_NAME(serl_dyn_kernel_)(RolloutArgs a, const double *cmds, double *states, int T)
@@ -480,11 +448,6 @@ void V_NAME(serl_launch_dyn_)(const RolloutArgs &a, const double *cmds, double *
   hipLaunchKernelGGL(V_NAME(serl_dyn_kernel_), dim3(grid), dim3(a.block), 0, stream, a, cmds, states, T);
 }
 
-void V_NAME(serl_launch_rollout_)(const RolloutArgs &a, int grid, hipStream_t stream)
-{
-  hipLaunchKernelGGL(V_NAME(serl_rollout_kernel_), dim3(grid), dim3(a.block), 0, stream, a);
-}
-
 #ifdef SERL_LANE_QUEUE
 // the lane slots [0, a.q0) of the launch start on the episode of their own number, the episodes [a.q0, a.e_end) wait behind a.queue
 __global__ void __launch_bounds__(SERL_BLOCK) V_NAME(serl_rollout_laneq_kernel_)(RolloutArgs a)
@@ -499,6 +462,10 @@ void V_NAME(serl_launch_rollout_laneq_)(const RolloutArgs &a, int grid, hipStrea
 }
 #endif
 #endif  // SERL_ROLLOUT_NOISE
+#undef V_EPISODE_KERNEL
+#undef V_NZ_PARAM
+#undef V_NZ_REF
+#undef V_NZ_ARG
 #endif
 #undef V_NAME
 #undef V_PASTE

@@ -38,24 +38,6 @@
 
 #ifndef SERL_VENV_COMMON
 #define SERL_VENV_COMMON
-// observation = [error (A), observed states, last_u (A, incremental only)] (envs/phlabenv.py:84-97,415-428,462-466)
-static __device__ __forceinline__ void serl_venv_write_obs(int cfg, bool incr, const double (&err)[3], const double (&x)[12],
-                                                           const double (&u)[3], double *o)
-{
-  if (cfg == SERL_ENV_SYMMETRIC) {
-    o[0] = err[0]; o[1] = x[1];
-    if (incr) o[2] = u[0];
-  } else if (cfg == SERL_ENV_FULL) {
-    o[0] = err[0]; o[1] = err[1]; o[2] = err[2];
-    for (int i = 0; i < 10; ++i) o[3 + i] = x[i];
-    if (incr) { o[13] = u[0]; o[14] = u[1]; o[15] = u[2]; }
-  } else {
-    o[0] = err[0]; o[1] = err[1]; o[2] = err[2];
-    o[3] = x[0]; o[4] = x[1]; o[5] = x[2]; o[6] = x[4];
-    if (incr) { o[7] = u[0]; o[8] = u[1]; o[9] = u[2]; }
-  }
-}
-
 // the outputs of an env that does not move in this call (not in the reset mask; stepped while done / never reset): its current
 // observation from the stored state, and (step) the stored x / ref / t / cost with reward 0 and done = 1
 static __device__ __forceinline__ void serl_venv_write_frozen(const VenvArgs &v, int e, bool step)
@@ -67,7 +49,7 @@ static __device__ __forceinline__ void serl_venv_write_frozen(const VenvArgs &v,
   double err[3], u[3], x[12];
   for (int i = 0; i < 3; ++i) { err[i] = S[(SERL_VF_ERR + i) * np + e]; u[i] = S[(SERL_VF_LASTU + i) * np + e]; }
   for (int i = 0; i < 12; ++i) x[i] = S[(SERL_VF_XO + i) * np + e];
-  serl_venv_write_obs(d.env_config, d.incremental != 0, err, x, u, v.obs + (size_t)e * d.state_dim);
+  serl_write_obs(d.env_config, d.incremental != 0, err, x, u, v.obs + (size_t)e * d.state_dim);
   if (!step) return;
   v.reward[e] = 0.0;
   v.done[e] = 1;
@@ -151,8 +133,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_reset_kernel_)(
   for (int i = 0; i < 3; ++i) err[i] = S[(SERL_VF_ERR + i) * np + e];      // self.error is never cleared
   if (d.err0) for (int i = 0; i < 3; ++i) err[i] = i < A ? d.err0[(size_t)e * 3 + i] : 0.0;
   const uint32_t tick = d.tick0 ? (uint32_t)d.tick0[e] : (uint32_t)I[SERL_VI_TICK * np + e];   // initialize() leaves the clock running
-  serl_fault_row f = {1.0, __longlong_as_double(0x7ff0000000000000LL), __longlong_as_double(0x7ff0000000000000LL),
-                      0.0, 0.0, 0, 0, 0};
+  serl_fault_row f = serl_fault_none();
   if (d.faults) f = d.faults[e];
   CitCtx ctx;
   cit_reset(&ctx, a.ro, a.t3, a.x0, a.dw0, a.dyn_dt);
@@ -164,7 +145,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_reset_kernel_)(
   if (f.rudder_jam_on != 0.0) cmd[2] = f.rudder_jam;
   VV_NAME(cit_step_)(&ctx, cmd, x);
   if (const double *sn = VV_SENSOR(0)) {
-    x[0] += sn[0]; x[1] += sn[1]; x[2] += sn[2]; x[4] += sn[3]; x[5] += sn[4]; x[6] += sn[5]; x[7] += sn[6];
+    serl_sensor_add(x, sn);
   }
   VV_NAME(serl_venv_store_ctx_)(v, e, ctx);
   for (int i = 0; i < 3; ++i) {
@@ -176,7 +157,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_reset_kernel_)(
   I[SERL_VI_K * np + e] = 0;
   I[SERL_VI_LIVE * np + e] = 1;
   I[SERL_VI_COST * np + e] = 0;
-  serl_venv_write_obs(d.env_config, d.incremental != 0, err, x, u, v.obs + (size_t)e * d.state_dim);
+  serl_write_obs(d.env_config, d.incremental != 0, err, x, u, v.obs + (size_t)e * d.state_dim);
 }
 
 #ifndef SERL_VENV_NOISE      // (the plain step has no noise instantiation: device noise needs auto-reset)
@@ -216,18 +197,15 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_step_kernel_)(Ro
     }
   }
   for (int i = 0; i < 3; ++i) u[i] = incr ? u[i] + scl[i] * dt : scl[i];
-  serl_fault_row f = {1.0, __longlong_as_double(0x7ff0000000000000LL), __longlong_as_double(0x7ff0000000000000LL),
-                      0.0, 0.0, 0, 0, 0};
+  serl_fault_row f = serl_fault_none();
   if (d.faults) f = d.faults[e];
   for (int i = 0; i < 10; ++i) cmd[i] = 0.0;
-  cmd[0] = serl_clip(u[0] * f.elev_gain, -f.elev_clip, f.elev_clip);
-  cmd[1] = serl_clip(u[1], -f.ail_clip, f.ail_clip);
-  cmd[2] = (f.rudder_jam_on != 0.0) ? f.rudder_jam : u[2];
+  serl_fault_apply(f, u, cmd);
   CitCtx ctx;
   VV_NAME(serl_venv_load_ctx_)(a, v, e, ctx);
   VV_NAME(cit_step_)(&ctx, cmd, x);
   if (const double *sn = serl_venv_sensor(d, e, k + 1)) {      // k < max_steps: entry k + 1 <= max_steps exists
-    x[0] += sn[0]; x[1] += sn[1]; x[2] += sn[2]; x[4] += sn[3]; x[5] += sn[4]; x[6] += sn[5]; x[7] += sn[6];
+    serl_sensor_add(x, sn);
   }
   double rk[3];
   if (d.ref_spec) serl_ref_generate(d.ref_spec + (size_t)e * d.ref_spec_stride, t, d.t_max, rk[0], rk[1], rk[2]);   // at the pre-increment t
@@ -254,7 +232,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_NAME(serl_venv_step_kernel_)(Ro
   I[SERL_VI_K * np + e] = k + 1;
   I[SERL_VI_LIVE * np + e] = done ? 0 : 1;
   I[SERL_VI_COST * np + e] = cost;
-  serl_venv_write_obs(cfg, incr, err, x, u, v.obs + (size_t)e * d.state_dim);
+  serl_write_obs(cfg, incr, err, x, u, v.obs + (size_t)e * d.state_dim);
   v.reward[e] = reward;
   v.done[e] = done ? 1 : 0;
   if (v.x) for (int i = 0; i < 12; ++i) v.x[(size_t)e * 12 + i] = x[i];
@@ -309,13 +287,10 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_step_auto_kerne
     }
   }
   for (int i = 0; i < 3; ++i) u[i] = incr ? u[i] + scl[i] * dt : scl[i];
-  serl_fault_row f = {1.0, __longlong_as_double(0x7ff0000000000000LL), __longlong_as_double(0x7ff0000000000000LL),
-                      0.0, 0.0, 0, 0, 0};
+  serl_fault_row f = serl_fault_none();
   if (d.faults) f = d.faults[e];
   for (int i = 0; i < 10; ++i) cmd[i] = 0.0;
-  cmd[0] = serl_clip(u[0] * f.elev_gain, -f.elev_clip, f.elev_clip);
-  cmd[1] = serl_clip(u[1], -f.ail_clip, f.ail_clip);
-  cmd[2] = (f.rudder_jam_on != 0.0) ? f.rudder_jam : u[2];
+  serl_fault_apply(f, u, cmd);
   // the running episode's reference: its row of the pool (the cursor is the caller's memory: kept inside the pool whatever it holds)
   const int32_t cur = au.cursor[e];
   const int row = au.ref_pool ? (int)((uint32_t)cur % (uint32_t)au.pool_rows) : 0;
@@ -330,7 +305,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_step_auto_kerne
   for (int trip = 0; trip < 2; ++trip) {
     VV_NAME(cit_step_)(&ctx, cmd, x);
     if (const double *sn = VV_SENSOR(restart ? 0 : k + 1)) {
-      x[0] += sn[0]; x[1] += sn[1]; x[2] += sn[2]; x[4] += sn[3]; x[5] += sn[4]; x[6] += sn[5]; x[7] += sn[6];
+      serl_sensor_add(x, sn);
     }
     if (restart) { V0n = x[3]; break; }
     if (spec) serl_ref_generate(spec, t, d.t_max, rk[0], rk[1], rk[2]);
@@ -349,7 +324,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_step_auto_kerne
     t += dt;
     k += 1;
     const bool done = fin || k >= d.max_steps;
-    serl_venv_write_obs(cfg, incr, err, x, u, fobs);
+    serl_write_obs(cfg, incr, err, x, u, fobs);
     v.reward[e] = reward;
     v.done[e] = done ? 1 : 0;
     if (v.x) for (int i = 0; i < 12; ++i) v.x[(size_t)e * 12 + i] = x[i];
@@ -387,7 +362,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_step_auto_kerne
   I[SERL_VI_LIVE * np + e] = 1;
   I[SERL_VI_COST * np + e] = cost;
   VV_NZ_STORE
-  serl_venv_write_obs(cfg, incr, err, x, u, v.obs + (size_t)e * d.state_dim);
+  serl_write_obs(cfg, incr, err, x, u, v.obs + (size_t)e * d.state_dim);
 }
 
 // K policy-driven steps of every env in one launch (serl_venv_rollout in include/serl_amd.h): per step the lane's own actor on the
@@ -411,7 +386,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_rollout_kernel_
   double err[3], u[3], x[12], obs[7];
   for (int i = 0; i < 3; ++i) { err[i] = S[(SERL_VF_ERR + i) * np + e]; u[i] = S[(SERL_VF_LASTU + i) * np + e]; }
   for (int i = 0; i < 12; ++i) x[i] = S[(SERL_VF_XO + i) * np + e];
-  serl_venv_write_obs(cfg, incr, err, x, u, obs);      // the current observation, as serl_venv_write_frozen rebuilds it
+  serl_write_obs(cfg, incr, err, x, u, obs);      // the current observation, as serl_venv_write_frozen rebuilds it
   for (int i = 0; i < 7; ++i) rd.obs[(size_t)e * 7 + i] = obs[i];
   if (!I[SERL_VI_LIVE * np + e]) {      // never reset: frozen in every row, as in serl_venv_step_auto (no action: zeros; the transition marks itself terminal)
     const double rf[3] = {S[(SERL_VF_REF + 0) * np + e], S[(SERL_VF_REF + 1) * np + e], S[(SERL_VF_REF + 2) * np + e]};
@@ -451,8 +426,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_rollout_kernel_
   double t = S[SERL_VF_T * np + e];
   int k = I[SERL_VI_K * np + e];
   int cost = 0;
-  serl_fault_row f = {1.0, __longlong_as_double(0x7ff0000000000000LL), __longlong_as_double(0x7ff0000000000000LL),
-                      0.0, 0.0, 0, 0, 0};
+  serl_fault_row f = serl_fault_none();
   if (d.faults) f = d.faults[e];
   // the env's member of the packed population (the index is the caller's memory: kept inside the population whatever it holds)
   const unsigned member = rd.member_of_env ? (unsigned)rd.member_of_env[e] % (unsigned)rd.n_members : 0u;
@@ -486,9 +460,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_rollout_kernel_
     }
     // ---- the step of serl_venv_step_auto_kernel_
     for (int i = 0; i < 10; ++i) cmd[i] = 0.0;
-    cmd[0] = serl_clip(u[0] * f.elev_gain, -f.elev_clip, f.elev_clip);
-    cmd[1] = serl_clip(u[1], -f.ail_clip, f.ail_clip);
-    cmd[2] = (f.rudder_jam_on != 0.0) ? f.rudder_jam : u[2];
+    serl_fault_apply(f, u, cmd);
     const int row = au.ref_pool ? (int)((uint32_t)cur % (uint32_t)au.pool_rows) : 0;
     const serl_ref_spec *spec = au.ref_pool ? au.ref_pool + (size_t)e * au.pool_rows + row
                               : d.ref_spec ? d.ref_spec + (size_t)e * d.ref_spec_stride : nullptr;
@@ -498,7 +470,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_rollout_kernel_
     for (int trip = 0; trip < 2; ++trip) {
       VV_NAME(cit_step_)(&ctx, cmd, x);
       if (const double *sn = VV_SENSOR(restart ? 0 : k + 1)) {
-        x[0] += sn[0]; x[1] += sn[1]; x[2] += sn[2]; x[4] += sn[3]; x[5] += sn[4]; x[6] += sn[5]; x[7] += sn[6];
+        serl_sensor_add(x, sn);
       }
       if (restart) { V0n = x[3]; break; }
       if (spec) serl_ref_generate(spec, t, d.t_max, rk[0], rk[1], rk[2]);
@@ -517,7 +489,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_rollout_kernel_
       t += dt;
       k += 1;
       const bool done = fin || k >= d.max_steps;
-      if (rd.final_obs) serl_venv_write_obs(cfg, incr, err, x, u, rd.final_obs + kn * 7);
+      if (rd.final_obs) serl_write_obs(cfg, incr, err, x, u, rd.final_obs + kn * 7);
       if (rd.reward) rd.reward[kn] = reward;
       if (rd.done) rd.done[kn] = done ? 1 : 0;
       if (rd.x) for (int i = 0; i < 12; ++i) rd.x[kn * 12 + i] = x[i];
@@ -527,7 +499,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_rollout_kernel_
       if (rd.transitions) {      // the row of rollout_variant.inc: the next observation is the terminal-aware one, never the restarted one
         float *tr = rd.transitions + kn * 20;
         double nobs[7];
-        serl_venv_write_obs(cfg, incr, err, x, u, nobs);
+        serl_write_obs(cfg, incr, err, x, u, nobs);
         for (int i = 0; i < 7; ++i) tr[i] = (float)obs[i];
         for (int i = 0; i < 3; ++i) tr[7 + i] = act[i];
         for (int i = 0; i < 7; ++i) tr[10 + i] = (float)nobs[i];
@@ -557,7 +529,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_rollout_kernel_
       if (f.rudder_jam_on != 0.0) cmd[2] = f.rudder_jam;
     }
     V0 = V0n;
-    serl_venv_write_obs(cfg, incr, err, x, u, obs);
+    serl_write_obs(cfg, incr, err, x, u, obs);
     for (int i = 0; i < 7; ++i) rd.obs[(kn + N) * 7 + i] = obs[i];
   }
   VV_NAME(serl_venv_store_ctx_)(v, e, ctx);
@@ -598,7 +570,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_rollout_general
   for (int i = 0; i < 12; ++i) x[i] = S_[(SERL_VF_XO + i) * np + e];
 #pragma unroll
   for (int i = 0; i < 16; ++i) obs[i] = 0.0;
-  serl_venv_write_obs(cfg, incr, err, x, u, obs);      // the current observation, as serl_venv_write_frozen rebuilds it
+  serl_write_obs(cfg, incr, err, x, u, obs);      // the current observation, as serl_venv_write_frozen rebuilds it
 #pragma unroll
   for (int i = 0; i < 16; ++i) if (i < S) rd.obs[(size_t)e * S + i] = obs[i];
   if (!I[SERL_VI_LIVE * np + e]) {      // never reset: frozen in every row, as in serl_venv_step_auto (no action: zeros; the transition marks itself terminal)
@@ -644,8 +616,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_rollout_general
   double t = S_[SERL_VF_T * np + e];
   int k = I[SERL_VI_K * np + e];
   int cost = 0;
-  serl_fault_row f = {1.0, __longlong_as_double(0x7ff0000000000000LL), __longlong_as_double(0x7ff0000000000000LL),
-                      0.0, 0.0, 0, 0, 0};
+  serl_fault_row f = serl_fault_none();
   if (d.faults) f = d.faults[e];
   // the env's member of the packed population (the index is the caller's memory: kept inside the population whatever it holds)
   const unsigned member = rd.member_of_env ? (unsigned)rd.member_of_env[e] % (unsigned)rd.n_members : 0u;
@@ -684,9 +655,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_rollout_general
     for (int i = 0; i < 3; ++i) u[i] = incr ? u[i] + scl[i] * dt : scl[i];
     // ---- the step of serl_venv_step_auto_kernel_
     for (int i = 0; i < 10; ++i) cmd[i] = 0.0;
-    cmd[0] = serl_clip(u[0] * f.elev_gain, -f.elev_clip, f.elev_clip);
-    cmd[1] = serl_clip(u[1], -f.ail_clip, f.ail_clip);
-    cmd[2] = (f.rudder_jam_on != 0.0) ? f.rudder_jam : u[2];
+    serl_fault_apply(f, u, cmd);
     const int row = au.ref_pool ? (int)((uint32_t)cur % (uint32_t)au.pool_rows) : 0;
     const serl_ref_spec *spec = au.ref_pool ? au.ref_pool + (size_t)e * au.pool_rows + row
                               : d.ref_spec ? d.ref_spec + (size_t)e * d.ref_spec_stride : nullptr;
@@ -696,7 +665,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_rollout_general
     for (int trip = 0; trip < 2; ++trip) {
       VV_NAME(cit_step_)(&ctx, cmd, x);
       if (const double *sn = VV_SENSOR(restart ? 0 : k + 1)) {
-        x[0] += sn[0]; x[1] += sn[1]; x[2] += sn[2]; x[4] += sn[3]; x[5] += sn[4]; x[6] += sn[5]; x[7] += sn[6];
+        serl_sensor_add(x, sn);
       }
       if (restart) { V0n = x[3]; break; }
       if (spec) serl_ref_generate(spec, t, d.t_max, rk[0], rk[1], rk[2]);
@@ -716,7 +685,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_rollout_general
       k += 1;
       const bool done = fin || k >= d.max_steps;
       double nobs[16];
-      serl_venv_write_obs(cfg, incr, err, x, u, nobs);      // the terminal-aware next observation: final_obs and the transition row
+      serl_write_obs(cfg, incr, err, x, u, nobs);      // the terminal-aware next observation: final_obs and the transition row
       if (rd.final_obs) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) if (i < S) rd.final_obs[kn * S + i] = nobs[i];
@@ -758,7 +727,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_rollout_general
       if (f.rudder_jam_on != 0.0) cmd[2] = f.rudder_jam;
     }
     V0 = V0n;
-    serl_venv_write_obs(cfg, incr, err, x, u, obs);
+    serl_write_obs(cfg, incr, err, x, u, obs);
 #pragma unroll
     for (int i = 0; i < 16; ++i) if (i < S) rd.obs[(kn + N) * S + i] = obs[i];
   }

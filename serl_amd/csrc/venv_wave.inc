@@ -44,23 +44,6 @@
 
 #ifndef SERL_VENVW_COMMON      // (family_venvw.hip includes this file twice: what follows up to the kernels is shared by both passes)
 #define SERL_VENVW_COMMON
-// observation = [error (A), observed states, last_u (A, incremental only)] (venv_variant.inc serl_venv_write_obs)
-static __device__ __forceinline__ void serl_venvw_write_obs(int cfg, bool incr, const double (&err)[3], const double (&x)[12], const double (&u)[3], double *o)
-{
-  if (cfg == SERL_ENV_SYMMETRIC) {
-    o[0] = err[0]; o[1] = x[1];
-    if (incr) o[2] = u[0];
-  } else if (cfg == SERL_ENV_FULL) {
-    o[0] = err[0]; o[1] = err[1]; o[2] = err[2];
-    for (int i = 0; i < 10; ++i) o[3 + i] = x[i];
-    if (incr) { o[13] = u[0]; o[14] = u[1]; o[15] = u[2]; }
-  } else {
-    o[0] = err[0]; o[1] = err[1]; o[2] = err[2];
-    o[3] = x[0]; o[4] = x[1]; o[5] = x[2]; o[6] = x[4];
-    if (incr) { o[7] = u[0]; o[8] = u[1]; o[9] = u[2]; }
-  }
-}
-
 // the outputs of an env that does not move in this call (venv_variant.inc serl_venv_write_frozen); fobs: serl_venv_step_auto's final_obs row, or nullptr.
 // One lane calls it.
 static __device__ __forceinline__ void serl_venvw_write_frozen(const VenvArgs &v, int e, bool step, double *fobs)
@@ -72,9 +55,9 @@ static __device__ __forceinline__ void serl_venvw_write_frozen(const VenvArgs &v
   double err[3], u[3], x[12];
   for (int i = 0; i < 3; ++i) { err[i] = S[(SERL_VF_ERR + i) * np + e]; u[i] = S[(SERL_VF_LASTU + i) * np + e]; }
   for (int i = 0; i < 12; ++i) x[i] = S[(SERL_VF_XO + i) * np + e];
-  serl_venvw_write_obs(d.env_config, d.incremental != 0, err, x, u, v.obs + (size_t)e * d.state_dim);
+  serl_write_obs(d.env_config, d.incremental != 0, err, x, u, v.obs + (size_t)e * d.state_dim);
   if (!step) return;
-  if (fobs) serl_venvw_write_obs(d.env_config, d.incremental != 0, err, x, u, fobs);
+  if (fobs) serl_write_obs(d.env_config, d.incremental != 0, err, x, u, fobs);
   v.reward[e] = 0.0;
   v.done[e] = 1;
   if (v.x) for (int i = 0; i < 12; ++i) v.x[(size_t)e * 12 + i] = x[i];
@@ -95,9 +78,7 @@ static __device__ __forceinline__ void serl_venvw_cmd(const serl_fault_row &f, c
 {
 #pragma unroll
   for (int i = 0; i < 10; ++i) cmd[i] = 0.0;
-  cmd[0] = serl_clip(u[0] * f.elev_gain, -f.elev_clip, f.elev_clip);
-  cmd[1] = serl_clip(u[1], -f.ail_clip, f.ail_clip);
-  cmd[2] = (f.rudder_jam_on != 0.0) ? f.rudder_jam : u[2];
+  serl_fault_apply(f, u, cmd);
 }
 
 // the dynamics state of env e: state buffer -> the wave family's state (lane i < 19: X[i]; the banks to g_dw[wv]; clock and time wave-uniform)
@@ -176,15 +157,14 @@ __global__ void __launch_bounds__(64 * CITW_MAX_WAVES) VW_KNAME(serl_venv_reset_
   for (int i = 0; i < 3; ++i) err[i] = S[(SERL_VF_ERR + i) * np + e];      // self.error is never cleared
   if (d.err0) for (int i = 0; i < 3; ++i) err[i] = i < A ? d.err0[(size_t)e * 3 + i] : 0.0;
   const uint32_t tick = d.tick0 ? (uint32_t)d.tick0[e] : (uint32_t)I[SERL_VI_TICK * np + e];   // initialize() leaves the clock running
-  serl_fault_row f = {1.0, __longlong_as_double(0x7ff0000000000000LL), __longlong_as_double(0x7ff0000000000000LL),
-                      0.0, 0.0, 0, 0, 0};
+  serl_fault_row f = serl_fault_none();
   if (d.faults) f = d.faults[e];
   CitwState s;
   VW_NAME(serl_venvw_init_)(a, wv, s, tick);
   serl_venvw_cmd(f, u, cmd);
   VW_NAME(citw_step_)(wv, s, cmd, x);
   if (const double *sn = VW_SENSOR(0)) {
-    x[0] += sn[0]; x[1] += sn[1]; x[2] += sn[2]; x[4] += sn[3]; x[5] += sn[4]; x[6] += sn[5]; x[7] += sn[6];
+    serl_sensor_add(x, sn);
   }
   VW_NAME(serl_venvw_store_)(v, e, wv, s, (const int32_t *)(a.dw0 + 29));      // (table3's cache image sits behind the banks)
   if (lane == 0) {
@@ -197,7 +177,7 @@ __global__ void __launch_bounds__(64 * CITW_MAX_WAVES) VW_KNAME(serl_venv_reset_
     I[SERL_VI_K * np + e] = 0;
     I[SERL_VI_LIVE * np + e] = 1;
     I[SERL_VI_COST * np + e] = 0;
-    serl_venvw_write_obs(d.env_config, d.incremental != 0, err, x, u, v.obs + (size_t)e * d.state_dim);
+    serl_write_obs(d.env_config, d.incremental != 0, err, x, u, v.obs + (size_t)e * d.state_dim);
   }
 }
 
@@ -247,8 +227,7 @@ static __device__ __forceinline__ void VW_KNAME(serl_venvw_step_)(const RolloutA
     }
   }
   for (int i = 0; i < 3; ++i) u[i] = incr ? u[i] + scl[i] * dt : scl[i];
-  serl_fault_row f = {1.0, __longlong_as_double(0x7ff0000000000000LL), __longlong_as_double(0x7ff0000000000000LL),
-                      0.0, 0.0, 0, 0, 0};
+  serl_fault_row f = serl_fault_none();
   if (d.faults) f = d.faults[e];
   serl_venvw_cmd(f, u, cmd);
   // the running episode's reference: its row of the pool (the cursor is the caller's memory: kept inside the pool whatever it holds)
@@ -272,7 +251,7 @@ static __device__ __forceinline__ void VW_KNAME(serl_venvw_step_)(const RolloutA
   for (int trip = 0; trip < 2; ++trip) {
     VW_NAME(citw_step_)(wv, s, cmd, x);
     if (const double *sn = VW_SENSOR(restart ? 0 : k + 1)) {      // k < max_steps: entry k + 1 <= max_steps exists
-      x[0] += sn[0]; x[1] += sn[1]; x[2] += sn[2]; x[4] += sn[3]; x[5] += sn[4]; x[6] += sn[5]; x[7] += sn[6];
+      serl_sensor_add(x, sn);
     }
     if (restart) { V0n = x[3]; break; }
     if (spec) serl_ref_generate(spec, t, d.t_max, rk[0], rk[1], rk[2]);      // at the pre-increment t
@@ -292,7 +271,7 @@ static __device__ __forceinline__ void VW_KNAME(serl_venvw_step_)(const RolloutA
     k += 1;
     const bool done = fin || k >= d.max_steps;     // (the tables end: the env freezes or restarts instead of reading past them)
     if (lane == 0) {
-      if constexpr (AUTO) serl_venvw_write_obs(cfg, incr, err, x, u, fobs);
+      if constexpr (AUTO) serl_write_obs(cfg, incr, err, x, u, fobs);
       v.reward[e] = reward;
       v.done[e] = done ? 1 : 0;
       if (v.x) for (int i = 0; i < 12; ++i) v.x[(size_t)e * 12 + i] = x[i];
@@ -331,7 +310,7 @@ static __device__ __forceinline__ void VW_KNAME(serl_venvw_step_)(const RolloutA
     I[SERL_VI_K * np + e] = k;
     I[SERL_VI_LIVE * np + e] = live ? 1 : 0;
     I[SERL_VI_COST * np + e] = cost;
-    serl_venvw_write_obs(cfg, incr, err, x, u, v.obs + (size_t)e * d.state_dim);
+    serl_write_obs(cfg, incr, err, x, u, v.obs + (size_t)e * d.state_dim);
   }
   VW_NZ_STORE
 }

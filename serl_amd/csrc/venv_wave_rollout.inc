@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(64 * CITW_MAX_WAVES) VR_KNAME(serl_venv_rollou
   for (int i = 0; i < 12; ++i) x[i] = S_[(SERL_VF_XO + i) * np + e];
 #pragma unroll
   for (int i = 0; i < 16; ++i) obs[i] = 0.0;
-  serl_venvw_write_obs(cfg, incr, err, x, u, obs);      // the current observation, as serl_venvw_write_frozen rebuilds it
+  serl_write_obs(cfg, incr, err, x, u, obs);      // the current observation, as serl_venvw_write_frozen rebuilds it
   if (lane == 0) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) if (i < S) rd.obs[(size_t)e * S + i] = obs[i];
@@ -116,8 +116,7 @@ __global__ void __launch_bounds__(64 * CITW_MAX_WAVES) VR_KNAME(serl_venv_rollou
   double t = S_[SERL_VF_T * np + e];
   int k = I[SERL_VI_K * np + e];
   int cost = 0;
-  serl_fault_row f = {1.0, __longlong_as_double(0x7ff0000000000000LL), __longlong_as_double(0x7ff0000000000000LL),
-                      0.0, 0.0, 0, 0, 0};
+  serl_fault_row f = serl_fault_none();
   if (d.faults) f = d.faults[e];
   // the env's member of the packed population (the index is the caller's memory: kept inside the population whatever it holds)
   const unsigned member = rd.member_of_env ? (unsigned)rd.member_of_env[e] % (unsigned)rd.n_members : 0u;
@@ -172,7 +171,7 @@ __global__ void __launch_bounds__(64 * CITW_MAX_WAVES) VR_KNAME(serl_venv_rollou
     for (int trip = 0; trip < 2; ++trip) {
       VR_NAME(citw_step_)(wv, s, cmd, x);
       if (const double *sn = VR_SENSOR(restart ? 0 : k + 1)) {      // k < max_steps: entry k + 1 <= max_steps exists
-        x[0] += sn[0]; x[1] += sn[1]; x[2] += sn[2]; x[4] += sn[3]; x[5] += sn[4]; x[6] += sn[5]; x[7] += sn[6];
+        serl_sensor_add(x, sn);
       }
       if (restart) { V0n = x[3]; break; }
       if (spec) serl_ref_generate(spec, t, d.t_max, rk[0], rk[1], rk[2]);      // at the pre-increment t
@@ -194,7 +193,7 @@ __global__ void __launch_bounds__(64 * CITW_MAX_WAVES) VR_KNAME(serl_venv_rollou
       double nobs[16];
 #pragma unroll
       for (int i = 0; i < 16; ++i) nobs[i] = 0.0;
-      serl_venvw_write_obs(cfg, incr, err, x, u, nobs);      // the terminal-aware next observation: final_obs and the transition row
+      serl_write_obs(cfg, incr, err, x, u, nobs);      // the terminal-aware next observation: final_obs and the transition row
       if (lane == 0) {
         if (rd.final_obs) {
 #pragma unroll
@@ -234,7 +233,7 @@ __global__ void __launch_bounds__(64 * CITW_MAX_WAVES) VR_KNAME(serl_venv_rollou
       serl_venvw_cmd(f, u, cmd);
     }
     V0 = V0n;
-    serl_venvw_write_obs(cfg, incr, err, x, u, obs);
+    serl_write_obs(cfg, incr, err, x, u, obs);
     if (lane == 0) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) if (i < S) rd.obs[(kn + N) * S + i] = obs[i];

@@ -5,6 +5,8 @@ scale_action, :347-399 calc_error / get_reward / get_cost / incremental_control 
 The same glue is written out by hand in about a dozen kernels (rollout_variant.inc, rollout_wave.inc, rollout_half.inc, three copies in
 rollout_team.inc, rollout_team_half.inc, four in venv_variant.inc, and the one-wavefront-per-env copies of venv_wave.inc -- reset, step,
 auto step -- and venv_wave_rollout.inc) and in oracle/rollout_ref.c, all from one reading of the reference.
+(A few of its statements -- fault row, sensor add, observation -- are shared through serl_amd/csrc/env_glue.h in the env kernels; this file and the
+oracle never include it.)
 `GlueEnv` is a second reading: Python floats (IEEE f64, one rounding per operation, no contraction) and np.float32 only, around
 oracle.dynamics.CitationDynamics(build, short_libm=True).  It shares no code with oracle/rollout_ref.c, oracle/rollout.py or serl_amd
 (the scenario builders use refsignals.tabulate_specs for generated references and oracle.rollout.activation for a bias-only actor's
