@@ -88,7 +88,7 @@ static __device__ void V_NAME(serl_wave_episodes_)(const RolloutArgs &a, int e, 
     if (prof) tc0 = __builtin_readcyclecounter();
 #ifdef SERL_LANE_GENERAL_ACTOR
     // ---- actor forward (family_laneg.hip, kernel_hint SERL_KERNEL_LANEG): every live lane runs its own actor of ANY shape over its member's row of
-    // [members][P] (rollout_device.h serl_actor_forward_lane_general: activations in private memory, no LDS, no regrouped copy); a lane without an
+    // [members][P] (lane_actor.h serl_actor_forward_lane_general: activations in private memory, no LDS, no regrouped copy); a lane without an
     // episode or with a finished one sits the pass out and loads no weight
     float act[3] = {0.0f, 0.0f, 0.0f};
     if (!done) {
@@ -106,7 +106,7 @@ static __device__ void V_NAME(serl_wave_episodes_)(const RolloutArgs &a, int e, 
     float obsf[7], act[3] = {0.0f, 0.0f, 0.0f};
     for (int i = 0; i < 7; ++i) obsf[i] = (float)obs[i];
     const unsigned wlo = (unsigned)(uintptr_t)w, whi = (unsigned)((uintptr_t)w >> 32);
-    if (lane_actor) {      // every lane runs its own actor in its own registers (rollout_device.h serl_actor_forward_lane32 / _t: the regrouped weights)
+    if (lane_actor) {      // every lane runs its own actor in its own registers (lane_actor.h serl_actor_forward_lane32 / _t: the regrouped weights)
       if (a.wt) serl_actor_forward_lane32_t(d, a.wt, a.wt_members, member, obsf, act);
       else serl_actor_forward_lane32(d, w, obsf, act);
     } else

@@ -182,7 +182,7 @@ static int32_t *serl_next_queue_counter(serl_ctx *c)
 }
 
 
-// Lane-per-episode kernels (rollout_device.h serl_actor_forward_lane32_t): the population [members][stride] regrouped to [ceil(P / 4)][mpad][4], so that parameter
+// Lane-per-episode kernels (lane_actor.h serl_actor_forward_lane32_t): the population [members][stride] regrouped to [ceil(P / 4)][mpad][4], so that parameter
 // group g of 64 consecutive members is ONE run of 1 KB.  Reads run along a member's row, writes are 16 B pieces (30 MB for 2 048 SERL50 actors: microseconds in front of a
 // launch of hundreds of milliseconds).
 __global__ void serl_regroup_weights_kernel(const float *w, int64_t stride, int32_t n_members, int32_t P, float *out, int32_t mpad)
@@ -484,7 +484,7 @@ int serl_rollout_noise(serl_ctx *c, const serl_rollout_desc *d, const serl_rollo
 }
 
 // serl_rollout (nz == NULL) / serl_rollout_noise of kernel_hint SERL_KERNEL_LANEG over a REGROUPED copy of the weights (family_lanegt.hip / family_lanegtn.hip:
-// rollout_device.h serl_actor_forward_lane_general_t): the same checks, then the LANEG plan with regroup = 1 (serl_plan.h serl_plan_rollout_regrouped), carried
+// lane_actor.h serl_actor_forward_lane_general_t): the same checks, then the LANEG plan with regroup = 1 (serl_plan.h serl_plan_rollout_regrouped), carried
 // out by serl_execute_plan as every plan -- the copy goes into the ring of SERL_WT_SLOTS slots the hidden-32 lane kernels use.
 int serl_rollout_regrouped(serl_ctx *c, const serl_rollout_desc *d, const serl_rollout_noise_desc *nz, void *stream_)
 {
@@ -648,7 +648,7 @@ static int serl_venv_launch(serl_ctx *c, const serl_venv_desc *d, VenvArgs &v, h
   a.block = p.block;
   v.d = *d;
   v.npad = serl_venv_npad(d->n_envs);
-  if (k.rd) {      // the actor shape the forward passes read (rollout_device.h serl_actor_forward_lane32 / _lane_general; venv_wave_rollout.inc reads it the same way)
+  if (k.rd) {      // the actor shape the forward passes read (lane_actor.h serl_actor_forward_lane32 / _lane_general; venv_wave_rollout.inc reads it the same way)
     a.d.state_dim = k.rd->state_dim; a.d.action_dim = k.rd->action_dim; a.d.hidden = k.rd->hidden;
     a.d.num_layers = k.rd->num_layers; a.d.activation = k.rd->activation;
   }
@@ -892,7 +892,7 @@ static int serl_venv_rollout_impl(const char *what, serl_ctx *c, const serl_venv
   { const int rc_ = serl_venv_rollout_head(w, c, d, au, rd); if (rc_ != SERL_OK) return rc_; }
   if (d->env_config != SERL_ENV_ATTITUDE || d->incremental != 0)
     return fail(SERL_E_INVALID, w + ": the attitude task without rate control only (env_config SERL_ENV_ATTITUDE, incremental 0)");
-  if (rd->hidden != 32 || rd->state_dim != 7 || rd->action_dim != 3)      // (rollout_device.h serl_lane_actor_ok)
+  if (rd->hidden != 32 || rd->state_dim != 7 || rd->action_dim != 3)      // (lane_actor.h serl_lane_actor_ok)
     return fail(SERL_E_INVALID, w + ": the in-kernel actor is 7 -> 32 .. -> 3 only (hidden 32, state_dim 7, action_dim 3)");
   if (rd->num_layers < 0) return fail(SERL_E_INVALID, w + ": num_layers < 0");
   return serl_venv_rollout_tail(w, c, d, au, rd, nz, stream_, false, false);

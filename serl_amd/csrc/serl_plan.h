@@ -130,7 +130,7 @@ static inline bool serl_use_team(const SerlCaps *c, int hint, int episodes)
 // (rollout_device.h: serl_lds_actor_ok) the actor shape whose weights live in LDS for the episode
 static inline bool serl_lds_actor_shape(const serl_rollout_desc &d) { return d.hidden == 32 && d.num_layers <= 3 && d.state_dim == 7 && d.action_dim == 3; }
 
-// (rollout_device.h serl_lane_actor_ok) the actor shape the lane-per-episode kernels read from the regrouped copy of the weights
+// (lane_actor.h serl_lane_actor_ok) the actor shape the lane-per-episode kernels read from the regrouped copy of the weights
 static inline bool serl_lane_regroup_shape(const SerlCaps *c, const serl_rollout_desc *d)
 {
   return c->env_lane_regroup && d->hidden == 32 && d->state_dim == 7 && d->action_dim == 3 && d->n_members <= (1 << 22);
@@ -175,7 +175,7 @@ static inline int serl_plan_check(const SerlCaps *c, const serl_rollout_desc *d,
 #define SERL_PLAN_FAIL(code, text) return (*message = (text), (code))
   const bool general_env = serl_plan_general_env(d);
   if (serl_resolve_hint(c, d->kernel_hint) == SERL_KERNEL_LANEG) {
-    // the limits of the lane kernel around the general lane actor (family_laneg.hip; rollout_device.h serl_actor_forward_lane_general), each by its name,
+    // the limits of the lane kernel around the general lane actor (family_laneg.hip; lane_actor.h serl_actor_forward_lane_general), each by its name,
     // in front of every other check: nothing is planned for a call the hint refuses
     if (d->env_config != SERL_ENV_ATTITUDE)
       SERL_PLAN_FAIL(SERL_E_UNSUPPORTED, "serl_rollout: kernel_hint LANEG: env_config must be SERL_ENV_ATTITUDE (the lane-per-episode kernels exist for the attitude task only)");
@@ -307,7 +307,7 @@ static inline SerlPlan serl_plan_rollout(const SerlCaps *c, const serl_rollout_d
     return p;
   }
   // Round 6, the saturating regime: from 80 episodes per CU on, one episode per LANE -- 64 per wavefront, the lane's own actor in its registers over
-  // the regrouped weights (rollout_device.h serl_actor_forward_lane32_t), at most two tables in flight and hinted index searches in the generated evaluation
+  // the regrouped weights (lane_actor.h serl_actor_forward_lane32_t), at most two tables in flight and hinted index searches in the generated evaluation
   // (tools/dag/codegen_lane.py) -- outruns the queue launch of four-episode teams (episodes x 2 001 steps, M env-steps/s: 16 384: 47.4 against 49.1; 20 480: 53.0
   // against 49.0; 32 768: 82.8; 65 536: 165.6 against 49.6; profiles/r06_saturate.jsonl).  The SERL50 actor shape, nominal / ice code, the attitude task, alone on the GPU.
   if (lanes <= 0 && hint == SERL_KERNEL_AUTO && d->concurrent_episodes <= 0 && d->hidden == 32 && d->state_dim == 7 && d->action_dim == 3 && n >= 80 * c->num_cus)
@@ -354,7 +354,7 @@ static inline SerlPlan serl_plan_rollout(const SerlCaps *c, const serl_rollout_d
 // serl_rollout_regrouped: the LANEG plan with the weights regrouped in front of the launch (family_lanegt.hip / family_lanegtn.hip read the copy; the family
 // reported stays SERL_FAMILY_LANEG).  The caller asked for the copy by name, so SERL_LANE_WEIGHTS=rows (caps env_lane_regroup == 0) does not apply.
 // `hint`: serl_plan_check's, which has refused every shape and env configuration the LANEG kernels do not take.
-#define SERL_PLAN_REGROUP_MAX_MEMBERS (1 << 22)      // (rollout_device.h serl_actor_forward_lane_general_t: the lane's 32-bit byte offset member x 16)
+#define SERL_PLAN_REGROUP_MAX_MEMBERS (1 << 22)      // (lane_actor.h serl_actor_forward_lane_general_t: the lane's 32-bit byte offset member x 16)
 static inline SerlPlan serl_plan_rollout_regrouped(const SerlCaps *c, const serl_rollout_desc *d, int hint, int noise)
 {
   if (hint != SERL_KERNEL_LANEG)

@@ -366,7 +366,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_step_auto_kerne
 }
 
 // K policy-driven steps of every env in one launch (serl_venv_rollout in include/serl_amd.h): per step the lane's own actor on the
-// current observation (rollout_device.h serl_actor_forward_lane32 on the member's plain row, a.d holds the actor shape), the action path
+// current observation (lane_actor.h serl_actor_forward_lane32 on the member's plain row, a.d holds the actor shape), the action path
 // of rollout_variant.inc, then serl_venv_step_auto_kernel_'s step, statement for statement.  The CitCtx, the env scalars and the run
 // state are loaded once and stored once; the outputs are step-major rows [k][n_envs].  Attitude task without rate control only
 // (7 observations, 3 actions: the lane actor's shape), so cfg / A / incr are constants here.  ONE call site of the actor and ONE of
@@ -549,7 +549,7 @@ __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_rollout_kernel_
 // The same K policy-driven steps for EVERY env configuration and actor shape (serl_venv_rollout_general in include/serl_amd.h): cfg, incr, S and A
 // come from the env descriptor at run time, as in serl_venv_step_auto_kernel_ -- whose action path, err / reward / write_obs handling for A == 1 and
 // incremental command are taken statement for statement, the noise and f32 forms from the general-env branch of the wave kernels (rollout_wave.inc) --
-// and the actor is rollout_device.h serl_actor_forward_lane_general (its two activation vectors in private memory).  Rows are [k][N][S], [k][N][A] and
+// and the actor is lane_actor.h serl_actor_forward_lane_general (its two activation vectors in private memory).  Rows are [k][N][S], [k][N][A] and
 // [k][N][2 S + A + 3]; action_noise stays [K][N][3], of which the first A columns are read.  ONE call site of the actor and ONE of cit_step_<v>, both loops
 // rolled, exactly as above.
 __global__ void __launch_bounds__(SERL_BLOCK) VV_KNAME(serl_venv_rollout_general_kernel_)(RolloutArgs a, VenvArgs v, serl_venv_auto_desc au, serl_venv_rollout_desc rd VV_NZ_PARAM)

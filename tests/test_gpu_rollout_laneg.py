@@ -1,5 +1,5 @@
 """The lane-per-episode population kernel for every actor shape (kernel='laneg': kernel_hint SERL_KERNEL_LANEG, csrc/family_laneg.hip and its device-noise
-twin family_lanegn.hip -- every live lane runs rollout_device.h serl_actor_forward_lane_general over its own member's row) at ZERO tolerance.
+twin family_lanegn.hip -- every live lane runs lane_actor.h serl_actor_forward_lane_general over its own member's row) at ZERO tolerance.
 
 Every launch asserts through last_rollout_info() that family 14 ('laneg') ran, and everything rollout() returns -- fitness, length_steps, length_t,
 cost_steps, the action / state / reward traces, the transition rows -- is held bit for bit to the same call with kernel='wave' (one wavefront per

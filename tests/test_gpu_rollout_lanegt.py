@@ -1,5 +1,5 @@
 """kernel='laneg' over a REGROUPED copy of the weights (lane_weights='regrouped': C ABI serl_rollout_regrouped, csrc/family_lanegt.hip and its device-noise
-twin family_lanegtn.hip -- every live lane runs rollout_device.h serl_actor_forward_lane_general_t over [ceil(P / 4)][members up to 64][4]) at ZERO tolerance.
+twin family_lanegtn.hip -- every live lane runs lane_actor.h serl_actor_forward_lane_general_t over [ceil(P / 4)][members up to 64][4]) at ZERO tolerance.
 
 Every launch asserts through last_rollout_info() that family 14 ('laneg') ran AND through last_rollout_weights() that it read a regrouped copy of the
 expected padded members and groups; everything rollout() returns -- fitness, length_steps, length_t, cost_steps, the action / state / reward traces, the

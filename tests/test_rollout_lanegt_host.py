@@ -1,5 +1,5 @@
 """kernel='laneg' over a REGROUPED copy of the weights (C ABI serl_rollout_regrouped / serl_host_plan_rollout_regrouped / serl_last_rollout_weights;
-csrc/family_lanegt.hip, family_lanegtn.hip around rollout_device.h serl_actor_forward_lane_general_t) as far as no GPU is needed: the three symbols in the
+csrc/family_lanegt.hip, family_lanegtn.hip around lane_actor.h serl_actor_forward_lane_general_t) as far as no GPU is needed: the three symbols in the
 header, the binding and the library; the ABI and the two enums it did not move; the build's ten new units; the property of the packed layout the forward
 rests on, for every shape it takes; the plans at 256 CUs word for word against the LANEG plans of serl_host_plan_rollout; every refusal with the limit it
 names; the `lane_weights` keyword through the package."""
