@@ -642,6 +642,30 @@ int serl_ga_scaled_perturb(serl_ctx *ctx, float *weights, int64_t stride, int32_
 int serl_ga_sensitivity(serl_ctx *ctx, const float *weights, int64_t stride, int32_t state_dim, int32_t hidden,
                         int32_t num_layers, int32_t action_dim, int32_t activation, const int32_t *members,
                         int32_t n_members, const float *states, int32_t batch, float *scaling, void *stream);
+/* The same sensitivity, batch-parallel, for every actor shape the TD3 learner takes (SERL_ABI_VERSION stays 9: added entry points):
+ * hidden a multiple of 4 in 4 .. 128, 0 .. 4 hidden layers, state_dim 1 .. 16, action_dim 1 .. 4, the three activations, minibatches
+ * of 1 .. 512 rows -- hidden 128 x 3, which serl_ga_sensitivity refuses for LDS, included.  weights, members, states and scaling are
+ * serl_ga_sensitivity's, scaling in the same genome order (W0, W1 .. WL, Wo); plus
+ *   work   DEVICE scratch of serl_ga_sensitivity_general_work_bytes(n_members, .., batch) bytes: per member the gradient of one output
+ *          over the genome and, per chunk of 128 samples, the states and the forward pass's tape.  Aligned as a float (4 B); what it
+ *          holds on entry does not matter, and no byte beyond work_bytes is touched.
+ *   dense  0 = the dense phases on the VALU, 1 = on the f32 matrix cores (v_mfma_f32_16x16x4_f32); the two give the same bits.
+ * One workgroup of 512 threads per member, built from the learner's phases (serl_td3_train): one forward pass over the minibatch in
+ * chunks of up to 128 samples, then per output a backward pass over every chunk whose weight gradients are batch-reduction products,
+ * accumulated over the chunks before they are squared.  `members` may repeat and need not be sorted; `stride` >= the row's parameter
+ * count; nothing outside scaling[n_members][G] and `work` is written.  Checks, in this order, all before any launch:
+ *   SERL_E_INVALID      a NULL ctx / weights / members / states / scaling, n_members < 0, batch <= 0;  dense not 0 or 1
+ *   SERL_E_UNSUPPORTED  a shape, an activation or a batch outside the ranges above
+ *   SERL_OK             n_members == 0 (nothing launched; `work` may be NULL)
+ *   SERL_E_INVALID      stride < the parameter count;  work NULL or work_bytes too small
+ *   SERL_E_UNSUPPORTED  the activation tiles (~135 KB) do not fit the device's LDS per workgroup
+ * serl_ga_sensitivity_general_work_bytes returns 0 for a shape or batch that is refused or n_members < 1. */
+int64_t serl_ga_sensitivity_general_work_bytes(int32_t n_members, int32_t state_dim, int32_t action_dim, int32_t hidden,
+                                               int32_t num_layers, int32_t batch);
+int serl_ga_sensitivity_general(serl_ctx *ctx, const float *weights, int64_t stride, int32_t state_dim, int32_t hidden,
+                                int32_t num_layers, int32_t action_dim, int32_t activation, const int32_t *members,
+                                int32_t n_members, const float *states, int32_t batch, float *scaling, void *work,
+                                int64_t work_bytes, int32_t dense, void *stream);
 /* Actor.get_novelty (genetic_agent.py:111-115) for n_pairs (actor, batch) pairs in one launch:
  *   novelty[p] = mean_b sum_a (actions[p][b][a] - actor_{members[p]}(states[p][b])[a])^2
  * -- the two halves of SSNE.get_distance (mod_neuro_evo.py:411-417), i.e. the keys of sort_groups_by_distance (:426-445). */

@@ -28,7 +28,8 @@ EXPORTS = ['serl_abi_version', 'serl_last_error', 'serl_param_count', 'serl_ctx_
            'serl_td3_train_wide', 'serl_td3_wide_layout', 'serl_td3_wide_work_bytes',
            'serl_td3_train_group_big', 'serl_td3_train_group_wide',
            'serl_ga_distill_general', 'serl_ga_distill_general_work_bytes',
-           'serl_rollout_regrouped', 'serl_host_plan_rollout_regrouped', 'serl_last_rollout_weights']
+           'serl_rollout_regrouped', 'serl_host_plan_rollout_regrouped', 'serl_last_rollout_weights',
+           'serl_ga_sensitivity_general', 'serl_ga_sensitivity_general_work_bytes']
 
 
 class BuildDesc(ctypes.Structure):
@@ -278,6 +279,8 @@ def lib():
     L.serl_abi_layout.argtypes = [VP, ctypes.c_int32]
     i32 = ctypes.c_int32
     L.serl_ga_sensitivity.argtypes = [VP, VP, ctypes.c_int64, i32, i32, i32, i32, i32, VP, i32, VP, i32, VP, VP]
+    L.serl_ga_sensitivity_general.argtypes = L.serl_ga_sensitivity.argtypes[:-1] + [VP, ctypes.c_int64, i32, VP]
+    L.serl_ga_sensitivity_general_work_bytes.argtypes = [i32] * 6
     L.serl_ga_novelty.argtypes = [VP, VP, ctypes.c_int64, i32, i32, i32, i32, i32, VP, i32, VP, VP, i32, VP, VP]
     L.serl_replay_scatter.argtypes = [VP, VP, ctypes.c_int64, VP, i32, VP]
     L.serl_replay_scatter_rows.argtypes = [VP, VP, ctypes.c_int64, i32, i32, VP, i32, VP]
@@ -347,7 +350,7 @@ def lib():
         elif f == 'serl_host_philox':
             L.serl_host_philox.restype = None
         elif f not in ('serl_last_error',):
-            getattr(L, f).restype = ctypes.c_longlong if f in ('serl_host_sample_slots', 'serl_venv_state_bytes', 'serl_td3_work_bytes', 'serl_td3_big_work_bytes', 'serl_td3_wide_work_bytes', 'serl_ga_distill_general_work_bytes') else ctypes.c_int
+            getattr(L, f).restype = ctypes.c_longlong if f in ('serl_host_sample_slots', 'serl_venv_state_bytes', 'serl_td3_work_bytes', 'serl_td3_big_work_bytes', 'serl_td3_wide_work_bytes', 'serl_ga_distill_general_work_bytes', 'serl_ga_sensitivity_general_work_bytes') else ctypes.c_int
     if L.serl_abi_version() != ABI_VERSION:
         raise RuntimeError('serl_amd: ABI version mismatch (library %d, binding %d): rebuild with `python serl_amd/build.py`'
                            % (L.serl_abi_version(), ABI_VERSION))

@@ -19,6 +19,13 @@ UNITS = {s: (s + '.hip', []) for s in ('serl_capi', 'serl_ga', 'serl_metrics', '
 UNITS.update({('rollout_' if f == 'lane' else 'rollout_%s_' % f) + v: ('family_%s.hip' % f, ['-DSERL_DYN=%d' % code])
               for f in FAMILIES for code, v in enumerate(VARIANTS)})
 UNITS['rollout_team4_mixed'] = ('rollout_team4_mixed.hip', [])      # (two code variants in one code object)
+# units added beside the table above, which tests pin entry by entry (the way _capi._Table keeps its later entries): compiled and linked like the others
+UNITS_BESIDE = {'serl_ga_sens': ('serl_ga_sens.hip', [])}            # serl_ga_sensitivity_general, built from the learner's phases (serl_td3_core.inc)
+
+
+def all_units():
+    """object stem -> (source, defines) of every unit of the library: UNITS and UNITS_BESIDE"""
+    return dict(UNITS, **UNITS_BESIDE)
 # -ffp-contract=off: the IEEE-754 operation order of the reference binary is part of the contract (no FMA fusion).
 # -disable-machine-licm: the model evaluation is inlined into the ODE5 stage loop; hoisting its ~110 f64 literals
 # out of the loop (2 SGPRs each) makes them spill -- rematerialising them at use is cheaper.
@@ -53,14 +60,14 @@ def source_hash():
 def unit_stem(unit):
     """The object stem of a unit named by its stem or, as before the family sources, by '<stem>.hip' (e.g. 'rollout_team4_nominal.hip': build/rollout_team4_nominal.o, family_team4.hip with -DSERL_DYN=0)."""
     stem = unit[:-4] if unit.endswith('.hip') else unit
-    if stem not in UNITS:
-        raise KeyError('unknown unit %r (one of: %s)' % (unit, ', '.join(UNITS)))
+    if stem not in all_units():
+        raise KeyError('unknown unit %r (one of: %s)' % (unit, ', '.join(all_units())))
     return stem
 
 
 def compile_argv(unit, out, extra_flags=(), flags=None):
     """The hipcc command line that compiles `unit` (unit_stem) into `out`: the product's FLAGS (or `flags`), the unit's defines, `extra_flags`."""
-    src, defines = UNITS[unit_stem(unit)]
+    src, defines = all_units()[unit_stem(unit)]
     return [HIPCC] + list(FLAGS if flags is None else flags) + defines + list(extra_flags) + ['-c', os.path.join(CSRC, src), '-o', out]
 
 
@@ -100,7 +107,7 @@ def build(force=False, verbose=False, extra_flags=(), lib=None, tag=''):
     path = os.path.join(CSRC, lib) if lib else LIB
     if not force and _fresh(path, _deps()):
         return path
-    return link(path, _compile(list(UNITS), tag, extra_flags, verbose))
+    return link(path, _compile(list(all_units()), tag, extra_flags, verbose))
 
 
 JITTER_LIB = 'libserl_amd_jitter.so'
@@ -115,7 +122,7 @@ def build_variant(lib, tag, extra_flags, units, force=False):
     if not force and _fresh(path, _deps() + [LIB]):
         return path
     units = [unit_stem(u) for u in units]
-    return link(path, _compile(units, tag, extra_flags) + [obj_path(u) for u in UNITS if u not in units])
+    return link(path, _compile(units, tag, extra_flags) + [obj_path(u) for u in all_units() if u not in units])
 
 
 def build_jitter(force=False):

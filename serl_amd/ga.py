@@ -137,11 +137,47 @@ def _kernel_shape_ok(spec: NetSpec):
     return 1 <= spec.state_dim <= 64 and 1 <= spec.action_dim <= 16 and 2 <= spec.hidden <= 256 and 0 <= spec.num_layers <= 16
 
 
-def sensitivity(engine, weights, members, spec: NetSpec, states, fallback=True):
+SENS_KERNELS = ('lds', 'general', 'auto')
+SENS_DENSE = ('valu', 'mfma')
+
+
+def _check_sens_choice(who, kernel, dense):
+    if kernel not in SENS_KERNELS:
+        raise ValueError('%s: kernel must be one of %s, not %r' % (who, ', '.join(SENS_KERNELS), kernel))
+    if dense not in SENS_DENSE:
+        raise ValueError('%s: dense must be one of %s, not %r' % (who, ', '.join(SENS_DENSE), dense))
+    if kernel == 'lds' and dense != 'valu':
+        raise ValueError('%s: dense=%r needs kernel=\'general\' or \'auto\' (serl_ga_sensitivity has no matrix-core phases)' % (who, dense))
+
+
+def _sens_workspace(engine, dev, spec: NetSpec, n, B):
+    """the workspace of serl_ga_sensitivity_general, cached on the engine per (shape, n, batch) -- and per stream: two launches on two
+    streams must not share one.  -> (tensor or None, bytes); 0 bytes: the library refuses the shape (the launch call says why)."""
+    nbytes = int(engine.lib.serl_ga_sensitivity_general_work_bytes(n, spec.state_dim, spec.action_dim, spec.hidden, spec.num_layers, B))
+    if nbytes <= 0:
+        return None, 0
+    cache = engine.__dict__.setdefault('_sens_work', {})
+    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream, spec.state_dim, spec.action_dim, spec.hidden, spec.num_layers, n, B)
+    work = cache.get(key)
+    if work is None:
+        work = cache[key] = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    return work, nbytes
+
+
+def sensitivity(engine, weights, members, spec: NetSpec, states, fallback=True, kernel='lds', dense='valu'):
     """The clamped output sensitivity of proximal_mutate / safe_mutate (mod_neuro_evo.py:188-217) for several members at
-    once: states f32 [n, B, state_dim] (device) -> scaling f32 [n, G] (device).  The kernel keeps one output's gradient of the
-    whole genome in LDS; an actor whose genome does not fit there (H = 128 with three hidden layers: ~208 KB) is refused with
-    SERL_E_UNSUPPORTED and, with `fallback`, computed by sensitivity_torch instead (the policy of serl_ga_distill)."""
+    once: states f32 [n, B, state_dim] (device) -> scaling f32 [n, G] (device).
+
+    kernel  'lds' (default): serl_ga_sensitivity, which keeps one output's gradient of the whole genome in LDS; an actor whose genome
+            does not fit there (H = 128 with three hidden layers: ~208 KB) is refused with SERL_E_UNSUPPORTED and, with `fallback`,
+            computed by sensitivity_torch instead (the policy of serl_ga_distill).
+            'general': serl_ga_sensitivity_general, batch-parallel, for every shape the TD3 learner takes (hidden a multiple of 4 in
+            4 .. 128, 0 .. 4 hidden layers, S <= 16, A <= 4, B <= 512); it is that kernel or a RuntimeError with the library's message,
+            never PyTorch: `fallback` does not apply to it.
+            'auto': 'lds' where it runs, 'general' where 'lds' is refused for LDS (the rule of distil_kernel='auto').
+    dense   the dense phases of the general kernel: 'valu' or 'mfma' (the f32 matrix cores; the same bits).  'mfma' with 'lds' is a
+            ValueError: that kernel has no such phases."""
+    _check_sens_choice('sensitivity', kernel, dense)
     dev = weights.device
     members = np.atleast_1d(np.asarray(members, dtype=np.int32))
     states = torch.as_tensor(states, dtype=torch.float32).to(dev).contiguous()
@@ -152,11 +188,22 @@ def sensitivity(engine, weights, members, spec: NetSpec, states, fallback=True):
         return torch.ones(n, G, dtype=torch.float32, device=dev)
     out = torch.empty(n, G, dtype=torch.float32, device=dev)
     m = _i32(dev, members)
-    rc = engine.lib.serl_ga_sensitivity(engine.ctx, weights.data_ptr(), weights.stride(0), *_net_args(spec), m.data_ptr(), n,
-                                        states.data_ptr(), B, out.data_ptr(), _stream(dev))
-    if rc == _capi.E_UNSUPPORTED and fallback and _kernel_shape_ok(spec):
-        return sensitivity_torch(weights, members, spec, states)
-    _capi.check(rc, 'serl_ga_sensitivity')
+    if kernel != 'general':
+        rc = engine.lib.serl_ga_sensitivity(engine.ctx, weights.data_ptr(), weights.stride(0), *_net_args(spec), m.data_ptr(), n,
+                                            states.data_ptr(), B, out.data_ptr(), _stream(dev))
+        if rc == _capi.E_UNSUPPORTED and _kernel_shape_ok(spec):        # refused for LDS
+            if kernel == 'auto' and engine.lib.serl_ga_sensitivity_general_work_bytes(n, spec.state_dim, spec.action_dim, spec.hidden,
+                                                                                      spec.num_layers, B) > 0:
+                kernel = 'general'
+            elif fallback:
+                return sensitivity_torch(weights, members, spec, states)
+        if kernel != 'general':
+            _capi.check(rc, 'serl_ga_sensitivity')
+            return out
+    work, nbytes = _sens_workspace(engine, dev, spec, n, B)
+    _capi.check(engine.lib.serl_ga_sensitivity_general(engine.ctx, weights.data_ptr(), weights.stride(0), *_net_args(spec), m.data_ptr(), n,
+                                                       states.data_ptr(), B, out.data_ptr(), work.data_ptr() if work is not None else None,
+                                                       nbytes, int(dense == 'mfma'), _stream(dev)), 'serl_ga_sensitivity_general')
     return out
 
 
@@ -209,13 +256,15 @@ def draw_delta(spec: NetSpec, mag):
     return dist.Normal(torch.zeros(G), torch.ones(G) * mag).sample()
 
 
-def proximal_mutate(engine, weights, member, spec: NetSpec, mag, buffer, batch_size, rng=random, delta=None):
+def proximal_mutate(engine, weights, member, spec: NetSpec, mag, buffer, batch_size, rng=random, delta=None, kernel='lds', dense='valu'):
     """SSNE.proximal_mutate (mod_neuro_evo.py:183-223) on the device-resident population: the batch is what the
     reference's `gene.buffer.sample(min(mutation_batch_size, len(buffer)))` picks (same python `random` draws), the
     sensitivity comes from serl_ga_sensitivity, delta from torch's generator, the update is serl_ga_scaled_perturb.
-    `buffer` is a replay.DeviceReplay.  safe_mutate (:254-298) is the same operator fed from the critical buffer."""
+    `buffer` is a replay.DeviceReplay.  safe_mutate (:254-298) is the same operator fed from the critical buffer.  kernel / dense:
+    sensitivity()'s, checked before any draw."""
+    _check_sens_choice('proximal_mutate', kernel, dense)
     states = buffer.sample(min(int(batch_size), len(buffer)), rng)[0]
-    scaling = sensitivity(engine, weights, [int(member)], spec, states[None])[0]
+    scaling = sensitivity(engine, weights, [int(member)], spec, states[None], kernel=kernel, dense=dense)[0]
     delta = draw_delta(spec, mag) if delta is None else delta
     scaled_perturb(engine, weights, int(member), spec, delta, scaling)
     return scaling
@@ -225,10 +274,13 @@ class ProximalBatch:
     """Several proximal / safe mutations of one epoch applied together: `add` makes a member's host draws right away, in the
     reference's order (its minibatch from python `random`, its delta from torch's generator); `apply` computes all
     sensitivities in ONE serl_ga_sensitivity launch per batch size (one workgroup per member, side by side instead of one
-    after the other) and perturbs the rows.  A mutation only reads and writes its own member."""
+    after the other) and perturbs the rows.  A mutation only reads and writes its own member.  kernel / dense: sensitivity()'s
+    (one launch per batch size whichever kernel runs)."""
 
-    def __init__(self, engine, weights, spec: NetSpec, mag, batch_size, rng=random):
+    def __init__(self, engine, weights, spec: NetSpec, mag, batch_size, rng=random, kernel='lds', dense='valu'):
+        _check_sens_choice('ProximalBatch', kernel, dense)
         self.engine, self.weights, self.spec, self.mag, self.batch_size, self.rng = engine, weights, spec, mag, int(batch_size), rng
+        self.kernel, self.dense = kernel, dense
         self.items = []
 
     def add(self, member, buffer, critical_buffer=None):
@@ -247,7 +299,8 @@ class ProximalBatch:
             by_size.setdefault(st.shape[0], []).append(k)
         scal = [None] * len(self.items)
         for B, ks in by_size.items():
-            sc = sensitivity(self.engine, self.weights, [self.items[k][0] for k in ks], self.spec, torch.stack([self.items[k][1] for k in ks]))
+            sc = sensitivity(self.engine, self.weights, [self.items[k][0] for k in ks], self.spec, torch.stack([self.items[k][1] for k in ks]),
+                             kernel=self.kernel, dense=self.dense)
             for j, k in enumerate(ks):
                 scal[k] = sc[j]
         deltas = torch.stack([d for _, _, d in self.items]).to(dev)
@@ -260,9 +313,10 @@ class ProximalBatch:
         self.items = []
 
 
-def safe_mutate(engine, weights, member, spec: NetSpec, mag, buffer, critical_buffer, batch_size, rng=random, delta=None):
+def safe_mutate(engine, weights, member, spec: NetSpec, mag, buffer, critical_buffer, batch_size, rng=random, delta=None, kernel='lds',
+                dense='valu'):
     src = critical_buffer if len(critical_buffer) > 1 else buffer          # mod_neuro_evo.py:258-261
-    return proximal_mutate(engine, weights, member, spec, mag, src, batch_size, rng, delta)
+    return proximal_mutate(engine, weights, member, spec, mag, src, batch_size, rng, delta, kernel, dense)
 
 
 def novelty(engine, weights, members, spec: NetSpec, states, actions):

@@ -120,11 +120,16 @@ class SSNE:
     critic   : callable (state, action) -> (q1, q2) on the device (TD3's critic); needed for distillation only
     record   : optional list receiving the operator calls (kind, a, b) -- the index decisions the tests pin
     distil_kernel, distil_dense : which kernel trains an epoch's distillation children and its dense phases, passed to
-               distill.distil_batch (kernel=, dense=; checked there); what ran is kept in last_distil_path"""
+               distill.distil_batch (kernel=, dense=; checked there); what ran is kept in last_distil_path
+    sensitivity_kernel, sensitivity_dense : which kernel computes the sensitivities of proximal / safe mutation and its dense phases,
+               passed to ga.sensitivity (kernel=, dense=: 'lds' | 'general' | 'auto', 'valu' | 'mfma'); checked here"""
 
-    def __init__(self, args, engine, spec, critic=None, record=None, distil_kernel='serl50', distil_dense='valu'):
+    def __init__(self, args, engine, spec, critic=None, record=None, distil_kernel='serl50', distil_dense='valu', sensitivity_kernel='lds',
+                 sensitivity_dense='valu'):
         self.args, self.engine, self.spec, self.critic, self.record = args, engine, spec, critic, record
         self.distil_kernel, self.distil_dense = distil_kernel, distil_dense
+        ga._check_sens_choice('SSNE', sensitivity_kernel, sensitivity_dense)
+        self.sensitivity_kernel, self.sensitivity_dense = sensitivity_kernel, sensitivity_dense
         self.last_distil_path = None           # info['path'] of the last distil_batch
         self.population_size = args.pop_size
         self.num_elitists = max(int(args.elite_fraction * args.pop_size), 1)
@@ -165,9 +170,11 @@ class SSNE:
         if self.mut_type in ('normal', 'inplace'):
             ga.mutate_inplace(e, weights, int(i), spec, a.mutation_mag, random, np.random)
         elif self.mut_type == 'proximal':
-            ga.proximal_mutate(e, weights, int(i), spec, a.mutation_mag, buffers[i], a.mutation_batch_size, random)
+            ga.proximal_mutate(e, weights, int(i), spec, a.mutation_mag, buffers[i], a.mutation_batch_size, random,
+                               kernel=self.sensitivity_kernel, dense=self.sensitivity_dense)
         else:
-            ga.safe_mutate(e, weights, int(i), spec, a.mutation_mag, buffers[i], critical[i], a.mutation_batch_size, random)
+            ga.safe_mutate(e, weights, int(i), spec, a.mutation_mag, buffers[i], critical[i], a.mutation_batch_size, random,
+                           kernel=self.sensitivity_kernel, dense=self.sensitivity_dense)
 
     def distilation_crossover(self, weights, first, second, buffers):
         self._rec(3, int(first), int(second))
@@ -253,7 +260,8 @@ class SSNE:
         # together afterwards (ga.ProximalBatch: one sensitivity launch for all of them)
         batch = None
         if self.mut_type in ('proximal', 'safe') and weights is not None:
-            batch = ga.ProximalBatch(self.engine, weights, self.spec, self.args.mutation_mag, self.args.mutation_batch_size, random)
+            batch = ga.ProximalBatch(self.engine, weights, self.spec, self.args.mutation_mag, self.args.mutation_batch_size, random,
+                                     kernel=self.sensitivity_kernel, dense=self.sensitivity_dense)
         for i in index_rank[self.num_elitists:]:
             if rng.random() < self.args.mutation_prob:
                 if batch is None:

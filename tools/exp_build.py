@@ -26,6 +26,6 @@ for u in units:
         sys.exit(r.stderr[-3000:])
     mine.append(obj)
 try:
-    print(B.link(os.path.join(B.CSRC, 'libserl_amd_%s.so' % tag), mine + [B.obj_path(u) for u in B.UNITS if u not in units]))
+    print(B.link(os.path.join(B.CSRC, 'libserl_amd_%s.so' % tag), mine + [B.obj_path(u) for u in B.all_units() if u not in units]))
 except RuntimeError as ex:
     sys.exit(str(ex)[-3000:])

@@ -4,7 +4,7 @@
   python tools/isa/compare_code_objects.py dump OUTDIR [--root TREE] [--units stem,stem,...] [--flags '-DX ...'] [--jobs N]
   python tools/isa/compare_code_objects.py compare PARENT_DIR BRANCH_DIR [--json OUT.json]
 
-`dump` compiles every unit of serl_amd.build.UNITS of TREE (default: this tree) device-only for gfx950 with the product's flags down to the assembly the
+`dump` compiles every unit of serl_amd.build (all_units(): UNITS and UNITS_BESIDE) of TREE (default: this tree) device-only for gfx950 with the product's flags down to the assembly the
 compiler hands its assembler (-S, no line tables) and writes OUTDIR/<unit>.json: per function symbol the text of its body with comments stripped (kept
 whole in OUTDIR/<unit>.s for diff), its SHA-256, and for kernels the resource numbers of the code-object metadata (VGPR, AGPR, SGPR, spills, private
 segment, LDS).  The assembly, not a disassembly of the linked code object: there a call of a function of the unit is a pc-relative displacement that moves
@@ -64,7 +64,7 @@ def dump_unit(B, unit, outdir, flags=()):
 
 def cmd_dump(a):
     B = load_build(os.path.abspath(a.root))
-    units = a.units.split(',') if a.units else list(B.UNITS)
+    units = a.units.split(',') if a.units else list(B.all_units() if hasattr(B, 'all_units') else B.UNITS)      # (a tree from before all_units: its UNITS)
     os.makedirs(a.outdir, exist_ok=True)
     with ThreadPoolExecutor(max_workers=a.jobs) as ex:
         for u in ex.map(lambda u: dump_unit(B, u, a.outdir, a.flags.split()), units):
