@@ -672,6 +672,38 @@ int serl_ga_sensitivity_general(serl_ctx *ctx, const float *weights, int64_t str
 int serl_ga_novelty(serl_ctx *ctx, const float *weights, int64_t stride, int32_t state_dim, int32_t hidden,
                     int32_t num_layers, int32_t action_dim, int32_t activation, const int32_t *members, int32_t n_pairs,
                     const float *states, const float *actions, int32_t batch, float *novelty, void *stream);
+/* The same novelty, batch-parallel, for every actor shape the TD3 learner takes (SERL_ABI_VERSION stays 9: an added entry point): hidden
+ * a multiple of 4 in 4 .. 128, 0 .. 4 hidden layers, state_dim 1 .. 16, action_dim 1 .. 4, the three activations, minibatches of up to
+ * max_batch <= 512 rows.  One workgroup of 512 threads per evaluation e < n_evals, built from the learner's forward phases
+ * (serl_td3_train) over chunks of 128 samples; no workspace.  An evaluation reads its minibatch itself:
+ *   state_base[e], action_base[e]   DEVICE arrays [n_evals] of device pointers; sample b of evaluation e is the state_dim floats at
+ *                  state_base[e] + r state_stride and the action_dim floats at action_base[e] + r action_stride (strides in floats),
+ *                  r = clamp(slots[e][b], 0, n_rows[e] - 1)
+ *   slots          DEVICE int32 [n_evals][max_batch], or NULL: slot b is b
+ *   n_rows, batch  DEVICE int32 [n_evals]: the rows behind the bases, and the minibatch B_e = clamp(batch[e], 0, max_batch); n_rows[e] < 1
+ *                  makes B_e 0.  Entries of slots[e] from B_e on are not read.
+ *   dense          0 = the dense phase on the VALU, 1 = on the f32 matrix cores (v_mfma_f32_16x16x4_f32); the two give the same bits.
+ * So one entry serves a replay ring (state_base = rows, action_base = rows + state_dim, both strides 2 state_dim + action_dim + 3,
+ * slots = physical ring slots) and the dense states [n][B][S] / actions [n][B][A] of serl_ga_novelty (bases = the rows of evaluation e,
+ * strides state_dim and action_dim, slots NULL, n_rows = batch = B).  Every table is read on the device: the entry reads nothing back
+ * and does not synchronise.  Samples from B_e on are zero columns and reach no sum.
+ *   novelty[e] = (sum_b sum_a (action[b][a] - actor_{members[e]}(state[b])[a])^2) / B_e     f32; B_e == 0: NaN (torch's mean of nothing)
+ * in one fixed order, so that the result is the same bits for both values of `dense`, for any n_evals and max_batch and for either
+ * layout: per sample a ascending, s_b = ((0 + d_0^2) + d_1^2) + .. (product and sum rounded separately); per column c < 128 the chunks
+ * ascending, t_c = ((s_c + s_(c+128)) + s_(c+256)) + s_(c+384), absent samples skipped; per half h of 64 columns the butterfly
+ * x_l += x_(l xor o), o = 32, 16, 8, 4, 2, 1, over t_(64 h + l) (absent columns +0); then (u_0 + u_1) / (float)B_e.
+ * `members` may repeat; `stride` >= the row's parameter count; nothing but novelty[0 .. n_evals) is written.  Checks, in this order, all
+ * before any launch (novelty untouched):
+ *   SERL_E_INVALID      a NULL ctx / weights / members / state_base / action_base / n_rows / batch / novelty, n_evals < 0;  dense not 0 or 1
+ *   SERL_E_UNSUPPORTED  a shape or an activation outside the ranges above, max_batch outside 1 .. 512
+ *   SERL_OK             n_evals == 0 (nothing launched)
+ *   SERL_E_INVALID      stride < the parameter count;  state_stride < state_dim or action_stride < action_dim
+ *   SERL_E_UNSUPPORTED  the activation tiles (~135 KB) do not fit the device's LDS per workgroup */
+int serl_ga_novelty_general(serl_ctx *ctx, const float *weights, int64_t stride, int32_t state_dim, int32_t hidden,
+                            int32_t num_layers, int32_t action_dim, int32_t activation, const int32_t *members, int32_t n_evals,
+                            const float *const *state_base, int64_t state_stride, const float *const *action_base,
+                            int64_t action_stride, const int32_t *slots, const int32_t *n_rows, const int32_t *batch,
+                            int32_t max_batch, float *novelty, int32_t dense, void *stream);
 
 /* ---- device replay rings (base/core/replay_memory.py:21-31 `add`, base/core/agent.py:101-112) ---------------------------
  * A ring is f32 [capacity][W] rows (obs S, action A, next_obs S, r, done, cost), W = 2 S + A + 3, in HBM -- the dense

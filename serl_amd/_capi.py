@@ -29,7 +29,8 @@ EXPORTS = ['serl_abi_version', 'serl_last_error', 'serl_param_count', 'serl_ctx_
            'serl_td3_train_group_big', 'serl_td3_train_group_wide',
            'serl_ga_distill_general', 'serl_ga_distill_general_work_bytes',
            'serl_rollout_regrouped', 'serl_host_plan_rollout_regrouped', 'serl_last_rollout_weights',
-           'serl_ga_sensitivity_general', 'serl_ga_sensitivity_general_work_bytes']
+           'serl_ga_sensitivity_general', 'serl_ga_sensitivity_general_work_bytes',
+           'serl_ga_novelty_general']
 
 
 class BuildDesc(ctypes.Structure):
@@ -282,6 +283,9 @@ def lib():
     L.serl_ga_sensitivity_general.argtypes = L.serl_ga_sensitivity.argtypes[:-1] + [VP, ctypes.c_int64, i32, VP]
     L.serl_ga_sensitivity_general_work_bytes.argtypes = [i32] * 6
     L.serl_ga_novelty.argtypes = [VP, VP, ctypes.c_int64, i32, i32, i32, i32, i32, VP, i32, VP, VP, i32, VP, VP]
+    # (ctx, weights, stride, S, H, L, A, act, members, n, state_base, state_stride, action_base, action_stride, slots, n_rows, batch, max_batch, novelty, dense, stream)
+    L.serl_ga_novelty_general.argtypes = [VP, VP, ctypes.c_int64, i32, i32, i32, i32, i32, VP, i32, VP, ctypes.c_int64, VP, ctypes.c_int64,
+                                          VP, VP, VP, i32, VP, i32, VP]
     L.serl_replay_scatter.argtypes = [VP, VP, ctypes.c_int64, VP, i32, VP]
     L.serl_replay_scatter_rows.argtypes = [VP, VP, ctypes.c_int64, i32, i32, VP, i32, VP]
     L.serl_smoothness.argtypes = [VP, VP, ctypes.c_int64, VP, i32, i32, ctypes.c_double, VP, VP, VP]

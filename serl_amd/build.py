@@ -20,7 +20,8 @@ UNITS.update({('rollout_' if f == 'lane' else 'rollout_%s_' % f) + v: ('family_%
               for f in FAMILIES for code, v in enumerate(VARIANTS)})
 UNITS['rollout_team4_mixed'] = ('rollout_team4_mixed.hip', [])      # (two code variants in one code object)
 # units added beside the table above, which tests pin entry by entry (the way _capi._Table keeps its later entries): compiled and linked like the others
-UNITS_BESIDE = {'serl_ga_sens': ('serl_ga_sens.hip', [])}            # serl_ga_sensitivity_general, built from the learner's phases (serl_td3_core.inc)
+UNITS_BESIDE = {'serl_ga_sens': ('serl_ga_sens.hip', []),            # serl_ga_sensitivity_general, built from the learner's phases (serl_td3_core.inc)
+                'serl_ga_nov': ('serl_ga_nov.hip', [])}              # serl_ga_novelty_general, likewise
 
 
 def all_units():

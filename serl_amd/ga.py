@@ -319,68 +319,205 @@ def safe_mutate(engine, weights, member, spec: NetSpec, mag, buffer, critical_bu
     return proximal_mutate(engine, weights, member, spec, mag, src, batch_size, rng, delta, kernel, dense)
 
 
-def novelty(engine, weights, members, spec: NetSpec, states, actions):
+NOV_KERNELS = ('lds', 'general', 'auto')
+NOV_DENSE = ('valu', 'mfma')
+NOV_MAX_BATCH = 512         # BIG_B of serl_td3_core.inc: the largest minibatch of serl_ga_novelty_general
+
+
+def _check_nov_choice(who, kernel, dense):
+    if kernel not in NOV_KERNELS:
+        raise ValueError('%s: kernel must be one of %s, not %r' % (who, ', '.join(NOV_KERNELS), kernel))
+    if dense not in NOV_DENSE:
+        raise ValueError('%s: dense must be one of %s, not %r' % (who, ', '.join(NOV_DENSE), dense))
+    if kernel == 'lds' and dense != 'valu':
+        raise ValueError('%s: dense=%r needs kernel=\'general\' or \'auto\' (serl_ga_novelty has no matrix-core phases)' % (who, dense))
+
+
+def _check_members(who, weights, members):
+    members = np.atleast_1d(np.asarray(members, dtype=np.int32))
+    if members.size and (members.min() < 0 or members.max() >= weights.shape[0]):
+        raise ValueError('%s: a member outside the population of %d rows' % (who, weights.shape[0]))
+    return members
+
+
+def _novelty_general(engine, weights, members, spec: NetSpec, state_ptr, state_stride, action_ptr, action_stride, slots, n_rows, batch,
+                     max_batch, dense):
+    """one launch of serl_ga_novelty_general: every table (host arrays; slots int32 [n, max_batch] or None) goes up in ONE int64 upload
+    -- pointers | members, n_rows, batch and the slot rows packed two int32 to a word -- and nothing comes back.  -> f32 [n] (device)"""
+    dev = weights.device
+    n = len(members)
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    i32s = [np.asarray(members, np.int32), np.asarray(n_rows, np.int32), np.asarray(batch, np.int32)]
+    if slots is not None:
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        assert slots.shape == (n, max_batch)
+        i32s.append(slots.reshape(-1))
+    ints = np.concatenate(i32s)
+    if ints.size % 2:
+        ints = np.concatenate([ints, np.zeros(1, np.int32)])
+    host = np.concatenate([np.asarray(state_ptr, np.int64), np.asarray(action_ptr, np.int64), ints.view(np.int64)])
+    tab = torch.from_numpy(host).to(dev)
+    base = tab.data_ptr()
+    p_state, p_action, p_int = base, base + 8 * n, base + 16 * n
+    _capi.check(engine.lib.serl_ga_novelty_general(engine.ctx, weights.data_ptr(), weights.stride(0), *_net_args(spec), p_int, n,
+                                                   p_state, int(state_stride), p_action, int(action_stride),
+                                                   p_int + 12 * n if slots is not None else None, p_int + 4 * n, p_int + 8 * n,
+                                                   int(max_batch), out.data_ptr(), int(dense == 'mfma'), _stream(dev)),
+                'serl_ga_novelty_general')
+    return out          # (tab is freed to torch's allocator, which hands it out again only behind this launch on its stream)
+
+
+def _general_takes(spec: NetSpec, B):
+    """the shape rule of the general kernels (td3_shape_ok of serl_td3_core.inc, max batch 512)"""
+    return (4 <= spec.hidden <= 128 and spec.hidden % 4 == 0 and 0 <= spec.num_layers <= 4 and 1 <= spec.state_dim <= 16
+            and 1 <= spec.action_dim <= 4 and 1 <= B <= NOV_MAX_BATCH)
+
+
+def novelty(engine, weights, members, spec: NetSpec, states, actions, kernel='lds', dense='valu'):
     """Actor.get_novelty (genetic_agent.py:111-115) for n (actor, batch) pairs: states [n, B, S], actions [n, B, A]
-    -> f32 [n] (device)"""
+    -> f32 [n] (device)
+
+    kernel  'lds' (default): serl_ga_novelty, one sample at a time, the shapes of check_net that fit the LDS.
+            'general': serl_ga_novelty_general, batch-parallel, for every shape the TD3 learner takes (hidden a multiple of 4 in 4 .. 128,
+            0 .. 4 hidden layers, S <= 16, A <= 4, B <= 512); it is that kernel or a RuntimeError with the library's message, never
+            another path.
+            'auto': 'lds' where it runs, 'general' where 'lds' is refused for LDS and the general kernel takes the shape.
+    dense   the dense phase of the general kernel: 'valu' or 'mfma' (the f32 matrix cores; the same bits).  'mfma' with 'lds' is a
+            ValueError: that kernel has no such phase."""
+    _check_nov_choice('novelty', kernel, dense)
     dev = weights.device
     members = np.atleast_1d(np.asarray(members, dtype=np.int32))
     states = torch.as_tensor(states, dtype=torch.float32).to(dev).contiguous()
     actions = torch.as_tensor(actions, dtype=torch.float32).to(dev).contiguous()
     n, B = states.shape[0], states.shape[1]
-    out = torch.empty(n, dtype=torch.float32, device=dev)
-    m = _i32(dev, members)
-    _capi.check(engine.lib.serl_ga_novelty(engine.ctx, weights.data_ptr(), weights.stride(0), *_net_args(spec), m.data_ptr(), n,
-                                           states.data_ptr(), actions.data_ptr(), B, out.data_ptr(), _stream(dev)), 'serl_ga_novelty')
-    return out
+    if kernel != 'general':
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        m = _i32(dev, members)
+        rc = engine.lib.serl_ga_novelty(engine.ctx, weights.data_ptr(), weights.stride(0), *_net_args(spec), m.data_ptr(), n,
+                                        states.data_ptr(), actions.data_ptr(), B, out.data_ptr(), _stream(dev))
+        if not (kernel == 'auto' and rc == _capi.E_UNSUPPORTED and _kernel_shape_ok(spec) and _general_takes(spec, B)):
+            _capi.check(rc, 'serl_ga_novelty')
+            return out
+    members = _check_members('novelty', weights, members)
+    assert n == len(members) and states.shape[2] == spec.state_dim and actions.shape == (n, B, spec.action_dim)
+    S, A = spec.state_dim, spec.action_dim
+    sp = states.data_ptr() + 4 * B * S * np.arange(n, dtype=np.int64)
+    ap = actions.data_ptr() + 4 * B * A * np.arange(n, dtype=np.int64)
+    return _novelty_general(engine, weights, members, spec, sp, S, ap, A, None, np.full(n, B), np.full(n, B), B, dense)
 
 
-def sort_groups_by_distance(engine, weights, genomes, buffers, spec: NetSpec, rng=random):
-    """SSNE.sort_groups_by_distance (mod_neuro_evo.py:426-445): every pair (i < j in list order) of `genomes` keyed by
-    get_distance = gene1.get_novelty(batch of gene2) + gene2.get_novelty(batch of gene1), batches of
-    min(256, len(buffer1), len(buffer2)) from the latest 1000 tuples of each buffer (same python `random` draws, in the
-    reference's order); all 2 * pairs forward batches in ONE launch.  -> [(second, first, distance)] sorted descending."""
+def distance_plan(genomes, buffers, rng=random):
+    """The host side of sort_groups_by_distance (mod_neuro_evo.py:426-445), pure: no GPU, no engine.  Every pair (i < j in list order)
+    of `genomes` is two evaluations -- gene1 judged on a batch of gene2's buffer, gene2 on one of gene1's -- with batches of
+    min(256, len(buffer1), len(buffer2)) picked from the latest 1000 tuples of a buffer: `ring.sample_from_latest(bs, 1000, rng)` of
+    gene1's buffer, then of gene2's, pair after pair -- the same python `random` draws in the reference's order (latest_slots(1000)
+    once per ring, runs of calls with the same (len(latest), batch) replayed in bulk by replay.sample_many).
+    -> dict: pairs   [(second, first, bs)]
+             members int32 [2 pairs]: evaluation 2 k is `first` on the batch of second's buffer, 2 k + 1 `second` on first's
+             rings   the ring every evaluation reads (2 k: buffers[second], 2 k + 1: buffers[first])
+             batch   int32 [2 pairs]
+             slots   int32 [2 pairs, max batch]: PHYSICAL ring slots of the batch rows, in draw order; 0 from batch[e] on
+             calls   [2 pairs]: the evaluation that gets the k-th sample_from_latest call of the reference's order"""
     from . import replay
-    pairs, members, calls = [], [], []
+    pairs, members, rings, calls = [], [], [], []
     for i, first in enumerate(genomes):
         for second in genomes[i + 1:]:
             b1, b2 = buffers[first], buffers[second]
             bs = min(256, min(len(b1), len(b2)))
-            calls += [(b1, bs), (b2, bs)]                  # sample_from_latest(bs, 1000) of gene1's, then of gene2's buffer
+            e = len(members)
+            calls += [e + 1, e]                            # sample_from_latest(bs, 1000) of gene1's, then of gene2's buffer
             pairs.append((second, first, bs))
             members += [first, second]                     # gene1 judged on gene2's batch, gene2 on gene1's
-    if not pairs:
-        return []
+            rings += [b2, b1]
+    n = len(members)
+    batch = np.asarray([pairs[e // 2][2] for e in range(n)], dtype=np.int32)
+    slots = np.zeros((n, int(batch.max()) if n else 0), dtype=np.int32)
     # the draws, in the reference's order; runs of calls with the same (len(latest), batch) are replayed in bulk
     latest = {}
-    for ring, _ in calls:
-        if id(ring) not in latest:
-            latest[id(ring)] = ring.latest_slots(1000)
-    picks, k0 = [None] * len(calls), 0
-    while k0 < len(calls):
-        n0, bs0 = len(latest[id(calls[k0][0])]), calls[k0][1]
+    for e in calls:
+        if id(rings[e]) not in latest:
+            latest[id(rings[e])] = rings[e].latest_slots(1000)
+    k0 = 0
+    while k0 < n:
+        key = lambda k: (len(latest[id(rings[calls[k]])]), int(batch[calls[k]]))
+        n0, bs0 = key(k0)
         k1 = k0
-        while k1 < len(calls) and (len(latest[id(calls[k1][0])]), calls[k1][1]) == (n0, bs0):
+        while k1 < n and key(k1) == (n0, bs0):
             k1 += 1
         got = replay.sample_many(n0, bs0, k1 - k0, rng)
         for k in range(k0, k1):
-            picks[k] = got[k - k0]
+            e = calls[k]
+            slots[e, :bs0] = latest[id(rings[e])][got[k - k0].astype(np.int64)]
         k0 = k1
-    batches = []
-    for (ring, _), pick in zip(calls, picks):
-        rows = ring.rows[torch.from_numpy(latest[id(ring)][pick.astype(np.int64)]).to(ring.device)]
-        batches.append(ring.split(rows))
-    st, ac = [], []
-    for k in range(len(pairs)):
-        (s1, a1, _, _, _), (s2, a2, _, _, _) = batches[2 * k], batches[2 * k + 1]
-        st += [s2, s1]; ac += [a2, a1]
-    sizes = {p[2] for p in pairs}
-    if len(sizes) == 1:
-        nov = novelty(engine, weights, members, spec, torch.stack(st), torch.stack(ac)).cpu().numpy().astype(np.float64)
-    else:               # buffers of different fill: one launch per batch size
-        nov = np.zeros(len(members), dtype=np.float64)
-        for bs in sizes:
-            idx = [k for k in range(len(members)) if pairs[k // 2][2] == bs]
-            nov[idx] = novelty(engine, weights, [members[k] for k in idx], spec, torch.stack([st[k] for k in idx]),
-                               torch.stack([ac[k] for k in idx])).cpu().numpy()
+    return dict(pairs=pairs, members=np.asarray(members, dtype=np.int32), rings=rings, batch=batch, slots=slots, calls=calls)
+
+
+def sort_groups_by_distance(engine, weights, genomes, buffers, spec: NetSpec, rng=random, kernel='lds', dense='valu'):
+    """SSNE.sort_groups_by_distance (mod_neuro_evo.py:426-445): every pair (i < j in list order) of `genomes` keyed by
+    get_distance = gene1.get_novelty(batch of gene2) + gene2.get_novelty(batch of gene1), batches of
+    min(256, len(buffer1), len(buffer2)) from the latest 1000 tuples of each buffer (same python `random` draws, in the
+    reference's order: distance_plan).  -> [(second, first, distance)] sorted descending.
+
+    kernel  'lds' (default): the batches are gathered from the rings by torch, evaluation by evaluation, and go through serl_ga_novelty,
+            one launch per distinct batch size.
+            'general': the plan's tables go up in one transfer and serl_ga_novelty_general reads the rings itself -- ONE launch for all
+            2 * pairs evaluations whatever their batch sizes, one read-back; a RuntimeError with the library's message where it refuses.
+            'auto': 'lds' where serl_ga_novelty takes the actor, 'general' where that is refused for LDS.
+    dense   novelty()'s.  A pair with an empty buffer is a ValueError before the launch with 'general' (and with 'auto' where it
+            resolves to it)."""
+    _check_nov_choice('sort_groups_by_distance', kernel, dense)
+    plan = distance_plan(genomes, buffers, rng)
+    pairs, members = plan['pairs'], plan['members']
+    if not pairs:
+        return []
+    if kernel == 'auto':
+        kernel = 'general' if (_kernel_shape_ok(spec) and not _novelty_lds_fits(spec) and _general_takes(spec, 1)) else 'lds'
+    if kernel == 'general':
+        nov = _distance_general(engine, weights, plan, spec, dense)
+    else:
+        st, ac = [], []
+        for ring, bs, sl in zip(plan['rings'], plan['batch'], plan['slots']):
+            s, a, _, _, _ = ring.split(ring.rows[torch.from_numpy(sl[:bs].astype(np.int64)).to(ring.device)])
+            st.append(s); ac.append(a)
+        members = [int(m) for m in members]
+        sizes = {p[2] for p in pairs}
+        if len(sizes) == 1:
+            nov = novelty(engine, weights, members, spec, torch.stack(st), torch.stack(ac)).cpu().numpy().astype(np.float64)
+        else:               # buffers of different fill: one launch per batch size
+            nov = np.zeros(len(members), dtype=np.float64)
+            for bs in sizes:
+                idx = [k for k in range(len(members)) if pairs[k // 2][2] == bs]
+                nov[idx] = novelty(engine, weights, [members[k] for k in idx], spec, torch.stack([st[k] for k in idx]),
+                                   torch.stack([ac[k] for k in idx])).cpu().numpy()
     groups = [(p[0], p[1], float(nov[2 * k]) + float(nov[2 * k + 1])) for k, p in enumerate(pairs)]   # two .item() floats added in f64
     return sorted(groups, key=lambda g: g[2], reverse=True)
+
+
+def _novelty_lds_fits(spec: NetSpec):
+    """whether serl_ga_novelty's forward buffers (serl_ga.hip FwdBuf) fit the 64 KB of LDS per workgroup every device has -- its only
+    refusal within _kernel_shape_ok.  They hold one sample, at most ~52 KB at hidden 256 x 16: today no shape is refused for LDS, and
+    'auto' is 'lds' on every shape serl_ga_novelty takes."""
+    S, H, L, A = spec.state_dim, spec.hidden, spec.num_layers, spec.action_dim
+    return 4 * (S + 2 * (L + 1) * H + L * H + L + 2 * A + 16) <= 64 * 1024
+
+
+def _distance_general(engine, weights, plan, spec: NetSpec, dense):
+    """the 2 * pairs evaluations of a distance_plan in ONE serl_ga_novelty_general launch that reads the rings in place -> f64 [2 pairs]"""
+    rings, batch = plan['rings'], plan['batch']
+    S, A = spec.state_dim, spec.action_dim
+    if int(batch.min()) < 1:
+        k = int(np.argmin(batch)) // 2
+        raise ValueError('sort_groups_by_distance: the pair (%d, %d) has an empty buffer: no batch to judge a distance on'
+                         % (plan['pairs'][k][1], plan['pairs'][k][0]))
+    members = _check_members('sort_groups_by_distance', weights, plan['members'])
+    for ring in rings:
+        if (ring.state_dim, ring.action_dim) != (S, A) or ring.rows.device != weights.device or not ring.rows.is_contiguous():
+            raise ValueError('sort_groups_by_distance: a ring of state_dim %d, action_dim %d on %s does not hold transitions of this actor '
+                             '(state_dim %d, action_dim %d on %s)' % (ring.state_dim, ring.action_dim, ring.rows.device, S, A, weights.device))
+    W = 2 * S + A + 3
+    sp = np.asarray([r.rows.data_ptr() for r in rings], dtype=np.int64)
+    out = _novelty_general(engine, weights, members, spec, sp, W, sp + 4 * S, W, plan['slots'], [r.capacity for r in rings], batch,
+                           int(batch.max()), dense)
+    return out.cpu().numpy().astype(np.float64)

@@ -10,7 +10,7 @@ CPU generator), so selection, pairing and mutation targets are the reference's; 
   mutate_inplace        sparse edits (`serl_ga_mutate`)                                         :329-369
   proximal / safe       sensitivity by analytic backward passes (`serl_ga_sensitivity`) + update (`serl_ga_scaled_perturb`)
                                                                                                 :183-223, :254-298
-  sort_groups_by_distance   all parent pairs' novelty batches in one launch (`serl_ga_novelty`)  :411-445
+  sort_groups_by_distance   all parent pairs' novelty batches in one launch (`serl_ga_novelty`; opt-in `serl_ga_novelty_general`)  :411-445
   distilation_crossover     behaviour cloning with Adam and the critic's Q-filter -- gradient code, PyTorch on the GPU
                             (`distill.py`), fed from the rings                                  :131-181
 
@@ -122,14 +122,20 @@ class SSNE:
     distil_kernel, distil_dense : which kernel trains an epoch's distillation children and its dense phases, passed to
                distill.distil_batch (kernel=, dense=; checked there); what ran is kept in last_distil_path
     sensitivity_kernel, sensitivity_dense : which kernel computes the sensitivities of proximal / safe mutation and its dense phases,
-               passed to ga.sensitivity (kernel=, dense=: 'lds' | 'general' | 'auto', 'valu' | 'mfma'); checked here"""
+               passed to ga.sensitivity (kernel=, dense=: 'lds' | 'general' | 'auto', 'valu' | 'mfma'); checked here
+    novelty_kernel, novelty_dense : which kernel computes the parent distances of the distillation crossover and its dense phase, passed
+               to ga.sort_groups_by_distance (kernel=, dense=: 'lds' | 'general' | 'auto', 'valu' | 'mfma'); checked here.  With
+               distil_kernel='general' and sensitivity_kernel='general', novelty_kernel='general' puts every actor-dependent operator
+               of the epoch on a batch-parallel kernel with the learner's shape contract"""
 
     def __init__(self, args, engine, spec, critic=None, record=None, distil_kernel='serl50', distil_dense='valu', sensitivity_kernel='lds',
-                 sensitivity_dense='valu'):
+                 sensitivity_dense='valu', novelty_kernel='lds', novelty_dense='valu'):
         self.args, self.engine, self.spec, self.critic, self.record = args, engine, spec, critic, record
         self.distil_kernel, self.distil_dense = distil_kernel, distil_dense
         ga._check_sens_choice('SSNE', sensitivity_kernel, sensitivity_dense)
         self.sensitivity_kernel, self.sensitivity_dense = sensitivity_kernel, sensitivity_dense
+        ga._check_nov_choice('SSNE', novelty_kernel, novelty_dense)
+        self.novelty_kernel, self.novelty_dense = novelty_kernel, novelty_dense
         self.last_distil_path = None           # info['path'] of the last distil_batch
         self.population_size = args.pop_size
         self.num_elitists = max(int(args.elite_fraction * args.pop_size), 1)
@@ -220,7 +226,8 @@ class SSNE:
             if 'fitness' in self.distil_type:
                 groups = sort_groups_by_fitness(parents, fitness)
             else:
-                groups = ga.sort_groups_by_distance(self.engine, weights, parents, buffers, self.spec, rng)
+                groups = ga.sort_groups_by_distance(self.engine, weights, parents, buffers, self.spec, rng, kernel=self.novelty_kernel,
+                                                    dense=self.novelty_dense)
                 if bcs_evals is not None:                   # mod_neuro_evo.py:505 (see the module docstring)
                     groups = sort_groups_by_novelty(parents, np.asarray(bcs_evals))
             # the children only replace unselected members, which are nobody's parents: the distillations of this loop do
