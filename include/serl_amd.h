@@ -1114,6 +1114,30 @@ int serl_host_plan_dyn(const int32_t caps[7], int32_t n_episodes, int32_t lanes_
  * i32 [n], *queue = every part drains a work queue on its share of the CUs, *place_out = the placement the launch uses. */
 int serl_host_plan_multi(int32_t num_cus, int32_t n, const int32_t *episodes, int32_t place, int32_t *grids, int32_t *queue, int32_t *place_out);
 
+/* ---- which kernel takes an actor shape (SERL_ABI_VERSION stays 9: new symbols only) --------------------------------------------------
+ * The shape contract of an entry point -- the library's own predicate (csrc/serl_shapes.h), the one the entry point refuses through --
+ * without a launch and without a device. */
+enum serl_shape_kernel {
+  SERL_SHAPE_GA_SENSITIVITY = 0,           /* serl_ga_sensitivity */
+  SERL_SHAPE_GA_NOVELTY = 1,               /* serl_ga_novelty */
+  SERL_SHAPE_GA_DISTILL = 2,               /* serl_ga_distill (batch is not read) */
+  SERL_SHAPE_TD3_TRAIN = 3,                /* serl_td3_train: minibatches of up to 128 rows; the LDS of the flavours that read tables */
+  SERL_SHAPE_TD3_TRAIN_BIG = 4,            /* serl_td3_train_big: up to 512 rows */
+  SERL_SHAPE_GA_SENSITIVITY_GENERAL = 5,   /* serl_ga_sensitivity_general */
+  SERL_SHAPE_GA_NOVELTY_GENERAL = 6,       /* serl_ga_novelty_general (batch: its max_batch) */
+  SERL_SHAPE_GA_DISTILL_GENERAL = 7,       /* serl_ga_distill_general (batch is not read) */
+  SERL_SHAPE_VENV_ROLLOUT = 8,             /* serl_venv_rollout; these two have no minibatch: `batch` is the env, env_config + 3 x (incremental != 0) */
+  SERL_SHAPE_VENV_ROLLOUT_GENERAL = 9,     /* serl_venv_rollout_general and serl_venv_rollout_wave */
+  SERL_SHAPE_KERNELS = 10
+};
+enum serl_shape_why { SERL_SHAPE_WHY_TAKES = 0, SERL_SHAPE_WHY_RANGE = 1, SERL_SHAPE_WHY_LDS = 2 };
+/* Returns what the entry point returns for this shape when nothing else is wrong with the call -- SERL_OK, or the code of its refusal with
+ * the entry point's own message in serl_last_error.  The LDS a workgroup may take is the context's (the device's sharedMemPerBlockOptin);
+ * with a NULL ctx, lds_bytes.  *why (may be NULL) tells the two refusals apart: outside the compiled range, or in range and too large for
+ * the LDS.  SERL_E_INVALID (why RANGE) for an unknown kernel. */
+int serl_shape_query(const serl_ctx *ctx, int32_t kernel, int32_t state_dim, int32_t action_dim, int32_t hidden, int32_t num_layers,
+                     int32_t activation, int32_t batch, int64_t lds_bytes, int32_t *why);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 """ctypes loader of the C-ABI HIP extension (include/serl_amd.h).  Fails loudly when the library is
 missing: the product has no CPU path."""
-import ctypes, os
+import collections, ctypes, os
 
 _D = ctypes.POINTER(ctypes.c_double)
 _F = ctypes.POINTER(ctypes.c_float)
@@ -30,7 +30,7 @@ EXPORTS = ['serl_abi_version', 'serl_last_error', 'serl_param_count', 'serl_ctx_
            'serl_ga_distill_general', 'serl_ga_distill_general_work_bytes',
            'serl_rollout_regrouped', 'serl_host_plan_rollout_regrouped', 'serl_last_rollout_weights',
            'serl_ga_sensitivity_general', 'serl_ga_sensitivity_general_work_bytes',
-           'serl_ga_novelty_general']
+           'serl_ga_novelty_general', 'serl_shape_query']
 
 
 class BuildDesc(ctypes.Structure):
@@ -348,6 +348,7 @@ def lib():
     L.serl_host_plan_rollout_regrouped.argtypes = L.serl_host_plan_rollout.argtypes
     L.serl_last_rollout_weights.argtypes = [VP, ctypes.POINTER(ctypes.c_int64)]
     L.serl_host_plan_multi.argtypes = [i32, i32, _I, i32, _I, _I, _I]
+    L.serl_shape_query.argtypes = [VP, i32, i32, i32, i32, i32, i32, i32, ctypes.c_int64, _I]
     for f in EXPORTS:
         if f == 'serl_host_uniform':
             L.serl_host_uniform.restype = ctypes.c_double
@@ -429,3 +430,31 @@ E_INVALID = -1          # SERL_E_INVALID
 def check(rc, what):
     if rc != 0:
         raise RuntimeError('%s failed (%d): %s' % (what, rc, lib().serl_last_error().decode()))
+
+
+# ---- which kernel takes an actor shape: serl_shape_query, the predicates the entry points themselves refuse through (csrc/serl_shapes.h) --------
+# enum serl_shape_kernel, by the entry point's name (serl_venv_rollout_wave shares serl_venv_rollout_general's contract)
+SHAPE_KERNELS = {'serl_ga_sensitivity': 0, 'serl_ga_novelty': 1, 'serl_ga_distill': 2, 'serl_td3_train': 3, 'serl_td3_train_big': 4,
+                 'serl_ga_sensitivity_general': 5, 'serl_ga_novelty_general': 6, 'serl_ga_distill_general': 7, 'serl_venv_rollout': 8,
+                 'serl_venv_rollout_general': 9}
+SHAPE_TAKES, SHAPE_RANGE, SHAPE_LDS = 0, 1, 2      # enum serl_shape_why
+
+
+class Shape(collections.namedtuple('Shape', 'what rc why message')):
+    """what serl_shape_query answered for the entry point `what`: its return code for the shape, why (SHAPE_*), its message"""
+    takes = property(lambda self: self.why == SHAPE_TAKES)
+    lds = property(lambda self: self.why == SHAPE_LDS)          # in range, too large for the LDS per workgroup
+
+    def check(self):
+        """the error the entry point itself would raise through check()"""
+        if self.rc != 0:
+            raise RuntimeError('%s failed (%d): %s' % (self.what, self.rc, self.message))
+
+
+def shape_query(what, spec, batch=1, ctx=None, lds_bytes=0):
+    """Would the entry point `what` run `spec` actors on minibatches of `batch` rows (the env kernels: on the env `batch` = env_config +
+    3 * incremental)?  With the LDS per workgroup of the context's device, or without a context of lds_bytes.  No device work."""
+    why = ctypes.c_int32(0)
+    rc = lib().serl_shape_query(ctx, SHAPE_KERNELS[what], spec.state_dim, spec.action_dim, spec.hidden, spec.num_layers, spec.activation_id,
+                                int(batch), int(lds_bytes), ctypes.byref(why))
+    return Shape(what, rc, why.value, lib().serl_last_error().decode() if rc else '')

@@ -851,23 +851,19 @@ int serl_venv_rollout_layout(int32_t *out, int32_t capacity)
   return n;
 }
 
-// What serl_venv_rollout_impl and serl_venv_rollout_general_impl check alike, around their own env / actor-shape refusals: the head ...
-// (the descriptors first: none of these checks reads the context)
-static int serl_venv_rollout_head(const std::string &w, serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd)
+// serl_venv_rollout* in one order: the descriptors (none of these checks reads the context), the kernel's shape contract (serl_shapes.h: the lane-32
+// kernel's, or with `general` that of the general and wave kernels), the weights and the auto-reset descriptor, the env descriptor; then the launch
+static int serl_venv_rollout_call(const char *what, serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd,
+                                  const serl_venv_noise_desc *nz, void *stream_, bool general, bool wave)
 {
+  const std::string w(what);
   if (!c || !d || !au || !rd) return fail(SERL_E_INVALID, w + ": NULL argument");
   if (!rd->obs || !rd->weights) return fail(SERL_E_INVALID, w + ": obs / weights is NULL");
   if (rd->n_steps < 1) return fail(SERL_E_INVALID, w + ": n_steps < 1");
   if (rd->n_members < 1) return fail(SERL_E_INVALID, w + ": n_members < 1");
-  return SERL_OK;
-}
-
-// ... and the tail, which ends in the launch
-static int serl_venv_rollout_tail(const std::string &w, serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd,
-                                  const serl_venv_noise_desc *nz, void *stream_, bool general, bool wave)
-{
-  if (rd->activation != SERL_ACT_TANH && rd->activation != SERL_ACT_ELU && rd->activation != SERL_ACT_LEAKY_RELU)
-    return fail(SERL_E_INVALID, w + ": unknown activation");
+  const SerlShape sv = serl_shape_of(general ? SERL_SHAPE_VENV_ROLLOUT_GENERAL : SERL_SHAPE_VENV_ROLLOUT, rd->state_dim, rd->action_dim, rd->hidden, rd->num_layers,
+                                     rd->activation, serl_shape_env(d->env_config, d->incremental));
+  if (sv.why != SERL_SHAPE_WHY_TAKES) return serl_refuse(w, sv);
   if (rd->weight_stride < (int64_t)serl_param_count(rd->state_dim, rd->hidden, rd->num_layers, rd->action_dim) || (rd->weight_stride & 3) != 0 ||
       ((uintptr_t)rd->weights & 15) != 0)
     return fail(SERL_E_INVALID, w + ": weight_stride below the parameter count or not a multiple of 4 floats, or weights not 16-byte aligned");
@@ -885,68 +881,40 @@ static int serl_venv_rollout_tail(const std::string &w, serl_ctx *c, const serl_
   return serl_venv_launch(c, &dd, v, (hipStream_t)stream_, k);
 }
 
-static int serl_venv_rollout_impl(const char *what, serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd,
-                                  const serl_venv_noise_desc *nz, void *stream_)
-{
-  const std::string w(what);
-  { const int rc_ = serl_venv_rollout_head(w, c, d, au, rd); if (rc_ != SERL_OK) return rc_; }
-  if (d->env_config != SERL_ENV_ATTITUDE || d->incremental != 0)
-    return fail(SERL_E_INVALID, w + ": the attitude task without rate control only (env_config SERL_ENV_ATTITUDE, incremental 0)");
-  if (rd->hidden != 32 || rd->state_dim != 7 || rd->action_dim != 3)      // (lane_actor.h serl_lane_actor_ok)
-    return fail(SERL_E_INVALID, w + ": the in-kernel actor is 7 -> 32 .. -> 3 only (hidden 32, state_dim 7, action_dim 3)");
-  if (rd->num_layers < 0) return fail(SERL_E_INVALID, w + ": num_layers < 0");
-  return serl_venv_rollout_tail(w, c, d, au, rd, nz, stream_, false, false);
-}
-
 int serl_venv_rollout(serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd, void *stream_)
 {
-  return serl_venv_rollout_impl("serl_venv_rollout", c, d, au, rd, nullptr, stream_);
+  return serl_venv_rollout_call("serl_venv_rollout", c, d, au, rd, nullptr, stream_, false, false);
 }
 
 int serl_venv_rollout_noise(serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd,
                             const serl_venv_noise_desc *nz, void *stream_)
 {
   { const int rc_ = serl_venv_noise_check("serl_venv_rollout_noise", d, rd, nz); if (rc_ != SERL_OK) return rc_; }
-  return serl_venv_rollout_impl("serl_venv_rollout_noise", c, d, au, rd, nz, stream_);
-}
-
-static int serl_venv_rollout_general_impl(const char *what, serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au,
-                                          const serl_venv_rollout_desc *rd, const serl_venv_noise_desc *nz, void *stream_, bool wave = false)
-{
-  const std::string w(what);
-  { const int rc_ = serl_venv_rollout_head(w, c, d, au, rd); if (rc_ != SERL_OK) return rc_; }
-  if (serl_env_state_dim(d->env_config, d->incremental) == 0)
-    return fail(SERL_E_INVALID, w + ": env_config must be SERL_ENV_ATTITUDE, SERL_ENV_SYMMETRIC or SERL_ENV_FULL");
-  if (rd->state_dim != serl_env_state_dim(d->env_config, d->incremental) || rd->action_dim != serl_env_action_dim(d->env_config))
-    return fail(SERL_E_INVALID, w + ": the actor's state_dim / action_dim do not match the env configuration (attitude 7 / 3, symmetric 2 / 1, full 13 / 3; incremental adds action_dim observations)");
-  if (rd->hidden < 4 || rd->hidden > SERL_MAX_HIDDEN || rd->hidden % 4 != 0)
-    return fail(SERL_E_UNSUPPORTED, w + ": hidden must be a multiple of 4 in 4 .. 128");
-  if (rd->num_layers < 0 || rd->num_layers > 16) return fail(SERL_E_UNSUPPORTED, w + ": num_layers must be 0 .. 16");
-  return serl_venv_rollout_tail(w, c, d, au, rd, nz, stream_, true, wave);
+  return serl_venv_rollout_call("serl_venv_rollout_noise", c, d, au, rd, nz, stream_, false, false);
 }
 
 int serl_venv_rollout_general(serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd, void *stream_)
 {
-  return serl_venv_rollout_general_impl("serl_venv_rollout_general", c, d, au, rd, nullptr, stream_);
+  return serl_venv_rollout_call("serl_venv_rollout_general", c, d, au, rd, nullptr, stream_, true, false);
 }
 
 int serl_venv_rollout_general_noise(serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd,
                                     const serl_venv_noise_desc *nz, void *stream_)
 {
   { const int rc_ = serl_venv_noise_check("serl_venv_rollout_general_noise", d, rd, nz); if (rc_ != SERL_OK) return rc_; }
-  return serl_venv_rollout_general_impl("serl_venv_rollout_general_noise", c, d, au, rd, nz, stream_);
+  return serl_venv_rollout_call("serl_venv_rollout_general_noise", c, d, au, rd, nz, stream_, true, false);
 }
 
 int serl_venv_rollout_wave(serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd, void *stream_)
 {
-  return serl_venv_rollout_general_impl("serl_venv_rollout_wave", c, d, au, rd, nullptr, stream_, true);
+  return serl_venv_rollout_call("serl_venv_rollout_wave", c, d, au, rd, nullptr, stream_, true, true);
 }
 
 int serl_venv_rollout_wave_noise(serl_ctx *c, const serl_venv_desc *d, const serl_venv_auto_desc *au, const serl_venv_rollout_desc *rd,
                                  const serl_venv_noise_desc *nz, void *stream_)
 {
   { const int rc_ = serl_venv_noise_check("serl_venv_rollout_wave_noise", d, rd, nz); if (rc_ != SERL_OK) return rc_; }
-  return serl_venv_rollout_general_impl("serl_venv_rollout_wave_noise", c, d, au, rd, nz, stream_, true);
+  return serl_venv_rollout_call("serl_venv_rollout_wave_noise", c, d, au, rd, nz, stream_, true, true);
 }
 
 // ---- the launch planner on the host (include/serl_amd.h): no context, no device ------------------------------------------------------
@@ -997,6 +965,16 @@ int serl_host_plan_multi(int32_t num_cus, int32_t n, const int32_t *episodes, in
   for (int k = 0; k < n; ++k) if (episodes[k] < 1) return fail(SERL_E_INVALID, "serl_host_plan_multi: bad argument");
   serl_plan_multi(num_cus, n, episodes, place, grids, queue, place_out);
   return SERL_OK;
+}
+
+// ---- which kernel takes an actor shape (include/serl_amd.h): the predicates of serl_shapes.h, no device ---------------------------------
+int serl_shape_query(const serl_ctx *c, int32_t kernel, int32_t state_dim, int32_t action_dim, int32_t hidden, int32_t num_layers, int32_t activation,
+                     int32_t batch, int64_t lds_bytes, int32_t *why)
+{
+  const char *who = serl_shape_who(kernel);
+  const SerlShape v = serl_shape_fit(serl_shape_of(kernel, state_dim, action_dim, hidden, num_layers, activation, batch), c ? c->lds_per_block : lds_bytes);
+  if (why) *why = v.why;
+  return v.why == SERL_SHAPE_WHY_TAKES ? SERL_OK : serl_refuse(who ? who : "serl_shape_query", v);
 }
 
 /* development aid (SERL_PROFILE=1): shader-clock cycles wave 0 of workgroup 0 spent in the actor forward, the

@@ -5,6 +5,7 @@
 #include <string>
 #include "../../include/serl_amd.h"
 #include "serl_plan.h"
+#include "serl_shapes.h"
 
 #define SERL_MAX_SLOTS 16
 #define SERL_QUEUE_COUNTERS 64
@@ -14,6 +15,8 @@
 #define SERL_MIXED_STATES 8             // placement states of serl_rollout_multi launches in flight (a ring, like the queue counters)
 
 int serl_fail(int code, const std::string &msg);      // records the thread-local message of serl_last_error()
+// the refusal of a shape predicate (serl_shapes.h) in the name of the entry point `who`
+static inline int serl_refuse(const std::string &who, const SerlShape &v) { return serl_fail(v.code, who + v.text); }
 #define HIP_TRY(expr)                                                                           \
   do {                                                                                          \
     hipError_t e_ = (expr);                                                                     \
@@ -59,3 +62,6 @@ struct serl_ctx {
   int32_t last_venv_info[4] = {};       // serl_venv_last_info: what the most recent step-wise env call launched (family, workgroups, wavefronts per workgroup, code)
   int32_t last_info[8] = {};            // serl_last_rollout_info: what the most recent rollout call launched (family, workgroups, episodes per team, queue, actor wavefronts, streamed, launches, code)
 };
+
+// a shape verdict held against this context's LDS per workgroup (the context is read for a shape in range only)
+static inline SerlShape serl_shape_here(const serl_ctx *c, const SerlShape &v) { return v.why == SERL_SHAPE_WHY_TAKES ? serl_shape_fit(v, c->lds_per_block) : v; }

@@ -360,18 +360,18 @@ int serl_ga_distill(serl_ctx *c, float *child, int64_t stride, int32_t n_pairs, 
 {
   if (!c || !child || !states || !targets || !keep || !slots || !n_steps || !batch || n_pairs < 0 || rows <= 0 || steps < 0)
     return serl_fail(SERL_E_INVALID, "serl_ga_distill: bad argument");
-  if (hidden != 32 || num_layers != 3 || state_dim < 1 || state_dim > DS_MAX || action_dim < 1 || action_dim > 4 || activation < 0 || activation > 2)
-    return serl_fail(SERL_E_UNSUPPORTED, "serl_ga_distill: compiled for the SERL50 actor family (hidden 32, 3 hidden layers); other shapes train in PyTorch");
+  static_assert(DB == SERL_DISTILL_THREADS && DS_MAX == SERL_DISTILL_MAX_S, "serl_shapes.h states this kernel's contract");
+  SerlShape v = serl_shape_of(SERL_SHAPE_GA_DISTILL, state_dim, action_dim, hidden, num_layers, activation, 1);
+  if (v.why != SERL_SHAPE_WHY_TAKES) return serl_refuse("serl_ga_distill", v);
   HIP_TRY(hipSetDevice(c->device));
   DistillArgs a;
   a.child = child; a.stride = stride; a.states = states; a.targets = targets; a.keep = keep; a.slots = slots; a.n_steps = n_steps;
   a.batch = batch; a.rows = rows; a.steps = steps; a.S = state_dim; a.A = action_dim; a.L = num_layers; a.act = activation;
   a.lr = lr; a.beta1 = 0.9f; a.beta2 = 0.999f; a.eps = 1e-8f;
-  const int P = hidden * state_dim + hidden + num_layers * (hidden * hidden + 3 * hidden) + action_dim * hidden + action_dim;
-  const size_t lds = ((size_t)4 * ((P + 3) & ~3) + (size_t)(num_layers + 3) * hidden * DB) * sizeof(float);
-  if (lds > (size_t)c->lds_per_block)
-    return serl_fail(SERL_E_UNSUPPORTED, "serl_ga_distill: the training state does not fit this device's LDS per workgroup; the caller trains pair by pair in PyTorch");
-  if (n_pairs == 0 || steps == 0) return SERL_OK;      // (n_pairs = 0 is the caller's probe: "would this shape run here?")
+  const size_t lds = (size_t)v.lds_bytes;
+  v = serl_shape_here(c, v);
+  if (v.why != SERL_SHAPE_WHY_TAKES) return serl_refuse("serl_ga_distill", v);
+  if (n_pairs == 0 || steps == 0) return SERL_OK;      // (behind every check: a call with nothing to train still says whether it would run)
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(distill_kernel<32, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL((distill_kernel<32, 3>), dim3(n_pairs), dim3(DB), lds, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());

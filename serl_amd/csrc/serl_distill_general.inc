@@ -103,12 +103,10 @@ int distill_general(serl_ctx *c, float *child, int64_t stride, int32_t n_pairs, 
   if (!c || !child || !states || !targets || !keep || !slots || !n_steps || !batch || n_pairs < 0 || rows <= 0 || steps < 0 || !(lr > 0.0f))
     return serl_fail(SERL_E_INVALID, who + ": bad argument");
   if (dense != 0 && dense != 1) return serl_fail(SERL_E_INVALID, who + ": dense must be 0 (valu) or 1 (mfma)");
-  if (!td3_shape_ok(state_dim, action_dim, hidden, num_layers, 1) || activation < 0 || activation > 2)
-    return serl_fail(SERL_E_UNSUPPORTED, who + ": compiled for hidden a multiple of 4 in 4 .. 128, 0 .. 4 hidden layers, state_dim 1 .. 16, "
-                                               "action_dim 1 .. 4, the three activations");
-  const size_t lds = td3_lds_bytes(0);
-  if (lds > (size_t)c->lds_per_block) return serl_fail(SERL_E_UNSUPPORTED, who + ": the activation tiles do not fit this device's LDS per workgroup");
-  if (n_pairs == 0 || steps == 0) return SERL_OK;       // (n_pairs = 0 is the caller's probe: "would this shape run here?")
+  const SerlShape v = serl_shape_here(c, serl_shape_of(SERL_SHAPE_GA_DISTILL_GENERAL, state_dim, action_dim, hidden, num_layers, activation, 1));
+  if (v.why != SERL_SHAPE_WHY_TAKES) return serl_refuse(who, v);
+  const size_t lds = (size_t)v.lds_bytes;
+  if (n_pairs == 0 || steps == 0) return SERL_OK;       // (behind every check: a call with nothing to train still says whether it would run)
   const int P = actor_params(state_dim, action_dim, hidden, num_layers);
   if (stride < P) return serl_fail(SERL_E_INVALID, who + ": the row stride is smaller than the parameter count");
   DistillGArgs a;

@@ -332,15 +332,6 @@ __global__ void __launch_bounds__(256) replay_scatter_rows_kernel(const float *s
   }
 }
 
-int check_net(const serl_ctx *c, int S, int H, int L, int A, int act, size_t lds_bytes, const char *who)
-{
-  if (S < 1 || S > 64 || A < 1 || A > 16 || H < 2 || H > 256 || L < 0 || L > 16 || act < 0 || act > 2)
-    return serl_fail(SERL_E_UNSUPPORTED, std::string(who) + ": network shape out of range");
-  if (lds_bytes > (size_t)c->lds_per_block)
-    return serl_fail(SERL_E_UNSUPPORTED, std::string(who) + ": network too large for the LDS-resident accumulators");
-  return SERL_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -352,11 +343,11 @@ int serl_ga_sensitivity(serl_ctx *c, const float *weights, int64_t stride, int32
   if (!c || !weights || !members || !states || !scaling || n_members < 0 || batch <= 0)
     return serl_fail(SERL_E_INVALID, "serl_ga_sensitivity: bad argument");
   if (n_members == 0) return SERL_OK;
+  const SerlShape v = serl_shape_here(c, serl_shape_of(SERL_SHAPE_GA_SENSITIVITY, state_dim, action_dim, hidden, num_layers, activation, batch));
+  if (v.why != SERL_SHAPE_WHY_TAKES) return serl_refuse("serl_ga_sensitivity", v);
   const NetDims n{state_dim, hidden, num_layers, action_dim, activation};
-  const int G = hidden * state_dim + num_layers * hidden * hidden + action_dim * hidden;
-  const int fwd = n.S + 2 * (n.L + 1) * n.H + n.L * n.H + n.L + 2 * n.A + 16;
-  const size_t lds = sizeof(float) * ((size_t)G + fwd + 2 * (size_t)hidden);
-  if (int rc = check_net(c, state_dim, hidden, num_layers, action_dim, activation, lds, "serl_ga_sensitivity")) return rc;
+  const int G = (int)serl_ga_genome_floats(state_dim, action_dim, hidden, num_layers);
+  const size_t lds = (size_t)v.lds_bytes;
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(ga_sensitivity_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(ga_sensitivity_kernel, dim3(n_members), dim3(256), lds, (hipStream_t)stream, weights, stride, n, members, states,
@@ -372,10 +363,10 @@ int serl_ga_novelty(serl_ctx *c, const float *weights, int64_t stride, int32_t s
   if (!c || !weights || !members || !states || !actions || !novelty || n_pairs < 0 || batch <= 0)
     return serl_fail(SERL_E_INVALID, "serl_ga_novelty: bad argument");
   if (n_pairs == 0) return SERL_OK;
+  const SerlShape v = serl_shape_here(c, serl_shape_of(SERL_SHAPE_GA_NOVELTY, state_dim, action_dim, hidden, num_layers, activation, batch));
+  if (v.why != SERL_SHAPE_WHY_TAKES) return serl_refuse("serl_ga_novelty", v);
   const NetDims n{state_dim, hidden, num_layers, action_dim, activation};
-  const int fwd = n.S + 2 * (n.L + 1) * n.H + n.L * n.H + n.L + 2 * n.A + 16;
-  const size_t lds = sizeof(float) * (size_t)fwd;
-  if (int rc = check_net(c, state_dim, hidden, num_layers, action_dim, activation, lds, "serl_ga_novelty")) return rc;
+  const size_t lds = (size_t)v.lds_bytes;
   HIP_TRY(hipSetDevice(c->device));
   hipLaunchKernelGGL(ga_novelty_kernel, dim3(n_pairs), dim3(256), lds, (hipStream_t)stream, weights, stride, n, members, states, actions,
                      batch, novelty);

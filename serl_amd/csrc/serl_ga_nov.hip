@@ -121,16 +121,15 @@ int serl_ga_novelty_general(serl_ctx *c, const float *weights, int64_t stride, i
   if (!c || !weights || !members || !state_base || !action_base || !n_rows || !batch || !novelty || n_evals < 0)
     return serl_fail(SERL_E_INVALID, who + ": bad argument");
   if (dense != 0 && dense != 1) return serl_fail(SERL_E_INVALID, who + ": dense must be 0 (valu) or 1 (mfma)");
-  if (!td3_shape_ok(state_dim, action_dim, hidden, num_layers, max_batch, BIG_B) || activation < 0 || activation > 2)
-    return serl_fail(SERL_E_UNSUPPORTED, who + ": compiled for hidden a multiple of 4 in 4 .. 128, 0 .. 4 hidden layers, state_dim 1 .. 16, "
-                                               "action_dim 1 .. 4, the three activations, minibatches of 1 .. 512 rows");
+  SerlShape v = serl_shape_of(SERL_SHAPE_GA_NOVELTY_GENERAL, state_dim, action_dim, hidden, num_layers, activation, max_batch);
+  if (v.why != SERL_SHAPE_WHY_TAKES) return serl_refuse(who, v);
   if (n_evals == 0) return SERL_OK;
   if (stride < actor_params(state_dim, action_dim, hidden, num_layers))
     return serl_fail(SERL_E_INVALID, who + ": the row stride is smaller than the parameter count");
   if (state_stride < state_dim || action_stride < action_dim)
     return serl_fail(SERL_E_INVALID, who + ": a row stride of the minibatch is smaller than its row (state_dim, action_dim)");
-  const size_t lds = td3_lds_bytes(0);
-  if (lds > (size_t)c->lds_per_block) return serl_fail(SERL_E_UNSUPPORTED, who + ": the activation tiles do not fit this device's LDS per workgroup");
+  const size_t lds = (size_t)v.lds_bytes;
+  if ((v = serl_shape_here(c, v)).why != SERL_SHAPE_WHY_TAKES) return serl_refuse(who, v);
   HIP_TRY(hipSetDevice(c->device));
   NovArgs a;
   a.weights = weights; a.stride = stride; a.members = members; a.state_base = state_base; a.action_base = action_base;

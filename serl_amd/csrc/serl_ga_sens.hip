@@ -139,7 +139,7 @@ extern "C" {
 int64_t serl_ga_sensitivity_general_work_bytes(int32_t n_members, int32_t state_dim, int32_t action_dim, int32_t hidden, int32_t num_layers,
                                                int32_t batch)
 {
-  if (n_members < 1 || !td3_shape_ok(state_dim, action_dim, hidden, num_layers, batch, BIG_B)) return 0;
+  if (n_members < 1 || !serl_learner_range(state_dim, action_dim, hidden, num_layers, batch, BIG_B)) return 0;
   return (int64_t)n_members * sens_work_floats(state_dim, action_dim, hidden, num_layers, batch) * (int64_t)sizeof(float);
 }
 
@@ -150,9 +150,8 @@ int serl_ga_sensitivity_general(serl_ctx *c, const float *weights, int64_t strid
   const std::string who("serl_ga_sensitivity_general");
   if (!c || !weights || !members || !states || !scaling || n_members < 0 || batch <= 0) return serl_fail(SERL_E_INVALID, who + ": bad argument");
   if (dense != 0 && dense != 1) return serl_fail(SERL_E_INVALID, who + ": dense must be 0 (valu) or 1 (mfma)");
-  if (!td3_shape_ok(state_dim, action_dim, hidden, num_layers, batch, BIG_B) || activation < 0 || activation > 2)
-    return serl_fail(SERL_E_UNSUPPORTED, who + ": compiled for hidden a multiple of 4 in 4 .. 128, 0 .. 4 hidden layers, state_dim 1 .. 16, "
-                                               "action_dim 1 .. 4, the three activations, minibatches of 1 .. 512 rows");
+  SerlShape v = serl_shape_of(SERL_SHAPE_GA_SENSITIVITY_GENERAL, state_dim, action_dim, hidden, num_layers, activation, batch);
+  if (v.why != SERL_SHAPE_WHY_TAKES) return serl_refuse(who, v);
   if (n_members == 0) return SERL_OK;
   if (stride < actor_params(state_dim, action_dim, hidden, num_layers))
     return serl_fail(SERL_E_INVALID, who + ": the row stride is smaller than the parameter count");
@@ -160,8 +159,8 @@ int serl_ga_sensitivity_general(serl_ctx *c, const float *weights, int64_t strid
   a.work_floats = sens_work_floats(state_dim, action_dim, hidden, num_layers, batch);
   if (!work || work_bytes < (int64_t)n_members * a.work_floats * (int64_t)sizeof(float))
     return serl_fail(SERL_E_INVALID, who + ": workspace NULL or smaller than serl_ga_sensitivity_general_work_bytes");
-  const size_t lds = td3_lds_bytes(0);
-  if (lds > (size_t)c->lds_per_block) return serl_fail(SERL_E_UNSUPPORTED, who + ": the activation tiles do not fit this device's LDS per workgroup");
+  const size_t lds = (size_t)v.lds_bytes;
+  if ((v = serl_shape_here(c, v)).why != SERL_SHAPE_WHY_TAKES) return serl_refuse(who, v);
   HIP_TRY(hipSetDevice(c->device));
   a.weights = weights; a.stride = stride; a.members = members; a.states = states; a.scaling = scaling; a.work = (float *)work;
   a.S = state_dim; a.A = action_dim; a.H = hidden; a.L = num_layers; a.act = activation; a.B = batch;

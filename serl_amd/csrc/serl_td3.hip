@@ -181,7 +181,7 @@ struct Td3Run {
   int slot_cols;
   bool caps;                            // CAPS on: the generator's switch, or the presence of the caller's table
   float *tq;                            // LDS [BP] target Q
-  int *slot_l;                          // LDS [BP] or [BIG_B] the minibatch's slots (RNG only: td3_lds_bytes)
+  int *slot_l;                          // LDS [BP] or [BIG_B] the minibatch's slots (RNG only: serl_shapes.h slot_rows)
   float max_grad_norm, invB, invBA;
 };
 
@@ -660,8 +660,9 @@ int td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream, const Td3Call &
   if (!d->actor || !d->actor_target || !d->actor_m || !d->actor_v || !d->critic || !d->critic_target || !d->critic_m || !d->critic_v ||
       !d->adam_steps || (own && !d->ring) || (tables && (!d->slots || !d->target_noise)) || !d->td_loss || !d->pg_loss || !d->work)
     return serl_fail(SERL_E_INVALID, who + ": NULL array (only caps_noise may be NULL: CAPS off)");
-  if (d->state_dim < 1 || d->action_dim < 1 || d->hidden < 1 || d->num_layers < 0 || d->batch < 1 || d->activation < 0 || d->activation > 2)
-    return serl_fail(SERL_E_INVALID, who + ": network shape / minibatch / activation");
+  // (the shape's two refusals stand where they always stood among the others: arguments first, the range behind the hyper-parameters, the LDS last)
+  SerlShape v = serl_shape_td3(d->state_dim, d->action_dim, d->hidden, d->num_layers, d->activation, d->batch, big, tables ? 0 : big ? BIG_B : BP);
+  if (v.code == SERL_E_INVALID) return serl_refuse(who, v);
   if (d->n_learners < 1 || d->n_updates < 0 || (own && d->capacity < 1) || (tables && d->slot_cols < d->batch) ||
       (own && (d->policy_update_freq < 1 || d->iteration0 < 0)))
     return serl_fail(SERL_E_INVALID, who + ": n_learners >= 1, n_updates >= 0, capacity >= 1, slot_cols >= batch, policy_update_freq >= 1, iteration0 >= 0");
@@ -670,9 +671,7 @@ int td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream, const Td3Call &
       (own && (!(d->lr > 0.0f) || !(d->gamma >= 0.0f) || !(d->tau >= 0.0f && d->tau <= 1.0f) || !(d->noise_sd >= 0.0f) || !(d->noise_clip >= 0.0f) ||
                !(d->eps_sd >= 0.0f) || d->lambda_s != d->lambda_s || d->lambda_t != d->lambda_t)))
     return serl_fail(SERL_E_INVALID, who + ": lr > 0, gamma >= 0, 0 <= tau <= 1, noise_sd >= 0, noise_clip >= 0, max_grad_norm > 0, eps_sd >= 0");
-  if (!td3_shape_ok(d->state_dim, d->action_dim, d->hidden, d->num_layers, d->batch, big ? BIG_B : BP))
-    return serl_fail(SERL_E_UNSUPPORTED, who + ": compiled for hidden a multiple of 4 in 4 .. 128, 0 .. 4 hidden layers, state_dim 1 .. 16, "
-                                         "action_dim 1 .. 4, minibatches of 1 .. " + (big ? "512" : "128") + " rows; other shapes train in PyTorch");
+  if (v.why != SERL_SHAPE_WHY_TAKES) return serl_refuse(who, v);
   const int Pa = serl_param_count(d->state_dim, d->hidden, d->num_layers, d->action_dim), Pc = serl_td3_param_count(d->state_dim, d->action_dim);
   if (d->actor_stride < Pa || d->critic_stride < Pc) return serl_fail(SERL_E_INVALID, who + ": a row stride is smaller than its parameter count");
   if ((own && d->ring_stride < 0) || (tables && (d->slots_stride < 0 || d->noise_stride < 0 || d->caps_stride < 0)) || d->loss_stride < d->n_updates)
@@ -685,8 +684,8 @@ int td3_train(serl_ctx *c, const serl_td3_desc *d, void *stream, const Td3Call &
   if (d->work_bytes < (int64_t)d->n_learners * (a.work_floats + (call.wide ? WIDE_SYNC_WORDS : 0)) * (int64_t)sizeof(float))
     return serl_fail(SERL_E_INVALID, who + ": workspace smaller than " +
                                          (call.wide ? "serl_td3_wide_work_bytes" : big ? "serl_td3_big_work_bytes" : "serl_td3_work_bytes"));
-  const size_t lds = td3_lds_bytes(tables ? 0 : big ? BIG_B : BP);
-  if (lds > (size_t)c->lds_per_block) return serl_fail(SERL_E_UNSUPPORTED, who + ": the activation tiles do not fit this device's LDS per workgroup");
+  const size_t lds = (size_t)v.lds_bytes;
+  if ((v = serl_shape_here(c, v)).why != SERL_SHAPE_WHY_TAKES) return serl_refuse(who, v);
   bool mfma = call.mfma;
   if (call.source == TD3_GROUP) {
     const serl_td3_group_desc *gd = call.group;
@@ -764,7 +763,7 @@ int serl_td3_param_count(int state_dim, int action_dim)
 
 int64_t serl_td3_work_bytes(int32_t n_learners, int32_t state_dim, int32_t action_dim, int32_t hidden, int32_t num_layers, int32_t batch)
 {
-  if (n_learners < 1 || !td3_shape_ok(state_dim, action_dim, hidden, num_layers, batch)) return 0;
+  if (n_learners < 1 || !serl_learner_range(state_dim, action_dim, hidden, num_layers, batch, BP)) return 0;
   return (int64_t)n_learners * td3_work_floats(state_dim, action_dim, hidden, num_layers) * (int64_t)sizeof(float);
 }
 
@@ -859,7 +858,7 @@ int serl_td3_rng_fill_big(serl_ctx *c, const serl_td3_rng_desc *rg, int32_t lear
 
 int64_t serl_td3_big_work_bytes(int32_t n_learners, int32_t state_dim, int32_t action_dim, int32_t hidden, int32_t num_layers, int32_t batch)
 {
-  if (n_learners < 1 || !td3_shape_ok(state_dim, action_dim, hidden, num_layers, batch, BIG_B)) return 0;
+  if (n_learners < 1 || !serl_learner_range(state_dim, action_dim, hidden, num_layers, batch, BIG_B)) return 0;
   return (int64_t)n_learners * td3_work_floats(state_dim, action_dim, hidden, num_layers, (batch + BP - 1) / BP) * (int64_t)sizeof(float);
 }
 
@@ -908,7 +907,7 @@ int serl_td3_train_wide(serl_ctx *c, const serl_td3_desc *d, const serl_td3_wide
 
 int64_t serl_ga_distill_general_work_bytes(int32_t n_pairs, int32_t state_dim, int32_t action_dim, int32_t hidden, int32_t num_layers)
 {
-  if (n_pairs < 1 || !td3_shape_ok(state_dim, action_dim, hidden, num_layers, 1)) return 0;
+  if (n_pairs < 1 || !serl_learner_range(state_dim, action_dim, hidden, num_layers, 1, BP)) return 0;
   return (int64_t)n_pairs * distill_g_work_floats(state_dim, action_dim, hidden, num_layers) * (int64_t)sizeof(float);
 }
 

@@ -365,13 +365,6 @@ __device__ __forceinline__ float *mlp_bwd(const Ctx &c, const Net &net, const fl
   return D;
 }
 
-// slot_rows: the slot array of the generator flavours (BP, or BIG_B for the chunked ones), 0 with tables
-size_t td3_lds_bytes(int slot_rows)
-{
-  return ((size_t)2 * TILE_ROWS * LP + NG * BP + 64 + BP + slot_rows) * sizeof(float);
-}
-
-bool td3_shape_ok(int S, int A, int H, int L, int B, int max_batch = BP)
-{
-  return H >= 4 && H <= TILE_ROWS && H % 4 == 0 && L >= 0 && L <= 4 && S >= 1 && S <= 16 && A >= 1 && A <= 4 && B >= 1 && B <= max_batch;
-}
+// the shapes this core runs and the LDS it takes are stated in serl_shapes.h (serl_learner_range, serl_shape_learner_takes)
+static_assert(NT == SERL_LEARNER_THREADS && BP == SERL_LEARNER_BP && BIG_B == SERL_LEARNER_BIG_B && LP == SERL_LEARNER_LP && TILE_ROWS == SERL_LEARNER_TILE_ROWS,
+              "serl_shapes.h states this core's contract");

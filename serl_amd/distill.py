@@ -122,22 +122,27 @@ def _batched_forward(spec, rows, states):
 
 
 KERNELS = ('serl50', 'general', 'auto')
-DENSE = ('valu', 'mfma')
 
 
-def _probe(engine, spec, weights, general):
-    """the n_pairs = 0 call of serl_ga_distill / serl_ga_distill_general: would the kernel run this shape on this device?  Launches
-    nothing and consumes no draw."""
-    import ctypes
+def resolve(engine, spec, dev, kernel, dense):
+    """The one path a checked choice trains `spec` children on, asked of the library (serl_shape_query) before any draw and any launch
+    -> 'fused' | 'fused-general' | 'fused-general-mfma' | 'torch'.  'serl50': serl_ga_distill where the device is a GPU and it takes the
+    shape, else PyTorch.  'general': serl_ga_distill_general or a RuntimeError.  'auto': the first of the three that runs."""
     from . import _capi
-    z = ctypes.c_void_p(0)
-    one = torch.zeros(4, dtype=torch.int32, device=weights.device)
-    a = (engine.ctx, weights.data_ptr(), weights.stride(0), 0, spec.state_dim, spec.hidden, spec.num_layers, spec.action_dim,
-         spec.activation_id, weights.data_ptr(), weights.data_ptr(), weights.data_ptr(), 1, one.data_ptr(), 0, one.data_ptr(),
-         one.data_ptr(), ctypes.c_float(1e-3))
-    if general:
-        return _capi.lib().serl_ga_distill_general(*a, z, 0, 0, z) == 0
-    return _capi.lib().serl_ga_distill(*a, z) == 0
+    general_path = 'fused-general-mfma' if dense == 'mfma' else 'fused-general'
+    if kernel == 'general':
+        v = _capi.shape_query('serl_ga_distill_general', spec, 1, engine.ctx) if dev.type == 'cuda' else None
+        if v is None or not v.takes:
+            raise RuntimeError('distil_batch(kernel=\'general\'): serl_ga_distill_general does not run %r on %s%s' % (
+                spec, dev, (': ' + v.message) if v else ''))
+        return general_path
+    if dev.type != 'cuda':
+        return 'torch'
+    if _capi.shape_query('serl_ga_distill', spec, 1, engine.ctx).takes:
+        return 'fused'
+    if kernel == 'auto' and _capi.shape_query('serl_ga_distill_general', spec, 1, engine.ctx).takes:
+        return general_path
+    return 'torch'
 
 
 def distil_batch(args, engine, spec, weights, pairs, buffers, critic, rng=random, kernel='serl50', dense='valu', info=None):
@@ -161,32 +166,12 @@ def distil_batch(args, engine, spec, weights, pairs, buffers, critic, rng=random
     import ctypes
     import numpy as np
     from . import _capi
-    if kernel not in KERNELS:
-        raise ValueError('distil_batch: kernel must be one of %s, not %r' % (', '.join(KERNELS), kernel))
-    if dense not in DENSE:
-        raise ValueError('distil_batch: dense must be one of %s, not %r' % (', '.join(DENSE), dense))
-    if kernel == 'serl50' and dense != 'valu':
-        raise ValueError('distil_batch: dense=%r needs kernel=\'general\' or \'auto\' (serl_ga_distill has no matrix-core phases)' % dense)
+    from . import ga
+    ga.check_choice('distil_batch', kernel, dense, 'serl_ga_distill', KERNELS)
     if critic is None:
         raise ValueError('distilation_crossover needs the learner\'s critic: SSNE(args, engine, spec, critic=...)')
     dev = weights.device
-    general_path = 'fused-general-mfma' if dense == 'mfma' else 'fused-general'
-    path = 'torch'
-    if kernel == 'general':
-        if dev.type != 'cuda' or not _probe(engine, spec, weights, True):
-            raise RuntimeError('distil_batch(kernel=\'general\'): serl_ga_distill_general does not run %r on %s%s' % (
-                spec, dev, (': ' + _capi.lib().serl_last_error().decode()) if dev.type == 'cuda' else ''))
-        path = general_path
-    else:
-        fused = dev.type == 'cuda' and spec.hidden == 32 and spec.num_layers == 3 and spec.state_dim <= 16 and spec.action_dim <= 4
-        if fused and pairs:
-            # probe before any host draw is consumed: n_pairs = 0 returns SERL_E_UNSUPPORTED when the training state does not fit
-            # this device's LDS per workgroup (the fused kernel needs ~158 KB), and then the pairs train one by one in PyTorch
-            fused = _probe(engine, spec, weights, False)
-        if fused:
-            path = 'fused'
-        elif kernel == 'auto' and dev.type == 'cuda' and _probe(engine, spec, weights, True):
-            path = general_path
+    path = resolve(engine, spec, dev, kernel, dense)
     if info is not None:
         info['path'] = path
     if path == 'torch' or not pairs:

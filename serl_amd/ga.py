@@ -132,22 +132,36 @@ def genome_size(spec: NetSpec):
     return sum(n for _, n in spec.genome_segments())
 
 
-# the network shapes serl_ga_sensitivity / serl_ga_novelty take (serl_ga.hip check_net); within them the only other refusal is LDS
-def _kernel_shape_ok(spec: NetSpec):
-    return 1 <= spec.state_dim <= 64 and 1 <= spec.action_dim <= 16 and 2 <= spec.hidden <= 256 and 0 <= spec.num_layers <= 16
+KERNELS = ('lds', 'general', 'auto')
+DENSE = ('valu', 'mfma')
 
 
-SENS_KERNELS = ('lds', 'general', 'auto')
-SENS_DENSE = ('valu', 'mfma')
+def check_choice(who, kernel, dense, entry, kernels=KERNELS):
+    """a (kernel, dense) pair of sensitivity / novelty / distil_batch: `kernels` = (the kernel behind `entry`, which has no matrix-core phases,
+    'general', 'auto')"""
+    if kernel not in kernels:
+        raise ValueError('%s: kernel must be one of %s, not %r' % (who, ', '.join(kernels), kernel))
+    if dense not in DENSE:
+        raise ValueError('%s: dense must be one of %s, not %r' % (who, ', '.join(DENSE), dense))
+    if kernel == kernels[0] and dense != 'valu':
+        raise ValueError('%s: dense=%r needs kernel=\'general\' or \'auto\' (%s has no matrix-core phases)' % (who, dense, entry))
 
 
-def _check_sens_choice(who, kernel, dense):
-    if kernel not in SENS_KERNELS:
-        raise ValueError('%s: kernel must be one of %s, not %r' % (who, ', '.join(SENS_KERNELS), kernel))
-    if dense not in SENS_DENSE:
-        raise ValueError('%s: dense must be one of %s, not %r' % (who, ', '.join(SENS_DENSE), dense))
-    if kernel == 'lds' and dense != 'valu':
-        raise ValueError('%s: dense=%r needs kernel=\'general\' or \'auto\' (serl_ga_sensitivity has no matrix-core phases)' % (who, dense))
+def resolve(engine, spec: NetSpec, B, kernel, entry, fallback=False):
+    """The one path a checked choice runs `spec` on at minibatches of B rows, asked of the library (serl_shape_query) before anything is
+    launched -> 'lds' (`entry`) | 'general' (`entry`_general) | 'torch'; where none of them is to run, the library's own error.
+    'general': that kernel.  'lds': `entry` where it takes the shape; refused for LDS (not for range), 'torch' with `fallback`.  'auto': as
+    'lds', but a shape refused for LDS goes to the general kernel where that takes it, before `fallback` is considered."""
+    if kernel == 'general':
+        return 'general'
+    v = _capi.shape_query(entry, spec, B, engine.ctx)
+    if v.lds:
+        if kernel == 'auto' and _capi.shape_query(entry + '_general', spec, B, engine.ctx).takes:
+            return 'general'
+        if fallback:
+            return 'torch'
+    v.check()
+    return 'lds'
 
 
 def _sens_workspace(engine, dev, spec: NetSpec, n, B):
@@ -177,29 +191,24 @@ def sensitivity(engine, weights, members, spec: NetSpec, states, fallback=True, 
             'auto': 'lds' where it runs, 'general' where 'lds' is refused for LDS (the rule of distil_kernel='auto').
     dense   the dense phases of the general kernel: 'valu' or 'mfma' (the f32 matrix cores; the same bits).  'mfma' with 'lds' is a
             ValueError: that kernel has no such phases."""
-    _check_sens_choice('sensitivity', kernel, dense)
+    check_choice('sensitivity', kernel, dense, 'serl_ga_sensitivity')
     dev = weights.device
     members = np.atleast_1d(np.asarray(members, dtype=np.int32))
     states = torch.as_tensor(states, dtype=torch.float32).to(dev).contiguous()
     n, B = states.shape[0], states.shape[1]
     assert n == len(members) and states.shape[2] == spec.state_dim
     G = genome_size(spec)
-    if B == 0:            # empty buffer: every gradient is zero -> scaling[scaling == 0] = 1
+    if B == 0 or n == 0:  # empty buffer: every gradient is zero -> scaling[scaling == 0] = 1; no members: nothing to ask or to launch
         return torch.ones(n, G, dtype=torch.float32, device=dev)
+    path = resolve(engine, spec, B, kernel, 'serl_ga_sensitivity', fallback)
+    if path == 'torch':
+        return sensitivity_torch(weights, members, spec, states)
     out = torch.empty(n, G, dtype=torch.float32, device=dev)
     m = _i32(dev, members)
-    if kernel != 'general':
-        rc = engine.lib.serl_ga_sensitivity(engine.ctx, weights.data_ptr(), weights.stride(0), *_net_args(spec), m.data_ptr(), n,
-                                            states.data_ptr(), B, out.data_ptr(), _stream(dev))
-        if rc == _capi.E_UNSUPPORTED and _kernel_shape_ok(spec):        # refused for LDS
-            if kernel == 'auto' and engine.lib.serl_ga_sensitivity_general_work_bytes(n, spec.state_dim, spec.action_dim, spec.hidden,
-                                                                                      spec.num_layers, B) > 0:
-                kernel = 'general'
-            elif fallback:
-                return sensitivity_torch(weights, members, spec, states)
-        if kernel != 'general':
-            _capi.check(rc, 'serl_ga_sensitivity')
-            return out
+    if path == 'lds':
+        _capi.check(engine.lib.serl_ga_sensitivity(engine.ctx, weights.data_ptr(), weights.stride(0), *_net_args(spec), m.data_ptr(), n,
+                                                   states.data_ptr(), B, out.data_ptr(), _stream(dev)), 'serl_ga_sensitivity')
+        return out
     work, nbytes = _sens_workspace(engine, dev, spec, n, B)
     _capi.check(engine.lib.serl_ga_sensitivity_general(engine.ctx, weights.data_ptr(), weights.stride(0), *_net_args(spec), m.data_ptr(), n,
                                                        states.data_ptr(), B, out.data_ptr(), work.data_ptr() if work is not None else None,
@@ -262,7 +271,7 @@ def proximal_mutate(engine, weights, member, spec: NetSpec, mag, buffer, batch_s
     sensitivity comes from serl_ga_sensitivity, delta from torch's generator, the update is serl_ga_scaled_perturb.
     `buffer` is a replay.DeviceReplay.  safe_mutate (:254-298) is the same operator fed from the critical buffer.  kernel / dense:
     sensitivity()'s, checked before any draw."""
-    _check_sens_choice('proximal_mutate', kernel, dense)
+    check_choice('proximal_mutate', kernel, dense, 'serl_ga_sensitivity')
     states = buffer.sample(min(int(batch_size), len(buffer)), rng)[0]
     scaling = sensitivity(engine, weights, [int(member)], spec, states[None], kernel=kernel, dense=dense)[0]
     delta = draw_delta(spec, mag) if delta is None else delta
@@ -278,7 +287,7 @@ class ProximalBatch:
     (one launch per batch size whichever kernel runs)."""
 
     def __init__(self, engine, weights, spec: NetSpec, mag, batch_size, rng=random, kernel='lds', dense='valu'):
-        _check_sens_choice('ProximalBatch', kernel, dense)
+        check_choice('ProximalBatch', kernel, dense, 'serl_ga_sensitivity')
         self.engine, self.weights, self.spec, self.mag, self.batch_size, self.rng = engine, weights, spec, mag, int(batch_size), rng
         self.kernel, self.dense = kernel, dense
         self.items = []
@@ -319,20 +328,6 @@ def safe_mutate(engine, weights, member, spec: NetSpec, mag, buffer, critical_bu
     return proximal_mutate(engine, weights, member, spec, mag, src, batch_size, rng, delta, kernel, dense)
 
 
-NOV_KERNELS = ('lds', 'general', 'auto')
-NOV_DENSE = ('valu', 'mfma')
-NOV_MAX_BATCH = 512         # BIG_B of serl_td3_core.inc: the largest minibatch of serl_ga_novelty_general
-
-
-def _check_nov_choice(who, kernel, dense):
-    if kernel not in NOV_KERNELS:
-        raise ValueError('%s: kernel must be one of %s, not %r' % (who, ', '.join(NOV_KERNELS), kernel))
-    if dense not in NOV_DENSE:
-        raise ValueError('%s: dense must be one of %s, not %r' % (who, ', '.join(NOV_DENSE), dense))
-    if kernel == 'lds' and dense != 'valu':
-        raise ValueError('%s: dense=%r needs kernel=\'general\' or \'auto\' (serl_ga_novelty has no matrix-core phases)' % (who, dense))
-
-
 def _check_members(who, weights, members):
     members = np.atleast_1d(np.asarray(members, dtype=np.int32))
     if members.size and (members.min() < 0 or members.max() >= weights.shape[0]):
@@ -369,37 +364,31 @@ def _novelty_general(engine, weights, members, spec: NetSpec, state_ptr, state_s
     return out          # (tab is freed to torch's allocator, which hands it out again only behind this launch on its stream)
 
 
-def _general_takes(spec: NetSpec, B):
-    """the shape rule of the general kernels (td3_shape_ok of serl_td3_core.inc, max batch 512)"""
-    return (4 <= spec.hidden <= 128 and spec.hidden % 4 == 0 and 0 <= spec.num_layers <= 4 and 1 <= spec.state_dim <= 16
-            and 1 <= spec.action_dim <= 4 and 1 <= B <= NOV_MAX_BATCH)
-
-
 def novelty(engine, weights, members, spec: NetSpec, states, actions, kernel='lds', dense='valu'):
     """Actor.get_novelty (genetic_agent.py:111-115) for n (actor, batch) pairs: states [n, B, S], actions [n, B, A]
     -> f32 [n] (device)
 
-    kernel  'lds' (default): serl_ga_novelty, one sample at a time, the shapes of check_net that fit the LDS.
+    kernel  'lds' (default): serl_ga_novelty, one sample at a time, the shapes of its contract (csrc/serl_shapes.h) that fit the LDS.
             'general': serl_ga_novelty_general, batch-parallel, for every shape the TD3 learner takes (hidden a multiple of 4 in 4 .. 128,
             0 .. 4 hidden layers, S <= 16, A <= 4, B <= 512); it is that kernel or a RuntimeError with the library's message, never
             another path.
             'auto': 'lds' where it runs, 'general' where 'lds' is refused for LDS and the general kernel takes the shape.
     dense   the dense phase of the general kernel: 'valu' or 'mfma' (the f32 matrix cores; the same bits).  'mfma' with 'lds' is a
             ValueError: that kernel has no such phase."""
-    _check_nov_choice('novelty', kernel, dense)
+    check_choice('novelty', kernel, dense, 'serl_ga_novelty')
     dev = weights.device
     members = np.atleast_1d(np.asarray(members, dtype=np.int32))
     states = torch.as_tensor(states, dtype=torch.float32).to(dev).contiguous()
     actions = torch.as_tensor(actions, dtype=torch.float32).to(dev).contiguous()
     n, B = states.shape[0], states.shape[1]
-    if kernel != 'general':
+    if n == 0 and B > 0:          # no evaluations: what every kernel returns for them, whatever the shape
+        return torch.empty(0, dtype=torch.float32, device=dev)
+    if resolve(engine, spec, B, kernel, 'serl_ga_novelty') == 'lds':
         out = torch.empty(n, dtype=torch.float32, device=dev)
         m = _i32(dev, members)
-        rc = engine.lib.serl_ga_novelty(engine.ctx, weights.data_ptr(), weights.stride(0), *_net_args(spec), m.data_ptr(), n,
-                                        states.data_ptr(), actions.data_ptr(), B, out.data_ptr(), _stream(dev))
-        if not (kernel == 'auto' and rc == _capi.E_UNSUPPORTED and _kernel_shape_ok(spec) and _general_takes(spec, B)):
-            _capi.check(rc, 'serl_ga_novelty')
-            return out
+        _capi.check(engine.lib.serl_ga_novelty(engine.ctx, weights.data_ptr(), weights.stride(0), *_net_args(spec), m.data_ptr(), n,
+                                               states.data_ptr(), actions.data_ptr(), B, out.data_ptr(), _stream(dev)), 'serl_ga_novelty')
+        return out
     members = _check_members('novelty', weights, members)
     assert n == len(members) and states.shape[2] == spec.state_dim and actions.shape == (n, B, spec.action_dim)
     S, A = spec.state_dim, spec.action_dim
@@ -467,13 +456,14 @@ def sort_groups_by_distance(engine, weights, genomes, buffers, spec: NetSpec, rn
             'auto': 'lds' where serl_ga_novelty takes the actor, 'general' where that is refused for LDS.
     dense   novelty()'s.  A pair with an empty buffer is a ValueError before the launch with 'general' (and with 'auto' where it
             resolves to it)."""
-    _check_nov_choice('sort_groups_by_distance', kernel, dense)
+    check_choice('sort_groups_by_distance', kernel, dense, 'serl_ga_novelty')
     plan = distance_plan(genomes, buffers, rng)
     pairs, members = plan['pairs'], plan['members']
     if not pairs:
         return []
-    if kernel == 'auto':
-        kernel = 'general' if (_kernel_shape_ok(spec) and not _novelty_lds_fits(spec) and _general_takes(spec, 1)) else 'lds'
+    if kernel == 'auto':          # (at batch 1: the general kernel where serl_ga_novelty is refused for LDS and it takes the actor, else 'lds' and its errors)
+        kernel = 'general' if (_capi.shape_query('serl_ga_novelty', spec, 1, engine.ctx).lds and
+                               _capi.shape_query('serl_ga_novelty_general', spec, 1, engine.ctx).takes) else 'lds'
     if kernel == 'general':
         nov = _distance_general(engine, weights, plan, spec, dense)
     else:
@@ -493,14 +483,6 @@ def sort_groups_by_distance(engine, weights, genomes, buffers, spec: NetSpec, rn
                                    torch.stack([ac[k] for k in idx])).cpu().numpy()
     groups = [(p[0], p[1], float(nov[2 * k]) + float(nov[2 * k + 1])) for k, p in enumerate(pairs)]   # two .item() floats added in f64
     return sorted(groups, key=lambda g: g[2], reverse=True)
-
-
-def _novelty_lds_fits(spec: NetSpec):
-    """whether serl_ga_novelty's forward buffers (serl_ga.hip FwdBuf) fit the 64 KB of LDS per workgroup every device has -- its only
-    refusal within _kernel_shape_ok.  They hold one sample, at most ~52 KB at hidden 256 x 16: today no shape is refused for LDS, and
-    'auto' is 'lds' on every shape serl_ga_novelty takes."""
-    S, H, L, A = spec.state_dim, spec.hidden, spec.num_layers, spec.action_dim
-    return 4 * (S + 2 * (L + 1) * H + L * H + L + 2 * A + 16) <= 64 * 1024
 
 
 def _distance_general(engine, weights, plan, spec: NetSpec, dense):

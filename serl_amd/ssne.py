@@ -132,9 +132,9 @@ class SSNE:
                  sensitivity_dense='valu', novelty_kernel='lds', novelty_dense='valu'):
         self.args, self.engine, self.spec, self.critic, self.record = args, engine, spec, critic, record
         self.distil_kernel, self.distil_dense = distil_kernel, distil_dense
-        ga._check_sens_choice('SSNE', sensitivity_kernel, sensitivity_dense)
+        ga.check_choice('SSNE', sensitivity_kernel, sensitivity_dense, 'serl_ga_sensitivity')
         self.sensitivity_kernel, self.sensitivity_dense = sensitivity_kernel, sensitivity_dense
-        ga._check_nov_choice('SSNE', novelty_kernel, novelty_dense)
+        ga.check_choice('SSNE', novelty_kernel, novelty_dense, 'serl_ga_novelty')
         self.novelty_kernel, self.novelty_dense = novelty_kernel, novelty_dense
         self.last_distil_path = None           # info['path'] of the last distil_batch
         self.population_size = args.pop_size

@@ -341,17 +341,19 @@ class CitationVecEnv:
     last_rollout_path = None
     ROLLOUT_PATHS = ('auto', 'fused', 'loop')
 
+    def _kernel_takes(self, entry, spec):
+        """whether the rollout entry point `entry` runs `spec` actors on this env: the library's own contract (serl_shape_query)"""
+        return _capi.shape_query(entry, spec, int(self.env_config) + 3 * bool(self.incremental)).takes
+
     def fused_rollout_ok(self, spec):
         """True when rollout() runs `spec` actors inside the kernel: the attitude task without rate control and the lane actor's
         shape (7 observations, hidden 32, 3 actions; any number of hidden layers and activation)."""
-        return (self.env_config == 0 and not self.incremental and
-                (spec.state_dim, spec.hidden, spec.action_dim) == (7, 32, 3) and spec.num_layers >= 0)
+        return self._kernel_takes('serl_venv_rollout', spec)
 
     def fused_general_ok(self, spec):
         """True when rollout(path='fused') can run `spec` actors inside the general kernel (serl_venv_rollout_general): every env
         configuration; an actor that fits this env, hidden a multiple of 4 in 4 .. 128, 0 .. 16 hidden layers, any activation."""
-        return ((spec.state_dim, spec.action_dim) == (self.state_dim, self.action_dim) and
-                spec.hidden % 4 == 0 and 4 <= spec.hidden <= 128 and 0 <= spec.num_layers <= 16)
+        return self._kernel_takes('serl_venv_rollout_general', spec)
 
     def fused_wave_ok(self, spec):
         """True when rollout(path='fused') on an env that steps on the wave kernels can run `spec` actors inside the wave rollout kernel
